@@ -6,6 +6,16 @@ Contract: `python bench.py --gpus N --steps K --warmup W`; for N>1 it is launche
 Rank 0 prints ONE JSON line.  Workload = BASELINE.json configs[1]: reference U-Net (smp Unet/resnet34
 topology), fp32, batch 32 per GPU, 512x512x3 synthetic tiles, losses GDICE+FOCAL, clip 0.5, Adam 3e-4.
 
+A plain run does only what the headline needs: set-up, `--warmup` steps, `--steps` timed steps, the outputs of the last
+timed step (`--dump-outputs DIR`), the JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`,
+...).  Everything else below — `roofline`, `whole_net`, the PCIe-inclusive rate, the bf16 and inference `legs`,
+`cpu_baseline` and the multi-rank evidence — runs only with `--full`.
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the last timed step handed its caller as DIR/<name>.npy
+(float32): training — the loss and its parts, the clipped gradient norm, the updated BatchNorm state, a fixed seeded
+sample of the updated parameters and of the gradient buffer; inference — the class map.  Inputs and parameters are
+seeded, so two builds run with the same arguments can be compared output for output.
+
 `roofline`: the dominant kernel (most GPU time among the convolution launches) timed live with HIP events on the launch
 stream.  `achieved` / `frac` are fractions of a ROOF, <= 1 by construction: for the Winograd F(2x2,3x3) kernels (every
 3x3 stride-1 layer with wide enough channels since round 2) `achieved` is the rate of the multiplies the kernel ISSUES on
@@ -32,6 +42,8 @@ FLOP_PER_TILE_TRAIN = 186.53e9      # SURVEY §8d / BASELINE.md §2 (conv FLOPs 
 BYTES_PER_TILE_TRAIN = 924.3e6      # (size/512)^2 for other tile sizes.  ideal-fused fp32 algorithmic HBM bytes
 PEAK_FP32_TFLOPS = 157.3
 PEAK_HBM_GBS = 8000.0
+DUMP_SAMPLE = 1 << 22               # --dump-outputs: elements kept of a larger output (fixed seeded sample, 16 MB fp32)
+DUMP_LIMIT = 64 << 20               # --dump-outputs: bytes in all
 
 
 def main():
@@ -46,13 +58,21 @@ def main():
                     help="replay the whole training step as one HIP graph (auto: single-GPU bf16, where the step "
                          "is shorter than the Python launch path; multi-GPU runs only with --graph on)")
     ap.add_argument("--cpu-steps", type=int, default=5)
-    ap.add_argument("--no-legs", action="store_true", help="skip the extra configs[2] (bf16, B=64) leg of the default run")
+    ap.add_argument("--no-legs", action="store_true", help="skip the extra configs[2] (bf16, B=64) leg of the --full run")
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32",
                     help="fp32 = BASELINE configs[1] (headline); bf16 = configs[2] (bf16 storage, fp32 accumulate)")
     ap.add_argument("--mode", choices=["train", "infer"], default="train",
                     help="train = BASELINE configs[1] (the headline metric); infer = tiled-inference forward "
                          "(uint8 tiles -> uint8 class maps, BASELINE configs[4] per-GPU leg)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / per-kernel table (two serial profiled "
+                         "steps), PCIe-inclusive rate, the bf16 B=64 and inference legs, the CPU baseline, multi-rank "
+                         "evidence")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` as typed: this process becomes a launcher — it starts the N ranks as a CHILD
@@ -99,7 +119,7 @@ def main():
     out = train_leg(args, ctx, args.precision, args.batch, headline=True)
     # configs[2] travels in the SAME JSON line as a leg (the headline stays configs[1]): bf16 storage / fp32 accumulate,
     # batch 64 per GPU, its own dominant-kernel roofline.  A failure of the leg must not cost the headline.
-    if args.precision == "fp32" and not args.no_legs:
+    if args.full and args.precision == "fp32" and not args.no_legs:
         try:
             leg = train_leg(args, ctx, "bf16", 64, headline=False)
             out["legs"] = {"bf16_b64": {k: leg[k] for k in ("value", "unit", "ms_per_step", "dtype", "config", "loss",
@@ -108,7 +128,7 @@ def main():
             out["legs"] = {"bf16_b64": {"error": f"{type(e).__name__}: {e}"}}
     # SURVEY 8d's secondary metric in the same line: forward-only tiles/s and km^2/h of the tiled inference path
     # (BASELINE configs[4]: 256x256 sub-tiles at batch 64, uint8 in / uint8 class map out; tiler-inclusive figure too)
-    if args.precision == "fp32" and not args.no_legs and world == 1:
+    if args.full and args.precision == "fp32" and not args.no_legs and world == 1:
         try:
             import copy
             from deadtrees_amd.network.unet import UNetHIP
@@ -124,7 +144,7 @@ def main():
             del im
         except Exception as e:  # noqa: BLE001
             out.setdefault("legs", {})["infer_fp32_256"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -267,6 +287,43 @@ def roofline_tables(prof, prof_steps, share_s):
     return by_name, table, issued_step, direct_step
 
 
+def _dump_array(t, seed: int):
+    """device tensor -> float32 numpy: whole if it has at most DUMP_SAMPLE elements, else DUMP_SAMPLE of them at fixed
+    flat indices drawn from `seed` (sorted; the same indices for every run of the same shape)"""
+    import torch
+    t = t.detach()
+    if t.numel() <= DUMP_SAMPLE:
+        return t.float().cpu().numpy()
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+    return t.reshape(-1)[idx.to(t.device)].float().cpu().numpy()
+
+
+def write_outputs(path: str, arrays: dict):
+    """--dump-outputs: name -> device tensor, written as path/<name>.npy (float32, DUMP_LIMIT bytes in all)"""
+    import numpy as np
+    host = {k: _dump_array(v, seed=0) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, f"{k}.npy"), a)
+
+
+def train_outputs(model, tr):
+    """what a caller of the training step holds after its last step: the loss and its parts (PART_KEYS order), the
+    clipped gradient norm, the updated parameters and BatchNorm state, the gradient buffer the step filled"""
+    import torch
+    from deadtrees_amd.loss.seg_loss import PART_KEYS
+    last = tr.last
+    return {"loss": last["loss"].reshape(1),
+            "loss_parts": torch.stack([last["parts"][k].reshape(()) for k in PART_KEYS]),
+            "grad_norm": last["grad_norm"].reshape(1),
+            "params_sample": model.flat_params, "grads_sample": model._grad_buffer(),
+            "bn_state": model.bn_state}
+
+
 def train_leg(args, ctx, precision, B, headline):
     """one timed training configuration -> result dict (the bench.py JSON contract keys + roofline block)"""
     import torch
@@ -326,6 +383,27 @@ def train_leg(args, ctx, precision, B, headline):
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     wall_rank = wall
     wall = float(dt)
+    if headline and rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, train_outputs(model, tr))
+    tiles = B * world * args.steps
+    value = tiles / wall
+    ms_per_step = 1e3 * wall / args.steps
+
+    out = {
+        "metric": f"{S}x{S} RGB tiles/sec (train fwd+bwd)", "value": round(value, 2), "unit": "tiles/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32" if precision == "fp32" else "bf16 (fp32 accumulate, fp32 master weights)", "data": "synthetic",
+        "config": {"workload": ("configs[1]" if precision == "fp32" else "configs[2]") +
+                               f": reference U-Net (smp Unet/resnet34 topology) {precision} train step, "
+                               f"batch {B}/GPU, {S}x{S}x3 tiles, GDICE+FOCAL, clip 0.5, Adam 3e-4",
+                   "global_batch": B * world, "tile": S, "parallelism": f"dp{world}"},
+        "loss": round(float(loss), 6), "hip_graph": use_graph,
+    }
+    if not args.full:
+        return out      # a plain run ends here (no further leg needs this one's memory)
+
+    # ---- --full only: two serial profiled steps, the PCIe leg, the rooflines, the N > 1 evidence
     serial_step_s = None
     # per-kernel events for the roofline block come from two EAGER, single-stream steps after the timed region (same
     # kernels, same shapes; the timed steps above were graph replays / had the weight gradients on a second stream)
@@ -374,10 +452,6 @@ def train_leg(args, ctx, precision, B, headline):
                 ev_free[k].record(main_s)
             torch.cuda.synchronize()
             pcie = B * n / (time.perf_counter() - t1)
-    tiles = B * world * args.steps
-    value = tiles / wall
-    ms_per_step = 1e3 * wall / args.steps
-
     # ---- roofline of the dominant conv kernel (rank 0's launches)
     prof_steps = 2
     share_s = serial_step_s            # the (serial) step the profiled launches belong to
@@ -427,29 +501,18 @@ def train_leg(args, ctx, precision, B, headline):
     step_wall_s = wall / args.steps
     peak_tf = PEAK_FP32_TFLOPS if precision == "fp32" else 2500.0   # dense bf16 MFMA peak
     bytes_per_tile = BYTES_PER_TILE_TRAIN if precision == "fp32" else 462.2e6
-    out = {
-        "metric": f"{S}x{S} RGB tiles/sec (train fwd+bwd)", "value": round(value, 2), "unit": "tiles/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32" if precision == "fp32" else "bf16 (fp32 accumulate, fp32 master weights)", "data": "synthetic",
-        "config": {"workload": ("configs[1]" if precision == "fp32" else "configs[2]") +
-                               f": reference U-Net (smp Unet/resnet34 topology) {precision} train step, "
-                               f"batch {B}/GPU, {S}x{S}x3 tiles, GDICE+FOCAL, clip 0.5, Adam 3e-4",
-                   "global_batch": B * world, "tile": S, "parallelism": f"dp{world}"},
-        "loss": round(float(loss), 6), "hip_graph": use_graph,
-        "pcie_inclusive_tiles_per_s": None if pcie is None else round(pcie, 2),
-        # whole step: the multiplies all convolution kernels ISSUE per step (profiled launches: Winograd layers count 16/36
-        # of their algorithmic FLOPs) / the timed step = the fraction of the matrix peak the step really uses; the
-        # direct-convolution-equivalent rate (SURVEY 8d's 186.53 GFLOP per tile) beside it is NOT a roofline fraction
-        "whole_net": {"mfma_issued_TFLOPs": round(issued_step / step_wall_s / 1e12, 2),
-                      "mfma_issued_frac": round(issued_step / step_wall_s / 1e12 / peak_tf, 4),
-                      "direct_equiv_TFLOPs": round(per_gpu_tiles_s * FLOP_PER_TILE_TRAIN / 1e12, 2),
-                      "direct_equiv_over_mfma_peak": round(per_gpu_tiles_s * FLOP_PER_TILE_TRAIN / 1e12 / peak_tf, 4),
-                      "profiled_conv_flops_per_step_over_model": round(direct_step / (B * (S / 512.0) ** 2 * FLOP_PER_TILE_TRAIN), 4),
-                      "hbm_frac_step": round(per_gpu_tiles_s * bytes_per_tile / 1e9 / PEAK_HBM_GBS, 4),
-                      "conv_fwd_dgrad_share_of_step": round((conv_time / prof_steps) / share_s, 4)},
-        "roofline": roof,
-    }
+    out["pcie_inclusive_tiles_per_s"] = None if pcie is None else round(pcie, 2)
+    # whole step: the multiplies all convolution kernels ISSUE per step (profiled launches: Winograd layers count 16/36
+    # of their algorithmic FLOPs) / the timed step = the fraction of the matrix peak the step really uses; the
+    # direct-convolution-equivalent rate (SURVEY 8d's 186.53 GFLOP per tile) beside it is NOT a roofline fraction
+    out["whole_net"] = {"mfma_issued_TFLOPs": round(issued_step / step_wall_s / 1e12, 2),
+                        "mfma_issued_frac": round(issued_step / step_wall_s / 1e12 / peak_tf, 4),
+                        "direct_equiv_TFLOPs": round(per_gpu_tiles_s * FLOP_PER_TILE_TRAIN / 1e12, 2),
+                        "direct_equiv_over_mfma_peak": round(per_gpu_tiles_s * FLOP_PER_TILE_TRAIN / 1e12 / peak_tf, 4),
+                        "profiled_conv_flops_per_step_over_model": round(direct_step / (B * (S / 512.0) ** 2 * FLOP_PER_TILE_TRAIN), 4),
+                        "hbm_frac_step": round(per_gpu_tiles_s * bytes_per_tile / 1e9 / PEAK_HBM_GBS, 4),
+                        "conv_fwd_dgrad_share_of_step": round((conv_time / prof_steps) / share_s, 4)}
+    out["roofline"] = roof
     if distributed:
         # N > 1 evidence: the collective really spans `world` ranks (an all-reduce of ones must return N), the spread of
         # the per-rank step times, and the gradient bytes each rank hands to the bucketed all-reduce per step
@@ -513,9 +576,11 @@ def infer_bench(args, model, dev, world, rank, distributed, as_leg=False):
     if distributed:
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     wall = float(dt)
+    if not as_leg and rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, {"classes": out})
     # roofline of the forward pass: per-launch events of two more (eager, single-stream) batches
     roof = None
-    if not use_graph and rank == 0:
+    if args.full and not use_graph and rank == 0:
         prof = []
         step()
         torch.cuda.synchronize()
@@ -561,7 +626,7 @@ def infer_bench(args, model, dev, world, rank, distributed, as_leg=False):
     # PCIe-inclusive rate (never `value`): uint8 tiles from pinned host memory, uint8 class maps back, double-buffered
     # on a copy stream so transfers overlap the previous batch's kernels
     pcie = None
-    if rank == 0:
+    if args.full and rank == 0:
         host_in = [u8.cpu().pin_memory() for _ in range(2)]
         host_out = [torch.empty((B, S, S), dtype=torch.uint8).pin_memory() for _ in range(2)]
         dev_in = [torch.empty_like(u8) for _ in range(2)]
@@ -590,7 +655,7 @@ def infer_bench(args, model, dev, world, rank, distributed, as_leg=False):
     # device -> uint8 D2H -> block merge.  Host work (split / merge, pageable copies) included; rank r takes ortho
     # tiles r, r + N, ... of the queue (no collective)
     tiler = None
-    if S in (256, 512):
+    if args.full and S in (256, 512):
         import numpy as np
         from deadtrees_amd.deployment.tiler import infer_tile
 
@@ -642,6 +707,9 @@ def infer_bench(args, model, dev, world, rank, distributed, as_leg=False):
            "tiler_inclusive": tiler,
            "foreground_pixels": int(out.sum()), "hip_graph": use_graph,
            "pcie_inclusive_tiles_per_s_per_gpu": None if pcie is None else round(pcie, 1)}
+    if not args.full:        # a plain run measured none of these
+        for k in ("roofline", "tiler_inclusive", "pcie_inclusive_tiles_per_s_per_gpu"):
+            del res[k]
     if as_leg:
         return res
     if rank == 0:

@@ -25,12 +25,12 @@ Pinning status:
     arithmetic) is now pinned by execution — ``oracle/make_golden_resunet.py`` loads the
     reference's in-tree twin of smp's decoder block (network/extra/resunet/decoder.py,
     extra/modules.py; they import nothing that is absent) by file path and writes
-    ``tests/golden/resunet_decoder.npz``; the resnet34 ENCODER stays unpinned.
+    ``tests/golden/resunet_decoder.part*.npz``; the resnet34 ENCODER stays unpinned.
   * ResUnet decoder (``resunet_ref.py``): pinned the same way (outputs, input gradients and
     parameter gradients of the reference's own ``ResUnetDecoder``).
   * Unet++ decoder (``unetpp_ref.py``): dense wiring pinned by executing the reference's
     ``extra/efficientunetplusplus/decoder.py`` (smp's UnetPlusPlusDecoder constructor / forward loop) with smp's plain
-    decoder block (``oracle/make_golden_unetpp.py`` -> ``tests/golden/unetpp_decoder.npz``).
+    decoder block (``oracle/make_golden_unetpp.py`` -> ``tests/golden/unetpp_decoder.part*.npz``).
   * bf16 training oracle (``unet_bf16_ref.py``): the fp32 restatement with bf16 roundings at
     the HIP path's storage points; ``dtype=float32`` reproduces the fp32 oracle exactly.
 """

@@ -1,4 +1,4 @@
-"""Generate tests/golden/resunet_decoder.npz by EXECUTING the reference's in-tree ResUnet decoder (build container).
+"""Generate tests/golden/resunet_decoder.part*.npz by EXECUTING the reference's in-tree ResUnet decoder (build container).
 
 TEST INFRASTRUCTURE.  Usage (where /root/reference exists):   python -m oracle.make_golden_resunet
 
@@ -20,8 +20,10 @@ import types
 import numpy as np
 import torch
 
+from oracle.golden import save_npz_parts
+
 REF = "/root/reference/deadtrees/network/extra"
-OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "resunet_decoder.npz")
+OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "resunet_decoder")   # .part*.npz
 ENC_CH = (3, 16, 16, 32, 64, 128)
 DEC_CH = (64, 32, 16, 16, 8)
 
@@ -81,8 +83,8 @@ def main():
     data["out_plain"] = dec2(*[f.detach() for f in feats]).detach().numpy()
     dec2.eval()
     data["out_plain_eval"] = dec2(*[f.detach() for f in feats]).detach().numpy()
-    np.savez_compressed(OUT, **data)
-    print("wrote", OUT, os.path.getsize(OUT), "bytes")
+    for path in save_npz_parts(OUT, data):
+        print("wrote", path, os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":

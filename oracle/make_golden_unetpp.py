@@ -1,4 +1,4 @@
-"""Generate tests/golden/unetpp_decoder.npz by EXECUTING the reference's in-tree dense (Unet++) decoder wiring.
+"""Generate tests/golden/unetpp_decoder.part*.npz by EXECUTING the reference's in-tree dense (Unet++) decoder wiring.
 
 TEST INFRASTRUCTURE.  Usage (where /root/reference exists):   python -m oracle.make_golden_unetpp
 
@@ -20,8 +20,10 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from oracle.golden import save_npz_parts
+
 REF = "/root/reference/deadtrees/network/extra"
-OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "unetpp_decoder.npz")
+OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "unetpp_decoder")   # .part*.npz
 ENC_CH = (3, 16, 16, 32, 64, 128)
 DEC_CH = (64, 32, 16, 16, 8)
 
@@ -87,8 +89,8 @@ def main():
     for k, v in dec.state_dict().items():
         if "running" in k:
             data[f"after:{k}"] = v.numpy()
-    np.savez_compressed(OUT, **data)
-    print("wrote", OUT, os.path.getsize(OUT), "bytes;", len(sd0), "state tensors;", sorted({k.split('.')[1] for k in sd0}))
+    paths = save_npz_parts(OUT, data)
+    print("wrote", paths, sum(os.path.getsize(p) for p in paths), "bytes;", len(sd0), "state tensors;", sorted({k.split('.')[1] for k in sd0}))
 
 
 if __name__ == "__main__":

@@ -3,7 +3,7 @@
 TEST INFRASTRUCTURE (see oracle/__init__.py).  PINNED: ``oracle/make_golden_resunet.py`` loads the reference's own
 ``deadtrees/network/extra/modules.py`` and ``extra/resunet/decoder.py`` by file path (they need only torch), runs
 ``ResUnetDecoder`` on seeded feature pyramids and stores inputs / outputs / gradients in
-``tests/golden/resunet_decoder.npz``; ``tests/test_oracle_golden.py`` checks this restatement against them.  The
+``tests/golden/resunet_decoder.part*.npz``; ``tests/test_oracle_golden.py`` checks this restatement against them.  The
 same fixture run with the 1x1 ``identity_conv`` zeroed pins the plain U-Net decoder wiring of ``unet_ref.py``
 (feature order, nearest x2, ``cat([x, skip])``, channel arithmetic) by execution rather than by reading.
 

@@ -6,7 +6,7 @@ decoder.py:102-184`` is smp's ``UnetPlusPlusDecoder`` with another block type (s
 arithmetic :133-153 and dense forward loop :156-184).  ``oracle/make_golden_unetpp.py`` EXECUTES that class (loaded by
 file path) with its block type swapped for smp's plain decoder block — nearest x2, ``cat([x, skip])``, two
 ``Conv2dReLU`` from the reference's ``extra/modules.py`` — and stores inputs / outputs / gradients in
-``tests/golden/unetpp_decoder.npz``; ``tests/test_oracle_golden.py`` checks this restatement against them.  So the dense
+``tests/golden/unetpp_decoder.part*.npz``; ``tests/test_oracle_golden.py`` checks this restatement against them.  So the dense
 wiring and channel arithmetic are PINNED by execution of the reference; the block internals are the plain decoder block
 pinned in ``resunet_ref.py``'s fixture; the ResNet-34 encoder and the head (3x3 + bias, smp ``SegmentationHead``
 default) stay PARITY UNPINNED like ``unet_ref.py``.

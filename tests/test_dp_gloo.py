@@ -239,7 +239,7 @@ def test_bench_gpus_2_runs_as_typed():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["DT_DIST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                        "--batch", "2", "--size", "64", "--no-cpu-baseline", "--no-legs"],
+                        "--batch", "2", "--size", "64", "--full", "--no-cpu-baseline", "--no-legs"],
                        env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

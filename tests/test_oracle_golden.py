@@ -104,17 +104,18 @@ def test_unet_ref_shapes_and_keys():
 
 
 def test_resunet_decoder_oracle_against_the_executed_reference(golden_dir):
-    """oracle/resunet_ref.ResUnetDecoderRef against tests/golden/resunet_decoder.npz (the reference's own
+    """oracle/resunet_ref.ResUnetDecoderRef against tests/golden/resunet_decoder.part*.npz (the reference's own
     ResUnetDecoder, executed by oracle/make_golden_resunet.py): output, every parameter gradient, every feature
     gradient, BatchNorm running statistics — and, with the identity convolutions zeroed, the PLAIN U-Net decoder of
     oracle/unet_ref.py, which pins its wiring (feature order, nearest x2, cat([x, skip]), channel arithmetic)."""
     import torch
+    from oracle.golden import load_npz_parts
     from oracle.resunet_ref import ResUnetDecoderRef
     from oracle.unet_ref import UnetDecoder
-    z = np.load(os.path.join(golden_dir, "resunet_decoder.npz"))
+    z = load_npz_parts(os.path.join(golden_dir, "resunet_decoder"))
     enc_ch, dec_ch = tuple(int(v) for v in z["enc_ch"]), tuple(int(v) for v in z["dec_ch"])
     dec = ResUnetDecoderRef(enc_ch, dec_ch)
-    sd = {k[3:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("sd:")}
+    sd = {k[3:]: torch.from_numpy(z[k]) for k in z if k.startswith("sd:")}
     assert set(sd) == set(dec.state_dict())                  # same parameter / buffer names as the reference module
     dec.load_state_dict(sd)
     dec.train()
@@ -146,16 +147,17 @@ def test_resunet_decoder_oracle_against_the_executed_reference(golden_dir):
 
 
 def test_unetplusplus_decoder_oracle_against_the_executed_reference_wiring(golden_dir):
-    """oracle/unetpp_ref.UnetPlusPlusDecoderRef against tests/golden/unetpp_decoder.npz: the reference's own dense decoder
+    """oracle/unetpp_ref.UnetPlusPlusDecoderRef against tests/golden/unetpp_decoder.part*.npz: the reference's own dense decoder
     class (network/extra/efficientunetplusplus/decoder.py — smp's UnetPlusPlusDecoder constructor and forward loop),
     executed by oracle/make_golden_unetpp.py with smp's plain decoder block: same state_dict names (x_{depth}_{layer}),
     output, every parameter and feature gradient, BatchNorm running statistics."""
     import torch
+    from oracle.golden import load_npz_parts
     from oracle.unetpp_ref import UnetPlusPlusDecoderRef
-    z = np.load(os.path.join(golden_dir, "unetpp_decoder.npz"))
+    z = load_npz_parts(os.path.join(golden_dir, "unetpp_decoder"))
     enc_ch, dec_ch = tuple(int(v) for v in z["enc_ch"]), tuple(int(v) for v in z["dec_ch"])
     dec = UnetPlusPlusDecoderRef(enc_ch, dec_ch)
-    sd = {k[3:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("sd:")}
+    sd = {k[3:]: torch.from_numpy(z[k]) for k in z if k.startswith("sd:")}
     assert set(sd) == set(dec.state_dict()) and len(dec.blocks) == 11
     dec.load_state_dict(sd)
     dec.train()

@@ -1,6 +1,6 @@
 """architecture "resunet" (the reference's in-tree ResUnet, deadtrees/network/segmodel.py:66-67 ->
 network/extra/resunet/{model,decoder}.py) on the HIP kernels, against oracle/resunet_ref.py — whose decoder is pinned
-by the executed reference (tests/golden/resunet_decoder.npz, tests/test_oracle_golden.py)."""
+by the executed reference (tests/golden/resunet_decoder.part*.npz, tests/test_oracle_golden.py)."""
 import copy
 
 import numpy as np

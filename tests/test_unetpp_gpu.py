@@ -1,6 +1,6 @@
 """architecture "unet++" / "unetplusplus" (smp.UnetPlusPlus, reference deadtrees/network/segmodel.py:64-65) on the HIP
 kernels, against oracle/unetpp_ref.py — whose dense decoder wiring is pinned by executing the reference's in-tree
-efficientunetplusplus/decoder.py (tests/golden/unetpp_decoder.npz, tests/test_oracle_golden.py)."""
+efficientunetplusplus/decoder.py (tests/golden/unetpp_decoder.part*.npz, tests/test_oracle_golden.py)."""
 import copy
 
 import numpy as np
