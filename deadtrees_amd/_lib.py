@@ -62,6 +62,8 @@ SIGNATURES = {
     "dt_conv2d_winograd_upsampled_dgrad_supported": (C.c_int, [_P]),
     "dt_conv2d_winograd_upsampled_dgrad_rows": (C.c_int, [_P]),
     "dt_conv2d_winograd_upsampled_dgrad": (C.c_int, [_P, c_f, c_f, c_f, c_f, c_f, C.POINTER(BnBwdFuse), C.c_int, c_f]),
+    "dt_conv2d_winograd_upsampled_dgrad_x_rows": (C.c_int, [_P]),
+    "dt_conv2d_winograd_upsampled_dgrad_x": (C.c_int, [_P, c_f, c_f, c_f, c_f, C.POINTER(BnBwdFuse), c_f]),
     "dt_conv2d_wgrad_workspace": (SZ, [_P]),
     "dt_conv2d_wgrad": (C.c_int, [_P, c_f, c_f, c_f, c_f, c_f, SZ, c_f, c_f, c_f]),
     "dt_conv2d_wgrad_winograd_supported": (C.c_int, [_P]),
@@ -163,6 +165,9 @@ SIGNATURES = {
     "dt_skip_from_loss": (C.c_int, [c_f, c_f, c_f]),
     "dt_adam_advance": (C.c_int, [c_f, c_f, c_f, F64, F64, c_f, c_f]),
     "dt_adam_step_dev": (C.c_int, [c_f, c_f, c_f, c_f, I64, c_f, F64, F64, F32, c_f, c_f, c_f]),
+    "dt_sumsq_ranges": (C.c_int, [c_f, c_f, C.c_int, C.c_int, c_f, c_f]),
+    "dt_adam_advance_ranges": (C.c_int, [c_f, c_f, C.c_int, c_f, c_f, F64, F64, c_f, c_f]),
+    "dt_adam_step_ranges": (C.c_int, [c_f, c_f, c_f, c_f, c_f, C.c_int, I64, c_f, F64, F64, F32, c_f, c_f, c_f]),
 }
 
 _lib = None

@@ -815,8 +815,8 @@ static int wn_updgrad_ok(const dt_conv_desc* d) {
 
 // one partial row per workgroup where every tile of a workgroup has the same channel block (32 % blocks == 0), else one per
 // spatial tile
-static int wn_updgrad_rows(const dt_conv_desc* d, int* pstats) {
-  const int nt = d->Cout / 64, sp = d->B * dt_cdiv(d->Ho, 16) * dt_cdiv(d->Wo, 16);
+static int wn_updgrad_rows(const dt_conv_desc* d, int* pstats, bool x_only = false) {
+  const int nt = (x_only ? d->cout_split : d->Cout) / 64, sp = d->B * dt_cdiv(d->Ho, 16) * dt_cdiv(d->Wo, 16);
   const long total = (long)sp * nt;
   *pstats = (32 % nt) == 0;
   return *pstats ? (int)(total < WN_MAX_WGS ? total : WN_MAX_WGS) : sp;
@@ -830,13 +830,13 @@ extern "C" int dt_conv2d_winograd_upsampled_dgrad_rows(const dt_conv_desc* d) {
   return wn_updgrad_rows(d, &ps);
 }
 
-extern "C" int dt_conv2d_winograd_upsampled_dgrad(const dt_conv_desc* d, const float* dy, const float* u, float* gx,
-                                                  float* dskip, float* red, const dt_bn_bwd_fuse* fuse, int launches,
-                                                  void* stream) {   // launches: reserved (one launch covers both parts)
+// x_only: only the up-sampled part's channel blocks [0, cout_split) (frozen encoder: the skip's gradient is not needed)
+static int wn_updgrad_launch(const dt_conv_desc* d, const float* dy, const float* u, float* gx, float* dskip, float* red,
+                             const dt_bn_bwd_fuse* fuse, bool x_only, void* stream) {
   DT_REQUIRE(d && dy && u && gx && red && fuse && fuse->y && fuse->mean && fuse->invstd && fuse->act_scale &&
                  fuse->act_shift && fuse->act == nullptr, "conv_winograd_upsampled_dgrad: null pointer / stored activation");
   DT_REQUIRE(wn_updgrad_ok(d), "conv_winograd_upsampled_dgrad: layer shape not supported");
-  DT_REQUIRE(d->cout_split == d->Cout || dskip, "conv_winograd_upsampled_dgrad: dskip missing");
+  DT_REQUIRE(x_only || d->cout_split == d->Cout || dskip, "conv_winograd_upsampled_dgrad: dskip missing");
   WinoArgs a;
   a.bnb = *fuse;
   a.src0 = dy; a.src1 = nullptr; a.u = u; a.in_scale = nullptr; a.in_shift = nullptr;
@@ -860,14 +860,35 @@ extern "C" int dt_conv2d_winograd_upsampled_dgrad(const dt_conv_desc* d, const f
   // ONE launch over all channel blocks: the tiles of the up-sampled part (blocks below cout_split / 64) take epilogue form
   // 6 (2x2 sums + BatchNorm-backward sums at half resolution), the skip's tiles the plain store into dskip
   // (two launches over the two parts measured time-neutral against the unfused chain: 806.0 vs 807.2 tiles/s)
-  (void)launches;
-  a.nt0 = 0; a.n_tiles = d->Cout / 64; a.stat_ld = d->cout_split;
-  a.P = wn_updgrad_rows(d, &a.pstats);
+  // x_only: the grid covers the up-sampled part's blocks only (all tiles take form 6; out1 is never addressed)
+  if (x_only) { a.out1 = nullptr; a.obytes1 = 0; }
+  a.nt0 = 0; a.n_tiles = (x_only ? d->cout_split : d->Cout) / 64; a.stat_ld = d->cout_split;
+  a.P = wn_updgrad_rows(d, &a.pstats, x_only);
   const int total = sp_tiles * a.n_tiles;
   hipLaunchKernelGGL((conv3x3_wino_kernel<false, 6, false>), dim3((unsigned)(total < WN_MAX_WGS ? total : WN_MAX_WGS)),
                      dim3(256), 0, st, a, total);
   DT_LAUNCH_CHECK();
   return DT_OK;
+}
+
+extern "C" int dt_conv2d_winograd_upsampled_dgrad(const dt_conv_desc* d, const float* dy, const float* u, float* gx,
+                                                  float* dskip, float* red, const dt_bn_bwd_fuse* fuse, int launches,
+                                                  void* stream) {   // launches: reserved (one launch covers both parts)
+  (void)launches;
+  return wn_updgrad_launch(d, dy, u, gx, dskip, red, fuse, false, stream);
+}
+
+// the same data gradient restricted to the up-sampled input channels [0, cout_split): no skip gradient is computed or
+// written (decoder blocks 1-3 with a frozen encoder).  P = dt_conv2d_winograd_upsampled_dgrad_x_rows(d).
+extern "C" int dt_conv2d_winograd_upsampled_dgrad_x_rows(const dt_conv_desc* d) {
+  if (d == nullptr || !wn_updgrad_ok(d)) return 0;
+  int ps;
+  return wn_updgrad_rows(d, &ps, true);
+}
+
+extern "C" int dt_conv2d_winograd_upsampled_dgrad_x(const dt_conv_desc* d, const float* dy, const float* u, float* gx,
+                                                    float* red, const dt_bn_bwd_fuse* fuse, void* stream) {
+  return wn_updgrad_launch(d, dy, u, gx, nullptr, red, fuse, true, stream);
 }
 
 // data gradient with the BatchNorm-backward sums of the layer the gradient belongs to fused into the epilogue: the

@@ -204,3 +204,137 @@ extern "C" int dt_adam_step_dev(float* p, const float* g, float* m, float* v, in
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
+
+// ---- clip + Adam over the TRAINABLE ranges of the flat buffer (frozen encoder: torch.optim.Adam skips a parameter
+// whose .grad is None — its m, v and step count do not move — and clip_grad_norm_ sees only parameters with a gradient).
+// Range table (device, int64 [4 * nranges]): (lo, hi, first partial row, segment).  lo / hi are multiples of 4 (the
+// flat layout aligns every tensor to 4 floats); `segment` indexes the per-segment step counts t_seg[] and the bias
+// corrections hyper_seg[3 * segment ..]: every range carries its own count, so a range that was frozen for k steps
+// starts its first update with the step-1 bias correction.  Frozen ranges are neither read nor written.
+
+__device__ __forceinline__ int rg_find(const int64_t* __restrict__ table, int nranges, int64_t row) {
+  int r = 0;
+  while (r + 1 < nranges && table[4 * (r + 1) + 2] <= row) ++r;
+  return r;
+}
+
+__global__ __launch_bounds__(256) void sumsq_ranges_kernel(const float* __restrict__ g, const int64_t* __restrict__ table,
+                                                           int nranges, double* __restrict__ partial) {
+  const int r = rg_find(table, nranges, blockIdx.x);
+  const int64_t lo = table[4 * r], hi = table[4 * r + 1];
+  const int64_t base = lo + ((int64_t)blockIdx.x - table[4 * r + 2]) * SUMSQ_PER_WG;
+  float s = 0.f;
+  for (int it = 0; it < 16; ++it) {
+    const int64_t i = base + ((int64_t)it * 256 + threadIdx.x) * 4;
+    if (i + 3 < hi) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
+      s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+    } else {
+      for (int64_t j = i; j < hi && j < i + 4; ++j) s += g[j] * g[j];
+    }
+  }
+  __shared__ double sh[4];
+  const double w = wave_sum_d((double)s);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+extern "C" int dt_sumsq_ranges(const float* g, const int64_t* table, int nranges, int rows, double* partial,
+                               void* stream) {
+  DT_REQUIRE(g && table && partial && nranges > 0 && rows > 0, "sumsq_ranges: bad args");
+  DT_REQUIRE((((uintptr_t)g) & 15) == 0, "sumsq_ranges: g must be 16-byte aligned");
+  hipLaunchKernelGGL(sumsq_ranges_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, g, table, nranges,
+                     partial);
+  DT_LAUNCH_CHECK();
+  return DT_OK;
+}
+
+__global__ void adam_advance_ranges_kernel(double* __restrict__ t_seg, const int64_t* __restrict__ table, int nranges,
+                                           const int32_t* __restrict__ skip, const double* __restrict__ lr, double b1,
+                                           double b2, float* __restrict__ hyper_seg) {
+  const int r = threadIdx.x;
+  if (r >= nranges) return;
+  const int s = (int)table[4 * r + 3];
+  double tt = t_seg[s];
+  if (!(skip && skip[0] != 0)) tt += 1.0;
+  t_seg[s] = tt;
+  const double te = tt < 1.0 ? 1.0 : tt;
+  hyper_seg[3 * s + 0] = (float)lr[0];
+  hyper_seg[3 * s + 1] = (float)(1.0 - pow(b1, te));
+  hyper_seg[3 * s + 2] = (float)(1.0 - pow(b2, te));
+}
+
+extern "C" int dt_adam_advance_ranges(double* t_seg, const int64_t* table, int nranges, const int32_t* skip_flag,
+                                      const double* lr_dev, double beta1, double beta2, float* hyper_seg, void* stream) {
+  DT_REQUIRE(t_seg && table && lr_dev && hyper_seg && nranges > 0 && nranges <= 64, "adam_advance_ranges: bad args");
+  hipLaunchKernelGGL(adam_advance_ranges_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t_seg, table, nranges,
+                     skip_flag, lr_dev, beta1, beta2, hyper_seg);
+  DT_LAUNCH_CHECK();
+  return DT_OK;
+}
+
+// grid (x: element blocks of the longest range, y: range); the body is adam_kernel's arithmetic
+__global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v,
+                                                          const int64_t* __restrict__ table, float b2, float omb1,
+                                                          float omb2, float eps, const float* __restrict__ clipcoef,
+                                                          const int32_t* __restrict__ skip,
+                                                          const float* __restrict__ hyper_seg) {
+  if (skip && skip[0] != 0) return;
+  const int r = blockIdx.y;
+  const int64_t lo = table[4 * r], hi = table[4 * r + 1];
+  const int s = (int)table[4 * r + 3];
+  const float cc = clipcoef ? clipcoef[0] : 1.f;
+  const float step = hyper_seg[3 * s] / hyper_seg[3 * s + 1];
+  const float rs2 = 1.f / sqrtf(hyper_seg[3 * s + 2]);
+  const int64_t n4 = (hi - lo) >> 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  f32x4* p4 = reinterpret_cast<f32x4*>(p + lo);
+  f32x4* m4 = reinterpret_cast<f32x4*>(m + lo);
+  f32x4* v4 = reinterpret_cast<f32x4*>(v + lo);
+  const f32x4* g4 = reinterpret_cast<const f32x4*>(g + lo);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const f32x4 gg = g4[i] * cc;
+    f32x4 mm = m4[i];
+    f32x4 vv = v4[i];
+    f32x4 pp = p4[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      mm[k] = mm[k] + (gg[k] - mm[k]) * omb1;
+      vv[k] = vv[k] * b2 + omb2 * gg[k] * gg[k];
+      const float denom = sqrtf(vv[k]) * rs2 + eps;
+      pp[k] = pp[k] - step * (mm[k] / denom);
+    }
+    m4[i] = mm;
+    v4[i] = vv;
+    p4[i] = pp;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    for (int64_t i = lo + (n4 << 2); i < hi; ++i) {
+      const float gk = g[i] * cc;
+      const float mk = m[i] + (gk - m[i]) * omb1;
+      const float vk = v[i] * b2 + omb2 * gk * gk;
+      m[i] = mk;
+      v[i] = vk;
+      p[i] = p[i] - step * (mk / (sqrtf(vk) * rs2 + eps));
+    }
+  }
+}
+
+extern "C" int dt_adam_step_ranges(float* p, const float* g, float* m, float* v, const int64_t* table, int nranges,
+                                   int64_t max_len, const float* hyper_seg, double beta1, double beta2, float eps,
+                                   const float* clipcoef, const int32_t* skip_flag, void* stream) {
+  DT_REQUIRE(p && g && m && v && table && hyper_seg && nranges > 0 && nranges <= 65535 && max_len > 0,
+             "adam_ranges: bad args");
+  DT_REQUIRE(((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0,
+             "adam_ranges: buffers must be 16-byte aligned");
+  int64_t grid = ((max_len >> 2) + 255) / 256;
+  if (grid > 256 * 16 / nranges) grid = 256 * 16 / nranges;
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(adam_ranges_kernel, dim3((unsigned)grid, (unsigned)nranges), dim3(256), 0, (hipStream_t)stream, p, g,
+                     m, v, table, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, clipcoef, skip_flag,
+                     hyper_seg);
+  DT_LAUNCH_CHECK();
+  return DT_OK;
+}

@@ -68,6 +68,13 @@ class UNetEngine:
         self.overlap_wgrad = os.environ.get("DT_OVERLAP_WGRAD", "1" if os.environ.get("DT_FP32_WINOGRAD", "1") != "0" else "0") != "0"
         self.overlap_wgrad_bf16 = bool(os.environ.get("DT_OVERLAP_WGRAD_BF16"))
         self._bwd_training = True
+        self._bwd_enc_training = True
+        # encoder = stem + layers 1-4: the first convolutions of the spec, the contiguous range [0, encoder_hi) of the flat
+        # buffer (the head+decoder bucket starts there)
+        self._enc_index = {c.index for c in spec.convs if c.key.startswith("encoder.")}
+        self.encoder_hi = spec.buckets[0][1]
+        # per backward: the convolutions whose data gradient / weight gradient were launched (tests, timing labels)
+        self.launches = {"dgrad": [], "wgrad": []}
         # BatchNorm-backward reduction of a block-output layer inside the fp32 gradient-JOIN epilogue: measured slower
         # than the separate pass (526 vs 530 tiles/s, same box: 48 extra loads per lane in the read-modify-write
         # epilogue); the bf16 path keeps it (its join epilogue is LDS-staged, +0.5 %).  Kernel support stays tested.
@@ -381,9 +388,13 @@ class UNetEngine:
 
     # ------------------------------------------------------------------ forward
     def forward(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor, training: bool,
-                save: bool, want_argmax: Optional[str] = None, nhwc: bool = False):
+                save: bool, want_argmax: Optional[str] = None, nhwc: bool = False, enc_training: Optional[bool] = None,
+                enc_frozen: bool = False):
         """nhwc=True: the input already is the kernels' layout [B,H,W,C] (the tiled-inference gather produces it):
-        no NCHW -> NHWC pass"""
+        no NCHW -> NHWC pass.  enc_training: BatchNorm mode of the encoder (stem + layers 1-4; default: `training`) —
+        False with training=True is fine-tuning on the encoder's running statistics.  enc_frozen: the encoder's weights
+        get no gradient: nothing of the encoder is saved for backward, and an encoder in eval mode runs the fused
+        inference form."""
         sp = self.spec
         if nhwc:
             if x_nchw.dim() != 4 or x_nchw.shape[3] != sp.in_channels:
@@ -402,18 +413,26 @@ class UNetEngine:
         st = _stream()
         lib = self.lib
         sv = _Saved() if save else None
+        dec_training = training
+        enc_training = training if enc_training is None else bool(enc_training)
+        enc_save = save and not enc_frozen
         self._u_all = self._wino_fwd_weights(params)
         bnws = self._buf("bnws", 4 * sp.n_bn_channels, device=dev)
         # repeated inference calls (tiled prediction): the 46 eval-mode scale/shift launches are skipped while neither the
         # parameters nor the running statistics changed (torch's version counters + the epochs of the raw device writes)
-        if training:
+        if training or enc_training:
             self._bn_epoch += 1
-        akey = None if (training or save) else (params.data_ptr(), params._version, self._weights_epoch, bnstate.data_ptr(),
+        akey = None if (training or enc_training or save) else (params.data_ptr(), params._version, self._weights_epoch, bnstate.data_ptr(),
                                                 bnstate._version, self._bn_epoch, bnws.data_ptr())
         self._affine_fresh = akey is not None and self._ws.get("affine_key") == akey
         self._ws["affine_key"] = akey
         self._fuse_eval = (self._fuse_eval_opt and not training and not save and self.winograd
                            and sp.decoder_kind not in ("resunet", "unetplusplus"))
+        dec_fuse_eval = self._fuse_eval
+        # a frozen encoder in eval mode: its layers take the fused inference form (nothing of it is saved)
+        if enc_frozen and not enc_training and self._fuse_eval_opt and self.winograd and sp.decoder_kind == "unet":
+            self._fuse_eval = True
+        training = enc_training
         if save:
             # mean/invstd are needed by backward: keep a private copy target per forward
             bnws = torch.empty(4 * sp.n_bn_channels, dtype=torch.float32, device=dev)
@@ -429,18 +448,22 @@ class UNetEngine:
             if save:
                 sv.d[key] = kw
 
+        def keep_enc(key, **kw):
+            if enc_save:
+                sv.d[key] = kw
+
         # ---- stem
         if self._fuse_eval:     # inference: BatchNorm + ReLU in the stem kernel's epilogue, no raw output
             f1, h, w_ = self._conv_affine_direct(sp.stem, params, bnstate, bnws, x, None, 0, B, H, W)
         else:
-            y, h, w_, ss = self._conv_bn(sp.stem, params, bnstate, bnws, x, None, 0, B, H, W, training, save_stats=save)
+            y, h, w_, ss = self._conv_bn(sp.stem, params, bnstate, bnws, x, None, 0, B, H, W, training, save_stats=enc_save)
             f1 = self._bn_act(y, ss)
-            keep("stem", x=x, y=y, z=f1, Hin=H, Win=W)
+            keep_enc("stem", x=x, y=y, z=f1, Hin=H, Win=W)
         hp, wp = (h + 2 - 3) // 2 + 1, (w_ + 2 - 3) // 2 + 1
         pool = torch.empty((B, hp, wp, 64), dtype=torch.float32, device=dev)
-        amax = torch.empty((B, hp, wp, 64), dtype=torch.uint8, device=dev) if save else None
+        amax = torch.empty((B, hp, wp, 64), dtype=torch.uint8, device=dev) if enc_save else None
         _lib.check(lib.dt_maxpool3x3s2(_p(f1), _p(pool), _p(amax), B, h, w_, 64, st), "dt_maxpool3x3s2")
-        keep("pool", amax=amax, H=h, W=w_)
+        keep_enc("pool", amax=amax, H=h, W=w_)
 
         feats = [f1]
         cur, ch, cw = pool, hp, wp
@@ -464,23 +487,24 @@ class UNetEngine:
                         cur, ch, cw = out, h1, w1
                         continue
                 y1, h1, w1, ss1 = self._conv_bn(blk.conv1, params, bnstate, bnws, xin, None, 0, B, ch, cw, training,
-                                                        save_stats=save)
+                                                        save_stats=enc_save)
                 # z1 = relu(bn1(y1)) is virtual: conv2 applies it while staging y1 (A/B switch DT_MATERIALIZE_Z1:
                 # a stored activation instead, read by the plain convolution / weight-gradient kernels)
                 z1 = self._bn_act(y1, ss1) if self._mat_z1 else None
                 y2, h2, w2, ss2 = self._conv_bn(blk.conv2, params, bnstate, bnws, y1 if z1 is None else z1, None, 0, B,
-                                                h1, w1, training, in_ss=ss1 if z1 is None else None, save_stats=save)
+                                                h1, w1, training, in_ss=ss1 if z1 is None else None, save_stats=enc_save)
                 if blk.down is not None:
                     yd, _, _, ssd = self._conv_bn(blk.down, params, bnstate, bnws, xin, None, 0, B, ch, cw, training,
-                                                  save_stats=save)
+                                                  save_stats=enc_save)
                     out = self._bn_act(y2, ss2, res=yd, res_ss=ssd)
                 else:
                     yd = None
                     out = self._bn_act(y2, ss2, res=xin)
-                keep(f"L{li}B{bi}", x=xin, y1=y1, z1=z1, y2=y2, yd=yd, out=out, Hin=ch, Win=cw, H=h2, W=w2)
+                keep_enc(f"L{li}B{bi}", x=xin, y1=y1, z1=z1, y2=y2, yd=yd, out=out, Hin=ch, Win=cw, H=h2, W=w2)
                 cur, ch, cw = out, h2, w2
             feats.append(cur)
         # feats = [f1, f2, f3, f4, f5]
+        training, self._fuse_eval = dec_training, dec_fuse_eval
         if sp.decoder_kind == "unetplusplus":
             d, dh, dw = self._forward_unetpp(feats, params, bnstate, bnws, B, training, save, keep)
             dec_blocks = []
@@ -559,6 +583,8 @@ class UNetEngine:
         if save:
             sv.d["B"] = B
             sv.d["training"] = bool(training)
+            sv.d["enc_training"] = bool(enc_training)
+            sv.d["enc_frozen"] = bool(enc_frozen)
             self.saved = sv
         return logits, (am64 if am64 is not None else am8)
 
@@ -913,10 +939,18 @@ class UNetEngine:
         return logits, (am64 if am64 is not None else am8)
 
     # ------------------------------------------------------------------ bf16 training (BASELINE configs[2])
-    def forward_bf16_train(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor):
+    def forward_bf16_train(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor,
+                           enc_training: bool = True, enc_frozen: bool = False):
         """training-mode forward with bf16 activations / weights, fp32 accumulation, fp32 BatchNorm statistics
-        (taken from the accumulators), fp32 master parameters.  Stem and head run in fp32."""
+        (taken from the accumulators), fp32 master parameters.  Stem and head run in fp32.
+        enc_frozen: the encoder's weights get no gradient — nothing of it is saved; enc_training=False (only with a
+        frozen encoder here: the bf16 path has no frozen-statistics BatchNorm backward) normalises the encoder with its
+        running statistics, which stay untouched."""
         sp, lib = self.spec, self.lib
+        if not enc_training and not enc_frozen:
+            raise NotImplementedError("bf16: an encoder in eval mode trains only with frozen weights "
+                                      "(model.encoder.requires_grad_(False)); use fp32 for trainable weights on "
+                                      "running statistics")
         B, Cin, H, W = x_nchw.shape
         if H % 32 or W % 32 or Cin != sp.in_channels:
             raise RuntimeError(f"bad input {tuple(x_nchw.shape)}")
@@ -932,6 +966,16 @@ class UNetEngine:
         nb = sp.n_bn_channels
 
         def finalize(c, stats, P, count):
+            if not enc_training and c.index in self._enc_index:
+                # eval-mode encoder: running statistics (the batch sums of the convolution are not used)
+                rm = bnstate[2 * c.bn_off:2 * c.bn_off + c.cout]
+                rv = bnstate[2 * c.bn_off + c.cout:2 * c.bn_off + 2 * c.cout]
+                _lib.check(lib.dt_bn_eval_affine(_p(params[c.g_off:c.g_off + c.cout]), _p(params[c.b_off:c.b_off + c.cout]),
+                                                 _p(rm), _p(rv), BN_EPS, c.cout,
+                                                 _p(bnws[2 * nb + c.bn_off:2 * nb + c.bn_off + c.cout]),
+                                                 _p(bnws[3 * nb + c.bn_off:3 * nb + c.bn_off + c.cout]), st),
+                           "dt_bn_eval_affine")
+                return self._ss(c, bnws)
             _lib.check(lib.dt_bn_finalize(_p(stats), P, c.cout, float(count), _p(params[c.g_off:c.g_off + c.cout]),
                                           _p(params[c.b_off:c.b_off + c.cout]), BN_EPS, BN_MOMENTUM,
                                           _p(bnstate[2 * c.bn_off:2 * c.bn_off + c.cout]),
@@ -976,13 +1020,15 @@ class UNetEngine:
         Pst, sstats = self._stem_bf16(x, params, ystem, True, B, H, W, Cin)
         ss = finalize(stc, sstats, Pst, B * h * w_)
         f1 = bn_act(ystem, ss)
-        sv.d["stem"] = dict(x=x, y=ystem, z=f1, Hin=H, Win=W, s2d=self._stem_s2d)
+        if not enc_frozen:
+            sv.d["stem"] = dict(x=x, y=ystem, z=f1, Hin=H, Win=W, s2d=self._stem_s2d)
         self._stem_s2d = None
         hp, wp = (h + 2 - 3) // 2 + 1, (w_ + 2 - 3) // 2 + 1
         pool = torch.empty((B, hp, wp, 64), dtype=bf, device=dev)
         amax = torch.empty((B, hp, wp, 64), dtype=torch.uint8, device=dev)
         _lib.check(lib.dt_maxpool3x3s2_bf16_amax(_p(f1), _p(pool), _p(amax), B, h, w_, 64, st), "dt_maxpool3x3s2_bf16_amax")
-        sv.d["pool"] = dict(amax=amax, H=h, W=w_)
+        if not enc_frozen:
+            sv.d["pool"] = dict(amax=amax, H=h, W=w_)
         self._tr("pool", pool)
         feats = [f1]
         cur, ch, cw = pool, hp, wp
@@ -998,7 +1044,8 @@ class UNetEngine:
                 else:
                     yd = None
                     out = bn_act(y2, ss2, res=xin)
-                sv.d[f"L{li}B{bi}"] = dict(x=xin, y1=y1, z1=z1, y2=y2, yd=yd, out=out, Hin=ch, Win=cw, H=h2, W=w2)
+                if not enc_frozen:
+                    sv.d[f"L{li}B{bi}"] = dict(x=xin, y1=y1, z1=z1, y2=y2, yd=yd, out=out, Hin=ch, Win=cw, H=h2, W=w2)
                 cur, ch, cw = out, h2, w2
             feats.append(cur)
         d, dh, dw, d_ss = feats[4], ch, cw, None
@@ -1054,6 +1101,7 @@ class UNetEngine:
         sv.d["head"] = dict(x=d, H=dh, W=dw)
         sv.d["B"] = B
         sv.d["bf16"] = True
+        sv.d["enc_frozen"] = bool(enc_frozen)
         self.saved = sv
         return logits
 
@@ -1066,6 +1114,8 @@ class UNetEngine:
             raise RuntimeError("backward called without a saved forward (was another forward run in between?)")
         S = sv.d
         B, bnws = S["B"], S["bnws"]
+        frozen = bool(S.get("enc_frozen", False))
+        self.launches = {"dgrad": [], "wgrad": []}
         dev, st, bf = dlogits.device, _stream(), torch.bfloat16
         wbd = self._bf16_weights(params, dgrad=True)
         wbdc = self._bf16_weights(params, dgrad=True, chunked=True)
@@ -1098,6 +1148,8 @@ class UNetEngine:
             return dy
 
         def wgrad(c, src0, src1, mode0, Hin, Win, dy, in_ss=None, side=True):
+            if side:
+                self.launches["wgrad"].append(c.key)
             if side and self.overlap_wgrad_bf16:
                 self._on_side(lambda: wgrad(c, src0, src1, mode0, Hin, Win, dy, in_ss, side=False), src0, src1, dy)
                 return
@@ -1122,6 +1174,7 @@ class UNetEngine:
             """stride-1 data gradient of conv c with the BatchNorm-backward reduction of bn_conv fused (fp32 twin:
             _dgrad_bn; act = stored block output -> gradient join) -> (red, P)"""
             Cq = bn_conv.cout
+            self.launches["dgrad"].append(c.key)
             desc = self._desc(B, Hh, Ww, c.cout, 0, 0, Hh, Ww, c.cin, c.k, 1, c.k - 1 - c.pad, 0, 0 if act is None else 1)
             P = lib.dt_conv2d_bf16_stat_rows(C.byref(desc))
             red = self._buf("bn_red_fused", lib.dt_bn_stats_floats(P, Cq), device=dev)
@@ -1142,6 +1195,7 @@ class UNetEngine:
             return red, P
 
         def dgrad(c, dy, Hin, Win, out0, out1=None, split=0, acc=False):
+            self.launches["dgrad"].append(c.key)
             Ho, Wo = dy.shape[1], dy.shape[2]
             pad = c.k - 1 - c.pad
             if c.stride == 1:
@@ -1302,12 +1356,17 @@ class UNetEngine:
             x_ss = self._ss(sp.decoder[i - 1].conv2, bnws) if d["x_virtual"] else None
             wgrad(blk.conv1, d["x"], d["skip"], 1, Hh, Ww, dy1, in_ss=x_ss)
             cx = blk.in_ch
+            if frozen and i == 0:      # block 0's input and skip are encoder features: no data gradient at all
+                del dy1
+                S[f"D{i}"] = None
+                continue
             if d["skip"] is None and i >= 1:
                 # dec4.conv1: data gradient, the 2x2 sums of the up-sampling's backward and the BatchNorm-backward sums of
                 # the block below in one launch of the narrow kernel — no full-resolution gradient tensor
                 c1 = blk.conv1
                 ddesc = self._desc(B, Hh, Ww, c1.cout, 0, 0, Hh, Ww, c1.cin, c1.k, 1, c1.k - 1 - c1.pad, 0, 0)
                 if lib.dt_conv2d_bf16_upsampled_dgrad_supported(C.byref(ddesc)):
+                    self.launches["dgrad"].append(c1.key)
                     pb = sp.decoder[i - 1].conv2
                     y2p = S[f"D{i - 1}"]["y2"]
                     P = lib.dt_conv2d_bf16_stat_rows(C.byref(ddesc))
@@ -1330,9 +1389,10 @@ class UNetEngine:
                     continue
             dup = torch.empty((B, Hh, Ww, cx), dtype=bf, device=dev)
             if d["skip"] is not None:
+                # (frozen encoder: the split kernel still writes the skip's part, to a tensor nobody reads)
                 dskip = torch.empty(d["skip"].shape, dtype=bf, device=dev)
                 dgrad(blk.conv1, dy1, Hh, Ww, dup, dskip, split=cx)
-                skip_grads[3 - i] = dskip
+                skip_grads[3 - i] = None if frozen else dskip
                 self._tr(f"D{i}.dskip", dskip)
             else:
                 dgrad(blk.conv1, dy1, Hh, Ww, dup)
@@ -1358,6 +1418,10 @@ class UNetEngine:
             self._tr(f"D{i}.g", g)
             S[f"D{i}"] = None
         self._bucket_done(sp.buckets[0])
+        if frozen:      # frozen encoder weights: backward stops at the decoder (no encoder data / weight gradient)
+            self._join_side()
+            self.saved = None
+            return
 
         for li in (3, 2, 1, 0):
             blocks = sp.layers[li]
@@ -1434,6 +1498,7 @@ class UNetEngine:
         dy = bn_bwd(sp.stem, gf1, None, stem["y"], virtual_act=True, reduced=stem_red)
         self._tr("stem.dy", dy)
         stc = sp.stem
+        self.launches["wgrad"].append(stc.key)
         if stem.get("s2d") is not None:
             # space-to-depth form on the bf16 MFMA kernels: dW over 16 taps x 16 channels, gathered back to 7x7
             cin = stem["x"].shape[-1]
@@ -1486,7 +1551,8 @@ class UNetEngine:
         dy = torch.empty_like(y)
         e0 = self._pb()
         # eval-mode (frozen) BatchNorm: y*scale+shift with constant statistics -> dy = g*gamma*invstd, no mean terms
-        fn = self.lib.dt_bn_bwd_apply if self._bwd_training else self.lib.dt_bn_bwd_apply_frozen
+        batch_stats = self._bwd_enc_training if c.index in self._enc_index else self._bwd_training
+        fn = self.lib.dt_bn_bwd_apply if batch_stats else self.lib.dt_bn_bwd_apply_frozen
         _lib.check(fn(_p(dout), _p(out_act), _p(y), _p(mean), _p(invstd), _p(gamma), _p(asc),
                       _p(ash), _p(red), P,
                       _p(grads[c.g_off:c.g_off + Cc]), _p(grads[c.b_off:c.b_off + Cc]),
@@ -1497,6 +1563,8 @@ class UNetEngine:
         return dy
 
     def _wgrad(self, c: ConvSpec, grads, src0, src1, mode0, B, Hin, Win, dy, in_ss=None, side=True):
+        if side:
+            self.launches["wgrad"].append(c.key)
         if side and self.overlap_wgrad:
             self._on_side(lambda: self._wgrad(c, grads, src0, src1, mode0, B, Hin, Win, dy, in_ss, side=False),
                           src0, src1, dy)
@@ -1537,6 +1605,7 @@ class UNetEngine:
         sums are taken over the joined tensor."""
         Cc = bn_conv.cout
         assert c.stride == 1 and c.cin == Cc and tuple(y.shape) == tuple(out0.shape)
+        self.launches["dgrad"].append(c.key)
         wd = self._wd_all[c.w_off:c.w_off + c.w_size]
         desc = self._desc(B, H, W, c.cout, 0, 0, H, W, c.cin, c.k, 1, c.k - 1 - c.pad, 0, 0 if act is None else 1)
         ud = self._u(c, dgrad=True)
@@ -1577,6 +1646,7 @@ class UNetEngine:
         desc = self._desc(B, Hh, Ww, cx, 0, 1, Hh, Ww, c.cout, c.k, c.stride, c.pad, 0, 0)
         if not self.lib.dt_conv2d_upsampled_dgrad_supported(C.byref(desc)):
             return False
+        self.launches["dgrad"].append(c.key)
         lib = self.lib
         P = lib.dt_conv2d_upsampled_dgrad_rows(C.byref(desc))
         red = self._buf("bn_red_up", lib.dt_bn_stats_floats(P, cx), device=dy1.device)
@@ -1595,6 +1665,7 @@ class UNetEngine:
 
     def _dgrad(self, c: ConvSpec, params, dy, B, Hin, Win, out0, out1=None, split=0, acc=False):
         """gradient wrt the conv's logical input [B,Hin,Win,cin] (before virtual upsample handling)."""
+        self.launches["dgrad"].append(c.key)
         Ho, Wo = dy.shape[1], dy.shape[2]
         wd = self._wd_all[c.w_off:c.w_off + c.w_size]     # flipped / transposed image, built at the start of backward
         pad = c.k - 1 - c.pad
@@ -1715,6 +1786,9 @@ class UNetEngine:
             raise RuntimeError("backward called without a saved forward (was another forward run in between?)")
         S = sv.d
         self._bwd_training = bool(S.get("training", True))
+        self._bwd_enc_training = bool(S.get("enc_training", self._bwd_training))
+        frozen = bool(S.get("enc_frozen", False))
+        self.launches = {"dgrad": [], "wgrad": []}
         B = S["B"]
         bnws = S["bnws"]
         dev = dlogits.device
@@ -1777,6 +1851,10 @@ class UNetEngine:
             x_ss = self._ss(sp.decoder[i - 1].conv2, bnws) if d["x_virtual"] else None
             self._wgrad(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1, in_ss=x_ss)
             cx = blk.in_ch
+            if frozen and i == 0:      # block 0's input and skip are encoder features: no data gradient at all
+                del dy1
+                S[f"D{i}"] = None
+                continue
             if d["skip"] is None and i >= 1 and self._fuse_bn and self._upsampled_dgrad(blk, sp.decoder[i - 1].conv2, params,
                                                                                        bnws, dy1, S[f"D{i - 1}"]["y2"], d, B, Hh, Ww):
                 g, g_red = d["g"], d["g_red"]
@@ -1789,7 +1867,30 @@ class UNetEngine:
                 c1 = blk.conv1
                 ddesc = self._desc(B, Hh, Ww, c1.cout, 0, 0, Hh, Ww, c1.cin, c1.k, 1, c1.k - 1 - c1.pad, cx, 0)
                 ud = self._u(c1, dgrad=True)
+                if frozen and ud is not None and lib.dt_conv2d_winograd_upsampled_dgrad_supported(C.byref(ddesc)):
+                    # frozen encoder: only the up-sampled channels [0, cx) — the skip's gradient is neither computed nor
+                    # written
+                    self.launches["dgrad"].append(c1.key)
+                    pb = sp.decoder[i - 1].conv2
+                    y2p = S[f"D{i - 1}"]["y2"]
+                    P = lib.dt_conv2d_winograd_upsampled_dgrad_x_rows(C.byref(ddesc))
+                    red = self._buf("bn_red_up", lib.dt_bn_stats_floats(P, cx), device=dev)
+                    psc, psh = self._ss(pb, bnws)
+                    nbq = sp.n_bn_channels
+                    fuse = _lib.BnBwdFuse(_p(y2p), _p(bnws[pb.bn_off: pb.bn_off + cx]),
+                                          _p(bnws[nbq + pb.bn_off: nbq + pb.bn_off + cx]), _p(psc), _p(psh))
+                    g = torch.empty_like(d["x"])
+                    ev = self._pb()
+                    _lib.check(lib.dt_conv2d_winograd_upsampled_dgrad_x(C.byref(ddesc), _p(dy1), _p(ud), _p(g), _p(red),
+                                                                        C.byref(fuse), st), "dt_conv2d_winograd_upsampled_dgrad_x")
+                    self._pe(ev, self._wino_kernel_name(False, 6) + " (x only)", 2.0 * 9 * cx * c1.cout * Hh * Ww * B,
+                             4.0 * B * Hh * Ww * c1.cout + 4.0 * B * (Hh // 2) * (Ww // 2) * cx * 2)
+                    g_red = (red, P)
+                    del dy1
+                    S[f"D{i}"] = None
+                    continue
                 if ud is not None and lib.dt_conv2d_winograd_upsampled_dgrad_supported(C.byref(ddesc)):
+                    self.launches["dgrad"].append(c1.key)
                     pb = sp.decoder[i - 1].conv2
                     y2p = S[f"D{i - 1}"]["y2"]
                     P = lib.dt_conv2d_winograd_upsampled_dgrad_rows(C.byref(ddesc))
@@ -1812,9 +1913,10 @@ class UNetEngine:
                     continue
             dup = torch.empty((B, Hh, Ww, cx), dtype=torch.float32, device=dev)
             if d["skip"] is not None:
+                # (frozen encoder without the Winograd form: the split kernel writes the skip's part to a scratch tensor)
                 dskip = torch.empty_like(d["skip"])
                 self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup, dskip, split=cx)
-                skip_grads[3 - i] = dskip
+                skip_grads[3 - i] = None if frozen else dskip
             else:
                 self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup)
             del dy1
@@ -1839,6 +1941,10 @@ class UNetEngine:
             del dup
             S[f"D{i}"] = None
         self._bucket_done(sp.buckets[0])
+        if frozen:      # frozen encoder weights: backward stops at the decoder (no encoder data / weight gradient)
+            self._join_side()
+            self.saved = None
+            return
 
         # g = gradient wrt f5 ; encoder layers in reverse
         for li in (3, 2, 1, 0):
@@ -1927,10 +2033,12 @@ class _UNetFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, flat, module):
         eng = module.engine
+        enc_tr, frozen = module._encoder_training(), module.encoder_frozen
         if module.precision == "bf16" and module.training:
-            logits = eng.forward_bf16_train(x, flat.detach(), module.bn_state)
+            logits = eng.forward_bf16_train(x, flat.detach(), module.bn_state, enc_training=enc_tr, enc_frozen=frozen)
         else:
-            logits, _ = eng.forward(x, flat.detach(), module.bn_state, module.training, save=True)
+            logits, _ = eng.forward(x, flat.detach(), module.bn_state, module.training, save=True, enc_training=enc_tr,
+                                    enc_frozen=frozen)
         # the activations belong to THIS autograd node, not to the engine: another grad-enabled forward (a validation
         # step, a second loss term) between this forward and its backward must not replace them
         ctx.saved_acts, eng.saved = eng.saved, None
@@ -1949,8 +2057,93 @@ class _UNetFunction(torch.autograd.Function):
             m.engine.backward_bf16(dlogits, m.flat_params.detach(), grads, saved=sv)
         else:
             m.engine.backward(dlogits, m.flat_params.detach(), grads, saved=sv)
+        if sv.d.get("enc_frozen"):
+            grads[:m.encoder_hi].zero_()     # never written by a frozen backward: no stale gradient reaches .grad
         # a trainer that consumes the flat buffer directly (HipTrainer) opts out of autograd's copy into .grad
         return None, (grads if m.deliver_grad_to_autograd else None), None
+
+
+IMAGENET_FILE = "resnet34-333f7ec4.pth"     # torchvision's resnet34 weights = smp's resnet34 "imagenet" encoder
+
+
+def patch_first_conv(w: torch.Tensor, in_channels: int) -> torch.Tensor:
+    """smp ``patch_first_conv`` (encoders/_utils.py, smp >= 0.2.1; restated from its published source, unpinned): a
+    3-channel pretrained first conv [O,3,k,k] for `in_channels` inputs — C = 1: the sum over the 3 channels; otherwise
+    input channel i takes pretrained channel i % 3 and the whole weight is scaled by 3 / C."""
+    if in_channels == w.shape[1]:
+        return w
+    if in_channels == 1:
+        return w.sum(1, keepdim=True)
+    out = torch.empty((w.shape[0], in_channels) + tuple(w.shape[2:]), dtype=w.dtype)
+    for i in range(in_channels):
+        out[:, i] = w[:, i % w.shape[1]]
+    return out * (w.shape[1] / in_channels)
+
+
+class EncoderView(nn.Module):
+    """``model.encoder``: the resnet34 encoder (stem + layers 1-4) of a ``UNetHIP`` as a parameter-free child module.
+
+    Its tensors live in the owner's flat buffer, so it adds no parameters and no state_dict keys to the model.
+    ``train()`` / ``eval()`` set the encoder's BatchNorm mode (the owner's ``train()`` / ``eval()`` recurse into it, as
+    torch does); ``requires_grad_(flag)`` freezes / unfreezes the encoder's weights as a whole (the contiguous range
+    [0, encoder_hi) of the flat buffer; per-tensor ``requires_grad`` is not supported); ``state_dict()`` /
+    ``load_state_dict()`` use smp's encoder key names (``smp_model.encoder``: no ``encoder.`` prefix; torchvision's
+    ``fc.*`` is ignored on load)."""
+
+    def __init__(self, owner: "UNetHIP"):
+        super().__init__()
+        object.__setattr__(self, "_owner_ref", owner)     # not a child module: no recursion, no parameters
+
+    def __setattr__(self, name, value):
+        # the reference's MultiStage assigns `m.requires_grad_ = False` to every encoder module: an attribute assignment
+        # that changes nothing there — a no-op here too (it must not shadow the method)
+        if name == "requires_grad_":
+            return
+        super().__setattr__(name, value)
+
+    def requires_grad_(self, requires_grad: bool = True):
+        self._owner_ref.encoder_frozen = not requires_grad
+        return self
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        pass        # the owner's state_dict already holds the encoder's tensors under "encoder.*"
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        pass
+
+    def state_dict(self, *args, destination=None, prefix: str = "", keep_vars: bool = False):
+        if destination is not None:     # the owner's state_dict recursing: its "encoder.*" keys are already there
+            return destination
+        sd = self._owner_ref.smp_state_dict()
+        out = {}
+        for k, v in sd.items():
+            if k.startswith("encoder."):
+                out[prefix + k[len("encoder."):]] = v
+        return out
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        """torchvision resnet34 / smp encoder keys (an ``encoder.`` prefix is accepted too); ``fc.*`` ignored.  Every
+        encoder tensor must be present with its shape (``num_batches_tracked`` excepted: old torchvision files lack it)."""
+        owner = self._owner_ref
+        sub = {(k[len("encoder."):] if k.startswith("encoder.") else k): v for k, v in state_dict.items()}
+        sub = {k: v for k, v in sub.items() if not k.startswith("fc.")}
+        full = owner.smp_state_dict()
+        enc_keys = [k[len("encoder."):] for k in full if k.startswith("encoder.")]
+        missing = [k for k in enc_keys if k not in sub and not k.endswith("num_batches_tracked")]
+        unexpected = [k for k in sub if k not in set(enc_keys)]
+        if missing:
+            raise RuntimeError(f"encoder state_dict: missing keys {missing[:8]}{'...' if len(missing) > 8 else ''}")
+        if strict and unexpected:
+            raise RuntimeError(f"encoder state_dict: unexpected keys {unexpected[:8]}")
+        for k in enc_keys:
+            if k in sub:
+                t = torch.as_tensor(sub[k])
+                if tuple(t.shape) != tuple(full["encoder." + k].shape):
+                    raise RuntimeError(f"size mismatch for encoder.{k}: {tuple(t.shape)} vs "
+                                       f"{tuple(full['encoder.' + k].shape)}")
+                full["encoder." + k] = t
+        owner.load_smp_state_dict(full)
+        return nn.modules.module._IncompatibleKeys([], unexpected)
 
 
 class UNetHIP(nn.Module):
@@ -1970,8 +2163,6 @@ class UNetHIP(nn.Module):
             raise NotImplementedError(f"encoder {encoder_name!r}: only resnet34 has HIP kernels")
         if encoder_depth != 5 or tuple(decoder_channels) != (256, 128, 64, 32, 16):
             raise NotImplementedError("only encoder_depth=5 / decoder_channels=(256,128,64,32,16)")
-        if encoder_weights is not None:
-            raise NotImplementedError("pretrained encoder weights need a network fetch; load a state_dict instead")
         self.spec = build_spec(in_channels, classes, decoder)
         self.flat_params = nn.Parameter(torch.zeros(self.spec.n_params, dtype=torch.float32))
         self.register_buffer("bn_state", torch.zeros(2 * self.spec.n_bn_channels, dtype=torch.float32),
@@ -1984,7 +2175,74 @@ class UNetHIP(nn.Module):
         # "fp32" (BASELINE configs[1]) or "bf16": bf16 activations/weights, fp32 accumulation, fp32 master
         # parameters and optimiser (configs[2]; the AMP setting of the reference's protocol.md:27)
         self.precision = "fp32"
+        # model.encoder: the encoder's BatchNorm mode (train / eval) and weight freeze (requires_grad_); adds no parameters
+        self.encoder = EncoderView(self)
+        self.encoder_frozen = False
+        self.encoder_hi = self.spec.buckets[0][1]          # encoder = flat buffer range [0, encoder_hi)
+        self._n_enc_convs = sum(c.key.startswith("encoder.") for c in self.spec.convs)
+        self.encoder_weights = encoder_weights
         self.reset_parameters()
+        if encoder_weights is not None:
+            self.init_decoder_smp()
+            self.load_encoder_weights(encoder_weights)
+
+    # ------------------------------------------------------------------ pretrained encoder
+    @staticmethod
+    def imagenet_path() -> str:
+        """where ``encoder_weights="imagenet"`` is read from: torch's hub cache (never downloaded here)"""
+        return os.path.join(torch.hub.get_dir(), "checkpoints", IMAGENET_FILE)
+
+    @torch.no_grad()
+    def load_encoder_weights(self, weights):
+        """"imagenet" -> the torchvision resnet34 file in the hub cache; any other string -> a path to a torchvision- or
+        smp-encoder-style state_dict; a dict -> that state_dict.  The first conv is patched as smp does for
+        in_channels != 3 (``patch_first_conv``)."""
+        if isinstance(weights, str):
+            path = self.imagenet_path() if weights == "imagenet" else weights
+            if not os.path.isfile(path):
+                raise FileNotFoundError(f"encoder weights {weights!r}: no file at {path} (nothing is downloaded; place "
+                                        f"torchvision's {IMAGENET_FILE} there or pass a state_dict path)")
+            sd = torch.load(path, map_location="cpu", weights_only=True)
+        else:
+            sd = weights
+        sd = {(k[len("encoder."):] if k.startswith("encoder.") else k): v for k, v in sd.items()}
+        if "conv1.weight" in sd:
+            sd["conv1.weight"] = patch_first_conv(torch.as_tensor(sd["conv1.weight"]).float(), self.spec.in_channels)
+        self.encoder.load_state_dict(sd, strict=False)
+
+    @torch.no_grad()
+    def init_decoder_smp(self):
+        """smp's initialisation of decoder and head (what the reference keeps when ``encoder_weights`` is set,
+        segmodel.py:87-89): decoder convs kaiming_uniform_(fan_in, relu) with zero bias, BatchNorm 1 / 0, head
+        xavier_uniform_ with zero bias.  Draws from torch's global generator."""
+        sd = self.smp_state_dict()
+        for c in self.spec.convs:
+            if c.key.startswith("encoder."):
+                continue
+            k = c.state_k
+            shape = (c.cout, c.cin, k, k)
+            w = torch.empty(shape)
+            if c is self.spec.head:
+                nn.init.xavier_uniform_(w)
+            else:
+                nn.init.kaiming_uniform_(w, mode="fan_in", nonlinearity="relu")
+            sd[c.key] = w
+            if c.bn_key is None:
+                sd[c.key.replace(".weight", ".bias")] = torch.zeros(c.cout)
+            else:
+                sd[f"{c.bn_key}.weight"] = torch.ones(c.cout)
+                sd[f"{c.bn_key}.bias"] = torch.zeros(c.cout)
+        self.load_smp_state_dict(sd)
+
+    def _encoder_training(self) -> bool:
+        """BatchNorm mode of the encoder for the next forward"""
+        return bool(self.training and self.encoder.training)
+
+    def trainable_ranges(self):
+        """[(lo, hi)] of the flat buffer that receive gradients and updates; None = all of it"""
+        if not self.encoder_frozen:
+            return None
+        return [(self.encoder_hi, self.spec.n_params)]
 
     # ------------------------------------------------------------------ init / state_dict
     def reset_parameters(self, seed: Optional[int] = None):
@@ -2134,7 +2392,10 @@ class UNetHIP(nn.Module):
 
     def _bn_tracked_inc(self):
         if self.training:
-            self.num_batches_tracked += 1
+            if self.encoder.training:
+                self.num_batches_tracked += 1
+            else:       # encoder on running statistics: its counters stay
+                self.num_batches_tracked[self._n_enc_convs:] += 1
 
     def _require_gpu(self, x):
         if not x.is_cuda:
@@ -2147,7 +2408,8 @@ class UNetHIP(nn.Module):
         x = x.float()
         if torch.is_grad_enabled() and self.flat_params.requires_grad:
             return _UNetFunction.apply(x, self.flat_params, self)
-        logits, _ = self.engine.forward(x, self.flat_params.detach(), self.bn_state, self.training, save=False)
+        logits, _ = self.engine.forward(x, self.flat_params.detach(), self.bn_state, self.training, save=False,
+                                        enc_training=self._encoder_training())
         self._bn_tracked_inc()
         return logits
 

@@ -747,6 +747,68 @@ class FlatAdam:
         self._lr_on_dev = float(lr)
         self.hyper = torch.ones(3, dtype=torch.float32, device=dev)
         self.skip = torch.zeros(1, dtype=torch.int32, device=dev)
+        # trainable ranges (set_trainable): None = the whole buffer with the one step count t_dev (the default launches).
+        # Otherwise the buffer is partitioned into segments at every range boundary seen so far, each with its own device
+        # step count (t_seg) and bias corrections (hyper_seg); the range table lists the trainable segments
+        self._segments = None       # [(lo, hi)] partition of [0, n)
+        self._trainable = None      # [bool] per segment
+        self.t_seg = self.hyper_seg = self.table = None
+        self._table_rows = self._table_n = self._max_len = 0
+
+    def set_trainable(self, ranges=None):
+        """Only the given [(lo, hi)] ranges of the flat buffer are clipped and updated (None = all).  torch.optim.Adam
+        semantics for a parameter without a gradient: its m, v and step count stay — every range keeps its own device
+        step count, so a range unfrozen after k steps starts with the step-1 bias correction.  Call outside graph
+        capture; calling it again with the same ranges changes nothing (no new device tensors)."""
+        n = self.p.numel()
+        rng = [(0, n)] if ranges is None else sorted((int(lo), int(hi)) for lo, hi in ranges if int(hi) > int(lo))
+        for lo, hi in rng:
+            if lo < 0 or hi > n or lo % 4 or hi % 4 and hi != n:
+                raise ValueError(f"trainable range [{lo}, {hi}) of a {n}-float buffer: ends must be multiples of 4")
+        if self._segments is None:
+            if rng == [(0, n)]:
+                return                  # all trainable, never partitioned: the default launches
+            self._segments = [(0, n)]
+            self.t_seg = self.t_dev.clone()
+            self.hyper_seg = self.hyper.clone()
+        cuts = sorted({b for seg in self._segments for b in seg} | {b for r in rng for b in r})
+        segs = list(zip(cuts[:-1], cuts[1:]))
+        trainable = [any(lo <= a and b <= hi for lo, hi in rng) for a, b in segs]
+        if segs == self._segments and trainable == self._trainable:
+            return
+        dev = self.p.device
+        if segs != self._segments:      # a split segment hands its step count to both parts
+            src = [next(i for i, (a, b) in enumerate(self._segments) if a <= lo and hi <= b) for lo, hi in segs]
+            idx = torch.tensor(src, dtype=torch.int64, device=dev)
+            self.t_seg = self.t_seg.index_select(0, idx)
+            self.hyper_seg = self.hyper_seg.view(-1, 3).index_select(0, idx).reshape(-1).contiguous()
+        self._segments, self._trainable = segs, trainable
+        table, row = [], 0
+        lib = _lib.load()
+        for si, ((lo, hi), tr) in enumerate(zip(segs, trainable)):
+            if tr:
+                table += [lo, hi, row, si]
+                row += lib.dt_sumsq_rows(hi - lo)
+        if not table:
+            raise ValueError("set_trainable: no trainable range")
+        self.table = torch.tensor(table, dtype=torch.int64, device=dev)
+        self._table_n = len(table) // 4
+        self._table_rows = row
+        self._max_len = max(hi - lo for (lo, hi), tr in zip(segs, trainable) if tr)
+        if row > self.partial.numel():
+            self.partial = torch.empty(row, dtype=torch.float64, device=dev)
+
+    def reset_state(self, lr: Optional[float] = None):
+        """a fresh torch.optim.Adam on the same parameters (the reference MultiStage's LR-reduce stage): moments and step
+        counts back to zero, trainable ranges kept"""
+        self.m.zero_()
+        self.v.zero_()
+        self.t_dev.zero_()
+        if self.t_seg is not None:
+            self.t_seg.zero_()
+        self.t = 0
+        if lr is not None:
+            self.lr = float(lr)
 
     def sync_lr(self):
         """push a changed learning rate to the device (stream-ordered fill: the value travels as a kernel argument).
@@ -764,7 +826,9 @@ class FlatAdam:
         return self.skip
 
     def steps_applied(self) -> int:
-        """optimiser steps that were not skipped (host sync)"""
+        """optimiser steps that were not skipped (host sync; with trainable ranges: the largest per-range count)"""
+        if self.t_seg is not None:
+            return int(self.t_seg.max().item())
         return int(self.t_dev.item())
 
     def step(self, grads: torch.Tensor, grad_scale: float = 1.0, skip_flag: Optional[torch.Tensor] = None,
@@ -778,6 +842,19 @@ class FlatAdam:
         st = _st()
         if skip_flag is None:          # stand-alone use: the non-finite-gradient guard of dt_clip_coef still applies
             skip_flag = self.skip.zero_()
+        if self._segments is not None:  # trainable ranges: frozen parts are neither read nor written
+            b1, b2 = self.betas
+            _lib.check(lib.dt_sumsq_ranges(_p(grads), _p(self.table), self._table_n, self._table_rows, _p(self.partial), st),
+                       "dt_sumsq_ranges")
+            _lib.check(lib.dt_clip_coef(_p(self.partial), self._table_rows, float(self.max_norm or 0.0), float(grad_scale),
+                                        _p(self.norm), _p(self.coef), _p(skip_flag), st), "dt_clip_coef")
+            _lib.check(lib.dt_adam_advance_ranges(_p(self.t_seg), _p(self.table), self._table_n, _p(skip_flag),
+                                                  _p(self.lr_dev), b1, b2, _p(self.hyper_seg), st), "dt_adam_advance_ranges")
+            _lib.check(lib.dt_adam_step_ranges(_p(self.p), _p(grads), _p(self.m), _p(self.v), _p(self.table), self._table_n,
+                                               self._max_len, _p(self.hyper_seg), b1, b2, self.eps, _p(self.coef),
+                                               _p(skip_flag), st), "dt_adam_step_ranges")
+            self.t += 1
+            return self.norm
         _lib.check(lib.dt_sumsq(_p(grads), n, _p(self.partial), st), "dt_sumsq")
         _lib.check(lib.dt_clip_coef(_p(self.partial), self.rows, float(self.max_norm or 0.0), float(grad_scale),
                                     _p(self.norm), _p(self.coef), _p(skip_flag), st), "dt_clip_coef")

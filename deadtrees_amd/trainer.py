@@ -81,7 +81,10 @@ class HipTrainer:
 
     def step(self, img: torch.Tensor, mask: torch.Tensor, distmap: Optional[torch.Tensor] = None,
              alpha: float = 1.0):
-        """returns the (device) loss tensor; no host synchronisation happens here."""
+        """returns the (device) loss tensor; no host synchronisation happens here.  Honours ``model.encoder``: its
+        BatchNorm mode (``model.encoder.eval()`` survives the step) and its weight freeze (frozen ranges get no
+        gradient, no all-reduce and no update)."""
+        self.opt.set_trainable(self.model.trainable_ranges())
         if self.use_graph:
             return self._graph_step(img, mask, distmap, alpha)
         return self._eager_step(img, mask, distmap, alpha)
@@ -90,9 +93,11 @@ class HipTrainer:
     def _graph_step(self, img, mask, distmap, alpha):
         # alpha (the per-epoch boundary ramp of segmodel.py:157-160) is baked into the captured loss blend: it belongs to
         # the key only where it is read (BOUNDARY-RAMPED) — otherwise fit()'s ramp would re-capture the step every epoch
+        # the encoder's freeze and BatchNorm mode change what the step launches: a change re-captures
         key = (tuple(img.shape), img.dtype, tuple(mask.shape), mask.dtype,
                None if distmap is None else tuple(distmap.shape),
-               float(alpha) if "BOUNDARY-RAMPED" in self.losses else None)
+               float(alpha) if "BOUNDARY-RAMPED" in self.losses else None,
+               self.model.encoder_frozen, self.model.encoder.training or not self.model.training)
         g = self._graph
         if g is None or g["key"] != key:
             self._graph = g = {"key": key, "warm": 0}     # new shapes / loss blend: drop the old graph, warm up again
@@ -113,7 +118,7 @@ class HipTrainer:
         self.opt.t += 1                      # host mirror; the authoritative count is the device's t_dev
         g["graph"].replay()
         self.model.engine.mark_weights_changed()
-        self.model.num_batches_tracked += 1  # module bookkeeping outside the graph (smp state_dict key)
+        self.model._bn_tracked_inc()         # module bookkeeping outside the graph (smp state_dict key)
         self.last = g["last"]
         return g["last"]["loss"]
 
@@ -147,18 +152,20 @@ class HipTrainer:
         """forward -> fused loss -> hand-scheduled backward -> (all-reduce) -> clip + Adam, straight on the C ABI:
         no autograd graph, no ATen arithmetic; every launch is the same for every step (HIP-graph capturable)."""
         m, eng, opt = self.model, self.model.engine, self.opt
-        m.train()
+        if not m.training:       # (a model put in eval() as a whole trains as before; model.encoder.eval() survives)
+            m.train()
         m._require_gpu(img)
+        enc_tr, frozen = m._encoder_training(), m.encoder_frozen
         params = m.flat_params.detach()
         grads = m._grad_buffer()
         with torch.no_grad():
             x = img if img.dtype == torch.float32 else img.float()
             if m.precision == "bf16":
-                logits = eng.forward_bf16_train(x, params, m.bn_state)
+                logits = eng.forward_bf16_train(x, params, m.bn_state, enc_training=enc_tr, enc_frozen=frozen)
             else:
-                logits, _ = eng.forward(x, params, m.bn_state, True, save=True)
+                logits, _ = eng.forward(x, params, m.bn_state, True, save=True, enc_training=enc_tr, enc_frozen=frozen)
             if not capturing:
-                m.num_batches_tracked += 1
+                m._bn_tracked_inc()
             if distmap is None and any(n.startswith("BOUNDARY") for n in self.losses):
                 distmap = distmaps_on_device(mask, logits.shape[1])
             parts, err, saved = loss_forward(logits, mask, distmap, {"losses": self.losses, "alpha": alpha})
@@ -183,14 +190,82 @@ class HipTrainer:
         return loss
 
 
+class _TrainerView:
+    """what a Lightning callback's ``on_train_epoch_start(trainer, pl_module)`` reads from ``trainer``:
+    ``current_epoch``, ``optimizers`` (assigning a new ``torch.optim.Adam`` resets the fused optimiser's state and takes
+    its lr as the new base lr) and ``lr_schedulers`` (assigning a ``CosineAnnealingLR`` restarts the cosine schedule from
+    the current epoch with its T_max)."""
+
+    def __init__(self, trainer: "HipTrainer", sched: dict):
+        self._trainer, self._sched = trainer, sched
+        self.current_epoch = 0
+        self.optimizer_frequencies = []
+
+    @property
+    def optimizers(self):
+        return [self._trainer.opt]
+
+    @optimizers.setter
+    def optimizers(self, opts):
+        opt = opts[0] if isinstance(opts, (list, tuple)) else opts
+        lr = float(opt.param_groups[0]["lr"]) if hasattr(opt, "param_groups") else float(opt.lr)
+        self._trainer.opt.reset_state(lr=lr)
+        self._sched.update(base_lr=lr, start=self.current_epoch)
+
+    @property
+    def lr_schedulers(self):
+        return [self._sched]
+
+    @lr_schedulers.setter
+    def lr_schedulers(self, scheds):
+        s = scheds[0] if isinstance(scheds, (list, tuple)) else scheds
+        s = s.get("scheduler", s) if isinstance(s, dict) else s
+        if hasattr(s, "T_max"):
+            self._sched.update(t_max=int(s.T_max), start=self.current_epoch)
+
+    def _configure_schedulers(self, schedulers, monitor=None, is_manual_optimization=False):
+        return list(schedulers)     # (Lightning's own wrapping is not needed here)
+
+
+class _ModuleView:
+    """what such a callback reads from ``pl_module``: ``model`` (with ``model.encoder``), ``encoder_weights``,
+    ``hparams.training.*`` and ``parameters()``"""
+
+    def __init__(self, model, encoder_weights, hparams):
+        self.model = model
+        self.encoder_weights = encoder_weights
+        self.hparams = hparams
+
+    def parameters(self):
+        return self.model.parameters()
+
+
 def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: int = 10, to_device=None,
-        on_epoch_end=None):
+        on_epoch_end=None, callbacks=None, pl_module=None):
     """Minimal stand-in for ``Trainer.fit`` on the hot path (reference deadtrees/train.py:113): per-batch
-    ``HipTrainer.step`` and the per-epoch ``CosineAnnealingLR(T_max)`` of segmodel.py:426-428."""
+    ``HipTrainer.step`` and the per-epoch ``CosineAnnealingLR(T_max)`` of segmodel.py:426-428.
+
+    callbacks: objects with ``on_train_epoch_start(trainer, pl_module)`` (e.g. ``MultiStage``), called at the start of
+    every epoch with views of this trainer and of ``pl_module`` (a ``SemSegment``; default: a view of the trainer's model
+    with ``encoder_weights`` taken from the model and ``hparams.training`` = learning_rate / cosineannealing_tmax).
+    There is no validation loop here, so an encoder put in eval mode stays there (Lightning puts the whole module back
+    in train mode after every validation run)."""
     from .network.segmodel import cosine_lr, create_combined_batch
+    from .utils.config import to_attrdict
     history = []
+    sched = {"base_lr": float(base_lr), "t_max": int(t_max), "start": 0}
+    tview = _TrainerView(trainer, sched)
+    if callbacks and pl_module is None:
+        hp = to_attrdict({"training": {"learning_rate": base_lr, "cosineannealing_tmax": t_max}})
+        pl_module = _ModuleView(trainer.model, getattr(trainer.model, "encoder_weights", None), hp)
+    elif callbacks and not hasattr(pl_module, "model"):
+        raise ValueError("fit(callbacks=...): pl_module must have .model")
     for epoch in range(epochs):
-        trainer.opt.lr = cosine_lr(base_lr, epoch, t_max)
+        tview.current_epoch = epoch
+        for cb in callbacks or ():
+            if hasattr(cb, "on_train_epoch_start"):
+                cb.on_train_epoch_start(tview, pl_module)
+        trainer.opt.lr = cosine_lr(sched["base_lr"], epoch - sched["start"], sched["t_max"])
         losses = []
         for batch in loader:
             img, mask, distmap, _, _ = create_combined_batch(batch) if isinstance(batch, dict) else batch

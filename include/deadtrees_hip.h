@@ -257,6 +257,11 @@ int dt_conv2d_winograd_upsampled_dgrad_rows(const dt_conv_desc* desc);
 int dt_conv2d_winograd_upsampled_dgrad(const dt_conv_desc* desc, const float* dy, const float* u, float* gx, float* dskip,
                                        float* red, const dt_bn_bwd_fuse* fuse, int launches /* reserved: pass 3 */,
                                        void* stream);
+/* the same restricted to the up-sampled input channels [0, cout_split): no skip gradient computed or written (decoder
+ * blocks 1-3 with a frozen encoder); red[2][P][cout_split], P = dt_conv2d_winograd_upsampled_dgrad_x_rows(desc) */
+int dt_conv2d_winograd_upsampled_dgrad_x_rows(const dt_conv_desc* desc);
+int dt_conv2d_winograd_upsampled_dgrad_x(const dt_conv_desc* desc, const float* dy, const float* u, float* gx, float* red,
+                                         const dt_bn_bwd_fuse* fuse, void* stream);
 
 /* ------------------------------------------------------------------ segmentation head (K11,K12,K19) */
 /* logits[B,K,H,W] (NCHW) = conv3x3(x[B,H,W,Cin], w[K][3][3][Cin]) + bias; optional uint8/int64 argmax
@@ -503,6 +508,18 @@ int dt_adam_advance(double* t_dev, const int32_t* skip_flag, const double* lr_de
  * training step captured in a HIP graph replays with the current learning rate and bias corrections. */
 int dt_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, double beta1,
                      double beta2, float eps, const float* clipcoef, const int32_t* skip_flag, void* stream);
+/* The same over the TRAINABLE ranges of the flat buffer only (frozen encoder; torch.optim.Adam skips a parameter whose
+ * .grad is None and clip_grad_norm_ sees only parameters with a gradient).  table: device int64 [4 * nranges] of
+ * (lo, hi, first partial row, segment); lo and hi multiples of 4; the rows of range r are
+ * dt_sumsq_rows(hi - lo) starting at its first row, `rows` their total (dt_clip_coef reads partial[rows]).  Each range
+ * carries its own step count t_seg[segment] and bias corrections hyper_seg[3 * segment ..]; frozen ranges are neither
+ * read nor written.  Everything stays on the device (capturable); the skip flag keeps its global meaning. */
+int dt_sumsq_ranges(const float* g, const int64_t* table, int nranges, int rows, double* partial, void* stream);
+int dt_adam_advance_ranges(double* t_seg, const int64_t* table, int nranges, const int32_t* skip_flag,
+                           const double* lr_dev, double beta1, double beta2, float* hyper_seg, void* stream);
+int dt_adam_step_ranges(float* p, const float* g, float* m, float* v, const int64_t* table, int nranges, int64_t max_len,
+                        const float* hyper_seg, double beta1, double beta2, float eps, const float* clipcoef,
+                        const int32_t* skip_flag, void* stream);
 
 /* ------------------------------------------------------------------ library options */
 /* Kernel-selection switches (host side, process wide; every choice computes the same values):
