@@ -719,6 +719,9 @@ def signed_distmap(labels: torch.Tensor, K: int):
     return dist, err
 
 
+MAX_TRAINABLE_SEGMENTS = 64      # dt_adam_advance_ranges: one thread per trainable segment, one wave
+
+
 class FlatAdam:
     """clip_grad_norm_(max_norm) + torch.optim.Adam on one flat buffer, two fused HIP passes
     (reference: configs/trainer/default.yaml:18 + segmodel.py:420-425).
@@ -765,15 +768,22 @@ class FlatAdam:
         for lo, hi in rng:
             if lo < 0 or hi > n or lo % 4 or hi % 4 and hi != n:
                 raise ValueError(f"trainable range [{lo}, {hi}) of a {n}-float buffer: ends must be multiples of 4")
+        if self._segments is None and rng == [(0, n)]:
+            return                      # all trainable, never partitioned: the default launches
+        old = self._segments or [(0, n)]
+        cuts = sorted({b for seg in old for b in seg} | {b for r in rng for b in r})
+        segs = list(zip(cuts[:-1], cuts[1:]))
+        trainable = [any(lo <= a and b <= hi for lo, hi in rng) for a, b in segs]
+        # checked before any state changes: after the error the last ranges stay in force
+        if not any(trainable):
+            raise ValueError("set_trainable: no trainable range")
+        if sum(trainable) > MAX_TRAINABLE_SEGMENTS:
+            raise ValueError(f"set_trainable: {sum(trainable)} trainable segments (cut at every range end seen so far), "
+                             f"at most {MAX_TRAINABLE_SEGMENTS}")
         if self._segments is None:
-            if rng == [(0, n)]:
-                return                  # all trainable, never partitioned: the default launches
             self._segments = [(0, n)]
             self.t_seg = self.t_dev.clone()
             self.hyper_seg = self.hyper.clone()
-        cuts = sorted({b for seg in self._segments for b in seg} | {b for r in rng for b in r})
-        segs = list(zip(cuts[:-1], cuts[1:]))
-        trainable = [any(lo <= a and b <= hi for lo, hi in rng) for a, b in segs]
         if segs == self._segments and trainable == self._trainable:
             return
         dev = self.p.device
@@ -789,8 +799,6 @@ class FlatAdam:
             if tr:
                 table += [lo, hi, row, si]
                 row += lib.dt_sumsq_rows(hi - lo)
-        if not table:
-            raise ValueError("set_trainable: no trainable range")
         self.table = torch.tensor(table, dtype=torch.int64, device=dev)
         self._table_n = len(table) // 4
         self._table_rows = row

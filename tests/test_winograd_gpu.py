@@ -290,7 +290,10 @@ def test_fused_inference_forward_is_bit_identical_to_the_unfused_one():
 
 
 @pytest.mark.parametrize("B,H,W,Cy,cx,sk", [(2, 32, 48, 64, 128, 64), (1, 36, 20, 32, 64, 64), (3, 18, 34, 64, 64, 0),
-                                           (2, 16, 16, 128, 256, 128)])
+                                           (2, 16, 16, 128, 256, 128),
+                                           # several rounds of the 256-workgroup grid, the last one partial: 480 tiles
+                                           # (6 channel blocks), 504 (3, ragged), 918 (2: one partial row per workgroup)
+                                           (5, 64, 64, 128, 256, 128), (4, 100, 84, 64, 128, 64), (3, 130, 258, 32, 64, 64)])
 def test_winograd_data_gradient_with_fused_upsample_backward(B, H, W, Cy, cx, sk):
     """dt_conv2d_winograd_upsampled_dgrad (epilogue form 6 + a plain launch for the skip's channels) against the chain it
     replaces — dt_conv2d_winograd with split outputs, then dt_upsample2x_bwd_bn: the 2x2-summed gradient and the skip's
