@@ -72,6 +72,7 @@ SIGNATURES = {
     "dt_bn_stats_floats": (I64, [C.c_int, C.c_int]),
     "dt_bn_bwd_red_floats": (I64, [I64, C.c_int]),
     "dt_bn_finalize": (C.c_int, [c_f, C.c_int, C.c_int, F64, c_f, c_f, F32, F32, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "dt_bn_finalize_dev": (C.c_int, [c_f, C.c_int, C.c_int, F64, c_f, c_f, F32, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "dt_bn_eval_affine": (C.c_int, [c_f, c_f, c_f, c_f, F32, C.c_int, c_f, c_f, c_f]),
     "dt_bn_act": (C.c_int, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, I64, C.c_int, C.c_int, c_f]),
     "dt_bn_bwd_rows": (C.c_int, [I64, C.c_int]),
@@ -167,6 +168,8 @@ SIGNATURES = {
     "dt_adam_step_dev": (C.c_int, [c_f, c_f, c_f, c_f, I64, c_f, F64, F64, F32, c_f, c_f, c_f]),
     "dt_sumsq_ranges": (C.c_int, [c_f, c_f, C.c_int, C.c_int, c_f, c_f]),
     "dt_adam_advance_ranges": (C.c_int, [c_f, c_f, C.c_int, c_f, c_f, F64, F64, c_f, c_f]),
+    "dt_weight_average": (C.c_int, [c_f, c_f, I64, c_f, c_f, C.c_int, F64, c_f]),
+    "dt_cma_advance": (C.c_int, [c_f, c_f, c_f]),
     "dt_adam_step_ranges": (C.c_int, [c_f, c_f, c_f, c_f, c_f, C.c_int, I64, c_f, F64, F64, F32, c_f, c_f, c_f]),
 }
 

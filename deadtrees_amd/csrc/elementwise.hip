@@ -61,10 +61,12 @@ int dt_reduce_rows_launch(const float* in, float* out, int planes, int P, int N,
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ stats, int P, int C,
                                                           double count, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, float eps,
-                                                          float momentum, float* running_mean,
+                                                          float momentum, const float* __restrict__ momentum_dev,
+                                                          float* running_mean,
                                                           float* running_var, float* mean, float* invstd,
                                                           float* scale, float* shift) {
   __shared__ double red[2][16][17];
+  if (momentum_dev) momentum = momentum_dev[0];   // dt_bn_finalize_dev: the value of the moment the kernel runs
   const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
   const int c = blockIdx.x * 16 + cl;
   double s1 = 0.0, s2 = 0.0;
@@ -120,10 +122,9 @@ extern "C" int64_t dt_bn_stats_floats(int P, int C) {
   return (int64_t)2 * P * C + (int64_t)2 * dt_reduce_rows_out(P, BN_STAGE1_RB) * C;
 }
 
-extern "C" int dt_bn_finalize(float* stats, int P, int C, double count, const float* gamma,
-                              const float* beta, float eps, float momentum, float* running_mean,
-                              float* running_var, float* mean, float* invstd, float* scale, float* shift,
-                              void* stream) {
+static int bn_finalize_launch(float* stats, int P, int C, double count, const float* gamma, const float* beta, float eps,
+                              float momentum, const float* momentum_dev, float* running_mean, float* running_var,
+                              float* mean, float* invstd, float* scale, float* shift, void* stream) {
   DT_REQUIRE(stats && gamma && beta && mean && invstd && scale && shift && P > 0 && C > 0 && count > 0,
              "bn_finalize: bad args");
   if (P > BN_STAGE1_MIN_ROWS && (C & 3) == 0) {
@@ -136,9 +137,26 @@ extern "C" int dt_bn_finalize(float* stats, int P, int C, double count, const fl
     P = PB;
   }
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(dt_cdiv(C, 16)), dim3(256), 0, (hipStream_t)stream, stats, P, C,
-                     count, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, scale, shift);
+                     count, gamma, beta, eps, momentum, momentum_dev, running_mean, running_var, mean, invstd, scale,
+                     shift);
   DT_LAUNCH_CHECK();
   return DT_OK;
+}
+
+extern "C" int dt_bn_finalize(float* stats, int P, int C, double count, const float* gamma,
+                              const float* beta, float eps, float momentum, float* running_mean,
+                              float* running_var, float* mean, float* invstd, float* scale, float* shift,
+                              void* stream) {
+  return bn_finalize_launch(stats, P, C, count, gamma, beta, eps, momentum, nullptr, running_mean, running_var, mean,
+                            invstd, scale, shift, stream);
+}
+
+extern "C" int dt_bn_finalize_dev(float* stats, int P, int C, double count, const float* gamma, const float* beta,
+                                  float eps, const float* momentum_dev, float* running_mean, float* running_var,
+                                  float* mean, float* invstd, float* scale, float* shift, void* stream) {
+  DT_REQUIRE(momentum_dev && running_mean && running_var, "bn_finalize_dev: momentum_dev and running statistics required");
+  return bn_finalize_launch(stats, P, C, count, gamma, beta, eps, 0.f, momentum_dev, running_mean, running_var, mean,
+                            invstd, scale, shift, stream);
 }
 
 __global__ void bn_eval_affine_kernel(const float* gamma, const float* beta, const float* rm, const float* rv,

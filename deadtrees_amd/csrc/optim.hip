@@ -338,3 +338,72 @@ extern "C" int dt_adam_step_ranges(float* p, const float* g, float* m, float* v,
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
+
+// ---- averaged copy of the flat parameter buffer (torch.optim.swa_utils.AveragedModel: get_swa_multi_avg_fn /
+// get_ema_multi_avg_fn).  The number of averaged models lives on the device and is advanced there, like t_dev of
+// dt_adam_advance: one thread bumps it (unless the step is skipped), then the streaming pass reads the NEW count, so
+// every workgroup sees the same value whatever order they run in.  Same launches for every update: capturable.
+__global__ void weight_average_advance_kernel(int64_t* __restrict__ count, const int32_t* __restrict__ skip) {
+  if (!(skip && skip[0] != 0)) count[0] = count[0] + 1;
+}
+
+__device__ __forceinline__ float wavg_one(float a, float p, int mode, float div, float omd) {
+  // SWA: avg + (p - avg) / (n + 1); EMA: avg.lerp(p, 1 - decay) (weight < 0.5 form: avg + w * (p - avg))
+  return mode == DT_AVG_SWA ? a + (p - a) / div : a + (p - a) * omd;
+}
+
+__global__ __launch_bounds__(256) void weight_average_kernel(float* __restrict__ avg, const float* __restrict__ p,
+                                                             int64_t n, const int64_t* __restrict__ count,
+                                                             const int32_t* __restrict__ skip, int mode, float omd) {
+  if (skip && skip[0] != 0) return;
+  const int64_t cnt = count[0];            // already advanced: this is model number cnt
+  const bool first = cnt <= 1;
+  const float div = (float)cnt;
+  const int64_t n4 = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const f32x4 pp = reinterpret_cast<const f32x4*>(p)[i];
+    f32x4 aa = pp;
+    if (!first) {
+      aa = reinterpret_cast<const f32x4*>(avg)[i];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) aa[k] = wavg_one(aa[k], pp[k], mode, div, omd);
+    }
+    reinterpret_cast<f32x4*>(avg)[i] = aa;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    for (int64_t i = n4 << 2; i < n; ++i) avg[i] = first ? p[i] : wavg_one(avg[i], p[i], mode, div, omd);
+  }
+}
+
+extern "C" int dt_weight_average(float* avg, const float* p, int64_t n, int64_t* count_dev, const int32_t* skip_flag,
+                                 int mode, double decay, void* stream) {
+  DT_REQUIRE(avg && p && count_dev && n > 0, "weight_average: bad args");
+  DT_REQUIRE(mode == DT_AVG_SWA || mode == DT_AVG_EMA, "weight_average: mode %d (DT_AVG_SWA or DT_AVG_EMA)", mode);
+  DT_REQUIRE(mode != DT_AVG_EMA || (decay >= 0.0 && decay <= 1.0), "weight_average: decay %g outside [0, 1]", decay);
+  DT_REQUIRE(((((uintptr_t)avg) | ((uintptr_t)p)) & 15) == 0, "weight_average: buffers must be 16-byte aligned");
+  int64_t grid = ((n >> 2) + 255) / 256;
+  if (grid > 256 * 16) grid = 256 * 16;
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(weight_average_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, count_dev, skip_flag);
+  DT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(weight_average_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, avg, p, n,
+                     (const int64_t*)count_dev, skip_flag, mode, (float)(1.0 - decay));
+  DT_LAUNCH_CHECK();
+  return DT_OK;
+}
+
+// cumulative moving average of BatchNorm statistics (momentum=None in torch: factor 1 / num_batches_tracked): the batch
+// count and the momentum dt_bn_finalize_dev reads stay on the device, so a captured recalibration pass replays
+__global__ void cma_advance_kernel(int64_t* __restrict__ n, float* __restrict__ momentum) {
+  const int64_t k = n[0] + 1;
+  n[0] = k;
+  momentum[0] = (float)(1.0 / (double)k);
+}
+
+extern "C" int dt_cma_advance(int64_t* n_dev, float* momentum_dev, void* stream) {
+  DT_REQUIRE(n_dev && momentum_dev, "cma_advance: bad args");
+  hipLaunchKernelGGL(cma_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, n_dev, momentum_dev);
+  DT_LAUNCH_CHECK();
+  return DT_OK;
+}

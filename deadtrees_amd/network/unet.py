@@ -75,6 +75,11 @@ class UNetEngine:
         self.encoder_hi = spec.buckets[0][1]
         # per backward: the convolutions whose data gradient / weight gradient were launched (tests, timing labels)
         self.launches = {"dgrad": [], "wgrad": []}
+        # BatchNorm recalibration forward (stochastic weight averaging): the device momentum float[1] every
+        # dt_bn_finalize_dev of the current pass reads (None outside such a pass), and the launch record of the last one:
+        # ("conv" | "bn_finalize_dev" | "bn_act" | "head", convolution key)
+        self._recal: Optional[torch.Tensor] = None
+        self.recal_launches: list = []
         # BatchNorm-backward reduction of a block-output layer inside the fp32 gradient-JOIN epilogue: measured slower
         # than the separate pass (526 vs 530 tiles/s, same box: 48 extra loads per lane in the read-modify-write
         # epilogue); the bf16 path keeps it (its join epilogue is LDS-staged, +0.5 %).  Kernel support stays tested.
@@ -296,9 +301,15 @@ class UNetEngine:
             P = self._stat_rows(desc, u)
             stats = self._buf("bn_stats", self.lib.dt_bn_stats_floats(P, c.cout), device=dev)
             self._conv(desc, src0, src1, w, y, None, stats, in_ss, u=u)
-            _lib.check(self.lib.dt_bn_finalize(_p(stats), P, c.cout, float(B * Ho * Wo), _p(gamma), _p(beta),
-                                               BN_EPS, BN_MOMENTUM, _p(rmean), _p(rvar), _p(mean), _p(invstd),
-                                               _p(scale), _p(shift), _stream()), "dt_bn_finalize")
+            if self._recal is not None:     # recalibration: cumulative-average momentum, read from the device
+                _lib.check(self.lib.dt_bn_finalize_dev(_p(stats), P, c.cout, float(B * Ho * Wo), _p(gamma), _p(beta),
+                                                       BN_EPS, _p(self._recal), _p(rmean), _p(rvar), _p(mean),
+                                                       _p(invstd), _p(scale), _p(shift), _stream()), "dt_bn_finalize_dev")
+                self.recal_launches += [("conv", c.key), ("bn_finalize_dev", c.key)]
+            else:
+                _lib.check(self.lib.dt_bn_finalize(_p(stats), P, c.cout, float(B * Ho * Wo), _p(gamma), _p(beta),
+                                                   BN_EPS, BN_MOMENTUM, _p(rmean), _p(rvar), _p(mean), _p(invstd),
+                                                   _p(scale), _p(shift), _stream()), "dt_bn_finalize")
         else:
             self._conv(desc, src0, src1, w, y, None, None, in_ss, u=u)
             if not self._affine_fresh:   # inference: the coefficients of the previous call are still valid (see forward)
@@ -313,12 +324,25 @@ class UNetEngine:
         """relu: True/1 = ReLU after the residual add, 2 = ReLU on the main branch only (ResUnet decoder), 0 = none"""
         B, H, W, Cc = y.shape
         z = torch.empty_like(y) if out is None else out
+        self._rec_act(ss)
         e0 = self._pb()
         _lib.check(self.lib.dt_bn_act(_p(y), _p(ss[0]), _p(ss[1]), _p(res),
                                       _p(res_ss[0]) if res_ss else None, _p(res_ss[1]) if res_ss else None,
                                       _p(z), B * H * W, Cc, int(relu), _stream()), "dt_bn_act")
         self._pe(e0, "bn_act_kernel", 0.0, 4.0 * y.numel() * (2 + (res is not None)))
         return z
+
+    def _rec_act(self, ss):
+        """recalibration launch record: the normalise pass of the convolution whose scale slice ss[0] is"""
+        if self._recal is not None:
+            off = ss[0].storage_offset() - 2 * self.spec.n_bn_channels
+            self.recal_launches.append(("bn_act", self._bn_off_key().get(off)))
+
+    def _bn_off_key(self):
+        tab = getattr(self, "_bn_off_tab", None)
+        if tab is None:
+            tab = self._bn_off_tab = {c.bn_off: c.key for c in self.spec.convs if c.bn_key is not None}
+        return tab
 
     def _conv_affine_direct(self, c: ConvSpec, params, bnstate, bnws, src0, src1, mode0, B, Hin, Win, relu=True):
         """inference: [relu](bn_eval(conv(x))) in one launch of the direct kernel (dt_conv2d_affine) — the layers that are
@@ -389,13 +413,24 @@ class UNetEngine:
     # ------------------------------------------------------------------ forward
     def forward(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor, training: bool,
                 save: bool, want_argmax: Optional[str] = None, nhwc: bool = False, enc_training: Optional[bool] = None,
-                enc_frozen: bool = False):
+                enc_frozen: bool = False, recal: Optional[torch.Tensor] = None):
         """nhwc=True: the input already is the kernels' layout [B,H,W,C] (the tiled-inference gather produces it):
         no NCHW -> NHWC pass.  enc_training: BatchNorm mode of the encoder (stem + layers 1-4; default: `training`) —
         False with training=True is fine-tuning on the encoder's running statistics.  enc_frozen: the encoder's weights
         get no gradient: nothing of the encoder is saved for backward, and an encoder in eval mode runs the fused
-        inference form."""
+        inference form.
+        recal: device float[1] momentum -> BatchNorm recalibration pass (`update_bn` of stochastic weight averaging): every
+        BatchNorm layer, encoder included, normalises with batch statistics and folds them into its running statistics
+        with THAT momentum (dt_bn_finalize_dev); nothing is saved.  With the Unet decoder the pass ends once the last
+        BatchNorm's statistics are final — no normalise pass of the last convolution, no head — and returns (None, None)."""
         sp = self.spec
+        self._recal = None
+        if recal is not None:
+            if not training or save or enc_frozen:
+                raise RuntimeError("recalibration forward: training statistics, nothing saved, no frozen-encoder form")
+            if recal.dtype != torch.float32 or recal.device != x_nchw.device:
+                raise RuntimeError("recalibration forward: the momentum is a float32 tensor on the input's device")
+            enc_training = True
         if nhwc:
             if x_nchw.dim() != 4 or x_nchw.shape[3] != sp.in_channels:
                 raise RuntimeError(f"expected NHWC input [B,H,W,{sp.in_channels}], got {tuple(x_nchw.shape)}")
@@ -412,6 +447,8 @@ class UNetEngine:
         x_nchw = x_nchw.contiguous()
         st = _stream()
         lib = self.lib
+        if recal is not None:
+            self._recal, self.recal_launches = recal, []
         sv = _Saved() if save else None
         dec_training = training
         enc_training = training if enc_training is None else bool(enc_training)
@@ -555,6 +592,9 @@ class UNetEngine:
             z1 = self._bn_act(y1, ss1) if (self._mat_z1 and blk.conv2.cout % 64 == 0) else None
             y2, h2, w2, ss2 = self._conv_bn(blk.conv2, params, bnstate, bnws, y1 if z1 is None else z1, None, 0, B, h1, w1,
                                             training, in_ss=ss1 if z1 is None else None, save_stats=save)
+            if self._recal is not None and i == len(sp.decoder) - 1:
+                self._recal = None              # every BatchNorm's statistics are final: nothing else to launch
+                return None, None
             if i == len(sp.decoder) - 1 or (self._mat_z2 and sp.decoder[i + 1].conv1.cout % 64 == 0):
                 z2 = self._bn_act(y2, ss2)      # the head kernel (or a Winograd conv1) reads a materialised activation
                 nxt, nxt_ss = z2, None
@@ -575,6 +615,9 @@ class UNetEngine:
             am8 = torch.empty((B, dh, dw), dtype=torch.uint8, device=dev)
         wh = params[hd.w_off:hd.w_off + hd.w_size]
         bh = params[hd.b_off:hd.b_off + K]
+        if self._recal is not None:
+            self.recal_launches.append(("head", hd.key))
+            self._recal = None
         e0 = self._pb()
         _lib.check(lib.dt_head_fwd(_p(d), _p(wh), _p(bh), _p(logits), _p(am64), _p(am8), B, dh, dw, hd.cin, K, st),
                    "dt_head_fwd")
@@ -940,13 +983,23 @@ class UNetEngine:
 
     # ------------------------------------------------------------------ bf16 training (BASELINE configs[2])
     def forward_bf16_train(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor,
-                           enc_training: bool = True, enc_frozen: bool = False):
+                           enc_training: bool = True, enc_frozen: bool = False, recal: Optional[torch.Tensor] = None):
         """training-mode forward with bf16 activations / weights, fp32 accumulation, fp32 BatchNorm statistics
         (taken from the accumulators), fp32 master parameters.  Stem and head run in fp32.
         enc_frozen: the encoder's weights get no gradient — nothing of it is saved; enc_training=False (only with a
         frozen encoder here: the bf16 path has no frozen-statistics BatchNorm backward) normalises the encoder with its
-        running statistics, which stay untouched."""
+        running statistics, which stay untouched.
+        recal: device float[1] momentum -> BatchNorm recalibration pass, see `forward`: the same kernels on the same
+        data as the training forward, nothing kept for backward (`self.saved` stays as it was), Unet: returns None after
+        the last BatchNorm's statistics."""
         sp, lib = self.spec, self.lib
+        self._recal = None
+        if recal is not None:
+            if enc_frozen or not enc_training:
+                raise RuntimeError("recalibration forward: every BatchNorm layer runs on batch statistics")
+            if recal.dtype != torch.float32 or recal.device != x_nchw.device:
+                raise RuntimeError("recalibration forward: the momentum is a float32 tensor on the input's device")
+            self._recal, self.recal_launches = recal, []
         if not enc_training and not enc_frozen:
             raise NotImplementedError("bf16: an encoder in eval mode trains only with frozen weights "
                                       "(model.encoder.requires_grad_(False)); use fp32 for trainable weights on "
@@ -976,6 +1029,18 @@ class UNetEngine:
                                                  _p(bnws[3 * nb + c.bn_off:3 * nb + c.bn_off + c.cout]), st),
                            "dt_bn_eval_affine")
                 return self._ss(c, bnws)
+            if recal is not None:
+                _lib.check(lib.dt_bn_finalize_dev(_p(stats), P, c.cout, float(count), _p(params[c.g_off:c.g_off + c.cout]),
+                                                  _p(params[c.b_off:c.b_off + c.cout]), BN_EPS, _p(recal),
+                                                  _p(bnstate[2 * c.bn_off:2 * c.bn_off + c.cout]),
+                                                  _p(bnstate[2 * c.bn_off + c.cout:2 * c.bn_off + 2 * c.cout]),
+                                                  _p(bnws[c.bn_off:c.bn_off + c.cout]),
+                                                  _p(bnws[nb + c.bn_off:nb + c.bn_off + c.cout]),
+                                                  _p(bnws[2 * nb + c.bn_off:2 * nb + c.bn_off + c.cout]),
+                                                  _p(bnws[3 * nb + c.bn_off:3 * nb + c.bn_off + c.cout]), st),
+                           "dt_bn_finalize_dev")
+                self.recal_launches += [("conv", c.key), ("bn_finalize_dev", c.key)]
+                return self._ss(c, bnws)
             _lib.check(lib.dt_bn_finalize(_p(stats), P, c.cout, float(count), _p(params[c.g_off:c.g_off + c.cout]),
                                           _p(params[c.b_off:c.b_off + c.cout]), BN_EPS, BN_MOMENTUM,
                                           _p(bnstate[2 * c.bn_off:2 * c.bn_off + c.cout]),
@@ -1004,6 +1069,7 @@ class UNetEngine:
         def bn_act(y, ss, res=None, res_ss=None, y_f32=False):
             Bq, Hq, Wq, Cq = y.shape
             z = torch.empty((Bq, Hq, Wq, Cq), dtype=bf, device=dev)
+            self._rec_act(ss)
             e0 = self._pb()
             _lib.check(lib.dt_bn_act_bf16(_p(y), 1 if y_f32 else 0, _p(ss[0]), _p(ss[1]), _p(res),
                                           _p(res_ss[0]) if res_ss else None, _p(res_ss[1]) if res_ss else None, _p(z),
@@ -1084,6 +1150,9 @@ class UNetEngine:
             wide = self._mat_dec_bf16 and blk.conv2.cout % 64 == 0
             z1 = bn_act(y1, ss1) if wide else None
             y2, h2, w2, ss2 = conv(blk.conv2, y1 if z1 is None else z1, None, 0, h1, w1, in_ss=ss1 if z1 is None else None)
+            if recal is not None and i == len(sp.decoder) - 1:
+                self._recal = None              # every BatchNorm's statistics are final: nothing else to launch
+                return None
             if i == len(sp.decoder) - 1 or wide:
                 z2 = bn_act(y2, ss2)
                 nxt, nxt_ss = z2, None
@@ -1095,9 +1164,14 @@ class UNetEngine:
         hd = sp.head
         K = hd.cout
         logits = torch.empty((B, K, dh, dw), dtype=torch.float32, device=dev)
+        if recal is not None:
+            self.recal_launches.append(("head", hd.key))
         _lib.check(lib.dt_head_fwd_bf16(_p(d), _p(params[hd.w_off:hd.w_off + hd.w_size]),
                                         _p(params[hd.b_off:hd.b_off + K]), _p(logits), None, None, B, dh, dw, hd.cin, K,
                                         st), "dt_head_fwd_bf16")
+        if recal is not None:       # nothing of this pass is for a backward
+            self._recal = None
+            return logits
         sv.d["head"] = dict(x=d, H=dh, W=dw)
         sv.d["B"] = B
         sv.d["bf16"] = True
@@ -2441,3 +2515,95 @@ class UNetHIP(nn.Module):
         self._require_gpu(x)
         logits, _ = self.engine.forward_bf16_eval(x.float(), self.flat_params.detach(), self.bn_state)
         return logits
+
+    # ------------------------------------------------------------------ BatchNorm recalibration (stochastic weight averaging)
+    def _bn_reset_pattern(self) -> torch.Tensor:
+        """running_mean = 0 / running_var = 1 for every BatchNorm layer, in the layout of ``bn_state``"""
+        pat = torch.zeros(2 * self.spec.n_bn_channels, dtype=torch.float32)
+        for c in self.spec.convs:
+            if c.bn_key is not None:
+                pat[2 * c.bn_off + c.cout:2 * c.bn_off + 2 * c.cout] = 1.0
+        return pat
+
+    @staticmethod
+    def _batch_image(batch) -> torch.Tensor:
+        """the image tensor of a batch: a tensor, an ``(img, ...)`` tuple / list or the datamodule's dict"""
+        if isinstance(batch, dict):
+            from .segmodel import create_combined_batch
+            batch = create_combined_batch(batch)
+        if isinstance(batch, (list, tuple)):
+            batch = batch[0]
+        if not torch.is_tensor(batch):
+            raise TypeError(f"update_bn: cannot find the image tensor of a {type(batch).__name__} batch")
+        return batch
+
+    def _recal_state(self):
+        """device scalars of a recalibration pass: batch count int64[1] and the momentum float[1] = 1 / count"""
+        dev = self.flat_params.device
+        st = getattr(self, "_recal_dev", None)
+        if st is None or st[0].device != dev:
+            st = self._recal_dev = (torch.zeros(1, dtype=torch.int64, device=dev),
+                                    torch.ones(1, dtype=torch.float32, device=dev))
+        return st
+
+    def recalibrate_batch(self, x: torch.Tensor, precision: Optional[str] = None):
+        """one batch of ``update_bn``: advance the device batch count (momentum = 1 / count), then the statistics-only
+        forward.  Launches the same kernels with the same arguments for every batch of one shape: capturable."""
+        self._require_gpu(x)
+        n_dev, mom = self._recal_state()
+        eng = self.engine
+        _lib.check(eng.lib.dt_cma_advance(_p(n_dev), _p(mom), _stream()), "dt_cma_advance")
+        params = self.flat_params.detach()
+        if (precision or self.precision) == "bf16":
+            eng.forward_bf16_train(x, params, self.bn_state, recal=mom)
+        else:
+            eng.forward(x, params, self.bn_state, True, save=False, recal=mom)
+
+    @torch.no_grad()
+    def update_bn(self, batches, precision: Optional[str] = None, to_device=None, _run=None) -> int:
+        """``torch.optim.swa_utils.update_bn`` for this model: running means to 0, variances to 1,
+        ``num_batches_tracked`` to 0, then one statistics-only forward per batch in which EVERY BatchNorm layer (the
+        encoder's too, whatever ``model.encoder.training`` says — torch calls ``model.train()``) normalises with batch
+        statistics and folds them into its running statistics with the cumulative momentum 1 / (batches so far).  The
+        train / eval flags of the module and of the encoder view come back exactly as found, ``num_batches_tracked``
+        ends at the batch count, parameters are not written.  Returns the batch count.
+
+        precision: "fp32" / "bf16" (default: ``self.precision``).  Batches: tensors, ``(img, ...)`` tuples or the
+        datamodule's dicts.  One deliberate difference from torch: an empty iterable raises ``ValueError`` BEFORE any
+        state changes (torch would leave every BatchNorm at mean 0 / variance 1)."""
+        precision = precision or self.precision
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"precision {precision!r}: use 'fp32' or 'bf16'")
+        if not self.flat_params.is_cuda:
+            raise RuntimeError("deadtrees_amd.UNetHIP runs only on an MI355X (HIP) device; there is no CPU fallback")
+        it = iter(batches)
+        try:
+            first = next(it)
+        except StopIteration:
+            raise ValueError("update_bn: no batches (the running statistics were left as they are)") from None
+        was, enc_was = self.training, self.encoder.training
+        n_dev, _ = self._recal_state()
+        k = 0
+        try:
+            self.bn_state.copy_(self._bn_reset_pattern())
+            self.num_batches_tracked.zero_()
+            n_dev.zero_()
+            batch = first
+            while True:
+                x = self._batch_image(batch)
+                if to_device is not None:
+                    x = x.to(to_device)
+                self._require_gpu(x)
+                x = x if x.dtype == torch.float32 else x.float()
+                (_run or self.recalibrate_batch)(x, precision)
+                k += 1
+                try:
+                    batch = next(it)
+                except StopIteration:
+                    break
+        finally:
+            self.num_batches_tracked.fill_(k)
+            self.engine._bn_epoch += 1      # running statistics rewritten on the device: cached eval affines are stale
+            self.train(was)
+            self.encoder.train(enc_was)
+        return k

@@ -181,6 +181,50 @@ def bn_finalize(stats, count, gamma, beta, running_mean=None, running_var=None, 
     return mean, invstd, scale, shift
 
 
+def bn_finalize_dev(stats, count, gamma, beta, running_mean, running_var, momentum_dev, eps=1e-5):
+    """``bn_finalize`` with the momentum read from the device tensor float32[1] when the kernel runs"""
+    _gpu(stats, gamma, beta, running_mean, running_var, momentum_dev)
+    if momentum_dev.dtype != torch.float32:
+        raise RuntimeError("bn_finalize_dev: the momentum is a float32 device tensor")
+    _, P, Cc = stats.shape
+    dev = stats.device
+    full = torch.empty(_lib.load().dt_bn_stats_floats(P, Cc), dtype=torch.float32, device=dev)
+    full[:2 * P * Cc] = stats.reshape(-1)
+    mean, invstd, scale, shift = (torch.empty(Cc, dtype=torch.float32, device=dev) for _ in range(4))
+    _lib.check(_lib.load().dt_bn_finalize_dev(_p(full), P, Cc, float(count), _p(gamma), _p(beta), eps, _p(momentum_dev),
+                                              _p(running_mean), _p(running_var), _p(mean), _p(invstd), _p(scale),
+                                              _p(shift), _st()), "dt_bn_finalize_dev")
+    return mean, invstd, scale, shift
+
+
+def cma_advance(n_dev, momentum_dev):
+    """n_dev (int64[1]) += 1; momentum_dev (float32[1]) = 1 / n_dev — the cumulative-average momentum of BatchNorm"""
+    _gpu(n_dev, momentum_dev)
+    if n_dev.dtype != torch.int64 or momentum_dev.dtype != torch.float32:
+        raise RuntimeError("cma_advance: int64 count and float32 momentum")
+    _lib.check(_lib.load().dt_cma_advance(_p(n_dev), _p(momentum_dev), _st()), "dt_cma_advance")
+
+
+AVG_MODES = {"swa": 0, "ema": 1}      # DT_AVG_SWA / DT_AVG_EMA
+
+
+def weight_average(avg, p, count_dev, mode="swa", decay=0.0, skip_flag=None):
+    """one ``dt_weight_average`` update of ``avg`` (fp32, contiguous, 16-byte aligned) with the parameters ``p``;
+    ``count_dev`` int64[1] is advanced on the device unless ``skip_flag`` (int32[1]) is set"""
+    _gpu(avg, p, count_dev, skip_flag)
+    if avg.dtype != torch.float32 or p.dtype != torch.float32 or count_dev.dtype != torch.int64:
+        raise RuntimeError("weight_average: float32 buffers and an int64 count")
+    if avg.numel() != p.numel() or not (avg.is_contiguous() and p.is_contiguous()):
+        raise RuntimeError("weight_average: avg and p must be contiguous and of one size")
+    if avg.device != p.device or count_dev.device != p.device or (skip_flag is not None and skip_flag.device != p.device):
+        raise RuntimeError(f"weight_average: avg on {avg.device}, parameters on {p.device}")
+    if skip_flag is not None and skip_flag.dtype != torch.int32:
+        raise RuntimeError("weight_average: the skip flag is an int32 device tensor")
+    _lib.check(_lib.load().dt_weight_average(_p(avg), _p(p), p.numel(), _p(count_dev), _p(skip_flag), AVG_MODES[mode],
+                                             float(decay), _st()), "dt_weight_average")
+    return avg
+
+
 def bn_act(y, scale, shift, res=None, rscale=None, rshift=None, relu=True):
     _gpu(y, scale, shift, res)
     out = torch.empty_like(y)
@@ -873,3 +917,73 @@ class FlatAdam:
                                         self.eps, _p(self.coef), _p(skip_flag), st), "dt_adam_step_dev")
         self.t += 1
         return self.norm
+
+
+def parse_average(mode):
+    """"swa" | "ema" | ("ema", decay) | ("swa",) -> (name, decay); ValueError otherwise"""
+    name, decay = (mode, None) if isinstance(mode, str) else (tuple(mode) + (None,))[:2]
+    if name == "swa" and not decay:
+        return "swa", 0.0
+    if name == "ema":
+        decay = 0.999 if decay is None else float(decay)      # torch's get_ema_multi_avg_fn default
+        if 0.0 <= decay <= 1.0:
+            return "ema", decay
+    raise ValueError(f"average {mode!r}: use 'swa' or ('ema', decay) with 0 <= decay <= 1")
+
+
+class WeightAverager:
+    """An averaged copy of a flat fp32 parameter buffer (``torch.optim.swa_utils.AveragedModel`` with
+    ``get_swa_multi_avg_fn`` / ``get_ema_multi_avg_fn``, parameters only — BatchNorm buffers are not averaged).
+
+    ``avg`` and the number of averaged models ``n_dev`` live on the parameters' device; ``update`` is one
+    ``dt_weight_average`` call with nothing that changes on the host, so it can sit inside a captured step."""
+
+    def __init__(self, params: torch.Tensor, mode="swa"):
+        _gpu(params)
+        if params.dtype != torch.float32 or params.dim() != 1 or not params.is_contiguous():
+            raise RuntimeError("WeightAverager: a contiguous flat float32 parameter buffer")
+        self.mode, self.decay = parse_average(mode)
+        self.p = params
+        self.avg = torch.zeros_like(params)
+        self.n_dev = torch.zeros(1, dtype=torch.int64, device=params.device)
+
+    def to(self, params: torch.Tensor) -> "WeightAverager":
+        """follow the parameters after ``model.to(device)``: rebind to the new buffer, moving ``avg`` and the count"""
+        _gpu(params)
+        if params.numel() != self.avg.numel():
+            raise RuntimeError(f"WeightAverager: {params.numel()} parameters, average of {self.avg.numel()}")
+        self.p = params
+        self.avg = self.avg.to(params.device)
+        self.n_dev = self.n_dev.to(params.device)
+        return self
+
+    def update(self, skip_flag: Optional[torch.Tensor] = None, capturing: bool = False):
+        """fold the current parameters into ``avg``; a set ``skip_flag`` leaves ``avg`` and the count alone.
+        capturing: inside a HIP-graph capture (nothing differs: there is no host-side state to refresh)"""
+        if self.p.device != self.avg.device:
+            raise RuntimeError(f"WeightAverager: average on {self.avg.device}, parameters on {self.p.device}: "
+                               "call averager.to(model.flat_params.data)")
+        weight_average(self.avg, self.p, self.n_dev, self.mode, self.decay, skip_flag)
+
+    @property
+    def n_averaged(self) -> int:
+        """number of models averaged so far (host sync)"""
+        return int(self.n_dev.item())
+
+    def copy_to(self, params: torch.Tensor):
+        if params.device != self.avg.device:
+            raise RuntimeError(f"WeightAverager: average on {self.avg.device}, target on {params.device}")
+        if params.numel() != self.avg.numel():
+            raise RuntimeError(f"WeightAverager: {params.numel()} parameters, average of {self.avg.numel()}")
+        params.detach().view(-1).copy_(self.avg)
+
+    def state_dict(self):
+        return {"mode": self.mode, "decay": self.decay, "avg": self.avg.detach().cpu().clone(),
+                "n_averaged": self.n_averaged}
+
+    def load_state_dict(self, sd):
+        if sd["avg"].numel() != self.avg.numel():
+            raise RuntimeError(f"WeightAverager: state of {sd['avg'].numel()} floats, buffer of {self.avg.numel()}")
+        self.mode, self.decay = parse_average((sd["mode"], sd["decay"]))
+        self.avg.copy_(sd["avg"].to(self.avg.device, torch.float32).view(-1))
+        self.n_dev.fill_(int(sd["n_averaged"]))

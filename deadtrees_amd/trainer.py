@@ -10,6 +10,8 @@ statistics, mean-reduced gradients — SURVEY §8e).
 """
 from __future__ import annotations
 
+import math
+from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
 import torch
@@ -17,7 +19,7 @@ import torch
 from .data.distmap import distmaps_on_device
 from .loss.seg_loss import PART_KEYS, loss_backward, loss_forward
 from .network.unet import UNetHIP
-from .ops import FlatAdam
+from .ops import FlatAdam, WeightAverager
 
 
 class GradReducer:
@@ -49,8 +51,13 @@ class GradReducer:
 class HipTrainer:
     def __init__(self, model: UNetHIP, lr: float = 3e-4, clip: float = 0.5,
                  losses: Sequence[str] = ("GDICE", "FOCAL"), distributed: bool = False, group=None,
-                 precision: str = "fp32", graph: bool = False):
-        """graph=True: after two eager steps the whole step (forward, loss, backward, clip, Adam) is captured into a
+                 precision: str = "fp32", graph: bool = False, average=None):
+        """average: None | "swa" | ("ema", decay) — an averaged copy of the flat parameters (``self.averager``,
+        torch.optim.swa_utils.AveragedModel semantics).  "ema": updated by every step right after Adam, inside the
+        captured graph, and left alone by a skipped (non-finite) step.  "swa": updated by ``update_average()``, which
+        ``fit(swa=...)`` calls once per epoch.  None allocates nothing and adds no launch.  With distributed=True the
+        average is local to each rank: ranks hold equal parameters, hence equal averages, and no collective runs.
+        graph=True: after two eager steps the whole step (forward, loss, backward, clip, Adam) is captured into a
         HIP graph and replayed — ~750 kernel launches become one, which matters once the bf16 step is shorter than
         the Python launch path."""
         if not model.flat_params.is_cuda:
@@ -72,12 +79,70 @@ class HipTrainer:
         # bench.py keeps multi-GPU runs eager until that has run on a real 8-GPU node)
         self.use_graph = bool(graph)
         self._graph = None
+        self.averager = None if average is None else WeightAverager(model.flat_params.data, average)
+        self._recal_graph = None
 
     @torch.no_grad()
     def broadcast_parameters(self, src: int = 0):
         if self.reducer and self.world > 1:
             self.reducer.dist.broadcast(self.model.flat_params.data, src, group=self.reducer.group)
             self.reducer.dist.broadcast(self.model.bn_state, src, group=self.reducer.group)
+
+    # ------------------------------------------------------------------ weight averaging
+    def _need_averager(self, what: str) -> WeightAverager:
+        if self.averager is None:
+            raise RuntimeError(f"{what}: this trainer keeps no average (HipTrainer(average='swa' | ('ema', decay)))")
+        if self.averager.p.data_ptr() != self.model.flat_params.data_ptr():
+            self.averager.to(self.model.flat_params.data)      # the model moved (model.to(device)): follow it
+        return self.averager
+
+    def update_average(self):
+        """fold the current parameters into the average (once per epoch under SWA; an EMA is updated by ``step``)"""
+        self._need_averager("update_average").update()
+
+    @torch.no_grad()
+    def swap_in_average(self):
+        """the averaged weights become the model's parameters.  The engine's weight images (Winograd, bf16) are marked
+        stale; Adam's moments stay as they are.  The running BatchNorm statistics still belong to the old weights:
+        ``update_bn`` recomputes them."""
+        self._need_averager("swap_in_average").copy_to(self.model.flat_params.data)
+        self.model.engine.mark_weights_changed()
+
+    @torch.no_grad()
+    def update_bn(self, loader, to_device=None) -> int:
+        """``UNetHIP.update_bn`` in this trainer's precision; with graph=True the statistics-only forward (the device
+        batch count and momentum included) is captured after two eager batches and replayed, one graph per input shape.
+        Distributed: every rank recalibrates on its own batches, then rank 0's statistics are broadcast."""
+        m = self.model
+        k = m.update_bn(loader, precision=m.precision, to_device=to_device,
+                        _run=self._recal_graph_batch if self.use_graph else None)
+        if self.reducer and self.world > 1:
+            self.reducer.dist.broadcast(m.bn_state, 0, group=self.reducer.group)
+        return k
+
+    def _recal_graph_batch(self, x: torch.Tensor, precision: str):
+        m, eng = self.model, self.model.engine
+        key = (tuple(x.shape), precision)
+        g = self._recal_graph
+        if g is None or g["key"] != key:
+            self._recal_graph = g = {"key": key, "warm": 0}
+        if "graph" not in g:
+            if g["warm"] < 2:    # eager warm-up: lazy initialisation (workspaces) must not be captured
+                g["warm"] += 1
+                return m.recalibrate_batch(x, precision)
+            g["x"] = x.clone()
+            eager_ws, eng._ws = eng._ws, {}       # workspaces of the captured pass live (and stay) in the graph's pool
+            graph = torch.cuda.CUDAGraph()
+            try:
+                torch.cuda.synchronize()
+                with torch.cuda.graph(graph):
+                    m.recalibrate_batch(g["x"], precision)
+            finally:
+                g["ws"], eng._ws = eng._ws, eager_ws
+            g["graph"] = graph
+        if x is not g["x"]:
+            g["x"].copy_(x)
+        g["graph"].replay()
 
     def step(self, img: torch.Tensor, mask: torch.Tensor, distmap: Optional[torch.Tensor] = None,
              alpha: float = 1.0):
@@ -184,6 +249,8 @@ class HipTrainer:
             if self.reducer and self.world > 1:
                 self.reducer.dist.all_reduce(skip, op=self.reducer.dist.ReduceOp.MAX, group=self.reducer.group)
             norm = opt.step(grads, grad_scale=1.0 / self.world, skip_flag=skip, capturing=capturing)
+            if self.averager is not None and self.averager.mode == "ema":
+                self._need_averager("step").update(skip_flag=skip, capturing=capturing)
         eng.mark_weights_changed()   # the fused optimiser wrote the flat buffer behind torch's version counter
         self.last = {"loss": loss, "parts": {k: parts[i] for i, k in enumerate(PART_KEYS)}, "grad_norm": norm,
                      "label_error": err, "skipped": skip}
@@ -240,8 +307,52 @@ class _ModuleView:
         return self.model.parameters()
 
 
+@dataclass
+class SWAConfig:
+    """stochastic weight averaging in ``fit``: averaging and the ``SWALR`` schedule start at epoch ``swa_start``;
+    ``swa_lr`` None = the base learning rate"""
+    swa_start: int
+    swa_lr: Optional[float] = None
+    anneal_epochs: int = 10
+    anneal_strategy: str = "cos"
+
+
+def swa_lr(epoch_in_swa: int, lr_at_start: float, swa_lr: float, anneal_epochs: int = 10, strategy: str = "cos") -> float:
+    """closed form of ``torch.optim.swa_utils.SWALR`` stepped once per epoch: ``epoch_in_swa`` = 0 in the first SWA
+    epoch (the rate the schedule before it had reached), ``swa_lr`` from ``anneal_epochs`` on"""
+    if strategy not in ("cos", "linear"):
+        raise ValueError(f"anneal_strategy {strategy!r}: use 'cos' or 'linear'")
+    if epoch_in_swa < 0 or anneal_epochs < 0:
+        raise ValueError("swa_lr: epoch_in_swa and anneal_epochs must not be negative")
+    t = 1.0 if anneal_epochs == 0 else min(1.0, epoch_in_swa / anneal_epochs)
+    a = (1.0 - math.cos(math.pi * t)) / 2.0 if strategy == "cos" else t
+    return swa_lr * a + lr_at_start * (1.0 - a)
+
+
+def resolve_swa(swa, epochs: int, base_lr: float) -> Optional[SWAConfig]:
+    """``fit``'s swa argument -> a checked SWAConfig (None stays None).  True = the defaults Lightning documents for
+    ``stochastic_weight_avg: True``: start at int(0.8 * epochs), 10 annealing epochs, cosine, swa_lr = the base rate."""
+    if swa is None or swa is False:
+        return None
+    cfg = SWAConfig(swa_start=int(0.8 * epochs)) if swa is True else swa
+    if not isinstance(cfg, SWAConfig):
+        raise ValueError(f"fit(swa=...): None, True or an SWAConfig, not {type(swa).__name__}")
+    lr = float(base_lr) if cfg.swa_lr is None else float(cfg.swa_lr)
+    if int(cfg.swa_start) != cfg.swa_start or cfg.swa_start < 0:
+        raise ValueError(f"swa_start {cfg.swa_start!r}: an epoch number >= 0")
+    if cfg.swa_start >= epochs:
+        raise ValueError(f"swa_start {cfg.swa_start} >= epochs {epochs}: nothing would be averaged")
+    if int(cfg.anneal_epochs) != cfg.anneal_epochs or cfg.anneal_epochs < 0:
+        raise ValueError(f"anneal_epochs {cfg.anneal_epochs!r}: an integer >= 0")
+    if not lr >= 0.0:
+        raise ValueError(f"swa_lr {cfg.swa_lr!r} must not be negative")
+    if cfg.anneal_strategy not in ("cos", "linear"):
+        raise ValueError(f"anneal_strategy {cfg.anneal_strategy!r}: use 'cos' or 'linear'")
+    return SWAConfig(int(cfg.swa_start), lr, int(cfg.anneal_epochs), cfg.anneal_strategy)
+
+
 def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: int = 10, to_device=None,
-        on_epoch_end=None, callbacks=None, pl_module=None):
+        on_epoch_end=None, callbacks=None, pl_module=None, swa=None):
     """Minimal stand-in for ``Trainer.fit`` on the hot path (reference deadtrees/train.py:113): per-batch
     ``HipTrainer.step`` and the per-epoch ``CosineAnnealingLR(T_max)`` of segmodel.py:426-428.
 
@@ -249,9 +360,19 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
     every epoch with views of this trainer and of ``pl_module`` (a ``SemSegment``; default: a view of the trainer's model
     with ``encoder_weights`` taken from the model and ``hparams.training`` = learning_rate / cosineannealing_tmax).
     There is no validation loop here, so an encoder put in eval mode stays there (Lightning puts the whole module back
-    in train mode after every validation run)."""
+    in train mode after every validation run).
+
+    swa: None | True | SWAConfig — the loop of torch's SWA documentation on a ``HipTrainer(average="swa")``: epochs before
+    ``swa_start`` keep the cosine schedule (or whatever a callback put in its place); from ``swa_start`` the rate follows
+    ``swa_lr`` (SWALR, annealing from the rate the schedule had reached) and the average is updated at the end of every
+    epoch; after the last epoch the average is swapped in and the BatchNorm statistics are recomputed over ``loader``.
+    The history then carries "swa/n_averaged" per epoch and a final {"swa/bn_batches": k} record."""
     from .network.segmodel import cosine_lr, create_combined_batch
     from .utils.config import to_attrdict
+    swa = resolve_swa(swa, epochs, base_lr)
+    if swa is not None and (getattr(trainer, "averager", None) is None or trainer.averager.mode != "swa"):
+        raise ValueError("fit(swa=...) needs HipTrainer(average='swa')")
+    swa_from = None       # the rate the schedule had reached when SWA took over
     history = []
     sched = {"base_lr": float(base_lr), "t_max": int(t_max), "start": 0}
     tview = _TrainerView(trainer, sched)
@@ -265,7 +386,11 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
         for cb in callbacks or ():
             if hasattr(cb, "on_train_epoch_start"):
                 cb.on_train_epoch_start(tview, pl_module)
-        trainer.opt.lr = cosine_lr(sched["base_lr"], epoch - sched["start"], sched["t_max"])
+        lr = cosine_lr(sched["base_lr"], epoch - sched["start"], sched["t_max"])
+        if swa is not None and epoch >= swa.swa_start:
+            swa_from = lr if swa_from is None else swa_from
+            lr = swa_lr(epoch - swa.swa_start, swa_from, swa.swa_lr, swa.anneal_epochs, swa.anneal_strategy)
+        trainer.opt.lr = lr
         losses = []
         for batch in loader:
             img, mask, distmap, _, _ = create_combined_batch(batch) if isinstance(batch, dict) else batch
@@ -276,6 +401,13 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
             losses.append(trainer.step(img, mask, distmap, alpha=alpha))
         mean = float(torch.stack(losses).mean()) if losses else float("nan")
         history.append({"epoch": epoch, "lr": trainer.opt.lr, "train/total_loss": mean})
+        if swa is not None:
+            if epoch >= swa.swa_start:
+                trainer.update_average()
+            history[-1]["swa/n_averaged"] = trainer.averager.n_averaged
         if on_epoch_end:
             on_epoch_end(history[-1])
+    if swa is not None:
+        trainer.swap_in_average()
+        history.append({"swa/bn_batches": trainer.update_bn(loader, to_device=to_device)})
     return history

@@ -137,6 +137,12 @@ int64_t dt_bn_stats_floats(int P, int C);
 int dt_bn_finalize(float* stats, int P, int C, double count, const float* gamma, const float* beta,
                    float eps, float momentum, float* running_mean, float* running_var,
                    float* mean, float* invstd, float* scale, float* shift, void* stream);
+/* The same kernel with the momentum read from the device (float[1]) when it runs: a captured graph replays with a
+ * momentum that changes every batch (cumulative average, see dt_cma_advance).  Given the same momentum value every
+ * output is bit-identical to dt_bn_finalize. */
+int dt_bn_finalize_dev(float* stats, int P, int C, double count, const float* gamma, const float* beta,
+                       float eps, const float* momentum_dev, float* running_mean, float* running_var,
+                       float* mean, float* invstd, float* scale, float* shift, void* stream);
 /* eval mode: scale/shift from running stats. */
 int dt_bn_eval_affine(const float* gamma, const float* beta, const float* running_mean,
                       const float* running_var, float eps, int C, float* scale, float* shift, void* stream);
@@ -520,6 +526,20 @@ int dt_adam_advance_ranges(double* t_seg, const int64_t* table, int nranges, con
 int dt_adam_step_ranges(float* p, const float* g, float* m, float* v, const int64_t* table, int nranges, int64_t max_len,
                         const float* hyper_seg, double beta1, double beta2, float eps, const float* clipcoef,
                         const int32_t* skip_flag, void* stream);
+
+/* Averaged copy of the flat parameter buffer (torch.optim.swa_utils.AveragedModel).  count_dev (int64[1], device) is
+ * the number of models averaged so far; it is advanced ON the device and the pass that follows reads it:
+ *   DT_AVG_SWA: avg = (count == 0) ? p : avg + (p - avg) / (count + 1)           (get_swa_multi_avg_fn)
+ *   DT_AVG_EMA: avg = (count == 0) ? p : avg + (p - avg) * (1 - decay)           (get_ema_multi_avg_fn)
+ * A set skip_flag (int32[1], as written by dt_clip_coef / dt_skip_from_loss; may be NULL) leaves avg AND the count
+ * untouched.  No host-side value changes between calls: capturable in a HIP graph.  avg, p: 16-byte aligned, n floats. */
+#define DT_AVG_SWA 0
+#define DT_AVG_EMA 1
+int dt_weight_average(float* avg, const float* p, int64_t n, int64_t* count_dev, const int32_t* skip_flag, int mode,
+                      double decay, void* stream);
+/* Cumulative moving average of BatchNorm statistics (torch: momentum=None): n_dev += 1, momentum_dev = 1 / n_dev.
+ * dt_bn_finalize_dev reads that momentum from the device. */
+int dt_cma_advance(int64_t* n_dev, float* momentum_dev, void* stream);
 
 /* ------------------------------------------------------------------ library options */
 /* Kernel-selection switches (host side, process wide; every choice computes the same values):
