@@ -196,6 +196,16 @@ def load() -> C.CDLL:
     return lib
 
 
+def ptr(t):
+    """device address of a tensor for a pointer argument of the ABI (None -> NULL)"""
+    return None if t is None else t.data_ptr()
+
+
+def stream() -> int:
+    """the current torch stream as the ABI's stream argument"""
+    return torch.cuda.current_stream().cuda_stream
+
+
 def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = load().dt_last_error()

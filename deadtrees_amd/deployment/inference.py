@@ -147,15 +147,12 @@ class GraphedTilePredictor:
             eng = self.model.engine
             self._eager(tiles_u8)                      # warm-up: lazy initialisation + weight images packed eagerly
             g = {"inp": tiles_u8.clone()}
-            keep = {k: v for k, v in eng._ws.items() if k.startswith("bf16_w")}
-            eager_ws, eng._ws = eng._ws, keep           # activations / scratch of the capture live in the graph's pool
             graph = torch.cuda.CUDAGraph()
-            try:
+            # activations / scratch of the capture live in the graph's pool; the bf16 weight images packed eagerly stay
+            with eng.capture_workspaces(keep=("bf16_w",)) as g["ws"]:
                 torch.cuda.synchronize()
                 with torch.cuda.graph(graph):
                     g["out"] = self._eager(g["inp"])
-            finally:
-                g["ws"], eng._ws = eng._ws, eager_ws
             g["graph"] = graph
             self._graphs[key] = g
         g["inp"].copy_(tiles_u8)

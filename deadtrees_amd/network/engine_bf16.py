@@ -1,0 +1,727 @@
+"""The bf16 schedule of the U-Net engine: bf16 activations / weight images, fp32 accumulation, fp32 BatchNorm statistics
+and coefficients (the launches of ``engine_core``), fp32 master parameters and gradients.  ``forward_bf16_eval``,
+``forward_bf16_train`` and ``backward_bf16`` with their units; stem and head run in fp32."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import torch
+
+from .bnview import BnView
+from .engine_core import _Saved, _pair
+from .spec import ConvSpec
+
+_BF = torch.bfloat16
+
+
+class Bf16Schedule:
+    # per pass (set by the two forwards): the convolutions write BatchNorm partial sums (training) / the encoder's
+    # coefficients come from its running statistics although they do (frozen encoder in eval mode)
+    _bf16_train = False
+    _bf16_enc_eval = False
+
+    # ------------------------------------------------------------------ convolution launches
+    def _bf16_mt(self, desc) -> int:
+        """kernel family dt_conv2d_bf16 picks for `desc`: 8 = LDS-DMA staged (conv_bf16_dma.hip), 16 = lean narrow-layer
+        kernel (conv_bf16_narrow.hip), else the register-staged kernels' tile multiplier"""
+        tw, tn, ck, mt = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        if self.lib.dt_conv2d_bf16_config(C.byref(desc), C.byref(tw), C.byref(tn), C.byref(ck), C.byref(mt)) != 0:
+            return -1
+        return mt.value
+
+    def _uses_dma_kernel(self, desc) -> bool:
+        """the LDS-DMA staged kernels (reported as mt == 8) read the CHUNKED weight images"""
+        return self._bf16_mt(desc) == 8
+
+    def _conv_bf16(self, desc, src0, src1, w, out0, out1, stats, in_ss, w_chunked=None):
+        if w_chunked is not None and self._uses_dma_kernel(desc):
+            w = w_chunked
+        e0 = self._pb()
+        self._call("dt_conv2d_bf16", desc, src0, src1, w, out0, out1, stats, *_pair(in_ss))
+        if e0 is not None:
+            tw, tn, ck, mt = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+            self.lib.dt_conv2d_bf16_config(C.byref(desc), C.byref(tw), C.byref(tn), C.byref(ck), C.byref(mt))
+            if mt.value == 8:     # the LDS-DMA staged 512-pixel kernel (conv_bf16_dma.hip)
+                name = f"conv3x3_bf16_dma_kernel<{'true' if in_ss else 'false'}, {2 if desc.accumulate else 0}>"
+            elif mt.value == 16:  # the lean narrow-layer kernel (conv_bf16_narrow.hip)
+                name = (f"conv3x3_bf16_narrow_kernel<{desc.C0 // 16}, {desc.Cout // 16}, "
+                        f"{'true' if in_ss else 'false'}, false>")
+            else:
+                name = (f"conv_fwd_bf16_kernel<{desc.ksize}, {desc.stride}, {tw.value}, {tn.value}, {ck.value}, "
+                        f"{mt.value}, {'true' if in_ss else 'false'}>")
+            self._pe(e0, name, *self._conv_work(desc, 2))
+
+    def _stem_bf16(self, x, params, y, stats, B, H, W, Cin):
+        """7x7/2 stem of the bf16 path into `y` (bf16) with optional BatchNorm partial statistics -> stat rows P.
+        Even tiles wider than 32 pixels run on the bf16 MFMA kernels through the 2x2 space-to-depth image
+        (dt_stem_s2d_bf16 + a 4x4 window: K = 256 bf16 instead of 147 fp32); anything else on the fp32 stem kernel."""
+        lib, stc = self.lib, self.spec.stem
+        w7 = stc.w(params)
+        h, w_ = y.shape[1], y.shape[2]
+        if H % 2 == 0 and W % 2 == 0 and w_ > 16 and stc.cout % 64 == 0 and stc.k == 7 and stc.stride == 2:
+            s2d = torch.empty((B, h, w_, 16), dtype=_BF, device=x.device)
+            self._call("dt_stem_s2d_bf16", x, s2d, B, H, W, Cin)
+            wp = self._buf("stem_w4", 16 * stc.cout * 16, dtype=_BF, device=x.device)
+            self._call("dt_stem_pack_weights_bf16", w7, wp, Cin, stc.cout)
+            desc = self._desc(B, h, w_, 16, 0, 0, h, w_, stc.cout, 4, 1, 2)
+            P = lib.dt_conv2d_bf16_stat_rows(C.byref(desc))
+            sbuf = self._buf("bn_stats", lib.dt_bn_stats_floats(P, stc.cout), device=x.device) if stats else None
+            self._conv_bf16(desc, s2d, None, wp, y, None, sbuf, None)
+            self._stem_s2d = s2d if stats else None     # training: the weight gradient reuses the image
+            return P, sbuf
+        sdesc = self._desc(B, H, W, Cin, 0, 0, h, w_, stc.cout, stc.k, stc.stride, stc.pad)
+        P = lib.dt_conv2d_stat_rows(C.byref(sdesc))
+        sbuf = self._buf("bn_stats", lib.dt_bn_stats_floats(P, stc.cout), device=x.device) if stats else None
+        self._call("dt_conv2d_out_bf16", sdesc, x, w7, y, sbuf)
+        self._stem_s2d = None
+        return P, sbuf
+
+    # ------------------------------------------------------------------ forward units (both forwards)
+    def _bn_coeffs_bf16(self, c: ConvSpec, params, bn: BnView, stats, P, count):
+        """(scale, shift) of conv c for this pass: from its running statistics (inference, an encoder in eval mode — the
+        batch sums of its convolutions are not used), else from the batch statistics"""
+        if not self._bf16_train or (self._bf16_enc_eval and c.index in self._enc_index):
+            return self._bn_eval_affine(c, params, bn)
+        return self._bn_finalize(c, params, bn, stats, P, count)
+
+    def _conv_bn_bf16(self, c: ConvSpec, params, bn: BnView, src0, src1, mode0, B, Hin, Win, in_ss=None):
+        """y = conv(x) in bf16 (+ BatchNorm partial statistics when training) -> y, Ho, Wo, (scale, shift)"""
+        desc = self._conv_desc(c, src0, src1, mode0, B, Hin, Win)
+        stats = P = None
+        if self._bf16_train:
+            P = self._rows("dt_conv2d_bf16_stat_rows", desc)
+            stats = self._buf("bn_stats", self.lib.dt_bn_stats_floats(P, c.cout), device=src0.device)
+        y = torch.empty((B, desc.Ho, desc.Wo, c.cout), dtype=_BF, device=src0.device)
+        wb, wbc = self._wb
+        self._conv_bf16(desc, src0, src1, c.w(wb), y, None, stats, in_ss, w_chunked=c.w(wbc))
+        return y, desc.Ho, desc.Wo, self._bn_coeffs_bf16(c, params, bn, stats, P, B * desc.Ho * desc.Wo)
+
+    def _bn_act_bf16(self, y, ss, res=None, res_ss=None, y_f32=False, of: Optional[ConvSpec] = None):
+        """of: the convolution whose normalise pass this is (recalibration launch record)"""
+        Bq, Hq, Wq, Cq = y.shape
+        z = torch.empty((Bq, Hq, Wq, Cq), dtype=_BF, device=y.device)
+        self._rec_act(of)
+        e0 = self._pb() if self._bf16_train else None      # the inference roofline lists the convolutions only
+        self._call("dt_bn_act_bf16", y, 1 if y_f32 else 0, ss[0], ss[1], res, *_pair(res_ss), z, Bq * Hq * Wq, Cq, 1)
+        self._pe(e0, "bn_act_bf16_kernel", 0.0, 2.0 * y.numel() * (2 + (res is not None)))
+        return z
+
+    def _resunet_join_bf16(self, blk, params, d, skip, y2, ss2, B, H, W):
+        """ResUnet decoder block output under AMP: bf16(relu(y2 * scale2 + shift2) + identity_conv(up(d) | skip) + bias) —
+        the 1x1 identity convolution over the virtual (up-sampled, concatenated) input on the bf16 kernels, the join in
+        dt_bn_act_bf16 (relu = 2: ReLU on the main branch only)"""
+        ic, dev = blk.idc, y2.device
+        idy = torch.empty((B, H, W, ic.cout), dtype=_BF, device=dev)
+        self._conv_bf16(self._conv_desc(ic, d, skip, 1, B, H, W), d, skip, ic.w(self._wb[0]), idy, None, None, None)
+        out = torch.empty((B, H, W, ic.cout), dtype=_BF, device=dev)
+        self._call("dt_bn_act_bf16", y2, 0, ss2[0], ss2[1], idy, self._const_vec(1.0, ic.cout, dev), ic.bias(params), out,
+                   B * H * W, ic.cout, 2)
+        return out
+
+    def _encoder_block_bf16(self, blk, params, bn: BnView, xin, B, ch, cw, z1_stored: bool, keep: bool):
+        """one resnet block -> (record for backward if `keep`, output, Ho, Wo); z1_stored: conv1's activation is
+        materialised"""
+        y1, h1, w1, ss1 = self._conv_bn_bf16(blk.conv1, params, bn, xin, None, 0, B, ch, cw)
+        z1 = self._bn_act_bf16(y1, ss1, of=blk.conv1) if z1_stored else None
+        y2, h2, w2, ss2 = self._conv_bn_bf16(blk.conv2, params, bn, y1 if z1 is None else z1, None, 0, B, h1, w1,
+                                             in_ss=ss1 if z1 is None else None)
+        if blk.down is not None:
+            yd, _, _, ssd = self._conv_bn_bf16(blk.down, params, bn, xin, None, 0, B, ch, cw)
+            out = self._bn_act_bf16(y2, ss2, res=yd, res_ss=ssd, of=blk.conv2)
+        else:
+            yd = None
+            out = self._bn_act_bf16(y2, ss2, res=xin, of=blk.conv2)
+        rec = dict(x=xin, y1=y1, z1=z1, y2=y2, yd=yd, out=out, Hin=ch, Win=cw, H=h2, W=w2) if keep else None
+        return rec, out, h2, w2
+
+    def _forward_unetpp_bf16(self, feats, params, bn: BnView, B, sv: Optional[_Saved]):
+        """smp UnetPlusPlus under AMP (fp32 twin: _forward_unetpp): every node = DecoderBlock(up x2 of its lower node, cat of
+        the nodes / encoder feature on its level); node outputs are stored bf16 activations (several consumers), conv2
+        reads conv1's raw output with BatchNorm + ReLU applied while staging"""
+        sp = self.spec
+        nodes = {f"f{k}": feats[4 - k] for k in range(5)}
+        for blk in sp.decoder:
+            low = nodes[blk.low]
+            skip, parts = (None, []) if not blk.cat else self._cat_channels([nodes[n] for n in blk.cat])
+            y1, h1, w1, ss1 = self._conv_bn_bf16(blk.conv1, params, bn, low, skip, 1, B, 2 * low.shape[1], 2 * low.shape[2])
+            y2, h2, w2, ss2 = self._conv_bn_bf16(blk.conv2, params, bn, y1, None, 0, B, h1, w1, in_ss=ss1)
+            z2 = self._bn_act_bf16(y2, ss2, of=blk.conv2)
+            if sv is not None:
+                sv.d["P" + blk.name] = dict(x=low, skip=skip, parts=parts, y1=y1, y2=y2, z2=z2, H=h1, W=w1)
+            nodes[blk.name] = z2
+        return nodes[sp.decoder[-1].name]
+
+    # ------------------------------------------------------------------ bf16 inference leg
+    def forward_bf16_eval(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor,
+                          want_argmax: Optional[str] = None):
+        """eval-mode forward with bf16 activations/weights and fp32 accumulation (stem and head stay fp32)."""
+        sp = self.spec
+        if x_nchw.dim() != 4 or x_nchw.shape[1] != sp.in_channels:
+            raise RuntimeError(f"expected input [B,{sp.in_channels},H,W], got {tuple(x_nchw.shape)}")
+        B, Cin, H, W = x_nchw.shape
+        if H % 32 or W % 32:
+            raise RuntimeError(f"H and W must be divisible by 32 (encoder depth 5), got {H}x{W}")
+        self._bf16_train, self._bf16_enc_eval = False, False
+        dev = x_nchw.device
+        self._wb = (self._bf16_weights(params), self._bf16_weights(params, chunked=True))
+        bnws = self._buf("bnws", BnView.ws_floats(sp), device=dev)
+        bn = BnView(sp, bnws, bnstate)
+        akey = (params.data_ptr(), params._version, self._weights_epoch, bnstate.data_ptr(), bnstate._version,
+                self._bn_epoch, bnws.data_ptr())
+        # same coefficients as the previous inference call: skip 46 launches
+        self._affine_fresh = self._ws.get("affine_key") == akey
+        self._ws["affine_key"] = akey
+
+        x = torch.empty((B, H, W, Cin), dtype=torch.float32, device=dev)
+        self._call("dt_nchw_to_nhwc", x_nchw.contiguous(), x, B, Cin, H, W)
+        # stem: bf16 MFMA over the space-to-depth image (fp32-MFMA kernel for odd / tiny tiles), bf16 output
+        stc = sp.stem
+        h, w_ = stc.out_size(H), stc.out_size(W)
+        y = torch.empty((B, h, w_, stc.cout), dtype=_BF, device=dev)
+        self._stem_bf16(x, params, y, False, B, H, W, Cin)
+        f1 = self._bn_act_bf16(y, self._bn_eval_affine(stc, params, bn))
+        hp, wp = (h + 2 - 3) // 2 + 1, (w_ + 2 - 3) // 2 + 1
+        pool = torch.empty((B, hp, wp, 64), dtype=_BF, device=dev)
+        self._call("dt_maxpool3x3s2_bf16", f1, pool, B, h, w_, 64)
+        feats = [f1]
+        cur, ch, cw = pool, hp, wp
+        for blocks in sp.layers:
+            for blk in blocks:
+                _, cur, ch, cw = self._encoder_block_bf16(blk, params, bn, cur, B, ch, cw, z1_stored=False, keep=False)
+            feats.append(cur)
+        d, dh, dw, d_ss = feats[4], ch, cw, None
+        skips = [feats[3], feats[2], feats[1], feats[0], None]
+        if sp.decoder_kind == "unetplusplus":      # dense decoder: node outputs are stored tensors
+            d = self._forward_unetpp_bf16(feats, params, bn, B, None)
+            dh, dw = d.shape[1], d.shape[2]
+        for i, blk in enumerate(sp.decoder if sp.decoder_kind != "unetplusplus" else ()):
+            y1, h1, w1, ss1 = self._conv_bn_bf16(blk.conv1, params, bn, d, skips[i], 1, B, 2 * dh, 2 * dw, in_ss=d_ss)
+            y2, h2, w2, ss2 = self._conv_bn_bf16(blk.conv2, params, bn, y1, None, 0, B, h1, w1, in_ss=ss1)
+            if sp.decoder_kind == "resunet":     # relu(bn2(conv2(.))) + identity_conv(up + skip) (resunet/decoder.py:40-52)
+                d, d_ss = self._resunet_join_bf16(blk, params, d, skips[i], y2, ss2, B, h2, w2), None
+                dh, dw = h2, w2
+                continue
+            if i == len(sp.decoder) - 1:
+                d, d_ss = self._bn_act_bf16(y2, ss2), None
+            else:
+                d, d_ss = y2, ss2
+            dh, dw = h2, w2
+        hd = sp.head
+        K = hd.cout
+        logits = torch.empty((B, K, dh, dw), dtype=torch.float32, device=dev)
+        am64 = torch.empty((B, dh, dw), dtype=torch.int64, device=dev) if want_argmax == "int64" else None
+        am8 = torch.empty((B, dh, dw), dtype=torch.uint8, device=dev) if want_argmax == "uint8" else None
+        self._call("dt_head_fwd_bf16", d, hd.w(params), hd.bias(params), logits, am64, am8, B, dh, dw, hd.cin, K)
+        return logits, (am64 if am64 is not None else am8)
+
+    # ------------------------------------------------------------------ bf16 training (BASELINE configs[2])
+    def forward_bf16_train(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor,
+                           enc_training: bool = True, enc_frozen: bool = False, recal: Optional[torch.Tensor] = None):
+        """training-mode forward with bf16 activations / weights, fp32 accumulation, fp32 BatchNorm statistics
+        (taken from the accumulators), fp32 master parameters.  Stem and head run in fp32.
+        enc_frozen: the encoder's weights get no gradient — nothing of it is saved; enc_training=False (only with a
+        frozen encoder here: the bf16 path has no frozen-statistics BatchNorm backward) normalises the encoder with its
+        running statistics, which stay untouched.
+        recal: device float[1] momentum -> BatchNorm recalibration pass, see `forward`: the same kernels on the same
+        data as the training forward, nothing kept for backward (`self.saved` stays as it was), Unet: returns None after
+        the last BatchNorm's statistics."""
+        sp = self.spec
+        self._recal = None
+        if recal is not None:
+            if enc_frozen or not enc_training:
+                raise RuntimeError("recalibration forward: every BatchNorm layer runs on batch statistics")
+            if recal.dtype != torch.float32 or recal.device != x_nchw.device:
+                raise RuntimeError("recalibration forward: the momentum is a float32 tensor on the input's device")
+            self._recal, self.recal_launches = recal, []
+        if not enc_training and not enc_frozen:
+            raise NotImplementedError("bf16: an encoder in eval mode trains only with frozen weights "
+                                      "(model.encoder.requires_grad_(False)); use fp32 for trainable weights on "
+                                      "running statistics")
+        B, Cin, H, W = x_nchw.shape
+        if H % 32 or W % 32 or Cin != sp.in_channels:
+            raise RuntimeError(f"bad input {tuple(x_nchw.shape)}")
+        self._bf16_train, self._bf16_enc_eval = True, not enc_training
+        self._affine_fresh = False   # an eval-mode encoder's coefficients are computed in every pass
+        dev = x_nchw.device
+        self._bn_epoch += 1          # running statistics are rewritten on the device (invalidates cached eval affines)
+        if self._bf16_images_fused:
+            self._bf16_weights_all(params)
+        self._wb = (self._bf16_weights(params), self._bf16_weights(params, chunked=True))
+        sv = _Saved()
+        bnws = torch.empty(BnView.ws_floats(sp), dtype=torch.float32, device=dev)
+        sv.d["bnws"] = bnws
+        bn = BnView(sp, bnws, bnstate)
+
+        x = torch.empty((B, H, W, Cin), dtype=torch.float32, device=dev)
+        self._call("dt_nchw_to_nhwc", x_nchw.contiguous(), x, B, Cin, H, W)
+        # stem: bf16 MFMA over the space-to-depth image (fp32-MFMA kernel for odd / tiny tiles), fp32 statistics
+        stc = sp.stem
+        h, w_ = stc.out_size(H), stc.out_size(W)
+        ystem = torch.empty((B, h, w_, stc.cout), dtype=_BF, device=dev)
+        Pst, sstats = self._stem_bf16(x, params, ystem, True, B, H, W, Cin)
+        ss = self._bn_coeffs_bf16(stc, params, bn, sstats, Pst, B * h * w_)
+        f1 = self._bn_act_bf16(ystem, ss, of=stc)
+        if not enc_frozen:
+            sv.d["stem"] = dict(x=x, y=ystem, z=f1, Hin=H, Win=W, s2d=self._stem_s2d)
+        self._stem_s2d = None
+        hp, wp = (h + 2 - 3) // 2 + 1, (w_ + 2 - 3) // 2 + 1
+        pool = torch.empty((B, hp, wp, 64), dtype=_BF, device=dev)
+        amax = torch.empty((B, hp, wp, 64), dtype=torch.uint8, device=dev)
+        self._call("dt_maxpool3x3s2_bf16_amax", f1, pool, amax, B, h, w_, 64)
+        if not enc_frozen:
+            sv.d["pool"] = dict(amax=amax, H=h, W=w_)
+        self._tr("pool", pool)
+        feats = [f1]
+        cur, ch, cw = pool, hp, wp
+        for li, blocks in enumerate(sp.layers):
+            for bi, blk in enumerate(blocks):
+                # conv1's activation is stored: A/B switch DT_BF16_MAT_Z1 (see __init__)
+                rec, cur, ch, cw = self._encoder_block_bf16(blk, params, bn, cur, B, ch, cw, z1_stored=self._mat_z1_bf16,
+                                                            keep=not enc_frozen)
+                if rec is not None:
+                    sv.d[f"L{li}B{bi}"] = rec
+            feats.append(cur)
+        d, dh, dw, d_ss = feats[4], ch, cw, None
+        skips = [feats[3], feats[2], feats[1], feats[0], None]
+        if sp.decoder_kind == "unetplusplus":
+            d = self._forward_unetpp_bf16(feats, params, bn, B, sv)
+            dh, dw = d.shape[1], d.shape[2]
+        for i, blk in enumerate(sp.decoder if sp.decoder_kind != "unetplusplus" else ()):
+            if sp.decoder_kind == "resunet":
+                # reference network/extra/resunet/decoder.py:40-52 under AMP: conv1 -> conv2 (conv-BN-ReLU each, both
+                # activations virtual) + the 1x1 identity_conv (bias) of the up-sampled + concatenated input; no activation
+                # after the sum; the block output is a stored bf16 tensor
+                y1, h1, w1, ss1 = self._conv_bn_bf16(blk.conv1, params, bn, d, skips[i], 1, B, 2 * dh, 2 * dw)
+                y2, h2, w2, ss2 = self._conv_bn_bf16(blk.conv2, params, bn, y1, None, 0, B, h1, w1, in_ss=ss1)
+                out = self._resunet_join_bf16(blk, params, d, skips[i], y2, ss2, B, h2, w2)
+                self._tr(f"D{i}.out", out)
+                sv.d[f"D{i}"] = dict(x=d, skip=skips[i], y1=y1, y2=y2, H=h1, W=w1)
+                d, dh, dw, d_ss = out, h2, w2, None
+                continue
+            y1, h1, w1, ss1 = self._conv_bn_bf16(blk.conv1, params, bn, d, skips[i], 1, B, 2 * dh, 2 * dw, in_ss=d_ss)
+            # round 3: the activations of the 64+-channel decoder blocks are stored (bn_act, 4 B per element moved) so that
+            # conv2 / the next conv1 AND their weight gradients run the pure LDS-DMA kernels (a DMA cannot transform);
+            # with the register-staged weight gradient this was neutral (2,236 vs 2,234), DT_BF16_MAT_DEC=0 restores it
+            wide = self._mat_dec_bf16 and blk.conv2.cout % 64 == 0
+            z1 = self._bn_act_bf16(y1, ss1, of=blk.conv1) if wide else None
+            y2, h2, w2, ss2 = self._conv_bn_bf16(blk.conv2, params, bn, y1 if z1 is None else z1, None, 0, B, h1, w1,
+                                                 in_ss=ss1 if z1 is None else None)
+            if recal is not None and i == len(sp.decoder) - 1:
+                self._recal = None              # every BatchNorm's statistics are final: nothing else to launch
+                return None
+            if i == len(sp.decoder) - 1 or wide:
+                z2 = self._bn_act_bf16(y2, ss2, of=blk.conv2)
+                nxt, nxt_ss = z2, None
+            else:
+                z2 = None
+                nxt, nxt_ss = y2, ss2
+            sv.d[f"D{i}"] = dict(x=d, x_virtual=d_ss is not None, skip=skips[i], y1=y1, z1=z1, y2=y2, z2=z2, H=h1, W=w1)
+            d, dh, dw, d_ss = nxt, h2, w2, nxt_ss
+        hd = sp.head
+        K = hd.cout
+        logits = torch.empty((B, K, dh, dw), dtype=torch.float32, device=dev)
+        if recal is not None:
+            self.recal_launches.append(("head", hd.key))
+        self._call("dt_head_fwd_bf16", d, hd.w(params), hd.bias(params), logits, None, None, B, dh, dw, hd.cin, K)
+        if recal is not None:       # nothing of this pass is for a backward
+            self._recal = None
+            return logits
+        sv.d["head"] = dict(x=d, H=dh, W=dw)
+        sv.d["B"] = B
+        sv.d["bf16"] = True
+        sv.d["enc_frozen"] = bool(enc_frozen)
+        self.saved = sv
+        return logits
+
+    # ------------------------------------------------------------------ backward units
+    def _bn_bwd_bf16(self, c: ConvSpec, params, grads, bn: BnView, dout, out_act, y, dres=None, dres_acc=False,
+                     virtual_act=False, reduced=None):
+        """fp32 twin: _bn_bwd.  reduced = (red, P): the partial sums came out of the kernel that wrote dout"""
+        Bq, Hq, Wq, Cq = y.shape
+        n_pix = Bq * Hq * Wq
+        mean, invstd = bn.mean(c), bn.invstd(c)
+        asc, ash = bn.ss(c) if virtual_act else (None, None)
+        if reduced is not None:
+            red, P = reduced
+        else:
+            P = self.lib.dt_bn_bwd_rows_bf16(n_pix)
+            red = self._buf("bn_red", self.lib.dt_bn_stats_floats(P, Cq), device=y.device)
+            e0 = self._pb()
+            self._call("dt_bn_bwd_reduce_bf16", dout, out_act, y, mean, invstd, asc, ash, red, n_pix, Cq)
+            self._pe(e0, "bn_bwd_reduce_bf16_kernel", 0.0, 2.0 * y.numel() * (2 + (out_act is not None)))
+        dy = torch.empty(y.shape, dtype=_BF, device=y.device)
+        e0 = self._pb()
+        self._call("dt_bn_bwd_apply_bf16", dout, out_act, y, mean, invstd, c.gamma(params), asc, ash, red, P,
+                   c.gamma(grads), c.beta(grads), dy, dres, 1 if dres_acc else 0, n_pix, Cq)
+        self._pe(e0, "bn_bwd_apply_bf16_kernel", 0.0,
+                 2.0 * y.numel() * (3 + (out_act is not None) + (dres is not None) * (2 if dres_acc else 1)))
+        return dy
+
+    def _wgrad_bf16(self, c: ConvSpec, grads, src0, src1, mode0, B, Hin, Win, dy, in_ss=None, side=True):
+        if side:
+            self.launches["wgrad"].append(c.key)
+        if side and self.overlap_wgrad_bf16:
+            self._on_side(lambda: self._wgrad_bf16(c, grads, src0, src1, mode0, B, Hin, Win, dy, in_ss, side=False),
+                          src0, src1, dy)
+            return
+        C0 = src0.shape[-1]
+        C1 = 0 if src1 is None else src1.shape[-1]
+        desc = self._desc(B, Hin, Win, C0, C1, mode0, dy.shape[1], dy.shape[2], c.cout, c.k, c.stride, c.pad)
+        nbytes = self._rows("dt_conv2d_wgrad_bf16_workspace", desc)
+        ws = self._buf("wgrad_ws", nbytes // 4, device=dy.device)
+        e0 = self._pb()
+        self._call("dt_conv2d_wgrad_bf16", desc, src0, src1, dy, c.w(grads), ws, ws.numel() * 4, *_pair(in_ss))
+        if e0 is not None:      # + the fp32 gradient out
+            self._pe(e0, "conv_wgrad_bf16_kernel (+ split-K final)", *self._conv_work(desc, 2, 2.0 * c.w_size))
+
+    def _dgrad_bn_bf16(self, c: ConvSpec, dy, B, Hh, Ww, out0, bn_conv: ConvSpec, y, bn: BnView, act=None):
+        """stride-1 data gradient of conv c with the BatchNorm-backward reduction of bn_conv fused (fp32 twin:
+        _dgrad_bn; act = stored block output -> gradient join) -> (red, P)"""
+        Cq = bn_conv.cout
+        self.launches["dgrad"].append(c.key)
+        desc = self._desc(B, Hh, Ww, c.cout, 0, 0, Hh, Ww, c.cin, c.k, 1, c.k - 1 - c.pad, 0, 0 if act is None else 1)
+        P = self.lib.dt_conv2d_bf16_stat_rows(C.byref(desc))
+        red = self._buf("bn_red_fused", self.lib.dt_bn_stats_floats(P, Cq), device=dy.device)
+        fuse = bn.fuse(bn_conv, y, act)
+        dma = self._uses_dma_kernel(desc)
+        e0 = self._pb()
+        self._call("dt_conv2d_bf16_bn_bwd", desc, dy, c.w(self._wbd[1] if dma else self._wbd[0]), out0, red, fuse)
+        if e0 is not None:
+            narrow = self._bf16_mt(desc) == 16
+            self._pe(e0, f"conv3x3_bf16_dma_kernel<false, {1 if act is None else 3}>" if dma else
+                     (f"conv3x3_bf16_narrow_kernel<{desc.C0 // 16}, {desc.Cout // 16}, false, true>" if narrow else
+                      "conv_fwd_bf16_kernel (data gradient + BatchNorm-backward sums)"),
+                     *self._conv_work(desc, 2, 2.0 * out0.numel()))
+        return red, P
+
+    def _dgrad_bf16(self, c: ConvSpec, dy, B, Hin, Win, out0, out1=None, split=0, acc=False):
+        self.launches["dgrad"].append(c.key)
+        Ho, Wo = dy.shape[1], dy.shape[2]
+        pad = c.k - 1 - c.pad
+        if c.stride == 1:
+            desc = self._desc(B, Ho, Wo, c.cout, 0, 0, Hin, Win, c.cin, c.k, 1, pad, split, 1 if acc else 0)
+        else:
+            desc = self._desc(B, Hin, Win, c.cout, 0, 2, Hin, Win, c.cin, c.k, 1, pad, split, 1 if acc else 0)
+        self._conv_bf16(desc, dy, None, c.w(self._wbd[0]), out0, out1, None, None, w_chunked=c.w(self._wbd[1]))
+
+    # ------------------------------------------------------------------ the three decoders, reversed
+    def _backward_unetpp_bf16(self, S, G, params, grads, bn: BnView, B, skip_grads, dev):
+        """reverse of the dense decoder (fp32 twin: _backward_unetpp): blocks in reverse forward order; a node's gradient is
+        the sum over its consumers — as the up-sampled input of the block to its right (accumulating 2x2 sums) and as a
+        slice of the concatenated skip of the blocks further right (accumulating slice copies), one rounding each.
+        G: {node name: gradient so far}, on entry the last node's (the caller lets go of it: it is freed once consumed).
+        Fills skip_grads (gradients of f1..f4) and returns the gradient of f5."""
+        sp = self.spec
+
+        def slot(name, shape):
+            t = G.get(name)
+            if t is None:
+                t = G[name] = torch.empty(shape, dtype=_BF, device=dev)
+                return t, 0
+            return t, 1
+
+        for blk in reversed(sp.decoder):
+            d = S["P" + blk.name]
+            g = G.pop(blk.name)
+            self._tr(f"P{blk.name}.g", g)
+            Hh, Ww = d["H"], d["W"]
+            dy2 = self._bn_bwd_bf16(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True)
+            self._tr(f"P{blk.name}.dy2", dy2)
+            del g
+            self._wgrad_bf16(blk.conv2, grads, d["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
+            dz1 = torch.empty(d["y1"].shape, dtype=_BF, device=dev)
+            red1 = self._dgrad_bn_bf16(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, d["y1"], bn)
+            del dy2
+            self._tr(f"P{blk.name}.dz1", dz1)
+            dy1 = self._bn_bwd_bf16(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
+            self._tr(f"P{blk.name}.dy1", dy1)
+            del dz1
+            self._wgrad_bf16(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1)
+            cx = blk.in_ch
+            dup = torch.empty((B, Hh, Ww, cx), dtype=_BF, device=dev)
+            dskip = None
+            if d["skip"] is not None:
+                dskip = torch.empty(d["skip"].shape, dtype=_BF, device=dev)
+                self._dgrad_bf16(blk.conv1, dy1, B, Hh, Ww, dup, dskip, split=cx)
+                self._tr(f"P{blk.name}.dskip", dskip)
+            else:
+                self._dgrad_bf16(blk.conv1, dy1, B, Hh, Ww, dup)
+            self._tr(f"P{blk.name}.dup", dup)
+            del dy1
+            glow, acc = slot(blk.low, d["x"].shape)
+            self._call("dt_upsample2x_bwd_acc_bf16", dup, glow, acc, B, Hh // 2, Ww // 2, cx)
+            del dup
+            if dskip is not None:
+                Cw = dskip.shape[-1]
+                for name, (off, Cn) in zip(blk.cat, d["parts"]):
+                    if len(blk.cat) == 1 and name not in G:
+                        G[name] = dskip                      # the skip was the tensor itself: its gradient as is
+                        continue
+                    gm, acc = slot(name, (B, Hh, Ww, Cn))
+                    self._call("dt_channel_slice_bf16", dskip, gm, B * Hh * Ww, Cn, Cw, off, 0, acc)
+            S["P" + blk.name] = None
+        for k in range(1, 5):
+            skip_grads[4 - k] = G[f"f{k}"]      # f_k of the decoder = feats[4 - k]
+            self._tr(f"Pf{k}.g", G[f"f{k}"])
+        self._tr("Pf0.g", G["f0"])
+        return G["f0"]
+
+    def _backward_resunet_block_bf16(self, i, blk, d, g, params, grads, bn: BnView, B, skip_grads):
+        """reverse of one ResUnet block (fp32 twin: _backward_resunet_block): g = gradient of the block output -> the
+        gradient of the block's low-resolution input; writes the skip gradient"""
+        lib, dev = self.lib, g.device
+        Hh, Ww = d["H"], d["W"]
+        ic, cx = blk.idc, blk.in_ch
+        sk = 0 if d["skip"] is None else d["skip"].shape[-1]
+        n_pix = B * Hh * Ww
+        self._wgrad_bf16(ic, grads, d["x"], d["skip"], 1, B, Hh, Ww, g)     # identity branch: dW over the virtual input
+        cws = self._buf("chsum_ws", int(lib.dt_channel_sums_bf16_workspace(n_pix, ic.cout)), device=dev)
+        self._call("dt_channel_sums_bf16", g, cws, n_pix, ic.cout, ic.bias(grads))      # its bias gradient = sum g
+        # main branch: both activations virtual
+        dy2 = self._bn_bwd_bf16(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True)
+        self._tr(f"D{i}.dy2", dy2)
+        self._wgrad_bf16(blk.conv2, grads, d["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
+        dz1 = torch.empty(d["y1"].shape, dtype=_BF, device=dev)
+        red1 = self._dgrad_bn_bf16(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, d["y1"], bn)
+        del dy2
+        self._tr(f"D{i}.dz1", dz1)
+        dy1 = self._bn_bwd_bf16(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
+        self._tr(f"D{i}.dy1", dy1)
+        del dz1
+        self._wgrad_bf16(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1)
+        dup = torch.empty((B, Hh, Ww, cx), dtype=_BF, device=dev)
+        dup_id = torch.empty((B, Hh, Ww, cx), dtype=_BF, device=dev)
+        one = self._const_vec(1.0, max(cx, sk, 8), dev)
+        zero = self._const_vec(0.0, max(cx, sk, 8), dev)
+        if sk:
+            dskip = torch.empty(d["skip"].shape, dtype=_BF, device=dev)
+            dskip_id = torch.empty(d["skip"].shape, dtype=_BF, device=dev)
+            self._dgrad_bf16(blk.conv1, dy1, B, Hh, Ww, dup, dskip, split=cx)
+            self._dgrad_bf16(ic, g, B, Hh, Ww, dup_id, dskip_id, split=cx)
+            # gradient of the skip feature = the two branches' parts, one rounding
+            self._call("dt_bn_act_bf16", dskip, 0, one, zero, dskip_id, None, None, dskip, n_pix, sk, 0)
+            skip_grads[3 - i] = dskip
+            self._tr(f"D{i}.dskip", dskip)
+            del dskip_id
+        else:
+            self._dgrad_bf16(blk.conv1, dy1, B, Hh, Ww, dup)
+            self._dgrad_bf16(ic, g, B, Hh, Ww, dup_id)
+        del dy1
+        self._call("dt_bn_act_bf16", dup, 0, one, zero, dup_id, None, None, dup, n_pix, cx, 0)
+        del dup_id
+        self._tr(f"D{i}.dup", dup)
+        gx = torch.empty(d["x"].shape, dtype=_BF, device=dev)
+        self._call("dt_upsample2x_bwd_bf16", dup, gx, B, Hh // 2, Ww // 2, cx)
+        del dup
+        self._tr(f"D{i}.g", gx)
+        return gx
+
+    def _backward_unet_block_bf16(self, i, S, g, g_red, params, grads, bn: BnView, B, frozen, skip_grads):
+        """reverse of one smp Unet decoder block: g = gradient of its (possibly virtual) output activation, g_red the
+        BatchNorm-backward sums that came with it -> (gradient of the block below's activation, its sums or None)"""
+        sp, lib, dev = self.spec, self.lib, g.device
+        blk, d = sp.decoder[i], S[f"D{i}"]
+        Hh, Ww = d["H"], d["W"]
+        # the ReLU mask is recomputed from y2 * scale + shift even where z2 was stored (same arithmetic as bn_act:
+        # identical mask, one tensor less to read in the reduce / apply passes)
+        dy2 = self._bn_bwd_bf16(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True, reduced=g_red)
+        self._tr(f"D{i}.dy2", dy2)
+        if d.get("z1") is not None:
+            self._wgrad_bf16(blk.conv2, grads, d["z1"], None, 0, B, Hh, Ww, dy2)
+        else:
+            self._wgrad_bf16(blk.conv2, grads, d["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
+        dz1 = torch.empty(d["y1"].shape, dtype=_BF, device=dev)
+        red1 = self._dgrad_bn_bf16(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, d["y1"], bn)
+        del dy2
+        self._tr(f"D{i}.dz1", dz1)
+        dy1 = self._bn_bwd_bf16(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
+        self._tr(f"D{i}.dy1", dy1)
+        del dz1
+        x_ss = bn.ss(sp.decoder[i - 1].conv2) if d["x_virtual"] else None
+        self._wgrad_bf16(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1, in_ss=x_ss)
+        cx = blk.in_ch
+        if frozen and i == 0:      # block 0's input and skip are encoder features: no data gradient at all
+            return g, g_red
+        # the new g is the gradient of relu(bn(y2)) of block i-1 (also where z2 was stored: the mask is recomputed from
+        # y2 * scale + shift either way): that block's BatchNorm-backward sums ride in the pass that writes it
+        below = bn.fuse(sp.decoder[i - 1].conv2, S[f"D{i - 1}"]["y2"]) if i >= 1 else None
+        if d["skip"] is None and i >= 1:
+            # dec4.conv1: data gradient, the 2x2 sums of the up-sampling's backward and the BatchNorm-backward sums of
+            # the block below in one launch of the narrow kernel — no full-resolution gradient tensor
+            c1 = blk.conv1
+            ddesc = self._desc(B, Hh, Ww, c1.cout, 0, 0, Hh, Ww, c1.cin, c1.k, 1, c1.k - 1 - c1.pad, 0, 0)
+            if lib.dt_conv2d_bf16_upsampled_dgrad_supported(C.byref(ddesc)):
+                self.launches["dgrad"].append(c1.key)
+                P = lib.dt_conv2d_bf16_stat_rows(C.byref(ddesc))
+                red = self._buf("bn_red_up", lib.dt_bn_stats_floats(P, cx), device=dev)
+                g = torch.empty(d["x"].shape, dtype=_BF, device=dev)
+                ev = self._pb()
+                self._call("dt_conv2d_bf16_upsampled_dgrad", ddesc, dy1, c1.w(self._wbd[0]), g, red, below)
+                self._pe(ev, f"conv3x3_bf16_narrow_kernel<{c1.cout // 16}, {c1.cin // 16}, false, true, true>",
+                         2.0 * 9 * c1.cin * c1.cout * Hh * Ww * B,
+                         2.0 * B * (Hh * Ww * c1.cout + (Hh // 2) * (Ww // 2) * cx * 2))
+                del dy1
+                self._tr(f"D{i}.g", g)
+                return g, (red, P)
+        dup = torch.empty((B, Hh, Ww, cx), dtype=_BF, device=dev)
+        if d["skip"] is not None:
+            # (frozen encoder: the split kernel still writes the skip's part, to a tensor nobody reads)
+            dskip = torch.empty(d["skip"].shape, dtype=_BF, device=dev)
+            self._dgrad_bf16(blk.conv1, dy1, B, Hh, Ww, dup, dskip, split=cx)
+            skip_grads[3 - i] = None if frozen else dskip
+            self._tr(f"D{i}.dskip", dskip)
+        else:
+            self._dgrad_bf16(blk.conv1, dy1, B, Hh, Ww, dup)
+        self._tr(f"D{i}.dup", dup)
+        del dy1
+        g = torch.empty(d["x"].shape, dtype=_BF, device=dev)
+        g_red = None
+        if i >= 1:
+            P = lib.dt_upsample2x_bwd_bn_bf16_rows(B, Hh // 2, Ww // 2, cx)
+            red = self._buf("bn_red_up", lib.dt_bn_stats_floats(P, cx), device=dev)
+            self._call("dt_upsample2x_bwd_bn_bf16", dup, g, below, red, B, Hh // 2, Ww // 2, cx)
+            g_red = (red, P)
+        else:
+            self._call("dt_upsample2x_bwd_bf16", dup, g, B, Hh // 2, Ww // 2, cx)
+        del dup
+        self._tr(f"D{i}.g", g)
+        return g, g_red
+
+    # ------------------------------------------------------------------ backward
+    def backward_bf16(self, dlogits: torch.Tensor, params: torch.Tensor, grads: torch.Tensor,
+                      saved: Optional[_Saved] = None):
+        """reverse pass of forward_bf16_train: bf16 activation gradients, fp32 parameter gradients"""
+        sp, lib = self.spec, self.lib
+        S = self._saved_of(saved)
+        B, bn = S["B"], BnView(sp, S["bnws"])
+        frozen = bool(S.get("enc_frozen", False))
+        self.launches = {"dgrad": [], "wgrad": []}
+        dev = dlogits.device
+        self._wbd = (self._bf16_weights(params, dgrad=True), self._bf16_weights(params, dgrad=True, chunked=True))
+
+        # ---- head (fp32) -> bf16 gradient of the last decoder activation
+        hd, hsv = sp.head, S["head"]
+        H, W, K = hsv["H"], hsv["W"], sp.head.cout
+        g = torch.empty(hsv["x"].shape, dtype=_BF, device=dev)
+        P = lib.dt_head_bwd_rows(B, H, W)
+        red = self._buf("head_red", lib.dt_head_bwd_red_floats(B, H, W, hd.cin, K), device=dev)
+        self._call("dt_head_bwd_bf16", hsv["x"], hd.w(params), dlogits.contiguous(), g, red, B, H, W, hd.cin, K)
+        self._call("dt_head_bwd_finalize", red, P, hd.w(grads), hd.bias(grads), hd.cin, K)
+        self._tr("head.g", g)
+
+        skip_grads = [None] * 5
+        g_red = None
+        self._head_tap_fix(grads)
+        if sp.decoder_kind == "unetplusplus":
+            G = {sp.decoder[-1].name: g}
+            del g
+            g = self._backward_unetpp_bf16(S, G, params, grads, bn, B, skip_grads, dev)
+            del G
+        for i in (range(4, -1, -1) if sp.decoder_kind != "unetplusplus" else ()):
+            if sp.decoder_kind == "resunet":
+                g = self._backward_resunet_block_bf16(i, sp.decoder[i], S[f"D{i}"], g, params, grads, bn, B, skip_grads)
+            else:
+                g, g_red = self._backward_unet_block_bf16(i, S, g, g_red, params, grads, bn, B, frozen, skip_grads)
+            S[f"D{i}"] = None
+        self._bucket_done(sp.buckets[0])
+        if frozen:      # frozen encoder weights: backward stops at the decoder (no encoder data / weight gradient)
+            self._join_side()
+            self.saved = None
+            return
+
+        for li in (3, 2, 1, 0):
+            blocks = sp.layers[li]
+            for bi in range(len(blocks) - 1, -1, -1):
+                blk, r = blocks[bi], S[f"L{li}B{bi}"]
+                Hin, Win, Hh, Ww = r["Hin"], r["Win"], r["H"], r["W"]
+                gin, gin_has = None, False
+                if bi == 0 and li > 0 and skip_grads[li] is not None:
+                    gin, gin_has = skip_grads[li], True
+                if gin is None:
+                    gin = torch.empty(r["x"].shape, dtype=_BF, device=dev)
+                if blk.down is None:
+                    dy2 = self._bn_bwd_bf16(blk.conv2, params, grads, bn, g, r["out"], r["y2"], dres=gin, dres_acc=gin_has,
+                                            reduced=g_red)
+                    gin_has = True
+                    dyd = None
+                    self._tr(f"L{li}B{bi}.gres", gin)
+                else:
+                    gd = torch.empty(r["out"].shape, dtype=_BF, device=dev)
+                    dy2 = self._bn_bwd_bf16(blk.conv2, params, grads, bn, g, r["out"], r["y2"], dres=gd, reduced=g_red)
+                    dyd = self._bn_bwd_bf16(blk.down, params, grads, bn, gd, None, r["yd"])
+                    self._tr(f"L{li}B{bi}.gres", gd)
+                    self._tr(f"L{li}B{bi}.dyd", dyd)
+                    del gd
+                self._tr(f"L{li}B{bi}.dy2", dy2)
+                if r.get("z1") is not None:
+                    self._wgrad_bf16(blk.conv2, grads, r["z1"], None, 0, B, Hh, Ww, dy2)
+                else:
+                    self._wgrad_bf16(blk.conv2, grads, r["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
+                dz1 = torch.empty(r["y1"].shape, dtype=_BF, device=dev)
+                red1 = self._dgrad_bn_bf16(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, r["y1"], bn)
+                del dy2
+                self._tr(f"L{li}B{bi}.dz1", dz1)
+                dy1 = self._bn_bwd_bf16(blk.conv1, params, grads, bn, dz1, None, r["y1"], virtual_act=True, reduced=red1)
+                self._tr(f"L{li}B{bi}.dy1", dy1)
+                del dz1
+                self._wgrad_bf16(blk.conv1, grads, r["x"], None, 0, B, Hin, Win, dy1)
+                g_red = None
+                if bi > 0 and blk.down is None and gin_has:
+                    # last writer of block bi-1's output gradient: its bn2 reduction (mask: stored output) rides along
+                    rp = S[f"L{li}B{bi - 1}"]
+                    g_red = self._dgrad_bn_bf16(blk.conv1, dy1, B, Hin, Win, gin, blocks[bi - 1].conv2, rp["y2"], bn,
+                                                act=rp["out"])
+                else:
+                    self._dgrad_bf16(blk.conv1, dy1, B, Hin, Win, gin, acc=gin_has)
+                gin_has = True
+                del dy1
+                self._tr(f"L{li}B{bi}.gin1", gin)
+                if dyd is not None:
+                    self._wgrad_bf16(blk.down, grads, r["x"], None, 0, B, Hin, Win, dyd)
+                    self._dgrad_bf16(blk.down, dyd, B, Hin, Win, gin, acc=True)
+                    del dyd
+                    self._tr(f"L{li}B{bi}.gin", gin)
+                g = gin
+                S[f"L{li}B{bi}"] = None
+            if li > 0:
+                self._bucket_done(sp.buckets[4 - li])
+
+        pl, stem = S["pool"], S["stem"]
+        gf1 = skip_grads[0]
+        stem_red = None
+        P = lib.dt_maxpool3x3s2_bwd_bn_bf16_rows(B, pl["H"], pl["W"], 64) if self._fuse_pool_bn else 0
+        if P > 0:      # even maps: the stem's BatchNorm-backward sums ride in the pass that writes its activation gradient
+            red = self._buf("bn_red_pool", lib.dt_bn_stats_floats(P, 64), device=dev)
+            self._call("dt_maxpool3x3s2_bwd_bn_bf16", g, pl["amax"], gf1, 1, bn.fuse(sp.stem, stem["y"]), red, B, pl["H"],
+                       pl["W"], 64)
+            stem_red = (red, P)
+        else:
+            self._call("dt_maxpool3x3s2_bwd_bf16", g, pl["amax"], gf1, 1, B, pl["H"], pl["W"], 64)
+        self._tr("gf1", gf1)
+        dy = self._bn_bwd_bf16(sp.stem, params, grads, bn, gf1, None, stem["y"], virtual_act=True, reduced=stem_red)
+        self._tr("stem.dy", dy)
+        self._stem_wgrad_bf16(stem, dy, grads, B)
+        self._join_side()
+        if self.grad_hook:
+            self.grad_hook(*sp.buckets[4])
+        self.saved = None
+
+    def _stem_wgrad_bf16(self, stem, dy, grads, B):
+        stc, lib, dev = self.spec.stem, self.lib, dy.device
+        self.launches["wgrad"].append(stc.key)
+        if stem.get("s2d") is not None:
+            # space-to-depth form on the bf16 MFMA kernels: dW over 16 taps x 16 channels, gathered back to 7x7
+            cin = stem["x"].shape[-1]
+            d4 = self._desc(B, dy.shape[1], dy.shape[2], 16, 0, 0, dy.shape[1], dy.shape[2], stc.cout, 4, 1, 2)
+            nbytes = self._rows("dt_conv2d_wgrad_bf16_workspace", d4)
+            ws = self._buf("wgrad_ws", nbytes // 4, device=dev)
+            dw4 = self._buf("stem_dw4", 16 * 16 * stc.cout, device=dev)
+            self._call("dt_conv2d_wgrad_bf16", d4, stem["s2d"], None, dy, dw4, ws, ws.numel() * 4, None, None)
+            self._call("dt_stem_unpack_wgrad", dw4, stc.w(grads), cin, stc.cout)
+        else:
+            sdesc = self._desc(B, stem["Hin"], stem["Win"], stem["x"].shape[-1], 0, 0, dy.shape[1], dy.shape[2], stc.cout,
+                               stc.k, stc.stride, stc.pad)
+            nbytes = lib.dt_conv2d_wgrad_workspace(C.byref(sdesc))
+            ws = self._buf("wgrad_ws", nbytes // 4, device=dev)
+            self._call("dt_conv2d_wgrad_stem_dy_bf16", sdesc, stem["x"], dy, stc.w(grads), ws, ws.numel() * 4)

@@ -1,0 +1,794 @@
+"""The fp32 schedule of the U-Net engine: ``forward`` / ``backward`` and their units (convolution + BatchNorm statistics,
+the fused inference forms, BatchNorm backward, weight / data gradients), the Unet++ and ResUnet halves."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import torch
+
+from .. import _lib
+from .bnview import BnView
+from .engine_core import _Saved, _pair
+from .spec import ConvSpec
+
+
+class Fp32Schedule:
+    # ------------------------------------------------------------------ convolution launches
+    def _conv_kernel_name(self, desc, transformed: bool = False) -> str:
+        """name of the kernel instantiation dt_conv2d launches, spelled like rocprofv3 prints it"""
+        tw, tn, ck = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self.lib.dt_conv2d_config(C.byref(desc), C.byref(tw), C.byref(tn), C.byref(ck)), "dt_conv2d_config")
+        if ck.value >= 2000:     # its sub-pixel form for the up-sampled input: ck = 2000 + 10 CB + NB
+            cb, nbk = (ck.value - 2000) // 10, (ck.value - 2000) % 10
+            return f"conv3x3_f32_upc_kernel<{cb}, {nbk}, {'true' if transformed else 'false'}>"
+        if ck.value >= 1000:     # the lean narrow-layer kernel (conv_narrow.hip): ck = 1000 + 10 CB + NB
+            cb, nbk = (ck.value - 1000) // 10, (ck.value - 1000) % 10
+            return f"conv3x3_f32_narrow_kernel<{cb}, {nbk}, {'true' if transformed else 'false'}, false>"
+        if tn.value == 16:
+            return "conv_fwd_n16_kernel"
+        zi = "true" if self.lib.dt_conv2d_uses_zi(C.byref(desc)) else "false"
+        tf = "true" if transformed else "false"
+        return f"conv_fwd_kernel<{desc.ksize}, {desc.stride}, {tw.value}, {tn.value}, {ck.value}, {zi}, {tf}>"
+
+    @staticmethod
+    def _wino_kernel_name(transformed: bool, epi: int) -> str:
+        return f"conv3x3_wino_kernel<{'true' if transformed else 'false'}, {epi}>"
+
+    def _use_wino(self, desc, u) -> bool:
+        return u is not None and bool(self.lib.dt_conv2d_winograd_supported(C.byref(desc)))
+
+    def _stat_rows(self, desc, u=None) -> int:
+        """rows of the BatchNorm partial-statistics buffer the convolution launch for `desc` writes"""
+        return self._rows("dt_conv2d_winograd_stat_rows" if self._use_wino(desc, u) else "dt_conv2d_stat_rows", desc)
+
+    def _conv(self, desc, src0, src1, w, out0, out1=None, stats=None, in_ss=None, u=None):
+        """u: the layer's Winograd weight image (or None): used when the kernel supports the descriptor"""
+        wino = self._use_wino(desc, u)
+        e0 = self._pb()
+        self._call("dt_conv2d_winograd" if wino else "dt_conv2d", desc, src0, src1, u if wino else w, out0, out1, stats,
+                   *_pair(in_ss))
+        if e0 is not None:
+            name = self._wino_kernel_name(in_ss is not None, 2 if desc.accumulate else 0) if wino else \
+                self._conv_kernel_name(desc, in_ss is not None)
+            self._pe(e0, name, *self._conv_work(desc))
+
+    # ------------------------------------------------------------------ forward units
+    def _conv_bn(self, c: ConvSpec, params, bn: BnView, src0, src1, mode0, B, Hin, Win, training, in_ss=None,
+                 save_stats=False):
+        """y = conv(x); BN statistics -> per-channel scale/shift in the workspace.  Returns y, Ho, Wo, (scale, shift).
+        in_ss: (scale, shift) of the layer that produced src0 when src0 is a RAW conv output whose
+        BatchNorm-apply + ReLU is fused into this conv's LDS staging (virtual activation)."""
+        desc = self._conv_desc(c, src0, src1, mode0, B, Hin, Win)
+        Ho, Wo = desc.Ho, desc.Wo
+        y = torch.empty((B, Ho, Wo, c.cout), dtype=torch.float32, device=src0.device)
+        u = self._u(c)
+        if training:
+            P = self._stat_rows(desc, u)
+            stats = self._buf("bn_stats", self.lib.dt_bn_stats_floats(P, c.cout), device=src0.device)
+            self._conv(desc, src0, src1, c.w(params), y, None, stats, in_ss, u=u)
+            ss = self._bn_finalize(c, params, bn, stats, P, B * Ho * Wo)
+        else:
+            self._conv(desc, src0, src1, c.w(params), y, None, None, in_ss, u=u)
+            ss = self._bn_eval_affine(c, params, bn)
+            if save_stats:
+                self._bn_eval_stats(c, bn)
+        return y, Ho, Wo, ss
+
+    def _bn_act(self, y, ss, res=None, res_ss=None, relu=True, out=None, of: Optional[ConvSpec] = None):
+        """relu: True/1 = ReLU after the residual add, 2 = ReLU on the main branch only (ResUnet decoder), 0 = none.
+        of: the convolution whose normalise pass this is (recalibration launch record)"""
+        B, H, W, Cc = y.shape
+        z = torch.empty_like(y) if out is None else out
+        self._rec_act(of)
+        e0 = self._pb()
+        self._call("dt_bn_act", y, ss[0], ss[1], res, *_pair(res_ss), z, B * H * W, Cc, int(relu))
+        self._pe(e0, "bn_act_kernel", 0.0, 4.0 * y.numel() * (2 + (res is not None)))
+        return z
+
+    def _conv_affine_direct(self, c: ConvSpec, params, bn: BnView, src0, src1, mode0, B, Hin, Win, relu=True):
+        """inference: [relu](bn_eval(conv(x))) in one launch of the direct kernel (dt_conv2d_affine) — the layers that are
+        neither Winograd nor narrow layers: stem, stride-2 3x3, 1x1 down-sample.  Returns (activation, Ho, Wo)."""
+        desc = self._conv_desc(c, src0, src1, mode0, B, Hin, Win)
+        scale, shift = self._bn_eval_affine(c, params, bn)
+        z = torch.empty((B, desc.Ho, desc.Wo, c.cout), dtype=torch.float32, device=src0.device)
+        e0 = self._pb()
+        self._call("dt_conv2d_affine", desc, src0, src1, c.w(params), z, scale, shift, 1 if relu else 0)
+        if e0 is not None:
+            self._pe(e0, self._conv_kernel_name(desc, False), *self._conv_work(desc))
+        return z, desc.Ho, desc.Wo
+
+    def _conv_affine_eval(self, c: ConvSpec, params, bn: BnView, src0, src1, mode0, B, Hin, Win, res=None, in_ss=None):
+        """inference: relu(bn_eval(conv(x)) [+ res]) in ONE Winograd launch (dt_conv2d_winograd_affine) — no raw output, no
+        bn_act pass.  Returns the activation, or None when the layer is not a Winograd layer (caller: conv + bn_act)."""
+        if not self._fuse_eval or c.k != 3 or c.stride != 1 or c.pad != 1:
+            return None
+        desc = self._conv_desc(c, src0, src1, mode0, B, Hin, Win)
+        u = self._u(c)
+        narrow = res is None and not self._use_wino(desc, u) and bool(self.lib.dt_conv2d_narrow_supported(C.byref(desc)))
+        if not narrow and (in_ss is not None or not self._use_wino(desc, u)):
+            return None
+        scale, shift = self._bn_eval_affine(c, params, bn)
+        z = torch.empty((B, Hin, Win, c.cout), dtype=torch.float32, device=src0.device)
+        e0 = self._pb()
+        if narrow:     # the narrow decoder layers (dec3.conv2, dec4): the lean kernel's inference epilogue
+            self._call("dt_conv2d_narrow_affine", desc, src0, c.w(params), z, scale, shift, *_pair(in_ss))
+            if e0 is not None:
+                self._pe(e0, f"conv3x3_f32_narrow_kernel<{desc.C0 // 16}, {c.cout // 16}, {'true' if in_ss else 'false'}, 4>",
+                         *self._conv_work(desc))
+            return z
+        self._call("dt_conv2d_winograd_affine", desc, src0, src1, u, z, scale, shift, res)
+        if e0 is not None:
+            self._pe(e0, self._wino_kernel_name(False, 5 if res is not None else 4),
+                     *self._conv_work(desc, extra_bytes=4.0 * z.numel() if res is not None else 0.0))
+        return z
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor, training: bool,
+                save: bool, want_argmax: Optional[str] = None, nhwc: bool = False, enc_training: Optional[bool] = None,
+                enc_frozen: bool = False, recal: Optional[torch.Tensor] = None):
+        """nhwc=True: the input already is the kernels' layout [B,H,W,C] (the tiled-inference gather produces it):
+        no NCHW -> NHWC pass.  enc_training: BatchNorm mode of the encoder (stem + layers 1-4; default: `training`) —
+        False with training=True is fine-tuning on the encoder's running statistics.  enc_frozen: the encoder's weights
+        get no gradient: nothing of the encoder is saved for backward, and an encoder in eval mode runs the fused
+        inference form.
+        recal: device float[1] momentum -> BatchNorm recalibration pass (`update_bn` of stochastic weight averaging): every
+        BatchNorm layer, encoder included, normalises with batch statistics and folds them into its running statistics
+        with THAT momentum (dt_bn_finalize_dev); nothing is saved.  With the Unet decoder the pass ends once the last
+        BatchNorm's statistics are final — no normalise pass of the last convolution, no head — and returns (None, None)."""
+        sp = self.spec
+        self._recal = None
+        if recal is not None:
+            if not training or save or enc_frozen:
+                raise RuntimeError("recalibration forward: training statistics, nothing saved, no frozen-encoder form")
+            if recal.dtype != torch.float32 or recal.device != x_nchw.device:
+                raise RuntimeError("recalibration forward: the momentum is a float32 tensor on the input's device")
+            enc_training = True
+        if nhwc:
+            if x_nchw.dim() != 4 or x_nchw.shape[3] != sp.in_channels:
+                raise RuntimeError(f"expected NHWC input [B,H,W,{sp.in_channels}], got {tuple(x_nchw.shape)}")
+            B, H, W, Cin = x_nchw.shape
+        else:
+            if x_nchw.dim() != 4 or x_nchw.shape[1] != sp.in_channels:
+                raise RuntimeError(f"expected input [B,{sp.in_channels},H,W], got {tuple(x_nchw.shape)}")
+            B, Cin, H, W = x_nchw.shape
+        if H % 32 or W % 32:
+            raise RuntimeError(f"H and W must be divisible by 32 (encoder depth 5), got {H}x{W}")
+        if x_nchw.dtype != torch.float32 or not x_nchw.is_cuda:
+            raise RuntimeError("input must be a float32 CUDA/HIP tensor")
+        dev = x_nchw.device
+        x_nchw = x_nchw.contiguous()
+        if recal is not None:
+            self._recal, self.recal_launches = recal, []
+        sv = _Saved() if save else None
+        dec_training = training
+        enc_training = training if enc_training is None else bool(enc_training)
+        enc_save = save and not enc_frozen
+        self._u_all = self._wino_fwd_weights(params)
+        bnws = self._buf("bnws", BnView.ws_floats(sp), device=dev)
+        # repeated inference calls (tiled prediction): the 46 eval-mode scale/shift launches are skipped while neither the
+        # parameters nor the running statistics changed (torch's version counters + the epochs of the raw device writes)
+        if training or enc_training:
+            self._bn_epoch += 1
+        akey = None if (training or enc_training or save) else (params.data_ptr(), params._version, self._weights_epoch, bnstate.data_ptr(),
+                                                bnstate._version, self._bn_epoch, bnws.data_ptr())
+        self._affine_fresh = akey is not None and self._ws.get("affine_key") == akey
+        self._ws["affine_key"] = akey
+        self._fuse_eval = (self._fuse_eval_opt and not training and not save and self.winograd
+                           and sp.decoder_kind not in ("resunet", "unetplusplus"))
+        dec_fuse_eval = self._fuse_eval
+        # a frozen encoder in eval mode: its layers take the fused inference form (nothing of it is saved)
+        if enc_frozen and not enc_training and self._fuse_eval_opt and self.winograd and sp.decoder_kind == "unet":
+            self._fuse_eval = True
+        training = enc_training
+        if save:
+            # mean/invstd are needed by backward: keep a private copy target per forward
+            bnws = torch.empty(BnView.ws_floats(sp), dtype=torch.float32, device=dev)
+            sv.d["bnws"] = bnws
+        bn = BnView(sp, bnws, bnstate)
+
+        if nhwc:
+            x = x_nchw
+        else:
+            x = torch.empty((B, H, W, Cin), dtype=torch.float32, device=dev)
+            self._call("dt_nchw_to_nhwc", x_nchw, x, B, Cin, H, W)
+
+        def keep(key, **kw):
+            if save:
+                sv.d[key] = kw
+
+        def keep_enc(key, **kw):
+            if enc_save:
+                sv.d[key] = kw
+
+        # ---- stem
+        if self._fuse_eval:     # inference: BatchNorm + ReLU in the stem kernel's epilogue, no raw output
+            f1, h, w_ = self._conv_affine_direct(sp.stem, params, bn, x, None, 0, B, H, W)
+        else:
+            y, h, w_, ss = self._conv_bn(sp.stem, params, bn, x, None, 0, B, H, W, training, save_stats=enc_save)
+            f1 = self._bn_act(y, ss, of=sp.stem)
+            keep_enc("stem", x=x, y=y, z=f1, Hin=H, Win=W)
+        hp, wp = (h + 2 - 3) // 2 + 1, (w_ + 2 - 3) // 2 + 1
+        pool = torch.empty((B, hp, wp, 64), dtype=torch.float32, device=dev)
+        amax = torch.empty((B, hp, wp, 64), dtype=torch.uint8, device=dev) if enc_save else None
+        self._call("dt_maxpool3x3s2", f1, pool, amax, B, h, w_, 64)
+        keep_enc("pool", amax=amax, H=h, W=w_)
+
+        feats = [f1]
+        cur, ch, cw = pool, hp, wp
+        for li, blocks in enumerate(sp.layers):
+            for bi, blk in enumerate(blocks):
+                xin = cur
+                if self._fuse_eval and blk.conv1.stride == 1 and blk.down is None:
+                    z1 = self._conv_affine_eval(blk.conv1, params, bn, xin, None, 0, B, ch, cw)
+                    out = None if z1 is None else self._conv_affine_eval(blk.conv2, params, bn, z1, None, 0, B, ch, cw,
+                                                                         res=xin)
+                    if out is not None:
+                        cur = out
+                        continue
+                if self._fuse_eval and blk.down is not None and blk.conv2.cout % 64 == 0:
+                    # first block of layers 2-4: relu(bn1(conv1)) and bn_d(down(x)) from the direct kernel's epilogue, the
+                    # join relu(bn2(conv2) + .) in the Winograd kernel's
+                    z1, h1, w1 = self._conv_affine_direct(blk.conv1, params, bn, xin, None, 0, B, ch, cw)
+                    rd, _, _ = self._conv_affine_direct(blk.down, params, bn, xin, None, 0, B, ch, cw, relu=False)
+                    out = self._conv_affine_eval(blk.conv2, params, bn, z1, None, 0, B, h1, w1, res=rd)
+                    if out is not None:
+                        cur, ch, cw = out, h1, w1
+                        continue
+                y1, h1, w1, ss1 = self._conv_bn(blk.conv1, params, bn, xin, None, 0, B, ch, cw, training,
+                                                save_stats=enc_save)
+                # z1 = relu(bn1(y1)) is virtual: conv2 applies it while staging y1 (A/B switch DT_MATERIALIZE_Z1:
+                # a stored activation instead, read by the plain convolution / weight-gradient kernels)
+                z1 = self._bn_act(y1, ss1, of=blk.conv1) if self._mat_z1 else None
+                y2, h2, w2, ss2 = self._conv_bn(blk.conv2, params, bn, y1 if z1 is None else z1, None, 0, B,
+                                                h1, w1, training, in_ss=ss1 if z1 is None else None, save_stats=enc_save)
+                if blk.down is not None:
+                    yd, _, _, ssd = self._conv_bn(blk.down, params, bn, xin, None, 0, B, ch, cw, training,
+                                                  save_stats=enc_save)
+                    out = self._bn_act(y2, ss2, res=yd, res_ss=ssd, of=blk.conv2)
+                else:
+                    yd = None
+                    out = self._bn_act(y2, ss2, res=xin, of=blk.conv2)
+                keep_enc(f"L{li}B{bi}", x=xin, y1=y1, z1=z1, y2=y2, yd=yd, out=out, Hin=ch, Win=cw, H=h2, W=w2)
+                cur, ch, cw = out, h2, w2
+            feats.append(cur)
+        # feats = [f1, f2, f3, f4, f5]
+        training, self._fuse_eval = dec_training, dec_fuse_eval
+        if sp.decoder_kind == "unetplusplus":
+            d, dh, dw = self._forward_unetpp(feats, params, bn, B, training, save, keep)
+            dec_blocks = []
+        else:
+            d, dh, dw = feats[4], ch, cw
+            dec_blocks = sp.decoder
+        d_ss = None   # (scale, shift) when d is a raw conv output with a virtual activation
+        skips = [feats[3], feats[2], feats[1], feats[0], None]
+        for i, blk in enumerate(dec_blocks):
+            skip = skips[i]
+            Hin, Win = 2 * dh, 2 * dw
+            if sp.decoder_kind == "resunet":
+                # reference network/extra/resunet/decoder.py:40-52: conv1 -> conv2 (conv-BN-ReLU each, extra/modules.py)
+                # plus the 1x1 identity_conv (with bias) of the up-sampled + concatenated input; no activation after
+                # the sum.  The block output is a real tensor (the next block and the head read it).
+                y1, h1, w1, ss1 = self._conv_bn(blk.conv1, params, bn, d, skip, 1, B, Hin, Win, training,
+                                                save_stats=save)
+                y2, h2, w2, ss2 = self._conv_bn(blk.conv2, params, bn, y1, None, 0, B, h1, w1, training,
+                                                in_ss=ss1, save_stats=save)
+                ic = blk.idc
+                idy = torch.empty((B, Hin, Win, ic.cout), dtype=torch.float32, device=dev)
+                self._conv(self._conv_desc(ic, d, skip, 1, B, Hin, Win), d, skip, ic.w(params), idy)
+                out = self._bn_act(y2, ss2, res=idy, res_ss=(self._const_vec(1.0, ic.cout, dev), ic.bias(params)),
+                                   relu=2, of=blk.conv2)
+                del idy
+                keep(f"D{i}", x=d, skip=skip, y1=y1, y2=y2, H=h1, W=w1)
+                d, dh, dw, d_ss = out, h2, w2, None
+                continue
+            if self._fuse_eval and d_ss is None:
+                z1 = self._conv_affine_eval(blk.conv1, params, bn, d, skip, 1, B, Hin, Win)
+                if z1 is not None:
+                    z2 = self._conv_affine_eval(blk.conv2, params, bn, z1, None, 0, B, Hin, Win)
+                else:
+                    # conv1 is neither a Winograd nor a narrow layer (dec3.conv1: 128 -> 32 from two sources): its raw output
+                    # feeds conv2's lean kernel, which applies bn1 + ReLU while staging AND bn2 + ReLU in its epilogue
+                    y1, _, _, ss1 = self._conv_bn(blk.conv1, params, bn, d, skip, 1, B, Hin, Win, training)
+                    z2 = self._conv_affine_eval(blk.conv2, params, bn, y1, None, 0, B, Hin, Win, in_ss=ss1)
+                    if z2 is None:
+                        z2 = self._bn_act(self._conv_bn(blk.conv2, params, bn, y1, None, 0, B, Hin, Win, training,
+                                                        in_ss=ss1)[0], bn.ss(blk.conv2), of=blk.conv2)
+                if z2 is not None:
+                    d, dh, dw, d_ss = z2, Hin, Win, None
+                    continue
+            y1, h1, w1, ss1 = self._conv_bn(blk.conv1, params, bn, d, skip, 1, B, Hin, Win, training,
+                                            in_ss=d_ss, save_stats=save)
+            z1 = self._bn_act(y1, ss1, of=blk.conv1) if (self._mat_z1 and blk.conv2.cout % 64 == 0) else None
+            y2, h2, w2, ss2 = self._conv_bn(blk.conv2, params, bn, y1 if z1 is None else z1, None, 0, B, h1, w1,
+                                            training, in_ss=ss1 if z1 is None else None, save_stats=save)
+            if self._recal is not None and i == len(sp.decoder) - 1:
+                self._recal = None              # every BatchNorm's statistics are final: nothing else to launch
+                return None, None
+            if i == len(sp.decoder) - 1 or (self._mat_z2 and sp.decoder[i + 1].conv1.cout % 64 == 0):
+                z2 = self._bn_act(y2, ss2, of=blk.conv2)   # the head kernel (or a Winograd conv1) reads a materialised activation
+                nxt, nxt_ss = z2, None
+            else:
+                z2 = None                        # virtual: the next block's conv1 applies bn2+relu while staging
+                nxt, nxt_ss = y2, ss2
+            keep(f"D{i}", x=d, x_virtual=d_ss is not None, skip=skip, y1=y1, z1=z1, y2=y2, z2=z2, H=h1, W=w1)
+            d, dh, dw, d_ss = nxt, h2, w2, nxt_ss
+
+        # ---- head
+        hd = sp.head
+        K = hd.cout
+        logits = torch.empty((B, K, dh, dw), dtype=torch.float32, device=dev)
+        am64 = am8 = None
+        if want_argmax == "int64":
+            am64 = torch.empty((B, dh, dw), dtype=torch.int64, device=dev)
+        elif want_argmax == "uint8":
+            am8 = torch.empty((B, dh, dw), dtype=torch.uint8, device=dev)
+        if self._recal is not None:
+            self.recal_launches.append(("head", hd.key))
+            self._recal = None
+        e0 = self._pb()
+        self._call("dt_head_fwd", d, hd.w(params), hd.bias(params), logits, am64, am8, B, dh, dw, hd.cin, K)
+        self._pe(e0, "head_fwd_kernel", 2.0 * 9 * hd.cin * K * B * dh * dw, 4.0 * B * dh * dw * (hd.cin + K))
+        keep("head", x=d, H=dh, W=dw)
+        if save:
+            sv.d["B"] = B
+            sv.d["training"] = bool(training)
+            sv.d["enc_training"] = bool(enc_training)
+            sv.d["enc_frozen"] = bool(enc_frozen)
+            self.saved = sv
+        return logits, (am64 if am64 is not None else am8)
+
+    # ------------------------------------------------------------------ Unet++ decoder (smp UnetPlusPlus)
+    def _forward_unetpp(self, feats, params, bn: BnView, B, training, save, keep):
+        """dense decoder of smp.UnetPlusPlus (wiring: reference network/extra/efficientunetplusplus/decoder.py:156-184):
+        every node x_{d}_{l} = DecoderBlock(up x2 of its lower node, cat of the nodes / encoder feature on its level).
+        Node outputs are materialised activations (they feed several consumers); conv2 reads conv1's raw output with the
+        BatchNorm+ReLU fused into its staging like everywhere else."""
+        sp = self.spec
+        nodes = {f"f{k}": feats[4 - k] for k in range(5)}     # f0 = deepest encoder feature ... f4 = stem output
+        for blk in sp.decoder:
+            low = nodes[blk.low]
+            Hin, Win = 2 * low.shape[1], 2 * low.shape[2]
+            skip, parts = (None, []) if not blk.cat else self._cat_channels([nodes[n] for n in blk.cat])
+            y1, h1, w1, ss1 = self._conv_bn(blk.conv1, params, bn, low, skip, 1, B, Hin, Win, training,
+                                            save_stats=save)
+            y2, h2, w2, ss2 = self._conv_bn(blk.conv2, params, bn, y1, None, 0, B, h1, w1, training,
+                                            in_ss=ss1, save_stats=save)
+            z2 = self._bn_act(y2, ss2, of=blk.conv2)
+            keep("P" + blk.name, x=low, skip=skip, parts=parts, y1=y1, y2=y2, z2=z2, H=h1, W=w1)
+            nodes[blk.name] = z2
+        out = nodes[sp.decoder[-1].name]
+        return out, out.shape[1], out.shape[2]
+
+    # ------------------------------------------------------------------ backward units
+    def _bn_bwd(self, c: ConvSpec, params, grads, bn: BnView, dout, out_act, y, dres=None, dres_acc=False,
+                virtual_act=False, reduced=None):
+        """virtual_act: the activation was never stored; its ReLU mask is recomputed from y*scale+shift.
+        reduced = (red, P): the partial sums were already produced by the data-gradient kernel that wrote `dout`
+        (`_dgrad_bn`), so the reduction pass over (dout, y) is skipped."""
+        B, H, W, Cc = y.shape
+        n_pix = B * H * W
+        mean, invstd = bn.mean(c), bn.invstd(c)
+        asc, ash = bn.ss(c) if virtual_act else (None, None)
+        if reduced is not None:
+            red, P = reduced
+        else:
+            P = self.lib.dt_bn_bwd_rows(n_pix, Cc)
+            red = self._buf("bn_red", self.lib.dt_bn_bwd_red_floats(n_pix, Cc), device=y.device)
+            e0 = self._pb()
+            self._call("dt_bn_bwd_reduce", dout, out_act, y, mean, invstd, asc, ash, red, n_pix, Cc)
+            self._pe(e0, "bn_bwd_reduce_kernel", 0.0, 4.0 * y.numel() * (2 + (out_act is not None)))
+        dy = torch.empty_like(y)
+        e0 = self._pb()
+        # eval-mode (frozen) BatchNorm: y*scale+shift with constant statistics -> dy = g*gamma*invstd, no mean terms
+        batch_stats = self._bwd_enc_training if c.index in self._enc_index else self._bwd_training
+        self._call("dt_bn_bwd_apply" if batch_stats else "dt_bn_bwd_apply_frozen", dout, out_act, y, mean, invstd,
+                   c.gamma(params), asc, ash, red, P, c.gamma(grads), c.beta(grads), dy, dres, 1 if dres_acc else 0,
+                   n_pix, Cc)
+        # dout + y (+ stored activation) read, dy written (+ residual-branch gradient written, or read-modify-written)
+        self._pe(e0, "bn_bwd_apply_kernel", 0.0, 4.0 * y.numel() * (3 + (out_act is not None) + (dres is not None) * (2 if dres_acc else 1)))
+        return dy
+
+    def _wgrad(self, c: ConvSpec, grads, src0, src1, mode0, B, Hin, Win, dy, in_ss=None, side=True):
+        if side:
+            self.launches["wgrad"].append(c.key)
+        if side and self.overlap_wgrad:
+            self._on_side(lambda: self._wgrad(c, grads, src0, src1, mode0, B, Hin, Win, dy, in_ss, side=False),
+                          src0, src1, dy)
+            return
+        C0 = src0.shape[-1]
+        C1 = 0 if src1 is None else src1.shape[-1]
+        desc = self._desc(B, Hin, Win, C0, C1, mode0, dy.shape[1], dy.shape[2], c.cout, c.k, c.stride, c.pad)
+        e0 = self._pb()
+        if self.winograd and self.lib.dt_conv2d_wgrad_winograd_supported(C.byref(desc)):
+            # 3x3 stride-1 layers with 64-channel blocks: the Winograd form (conv_wino_wgrad.hip, 1.6-1.75x the direct one)
+            nbytes = self.lib.dt_conv2d_wgrad_winograd_workspace(C.byref(desc))
+            ws = self._buf("wgrad_ws", nbytes // 4, device=dy.device)
+            self._call("dt_conv2d_wgrad_winograd", desc, src0, src1, dy, c.w(grads), ws, ws.numel() * 4, *_pair(in_ss))
+            if e0 is not None:
+                self._pe(e0, "conv3x3_wino_wgrad_kernel (+ split-K reduce / final)", *self._conv_work(desc))
+            return
+        nbytes = self._rows("dt_conv2d_wgrad_workspace", desc)
+        ws = self._buf("wgrad_ws", nbytes // 4, device=dy.device)
+        self._call("dt_conv2d_wgrad", desc, src0, src1, dy, c.w(grads), ws, ws.numel() * 4, *_pair(in_ss))
+        if e0 is not None:
+            self._pe(e0, "conv_wgrad_stem_kernel (+ reduce)" if c is self.spec.stem else
+                     ("conv_wgrad_n16_kernel (+ reduce)" if max(desc.C0 + desc.C1, desc.Cout) <= 32 and min(desc.C0 + desc.C1, desc.Cout) <= 16
+                      else "conv_wgrad_kernel (+ split-K reduce)"), *self._conv_work(desc))
+
+    def _dgrad_bn(self, c: ConvSpec, dy, B, H, W, out0, bn_conv: ConvSpec, y, bn: BnView, act=None):
+        """stride-1 data gradient of conv `c` into out0 with the BatchNorm-backward reduction of `bn_conv` (the layer
+        whose raw output `y` has out0's shape) fused into the epilogue -> (red, P) for _bn_bwd.  act None: plain store,
+        virtual activation (mask from y); act = stored block output: the gradient is ADDED to out0 (join) and the
+        sums are taken over the joined tensor."""
+        Cc = bn_conv.cout
+        assert c.stride == 1 and c.cin == Cc and tuple(y.shape) == tuple(out0.shape)
+        self.launches["dgrad"].append(c.key)
+        desc = self._desc(B, H, W, c.cout, 0, 0, H, W, c.cin, c.k, 1, c.k - 1 - c.pad, 0, 0 if act is None else 1)
+        ud = self._u(c, dgrad=True)
+        wino = self._use_wino(desc, ud)
+        P = self._stat_rows(desc, ud)
+        red = self._buf("bn_red_fused", self.lib.dt_bn_stats_floats(P, Cc), device=dy.device)
+        fuse = bn.fuse(bn_conv, y, act)
+        e0 = self._pb()
+        self._call("dt_conv2d_winograd_bn_bwd" if wino else "dt_conv2d_bn_bwd", desc, dy, ud if wino else c.w(self._wd_all),
+                   out0, red, fuse)
+        if e0 is not None:
+            # on top of a plain convolution's traffic: y read (+ the stored output read and the join's second pass)
+            name = self._wino_kernel_name(False, 1 if act is None else 3) if wino else self._conv_kernel_name(desc, False)
+            self._pe(e0, name, *self._conv_work(desc, extra_bytes=(4.0 if act is None else 8.0) * out0.numel()))
+        return red, P
+
+    def _upsampled_dgrad(self, blk, prev_conv: ConvSpec, params, bn: BnView, dy1, y2p, d, B, Hh, Ww) -> bool:
+        """decoder block without a skip: gradient of the block input (low resolution) straight from dy1 — the data
+        gradient of conv1 and the backward of the nearest x2 upsample in one sub-pixel kernel, the BatchNorm-backward
+        sums of the previous block's conv2 in its epilogue.  Fills d["g"], d["g_red"]; False where the layer shape is
+        not covered (the generic chain runs)."""
+        c = blk.conv1
+        cx = blk.in_ch
+        desc = self._desc(B, Hh, Ww, cx, 0, 1, Hh, Ww, c.cout, c.k, c.stride, c.pad, 0, 0)
+        if not self.lib.dt_conv2d_upsampled_dgrad_supported(C.byref(desc)):
+            return False
+        self.launches["dgrad"].append(c.key)
+        P = self.lib.dt_conv2d_upsampled_dgrad_rows(C.byref(desc))
+        red = self._buf("bn_red_up", self.lib.dt_bn_stats_floats(P, cx), device=dy1.device)
+        fuse = bn.fuse(prev_conv, y2p)
+        g = torch.empty_like(d["x"])
+        ev = self._pb()
+        self._call("dt_conv2d_upsampled_dgrad", desc, dy1, c.w(params), g, red, fuse)
+        self._pe(ev, "conv3x3_f32_upc_dgrad_kernel", 2.0 * 9 * cx * c.cout * Hh * Ww * B,
+                 4.0 * B * Hh * Ww * c.cout + 4.0 * B * (Hh // 2) * (Ww // 2) * cx * 2)
+        d["g"], d["g_red"] = g, (red, P)
+        return True
+
+    def _wino_upsampled_dgrad(self, blk, prev_conv: ConvSpec, bn: BnView, dy1, y2p, d, B, Hh, Ww, x_only: bool):
+        """decoder blocks 1-3: the Winograd data gradient of conv1 with the up-sampling's backward (2x2 sums) and the
+        BatchNorm-backward sums of the block below in its epilogue; the skip's gradient from a second launch — or, with a
+        frozen encoder (x_only), only the up-sampled channels [0, cx): the skip's gradient is neither computed nor
+        written.  -> (g, (red, P), dskip | None), or None where the layer shape is not covered"""
+        c1, cx, lib = blk.conv1, blk.in_ch, self.lib
+        ddesc = self._desc(B, Hh, Ww, c1.cout, 0, 0, Hh, Ww, c1.cin, c1.k, 1, c1.k - 1 - c1.pad, cx, 0)
+        ud = self._u(c1, dgrad=True)
+        if ud is None or not lib.dt_conv2d_winograd_upsampled_dgrad_supported(C.byref(ddesc)):
+            return None
+        self.launches["dgrad"].append(c1.key)
+        rows = lib.dt_conv2d_winograd_upsampled_dgrad_x_rows if x_only else lib.dt_conv2d_winograd_upsampled_dgrad_rows
+        P = rows(C.byref(ddesc))
+        red = self._buf("bn_red_up", lib.dt_bn_stats_floats(P, cx), device=dy1.device)
+        fuse = bn.fuse(prev_conv, y2p)
+        dskip = None if x_only else torch.empty_like(d["skip"])
+        g = torch.empty_like(d["x"])
+        ev = self._pb()
+        if x_only:
+            self._call("dt_conv2d_winograd_upsampled_dgrad_x", ddesc, dy1, ud, g, red, fuse)
+            self._pe(ev, self._wino_kernel_name(False, 6) + " (x only)", 2.0 * 9 * cx * c1.cout * Hh * Ww * B,
+                     4.0 * B * Hh * Ww * c1.cout + 4.0 * B * (Hh // 2) * (Ww // 2) * cx * 2)
+        else:
+            self._call("dt_conv2d_winograd_upsampled_dgrad", ddesc, dy1, ud, g, dskip, red, fuse, 3)
+            self._pe(ev, self._wino_kernel_name(False, 6), 2.0 * 9 * c1.cin * c1.cout * Hh * Ww * B,
+                     4.0 * B * Hh * Ww * (c1.cout + (c1.cin - cx)) + 4.0 * B * (Hh // 2) * (Ww // 2) * cx * 2)
+        return g, (red, P), dskip
+
+    def _dgrad(self, c: ConvSpec, params, dy, B, Hin, Win, out0, out1=None, split=0, acc=False):
+        """gradient wrt the conv's logical input [B,Hin,Win,cin] (before virtual upsample handling)."""
+        self.launches["dgrad"].append(c.key)
+        Ho, Wo = dy.shape[1], dy.shape[2]
+        wd = c.w(self._wd_all)     # flipped / transposed image, built at the start of backward
+        pad = c.k - 1 - c.pad
+        if c.stride == 1:
+            desc = self._desc(B, Ho, Wo, c.cout, 0, 0, Hin, Win, c.cin, c.k, 1, pad, split, 1 if acc else 0)
+        else:
+            assert Hin == 2 * Ho and Win == 2 * Wo
+            desc = self._desc(B, Hin, Win, c.cout, 0, 2, Hin, Win, c.cin, c.k, 1, pad, split, 1 if acc else 0)
+        self._conv(desc, dy, None, wd, out0, out1, None, u=self._u(c, dgrad=True) if c.stride == 1 else None)
+
+    def _backward_unetpp(self, S, g_head, params, grads, bn: BnView, B, skip_grads):
+        """reverse of _forward_unetpp: the blocks in reverse forward order (every consumer of a node comes before the
+        node); a node's gradient is the sum over its consumers — as the upsampled input of the block to its right
+        (dt_upsample2x_bwd, accumulating) and as a slice of the concatenated skip of the blocks further right
+        (dt_channel_slice, accumulating).  Fills skip_grads (gradients of f1..f4) and returns the gradient of f5."""
+        sp = self.spec
+        G = {sp.decoder[-1].name: g_head}
+
+        def slot(name, shape, dev):
+            t = G.get(name)
+            if t is None:
+                t = G[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+                return t, 0
+            return t, 1
+
+        for blk in reversed(sp.decoder):
+            d = S["P" + blk.name]
+            g = G.pop(blk.name)
+            dev = g.device
+            Hh, Ww = d["H"], d["W"]
+            dy2 = self._bn_bwd(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True)
+            del g
+            self._wgrad(blk.conv2, grads, d["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
+            dz1 = torch.empty_like(d["y1"])
+            if self._fuse_bn:
+                red1 = self._dgrad_bn(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, d["y1"], bn)
+            else:
+                red1 = self._dgrad(blk.conv2, params, dy2, B, Hh, Ww, dz1)
+            del dy2
+            dy1 = self._bn_bwd(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
+            del dz1
+            self._wgrad(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1)
+            cx = blk.in_ch
+            dup = torch.empty((B, Hh, Ww, cx), dtype=torch.float32, device=dev)
+            dskip = None
+            if d["skip"] is not None:
+                dskip = torch.empty_like(d["skip"])
+                self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup, dskip, split=cx)
+            else:
+                self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup)
+            del dy1
+            glow, acc = slot(blk.low, d["x"].shape, dev)
+            self._call("dt_upsample2x_bwd", dup, glow, acc, B, Hh // 2, Ww // 2, cx)
+            del dup
+            if dskip is not None:
+                Cw = dskip.shape[-1]
+                for name, (off, Cn) in zip(blk.cat, d["parts"]):
+                    if len(blk.cat) == 1 and name not in G:
+                        G[name] = dskip                      # the skip was the tensor itself: its gradient as is
+                        continue
+                    gm, acc = slot(name, (B, Hh, Ww, Cn), dev)
+                    self._call("dt_channel_slice", dskip, gm, B * Hh * Ww, Cn, Cw, off, 0, acc)
+            S["P" + blk.name] = None
+        for k in range(1, 5):
+            skip_grads[4 - k] = G[f"f{k}"]      # f_k of the decoder = feats[4 - k]
+        return G["f0"]
+
+    def _backward_resunet_block(self, blk, d, g, params, grads, bn: BnView, B, Hh, Ww, skip_grads, skip_slot):
+        """reverse of one ResUnet decoder block (forward: see the decoder loop): g = gradient of the block output
+        [B,Hh,Ww,cout] -> returns the gradient of the block's low-resolution input; writes the skip gradient."""
+        lib, dev = self.lib, g.device
+        ic, cx = blk.idc, blk.in_ch
+        sk = 0 if d["skip"] is None else d["skip"].shape[-1]
+        n_pix = B * Hh * Ww
+        # identity branch: weight gradient over the virtual (up-sampled + concatenated) input, bias gradient = sum g
+        self._wgrad(ic, grads, d["x"], d["skip"], 1, B, Hh, Ww, g)
+        ws = self._buf("chsum_ws", int(lib.dt_channel_sums_workspace(n_pix, ic.cout)), device=dev)
+        self._call("dt_channel_sums", g, ws, n_pix, ic.cout, ic.bias(grads))
+        # main branch: relu(bn2(conv2(relu(bn1(conv1(xin))))))  (both activations virtual: masks from y*scale+shift)
+        dy2 = self._bn_bwd(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True)
+        self._wgrad(blk.conv2, grads, d["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
+        dz1 = torch.empty_like(d["y1"])
+        red1 = self._dgrad_bn(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, d["y1"], bn) if self._fuse_bn else \
+            self._dgrad(blk.conv2, params, dy2, B, Hh, Ww, dz1)
+        del dy2
+        dy1 = self._bn_bwd(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
+        del dz1
+        self._wgrad(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1)
+        dup = torch.empty((B, Hh, Ww, cx), dtype=torch.float32, device=dev)
+        dup_id = torch.empty_like(dup)
+        if sk:
+            dskip, dskip_id = torch.empty_like(d["skip"]), torch.empty_like(d["skip"])
+            self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup, dskip, split=cx)
+            self._dgrad(ic, params, g, B, Hh, Ww, dup_id, dskip_id, split=cx)
+            # dskip += dskip_id (the split data-gradient kernels accumulate into their first output only)
+            one, zero = self._const_vec(1.0, sk, dev), self._const_vec(0.0, sk, dev)
+            self._bn_act(dskip, (one, zero), res=dskip_id, relu=0, out=dskip)
+            skip_grads[skip_slot] = dskip
+            del dskip_id
+        else:
+            self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup)
+            self._dgrad(ic, params, g, B, Hh, Ww, dup_id)
+        del dy1
+        gx = torch.empty_like(d["x"])
+        self._call("dt_upsample2x_bwd", dup, gx, 0, B, Hh // 2, Ww // 2, cx)
+        self._call("dt_upsample2x_bwd", dup_id, gx, 1, B, Hh // 2, Ww // 2, cx)
+        return gx
+
+    # ------------------------------------------------------------------ backward
+    def backward(self, dlogits: torch.Tensor, params: torch.Tensor, grads: torch.Tensor, saved: Optional[_Saved] = None):
+        """Hand-scheduled reverse pass.  Writes every parameter gradient into ``grads`` (flat, same layout
+        as ``params``) and calls ``grad_hook(name, lo, hi)`` as each bucket of the flat buffer completes.
+        ``saved``: the activations of the forward pass this gradient belongs to (default: the engine's last one)."""
+        sp, lib = self.spec, self.lib
+        S = self._saved_of(saved)
+        self._bwd_training = bool(S.get("training", True))
+        self._bwd_enc_training = bool(S.get("enc_training", self._bwd_training))
+        frozen = bool(S.get("enc_frozen", False))
+        self.launches = {"dgrad": [], "wgrad": []}
+        B = S["B"]
+        bn = BnView(sp, S["bnws"])
+        dev = dlogits.device
+        dlogits = dlogits.contiguous()
+        # data-gradient weight images of every layer ([tap'][co][ci], taps reversed) in one launch
+        self._wd_all = self._buf("wd_all", sp.n_params, device=dev)
+        self._weight_images(params, self._wd_all, 0)
+        self._ud_all = self._wino_images(self._wd_all, "wino_ud", True) if self.winograd else None
+
+        # ---- head
+        hd = sp.head
+        h = S["head"]
+        H, W = h["H"], h["W"]
+        K = hd.cout
+        g = torch.empty_like(h["x"])
+        P = lib.dt_head_bwd_rows(B, H, W)
+        red = self._buf("head_red", lib.dt_head_bwd_red_floats(B, H, W, hd.cin, K), device=dev)
+        e0 = self._pb()
+        self._call("dt_head_bwd", h["x"], hd.w(params), dlogits, g, red, B, H, W, hd.cin, K)
+        self._pe(e0, "head_bwd_kernel", 4.0 * 9 * hd.cin * K * B * H * W, 4.0 * B * H * W * (2 * hd.cin + K))
+        self._call("dt_head_bwd_finalize", red, P, hd.w(grads), hd.bias(grads), hd.cin, K)
+
+        # ---- decoder (reverse)
+        skip_grads = [None] * 5  # gradient of feats[0..4] = f1..f5
+        g_red = None             # BatchNorm-backward partial sums that already came with g (fused producers)
+        self._head_tap_fix(grads)
+        if sp.decoder_kind == "unetplusplus":
+            g = self._backward_unetpp(S, g, params, grads, bn, B, skip_grads)
+        for i in (range(4, -1, -1) if sp.decoder_kind != "unetplusplus" else ()):
+            blk = sp.decoder[i]
+            d = S[f"D{i}"]
+            Hh, Ww = d["H"], d["W"]
+            if sp.decoder_kind == "resunet":
+                g = self._backward_resunet_block(blk, d, g, params, grads, bn, B, Hh, Ww, skip_grads, 3 - i)
+                S[f"D{i}"] = None
+                continue
+            # conv2 + BN + ReLU (activation stored only for the last block)
+            # mask recomputed from y2 * scale + shift even where z2 was stored (identical to bn_act's; one read less)
+            dy2 = self._bn_bwd(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True, reduced=g_red)
+            if d.get("z1") is not None:
+                self._wgrad(blk.conv2, grads, d["z1"], None, 0, B, Hh, Ww, dy2)
+            else:
+                self._wgrad(blk.conv2, grads, d["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
+            dz1 = torch.empty_like(d["y1"])
+            if self._fuse_bn:
+                red1 = self._dgrad_bn(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, d["y1"], bn)
+            else:
+                red1 = self._dgrad(blk.conv2, params, dy2, B, Hh, Ww, dz1)
+            del dy2
+            dy1 = self._bn_bwd(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
+            del dz1
+            x_ss = bn.ss(sp.decoder[i - 1].conv2) if d["x_virtual"] else None
+            self._wgrad(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1, in_ss=x_ss)
+            cx = blk.in_ch
+            if frozen and i == 0:      # block 0's input and skip are encoder features: no data gradient at all
+                del dy1
+                S[f"D{i}"] = None
+                continue
+            # g becomes the gradient of relu(bn(y2)) of decoder block i-1 (never stored)
+            below = (sp.decoder[i - 1].conv2, S[f"D{i - 1}"]["y2"]) if i >= 1 else None
+            if d["skip"] is None and i >= 1 and self._fuse_bn and self._upsampled_dgrad(blk, below[0], params, bn, dy1,
+                                                                                       below[1], d, B, Hh, Ww):
+                g, g_red = d["g"], d["g_red"]
+                del dy1
+                S[f"D{i}"] = None
+                continue
+            if d["skip"] is not None and i >= 1 and self._fuse_bn and self.winograd:
+                # frozen encoder: the form that leaves the skip's gradient out, else (or where it does not apply) the full one
+                got = self._wino_upsampled_dgrad(blk, below[0], bn, dy1, below[1], d, B, Hh, Ww, x_only=True) if frozen else None
+                if got is None:
+                    got = self._wino_upsampled_dgrad(blk, below[0], bn, dy1, below[1], d, B, Hh, Ww, x_only=False)
+                if got is not None:
+                    g, g_red, dskip = got
+                    if dskip is not None:
+                        skip_grads[3 - i] = dskip
+                    del dy1
+                    S[f"D{i}"] = None
+                    continue
+            dup = torch.empty((B, Hh, Ww, cx), dtype=torch.float32, device=dev)
+            if d["skip"] is not None:
+                # (frozen encoder without the Winograd form: the split kernel writes the skip's part to a scratch tensor)
+                dskip = torch.empty_like(d["skip"])
+                self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup, dskip, split=cx)
+                skip_grads[3 - i] = None if frozen else dskip
+            else:
+                self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup)
+            del dy1
+            g = torch.empty_like(d["x"])
+            g_red = None
+            if i >= 1 and self._fuse_bn:     # also where z2 was stored (DT_MATERIALIZE_Z2): the mask is recomputed from y2
+                # the BatchNorm-backward reduction of the block below rides along in the pass that writes g
+                P = lib.dt_upsample2x_bwd_bn_rows(B, Hh // 2, Ww // 2, cx)
+                red = self._buf("bn_red_up", lib.dt_bn_stats_floats(P, cx), device=dev)
+                self._call("dt_upsample2x_bwd_bn", dup, g, bn.fuse(*below), red, B, Hh // 2, Ww // 2, cx)
+                g_red = (red, P)
+            else:
+                self._call("dt_upsample2x_bwd", dup, g, 0, B, Hh // 2, Ww // 2, cx)
+            del dup
+            S[f"D{i}"] = None
+        self._bucket_done(sp.buckets[0])
+        if frozen:      # frozen encoder weights: backward stops at the decoder (no encoder data / weight gradient)
+            self._join_side()
+            self.saved = None
+            return
+
+        # g = gradient wrt f5 ; encoder layers in reverse
+        for li in (3, 2, 1, 0):
+            blocks = sp.layers[li]
+            for bi in range(len(blocks) - 1, -1, -1):
+                blk = blocks[bi]
+                r = S[f"L{li}B{bi}"]
+                Hin, Win, Hh, Ww = r["Hin"], r["Win"], r["H"], r["W"]
+                # gradient buffer of the block input; a decoder skip gradient may already live there
+                gin = None
+                gin_has = False
+                if bi == 0 and li > 0 and skip_grads[li] is not None:
+                    gin, gin_has = skip_grads[li], True   # block input of layer(li+1).0 is f_{li+1} = feats[li]
+                if gin is None:
+                    gin = torch.empty_like(r["x"])
+                if blk.down is None:
+                    dy2 = self._bn_bwd(blk.conv2, params, grads, bn, g, r["out"], r["y2"], dres=gin,
+                                       dres_acc=gin_has, reduced=g_red)
+                    gin_has = True
+                    dyd = None
+                else:
+                    gd = torch.empty_like(r["out"])
+                    dy2 = self._bn_bwd(blk.conv2, params, grads, bn, g, r["out"], r["y2"], dres=gd, reduced=g_red)
+                    dyd = self._bn_bwd(blk.down, params, grads, bn, gd, None, r["yd"])
+                    del gd
+                if r.get("z1") is not None:
+                    self._wgrad(blk.conv2, grads, r["z1"], None, 0, B, Hh, Ww, dy2)
+                else:
+                    self._wgrad(blk.conv2, grads, r["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
+                dz1 = torch.empty_like(r["y1"])
+                if self._fuse_bn:
+                    red1 = self._dgrad_bn(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, r["y1"], bn)
+                else:
+                    red1 = self._dgrad(blk.conv2, params, dy2, B, Hh, Ww, dz1)
+                del dy2
+                dy1 = self._bn_bwd(blk.conv1, params, grads, bn, dz1, None, r["y1"], virtual_act=True, reduced=red1)
+                del dz1
+                self._wgrad(blk.conv1, grads, r["x"], None, 0, B, Hin, Win, dy1)
+                g_red = None
+                if self.fuse_join_fp32 and bi > 0 and blk.down is None and gin_has:
+                    # gin becomes the output gradient of block bi-1: this join is its last writer, so the
+                    # BatchNorm-backward sums of that block's bn2 (mask: its stored output) ride along
+                    rp = S[f"L{li}B{bi - 1}"]
+                    g_red = self._dgrad_bn(blk.conv1, dy1, B, Hin, Win, gin, blocks[bi - 1].conv2, rp["y2"], bn,
+                                           act=rp["out"])
+                else:
+                    self._dgrad(blk.conv1, params, dy1, B, Hin, Win, gin, acc=gin_has)
+                gin_has = True
+                del dy1
+                if dyd is not None:
+                    self._wgrad(blk.down, grads, r["x"], None, 0, B, Hin, Win, dyd)
+                    self._dgrad(blk.down, params, dyd, B, Hin, Win, gin, acc=True)
+                    del dyd
+                g = gin
+                S[f"L{li}B{bi}"] = None
+            if li > 0:
+                self._bucket_done(sp.buckets[4 - li])
+
+        # ---- maxpool + stem
+        pl = S["pool"]
+        stem = S["stem"]
+        gf1 = skip_grads[0]
+        stem_red = None
+        P = lib.dt_maxpool3x3s2_bwd_bn_rows(B, pl["H"], pl["W"], 64) if (self._fuse_bn and self._fuse_pool_bn) else 0
+        if P > 0:      # even maps: the stem's BatchNorm-backward sums ride in the pass that writes its activation gradient
+            red = self._buf("bn_red_pool", lib.dt_bn_stats_floats(P, 64), device=dev)
+            self._call("dt_maxpool3x3s2_bwd_bn", g, pl["amax"], gf1, 1, bn.fuse(sp.stem, stem["y"]), red, B, pl["H"],
+                       pl["W"], 64)
+            stem_red = (red, P)
+        else:
+            self._call("dt_maxpool3x3s2_bwd", g, pl["amax"], gf1, 1, B, pl["H"], pl["W"], 64)
+        dy = self._bn_bwd(sp.stem, params, grads, bn, gf1, None, stem["y"], virtual_act=True, reduced=stem_red)
+        self._wgrad(sp.stem, grads, stem["x"], None, 0, B, stem["Hin"], stem["Win"], dy)
+        self._join_side()
+        if self.grad_hook:
+            self.grad_hook(*sp.buckets[4])
+        self.saved = None

@@ -41,6 +41,23 @@ class ConvSpec:
     def state_k(self) -> int:
         return self.sd_k or self.k
 
+    # ---- this convolution's ranges of any tensor laid out like the flat parameter buffer (params, grads, the bf16 /
+    # flipped weight images) and its output size: the ONE place that spells the flat-buffer layout
+    def w(self, flat):
+        return flat[self.w_off:self.w_off + self.w_size]
+
+    def gamma(self, flat):
+        return flat[self.g_off:self.g_off + self.cout]
+
+    def beta(self, flat):
+        """BatchNorm beta — or the bias of a convolution without BatchNorm (head, identity_conv)"""
+        return flat[self.b_off:self.b_off + self.cout]
+
+    bias = beta
+
+    def out_size(self, n: int) -> int:
+        return (n + 2 * self.pad - self.k) // self.stride + 1
+
 
 @dataclass
 class BlockSpec:

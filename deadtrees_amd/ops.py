@@ -12,14 +12,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _st():
-    return torch.cuda.current_stream().cuda_stream
+from ._lib import ptr as _p, stream as _st
 
 
 def _gpu(*ts):

@@ -131,14 +131,11 @@ class HipTrainer:
                 g["warm"] += 1
                 return m.recalibrate_batch(x, precision)
             g["x"] = x.clone()
-            eager_ws, eng._ws = eng._ws, {}       # workspaces of the captured pass live (and stay) in the graph's pool
             graph = torch.cuda.CUDAGraph()
-            try:
+            with eng.capture_workspaces() as g["ws"]:   # workspaces of the captured pass live (and stay) in the graph's pool
                 torch.cuda.synchronize()
                 with torch.cuda.graph(graph):
                     m.recalibrate_batch(g["x"], precision)
-            finally:
-                g["ws"], eng._ws = eng._ws, eager_ws
             g["graph"] = graph
         if x is not g["x"]:
             g["x"].copy_(x)
@@ -202,14 +199,11 @@ class HipTrainer:
         g["distmap"] = None if distmap is None else distmap.clone()
         self.opt.sync_lr()
         t_host = self.opt.t
-        eager_ws, eng._ws = eng._ws, {}       # workspaces of the captured step live (and stay) in the graph's pool
         graph = torch.cuda.CUDAGraph()
-        try:
+        with eng.capture_workspaces() as g["ws"]:   # workspaces of the captured step live (and stay) in the graph's pool
             torch.cuda.synchronize()
             with torch.cuda.graph(graph):
                 self._eager_step(g["img"], g["mask"], g["distmap"], alpha, capturing=True)
-        finally:
-            g["ws"], eng._ws = eng._ws, eager_ws
         self.opt.t = t_host                   # capture launched nothing: the step count has not moved
         g["graph"], g["last"] = graph, self.last
 

@@ -4,7 +4,7 @@ TEST INFRASTRUCTURE (see oracle/__init__.py).  PARITY UNPINNED for topology like
 restated smp ``Unet``/``resnet34`` graph — the module passed in IS a ``UNetR34Ref``); what this file adds is
 the *numerics contract* of the mixed-precision path: the reference trains under Lightning AMP
 (reference protocol.md:27, configs/trainer/default.yaml ``precision``) where torch.autocast decides the
-rounding points; the HIP path (deadtrees_amd/network/unet.py ``forward_bf16_train`` / ``backward_bf16``)
+rounding points; the HIP path (deadtrees_amd/network/engine_bf16.py ``forward_bf16_train`` / ``backward_bf16``)
 fixes them explicitly, and this oracle rounds to bf16 at exactly those points while accumulating in
 fp64 (or fp32), so a parity test can separate "bf16 numerics" from "a mis-scheduled layer":
 
@@ -48,7 +48,7 @@ Two ways to use it (tests/test_bf16_gpu.py):
   off by one bf16 ulp): a wrong scale/shift pairing, a dropped residual or a missed gradient join shows up as an
   O(1) error in exactly the unit that has it.
 
-Follows deadtrees_amd/network/unet.py ``forward_bf16_train`` / ``backward_bf16`` step by step.
+Follows deadtrees_amd/network/engine_bf16.py ``forward_bf16_train`` / ``backward_bf16`` step by step.
 """
 from __future__ import annotations
 

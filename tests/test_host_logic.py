@@ -55,10 +55,13 @@ def test_product_path_fails_loudly_without_gpu():
         m(torch.zeros(1, 3, 64, 64))
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         seg_loss(torch.zeros(1, 2, 8, 8), torch.zeros(1, 8, 8, dtype=torch.int64))
-    src = open(os.path.join(ROOT, "deadtrees_amd", "network", "unet.py")).read()
-    for mod in ("unet.py", "segmodel.py"):
-        assert "import oracle" not in open(os.path.join(ROOT, "deadtrees_amd", "network", mod)).read()
-    assert "oracle" not in src.replace("oracle/", "")
+    netdir = os.path.join(ROOT, "deadtrees_amd", "network")
+    mods = sorted(f for f in os.listdir(netdir) if f.endswith(".py"))
+    assert {"unet.py", "segmodel.py", "engine_core.py", "engine_fp32.py", "engine_bf16.py", "module.py"} <= set(mods)
+    for mod in mods:
+        src = open(os.path.join(netdir, mod)).read()
+        assert "import oracle" not in src, mod
+        assert "oracle" not in src.replace("oracle/", ""), mod
 
 
 def test_no_product_module_imports_the_oracle():
@@ -375,3 +378,55 @@ def test_winograd_layer_selection_and_weight_image_tables():
     d32 = ops.conv_desc(32, 256, 256, 32, 0, 0, 128, 3, 1, 1)              # dec.3 data gradient: forward form only
     assert lib.dt_conv2d_winograd_supported(C.byref(d32)) == 1 and lib.dt_conv2d_wgrad_winograd_supported(C.byref(d32)) == 0
     assert lib.dt_conv2d_wgrad_winograd_workspace(C.byref(d)) > 0 and lib.dt_conv2d_wgrad_winograd_workspace(C.byref(d32)) == 0
+
+
+def test_layout_accessors_match_the_written_out_formulas_and_tile_their_buffers():
+    """ConvSpec.w / gamma / beta / out_size and BnView against the index arithmetic the engine spelled at every use
+    before they existed (written out here), for the three decoder kinds: every slice has that offset and length, the
+    four workspace rows and the two state slices of all BatchNorm-ed convolutions tile ``bnws`` / ``bn_state`` without
+    overlap, the parameter ranges tile [0, n_params) up to the 4-float alignment padding."""
+    from deadtrees_amd.network.bnview import BnView
+    from deadtrees_amd.network.spec import build_spec
+
+    def span(t):
+        return t.storage_offset(), t.storage_offset() + t.numel()
+
+    for kind in ("unet", "resunet", "unetplusplus"):
+        s = build_spec(3, 2, kind)
+        nb = s.n_bn_channels
+        assert BnView.ws_floats(s) == 4 * nb and BnView.state_floats(s) == 2 * nb
+        flat = torch.arange(s.n_params, dtype=torch.float32)
+        bnws, state = torch.zeros(4 * nb), torch.zeros(2 * nb)
+        bn = BnView(s, bnws, state)
+        ws_spans, st_spans, p_spans = [], [], []
+        for c in s.convs:
+            assert span(c.w(flat)) == (c.w_off, c.w_off + c.k * c.k * c.cin * c.cout)
+            assert span(c.beta(flat)) == (c.b_off, c.b_off + c.cout) == span(c.bias(flat))
+            p_spans += [span(c.w(flat)), span(c.beta(flat))]
+            for n in (64, 96, 512):
+                assert c.out_size(n) == (n + 2 * c.pad - c.k) // c.stride + 1
+            if c.bn_key is None:
+                continue
+            assert span(c.gamma(flat)) == (c.g_off, c.g_off + c.cout)
+            p_spans.append(span(c.gamma(flat)))
+            rows = (bn.mean(c), bn.invstd(c), bn.scale(c), bn.shift(c))
+            for k, t in enumerate(rows):
+                assert span(t) == (k * nb + c.bn_off, k * nb + c.bn_off + c.cout), (c.key, k)
+                assert t.data_ptr() == bnws.data_ptr() + 4 * (k * nb + c.bn_off)
+            assert [span(t) for t in bn.ss(c)] == [span(rows[2]), span(rows[3])]
+            assert span(bn.running_mean(c)) == (2 * c.bn_off, 2 * c.bn_off + c.cout)
+            assert span(bn.running_var(c)) == (2 * c.bn_off + c.cout, 2 * c.bn_off + 2 * c.cout)
+            assert bn.running_mean(c).data_ptr() == state.data_ptr() + 4 * 2 * c.bn_off
+            ws_spans += [span(t) for t in rows]
+            st_spans += [span(bn.running_mean(c)), span(bn.running_var(c))]
+            f = bn.fuse(c, rows[0])        # (any tensor stands in for y)
+            assert (f.mean, f.invstd, f.act_scale, f.act_shift, f.act) == (rows[0].data_ptr(), rows[1].data_ptr(),
+                                                                           rows[2].data_ptr(), rows[3].data_ptr(), None)
+            f = bn.fuse(c, rows[0], act=rows[1])
+            assert (f.mean, f.invstd, f.act_scale, f.act_shift, f.act) == (rows[0].data_ptr(), rows[1].data_ptr(), None,
+                                                                           None, rows[1].data_ptr())
+        for spans, total, pad in ((ws_spans, 4 * nb, 0), (st_spans, 2 * nb, 0), (p_spans, s.n_params, 3)):
+            spans = sorted(spans)
+            assert spans[0][0] == 0 and 0 <= total - spans[-1][1] <= pad
+            for (lo, hi), (lo2, hi2) in zip(spans, spans[1:]):
+                assert 0 <= lo2 - hi <= pad, (kind, lo, hi, lo2)       # no overlap; gaps only from the alignment
