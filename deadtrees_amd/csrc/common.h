@@ -4,11 +4,20 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <type_traits>
 
 #include "../../include/deadtrees_hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef const void __attribute__((address_space(1)))* dt_gptr;   // global memory, as the LDS-DMA builtin takes it
+typedef void __attribute__((address_space(3)))* dt_lptr;         // LDS
 
 void dt_set_error(const char* fmt, ...);
 
@@ -47,6 +56,22 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 // rows_per_block RB; N % 4 == 0; fp32 partial sums in a fixed order (deterministic).
 int dt_reduce_rows_launch(const float* in, float* out, int planes, int P, int N, int RB, hipStream_t st);
 static inline int dt_reduce_rows_out(int P, int RB) { return (P + RB - 1) / RB; }
+
+// compile-time loop: f(std::integral_constant<int, K>) for K = first .. N-1.  The slot schedules of the persistent kernels
+// index register arrays (accumulators, patch pixels) with K — an ordinary loop that hipcc declines to unroll completely
+// would push them to scratch memory
+template <int K, int N, class F>
+__device__ __forceinline__ void dt_static_for(F&& f) {
+  if constexpr (K < N) {
+    f(std::integral_constant<int, K>{});
+    dt_static_for<K + 1, N>(f);
+  }
+}
+
+// 16 bytes per lane global -> LDS without passing through registers (buffer_load ... lds)
+__device__ __forceinline__ void dt_dma16(const void* g, void* l) {
+  __builtin_amdgcn_global_load_lds((dt_gptr)g, (dt_lptr)l, 16, 0, 0);
+}
 
 // XCD-aware workgroup id remap (bijective for any grid size): hardware deals consecutive workgroup ids
 // round-robin over the 8 XCDs, so ids b and b+8 share an L2.  Returns a logical id such that logical

@@ -1,6 +1,6 @@
 // Argument block shared by the bf16 convolution kernels (conv_bf16.hip, conv_bf16_dma.hip).
 #pragma once
-#include "common.h"
+#include "conv_host.h"
 
 struct ConvBfArgs {
   const __bf16* src0;

@@ -10,10 +10,8 @@
 //   * fp32 accumulators, one rounding to bf16 at the store (v_cvt_pk_bf16_f32 keeps NaN a NaN).
 // Replaces the same ATen ops as conv_fwd.hip for the autocast/AMP configuration the reference trains with
 // (protocol.md:27 "AMP"; configs/trainer/default.yaml precision key).
-#include "common.h"
+#include "conv_host.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 #include "conv_bf16.h"
 
@@ -384,8 +382,8 @@ __global__ __launch_bounds__(256, (KS == 3 && STRIDE == 2) ? 1 : 2) void conv_fw
 }
 
 static int bf_validate(const dt_conv_desc* d) {
-  DT_REQUIRE(d != nullptr, "conv_bf16: null descriptor");
-  DT_REQUIRE(d->B > 0 && d->Hin > 0 && d->Win > 0 && d->C0 > 0 && d->C1 >= 0 && d->Cout > 0, "conv_bf16: bad sizes");
+  DT_TRY(dt_conv_validate_null(d, "conv_bf16"));
+  DT_TRY(dt_conv_validate_sizes(d, "conv_bf16"));
   if (d->ksize == 4) {
     // the space-to-depth stem (dt_stem_s2d_bf16): 4x4 stride-1 window over 16 channels, 2 rows/cols of padding before
     // and 1 after (pad = 2), same-size output
@@ -399,12 +397,9 @@ static int bf_validate(const dt_conv_desc* d) {
   DT_REQUIRE((d->C0 & 7) == 0 && (d->C1 & 7) == 0 && (d->Cout & 7) == 0, "conv_bf16: channels must be multiples of 8");
   DT_REQUIRE(d->C1 == 0 || (d->C0 % BF_CK) == 0, "conv_bf16: concat needs C0 %% 32 == 0");
   DT_REQUIRE(d->mode0 >= 0 && d->mode0 <= 2, "conv_bf16: mode0 %d unsupported", d->mode0);
-  DT_REQUIRE(d->mode0 == 0 || ((d->Hin & 1) == 0 && (d->Win & 1) == 0), "conv_bf16: mode0 needs even Hin/Win");
-  DT_REQUIRE(d->cout_split == 0 || ((d->cout_split % 32) == 0 && d->cout_split < d->Cout),
-             "conv_bf16: cout_split must be a multiple of 32 below Cout");
-  const int ho = (d->Hin + 2 * d->pad - d->ksize) / d->stride + 1, wo = (d->Win + 2 * d->pad - d->ksize) / d->stride + 1;
-  DT_REQUIRE(ho == d->Ho && wo == d->Wo, "conv_bf16: Ho/Wo mismatch");
-  return DT_OK;
+  DT_TRY(dt_conv_validate_even(d, "conv_bf16"));
+  DT_TRY(dt_conv_validate_split(d, "conv_bf16"));
+  return dt_conv_validate_out(d, "conv_bf16");
 }
 
 template <int KS, int STRIDE, int TW, int TN, int CK, int MT>
@@ -491,62 +486,8 @@ extern "C" int dt_conv2d_bf16_stat_rows(const dt_conv_desc* d) {
 
 static int conv2d_bf16_impl(const dt_conv_desc* d, const void* src0, const void* src1, const void* w_bf16, void* out,
                             void* out1, float* stats, const float* in_scale, const float* in_shift, void* stream,
-                            const dt_bn_bwd_fuse* fuse);
-
-extern "C" int dt_conv2d_bf16(const dt_conv_desc* d, const void* src0, const void* src1, const void* w_bf16,
-                              void* out, void* out1, float* stats, const float* in_scale, const float* in_shift,
-                              void* stream) {
-  return conv2d_bf16_impl(d, src0, src1, w_bf16, out, out1, stats, in_scale, in_shift, stream, nullptr);
-}
-
-extern "C" int dt_conv2d_bf16_bn_bwd(const dt_conv_desc* d, const void* src0, const void* w_bf16, void* out, float* red,
-                                     const dt_bn_bwd_fuse* fuse, void* stream) {
-  DT_REQUIRE(d && fuse && red && fuse->y && fuse->mean && fuse->invstd, "conv_bf16_bn_bwd: null pointer");
-  DT_REQUIRE(fuse->act != nullptr || (fuse->act_scale && fuse->act_shift),
-             "conv_bf16_bn_bwd: give the stored activation or the scale/shift of a virtual one");
-  DT_REQUIRE(d->ksize == 3 && d->stride == 1 && d->mode0 == 0 && d->C1 == 0 && d->cout_split == 0,
-             "conv_bf16_bn_bwd: plain 3x3 stride-1 data gradients only");
-  DT_REQUIRE((d->accumulate != 0) == (fuse->act != nullptr),
-             "conv_bf16_bn_bwd: gradient joins (accumulate) go with a stored activation, plain stores with a virtual one");
-  DT_REQUIRE((((uintptr_t)fuse->mean | (uintptr_t)fuse->invstd | (uintptr_t)fuse->act_scale |
-               (uintptr_t)fuse->act_shift) & 15) == 0, "conv_bf16_bn_bwd: per-channel arrays must be 16-byte aligned");
-  return conv2d_bf16_impl(d, src0, nullptr, w_bf16, out, nullptr, red, nullptr, nullptr, stream, fuse);
-}
-
-// data gradient of a convolution whose input was a nearest x2 up-sampling, for the narrow layers (dec4.conv1): `d`, src0 =
-// dy and w_bf16 as for dt_conv2d_bf16_bn_bwd (the full-resolution data-gradient form); the 2x2 sums of the up-sampling's
-// backward are taken on the accumulators and gx [B, Ho/2, Wo/2, Cout] is stored with the BatchNorm-backward sums of the
-// layer below in red (P = dt_conv2d_bf16_stat_rows(d)) — replaces dt_conv2d_bf16 + dt_upsample2x_bwd_bn_bf16
-extern "C" int dt_conv2d_bf16_upsampled_dgrad_supported(const dt_conv_desc* d) {
-  static const int on = [] {
-    const char* e = getenv("DT_BF16_FUSE_UPSAMPLE_BWD");
-    return (e == nullptr || e[0] != '0') ? 1 : 0;
-  }();
-  return on && d != nullptr && bf_validate(d) == DT_OK && dt_conv_bf16_narrow_supported(d) && d->mode0 == 0 &&
-         ((d->Ho | d->Wo) & 1) == 0;
-}
-
-extern "C" int dt_conv2d_bf16_upsampled_dgrad(const dt_conv_desc* d, const void* dy, const void* w_bf16, void* gx, float* red,
-                                              const dt_bn_bwd_fuse* fuse, void* stream) {
-  DT_REQUIRE(d && dy && w_bf16 && gx && red && fuse && fuse->y && fuse->mean && fuse->invstd && fuse->act_scale &&
-                 fuse->act_shift && fuse->act == nullptr, "conv_bf16_upsampled_dgrad: null pointer / stored activation");
-  DT_REQUIRE(dt_conv2d_bf16_upsampled_dgrad_supported(d), "conv_bf16_upsampled_dgrad: layer shape not supported");
-  ConvBfArgs a;
-  a.bnb = *fuse;
-  a.out1 = nullptr; a.stats = red; a.cout_split = 0; a.accumulate = 0;
-  a.src0 = (const __bf16*)dy; a.src1 = nullptr; a.w = (const __bf16*)w_bf16;
-  a.in_scale = nullptr; a.in_shift = nullptr; a.out = (__bf16*)gx;
-  a.B = d->B; a.Hin = d->Hin; a.Win = d->Win; a.C0 = d->C0; a.C1 = 0; a.mode0 = 0;
-  a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.pad = d->pad;
-  a.n_tiles = 1;
-  return dt_conv_bf16_narrow_launch(d, a, (hipStream_t)stream, true);
-}
-
-static int conv2d_bf16_impl(const dt_conv_desc* d, const void* src0, const void* src1, const void* w_bf16, void* out,
-                            void* out1, float* stats, const float* in_scale, const float* in_shift, void* stream,
                             const dt_bn_bwd_fuse* fuse) {
-  int rc = bf_validate(d);
-  if (rc != DT_OK) return rc;
+  DT_TRY(bf_validate(d));
   DT_REQUIRE(src0 && w_bf16 && out, "conv_bf16: null pointer");
   DT_REQUIRE(d->C1 == 0 || src1, "conv_bf16: src1 missing");
   DT_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "conv_bf16: in_scale/in_shift must come together");
@@ -574,6 +515,50 @@ static int conv2d_bf16_impl(const dt_conv_desc* d, const void* src0, const void*
   if (d->ksize == 3 && d->stride == 2) return bf_dispatch<3, 2>(a, tw, tn, ck, mt, st);
   if (d->ksize == 1 && d->stride == 1) return bf_dispatch<1, 1>(a, tw, tn, ck, mt, st);
   return bf_dispatch<1, 2>(a, tw, tn, ck, mt, st);
+}
+
+extern "C" int dt_conv2d_bf16(const dt_conv_desc* d, const void* src0, const void* src1, const void* w_bf16,
+                              void* out, void* out1, float* stats, const float* in_scale, const float* in_shift,
+                              void* stream) {
+  return conv2d_bf16_impl(d, src0, src1, w_bf16, out, out1, stats, in_scale, in_shift, stream, nullptr);
+}
+
+extern "C" int dt_conv2d_bf16_bn_bwd(const dt_conv_desc* d, const void* src0, const void* w_bf16, void* out, float* red,
+                                     const dt_bn_bwd_fuse* fuse, void* stream) {
+  DT_REQUIRE(d && fuse && red && fuse->y && fuse->mean && fuse->invstd, "conv_bf16_bn_bwd: null pointer");
+  DT_REQUIRE(fuse->act != nullptr || (fuse->act_scale && fuse->act_shift),
+             "conv_bf16_bn_bwd: give the stored activation or the scale/shift of a virtual one");
+  DT_REQUIRE(d->ksize == 3 && d->stride == 1 && d->mode0 == 0 && d->C1 == 0 && d->cout_split == 0,
+             "conv_bf16_bn_bwd: plain 3x3 stride-1 data gradients only");
+  DT_REQUIRE((d->accumulate != 0) == (fuse->act != nullptr),
+             "conv_bf16_bn_bwd: gradient joins (accumulate) go with a stored activation, plain stores with a virtual one");
+  DT_REQUIRE_COEF_ALIGNED(dt_fuse_aligned16(fuse), "conv_bf16_bn_bwd");
+  return conv2d_bf16_impl(d, src0, nullptr, w_bf16, out, nullptr, red, nullptr, nullptr, stream, fuse);
+}
+
+// data gradient of a convolution whose input was a nearest x2 up-sampling, for the narrow layers (dec4.conv1): `d`, src0 =
+// dy and w_bf16 as for dt_conv2d_bf16_bn_bwd (the full-resolution data-gradient form); the 2x2 sums of the up-sampling's
+// backward are taken on the accumulators and gx [B, Ho/2, Wo/2, Cout] is stored with the BatchNorm-backward sums of the
+// layer below in red (P = dt_conv2d_bf16_stat_rows(d)) — replaces dt_conv2d_bf16 + dt_upsample2x_bwd_bn_bf16
+extern "C" int dt_conv2d_bf16_upsampled_dgrad_supported(const dt_conv_desc* d) {
+  return dt_env_on("DT_BF16_FUSE_UPSAMPLE_BWD") && d != nullptr && bf_validate(d) == DT_OK &&
+         dt_conv_bf16_narrow_supported(d) && d->mode0 == 0 && ((d->Ho | d->Wo) & 1) == 0;
+}
+
+extern "C" int dt_conv2d_bf16_upsampled_dgrad(const dt_conv_desc* d, const void* dy, const void* w_bf16, void* gx, float* red,
+                                              const dt_bn_bwd_fuse* fuse, void* stream) {
+  DT_REQUIRE(d && dy && w_bf16 && gx && red && fuse && fuse->y && fuse->mean && fuse->invstd && fuse->act_scale &&
+                 fuse->act_shift && fuse->act == nullptr, "conv_bf16_upsampled_dgrad: null pointer / stored activation");
+  DT_REQUIRE(dt_conv2d_bf16_upsampled_dgrad_supported(d), "conv_bf16_upsampled_dgrad: layer shape not supported");
+  ConvBfArgs a;
+  a.bnb = *fuse;
+  a.out1 = nullptr; a.stats = red; a.cout_split = 0; a.accumulate = 0;
+  a.src0 = (const __bf16*)dy; a.src1 = nullptr; a.w = (const __bf16*)w_bf16;
+  a.in_scale = nullptr; a.in_shift = nullptr; a.out = (__bf16*)gx;
+  a.B = d->B; a.Hin = d->Hin; a.Win = d->Win; a.C0 = d->C0; a.C1 = 0; a.mode0 = 0;
+  a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.pad = d->pad;
+  a.n_tiles = 1;
+  return dt_conv_bf16_narrow_launch(d, a, (hipStream_t)stream, true);
 }
 
 // ------------------------------------------------------------------ weights: fp32 HWIO -> bf16 [tap][Cout][Cin]
@@ -617,8 +602,7 @@ __global__ void pack_dgrad_weights_bf16_kernel(const float* __restrict__ w, __bf
 extern "C" int dt_pack_dgrad_weights_bf16(const float* w_hwio, void* out, int ksize, int Cin, int Cout, void* stream) {
   DT_REQUIRE(w_hwio && out && ksize > 0 && Cin > 0 && Cout > 0, "pack_dgrad_weights_bf16: bad args");
   const int64_t per_tap = (int64_t)Cin * Cout;
-  int64_t g = (per_tap * ksize * ksize + 255) / 256;
-  if (g > 4096) g = 4096;
+  const int g = dt_ew_grid(per_tap * ksize * ksize, 4096);
   hipLaunchKernelGGL(pack_dgrad_weights_bf16_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, w_hwio,
                      (__bf16*)out, ksize * ksize, per_tap);
   DT_LAUNCH_CHECK();
@@ -657,8 +641,7 @@ __global__ __launch_bounds__(256) void stem_s2d_bf16_kernel(const float* __restr
 extern "C" int dt_stem_s2d_bf16(const float* x_nhwc, void* out, int B, int H, int W, int Cin, void* stream) {
   DT_REQUIRE(x_nhwc && out && B > 0 && H > 0 && W > 0 && (H & 1) == 0 && (W & 1) == 0 && Cin >= 1 && Cin <= 4,
              "stem_s2d_bf16: needs even H, W and 1..4 channels");
-  int64_t g = ((int64_t)B * (H / 2) * (W / 2) + 255) / 256;
-  if (g > 8192) g = 8192;
+  const int g = dt_ew_grid((int64_t)B * (H / 2) * (W / 2), 8192);
   hipLaunchKernelGGL(stem_s2d_bf16_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, x_nhwc, (__bf16*)out, B,
                      H, W, Cin);
   DT_LAUNCH_CHECK();
@@ -902,11 +885,9 @@ extern "C" int dt_bn_act_bf16(const void* y, int y_is_f32, const float* scale, c
   DT_REQUIRE(y && scale && shift && out && n_pix > 0 && C > 0 && (C & 7) == 0, "bn_act_bf16: bad args (C%%8)");
   DT_REQUIRE((rscale == nullptr) == (rshift == nullptr), "bn_act_bf16: rscale/rshift must come together");
   DT_REQUIRE(256 % (C / 8) == 0, "bn_act_bf16: C/8 must divide 256 (C=%d)", C);
-  DT_REQUIRE((((uintptr_t)scale | (uintptr_t)shift | (uintptr_t)rscale | (uintptr_t)rshift) & 15) == 0,
-             "bn_act_bf16: per-channel arrays must be 16-byte aligned");
+  DT_REQUIRE_COEF_ALIGNED(dt_aligned16(scale, shift, rscale, rshift), "bn_act_bf16");
   const int64_t n8 = n_pix * C / 8;
-  int64_t g = (n8 + 255) / 256;
-  if (g > 4096) g = 4096;
+  const int g = dt_ew_grid(n8, 4096);
   if (y_is_f32)
     hipLaunchKernelGGL(bn_act_bf16_kernel<true>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, y, scale, shift,
                        (const __bf16*)res, rscale, rshift, (__bf16*)out, n8, C / 8, relu);
@@ -956,8 +937,7 @@ extern "C" int dt_maxpool3x3s2_bf16(const void* x, void* out, int B, int H, int 
   DT_REQUIRE(x && out && B > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0, "maxpool_bf16: bad args");
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const int64_t total = (int64_t)B * Ho * Wo * (C / 8);
-  int64_t g = (total + 255) / 256;
-  if (g > 4096) g = 4096;
+  const int g = dt_ew_grid(total, 4096);
   hipLaunchKernelGGL(maxpool_bf16_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)x,
                      (bf16x8*)out, B, H, W, C / 8, Ho, Wo);
   DT_LAUNCH_CHECK();
@@ -982,8 +962,7 @@ __global__ __launch_bounds__(256) void bf16_to_f32_kernel(const bf16x8* __restri
 
 extern "C" int dt_bf16_to_f32(const void* x, float* out, int64_t n, void* stream) {
   DT_REQUIRE(x && out && n > 0 && (n & 7) == 0, "bf16_to_f32: n must be a multiple of 8");
-  int64_t g = (n / 8 + 255) / 256;
-  if (g > 4096) g = 4096;
+  const int g = dt_ew_grid(n / 8, 4096);
   hipLaunchKernelGGL(bf16_to_f32_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)x,
                      (f32x4*)out, n / 8);
   DT_LAUNCH_CHECK();
@@ -1007,7 +986,6 @@ struct WgradBfArgs {
 };
 
 #define WB_PITCH 72   // bf16 elements per LDS row (64 used): 144 bytes (multiple of 8 for the transposed reads)
-typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
 
 // BLK = 64: a workgroup owns a 64ci x 64co block, its 4 waves split the channels 2 x 2.
 // BLK = 32 (layers with Cin, Cout <= 32 — the full-resolution decoder end, HBM-bound in bf16): one 32 x 32 block,
@@ -1119,7 +1097,7 @@ __global__ __launch_bounds__(256, (KS == 3 && STRIDE == 2) ? 1 : 2) void conv_wg
       if (pix < TPX) *reinterpret_cast<f32x4*>(ly + pix * WB_PITCH + 8 * q8) = ry[it];
     }
     __syncthreads();
-    typedef bf16x4v __attribute__((address_space(3))) * lds_ptr;
+    typedef bf16x4 __attribute__((address_space(3))) * lds_ptr;
     constexpr int ROWS_W = BLK == 64 ? TH : TH / 4;   // BLK 32: this wave's share of the tile's pixel rows
     const int row_w0 = BLK == 64 ? 0 : wave * ROWS_W;
 #pragma unroll
@@ -1131,8 +1109,8 @@ __global__ __launch_bounds__(256, (KS == 3 && STRIDE == 2) ? 1 : 2) void conv_wg
         bf16x8 bv;
         {
           const int e = ylane + (row * TW + 16 * xs) * WB_PITCH;
-          const bf16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(ly + e));
-          const bf16x4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(ly + e + 4 * WB_PITCH));
+          const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(ly + e));
+          const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(ly + e + 4 * WB_PITCH));
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             bv[k] = lo[k];
@@ -1143,8 +1121,8 @@ __global__ __launch_bounds__(256, (KS == 3 && STRIDE == 2) ? 1 : 2) void conv_wg
         for (int t = 0; t < NTAP; ++t) {
           const int kh = kh0 + t / KS, kw = t % KS;
           const int e = xlane + ((row * LS + kh) * HALO_W + 16 * xs * LS + kw) * WB_PITCH;
-          const bf16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(lx + e));
-          const bf16x4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(lx + e + 4 * LS * WB_PITCH));
+          const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(lx + e));
+          const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(lx + e + 4 * LS * WB_PITCH));
           bf16x8 av;
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
@@ -1209,16 +1187,10 @@ static int wb_cfg(const dt_conv_desc* d, int* tw, int* ksplit, int* T, int* cib,
 }
 
 // DT_BF16_WGRAD_DMA=0 keeps every layer on the register-staged kernel below (A/B switch; read once)
-static bool wb_use_dma() {
-  static const int on = [] {
-    const char* e = getenv("DT_BF16_WGRAD_DMA");
-    return (e == nullptr || e[0] != '0') ? 1 : 0;
-  }();
-  return on != 0;
-}
+static bool wb_use_dma() { return dt_env_on("DT_BF16_WGRAD_DMA"); }
 
 static int wb_validate(const dt_conv_desc* d) {
-  DT_REQUIRE(d != nullptr, "wgrad_bf16: null descriptor");
+  DT_TRY(dt_conv_validate_null(d, "wgrad_bf16"));
   if (d->ksize == 4) {   // the space-to-depth stem (see dt_stem_s2d_bf16)
     DT_REQUIRE(d->stride == 1 && d->pad == 2 && d->C0 == 16 && d->C1 == 0 && d->mode0 == 0 && (d->Cout % 32) == 0 &&
                    d->Ho == d->Hin && d->Wo == d->Win && d->Wo > 16,
@@ -1229,9 +1201,7 @@ static int wb_validate(const dt_conv_desc* d) {
              "wgrad_bf16: ksize/stride (%d,%d) unsupported", d->ksize, d->stride);
   DT_REQUIRE((d->C0 & 7) == 0 && (d->C1 & 7) == 0 && (d->Cout & 7) == 0, "wgrad_bf16: channels must be multiples of 8");
   DT_REQUIRE(d->mode0 >= 0 && d->mode0 <= 1, "wgrad_bf16: mode0");
-  const int ho = (d->Hin + 2 * d->pad - d->ksize) / d->stride + 1, wo = (d->Win + 2 * d->pad - d->ksize) / d->stride + 1;
-  DT_REQUIRE(ho == d->Ho && wo == d->Wo, "wgrad_bf16: Ho/Wo mismatch");
-  return DT_OK;
+  return dt_conv_validate_out(d, "wgrad_bf16");
 }
 
 extern "C" size_t dt_conv2d_wgrad_bf16_workspace(const dt_conv_desc* d) {

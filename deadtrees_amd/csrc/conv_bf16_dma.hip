@@ -20,14 +20,9 @@
 // setting, protocol.md:27).
 #include "conv_bf16.h"
 
-#include <stdlib.h>
 #include <string.h>
 
-#include <type_traits>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef const void __attribute__((address_space(1)))* dm_gptr;
-typedef void __attribute__((address_space(3)))* dm_lptr;
 
 #define DM_TW 32
 #define DM_TH 16
@@ -45,10 +40,6 @@ typedef void __attribute__((address_space(3)))* dm_lptr;
 #define DM_MAX_WGS 256                                 // CUs of an MI355X
 
 __device__ __attribute__((aligned(64))) unsigned dm_zero_block[16];
-
-__device__ __forceinline__ void dm_dma16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((dm_gptr)g, (dm_lptr)l, 16, 0, 0);
-}
 
 // EPI selects the epilogue at compile time (register pressure: the persistent loop keeps the accumulators, the next
 // tile's staging context and the epilogue's state live together): 0 plain store (+ BatchNorm statistics, split
@@ -114,7 +105,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bf16_dma_kernel(const ConvBfAr
     if (k < DM_PPW) {
       const int wp = wave + 8 * k;
       if (wp < DM_W_PIECES)
-        dm_dma16(a.w + (size_t)woff[k] + (size_t)s_chunk * a.Cout * 32, lds + buf + (DM_IN_PIECES + wp) * 1024);
+        dt_dma16(a.w + (size_t)woff[k] + (size_t)s_chunk * a.Cout * 32, lds + buf + (DM_IN_PIECES + wp) * 1024);
       return;
     }
     const int i = k - DM_PPW;
@@ -138,7 +129,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bf16_dma_kernel(const ConvBfAr
     } else {
       if (ip < DM_IN_PIECES) {
         const __bf16* g = p >= 0 ? src + (size_t)p * C + cc : zsrc;
-        dm_dma16(g, lds + buf + ip * 1024);
+        dt_dma16(g, lds + buf + ip * 1024);
       }
     }
   };

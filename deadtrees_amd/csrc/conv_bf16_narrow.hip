@@ -26,8 +26,6 @@
 // store; the K order differs (taps paired), so results agree to fp32 accumulation-order noise, not bit for bit.
 #include "conv_bf16.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #define NR_TW 32
 #define NR_TH 8
@@ -225,7 +223,6 @@ __global__ __launch_bounds__(256, (CB == 2 && NB == 2) ? 2 : (CB == 1 && NB == 1
     }
     // pack channel pairs (n, n + 1) across the lane pair and write the bf16 tile [pixel][channel] to the staging image
     if constexpr (UPB) {
-      typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
       for (int mbx = 0; mbx < 2; ++mbx)
 #pragma unroll
@@ -250,7 +247,6 @@ __global__ __launch_bounds__(256, (CB == 2 && NB == 2) ? 2 : (CB == 1 && NB == 1
           const float y0 = nr_swap_pair(x0), y1 = nr_swap_pair(x1);
           // even lane: channels (n, n + 1) of pixel 2 ip; odd lane: channels (n - 1, n) of pixel 2 ip + 1
           const float lo = odd ? y1 : x0, hi = odd ? x1 : y0;
-          typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
           const bf16x2 pk = {(__bf16)lo, (__bf16)hi};
           const int pl = (2 * wave + (mb >> 1)) * NR_TW + 16 * (mb & 1) + 4 * kg + 2 * ip + (odd ? 1 : 0);
           *reinterpret_cast<bf16x2*>(lds_out + pl * G::OUTP + 2 * (16 * nb + (m & ~1))) = pk;
@@ -329,13 +325,7 @@ __global__ __launch_bounds__(256, (CB == 2 && NB == 2) ? 2 : (CB == 1 && NB == 1
 }
 
 // ---------------------------------------------------------------- host side
-static bool nr_enabled() {
-  static const int on = [] {
-    const char* e = getenv("DT_BF16_NARROW");
-    return (e == nullptr || e[0] != '0') ? 1 : 0;
-  }();
-  return on != 0;
-}
+static bool nr_enabled() { return dt_env_on("DT_BF16_NARROW"); }
 
 int dt_conv_bf16_narrow_supported(const dt_conv_desc* d) {
   if (!nr_enabled() || d == nullptr) return 0;
@@ -444,8 +434,7 @@ int dt_conv_bf16_narrow_launch(const dt_conv_desc* d, ConvBfArgs a, hipStream_t 
 //     row are read once; 9 x CB x NB accumulators (4 registers each) live for the whole kernel;
 //   * persistent over 8 x 32-pixel tiles with the next tile in flight in registers; the four waves split the tile's rows
 //     and are summed through LDS once at the end (fixed order); one slab per workgroup -> wgrad_bf16_final_kernel.
-typedef __bf16 bf16x4n __attribute__((ext_vector_type(4)));
-typedef bf16x4n __attribute__((address_space(3)))* nr_trptr;
+typedef bf16x4 __attribute__((address_space(3)))* nr_trptr;
 
 struct NrWgArgs {
   const __bf16* src0;
@@ -528,8 +517,8 @@ __global__ __launch_bounds__(256, (CB == 2 && NB == 2) ? 2 : 3) void conv3x3_wgr
   const int xlane = (4 * kg + q4) * PX + 8 * p4;
   const int ylane = (4 * kg + q4) * PY + 8 * p4;
   auto tr8 = [&](const unsigned char* p, int pitch) -> bf16x8 {
-    const bf16x4n lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((nr_trptr)p);
-    const bf16x4n hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((nr_trptr)(p + 16 * pitch));
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((nr_trptr)p);
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((nr_trptr)(p + 16 * pitch));
     bf16x8 v;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {

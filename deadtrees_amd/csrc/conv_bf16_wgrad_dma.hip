@@ -30,13 +30,7 @@
 //     that wgrad_bf16_final_kernel (conv_bf16.hip) reduces in one launch — deterministic, no atomics.
 #include "conv_bf16.h"
 
-#include <type_traits>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4w __attribute__((ext_vector_type(4)));
-typedef void __attribute__((address_space(3)))* wd_lptr;
-typedef const void __attribute__((address_space(1)))* wd_gptr;
-typedef bf16x4w __attribute__((address_space(3)))* wd_trptr;
+typedef bf16x4 __attribute__((address_space(3)))* wd_trptr;
 
 #define WD_OOB 0x80000000u     // byte offset beyond every buffer this kernel takes (host check: operands < 2 GiB)
 #define WD_MAX_WGS 256
@@ -54,14 +48,6 @@ struct WgDmaArgs {
   int tiles_x, tiles_y, T, ci_blocks, co_blocks, ksplit, tps;   // tps: tiles per split
   unsigned bytes0, bytes1, dybytes;
 };
-
-template <int K, int N, class F>
-__device__ __forceinline__ void wd_static_for(F&& f) {
-  if constexpr (K < N) {
-    f(std::integral_constant<int, K>{});
-    wd_static_for<K + 1, N>(f);
-  }
-}
 
 // TW = 32: tiles of 4 rows x 32 pixels (halo 6 x 40); TW = 16 (maps at most 16 pixels wide): 8 rows x 16 (halo 10 x 24)
 template <int TW>
@@ -127,7 +113,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_bf16_dma_kernel(const Wg
     // global_load_lds, not buffer_load ... lds: behind the buffer form hipcc (ROCm 7.2) puts `s_waitcnt vmcnt(0)` in front
     // of the next LDS read (it cannot prove that the read misses the DMA's destination) — every piece's whole latency was
     // exposed (first version of this kernel: 0.7x the register-staged one); the global form is not tracked that way
-    __builtin_amdgcn_global_load_lds((wd_gptr)g, (wd_lptr)dst, 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((dt_gptr)g, (dt_lptr)dst, 16, 0, 0);
   };
   auto stage_advance = [&]() {
     if (++s_tx == a.tiles_x) {
@@ -163,9 +149,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_bf16_dma_kernel(const Wg
   // (first versions of this kernel: 0.65-0.75x the register-staged one).  The ordering that matters is established by
   // hand instead: vmcnt(0) + barrier once per tile (below); LDS returns reads in order, so `lgkmcnt(2)` after issuing the
   // next fragment's two reads means the current fragment has landed.
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
   struct Frag { u32x2 lo, hi; };
-  const unsigned lds0 = (unsigned)(unsigned long)(wd_lptr)lds;
+  const unsigned lds0 = (unsigned)(unsigned long)(dt_lptr)lds;
   auto frag_issue = [&](Frag& fr, unsigned base, auto imm_tag) {
     constexpr int IMM = decltype(imm_tag)::value;
     asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%3\n\tds_read_b64_tr_b16 %1, %2 offset:%4"
@@ -192,7 +177,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_bf16_dma_kernel(const Wg
     const unsigned yb = lds0 + cur + bbase + (wpx * WROWS * TW) * 128;
     // dy fragments of this wave's rows: read once per tile
     Frag fbr[WROWS][XS];
-    wd_static_for<0, WROWS * XS>([&](auto ic) {
+    dt_static_for<0, WROWS * XS>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       frag_issue(fbr[i / XS][i % XS], yb, std::integral_constant<int, ((i / XS) * TW + 16 * (i % XS)) * 128>{});
     });
@@ -202,7 +187,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad_bf16_dma_kernel(const Wg
     Frag far[2];
     frag_issue(far[0], xa0, std::integral_constant<int, 0>{});
     bf16x8 fb[WROWS][XS];
-    wd_static_for<0, NF>([&](auto fc) {
+    dt_static_for<0, NF>([&](auto fc) {
       constexpr int f = decltype(fc)::value;
       constexpr int kw = f % 3, xs = (f / 3) % XS, hr = f / (3 * XS);
       if constexpr (f + 1 < NF) {

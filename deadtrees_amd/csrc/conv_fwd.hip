@@ -16,7 +16,7 @@
 //   * epilogue: coalesced 128-B row stores + per-channel sum / sum-of-squares partials for the
 //     following BatchNorm (wave64 shuffle -> LDS -> one row per workgroup; reduced later in fixed
 //     order, so results are run-to-run deterministic — no float atomics).
-#include "common.h"
+#include "conv_host.h"
 
 struct ConvArgs {
   const float* src0;
@@ -596,54 +596,81 @@ __global__ __launch_bounds__(256, (KS == 3 && STRIDE == 1 && CK == 8 && TN == 32
 }
 
 // ---------------------------------------------------------------- host dispatch
-struct ConvCfg {
-  int tw, tn;
-};
-
 // stride-2 3x3 layers with maps of at most 8 x 8 output pixels: four images share an 8 x 32 tile (ConvArgs::pack)
 static int conv_packs(const dt_conv_desc* d) {
   return d->ksize == 3 && d->stride == 2 && d->pad == 1 && d->mode0 == 0 && d->C1 == 0 && d->Ho <= 8 && d->Wo <= 8 &&
          d->Hin <= 16 && d->B >= 2;
 }
 
-static ConvCfg pick_cfg(const dt_conv_desc* d) {
-  ConvCfg c;
-  c.tw = d->Wo > 16 ? 32 : (d->Wo > 8 ? 16 : 8);
-  int tn = d->Cout >= 64 ? 64 : 32;
-  if (d->cout_split > 0 && (d->cout_split % 64) != 0) tn = 32;
-  // keep >= 2 workgroups per CU in flight when the grid is small (deep layers: few spatial tiles)
-  if (tn == 64) {
-    const int th = 256 / c.tw;
-    const long sp = conv_packs(d) ? dt_cdiv(d->B, 4) : (long)d->B * dt_cdiv(d->Ho, th) * dt_cdiv(d->Wo, c.tw);
-    const long wgs = sp * dt_cdiv(d->Cout, 64);
-    if (wgs < 512) tn = 32;
-  }
-  c.tn = tn;
-  return c;
-}
-
 static int validate(const dt_conv_desc* d) {
-  DT_REQUIRE(d != nullptr, "conv: null descriptor");
-  DT_REQUIRE(d->B > 0 && d->Hin > 0 && d->Win > 0 && d->C0 > 0 && d->C1 >= 0 && d->Cout > 0, "conv: bad sizes");
+  DT_TRY(dt_conv_validate_null(d, "conv"));
+  DT_TRY(dt_conv_validate_sizes(d, "conv"));
   DT_REQUIRE(d->ksize == 1 || d->ksize == 3 || d->ksize == 7, "conv: ksize %d unsupported", d->ksize);
   DT_REQUIRE(d->stride == 1 || d->stride == 2, "conv: stride %d unsupported", d->stride);
   DT_REQUIRE(d->mode0 >= 0 && d->mode0 <= 2, "conv: mode0 %d", d->mode0);
-  DT_REQUIRE(d->mode0 == 0 || ((d->Hin & 1) == 0 && (d->Win & 1) == 0), "conv: mode0 needs even Hin/Win");
-  const int ho = (d->Hin + 2 * d->pad - d->ksize) / d->stride + 1;
-  const int wo = (d->Win + 2 * d->pad - d->ksize) / d->stride + 1;
+  DT_TRY(dt_conv_validate_even(d, "conv"));
+  int ho, wo;
+  dt_conv_out_size(d, &ho, &wo);
   DT_REQUIRE(ho == d->Ho && wo == d->Wo, "conv: Ho/Wo (%d,%d) != expected (%d,%d)", d->Ho, d->Wo, ho, wo);
   DT_REQUIRE(d->C1 == 0 || (d->C0 % 16) == 0, "conv: concat needs C0 %% 16 == 0");
-  DT_REQUIRE(d->cout_split == 0 || ((d->cout_split % 32) == 0 && d->cout_split < d->Cout),
-             "conv: cout_split must be a multiple of 32 below Cout");
+  DT_TRY(dt_conv_validate_split(d, "conv"));
   DT_REQUIRE(d->ksize != 7 || (d->stride == 2 && d->C1 == 0 && d->C0 <= 4), "conv: 7x7 only as the stem");
   return DT_OK;
 }
 
-extern "C" int dt_conv2d_stat_rows(const dt_conv_desc* d) {
-  if (validate(d) != DT_OK) return DT_EINVAL;
-  if (dt_conv2d_narrow_supported(d)) return dt_conv2d_narrow_rows(d);   // one row per persistent workgroup (upper bound)
-  ConvCfg c = pick_cfg(d);
-  return d->B * dt_cdiv(d->Ho, 256 / c.tw) * dt_cdiv(d->Wo, c.tw);
+// The ONE place that decides which kernel a (validated) descriptor runs on and with which tiles: the launch, the
+// statistics-row count the engine sizes its buffers from, dt_conv2d_config and dt_conv2d_uses_zi all read it.
+enum ConvFamily { CONV_NARROW, CONV_N16, CONV_ZI, CONV_TILED, CONV_STEM };
+struct ConvPlan {
+  ConvFamily family;
+  int tw, tn, ck;   // pixel-tile width (tile = tw x 256/tw pixels), output channels per workgroup, channels per K step
+  int pack;         // conv_packs
+  int n_tiles;      // channel tiles of the grid (tiled / zero-insertion / stem)
+  int rows;         // rows of the BatchNorm statistics buffer
+};
+
+// affine: the launch applies an eval-mode BatchNorm in the epilogue (dt_conv2d_affine), out_bf16: it stores bf16
+// (dt_conv2d_out_bf16) — the lean kernels of conv_narrow.hip have neither epilogue.  The queries ask with both false.
+static ConvPlan conv_plan(const dt_conv_desc* d, bool affine, bool out_bf16) {
+  ConvPlan p;
+  p.pack = conv_packs(d);
+  p.tw = d->Wo > 16 ? 32 : (d->Wo > 8 ? 16 : 8);
+  p.tn = d->Cout >= 64 ? 64 : 32;
+  if (d->cout_split > 0 && (d->cout_split % 64) != 0) p.tn = 32;
+  // keep >= 2 workgroups per CU in flight when the grid is small (deep layers: few spatial tiles)
+  if (p.tn == 64) {
+    const int th = 256 / p.tw;
+    const long sp = p.pack ? dt_cdiv(d->B, 4) : (long)d->B * dt_cdiv(d->Ho, th) * dt_cdiv(d->Wo, p.tw);
+    const long wgs = sp * dt_cdiv(d->Cout, 64);
+    if (wgs < 512) p.tn = 32;
+  }
+  p.n_tiles = dt_cdiv(d->Cout, p.tn);   // (the stem's grid keeps this count although its kernel is always 64 wide)
+  p.rows = d->B * dt_cdiv(d->Ho, 256 / p.tw) * dt_cdiv(d->Wo, p.tw);   // packed tiles: still one row per image
+  if (!affine && !out_bf16 && dt_conv2d_narrow_supported(d)) {
+    // Cin, Cout in {16, 32} at full resolution: conv3x3_f32_narrow_kernel<CB, NB, ...>, reported as ck = 1000 + 10 CB + NB
+    // (2000 +: conv3x3_f32_upc_kernel, the sub-pixel form); one statistics row per persistent workgroup (upper bound)
+    p.family = CONV_NARROW;
+    p.tw = 32;
+    p.tn = d->Cout;
+    p.ck = (dt_conv2d_narrow_subpixel(d) ? 2000 : 1000) + 10 * (d->C0 / 16) + d->Cout / 16;
+    p.rows = dt_conv2d_narrow_rows(d);
+  } else if (!affine && dt_conv2d_n16_supported(d)) {   // conv_fwd_n16_kernel: 8x32 pixel tile, 16 output channels, CK 16
+    p.family = CONV_N16;
+    p.tw = 32;
+    p.tn = 16;
+    p.ck = 16;
+  } else if (d->ksize == 7) {
+    p.family = CONV_STEM;
+    p.tn = 64;
+    p.ck = 4;
+  } else if (d->mode0 == 2 && d->stride == 1 && p.tw == 32 && d->C0 > 32) {   // transposed conv: parity-class tiles
+    p.family = CONV_ZI;
+    p.ck = 16;
+  } else {
+    p.family = CONV_TILED;
+    p.ck = (d->ksize == 3 && (d->stride == 2 || (d->C0 + d->C1 <= 32 && p.tn == 32))) ? 8 : 16;
+  }
+  return p;
 }
 
 template <int KS, int STRIDE, int TW, int TN, int CK, bool ZI = false>
@@ -667,21 +694,63 @@ static int launch(const ConvArgs& a, hipStream_t st) {
 }
 
 template <int KS, int STRIDE, int CK>
-static int launch_tw_tn(const ConvArgs& a, const ConvCfg& c, hipStream_t st) {
-  if (c.tn == 64) {
-    if (c.tw == 32) return launch<KS, STRIDE, 32, 64, CK>(a, st);
-    if (c.tw == 16) return launch<KS, STRIDE, 16, 64, CK>(a, st);
+static int launch_tw_tn(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
+  if (p.tn == 64) {
+    if (p.tw == 32) return launch<KS, STRIDE, 32, 64, CK>(a, st);
+    if (p.tw == 16) return launch<KS, STRIDE, 16, 64, CK>(a, st);
     return launch<KS, STRIDE, 8, 64, CK>(a, st);
   }
-  if (c.tw == 32) return launch<KS, STRIDE, 32, 32, CK>(a, st);
-  if (c.tw == 16) return launch<KS, STRIDE, 16, 32, CK>(a, st);
+  if (p.tw == 32) return launch<KS, STRIDE, 32, 32, CK>(a, st);
+  if (p.tw == 16) return launch<KS, STRIDE, 16, 32, CK>(a, st);
   return launch<KS, STRIDE, 8, 32, CK>(a, st);
 }
 
 static int conv2d_impl(const dt_conv_desc* d, const float* src0, const float* src1, const float* w, float* out0,
                        float* out1, float* stats, const float* in_scale, const float* in_shift, void* out_bf16,
                        void* stream, const dt_bn_bwd_fuse* fuse = nullptr, const float* aff_scale = nullptr,
-                       const float* aff_shift = nullptr, int aff_relu = 0);
+                       const float* aff_shift = nullptr, int aff_relu = 0) {
+  DT_TRY(validate(d));
+  DT_REQUIRE(src0 && w && out0, "conv: null pointer");
+  DT_REQUIRE(d->C1 == 0 || src1, "conv: src1 missing");
+  DT_REQUIRE(d->cout_split == 0 || out1, "conv: out1 missing");
+  DT_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "conv: in_scale/in_shift must come together");
+  DT_REQUIRE(in_scale == nullptr || (d->ksize == 3 && d->stride == 1 && d->mode0 != 2 && d->C0 <= DT_TF_MAXC),
+             "conv: input transform needs a 3x3 stride-1 layer with C0 <= %d and no zero-insertion", DT_TF_MAXC);
+  hipStream_t st = (hipStream_t)stream;
+  // the narrow layers have a BatchNorm + ReLU form of their own
+  if (aff_scale != nullptr && aff_relu && src1 == nullptr && dt_conv2d_narrow_supported(d))
+    return dt_conv2d_narrow_affine(d, src0, w, out0, aff_scale, aff_shift, nullptr, nullptr, stream);
+  const ConvPlan p = conv_plan(d, aff_scale != nullptr, out_bf16 != nullptr);
+  if (p.family == CONV_NARROW) return dt_conv2d_narrow_launch(d, src0, w, out0, stats, in_scale, in_shift, st, fuse);
+  if (p.family == CONV_N16) return dt_conv2d_n16_launch(d, src0, w, out0, stats, in_scale, in_shift, st, fuse);
+  ConvArgs a;
+  a.bnb = fuse ? *fuse : dt_bn_bwd_fuse{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  a.src0 = src0; a.src1 = src1; a.w = w; a.out0 = out0; a.out1 = out1; a.stats = stats;
+  a.in_scale = in_scale; a.in_shift = in_shift; a.out0_bf16 = (__bf16*)out_bf16;
+  a.aff_scale = aff_scale; a.aff_shift = aff_shift; a.aff_relu = aff_relu;
+  a.B = d->B; a.Hin = d->Hin; a.Win = d->Win; a.C0 = d->C0; a.C1 = d->C1; a.mode0 = d->mode0;
+  a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.cout_split = d->cout_split; a.pad = d->pad;
+  a.accumulate = d->accumulate;
+  a.tiles_x = dt_cdiv(d->Wo, p.tw);
+  a.tiles_y = dt_cdiv(d->Ho, 256 / p.tw);
+  a.n_tiles = p.n_tiles;
+  a.pack = p.pack;
+  a.P = p.rows;                                  // statistics rows (packed tiles: still one per image)
+  a.sp_tiles = a.pack ? dt_cdiv(d->B, 4) : a.P;  // spatial tiles of the grid
+  // (the instantiations are emitted in the order of the lines below)
+  if (p.family == CONV_ZI) {
+    if (d->ksize == 3) return p.tn == 64 ? launch<3, 1, 32, 64, 16, true>(a, st) : launch<3, 1, 32, 32, 16, true>(a, st);
+    if (d->ksize == 1) return p.tn == 64 ? launch<1, 1, 32, 64, 16, true>(a, st) : launch<1, 1, 32, 32, 16, true>(a, st);
+  }
+  if (d->ksize == 3 && d->stride == 1) return p.ck == 8 ? launch_tw_tn<3, 1, 8>(a, p, st) : launch_tw_tn<3, 1, 16>(a, p, st);
+  if (d->ksize == 3 && d->stride == 2) return launch_tw_tn<3, 2, 8>(a, p, st);
+  if (d->ksize == 1 && d->stride == 2) return launch_tw_tn<1, 2, 16>(a, p, st);
+  if (d->ksize == 1 && d->stride == 1) return launch_tw_tn<1, 1, 16>(a, p, st);
+  // CONV_STEM: one 64-channel kernel per tile width
+  if (p.tw == 32) return launch<7, 2, 32, 64, 4>(a, st);
+  if (p.tw == 16) return launch<7, 2, 16, 64, 4>(a, st);
+  return launch<7, 2, 8, 64, 4>(a, st);
+}
 
 // inference: out = [relu](conv(x) * scale + shift) in one launch — eval-mode BatchNorm (+ ReLU) of the layers that are
 // neither Winograd layers (dt_conv2d_winograd_affine) nor narrow ones (dt_conv2d_narrow_affine): the stem, the stride-2
@@ -713,56 +782,34 @@ extern "C" int dt_conv2d_bn_bwd(const dt_conv_desc* d, const float* src0, const 
   return conv2d_impl(d, src0, nullptr, w, out0, nullptr, red, nullptr, nullptr, nullptr, stream, fuse);
 }
 
-static int conv2d_impl(const dt_conv_desc* d, const float* src0, const float* src1, const float* w, float* out0,
-                       float* out1, float* stats, const float* in_scale, const float* in_shift, void* out_bf16,
-                       void* stream, const dt_bn_bwd_fuse* fuse, const float* aff_scale, const float* aff_shift,
-                       int aff_relu) {
-  int rc = validate(d);
-  if (rc != DT_OK) return rc;
-  DT_REQUIRE(src0 && w && out0, "conv: null pointer");
-  DT_REQUIRE(d->C1 == 0 || src1, "conv: src1 missing");
-  DT_REQUIRE(d->cout_split == 0 || out1, "conv: out1 missing");
-  DT_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "conv: in_scale/in_shift must come together");
-  DT_REQUIRE(in_scale == nullptr || (d->ksize == 3 && d->stride == 1 && d->mode0 != 2 && d->C0 <= DT_TF_MAXC),
-             "conv: input transform needs a 3x3 stride-1 layer with C0 <= %d and no zero-insertion", DT_TF_MAXC);
-  if (aff_scale != nullptr && aff_relu && src1 == nullptr && dt_conv2d_narrow_supported(d))
-    return dt_conv2d_narrow_affine(d, src0, w, out0, aff_scale, aff_shift, nullptr, nullptr, stream);
-  if (aff_scale == nullptr && out_bf16 == nullptr && dt_conv2d_narrow_supported(d))   // Cin, Cout in {16, 32} at full resolution: the lean kernel
-    return dt_conv2d_narrow_launch(d, src0, w, out0, stats, in_scale, in_shift, (hipStream_t)stream, fuse);
-  if (aff_scale == nullptr && dt_conv2d_n16_supported(d))
-    return dt_conv2d_n16_launch(d, src0, w, out0, stats, in_scale, in_shift, (hipStream_t)stream, fuse);
-  ConvCfg c = pick_cfg(d);
-  ConvArgs a;
-  a.bnb = fuse ? *fuse : dt_bn_bwd_fuse{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  a.src0 = src0; a.src1 = src1; a.w = w; a.out0 = out0; a.out1 = out1; a.stats = stats;
-  a.in_scale = in_scale; a.in_shift = in_shift; a.out0_bf16 = (__bf16*)out_bf16;
-  a.aff_scale = aff_scale; a.aff_shift = aff_shift; a.aff_relu = aff_relu;
-  a.B = d->B; a.Hin = d->Hin; a.Win = d->Win; a.C0 = d->C0; a.C1 = d->C1; a.mode0 = d->mode0;
-  a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.cout_split = d->cout_split; a.pad = d->pad;
-  a.accumulate = d->accumulate;
-  a.tiles_x = dt_cdiv(d->Wo, c.tw);
-  a.tiles_y = dt_cdiv(d->Ho, 256 / c.tw);
-  a.n_tiles = dt_cdiv(d->Cout, c.tn);
-  a.pack = conv_packs(d);
-  a.P = d->B * a.tiles_x * a.tiles_y;            // statistics rows (packed tiles: still one per image)
-  a.sp_tiles = a.pack ? dt_cdiv(d->B, 4) : a.P;  // spatial tiles of the grid
-  hipStream_t st = (hipStream_t)stream;
-  if (d->mode0 == 2 && d->stride == 1 && c.tw == 32 && d->C0 > 32) {   // transposed conv: parity-class tiles
-    if (d->ksize == 3) return c.tn == 64 ? launch<3, 1, 32, 64, 16, true>(a, st) : launch<3, 1, 32, 32, 16, true>(a, st);
-    if (d->ksize == 1) return c.tn == 64 ? launch<1, 1, 32, 64, 16, true>(a, st) : launch<1, 1, 32, 32, 16, true>(a, st);
-  }
-  if (d->ksize == 3 && d->stride == 1)
-    return (d->C0 + d->C1 <= 32 && c.tn == 32) ? launch_tw_tn<3, 1, 8>(a, c, st) : launch_tw_tn<3, 1, 16>(a, c, st);
-  if (d->ksize == 3 && d->stride == 2) return launch_tw_tn<3, 2, 8>(a, c, st);
-  if (d->ksize == 1 && d->stride == 2) return launch_tw_tn<1, 2, 16>(a, c, st);
-  if (d->ksize == 1 && d->stride == 1) return launch_tw_tn<1, 1, 16>(a, c, st);
-  if (d->ksize == 7) {
-    if (c.tw == 32) return launch<7, 2, 32, 64, 4>(a, st);
-    if (c.tw == 16) return launch<7, 2, 16, 64, 4>(a, st);
-    return launch<7, 2, 8, 64, 4>(a, st);
-  }
-  dt_set_error("conv: configuration not implemented");
-  return DT_ENOSYS;
+// fp32 operands and accumulation, bf16 output (+ fp32 BatchNorm partial statistics): the stem of the bf16 path
+extern "C" int dt_conv2d_out_bf16(const dt_conv_desc* d, const float* src0, const float* w_hwio, void* out_bf16,
+                                  float* stats, void* stream) {
+  DT_REQUIRE(d && d->cout_split == 0 && d->accumulate == 0 && d->C1 == 0 && out_bf16, "conv_out_bf16: bad args");
+  DT_REQUIRE(!dt_conv2d_n16_supported(d), "conv_out_bf16: not built for the 16-wide kernels");
+  return conv2d_impl(d, src0, nullptr, w_hwio, reinterpret_cast<float*>(out_bf16), nullptr, stats, nullptr, nullptr,
+                     out_bf16, stream);
+}
+
+extern "C" int dt_conv2d_stat_rows(const dt_conv_desc* d) {
+  if (validate(d) != DT_OK) return DT_EINVAL;
+  return conv_plan(d, false, false).rows;
+}
+
+// 1 when dt_conv2d runs the parity-class (zero-insertion) tiles for this descriptor
+extern "C" int dt_conv2d_uses_zi(const dt_conv_desc* d) {
+  if (validate(d) != DT_OK) return 0;
+  return conv_plan(d, false, false).family == CONV_ZI;
+}
+
+// which kernel instantiation dt_conv2d launches for a descriptor (profiling / roofline attribution)
+extern "C" int dt_conv2d_config(const dt_conv_desc* d, int* tw, int* tn, int* ck) {
+  DT_TRY(validate(d));
+  const ConvPlan p = conv_plan(d, false, false);
+  if (tw) *tw = p.tw;
+  if (tn) *tn = p.tn;
+  if (ck) *ck = p.ck;
+  return DT_OK;
 }
 
 // ---------------------------------------------------------------- weight flip+transpose for dgrad
@@ -795,41 +842,3 @@ extern "C" int dt_weight_flip_transpose(const float* w, float* wd, int ksize, in
   return DT_OK;
 }
 
-// which kernel instantiation dt_conv2d launches for a descriptor (profiling / roofline attribution)
-// fp32 operands and accumulation, bf16 output (+ fp32 BatchNorm partial statistics): the stem of the bf16 path
-extern "C" int dt_conv2d_out_bf16(const dt_conv_desc* d, const float* src0, const float* w_hwio, void* out_bf16,
-                                  float* stats, void* stream) {
-  DT_REQUIRE(d && d->cout_split == 0 && d->accumulate == 0 && d->C1 == 0 && out_bf16, "conv_out_bf16: bad args");
-  DT_REQUIRE(!dt_conv2d_n16_supported(d), "conv_out_bf16: not built for the 16-wide kernels");
-  return conv2d_impl(d, src0, nullptr, w_hwio, reinterpret_cast<float*>(out_bf16), nullptr, stats, nullptr, nullptr,
-                     out_bf16, stream);
-}
-
-// 1 when dt_conv2d runs the parity-class (zero-insertion) tiles for this descriptor
-extern "C" int dt_conv2d_uses_zi(const dt_conv_desc* d) {
-  if (validate(d) != DT_OK) return 0;
-  ConvCfg c = pick_cfg(d);
-  return d->mode0 == 2 && d->stride == 1 && c.tw == 32 && d->C0 > 32 && (d->ksize == 3 || d->ksize == 1);
-}
-
-extern "C" int dt_conv2d_config(const dt_conv_desc* d, int* tw, int* tn, int* ck) {
-  int rc = validate(d);
-  if (rc != DT_OK) return rc;
-  ConvCfg c = pick_cfg(d);
-  if (dt_conv2d_narrow_supported(d)) {   // conv3x3_f32_narrow_kernel<CB, NB, ...>: reported as ck = 1000 + 10 CB + NB
-    if (tw) *tw = 32;
-    if (tn) *tn = d->Cout;
-    if (ck) *ck = (dt_conv2d_narrow_subpixel(d) ? 2000 : 1000) + 10 * (d->C0 / 16) + d->Cout / 16;   // 2000 +: conv3x3_f32_upc_kernel
-    return DT_OK;
-  }
-  if (dt_conv2d_n16_supported(d)) {   // conv_fwd_n16_kernel: 8x32 pixel tile, 16 output channels, CK 16
-    if (tw) *tw = 32;
-    if (tn) *tn = 16;
-    if (ck) *ck = 16;
-    return DT_OK;
-  }
-  if (tw) *tw = c.tw;
-  if (tn) *tn = d->ksize == 7 ? 64 : c.tn;
-  if (ck) *ck = d->ksize == 7 ? 4 : ((d->ksize == 3 && (d->stride == 2 || (d->C0 + d->C1 <= 32 && c.tn == 32))) ? 8 : 16);
-  return DT_OK;
-}

@@ -1,0 +1,81 @@
+// Host-side plumbing shared by the kernel files: descriptor checks, environment switches, grid sizing, alignment checks.
+// Nothing here reaches device code.
+#pragma once
+#include <stdlib.h>
+
+#include "common.h"
+
+// return the first failure of a chain of checks
+#define DT_TRY(expr)                  \
+  do {                                \
+    const int rc__ = (expr);          \
+    if (rc__ != DT_OK) return rc__;   \
+  } while (0)
+
+// ---- convolution descriptors.  Every family (fp32 direct `conv`, `conv_bf16`, `wgrad`, `wgrad_bf16`) starts with
+// dt_conv_validate_null and then runs the shared rules it has, in its own order (the first message reported is part of
+// the ABI's behaviour), followed by its own rules.  `tag` prefixes the message.
+static inline int dt_conv_validate_null(const dt_conv_desc* d, const char* tag) {
+  DT_REQUIRE(d != nullptr, "%s: null descriptor", tag);
+  return DT_OK;
+}
+static inline int dt_conv_validate_sizes(const dt_conv_desc* d, const char* tag) {
+  DT_REQUIRE(d->B > 0 && d->Hin > 0 && d->Win > 0 && d->C0 > 0 && d->C1 >= 0 && d->Cout > 0, "%s: bad sizes", tag);
+  return DT_OK;
+}
+// mode0 1 (nearest x2 up-sampling) and 2 (zero insertion) read a half-resolution source
+static inline int dt_conv_validate_even(const dt_conv_desc* d, const char* tag) {
+  DT_REQUIRE(d->mode0 == 0 || ((d->Hin & 1) == 0 && (d->Win & 1) == 0), "%s: mode0 needs even Hin/Win", tag);
+  return DT_OK;
+}
+static inline int dt_conv_validate_split(const dt_conv_desc* d, const char* tag) {
+  DT_REQUIRE(d->cout_split == 0 || ((d->cout_split % 32) == 0 && d->cout_split < d->Cout),
+             "%s: cout_split must be a multiple of 32 below Cout", tag);
+  return DT_OK;
+}
+// the output size the descriptor's input size, padding, window and stride give
+static inline void dt_conv_out_size(const dt_conv_desc* d, int* ho, int* wo) {
+  *ho = (d->Hin + 2 * d->pad - d->ksize) / d->stride + 1;
+  *wo = (d->Win + 2 * d->pad - d->ksize) / d->stride + 1;
+}
+static inline int dt_conv_validate_out(const dt_conv_desc* d, const char* tag) {
+  int ho, wo;
+  dt_conv_out_size(d, &ho, &wo);
+  DT_REQUIRE(ho == d->Ho && wo == d->Wo, "%s: Ho/Wo mismatch", tag);
+  return DT_OK;
+}
+
+// ---- NAME=0 in the environment switches a kernel family off (A/B measurements); unset or anything not starting with '0'
+// means on.  Read once per process (per call site).
+static inline bool dt_env_read_on(const char* name) {
+  const char* e = getenv(name);
+  return e == nullptr || e[0] != '0';
+}
+#define dt_env_on(NAME) ([] { static const bool on__ = dt_env_read_on(NAME); return on__; }())
+
+// ---- grid of a grid-stride element-wise launch: one 256-thread workgroup per 256 items, at least 1, at most `cap`
+static inline int dt_ew_grid(int64_t n_items, int64_t cap) {
+  const int64_t g = (n_items + 255) / 256;
+  return (int)(g < cap ? (g > 0 ? g : 1) : cap);
+}
+
+// ---- rows (pixels) per workgroup of the BatchNorm-backward reductions of both precisions: 256 for small maps, grown so
+// that a launch has at most ~2048 row blocks — the in-workgroup reduction and the second-stage row count then stay small
+// next to the streaming part
+#define BNB_RB 256
+static inline int64_t bnb_rb(int64_t n_pix) {
+  int64_t rb = BNB_RB;
+  const int64_t want = (n_pix + 2047) / 2048;
+  if (want > rb) rb = (want + BNB_RB - 1) / BNB_RB * BNB_RB;
+  return rb;
+}
+
+// ---- 16-byte alignment of the arrays a kernel reads with 16-byte loads (a null pointer counts as aligned)
+template <class... P>
+static inline bool dt_aligned16(const P*... p) {
+  return ((... | (uintptr_t)p) & 15) == 0;
+}
+static inline bool dt_fuse_aligned16(const dt_bn_bwd_fuse* f) {
+  return dt_aligned16(f->mean, f->invstd, f->act_scale, f->act_shift);
+}
+#define DT_REQUIRE_COEF_ALIGNED(ok, tag) DT_REQUIRE(ok, tag ": per-channel arrays must be 16-byte aligned")

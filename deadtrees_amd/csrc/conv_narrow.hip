@@ -9,7 +9,7 @@
 // epilogue; split-K weight gradient with deterministic slab reduction.
 // Reference ops replaced: ATen conv2d / convolution_backward of smp UnetDecoder block 4
 // (deadtrees/network/segmodel.py:214; twin deadtrees/network/extra/resunet/decoder.py:40-52).
-#include "common.h"
+#include "conv_host.h"
 
 struct NarrowArgs {
   const float* src0;
@@ -494,14 +494,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_f32_upc_kernel(const Nar
     }
 }
 
-static bool nl_upc_enabled();
+static bool nl_upc_enabled() { return dt_env_on("DT_FP32_SUBPIXEL"); }
 static int wg_upc(const dt_conv_desc* d) {   // 1: the sub-pixel weight-gradient kernel takes this (n16-supported) layer
-  static const int on = [] {
-    const char* e = getenv("DT_FP32_SUBPIXEL_WGRAD");
-    return (e == nullptr || e[0] != '0') ? 1 : 0;
-  }();
-  return on && nl_upc_enabled() && d->mode0 == 1 && d->C1 == 0 && (d->C0 == 16 || d->C0 == 32) && d->Cout == 16 &&
-         ((d->Hin | d->Win) & 1) == 0 && d->Ho == d->Hin && d->Wo == d->Win && d->Win >= 64;
+  return dt_env_on("DT_FP32_SUBPIXEL_WGRAD") && nl_upc_enabled() && d->mode0 == 1 && d->C1 == 0 &&
+         (d->C0 == 16 || d->C0 == 32) && d->Cout == 16 && ((d->Hin | d->Win) & 1) == 0 && d->Ho == d->Hin &&
+         d->Wo == d->Win && d->Win >= 64;
 }
 
 int dt_wgrad_n16_cfg(const dt_conv_desc* d, int* ksplit, int* parts) {
@@ -776,13 +773,7 @@ __global__ __launch_bounds__(256, (CB * NB == 1) ? 3 : 2) void conv3x3_f32_narro
   }
 }
 
-static bool nl_enabled() {
-  static const int on = [] {
-    const char* e = getenv("DT_FP32_NARROW");
-    return (e == nullptr || e[0] != '0') ? 1 : 0;
-  }();
-  return on != 0;
-}
+static bool nl_enabled() { return dt_env_on("DT_FP32_NARROW"); }
 
 extern "C" int dt_conv2d_narrow_supported(const dt_conv_desc* d) {
   if (!nl_enabled() || d == nullptr) return 0;
@@ -835,17 +826,9 @@ static int nl_launch(const NarrowLeanArgs& a, int total, bool tf, int epi, hipSt
 
 int dt_conv2d_narrow_launch_upc(const dt_conv_desc* d, const NarrowLeanArgs& a, int total, bool tf, int epi, hipStream_t st);
 
-static bool nl_upc_enabled();
 // 1 when the (supported) narrow layer runs in its sub-pixel form
 int dt_conv2d_narrow_subpixel(const dt_conv_desc* d) {
   return d->mode0 == 1 && nl_upc_enabled() && ((d->Hin | d->Win) & 1) == 0 && d->C0 * d->Cout <= 512;
-}
-static bool nl_upc_enabled() {
-  static const int on = [] {
-    const char* e = getenv("DT_FP32_SUBPIXEL");
-    return (e == nullptr || e[0] != '0') ? 1 : 0;
-  }();
-  return on != 0;
 }
 
 int dt_conv2d_narrow_launch(const dt_conv_desc* d, const float* src0, const float* w, float* out, float* stats,
@@ -1319,11 +1302,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f32_upc_dgrad_kernel(const Upc
 // `d` describes the FORWARD convolution (mode0 = 1, C0 = CI low-resolution input channels, Cout = CO, Hin x Win = the
 // full-resolution map)
 extern "C" int dt_conv2d_upsampled_dgrad_supported(const dt_conv_desc* d) {
-  static const int on = [] {
-    const char* e = getenv("DT_FP32_SUBPIXEL_DGRAD");
-    return (e == nullptr || e[0] != '0') ? 1 : 0;
-  }();
-  if (!on || !nl_enabled() || !nl_upc_enabled() || d == nullptr) return 0;
+  if (!dt_env_on("DT_FP32_SUBPIXEL_DGRAD") || !nl_enabled() || !nl_upc_enabled() || d == nullptr) return 0;
   if (d->ksize != 3 || d->stride != 1 || d->pad != 1 || d->mode0 != 1 || d->C1 != 0 || d->cout_split != 0) return 0;
   if ((d->C0 != 16 && d->C0 != 32) || (d->Cout != 16 && d->Cout != 32) || d->C0 * d->Cout > 512) return 0;
   if (((d->Hin | d->Win) & 1) != 0 || d->Ho != d->Hin || d->Wo != d->Win || d->Win < 32 || d->Hin < 8) return 0;

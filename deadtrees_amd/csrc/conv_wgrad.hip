@@ -9,7 +9,7 @@
 // halo tile is re-used by all KS*KS taps.  The pixel dimension is split over workgroups (and
 // optionally over the waves of a workgroup); each split writes one fp32 partial slab and a second
 // kernel sums the slabs in a fixed order -> run-to-run deterministic, no float atomics.
-#include "common.h"
+#include "conv_host.h"
 
 struct WgradArgs {
   const float* src0;
@@ -263,8 +263,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_stem_kernel(const WgradArgs
       if (idx < YT && oy < a.Ho && ox < a.Wo && c < a.Cout) {
         const size_t o = (((size_t)b * a.Ho + oy) * a.Wo + ox) * a.Cout + c;
         if (a.dy_bf16 != nullptr) {
-          typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-          const bf16x4_t q = *reinterpret_cast<const bf16x4_t*>(a.dy_bf16 + o);
+          const bf16x4 q = *reinterpret_cast<const bf16x4*>(a.dy_bf16 + o);
 #pragma unroll
           for (int k = 0; k < 4; ++k) v[k] = (float)q[k];
         } else {
@@ -322,19 +321,16 @@ struct WgCfg {
 };
 
 static int wg_validate(const dt_conv_desc* d) {
-  DT_REQUIRE(d != nullptr, "wgrad: null descriptor");
-  DT_REQUIRE(d->B > 0 && d->Hin > 0 && d->Win > 0 && d->C0 > 0 && d->C1 >= 0 && d->Cout > 0, "wgrad: bad sizes");
+  DT_TRY(dt_conv_validate_null(d, "wgrad"));
+  DT_TRY(dt_conv_validate_sizes(d, "wgrad"));
   DT_REQUIRE((d->ksize == 3 && (d->stride == 1 || d->stride == 2)) || (d->ksize == 1 && (d->stride == 1 || d->stride == 2)) ||
                  (d->ksize == 7 && d->stride == 2 && d->C1 == 0 && d->C0 <= 4 && d->mode0 == 0),
              "wgrad: ksize/stride (%d,%d) unsupported", d->ksize, d->stride);
   DT_REQUIRE(d->ksize == 7 || ((d->C0 & 3) == 0 && (d->C1 & 3) == 0), "wgrad: channels must be multiples of 4");
   DT_REQUIRE((d->Cout & 3) == 0, "wgrad: Cout must be a multiple of 4");
   DT_REQUIRE(d->mode0 >= 0 && d->mode0 <= 2, "wgrad: mode0");
-  DT_REQUIRE(d->mode0 == 0 || ((d->Hin & 1) == 0 && (d->Win & 1) == 0), "wgrad: mode0 needs even Hin/Win");
-  const int ho = (d->Hin + 2 * d->pad - d->ksize) / d->stride + 1;
-  const int wo = (d->Win + 2 * d->pad - d->ksize) / d->stride + 1;
-  DT_REQUIRE(ho == d->Ho && wo == d->Wo, "wgrad: Ho/Wo mismatch");
-  return DT_OK;
+  DT_TRY(dt_conv_validate_even(d, "wgrad"));
+  return dt_conv_validate_out(d, "wgrad");
 }
 
 static WgCfg wg_cfg(const dt_conv_desc* d) {
@@ -420,24 +416,6 @@ static int wg_dispatch(const WgradArgs& a, const WgCfg& c, int grid, hipStream_t
 
 static int wgrad_impl(const dt_conv_desc* d, const float* src0, const float* src1, const float* dy, const void* dy_bf16,
                       float* dw, float* workspace, size_t workspace_bytes, const float* in_scale,
-                      const float* in_shift, void* stream);
-
-extern "C" int dt_conv2d_wgrad(const dt_conv_desc* d, const float* src0, const float* src1, const float* dy,
-                               float* dw, float* workspace, size_t workspace_bytes, const float* in_scale,
-                               const float* in_shift, void* stream) {
-  return wgrad_impl(d, src0, src1, dy, nullptr, dw, workspace, workspace_bytes, in_scale, in_shift, stream);
-}
-
-// stem (7x7/2, fp32 image) weight gradient with dy in bf16 — the bf16 training path
-extern "C" int dt_conv2d_wgrad_stem_dy_bf16(const dt_conv_desc* d, const float* src0, const void* dy_bf16, float* dw,
-                                            float* workspace, size_t workspace_bytes, void* stream) {
-  DT_REQUIRE(d && d->ksize == 7 && dy_bf16, "wgrad_stem_dy_bf16: 7x7 stem only");
-  return wgrad_impl(d, src0, nullptr, reinterpret_cast<const float*>(dy_bf16), dy_bf16, dw, workspace, workspace_bytes,
-                    nullptr, nullptr, stream);
-}
-
-static int wgrad_impl(const dt_conv_desc* d, const float* src0, const float* src1, const float* dy, const void* dy_bf16,
-                      float* dw, float* workspace, size_t workspace_bytes, const float* in_scale,
                       const float* in_shift, void* stream) {
   int rc = wg_validate(d);
   if (rc != DT_OK) return rc;
@@ -485,9 +463,22 @@ static int wgrad_impl(const dt_conv_desc* d, const float* src0, const float* src
     slabs = stage;
     nslabs = c.parts2;
   }
-  int64_t g = (E + 255) / 256;
-  if (g > 256 * 8) g = 256 * 8;
+  const int g = dt_ew_grid(E, 256 * 8);
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)g), dim3(256), 0, st, slabs, dw, nslabs, E);
   DT_LAUNCH_CHECK();
   return DT_OK;
+}
+
+extern "C" int dt_conv2d_wgrad(const dt_conv_desc* d, const float* src0, const float* src1, const float* dy,
+                               float* dw, float* workspace, size_t workspace_bytes, const float* in_scale,
+                               const float* in_shift, void* stream) {
+  return wgrad_impl(d, src0, src1, dy, nullptr, dw, workspace, workspace_bytes, in_scale, in_shift, stream);
+}
+
+// stem (7x7/2, fp32 image) weight gradient with dy in bf16 — the bf16 training path
+extern "C" int dt_conv2d_wgrad_stem_dy_bf16(const dt_conv_desc* d, const float* src0, const void* dy_bf16, float* dw,
+                                            float* workspace, size_t workspace_bytes, void* stream) {
+  DT_REQUIRE(d && d->ksize == 7 && dy_bf16, "wgrad_stem_dy_bf16: 7x7 stem only");
+  return wgrad_impl(d, src0, nullptr, reinterpret_cast<const float*>(dy_bf16), dy_bf16, dw, workspace, workspace_bytes,
+                    nullptr, nullptr, stream);
 }

@@ -27,15 +27,9 @@
 // Measured (B=32, scripts/bench_wino.py, TF/s of direct-convolution FLOPs, vs conv_fwd.hip): 64->64@128^2 167 vs 103,
 // 128->128@64^2 190 vs 110, 256->256@32^2 204 vs 114, 512->512@16^2 209 vs 110, 768->256@32^2 240 vs 127; matrix-pipe
 // utilisation 57 % (PMC) on 16/36 of the multiplies.  What limits it and what was tried: DESIGN.md section 5.
-#include "common.h"
+#include "conv_host.h"
 #include "conv_wino.h"
 
-#include <type_traits>
-
-typedef const void __attribute__((address_space(1)))* wn_gptr;
-typedef void __attribute__((address_space(3)))* wn_lptr;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 #define WN_PS 288                      // floats per (position, k-half) plane: 64 x 4 + 32 (bank skew for the V writes)
 #define WN_BUF (32 * WN_PS)            // one operand image of one chunk: 36,864 B
@@ -65,20 +59,6 @@ struct WinoArgs {
   unsigned obytes0, obytes1; // sizes of the two outputs
   unsigned ubytes;           // size of the transformed weights
 };
-
-// compile-time loop: the slot schedule below indexes register arrays (accumulators, patch pixels) with k — an ordinary
-// loop that hipcc declines to unroll completely would push them to scratch memory
-template <int K, int N, class F>
-__device__ __forceinline__ void wn_static_for(F&& f) {
-  if constexpr (K < N) {
-    f(std::integral_constant<int, K>{});
-    wn_static_for<K + 1, N>(f);
-  }
-}
-
-__device__ __forceinline__ void wn_dma16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((wn_gptr)g, (wn_lptr)l, 16, 0, 0);
-}
 
 // EPI: 0 store (+ BatchNorm statistics, split outputs); 1 store + fused BatchNorm-backward sums (virtual activation);
 //      2 gradient join (out0 += ...); 3 join + BatchNorm-backward sums (stored activation);
@@ -275,7 +255,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
     const int pos = plane >> 1, k = plane & 1;
     const int ch = __builtin_amdgcn_readfirstlane(w_chunk);
     const int soff = ((pos * nch + ch) * 2 + k) * a.Cout * 16;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsu, (wn_lptr)(Ud + plane * WN_PS), 16, u_voff, soff, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsu, (dt_lptr)(Ud + plane * WN_PS), 16, u_voff, soff, 0, 0);
   };
   auto advance_weights = [&]() {
     if (++w_chunk == nch) {
@@ -335,7 +315,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
     f32x4 fa[2], fb[2];
     fa[0] = *reinterpret_cast<const f32x4*>(Vc);
     fb[0] = *reinterpret_cast<const f32x4*>(Uc);
-    wn_static_for<0, 64>([&](auto kc) {
+    dt_static_for<0, 64>([&](auto kc) {
       constexpr int k = decltype(kc)::value;
       constexpr int p = k >> 2, j = k & 3, cur = p & 1;
       acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][j], fb[cur][j], acc[p], 0, 0, 0);
@@ -805,12 +785,8 @@ extern "C" int dt_conv2d_winograd_affine(const dt_conv_desc* d, const float* src
 // Cout - cout_split] the skip's gradient.  One launch, per tile epilogue form 6 or the plain store; replaces
 // dt_conv2d_winograd (split outputs) + dt_upsample2x_bwd_bn.  P = dt_conv2d_winograd_upsampled_dgrad_rows(d).
 static int wn_updgrad_ok(const dt_conv_desc* d) {
-  static const int on = [] {
-    const char* e = getenv("DT_FP32_WINO_UPSAMPLE_BWD");
-    return (e == nullptr || e[0] != '0') ? 1 : 0;
-  }();
-  return on && dt_conv2d_winograd_supported(d) && d->mode0 == 0 && d->C1 == 0 && d->accumulate == 0 && d->cout_split > 0 &&
-         (d->cout_split % 64) == 0 && ((d->Hin | d->Win) & 1) == 0 && !wn_pack(d);
+  return dt_env_on("DT_FP32_WINO_UPSAMPLE_BWD") && dt_conv2d_winograd_supported(d) && d->mode0 == 0 && d->C1 == 0 &&
+         d->accumulate == 0 && d->cout_split > 0 && (d->cout_split % 64) == 0 && ((d->Hin | d->Win) & 1) == 0 && !wn_pack(d);
 }
 
 // one partial row per workgroup where every tile of a workgroup has the same channel block (32 % blocks == 0), else one per

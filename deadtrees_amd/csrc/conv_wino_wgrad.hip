@@ -17,12 +17,8 @@
 //   * LDS images double-buffered, one barrier per chunk; loads run two chunks ahead (two register sets);
 //   * partial dU blocks go to a workspace; a fixed-order two-stage reduction sums the splits and applies G^T . G
 //     (deterministic: no float atomics).
-#include "common.h"
+#include "conv_host.h"
 
-#include <type_traits>
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 #define WW_BUF 8192                    // floats of one operand image of one chunk: 16 pos x 2 halves x 4 steps x 64 ch
 #define WW_TF_MAXC 512
@@ -41,14 +37,6 @@ struct WinoWgArgs {
   int ci_blocks, co_blocks, ksplit, cps;   // cps: chunks (of 8 tiles) per split, even
   unsigned bytes0, bytes1, dybytes, wsbytes;
 };
-
-template <int K, int N, class F>
-__device__ __forceinline__ void ww_static_for(F&& f) {
-  if constexpr (K < N) {
-    f(std::integral_constant<int, K>{});
-    ww_static_for<K + 1, N>(f);
-  }
-}
 
 // CO32: a layer with 32 output channels (dec3.conv1: 128 -> 32): one 32-channel co block.  The two waves of a ci half
 // (wn = 0, 1) would multiply the same 32 x 32 block twice, so they split the chunk's K instead — wave wn takes k-steps
@@ -307,7 +295,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_wgrad_kernel(const WinoWg
       if (k >= 43 && k < 47) x_row_write(Vn, k - 43);
       if (k >= 47 && k < 51) g_write(SN{}, Wn, k - 47);
     };
-    ww_static_for<0, 16 * NJ>([&](auto mc) {
+    dt_static_for<0, 16 * NJ>([&](auto mc) {
       constexpr int mslot = decltype(mc)::value;
       constexpr int p = mslot / NJ, j = mslot % NJ, cur = p & 1;
       acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][j], fb[cur][j], acc[p], 0, 0, 0);
@@ -425,11 +413,7 @@ static WwCfg ww_cfg(const dt_conv_desc* d) {
 }
 
 static bool ww_co32(const dt_conv_desc* d) {   // 32 output channels: the K-split form (DT_FP32_WINO_WGRAD_CO32=0 switches it off)
-  static const int on = [] {
-    const char* e = getenv("DT_FP32_WINO_WGRAD_CO32");
-    return (e == nullptr || e[0] != '0') ? 1 : 0;
-  }();
-  return on && d->Cout == 32;
+  return dt_env_on("DT_FP32_WINO_WGRAD_CO32") && d->Cout == 32;
 }
 
 extern "C" int dt_conv2d_wgrad_winograd_supported(const dt_conv_desc* d) {

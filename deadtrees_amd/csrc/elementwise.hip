@@ -4,7 +4,7 @@
 // ResNet-34 encoder + UnetDecoder (reference call site deadtrees/network/segmodel.py:214).
 // All kernels: 16 B per lane (f32x4) coalesced along the channel-fastest NHWC axis, wave64 shuffle
 // reductions, deterministic two-stage sums (no float atomics).
-#include "common.h"
+#include "conv_host.h"
 
 #include <math.h>
 
@@ -335,11 +335,7 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const f32x4* __restrict__ y
   }
 }
 
-static inline int ew_grid(int64_t n_items) {
-  int64_t g = (n_items + 255) / 256;
-  const int64_t cap = 256 * 16;  // 16 workgroups per CU, grid-stride beyond
-  return (int)(g < cap ? (g > 0 ? g : 1) : cap);
-}
+#define EW_CAP (256 * 16)   // grid cap of the passes below: 16 workgroups per CU, grid-stride beyond
 
 extern "C" int dt_bn_act(const float* y, const float* scale, const float* shift, const float* res,
                          const float* rscale, const float* rshift, float* out, int64_t n_pix, int C, int relu,
@@ -347,24 +343,15 @@ extern "C" int dt_bn_act(const float* y, const float* scale, const float* shift,
   DT_REQUIRE(y && scale && shift && out && n_pix > 0 && C > 0 && (C & 3) == 0, "bn_act: bad args (C%%4)");
   DT_REQUIRE((rscale == nullptr) == (rshift == nullptr), "bn_act: rscale/rshift must come together");
   const int64_t n4 = n_pix * C / 4;
-  hipLaunchKernelGGL(bn_act_kernel, dim3(ew_grid(n4)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)y, scale,
+  hipLaunchKernelGGL(bn_act_kernel, dim3(dt_ew_grid(n4, EW_CAP)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)y, scale,
                      shift, (const f32x4*)res, rscale, rshift, (f32x4*)out, n4, C / 4, relu);
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
 
 // ------------------------------------------------------------------ BN backward
-// pass 1: per-channel partial sums of g and g*xhat over blocks of BNB_RB pixels.
+// pass 1: per-channel partial sums of g and g*xhat over blocks of bnb_rb(n_pix) pixels (conv_host.h).
 // 256 threads = Q channel-quads x (256/Q) pixel lanes; 2 pixels in flight per thread.
-#define BNB_RB 256
-// rows (pixels) per workgroup: 256 for small maps, grown so that a launch has at most ~2048 row blocks
-static inline int64_t bnb_rb(int64_t n_pix) {
-  int64_t rb = BNB_RB;
-  const int64_t want = (n_pix + 2047) / 2048;
-  if (want > rb) rb = (want + BNB_RB - 1) / BNB_RB * BNB_RB;
-  return rb;
-}
-
 extern "C" int dt_bn_bwd_rows(int64_t n_pix, int C) {
   (void)C;
   return dt_cdiv(n_pix, bnb_rb(n_pix));
@@ -586,7 +573,7 @@ static int bn_bwd_apply_impl(const float* dout, const float* out_act, const floa
   const int64_t n4 = n_pix * C / 4;
   // frozen statistics (eval-mode BatchNorm): mean / invstd are constants of the layer, so the two batch-mean terms
   // of the training-mode formula vanish -> inv_count = 0 turns dy into g * gamma * invstd
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(n4)), dim3(256), 0, st, (const f32x4*)dout,
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(dt_ew_grid(n4, EW_CAP)), dim3(256), 0, st, (const f32x4*)dout,
                      (const f32x4*)out_act, (const f32x4*)y, mean, invstd, gamma, dgamma, dbeta, act_scale, act_shift,
                      (f32x4*)dy, (f32x4*)dres, dres_accumulate, n4, C / 4, frozen ? 0.f : (float)(1.0 / (double)n_pix));
   DT_LAUNCH_CHECK();
@@ -655,7 +642,7 @@ extern "C" int dt_maxpool3x3s2(const float* x, float* out, uint8_t* argmax, int 
   DT_REQUIRE(x && out && B > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0, "maxpool: bad args");
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const int64_t total = (int64_t)B * Ho * Wo * (C / 4);
-  hipLaunchKernelGGL(maxpool_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)x,
+  hipLaunchKernelGGL(maxpool_kernel, dim3(dt_ew_grid(total, EW_CAP)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)x,
                      (f32x4*)out, (uint32_t*)argmax, B, H, W, C / 4, Ho, Wo);
   DT_LAUNCH_CHECK();
   return DT_OK;
@@ -833,7 +820,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_quad_bn_kernel(const f32x4* _
 
 extern "C" int dt_maxpool3x3s2_bwd_bn_rows(int B, int H, int W, int C) {
   if (((H | W) & 1) != 0 || C <= 0 || (C & 3) != 0 || C / 4 > 256 || 256 % (C / 4) != 0) return 0;   // even maps only
-  return ew_grid((int64_t)B * (H / 2) * (W / 2) * (C / 4));
+  return dt_ew_grid((int64_t)B * (H / 2) * (W / 2) * (C / 4), EW_CAP);
 }
 
 extern "C" int dt_maxpool3x3s2_bwd_bn(const float* dout, const uint8_t* argmax, float* dx, int accumulate,
@@ -854,14 +841,14 @@ extern "C" int dt_maxpool3x3s2_bwd(const float* dout, const uint8_t* argmax, flo
   DT_REQUIRE(dout && argmax && dx && B > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0, "maxpool_bwd: bad args");
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   if (((H | W) & 1) == 0) {
-    hipLaunchKernelGGL(maxpool_bwd_quad_kernel, dim3(ew_grid((int64_t)B * Ho * Wo * (C / 4))), dim3(256), 0,
+    hipLaunchKernelGGL(maxpool_bwd_quad_kernel, dim3(dt_ew_grid((int64_t)B * Ho * Wo * (C / 4), EW_CAP)), dim3(256), 0,
                        (hipStream_t)stream, (const f32x4*)dout, (const uint32_t*)argmax, (f32x4*)dx, accumulate, B, H, W,
                        C / 4, Ho, Wo);
     DT_LAUNCH_CHECK();
     return DT_OK;
   }
   const int64_t total = (int64_t)B * H * W * (C / 4);
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(dt_ew_grid(total, EW_CAP)), dim3(256), 0, (hipStream_t)stream,
                      (const f32x4*)dout, (const uint32_t*)argmax, (f32x4*)dx, accumulate, B, H, W, C / 4, Ho, Wo);
   DT_LAUNCH_CHECK();
   return DT_OK;
@@ -893,7 +880,7 @@ extern "C" int dt_upsample2x_bwd(const float* dup, float* dx, int accumulate, in
                                  void* stream) {
   DT_REQUIRE(dup && dx && B > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0, "upsample2x_bwd: bad args");
   const int64_t total = (int64_t)B * H * W * (C / 4);
-  hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(dt_ew_grid(total, EW_CAP)), dim3(256), 0, (hipStream_t)stream,
                      (const f32x4*)dup, (f32x4*)dx, accumulate, B, H, W, C / 4);
   DT_LAUNCH_CHECK();
   return DT_OK;
@@ -953,7 +940,7 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_bn_kernel(const f32x4* __r
 }
 
 extern "C" int dt_upsample2x_bwd_bn_rows(int B, int H, int W, int C) {
-  return ew_grid((int64_t)B * H * W * (C / 4));
+  return dt_ew_grid((int64_t)B * H * W * (C / 4), EW_CAP);
 }
 
 extern "C" int dt_upsample2x_bwd_bn(const float* dup, float* dx, const dt_bn_bwd_fuse* fuse, float* red, int B, int H,
@@ -995,7 +982,7 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restri
 extern "C" int dt_nchw_to_nhwc(const float* src, float* dst, int B, int C, int H, int W, void* stream) {
   DT_REQUIRE(src && dst && B > 0 && C > 0 && H > 0 && W > 0, "nchw_to_nhwc: bad args");
   const int64_t HW = (int64_t)H * W;
-  hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(ew_grid(B * HW)), dim3(256), 0, (hipStream_t)stream, src, dst, B, C,
+  hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(dt_ew_grid(B * HW, EW_CAP)), dim3(256), 0, (hipStream_t)stream, src, dst, B, C,
                      HW);
   DT_LAUNCH_CHECK();
   return DT_OK;
@@ -1003,7 +990,7 @@ extern "C" int dt_nchw_to_nhwc(const float* src, float* dst, int B, int C, int H
 extern "C" int dt_nhwc_to_nchw(const float* src, float* dst, int B, int C, int H, int W, void* stream) {
   DT_REQUIRE(src && dst && B > 0 && C > 0 && H > 0 && W > 0, "nhwc_to_nchw: bad args");
   const int64_t HW = (int64_t)H * W;
-  hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(ew_grid(B * HW)), dim3(256), 0, (hipStream_t)stream, src, dst, B, C,
+  hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(dt_ew_grid(B * HW, EW_CAP)), dim3(256), 0, (hipStream_t)stream, src, dst, B, C,
                      HW);
   DT_LAUNCH_CHECK();
   return DT_OK;
@@ -1030,7 +1017,7 @@ extern "C" int dt_normalize_u8(const uint8_t* src, float* dst, int64_t n_pix, in
     m[c] = mean[c];
     s[c] = stdv[c];
   }
-  hipLaunchKernelGGL(normalize_u8_kernel, dim3(ew_grid(n_pix)), dim3(256), 0, (hipStream_t)stream, src, dst, n_pix,
+  hipLaunchKernelGGL(normalize_u8_kernel, dim3(dt_ew_grid(n_pix, EW_CAP)), dim3(256), 0, (hipStream_t)stream, src, dst, n_pix,
                      Csrc, Cdst, m, s);
   DT_LAUNCH_CHECK();
   return DT_OK;
@@ -1070,7 +1057,7 @@ extern "C" int dt_split_normalize_u8(const uint8_t* raster_chw, float* dst_nhwc,
     s[c] = stdv[c];
   }
   const int64_t n_pix = (int64_t)n_blocks * d * d;
-  hipLaunchKernelGGL(split_normalize_u8_kernel, dim3(ew_grid(n_pix)), dim3(256), 0, (hipStream_t)stream, raster_chw,
+  hipLaunchKernelGGL(split_normalize_u8_kernel, dim3(dt_ew_grid(n_pix, EW_CAP)), dim3(256), 0, (hipStream_t)stream, raster_chw,
                      dst_nhwc, h, w, d, nbx, first_block, n_pix, Cdst, m, s);
   DT_LAUNCH_CHECK();
   return DT_OK;
@@ -1091,7 +1078,7 @@ __global__ __launch_bounds__(256) void band_has_data_kernel(const uint8_t* __res
 
 extern "C" int dt_band_has_data(const uint8_t* band, int64_t n, int32_t* flag, void* stream) {
   DT_REQUIRE(band && flag && n > 0, "band_has_data: bad args");
-  hipLaunchKernelGGL(band_has_data_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, band, n, flag);
+  hipLaunchKernelGGL(band_has_data_kernel, dim3(dt_ew_grid(n, EW_CAP)), dim3(256), 0, (hipStream_t)stream, band, n, flag);
   DT_LAUNCH_CHECK();
   return DT_OK;
 }

@@ -1,11 +1,8 @@
 // HBM-bound passes of the bf16 training path: BatchNorm backward, max-pool (+argmax) and its backward,
 // nearest-upsample backward, fp32 <-> bf16 shuttles.  8 bf16 (16 B) per lane; every sum in fp32/fp64 with the
 // same deterministic two-stage reductions as the fp32 path (elementwise.hip).
-#include "common.h"
+#include "conv_host.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-#define BNB16_RB 256
 
 __device__ __forceinline__ void load8(const bf16x8* p, size_t i, float (&v)[8]) {
   const bf16x8 a = p[i];
@@ -30,15 +27,7 @@ __device__ __forceinline__ void ldc8(const float* __restrict__ p, int c, float (
   }
 }
 
-// ------------------------------------------------------------------ BN backward, pass 1
-// rows (pixels) per workgroup: 256 for small maps, grown so that a launch has at most ~2048 row blocks — the
-// in-workgroup reduction and the second-stage row count then stay small next to the streaming part.
-static inline int64_t bnb16_rb(int64_t n_pix) {
-  int64_t rb = BNB16_RB;
-  const int64_t want = (n_pix + 2047) / 2048;
-  if (want > rb) rb = (want + BNB16_RB - 1) / BNB16_RB * BNB16_RB;
-  return rb;
-}
+// ------------------------------------------------------------------ BN backward, pass 1 (rows per workgroup: bnb_rb)
 
 __global__ __launch_bounds__(256) void bn_bwd_reduce_bf16_kernel(const bf16x8* __restrict__ dout,
                                                                  const bf16x8* __restrict__ out_act,
@@ -140,14 +129,13 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_bf16_kernel(const bf16x8* _
   }
 }
 
-extern "C" int dt_bn_bwd_rows_bf16(int64_t n_pix) { return dt_cdiv(n_pix, bnb16_rb(n_pix)); }
+extern "C" int dt_bn_bwd_rows_bf16(int64_t n_pix) { return dt_cdiv(n_pix, bnb_rb(n_pix)); }
 
 extern "C" int dt_bn_bwd_reduce_bf16(const void* dout, const void* out_act, const void* y, const float* mean,
                                      const float* invstd, const float* act_scale, const float* act_shift, float* red,
                                      int64_t n_pix, int C, void* stream) {
   DT_REQUIRE(dout && y && mean && invstd && red && n_pix > 0 && C > 0 && (C & 7) == 0, "bn_bwd_reduce_bf16: bad args");
-  DT_REQUIRE((((uintptr_t)mean | (uintptr_t)invstd | (uintptr_t)act_scale | (uintptr_t)act_shift) & 15) == 0,
-             "bn_bwd_reduce_bf16: per-channel arrays must be 16-byte aligned");
+  DT_REQUIRE_COEF_ALIGNED(dt_aligned16(mean, invstd, act_scale, act_shift), "bn_bwd_reduce_bf16");
   const int C8 = C / 8;
   int Q = 64;
   while (Q > C8) Q >>= 1;
@@ -155,7 +143,7 @@ extern "C" int dt_bn_bwd_reduce_bf16(const void* dout, const void* out_act, cons
   const int P = dt_bn_bwd_rows_bf16(n_pix);
   hipLaunchKernelGGL(bn_bwd_reduce_bf16_kernel, dim3(C8 / Q, P), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)dout,
                      (const bf16x8*)out_act, (const bf16x8*)y, mean, invstd, act_scale, act_shift, red, n_pix, C8, Q, P,
-                     bnb16_rb(n_pix));
+                     bnb_rb(n_pix));
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
@@ -245,15 +233,12 @@ extern "C" int dt_bn_bwd_apply_bf16(const void* dout, const void* out_act, const
                  (C & 7) == 0 && P > 0,
              "bn_bwd_apply_bf16: bad args");
   DT_REQUIRE(256 % (C / 8) == 0, "bn_bwd_apply_bf16: C/8 must divide 256 (C=%d)", C);
-  DT_REQUIRE((((uintptr_t)mean | (uintptr_t)invstd | (uintptr_t)gamma | (uintptr_t)dgamma | (uintptr_t)dbeta |
-               (uintptr_t)act_scale | (uintptr_t)act_shift) & 15) == 0,
-             "bn_bwd_apply_bf16: per-channel arrays must be 16-byte aligned");
+  DT_REQUIRE_COEF_ALIGNED(dt_aligned16(mean, invstd, gamma, dgamma, dbeta, act_scale, act_shift), "bn_bwd_apply_bf16");
   hipStream_t st = (hipStream_t)stream;
   int rc = dt_bn_bwd_finish_sums(red, P, C, dgamma, dbeta, st);
   if (rc != DT_OK) return rc;
   const int64_t n8 = n_pix * C / 8;
-  int64_t g = (n8 + 255) / 256;
-  if (g > 4096) g = 4096;
+  const int g = dt_ew_grid(n8, 4096);
   hipLaunchKernelGGL(bn_bwd_apply_bf16_kernel, dim3((unsigned)g), dim3(256), 0, st, (const bf16x8*)dout,
                      (const bf16x8*)out_act, (const bf16x8*)y, mean, invstd, gamma, dgamma, dbeta, act_scale, act_shift,
                      (bf16x8*)dy, (bf16x8*)dres, dres_accumulate, n8, C / 8, (float)(1.0 / (double)n_pix));
@@ -311,8 +296,7 @@ extern "C" int dt_maxpool3x3s2_bf16_amax(const void* x, void* out, uint8_t* argm
   DT_REQUIRE(x && out && argmax && B > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0, "maxpool_bf16_amax: bad args");
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const int64_t total = (int64_t)B * Ho * Wo * (C / 8);
-  int64_t g = (total + 255) / 256;
-  if (g > 4096) g = 4096;
+  const int g = dt_ew_grid(total, 4096);
   hipLaunchKernelGGL(maxpool_bf16_amax_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)x,
                      (bf16x8*)out, (uint2*)argmax, B, H, W, C / 8, Ho, Wo);
   DT_LAUNCH_CHECK();
@@ -527,8 +511,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_bf16_quad_bn_kernel(const bf1
 
 extern "C" int dt_maxpool3x3s2_bwd_bn_bf16_rows(int B, int H, int W, int C) {
   if (((H | W) & 1) != 0 || C <= 0 || (C & 7) != 0 || C / 8 > 256 || 256 % (C / 8) != 0) return 0;   // even maps only
-  const int64_t g = ((int64_t)B * (H / 2) * (W / 2) * (C / 8) + 255) / 256;
-  return (int)(g > 4096 ? 4096 : (g > 0 ? g : 1));
+  return dt_ew_grid((int64_t)B * (H / 2) * (W / 2) * (C / 8), 4096);
 }
 
 extern "C" int dt_maxpool3x3s2_bwd_bn_bf16(const void* dout, const uint8_t* argmax, void* dx, int accumulate,
@@ -537,8 +520,7 @@ extern "C" int dt_maxpool3x3s2_bwd_bn_bf16(const void* dout, const uint8_t* argm
                  fuse->act_shift && B > 0 && H > 0 && W > 0, "maxpool_bwd_bn_bf16: bad args");
   const int P = dt_maxpool3x3s2_bwd_bn_bf16_rows(B, H, W, C);
   DT_REQUIRE(P > 0, "maxpool_bwd_bn_bf16: even maps, C/8 a divisor of 256 (H=%d W=%d C=%d)", H, W, C);
-  DT_REQUIRE((((uintptr_t)fuse->mean | (uintptr_t)fuse->invstd | (uintptr_t)fuse->act_scale | (uintptr_t)fuse->act_shift) & 15) == 0,
-             "maxpool_bwd_bn_bf16: per-channel arrays must be 16-byte aligned");
+  DT_REQUIRE_COEF_ALIGNED(dt_fuse_aligned16(fuse), "maxpool_bwd_bn_bf16");
   hipLaunchKernelGGL(maxpool_bwd_bf16_quad_bn_kernel, dim3(P), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)dout,
                      (const uint2*)argmax, (bf16x8*)dx, (const bf16x8*)fuse->y, fuse->mean, fuse->invstd, fuse->act_scale,
                      fuse->act_shift, red, accumulate, B, H, W, C / 8, H / 2, W / 2, P);
@@ -551,16 +533,14 @@ extern "C" int dt_maxpool3x3s2_bwd_bf16(const void* dout, const uint8_t* argmax,
   DT_REQUIRE(dout && argmax && dx && B > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0, "maxpool_bwd_bf16: bad args");
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   if (((H | W) & 1) == 0) {
-    int64_t gq = ((int64_t)B * Ho * Wo * (C / 8) + 255) / 256;
-    if (gq > 8192) gq = 8192;
+    const int gq = dt_ew_grid((int64_t)B * Ho * Wo * (C / 8), 8192);
     hipLaunchKernelGGL(maxpool_bwd_bf16_quad_kernel, dim3((unsigned)gq), dim3(256), 0, (hipStream_t)stream,
                        (const bf16x8*)dout, (const uint2*)argmax, (bf16x8*)dx, accumulate, B, H, W, C / 8, Ho, Wo);
     DT_LAUNCH_CHECK();
     return DT_OK;
   }
   const int64_t total = (int64_t)B * H * W * (C / 8);
-  int64_t g = (total + 255) / 256;
-  if (g > 4096) g = 4096;
+  const int g = dt_ew_grid(total, 4096);
   hipLaunchKernelGGL(maxpool_bwd_bf16_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)dout,
                      (const uint2*)argmax, (bf16x8*)dx, accumulate, B, H, W, C / 8, Ho, Wo);
   DT_LAUNCH_CHECK();
@@ -655,8 +635,7 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_bf16_kernel(const bf16x8* 
 static int upsample2x_bwd_bf16_launch(const void* dup, void* dx, int acc, int B, int H, int W, int C, void* stream) {
   DT_REQUIRE(dup && dx && B > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0, "upsample2x_bwd_bf16: bad args");
   const int64_t total = (int64_t)B * H * W * (C / 8);
-  int64_t g = (total + 255) / 256;
-  if (g > 4096) g = 4096;
+  const int g = dt_ew_grid(total, 4096);
   hipLaunchKernelGGL(upsample2x_bwd_bf16_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream,
                      (const bf16x8*)dup, (bf16x8*)dx, acc, B, H, W, C / 8);
   DT_LAUNCH_CHECK();
@@ -782,8 +761,7 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_bn_bf16_kernel(const bf16x
 }
 
 extern "C" int dt_upsample2x_bwd_bn_bf16_rows(int B, int H, int W, int C) {
-  int64_t g = ((int64_t)B * H * W * (C / 8) + 255) / 256;
-  return (int)(g > 4096 ? 4096 : (g > 0 ? g : 1));
+  return dt_ew_grid((int64_t)B * H * W * (C / 8), 4096);
 }
 
 extern "C" int dt_upsample2x_bwd_bn_bf16(const void* dup, void* dx, const dt_bn_bwd_fuse* fuse, float* red, int B, int H,
@@ -793,8 +771,7 @@ extern "C" int dt_upsample2x_bwd_bn_bf16(const void* dup, void* dx, const dt_bn_
              "upsample2x_bwd_bn_bf16: bad args");
   const int C8 = C / 8;
   DT_REQUIRE(C8 <= 256 && 256 % C8 == 0, "upsample2x_bwd_bn_bf16: C/8 must divide 256 (C=%d)", C);
-  DT_REQUIRE((((uintptr_t)fuse->mean | (uintptr_t)fuse->invstd | (uintptr_t)fuse->act_scale |
-               (uintptr_t)fuse->act_shift) & 15) == 0, "upsample2x_bwd_bn_bf16: per-channel arrays must be 16-byte aligned");
+  DT_REQUIRE_COEF_ALIGNED(dt_fuse_aligned16(fuse), "upsample2x_bwd_bn_bf16");
   const int P = dt_upsample2x_bwd_bn_bf16_rows(B, H, W, C);
   hipLaunchKernelGGL(upsample2x_bwd_bn_bf16_kernel, dim3(P), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)dup,
                      (bf16x8*)dx, (const bf16x8*)fuse->y, fuse->mean, fuse->invstd, fuse->act_scale, fuse->act_shift, red,
@@ -821,8 +798,7 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const f32x4* __restric
 
 extern "C" int dt_f32_to_bf16(const float* x, void* out, int64_t n, void* stream) {
   DT_REQUIRE(x && out && n > 0 && (n & 7) == 0, "f32_to_bf16: n must be a multiple of 8");
-  int64_t g = (n / 8 + 255) / 256;
-  if (g > 4096) g = 4096;
+  const int g = dt_ew_grid(n / 8, 4096);
   hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const f32x4*)x,
                      (bf16x8*)out, n / 8);
   DT_LAUNCH_CHECK();

@@ -11,7 +11,7 @@
 //   argmax(dim=1)                                      segmodel.py:273,289; deployment/inference.py:62
 // All HBM-bound: one read of the 16-channel decoder output / of the logits, wave64 shuffle
 // reductions -> LDS -> one fp64 row per workgroup (fixed-order finalize, no float atomics).
-#include "common.h"
+#include "conv_host.h"
 
 #include <math.h>
 
@@ -21,13 +21,12 @@
 #define HEAD_CIN 16
 
 // ------------------------------------------------------------------ head forward
-typedef __bf16 hbf16x4 __attribute__((ext_vector_type(4)));
 
 // 4 consecutive channels of pixel `pix_elem_off` from an fp32 or bf16 NHWC tensor
 template <bool XB>
 __device__ __forceinline__ f32x4 head_load4(const void* x, size_t elem_off) {
   if constexpr (XB) {
-    const hbf16x4 q = *reinterpret_cast<const hbf16x4*>(reinterpret_cast<const __bf16*>(x) + elem_off);
+    const bf16x4 q = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const __bf16*>(x) + elem_off);
     return f32x4{(float)q[0], (float)q[1], (float)q[2], (float)q[3]};
   } else {
     return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(x) + elem_off);
@@ -280,8 +279,8 @@ __global__ __launch_bounds__(256, K <= 2 ? 4 : (K == 3 ? 3 : 2)) void head_bwd_k
       if (oy < H && ox < W) {
         const size_t o = (((size_t)b * H + oy) * W + ox) * C + 4 * j;
         if constexpr (XB) {
-          hbf16x4 v = {(__bf16)a[0], (__bf16)a[1], (__bf16)a[2], (__bf16)a[3]};
-          *reinterpret_cast<hbf16x4*>(reinterpret_cast<__bf16*>(dx) + o) = v;
+          bf16x4 v = {(__bf16)a[0], (__bf16)a[1], (__bf16)a[2], (__bf16)a[3]};
+          *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(dx) + o) = v;
         } else {
           *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(dx) + o) = a;
         }
@@ -648,8 +647,7 @@ extern "C" int dt_seg_loss_bwd(const float* logits, const int64_t* labels, const
   DT_REQUIRE((wass_m == nullptr) == (wass_coef == nullptr) && (wass_m == nullptr) == (gw_posgrad == nullptr),
              "seg_loss_bwd: wass_m, wass_coef and gw_posgrad go together");
   const int64_t HW = (int64_t)H * W, total = (int64_t)B * HW;
-  int64_t g = (total + 255) / 256;
-  if (g > 256 * 16) g = 256 * 16;
+  const int g = dt_ew_grid(total, 256 * 16);
   hipStream_t st = (hipStream_t)stream;
   switch (K) {
     case 2: hipLaunchKernelGGL(seg_loss_bwd_kernel<2>, dim3((unsigned)g), dim3(256), 0, st, logits, labels, dist, coef, wfocal, wbound, gscale, wass_m, wass_coef, gw_posgrad, dlogits, HW, total); break;
@@ -951,8 +949,7 @@ extern "C" int dt_ensemble_vote(const uint8_t* maps, int M, int64_t n, int K, ui
   DT_REQUIRE((n & 3) == 0, "ensemble_vote: pixel count must be a multiple of 4 (n=%lld)", (long long)n);
   DT_REQUIRE(K >= 2 && K <= VOTE_MAXK, "ensemble_vote: K=%d unsupported (2..%d)", K, VOTE_MAXK);
   const int64_t n4 = n / 4;
-  int64_t g = (n4 + 255) / 256;
-  if (g > 4096) g = 4096;
+  const int g = dt_ew_grid(n4, 4096);
   hipLaunchKernelGGL(ensemble_vote_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)maps,
                      M, n4, K, (uint32_t*)out_u8, out_i64, err_flag);
   DT_LAUNCH_CHECK();

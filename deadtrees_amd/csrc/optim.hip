@@ -4,7 +4,7 @@
 // launches per step in the reference — with two HBM-bound passes: read g (norm), then
 // read g,m,v,p / write m,v,p.  The clip coefficient and the non-finite-loss skip flag stay on the
 // device: no host synchronisation in the step.
-#include "common.h"
+#include "conv_host.h"
 
 #include <math.h>
 #include <string.h>
@@ -146,9 +146,7 @@ extern "C" int dt_adam_step(float* p, const float* g, float* m, float* v, int64_
   DT_REQUIRE(p && g && m && v && n > 0 && bias_c1 > 0.f && bias_c2 > 0.f, "adam: bad args");
   DT_REQUIRE(((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0,
              "adam: buffers must be 16-byte aligned");
-  int64_t grid = ((n >> 2) + 255) / 256;
-  if (grid > 256 * 16) grid = 256 * 16;
-  if (grid < 1) grid = 1;
+  const int grid = dt_ew_grid(n >> 2, 256 * 16);
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
                      (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, bias_c1, bias_c2, clipcoef,
                      skip_flag, (const float*)nullptr);
@@ -195,9 +193,7 @@ extern "C" int dt_adam_step_dev(float* p, const float* g, float* m, float* v, in
   DT_REQUIRE(p && g && m && v && hyper && n > 0, "adam_dev: bad args");
   DT_REQUIRE(((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0,
              "adam_dev: buffers must be 16-byte aligned");
-  int64_t grid = ((n >> 2) + 255) / 256;
-  if (grid > 256 * 16) grid = 256 * 16;
-  if (grid < 1) grid = 1;
+  const int grid = dt_ew_grid(n >> 2, 256 * 16);
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, 0.f,
                      (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, 1.f, 1.f, clipcoef, skip_flag,
                      hyper);
@@ -382,9 +378,7 @@ extern "C" int dt_weight_average(float* avg, const float* p, int64_t n, int64_t*
   DT_REQUIRE(mode == DT_AVG_SWA || mode == DT_AVG_EMA, "weight_average: mode %d (DT_AVG_SWA or DT_AVG_EMA)", mode);
   DT_REQUIRE(mode != DT_AVG_EMA || (decay >= 0.0 && decay <= 1.0), "weight_average: decay %g outside [0, 1]", decay);
   DT_REQUIRE(((((uintptr_t)avg) | ((uintptr_t)p)) & 15) == 0, "weight_average: buffers must be 16-byte aligned");
-  int64_t grid = ((n >> 2) + 255) / 256;
-  if (grid > 256 * 16) grid = 256 * 16;
-  if (grid < 1) grid = 1;
+  const int grid = dt_ew_grid(n >> 2, 256 * 16);
   hipLaunchKernelGGL(weight_average_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, count_dev, skip_flag);
   DT_LAUNCH_CHECK();
   hipLaunchKernelGGL(weight_average_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, avg, p, n,
