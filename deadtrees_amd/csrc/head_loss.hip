@@ -780,7 +780,8 @@ extern "C" int dt_seg_loss_algebra(const double* acc, const dt_loss_cfg* cfg, in
 // "generalised true positives" of sample i are  sum_s alpha_i(s) * V(s)  with  V(s) = sum_j (1 - wass_j(s))
 // over ALL samples j.  The reference trains with that; these two small passes reproduce it:
 //   fwd:  V[s] = sum_j (1 - wass_j(s))                       (sequential over j: fixed order)
-//   bwd:  G[s] = sum_i a[i] * alpha(label_i(s)),  alpha = [k > 0]   (d loss / d wass_j(s) = G[s] + c[j])
+//   bwd:  G[s] = sum_i a[i] * alpha(label_i(s)),  alpha = [0 < k < K]   (d loss / d wass_j(s) = G[s] + c[j]);
+//         a label outside [0,K) has an all-zero one-hot row, so alpha = 0 as in the forward pass (acc[k][9])
 template <int K>
 __global__ __launch_bounds__(256) void gwdice_possum_kernel(const float* __restrict__ logits,
                                                             const int64_t* __restrict__ labels,
@@ -822,12 +823,14 @@ __global__ __launch_bounds__(256) void gwdice_possum_kernel(const float* __restr
 
 __global__ __launch_bounds__(256) void gwdice_posgrad_kernel(const int64_t* __restrict__ labels,
                                                              const float* __restrict__ a, float* __restrict__ G,
-                                                             int B, int64_t HW) {
+                                                             int B, int K, int64_t HW) {
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= HW) return;
   float g = 0.f;
-  for (int b = 0; b < B; ++b)
-    if (labels[(size_t)b * HW + p] > 0) g += a[b];
+  for (int b = 0; b < B; ++b) {
+    const int64_t lab = labels[(size_t)b * HW + p];
+    if (lab > 0 && lab < K) g += a[b];
+  }
   G[p] = g;
 }
 
@@ -847,12 +850,13 @@ extern "C" int dt_gwdice_possum(const float* logits, const int64_t* labels, cons
   return DT_OK;
 }
 
-extern "C" int dt_gwdice_posgrad(const int64_t* labels, const float* sample_coef, float* posgrad, int B, int H, int W,
-                                 void* stream) {
+extern "C" int dt_gwdice_posgrad(const int64_t* labels, const float* sample_coef, float* posgrad, int B, int K, int H,
+                                 int W, void* stream) {
   DT_REQUIRE(labels && sample_coef && posgrad && B > 0 && H > 0 && W > 0, "gwdice_posgrad: bad args");
+  DT_REQUIRE(K >= 2 && K <= HEAD_MAXK, "gwdice_posgrad: K=%d unsupported", K);
   const int64_t HW = (int64_t)H * W;
   hipLaunchKernelGGL(gwdice_posgrad_kernel, dim3(dt_cdiv(HW, 256)), dim3(256), 0, (hipStream_t)stream, labels,
-                     sample_coef, posgrad, B, HW);
+                     sample_coef, posgrad, B, K, HW);
   DT_LAUNCH_CHECK();
   return DT_OK;
 }

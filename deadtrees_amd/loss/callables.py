@@ -3,7 +3,15 @@
 Same names, constructor arguments and call signature ``loss(probs, target) -> 0-d tensor`` (probabilities in, like
 segmodel.py:214-218 hands them over), so code written against ``deadtrees.loss`` keeps working; the arithmetic is
 the ONE fused reduction pass of ``seg_loss`` (softmax(log p) == p for a probability vector, so the kernels see
-the caller's probabilities), differentiable with respect to ``probs``.
+the caller's probabilities).
+
+Differentiability.  The kernels see ``probs / probs.sum(1)``: an input that does not sum to one over the classes is
+renormalised, and the gradient delivered to ``probs`` is the reference's gradient ``g`` projected onto the simplex'
+tangent at each pixel, ``g_k - sum_j p_j g_j`` (the reference's minus its p-weighted mean).  The two differ by a term
+that is constant over the classes of a pixel, which the Jacobian of any softmax upstream maps to zero: for
+``probs = logits.softmax(1)`` - the only way ``SemSegment`` produces them - d loss / d logits is exactly the
+reference's.  Code that optimises a *leaf* ``probs`` tensor directly gets the projected gradient, not ``g``
+(tests/test_loss_kernels_gpu.py pins both statements).
 
 Only the class selections ``SemSegment`` uses are built (segmodel.py:113-134): Dice / Boundary over the non-background
 classes, Focal / CrossEntropy over all classes; another ``idc`` raises ``NotImplementedError``.

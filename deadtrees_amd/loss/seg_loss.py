@@ -134,7 +134,7 @@ def loss_backward(saved, gtotal: Optional[torch.Tensor] = None) -> torch.Tensor:
     posgrad = None
     if wass_m is not None:
         posgrad = torch.empty(H * W, dtype=torch.float32, device=logits.device)
-        _lib.check(lib.dt_gwdice_posgrad(_p(labels), _p(wass_a), _p(posgrad), B, H, W, _stream()),
+        _lib.check(lib.dt_gwdice_posgrad(_p(labels), _p(wass_a), _p(posgrad), B, K, H, W, _stream()),
                    "dt_gwdice_posgrad")
     _lib.check(lib.dt_seg_loss_bwd(_p(logits), _p(labels), _p(distmap), _p(coef), _p(wf), _p(wbound), _p(gs),
                                    _p(wass_m), _p(wass_c), _p(posgrad), _p(dl), B, K, H, W, _stream()), "dt_seg_loss_bwd")

@@ -324,10 +324,11 @@ int dt_seg_loss_algebra(const double* acc, const dt_loss_cfg* cfg, int B, int K,
  * i's generalised true positives are sum_s alpha_i(s) * V(s), V(s) = sum_j (1 - wass_j(s)) over the whole batch
  * (equal to the published formula only for B = 1); reproduced because the reference trains with it.
  *   dt_gwdice_possum : possum[H*W] = V                                   (forward, before dt_seg_loss_fwd)
- *   dt_gwdice_posgrad: posgrad[H*W] = sum_i sample_coef[i] * [label_i(s) > 0]   (backward, before dt_seg_loss_bwd) */
+ *   dt_gwdice_posgrad: posgrad[H*W] = sum_i sample_coef[i] * [0 < label_i(s) < K]   (backward, before dt_seg_loss_bwd;
+ *                      a label outside [0,K) counts for no class, as in dt_seg_loss_fwd) */
 int dt_gwdice_possum(const float* logits, const int64_t* labels, const float* wass_m, float* possum, int B, int K,
                      int H, int W, void* stream);
-int dt_gwdice_posgrad(const int64_t* labels, const float* sample_coef, float* posgrad, int B, int H, int W,
+int dt_gwdice_posgrad(const int64_t* labels, const float* sample_coef, float* posgrad, int B, int K, int H, int W,
                       void* stream);
 
 /* K x K confusion counts accumulated on the device (eval reductions, segmodel.py:291-309,337-365):

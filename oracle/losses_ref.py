@@ -124,8 +124,9 @@ def fscore(p: torch.Tensor, mask: torch.Tensor, ignore_channels=(), threshold: f
     return ((1 + b2) * tp + eps) / ((1 + b2) * tp + b2 * fn + fp + eps)
 
 
-def compound_loss(p, mask, losses=("GDICE", "FOCAL"), distmap=None, alpha: float = 1.0):
-    """reference segmodel.py:169-200 ``calculate_loss`` for the loss names parsed at :113-138."""
+def compound_loss(p, mask, losses=("GDICE", "FOCAL"), distmap=None, alpha: float = 1.0, gamma: float = 2.0):
+    """reference segmodel.py:169-200 ``calculate_loss`` for the loss names parsed at :113-138 (``gamma``: the focal
+    exponent, 2 at segmodel.py:129)."""
     K = p.shape[1]
     total = 0.0
     parts = {}
@@ -141,7 +142,7 @@ def compound_loss(p, mask, losses=("GDICE", "FOCAL"), distmap=None, alpha: float
         parts["boundary_loss"] = boundary(p, distmap, list(range(1, K)))
         total = total + (alpha if "BOUNDARY-RAMPED" in losses else 1.0) * parts["boundary_loss"]
     if "FOCAL" in losses:
-        parts["focal_loss"] = focal(p, mask, list(range(K)), 2.0)
+        parts["focal_loss"] = focal(p, mask, list(range(K)), gamma)
         total = total + parts["focal_loss"]
     parts["total_loss"] = total
     return total, parts

@@ -52,7 +52,7 @@ def boundary_t(p, dist, idc):
     return (p[:, idc].float() * dist[:, idc].float()).mean()
 
 
-def loss_from_logits(logits, mask, losses=("GDICE", "FOCAL"), distmap=None, alpha=1.0):
+def loss_from_logits(logits, mask, losses=("GDICE", "FOCAL"), distmap=None, alpha=1.0, gamma=2):
     K = logits.shape[1]
     t = onehot_f32(mask, K)
     p = logits.softmax(dim=1)
@@ -70,7 +70,7 @@ def loss_from_logits(logits, mask, losses=("GDICE", "FOCAL"), distmap=None, alph
         total = total + (alpha if "BOUNDARY-RAMPED" in losses else 1.0) * boundary_t(
             p, distmap, list(range(1, K)))
     if "FOCAL" in losses:
-        total = total + focal_t(p, t, list(range(K)), 2)
+        total = total + focal_t(p, t, list(range(K)), gamma)
     return total, p
 
 

@@ -38,6 +38,41 @@ def test_loss_values(path):
     assert float(L.cross_entropy(p, mask, al)) == pytest.approx(float(z["ce"]), rel=2e-6, abs=2e-7)
     assert float(L.boundary(p, dist, fg)) == pytest.approx(float(z["boundary"]), rel=2e-6, abs=2e-6)
     assert float(L.gwdice(p.double(), mask)) == pytest.approx(float(z["gwdice"]), rel=2e-6, abs=2e-7)
+    if "focal_gammas" in z:   # focal exponents other than 2 (the off-grid fixtures)
+        for gm, want in zip(z["focal_gammas"], z["focal_at_gammas"]):
+            assert float(L.focal(p, mask, al, float(gm))) == pytest.approx(float(want), rel=2e-6, abs=2e-7)
+
+
+def test_off_grid_cases_are_present():
+    """the fixtures the GPU loss tests lean on: odd sizes, focal gamma 0.5 / 1 / 3.5, an absent class, B = 1"""
+    shapes, gammas, absent = set(), set(), False
+    for c in CASES:
+        z = np.load(c)
+        shapes.add(tuple(z["logits"].shape))
+        gammas |= set(float(g) for g in z["focal_gammas"]) if "focal_gammas" in z else set()
+        absent |= bool((z["onehot_sum"][1:] == 0).any())
+    assert (2, 3, 19, 23) in shapes and any(s[0] == 1 for s in shapes)
+    assert {0.5, 1.0, 3.5} <= gammas and absent
+
+
+GAMMA_CASES = [(c, float(g)) for c in CASES for g in (np.load(c)["focal_gammas"] if "focal_gammas" in np.load(c) else ())]
+
+
+@pytest.mark.parametrize("path,gamma", GAMMA_CASES, ids=[f"{os.path.basename(c)}-g{g:g}" for c, g in GAMMA_CASES])
+def test_differentiable_restatement_grads_at_other_gammas(path, gamma):
+    """the ``gamma`` parameter of train_ref.loss_from_logits / losses_ref.compound_loss vs autograd through the
+    imported reference FocalLoss(gamma=...), at the tolerances of test_differentiable_restatement_grads."""
+    z = np.load(path)
+    logits = torch.from_numpy(z["logits"]).clone().requires_grad_(True)
+    mask = torch.from_numpy(z["mask"])
+    loss, p = T.loss_from_logits(logits, mask, ("GDICE", "FOCAL"), gamma=gamma)
+    loss.backward()
+    key = f"GDICE+FOCAL@gamma={gamma:g}"
+    assert float(loss.detach()) == pytest.approx(float(z[f"loss[{key}]"]), rel=1e-6, abs=1e-7)
+    ref = z[f"dlogits[{key}]"]
+    np.testing.assert_allclose(logits.grad.numpy(), ref, rtol=1e-5, atol=1e-9 + 1e-6 * np.abs(ref).max())
+    total64, _ = L.compound_loss(p.detach(), mask, ("GDICE", "FOCAL"), gamma=gamma)
+    assert float(total64) == pytest.approx(float(z[f"loss[{key}]"]), rel=2e-6, abs=2e-7)
 
 
 @pytest.mark.parametrize("path", CASES, ids=[os.path.basename(c) for c in CASES])
