@@ -83,6 +83,20 @@ class PyTorchInference(Inference):
         x = ops.split_normalize_u8(raster_chw_u8, d, first, count, MEAN, STD, self._channels)
         return self._model.predict_classes(x, dtype="uint8", nhwc=True)
 
+    def run_windows(self, raster_chw_u8: torch.Tensor, d: int, overlap: int, first: int, count: int,
+                    want: str = "classes", precision: str = "fp32") -> torch.Tensor:
+        """``run_blocks`` on the overlap-stitch grid (``tiler.window_grid``: origins ``d - overlap`` apart; overlap 0 is
+        the block grid): windows ``first`` .. ``first + count - 1`` through ONE gather (``dt_window_normalize_u8``) and the
+        forward -> ``want="classes"``: uint8 class maps [count,d,d] (fused argmax, for ``ops.stitch_classes``);
+        ``want="logits"``: fp32 NCHW logits [count,K,d,d] (for ``ops.stitch_accumulate``)"""
+        if want not in ("classes", "logits"):
+            raise ValueError(f"want {want!r}: use 'classes' or 'logits'")
+        self._model.to(raster_chw_u8.device)
+        x = ops.window_normalize_u8(raster_chw_u8, d, overlap, first, count, MEAN, STD, self._channels)
+        if want == "classes":
+            return self._model.predict_classes(x, dtype="uint8", precision=precision, nhwc=True)
+        return self._model.predict_logits(x, precision=precision, nhwc=True)
+
     @staticmethod
     def is_valid_raster(raster_chw_u8: torch.Tensor) -> bool:
         """scripts/inference.py:60-62 ``is_valid_tile`` on a raster in HBM: False when band 1 holds only 0 / 255"""

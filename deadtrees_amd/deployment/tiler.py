@@ -44,6 +44,41 @@ def unmake_blocks_vectorized(x, d: int, m: int, n: int) -> np.ndarray:
     return np.concatenate(x).reshape(m // d, n // d, d, d).transpose(0, 2, 1, 3).reshape(m, n)
 
 
+# ---------------------------------------------------------------------- overlap-stitch geometry (no GPU needed)
+# One definition, restated by csrc/stitch.hip: d = window edge, overlap o even with 0 <= o <= d/2, stride s = d - o; an
+# axis of length L carries n(L) = max(1, ceil((L - o) / s)) windows; window k = i * nx + j starts at (i * s, j * s).
+def _check_overlap(d: int, overlap: int) -> None:
+    if d <= 0:
+        raise ValueError(f"window edge must be positive, got {d}")
+    if overlap < 0 or overlap % 2:
+        raise ValueError(f"overlap must be even and >= 0, got {overlap}")
+    if 2 * overlap > d:
+        raise ValueError(f"overlap must be <= d/2 = {d // 2}, got {overlap}")
+
+
+def window_grid(h: int, w: int, d: int, overlap: int = 0) -> Tuple[int, int, int]:
+    """(ny, nx, stride) of the d x d windows that cover an h x w raster with ``overlap`` pixels shared between neighbours;
+    overlap 0 is the block grid (ceil(h/d), ceil(w/d), d)"""
+    _check_overlap(d, overlap)
+    s = d - overlap
+    return max(1, -(-(h - overlap) // s)), max(1, -(-(w - overlap) // s)), s
+
+
+def blend_ramp(d: int, overlap: int) -> np.ndarray:
+    """fp64 [d] blend weights along one axis of a window: r(t) = min(1, (t+1)/(o+1), (d-t)/(o+1)); a window pixel (y, x)
+    weighs r(y) * r(x), and the ramps of two neighbouring windows sum to 1 across their overlap"""
+    _check_overlap(d, overlap)
+    t = np.arange(d, dtype=np.float64)
+    return np.minimum(1.0, np.minimum((t + 1.0) / (overlap + 1.0), (d - t) / (overlap + 1.0)))
+
+
+def window_keep(i: int, n: int, d: int, overlap: int) -> Tuple[int, int]:
+    """crop mode: the raster rows (columns alike) [lo, hi) that window ``i`` of ``n`` keeps — interior edges give up
+    overlap/2 pixels; the kept ranges tile [0, (n-1) * stride + d) exactly once"""
+    s = d - overlap
+    return i * s + (overlap // 2 if i > 0 else 0), i * s + d - (overlap // 2 if i < n - 1 else 0)
+
+
 @dataclass
 class TileInfo:
     size: Tuple[int, int]
@@ -174,28 +209,51 @@ class Tiler:
 
 
 def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, rank: int = 0, world: int = 1,
-                  device: str = "cuda", tile_shape: Optional[Tuple[int, int]] = None, skip_blank: bool = True):
+                  device: str = "cuda", tile_shape: Optional[Tuple[int, int]] = None, skip_blank: bool = True,
+                  overlap: int = 0, blend: str = "crop", return_probs: bool = False):
     """the directory loop of scripts/inference.py:71-115 over in-memory rasters (GeoTIFF I/O needs rioxarray, absent
     here): ``rasters`` yields ``array`` or ``(key, array)``; rank r of ``world`` takes rasters r, r + world, ... (tiles are
     independent: no collective).  Yields ``(key, class_map)`` in input order of the rank's share; rasters whose band 1
     holds only 0 / 255 (``is_valid_tile``, :60-62) are skipped like the reference does — ``(key, None)`` — without a
-    forward pass (device reduction over the uploaded raster, ``ops.band_has_data``)."""
+    forward pass (device reduction over the uploaded raster, ``ops.band_has_data``).  ``overlap`` / ``blend`` /
+    ``return_probs``: as in ``infer_tile`` (every raster stays on its rank, so overlap needs no exchange)."""
     for i, item in enumerate(rasters):
         if i % world != rank:
             continue
         key, arr = item if isinstance(item, tuple) else (i, item)
         yield key, infer_tile(inference, arr, subtile=subtile, batch_size=batch_size, device=device, tile_shape=tile_shape,
-                              skip_blank=skip_blank)
+                              skip_blank=skip_blank, overlap=overlap, blend=blend, return_probs=return_probs)
 
 
 def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size: int = 64, rank: int = 0,
                world: int = 1, device: str = "cuda", group=None, tile_shape: Optional[Tuple[int, int]] = None,
-               on_device: Optional[bool] = None, skip_blank: bool = False) -> Optional[np.ndarray]:
+               on_device: Optional[bool] = None, skip_blank: bool = False, overlap: int = 0, blend: str = "crop",
+               return_probs: bool = False):
     """whole-tile inference of scripts/inference.py:80-115 on the MI355X path: split -> (uint8 H2D, normalise on the
     device) -> forward + fused argmax -> uint8 D2H -> merge.  With world > 1 the sub-tile batches j = rank (mod world)
     are processed locally and the uint8 class maps are all-gathered (no other collective: tiles are independent).
     ``on_device`` (default: single rank + uint8 raster + HIP device) does the block split / merge on the GPU as well:
-    one H2D copy of the raster, one D2H copy of the merged map (``_infer_tile_on_device``; same result, tested)."""
+    one H2D copy of the raster, one D2H copy of the merged map (``_infer_tile_on_device``; same result, tested).
+
+    ``overlap`` > 0 (even, <= subtile/2): neighbouring windows share that many pixels (``window_grid``) and are stitched
+    on the device, single rank only — ``blend="crop"``: every window keeps its centre (``window_keep``), the map is the
+    fused argmax of exactly one window per pixel; ``blend="average"``: the windows' softmax probabilities are blended with
+    the ramp weights of ``blend_ramp`` and the map is their argmax; ``return_probs=True`` (average mode) returns
+    ``(map, probs fp32 [K,h,w])``.  ``overlap=0`` is the block path above, unchanged."""
+    if blend not in ("crop", "average"):
+        raise ValueError(f"blend {blend!r}: use 'crop' or 'average'")
+    if overlap:
+        _check_overlap(subtile, overlap)
+        if world != 1:
+            raise ValueError("infer_tile: overlap stitching is the single-rank form (shard by raster: infer_rasters)")
+        if return_probs and blend != "average":
+            raise ValueError("infer_tile: return_probs needs blend='average'")
+        if on_device is False or not hasattr(inference, "run_windows"):
+            raise ValueError("infer_tile: overlap stitching runs on the device and needs an inference object with run_windows")
+        return _infer_tile_stitched(inference, arr_chw_u8, subtile, overlap, blend, batch_size, device, skip_blank,
+                                    return_probs)
+    if return_probs:
+        raise ValueError("infer_tile: return_probs needs overlap > 0 and blend='average'")
     if tile_shape is None:
         h, w = arr_chw_u8.shape[1], arr_chw_u8.shape[2]
         if h <= 2048 and w <= 2048 and 2048 % subtile == 0:
@@ -266,3 +324,38 @@ def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch
     maps = (outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)).to(torch.uint8)
     merged = maps.view(nby, nbx, d, d).permute(0, 2, 1, 3).reshape(nby * d, nbx * d)
     return merged[:h, :w].contiguous().cpu().numpy()
+
+
+def _infer_tile_stitched(inference, arr_chw_u8: np.ndarray, d: int, overlap: int, blend: str, batch_size: int, device: str,
+                         skip_blank: bool = False, return_probs: bool = False):
+    """``infer_tile`` with overlapping windows: ONE uint8 H2D copy of the raster, per batch of windows one gather
+    (``dt_window_normalize_u8``) + forward + one stitch kernel into a raster-sized buffer in HBM, ONE uint8 D2H copy of the
+    map (plus the fp32 probabilities when asked for).  Batches run in ascending window order, which is what makes the
+    average-mode accumulator independent of ``batch_size``."""
+    from .. import ops
+    if arr_chw_u8.dtype != np.uint8:
+        raise ValueError(f"infer_tile: overlap stitching reads a uint8 raster, got {arr_chw_u8.dtype}")
+    C, h, w = arr_chw_u8.shape
+    ny, nx, _ = window_grid(h, w, d, overlap)
+    nch = int(getattr(inference, "in_channels", C) or C)
+    if 0 < nch < C:                 # band planes the network never reads stay on the host
+        arr_chw_u8, C = arr_chw_u8[:nch], nch
+    x = torch.from_numpy(np.ascontiguousarray(arr_chw_u8)).to(device, non_blocking=True)
+    if skip_blank and int(ops.band_has_data(x[0])) == 0:
+        return None
+    n = ny * nx
+    if blend == "crop":
+        out = torch.empty((h, w), dtype=torch.uint8, device=x.device)      # the kept regions tile it: every byte is written
+        for j in range(0, n, batch_size):
+            ops.stitch_classes(inference.run_windows(x, d, overlap, j, min(batch_size, n - j), want="classes"), out, overlap, j)
+        return out.cpu().numpy()
+    acc = None
+    for j in range(0, n, batch_size):
+        logits = inference.run_windows(x, d, overlap, j, min(batch_size, n - j), want="logits")
+        if acc is None:
+            acc = torch.zeros((logits.shape[1], h, w), dtype=torch.float32, device=x.device)
+        ops.stitch_accumulate(logits, acc, overlap, j)
+    if return_probs:
+        classes, probs = ops.stitch_finalize(acc, want_probs=True)
+        return classes.cpu().numpy(), probs.cpu().numpy()
+    return ops.stitch_finalize(acc).cpu().numpy()

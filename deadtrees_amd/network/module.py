@@ -414,6 +414,24 @@ class UNetHIP(nn.Module):
         return am
 
     @torch.no_grad()
+    def predict_logits(self, x: torch.Tensor, precision: str = "fp32", nhwc: bool = False) -> torch.Tensor:
+        """the fp32 NCHW logits ``predict_classes`` takes its argmax of (same forward, eval-mode BN, same ``precision`` /
+        ``nhwc`` meaning): what the overlap-stitch blend reads"""
+        self._require_gpu(x)
+        if precision == "bf16":
+            if nhwc:
+                x = x.permute(0, 3, 1, 2).contiguous()
+            return self.engine.forward_bf16_eval(x.float(), self.flat_params.detach(), self.bn_state)[0]
+        if precision != "fp32":
+            raise ValueError(f"precision {precision!r}: use 'fp32' or 'bf16'")
+        was = self.training
+        self.eval()
+        try:
+            return self.engine.forward(x.float(), self.flat_params.detach(), self.bn_state, False, save=False, nhwc=nhwc)[0]
+        finally:
+            self.train(was)
+
+    @torch.no_grad()
     def forward_bf16(self, x: torch.Tensor) -> torch.Tensor:
         """eval-mode logits (fp32 tensor) from the bf16 path"""
         self._require_gpu(x)

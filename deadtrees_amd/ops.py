@@ -683,6 +683,75 @@ def split_normalize_u8(raster_chw_u8, d: int, first: int, count: int, mean, std,
     return out
 
 
+def _stitch_grid(h: int, w: int, d: int, overlap: int, what: str):
+    """(ny, nx) of the overlap-stitch window grid, from the library's own count (the kernels' definition)"""
+    lib = _lib.load()
+    ny, nx = lib.dt_stitch_window_count(h, d, overlap), lib.dt_stitch_window_count(w, d, overlap)
+    _lib.check(min(ny, nx, 0), what)
+    return ny, nx
+
+
+def window_normalize_u8(raster_chw_u8, d: int, overlap: int, first: int, count: int, mean, std, c_dst: int):
+    """``split_normalize_u8`` with window origins ``d - overlap`` apart: band-major uint8 raster [C,h,w] on the device -> the
+    fp32 NHWC windows [count,d,d,c_dst] ``first`` .. of the row-major overlap-stitch grid (``tiler.window_grid``); overlap 0
+    is the block grid, bit-identical to ``split_normalize_u8``"""
+    _gpu(raster_chw_u8)
+    if raster_chw_u8.dtype != torch.uint8 or raster_chw_u8.dim() != 3:
+        raise RuntimeError("window_normalize_u8: raster must be uint8 [C,h,w]")
+    cs, h, w = raster_chw_u8.shape
+    ny, nx = _stitch_grid(h, w, d, overlap, "window_normalize_u8")
+    if first < 0 or count <= 0 or first + count > ny * nx:
+        raise RuntimeError(f"window_normalize_u8: windows {first}..{first + count - 1} outside the {ny} x {nx} grid")
+    out = torch.empty((count, d, d, c_dst), dtype=torch.float32, device=raster_chw_u8.device)
+    m = (C.c_float * c_dst)(*[float(v) for v in mean[:c_dst]])
+    s = (C.c_float * c_dst)(*[float(v) for v in std[:c_dst]])
+    _lib.check(_lib.load().dt_window_normalize_u8(_p(raster_chw_u8.contiguous()), _p(out), cs, h, w, d, d - overlap, nx, first,
+                                                  count, c_dst, m, s, _st()), "dt_window_normalize_u8")
+    return out
+
+
+def stitch_accumulate(logits, acc, overlap: int, first: int):
+    """average-mode blend: fp32 NCHW logits [count,K,d,d] of the windows ``first`` .. -> ``acc`` fp32 [K,h,w] (zeroed before
+    the first call) += ramp weight * softmax, in place.  Calls in ascending window order give a bit-identical accumulator
+    for every split of the windows into calls.  Returns ``acc``."""
+    _gpu(logits, acc)
+    if logits.dtype != torch.float32 or logits.dim() != 4 or logits.shape[2] != logits.shape[3]:
+        raise RuntimeError("stitch_accumulate: logits must be float32 [count,K,d,d]")
+    count, K, d, _ = logits.shape
+    if acc.dtype != torch.float32 or acc.dim() != 3 or acc.shape[0] != K or not acc.is_contiguous():
+        raise RuntimeError(f"stitch_accumulate: acc must be contiguous float32 [{K},h,w]")
+    _lib.check(_lib.load().dt_stitch_accumulate(_p(logits.contiguous()), _p(acc), K, acc.shape[1], acc.shape[2], d, overlap,
+                                                first, count, _st()), "dt_stitch_accumulate")
+    return acc
+
+
+def stitch_finalize(acc, want_probs: bool = False):
+    """accumulator fp32 [K,h,w] -> uint8 class map [h,w] (argmax, ties -> lowest class); with ``want_probs`` also the
+    normalised probabilities fp32 [K,h,w]: returns ``classes`` or ``(classes, probs)``"""
+    _gpu(acc)
+    if acc.dtype != torch.float32 or acc.dim() != 3 or not acc.is_contiguous():
+        raise RuntimeError("stitch_finalize: acc must be contiguous float32 [K,h,w]")
+    K, h, w = acc.shape
+    classes = torch.empty((h, w), dtype=torch.uint8, device=acc.device)
+    probs = torch.empty_like(acc) if want_probs else None
+    _lib.check(_lib.load().dt_stitch_finalize(_p(acc), _p(classes), _p(probs), K, h, w, _st()), "dt_stitch_finalize")
+    return (classes, probs) if want_probs else classes
+
+
+def stitch_classes(maps_u8, out_hw_u8, overlap: int, first: int):
+    """crop-mode merge: uint8 class maps [count,d,d] of the windows ``first`` .. -> their kept regions written into the
+    uint8 raster map ``out_hw_u8`` [h,w] in place (regions are disjoint).  Returns ``out_hw_u8``."""
+    _gpu(maps_u8, out_hw_u8)
+    if maps_u8.dtype != torch.uint8 or maps_u8.dim() != 3 or maps_u8.shape[1] != maps_u8.shape[2]:
+        raise RuntimeError("stitch_classes: maps must be uint8 [count,d,d]")
+    if out_hw_u8.dtype != torch.uint8 or out_hw_u8.dim() != 2 or not out_hw_u8.is_contiguous():
+        raise RuntimeError("stitch_classes: the raster map must be contiguous uint8 [h,w]")
+    count, d, _ = maps_u8.shape
+    _lib.check(_lib.load().dt_stitch_classes_u8(_p(maps_u8.contiguous()), _p(out_hw_u8), out_hw_u8.shape[0],
+                                                out_hw_u8.shape[1], d, overlap, first, count, _st()), "dt_stitch_classes_u8")
+    return out_hw_u8
+
+
 def band_has_data(band_u8) -> torch.Tensor:
     """int32[1] device flag: 1 iff some byte is neither 0 nor 255 (scripts/inference.py:60-62 is_valid_tile, no host pass)"""
     _gpu(band_u8)

@@ -213,6 +213,33 @@ int dt_normalize_u8(const uint8_t* src, float* dst, int64_t n_pix, int Csrc, int
  * wide; pixels beyond the raster are the tiler's zero padding (normalised like a zero byte). */
 int dt_split_normalize_u8(const uint8_t* raster_chw, float* dst_nhwc, int Csrc, int h, int w, int d, int nbx,
                           int first_block, int n_blocks, int Cdst, const float* mean, const float* stdv, void* stream);
+
+/* Overlap-stitched tiled inference (BASELINE configs[5]; the reference has no overlap).  Geometry, shared by the four
+ * entry points: d = window edge, overlap o even with 0 <= o <= d/2, stride s = d - o; an axis of length L carries
+ * n(L) = max(1, ceil((L - o) / s)) windows (dt_stitch_window_count; <0 on bad arguments); window k = i * nx + j has its
+ * origin at (i * s, j * s), row-major; pixels beyond the raster are the tiler's zero byte; o = 0 is the block grid of
+ * dt_split_normalize_u8.  A raster pixel lies in at most 2 windows per axis.  K <= 4 classes. */
+int dt_stitch_window_count(int L, int d, int overlap);
+/* dt_split_normalize_u8 with window origins `stride` = d - o apart (same arithmetic: bit-identical at stride == d, which is
+ * how dt_split_normalize_u8 is served): windows first .. first + count - 1 of the grid that is nwx = n(w) windows wide ->
+ * fp32 NHWC [count][d][d][Cdst]. */
+int dt_window_normalize_u8(const uint8_t* raster_chw, float* dst_nhwc, int Csrc, int h, int w, int d, int stride, int nwx,
+                           int first, int count, int Cdst, const float* mean, const float* stdv, void* stream);
+/* average mode.  logits: fp32 NCHW [count][K][d][d] of the windows first .. first + count - 1; acc: fp32 planar [K][h][w],
+ * zeroed before the first call.  acc[k][gy][gx] += r(y) * r(x) * softmax_k(logits) for every window of the range that
+ * covers the pixel, r(t) = min(1, (t + 1) / (o + 1), (d - t) / (o + 1)).  One thread owns a pixel and adds its windows in
+ * ascending index: with calls in ascending window order the accumulator is bit-identical for every split into calls. */
+int dt_stitch_accumulate(const float* logits, float* acc, int K, int h, int w, int d, int overlap, int first, int count,
+                         void* stream);
+/* classes uint8 [h][w] = argmax_k acc (ties -> lowest k, the head kernel's rule); probs (may be NULL): fp32 [K][h][w] =
+ * acc_k / sum_k acc. */
+int dt_stitch_finalize(const float* acc, uint8_t* classes, float* probs, int K, int h, int w, void* stream);
+/* crop mode.  maps: uint8 [count][d][d] class maps of the windows first .. (the head kernel's fused argmax); window i of n
+ * keeps rows (columns alike) [i * s + (i > 0) * o/2, i * s + d - (i < n - 1) * o/2) — disjoint regions that tile the
+ * raster — and writes them into classes uint8 [h][w]. */
+int dt_stitch_classes_u8(const uint8_t* maps, uint8_t* classes, int h, int w, int d, int overlap, int first, int count,
+                         void* stream);
+
 /* scripts/inference.py:60-62 is_valid_tile: flag[0] (int32, zero it first) = 1 iff some byte of band[n] is neither 0 nor
  * 255 (a raster whose first band is all 0 / 255 is skipped by the reference's driver). */
 int dt_band_has_data(const uint8_t* band, int64_t n, int32_t* flag, void* stream);
