@@ -5,6 +5,7 @@
 // All kernels: 16 B per lane (f32x4) coalesced along the channel-fastest NHWC axis, wave64 shuffle
 // reductions, deterministic two-stage sums (no float atomics).
 #include "conv_host.h"
+#include "views.h"
 
 #include <math.h>
 
@@ -1060,18 +1061,8 @@ extern "C" int dt_band_has_data(const uint8_t* band, int64_t n, int32_t* flag, v
 // RandomBrightnessContrast(brightness_by_max=False) -> Normalize -> ToTensorV2, per sample on loader CPUs.
 // Here: the host draws the per-sample parameters, one gather pass applies flip + rot90 + the brightness/contrast
 // LUT + normalisation while converting uint8 NHWC tiles to the fp32 NHWC stem input; labels take the same
-// geometric map.  geo[b] = (flip: 0 none, 1 horizontal, 2 vertical; rot: k of np.rot90, counter-clockwise).
-__device__ __forceinline__ void aug_source_pixel(int flip, int rot, int y, int x, int H, int W, int* sy, int* sx) {
-  // out = rot90^k(flip(in)):  rot90(m,1)[i][j] = m[j][N-1-i]
-  int ry = y, rx = x;
-  if (rot == 1) { ry = x; rx = W - 1 - y; }
-  else if (rot == 2) { ry = H - 1 - y; rx = W - 1 - x; }
-  else if (rot == 3) { ry = H - 1 - x; rx = y; }
-  if (flip == 1) rx = W - 1 - rx;
-  else if (flip == 2) ry = H - 1 - ry;
-  *sy = ry;
-  *sx = rx;
-}
+// geometric map.  geo[b] = (flip: 0 none, 1 horizontal, 2 vertical; rot: k of np.rot90, counter-clockwise); the pixel map
+// itself is aug_source_pixel of views.h, shared with the test-time views of stitch.hip.
 
 __global__ __launch_bounds__(256) void u8_image_sums_kernel(const uint8_t* __restrict__ src, int64_t n_per,
                                                             unsigned long long* __restrict__ sums) {

@@ -84,18 +84,24 @@ class PyTorchInference(Inference):
         return self._model.predict_classes(x, dtype="uint8", nhwc=True)
 
     def run_windows(self, raster_chw_u8: torch.Tensor, d: int, overlap: int, first: int, count: int,
-                    want: str = "classes", precision: str = "fp32") -> torch.Tensor:
+                    want: str = "classes", precision: str = "fp32", views=None) -> torch.Tensor:
         """``run_blocks`` on the overlap-stitch grid (``tiler.window_grid``: origins ``d - overlap`` apart; overlap 0 is
         the block grid): windows ``first`` .. ``first + count - 1`` through ONE gather (``dt_window_normalize_u8``) and the
         forward -> ``want="classes"``: uint8 class maps [count,d,d] (fused argmax, for ``ops.stitch_classes``);
-        ``want="logits"``: fp32 NCHW logits [count,K,d,d] (for ``ops.stitch_accumulate``)"""
+        ``want="logits"``: fp32 NCHW logits [count,K,d,d] (for ``ops.stitch_accumulate``).  ``views`` (T (flip, rot) pairs,
+        ``tiler.tta_views``): every window goes through the network once per view (``dt_window_normalize_u8_views``) ->
+        logits [count,T,K,d,d], still in view orientation (``ops.stitch_accumulate(views=...)`` maps them back); a class
+        map cannot be averaged, so ``want="classes"`` with views is a ``ValueError``"""
         if want not in ("classes", "logits"):
             raise ValueError(f"want {want!r}: use 'classes' or 'logits'")
+        if views is not None and want == "classes":
+            raise ValueError("run_windows: views need want='logits' (class maps of several views cannot be averaged)")
         self._model.to(raster_chw_u8.device)
-        x = ops.window_normalize_u8(raster_chw_u8, d, overlap, first, count, MEAN, STD, self._channels)
+        x = ops.window_normalize_u8(raster_chw_u8, d, overlap, first, count, MEAN, STD, self._channels, views=views)
         if want == "classes":
             return self._model.predict_classes(x, dtype="uint8", precision=precision, nhwc=True)
-        return self._model.predict_logits(x, precision=precision, nhwc=True)
+        logits = self._model.predict_logits(x, precision=precision, nhwc=True)
+        return logits if views is None else logits.reshape(count, len(views), *logits.shape[1:])
 
     @staticmethod
     def is_valid_raster(raster_chw_u8: torch.Tensor) -> bool:
@@ -106,23 +112,46 @@ class PyTorchInference(Inference):
 class PyTorchEnsembleInference:
     """reference deployment/inference.py:65-116: an odd number of checkpoints, per-pixel majority (torch.mode) of
     their class maps.  Here every model emits a uint8 map from the fused head kernel and one vote kernel
-    (``dt_ensemble_vote``, ties -> smallest class like torch.mode) replaces stack + mode."""
+    (``dt_ensemble_vote``, ties -> smallest class like torch.mode) replaces stack + mode.
 
-    def __init__(self, *model_files: Union[str, Path]):
-        self._models, self._channels, self._classes = [], None, None
+    ``vote`` says how ``tiler.infer_tile`` combines the members over a whole raster (``.run`` is always the reference's
+    hard vote): ``"hard"`` (default) — the majority of the members' raster class maps; ``"soft"`` — the members'
+    probabilities are added into one accumulator and the map is its argmax.  ``members`` are the ``PyTorchInference``
+    objects the tiler runs window batches through."""
+
+    def __init__(self, *model_files: Union[str, Path], vote: str = "hard"):
+        self._models, self._members, self._channels, self._classes = [], [], None, None
+        if vote not in ("hard", "soft"):
+            raise ValueError(f"vote {vote!r}: use 'hard' or 'soft'")
+        self.vote = vote
         if len(model_files) % 2 == 0:
             raise ValueError("PyTorchEnsembleInference requires an uneven number of models")
         for model_file in model_files:
             model_file = Path(model_file)
             if model_file.suffix != ".ckpt":
                 raise ValueError(f"Ckpt file expected, but {model_file.suffix} received")
-            model = SemSegment.load_from_checkpoint(model_file)
-            model.eval()
+            member = PyTorchInference(model_file)
+            channels, classes = member.in_channels, member._model.spec.classes
             if not self._channels:
-                self._channels, self._classes = model.in_channels, model.model.spec.classes
-            if model.in_channels != self._channels or model.model.spec.classes != self._classes:
+                self._channels, self._classes = channels, classes
+            if channels != self._channels or classes != self._classes:
                 raise ValueError("Models are not compatible since they were trained for different channel configs")
-            self._models.append(model.model)
+            self._members.append(member)
+            self._models.append(member._model)
+
+    @property
+    def members(self):
+        """one ``PyTorchInference`` per checkpoint, in the order given"""
+        return tuple(self._members)
+
+    @property
+    def in_channels(self):
+        """band planes the members read (infer_tile copies only these to the device)"""
+        return self._channels
+
+    @property
+    def classes(self):
+        return self._classes
 
     def run(self, input_tensor, device: str = "cuda"):
         if not isinstance(input_tensor, torch.Tensor):

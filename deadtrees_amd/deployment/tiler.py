@@ -79,6 +79,42 @@ def window_keep(i: int, n: int, d: int, overlap: int) -> Tuple[int, int]:
     return i * s + (overlap // 2 if i > 0 else 0), i * s + d - (overlap // 2 if i < n - 1 else 0)
 
 
+# ---------------------------------------------------------------------- test-time augmentation views (no GPU needed)
+# A view is (flip, rot): flip 0 none / 1 horizontal / 2 vertical, rot = k of np.rot90; view = rot90^k(flip(window)) — the
+# convention of the training augmentation (csrc/views.h).  A vertical flip is a horizontal one turned by 180 degrees, so
+# (2, k) is stored as (1, (k + 2) % 4): the eight distinct views are flip in {0, 1} x rot in 0..3.
+_TTA_SETS = {
+    "flips": ((0, 0), (1, 0), (2, 0), (0, 2)),          # identity, horizontal, vertical, both
+    "d4": tuple((f, k) for f in (0, 1) for k in range(4)),
+}
+
+
+def tta_views(spec=None) -> Tuple[Tuple[int, int], ...]:
+    """the views of a test-time-augmentation request as canonical ``(flip, rot)`` pairs: ``None`` -> the identity alone,
+    ``"flips"`` -> identity / horizontal / vertical / both, ``"d4"`` -> all eight, or an explicit sequence of pairs.
+    ``ValueError`` for an unknown name, an empty list, values outside flip 0..2 / rot 0..3, and views that coincide"""
+    if spec is None:
+        return ((0, 0),)
+    if isinstance(spec, str):
+        if spec not in _TTA_SETS:
+            raise ValueError(f"tta {spec!r}: use None, 'flips', 'd4' or a sequence of (flip, rot) pairs")
+        spec = _TTA_SETS[spec]
+    views = []
+    for item in spec:
+        try:
+            flip, rot = item
+        except (TypeError, ValueError):
+            raise ValueError(f"tta view {item!r}: expected a (flip, rot) pair") from None
+        if flip not in (0, 1, 2) or rot not in (0, 1, 2, 3):
+            raise ValueError(f"tta view {item!r}: flip must be in 0..2 and rot in 0..3")
+        views.append((1, (int(rot) + 2) % 4) if flip == 2 else (int(flip), int(rot)))
+    if not views:
+        raise ValueError("tta: no views given")
+    if len(set(views)) != len(views):
+        raise ValueError(f"tta: duplicate views after canonicalisation: {views}")
+    return tuple(views)
+
+
 @dataclass
 class TileInfo:
     size: Tuple[int, int]
@@ -210,25 +246,25 @@ class Tiler:
 
 def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, rank: int = 0, world: int = 1,
                   device: str = "cuda", tile_shape: Optional[Tuple[int, int]] = None, skip_blank: bool = True,
-                  overlap: int = 0, blend: str = "crop", return_probs: bool = False):
+                  overlap: int = 0, blend: str = "crop", return_probs: bool = False, tta=None):
     """the directory loop of scripts/inference.py:71-115 over in-memory rasters (GeoTIFF I/O needs rioxarray, absent
     here): ``rasters`` yields ``array`` or ``(key, array)``; rank r of ``world`` takes rasters r, r + world, ... (tiles are
     independent: no collective).  Yields ``(key, class_map)`` in input order of the rank's share; rasters whose band 1
     holds only 0 / 255 (``is_valid_tile``, :60-62) are skipped like the reference does — ``(key, None)`` — without a
     forward pass (device reduction over the uploaded raster, ``ops.band_has_data``).  ``overlap`` / ``blend`` /
-    ``return_probs``: as in ``infer_tile`` (every raster stays on its rank, so overlap needs no exchange)."""
+    ``return_probs`` / ``tta``: as in ``infer_tile`` (every raster stays on its rank, so overlap needs no exchange)."""
     for i, item in enumerate(rasters):
         if i % world != rank:
             continue
         key, arr = item if isinstance(item, tuple) else (i, item)
         yield key, infer_tile(inference, arr, subtile=subtile, batch_size=batch_size, device=device, tile_shape=tile_shape,
-                              skip_blank=skip_blank, overlap=overlap, blend=blend, return_probs=return_probs)
+                              skip_blank=skip_blank, overlap=overlap, blend=blend, return_probs=return_probs, tta=tta)
 
 
 def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size: int = 64, rank: int = 0,
                world: int = 1, device: str = "cuda", group=None, tile_shape: Optional[Tuple[int, int]] = None,
                on_device: Optional[bool] = None, skip_blank: bool = False, overlap: int = 0, blend: str = "crop",
-               return_probs: bool = False):
+               return_probs: bool = False, tta=None):
     """whole-tile inference of scripts/inference.py:80-115 on the MI355X path: split -> (uint8 H2D, normalise on the
     device) -> forward + fused argmax -> uint8 D2H -> merge.  With world > 1 the sub-tile batches j = rank (mod world)
     are processed locally and the uint8 class maps are all-gathered (no other collective: tiles are independent).
@@ -239,9 +275,30 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     on the device, single rank only — ``blend="crop"``: every window keeps its centre (``window_keep``), the map is the
     fused argmax of exactly one window per pixel; ``blend="average"``: the windows' softmax probabilities are blended with
     the ramp weights of ``blend_ramp`` and the map is their argmax; ``return_probs=True`` (average mode) returns
-    ``(map, probs fp32 [K,h,w])``.  ``overlap=0`` is the block path above, unchanged."""
+    ``(map, probs fp32 [K,h,w])``.  ``overlap=0`` is the block path above, unchanged.
+
+    ``tta`` (``tta_views``: ``"flips"``, ``"d4"`` or (flip, rot) pairs) averages every window's softmax over its views
+    before the blend; an ensemble (an inference object with ``members``) votes over its models — ``vote="hard"``: the
+    majority of the members' raster maps, ``vote="soft"``: all members add into one accumulator.  Both always take the
+    stitched device path, ``overlap=0`` included (``_infer_tile_multipass``); ``batch_size`` counts forward tiles."""
     if blend not in ("crop", "average"):
         raise ValueError(f"blend {blend!r}: use 'crop' or 'average'")
+    members = getattr(inference, "members", None)
+    if tta is not None or members is not None:
+        views = tta_views(tta)
+        _check_overlap(subtile, overlap)
+        if world != 1:
+            raise ValueError("infer_tile: test-time augmentation and ensembles are the single-rank form (shard by raster: "
+                             "infer_rasters)")
+        vote = getattr(inference, "vote", "hard") if members is not None else None
+        if return_probs and (blend != "average" or vote == "hard"):
+            raise ValueError("infer_tile: return_probs needs blend='average' and, for an ensemble, vote='soft'")
+        models = list(members) if members is not None else [inference]
+        if on_device is False or not all(hasattr(m, "run_windows") for m in models):
+            raise ValueError("infer_tile: test-time augmentation and ensembles run on the device and need inference objects "
+                             "with run_windows")
+        return _infer_tile_multipass(inference, models, vote, arr_chw_u8, subtile, overlap, blend, batch_size, device,
+                                     skip_blank, return_probs, None if tta is None else views)
     if overlap:
         _check_overlap(subtile, overlap)
         if world != 1:
@@ -355,6 +412,70 @@ def _infer_tile_stitched(inference, arr_chw_u8: np.ndarray, d: int, overlap: int
         if acc is None:
             acc = torch.zeros((logits.shape[1], h, w), dtype=torch.float32, device=x.device)
         ops.stitch_accumulate(logits, acc, overlap, j)
+    if return_probs:
+        classes, probs = ops.stitch_finalize(acc, want_probs=True)
+        return classes.cpu().numpy(), probs.cpu().numpy()
+    return ops.stitch_finalize(acc).cpu().numpy()
+
+
+def _infer_tile_multipass(inference, models, vote: Optional[str], arr_chw_u8: np.ndarray, d: int, overlap: int, blend: str,
+                          batch_size: int, device: str, skip_blank: bool, return_probs: bool, views):
+    """``infer_tile`` with test-time augmentation (``views``: canonical pairs, or None for the plain window) and / or an
+    ensemble (``models``; ``vote`` None for a single model).  One uint8 H2D copy of the raster; per model and batch of
+    windows one (views) gather + forward + one stitch kernel; one uint8 D2H copy of the map.
+
+    A model's own raster result follows the single-model rule — plain crop mode scatters the fused argmax
+    (``stitch_classes``); everything else accumulates probabilities (``weight="ramp"`` for ``blend="average"``,
+    ``weight="keep"`` for crop with views) and finalizes.  Hard vote: one ``ops.ensemble_vote`` over the members' raster
+    maps.  Soft vote: ONE accumulator, members outer / window batches inner, no 1/M (finalize normalises) — each pixel's
+    terms arrive model-major, windows ascending, views ascending, for every batch size."""
+    from .. import ops
+    if arr_chw_u8.dtype != np.uint8:
+        raise ValueError(f"infer_tile: the stitched device path reads a uint8 raster, got {arr_chw_u8.dtype}")
+    C, h, w = arr_chw_u8.shape
+    ny, nx, _ = window_grid(h, w, d, overlap)
+    n = ny * nx
+    nch = int(getattr(inference, "in_channels", C) or C)
+    if 0 < nch < C:                 # band planes the network never reads stay on the host
+        arr_chw_u8, C = arr_chw_u8[:nch], nch
+    x = torch.from_numpy(np.ascontiguousarray(arr_chw_u8)).to(device, non_blocking=True)
+    if skip_blank and int(ops.band_has_data(x[0])) == 0:
+        return None
+    T = len(views) if views is not None else 1
+    per = max(1, batch_size // T)                   # batch_size counts forward tiles
+    weight = "ramp" if blend == "average" else "keep"
+
+    def accumulate(model, acc):
+        for j in range(0, n, per):
+            cnt = min(per, n - j)
+            if views is None:
+                logits = model.run_windows(x, d, overlap, j, cnt, want="logits").unsqueeze(1)   # [count,1,K,d,d]: identity
+            else:
+                logits = model.run_windows(x, d, overlap, j, cnt, want="logits", views=views)
+            if acc is None:
+                acc = torch.zeros((logits.shape[2], h, w), dtype=torch.float32, device=x.device)
+            ops.stitch_accumulate(logits, acc, overlap, j, views=views or ((0, 0),), weight=weight)
+        return acc
+
+    def class_map(model):
+        if views is None and blend == "crop":
+            out = torch.empty((h, w), dtype=torch.uint8, device=x.device)
+            for j in range(0, n, batch_size):
+                ops.stitch_classes(model.run_windows(x, d, overlap, j, min(batch_size, n - j), want="classes"), out, overlap, j)
+            return out
+        return ops.stitch_finalize(accumulate(model, None))
+
+    if vote == "hard":
+        maps = torch.stack([class_map(m) for m in models], dim=0)
+        if len(models) == 1:
+            return maps[0].cpu().numpy()
+        out, _ = ops.ensemble_vote(maps, int(inference.classes), dtype="uint8")
+        return out.cpu().numpy()
+    if vote is None and not return_probs:
+        return class_map(models[0]).cpu().numpy()
+    acc = None
+    for m in models:
+        acc = accumulate(m, acc)
     if return_probs:
         classes, probs = ops.stitch_finalize(acc, want_probs=True)
         return classes.cpu().numpy(), probs.cpu().numpy()

@@ -214,7 +214,7 @@ int dt_normalize_u8(const uint8_t* src, float* dst, int64_t n_pix, int Csrc, int
 int dt_split_normalize_u8(const uint8_t* raster_chw, float* dst_nhwc, int Csrc, int h, int w, int d, int nbx,
                           int first_block, int n_blocks, int Cdst, const float* mean, const float* stdv, void* stream);
 
-/* Overlap-stitched tiled inference (BASELINE configs[5]; the reference has no overlap).  Geometry, shared by the four
+/* Overlap-stitched tiled inference (BASELINE configs[5]; the reference has no overlap).  Geometry, shared by all its
  * entry points: d = window edge, overlap o even with 0 <= o <= d/2, stride s = d - o; an axis of length L carries
  * n(L) = max(1, ceil((L - o) / s)) windows (dt_stitch_window_count; <0 on bad arguments); window k = i * nx + j has its
  * origin at (i * s, j * s), row-major; pixels beyond the raster are the tiler's zero byte; o = 0 is the block grid of
@@ -239,6 +239,25 @@ int dt_stitch_finalize(const float* acc, uint8_t* classes, float* probs, int K, 
  * raster — and writes them into classes uint8 [h][w]. */
 int dt_stitch_classes_u8(const uint8_t* maps, uint8_t* classes, int h, int w, int d, int overlap, int first, int count,
                          void* stream);
+/* Test-time augmentation on the stitched path.  A view is (flip: 0 none, 1 horizontal, 2 vertical; rot: k of np.rot90),
+ * view = rot90^k(flip(window)) as in dt_augment_normalize_u8; windows are square, so all eight are legal.  `views` is a
+ * HOST array of n_views <= 8 pairs (flip_0, rot_0, flip_1, rot_1, ...); it is read during the call and travels to the
+ * kernel by value.
+ * dt_window_normalize_u8 for n_views views per window: fp32 NHWC [count][n_views][d][d][Cdst], tile k * n_views + v is
+ * view v of window first + k — a bit-exact permutation of the plain window (zero padding included). */
+int dt_window_normalize_u8_views(const uint8_t* raster_chw, float* dst_nhwc, int Csrc, int h, int w, int d, int stride,
+                                 int nwx, int first, int count, int Cdst, const float* mean, const float* stdv,
+                                 const int* views, int n_views, void* stream);
+/* dt_stitch_accumulate for logits fp32 [count][n_views][K][d][d] of those tiles: per covering window (ascending index) the
+ * softmax of every view is read where the window pixel sits in that view, the n_views probability vectors are summed in
+ * view order and multiplied by 1.0f / n_views, then acc_k += weight * mean_k.  weight_mode DT_STITCH_WEIGHT_RAMP: the
+ * r(y) * r(x) of dt_stitch_accumulate (one view (0, 0): bit-identical to it); DT_STITCH_WEIGHT_KEEP: 1 inside the
+ * window's kept region of dt_stitch_classes_u8 and 0 outside, i.e. exactly one window per pixel.  Several models may add
+ * into one acc (soft vote), each in ascending window order; dt_stitch_finalize normalises. */
+#define DT_STITCH_WEIGHT_RAMP 0
+#define DT_STITCH_WEIGHT_KEEP 1
+int dt_stitch_accumulate_views(const float* logits, float* acc, int K, int h, int w, int d, int overlap, int first,
+                               int count, const int* views, int n_views, int weight_mode, void* stream);
 
 /* scripts/inference.py:60-62 is_valid_tile: flag[0] (int32, zero it first) = 1 iff some byte of band[n] is neither 0 nor
  * 255 (a raster whose first band is all 0 / 255 is skipped by the reference's driver). */
