@@ -120,6 +120,12 @@ SIGNATURES = {
     "dt_seg_loss_algebra": (C.c_int, [c_f, C.POINTER(LossCfg), C.c_int, C.c_int, C.c_int, C.c_int, c_f, c_f, c_f, c_f, c_f,
                                       c_f, c_f]),
     "dt_confusion_matrix": (C.c_int, [c_f, c_f, c_f, c_f, C.c_int, I64, c_f, c_f, c_f]),
+    "dt_head_eval_acc_doubles": (I64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dt_head_eval": (C.c_int, [c_f, c_f, c_f, c_f, c_f, c_f, F32, c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int,
+                               C.c_int, c_f]),
+    "dt_head_eval_bf16": (C.c_int, [c_f, c_f, c_f, c_f, c_f, c_f, F32, c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, c_f]),
+    "dt_eval_accumulate": (C.c_int, [c_f, F64, c_f, c_f]),
     "dt_augment_normalize_u8": (C.c_int, [c_f, c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(C.c_float), C.POINTER(C.c_float), c_f]),
     "dt_augment_labels": (C.c_int, [c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, c_f]),

@@ -33,6 +33,68 @@ __device__ __forceinline__ f32x4 head_load4(const void* x, size_t elem_off) {
   }
 }
 
+// One 8x32 output tile of image b with its halo -> LDS (zeros outside the image), for every kernel that computes logits
+template <bool XB>
+__device__ __forceinline__ void head_stage_tile(float (*tile)[HEAD_CIN + 1], const void* __restrict__ x, int b, int oy0,
+                                                int ox0, int H, int W, int t) {
+  constexpr int C = HEAD_CIN;
+  constexpr int HH = HEAD_TH + 2, HW_ = HEAD_TW + 2;
+  for (int i = t; i < HH * HW_ * (C / 4); i += 256) {
+    const int q = i % (C / 4), pix = i / (C / 4);
+    const int hy = pix / HW_, hx = pix % HW_;
+    const int iy = oy0 - 1 + hy, ix = ox0 - 1 + hx;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
+      v = head_load4<XB>(x, (((size_t)b * H + iy) * W + ix) * C + 4 * q);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tile[pix][4 * q + k] = v[k];
+  }
+}
+
+// The K logits of tile pixel (py, px) from the staged tile: THE definition of the head's arithmetic — head_tile_sums
+// (summation order kh -> kw -> cin, fp32 fma), then head_add_bias.  head_fwd_kernel and head_eval_kernel both call
+// them, so their logits, arg-max maps and [p > 0.5] counts are bit-identical.
+template <int K>
+__device__ __forceinline__ void head_tile_sums(const float (*tile)[HEAD_CIN + 1], const float* __restrict__ w, int py,
+                                               int px, float (&acc)[K]) {
+  constexpr int C = HEAD_CIN;
+  constexpr int HW_ = HEAD_TW + 2;
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = 0.f;
+#pragma unroll
+  for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) {
+      const float* tp = tile[(py + kh) * HW_ + px + kw];
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const float xv = tp[c];
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc[k] = fmaf(xv, w[(k * 9 + kh * 3 + kw) * C + c], acc[k]);
+      }
+    }
+}
+
+template <int K>
+__device__ __forceinline__ void head_add_bias(float (&z)[K], const float* __restrict__ bias) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) z[k] = z[k] + bias[k];
+}
+
+// ties -> lowest index (torch.argmax)
+template <int K>
+__device__ __forceinline__ int head_argmax(const float (&z)[K]) {
+  int best = 0;
+  float bv = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+    if (k == 0 || z[k] > bv) {
+      bv = z[k];
+      best = k;
+    }
+  return best;
+}
+
 template <int K, bool XB = false>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const void* __restrict__ x, const float* __restrict__ w,
                                                        const float* __restrict__ bias, float* __restrict__ logits,
@@ -47,47 +109,17 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const void* __restrict__ 
   const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, b = blockIdx.x / (tiles_x * tiles_y);
   const int oy0 = ty * HEAD_TH, ox0 = tx * HEAD_TW;
   const int t = threadIdx.x;
-  for (int i = t; i < HH * HW_ * (C / 4); i += 256) {
-    const int q = i % (C / 4), pix = i / (C / 4);
-    const int hy = pix / HW_, hx = pix % HW_;
-    const int iy = oy0 - 1 + hy, ix = ox0 - 1 + hx;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
-      v = head_load4<XB>(x, (((size_t)b * H + iy) * W + ix) * C + 4 * q);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) tile[pix][4 * q + k] = v[k];
-  }
+  head_stage_tile<XB>(tile, x, b, oy0, ox0, H, W, t);
   __syncthreads();
   const int py = t / HEAD_TW, px = t % HEAD_TW;
   const int oy = oy0 + py, ox = ox0 + px;
-  float acc[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) acc[k] = 0.f;
-  // summation order kh -> kw -> cin (then + bias) per output, fp32 fma
-#pragma unroll
-  for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw) {
-      const float* tp = tile[(py + kh) * HW_ + px + kw];
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        const float xv = tp[c];
-#pragma unroll
-        for (int k = 0; k < K; ++k) acc[k] = fmaf(xv, w[(k * 9 + kh * 3 + kw) * C + c], acc[k]);
-      }
-    }
+  float z[K];
+  head_tile_sums<K>(tile, w, py, px, z);
   if (oy < H && ox < W) {
-    int best = 0;
-    float bv = 0.f;
+    head_add_bias<K>(z, bias);
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const float v = acc[k] + bias[k];
-      logits[(((size_t)b * K + k) * H + oy) * W + ox] = v;
-      if (k == 0 || v > bv) {  // ties -> lowest index (torch.argmax)
-        bv = v;
-        best = k;
-      }
-    }
+    for (int k = 0; k < K; ++k) logits[(((size_t)b * K + k) * H + oy) * W + ox] = z[k];
+    const int best = head_argmax<K>(z);
     const size_t o = ((size_t)b * H + oy) * W + ox;
     if (am64) am64[o] = best;
     if (am8) am8[o] = (uint8_t)best;
@@ -899,6 +931,182 @@ extern "C" int dt_confusion_matrix(const int64_t* pred_i64, const uint8_t* pred_
   if (g < 1) g = 1;
   hipLaunchKernelGGL(confusion_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, pred_i64, pred_u8, target,
                      lu, K, n, (unsigned long long*)counts, err_flag);
+  DT_LAUNCH_CHECK();
+  return DT_OK;
+}
+
+// ------------------------------------------------------------------ fused evaluation head (validation epoch)
+// One pass over the 16-channel decoder output does what dt_head_fwd -> dt_seg_loss_fwd -> dt_confusion_matrix do in
+// three: head convolution (head_tile_sums + head_add_bias: the logits are those of dt_head_fwd, bit for bit, and never reach HBM),
+// channel softmax, the sums 0-7 of DT_LOSS_NACC (8, 9 = GWDICE need a cross-sample pre-pass over the logits: zero
+// here), arg-max, both confusion planes and the label-range flag.
+// A workgroup walks HE_TPW tiles of ONE image (4096 pixels, what seg_loss_fwd_kernel covers): the sums stay in fp32
+// registers (<= HE_TPW addends per lane: the integer slots 0, 6, 7 are exact), are reduced ONCE to fp64 across the
+// workgroup and leave as one partial row [K][NACC]; seg_loss_finalize_kernel adds the rows of an image in a fixed
+// order.  Confusion counts: LDS histogram -> 64-bit integer atomics (exact in any order), like confusion_kernel.
+#define HE_TPW 16
+
+static inline int head_eval_chunks(int H, int W) { return dt_cdiv(dt_cdiv(H, HEAD_TH) * dt_cdiv(W, HEAD_TW), HE_TPW); }
+
+template <int K, bool XB>
+__global__ __launch_bounds__(256) void head_eval_kernel(const void* __restrict__ x, const float* __restrict__ w,
+                                                        const float* __restrict__ bias,
+                                                        const int64_t* __restrict__ labels,
+                                                        const int64_t* __restrict__ lu, const float* __restrict__ dist,
+                                                        float gamma, double* __restrict__ part,
+                                                        unsigned long long* __restrict__ counts,
+                                                        uint8_t* __restrict__ am8, int32_t* __restrict__ err, int H,
+                                                        int W, int chunks) {
+  constexpr int C = HEAD_CIN;
+  constexpr int HH = HEAD_TH + 2, HW_ = HEAD_TW + 2;
+  constexpr int NS = 8;                       // slots 0-7
+  __shared__ float tile[HH * HW_][C + 1];
+  __shared__ unsigned int hist[2 * K * K];
+  __shared__ double sh[4][K * NS];
+  const int tiles_x = (W + HEAD_TW - 1) / HEAD_TW, tiles_img = tiles_x * ((H + HEAD_TH - 1) / HEAD_TH);
+  const int b = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
+  const int t = threadIdx.x;
+  const int py = t / HEAD_TW, px = t % HEAD_TW;
+  const size_t HWs = (size_t)H * W;
+  if (t < 2 * K * K) hist[t] = 0;
+  float acc[K][NS];
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int j = 0; j < NS; ++j) acc[k][j] = 0.f;
+  const int ti0 = chunk * HE_TPW;
+  const int ti1 = ti0 + HE_TPW < tiles_img ? ti0 + HE_TPW : tiles_img;
+#pragma unroll 1
+  for (int ti = ti0; ti < ti1; ++ti) {
+    const int oy0 = (ti / tiles_x) * HEAD_TH, ox0 = (ti % tiles_x) * HEAD_TW;
+    __syncthreads();                          // the previous tile's reads are done (first tile: hist is zero)
+    head_stage_tile<XB>(tile, x, b, oy0, ox0, H, W, t);
+    __syncthreads();
+    // (the opaque scalar zero keeps hipcc from hoisting the K * 144 scalar weight loads out of the tile loop: several
+    // hundred SGPRs spilled to VGPR lanes otherwise)
+    int zs = 0;
+    asm volatile("" : "+s"(zs));
+    float z[K];
+    head_tile_sums<K>(tile, w + zs, py, px, z);
+    const int oy = oy0 + py, ox = ox0 + px;
+    if (oy < H && ox < W) {
+      head_add_bias<K>(z, bias);
+      const size_t p = (size_t)oy * W + ox, o = (size_t)b * HWs + p;
+      const int best = head_argmax<K>(z);
+      if (am8) am8[o] = (uint8_t)best;
+      const int64_t lab = labels[o];
+      if (lab < 0 || lab >= K) {
+        err[0] = 1;                           // counted nowhere in the confusion planes (confusion_kernel skips it too)
+      } else {
+        atomicAdd(&hist[(int)lab * K + best], 1u);
+        if (lu && lu[o] == 1) atomicAdd(&hist[K * K + (int)lab * K + best], 1u);
+      }
+      // the per-pixel arithmetic of seg_loss_fwd_kernel, expression for expression
+      float pr[K];
+      float m = -INFINITY;
+#pragma unroll
+      for (int k = 0; k < K; ++k) m = fmaxf(m, z[k]);
+      float sum = 0.f;
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        pr[k] = expf(z[k] - m);
+        sum += pr[k];
+      }
+      const float inv = 1.f / sum;
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const float pk = pr[k] * inv;
+        const float tk = (lab == k) ? 1.f : 0.f;
+        const float lp = logf(pk + 1e-10f);
+        const float om = 1.f - pk;
+        const float wgt = (gamma == 2.f) ? om * om : (gamma == 0.f ? 1.f : powf(om, gamma));
+        const float hard = pk > 0.5f ? 1.f : 0.f;
+        acc[k][0] += tk;
+        acc[k][1] += pk * tk;
+        acc[k][2] += pk;
+        acc[k][3] += wgt * tk * lp;
+        acc[k][4] += tk * lp;
+        if (dist) acc[k][5] += pk * dist[((size_t)b * K + k) * HWs + p];
+        acc[k][6] += tk * hard;
+        acc[k][7] += hard;
+      }
+    }
+  }
+  const int lane = t & 63, wave = t >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      const double v = wave_sum_d((double)acc[k][j]);
+      if (lane == 0) sh[wave][k * NS + j] = v;
+    }
+  __syncthreads();                            // also: every histogram update of this workgroup is done
+  if (t < K * DT_LOSS_NACC) {
+    const int k = t / DT_LOSS_NACC, j = t % DT_LOSS_NACC;
+    const int i = k * NS + j;
+    part[(size_t)blockIdx.x * K * DT_LOSS_NACC + t] = j < NS ? (sh[0][i] + sh[1][i]) + (sh[2][i] + sh[3][i]) : 0.0;
+  }
+  if (t < 2 * K * K && hist[t]) atomicAdd(&counts[t], (unsigned long long)hist[t]);
+}
+
+extern "C" int64_t dt_head_eval_acc_doubles(int B, int K, int H, int W) {
+  if (B <= 0 || K <= 0 || H <= 0 || W <= 0) return 0;
+  return (int64_t)B * (1 + head_eval_chunks(H, W)) * K * DT_LOSS_NACC;
+}
+
+template <bool XB>
+static int head_eval_launch(const void* x, const float* w, const float* bias, const int64_t* labels, const int64_t* lu,
+                            const float* dist, float gamma, double* acc, int64_t* counts, uint8_t* am8, int32_t* err,
+                            int B, int H, int W, int Cin, int K, void* stream) {
+  DT_REQUIRE(x && w && bias && labels && acc && counts && err, "head_eval: null pointer (x, w, bias, labels, acc, counts, err_flag are required)");
+  DT_REQUIRE(B > 0 && H > 0 && W > 0, "head_eval: bad sizes B=%d H=%d W=%d", B, H, W);
+  DT_REQUIRE(Cin == HEAD_CIN, "head_eval: Cin must be %d (decoder_channels[-1]), got %d", HEAD_CIN, Cin);
+  DT_REQUIRE(K >= 2 && K <= HEAD_MAXK, "head_eval: K=%d unsupported (2..%d)", K, HEAD_MAXK);
+  DT_REQUIRE((int64_t)B * H * W < ((int64_t)1 << 40), "head_eval: too many pixels");
+  const int chunks = head_eval_chunks(H, W);
+  DT_REQUIRE((int64_t)B * chunks <= 0x7fffffff, "head_eval: grid too large");
+  const int grid = B * chunks;
+  double* part = acc + (size_t)B * K * DT_LOSS_NACC;
+  unsigned long long* cnt = (unsigned long long*)counts;
+  hipStream_t st = (hipStream_t)stream;
+  switch (K) {
+    case 2: hipLaunchKernelGGL((head_eval_kernel<2, XB>), dim3(grid), dim3(256), 0, st, x, w, bias, labels, lu, dist, gamma, part, cnt, am8, err, H, W, chunks); break;
+    case 3: hipLaunchKernelGGL((head_eval_kernel<3, XB>), dim3(grid), dim3(256), 0, st, x, w, bias, labels, lu, dist, gamma, part, cnt, am8, err, H, W, chunks); break;
+    default: hipLaunchKernelGGL((head_eval_kernel<4, XB>), dim3(grid), dim3(256), 0, st, x, w, bias, labels, lu, dist, gamma, part, cnt, am8, err, H, W, chunks); break;
+  }
+  DT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(seg_loss_finalize_kernel, dim3(B), dim3(64), 0, st, part, acc, chunks, K * DT_LOSS_NACC);
+  DT_LAUNCH_CHECK();
+  return DT_OK;
+}
+
+extern "C" int dt_head_eval(const float* x, const float* w, const float* bias, const int64_t* labels, const int64_t* lu,
+                            const float* dist, float gamma, double* acc, int64_t* counts, uint8_t* argmax_u8,
+                            int32_t* err_flag, int B, int H, int W, int Cin, int K, void* stream) {
+  return head_eval_launch<false>(x, w, bias, labels, lu, dist, gamma, acc, counts, argmax_u8, err_flag, B, H, W, Cin, K, stream);
+}
+
+extern "C" int dt_head_eval_bf16(const void* x_bf16, const float* w, const float* bias, const int64_t* labels,
+                                 const int64_t* lu, const float* dist, float gamma, double* acc, int64_t* counts,
+                                 uint8_t* argmax_u8, int32_t* err_flag, int B, int H, int W, int Cin, int K,
+                                 void* stream) {
+  return head_eval_launch<true>(x_bf16, w, bias, labels, lu, dist, gamma, acc, counts, argmax_u8, err_flag, B, H, W, Cin, K, stream);
+}
+
+// epoch[i] += weight * parts[i] (i < 8), epoch[8] += weight, fp64: the batch-size weighted epoch mean of the eight loss
+// and metric scalars is formed on the device, so a validation epoch ends with one device-to-host copy
+__global__ void eval_accumulate_kernel(const float* __restrict__ parts, double weight, double* __restrict__ epoch) {
+  const int i = threadIdx.x;
+  if (i < 8)
+    epoch[i] += weight * (double)parts[i];
+  else if (i == 8)
+    epoch[8] += weight;
+}
+
+extern "C" int dt_eval_accumulate(const float* parts, double weight, double* epoch, void* stream) {
+  DT_REQUIRE(parts && epoch, "eval_accumulate: null pointer");
+  DT_REQUIRE(weight >= 0.0, "eval_accumulate: weight must not be negative");
+  hipLaunchKernelGGL(eval_accumulate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, parts, weight, epoch);
   DT_LAUNCH_CHECK();
   return DT_OK;
 }

@@ -86,6 +86,36 @@ _DICE_KINDS = {"GDICE": 0, "DICE": 1, "GWDICE": 2}
 _KIND_CODE = dict(_DICE_KINDS, NONE=3)
 
 
+def dice_kind_of(losses, allow_no_dice: bool = False) -> str:
+    """the dice term of a loss list ("GDICE" | "DICE" | "GWDICE" | "NONE"): a later entry replaces an earlier one"""
+    dice_kind = [n for n in losses if n in _DICE_KINDS]
+    if not dice_kind:
+        if not allow_no_dice:
+            raise AssertionError("a dice term (GDICE, DICE or GWDICE) is mandatory")  # segmodel.py:143
+        return "NONE"          # the stand-alone loss callables of loss/callables.py
+    return dice_kind[-1]       # segmodel.py:113-127: a later entry replaces self.dice_loss
+
+
+def loss_algebra(acc: torch.Tensor, losses, B: int, K: int, H: int, W: int, use_boundary: bool, alpha: float = 1.0,
+                 gamma: float = 2.0, dice_kind: Optional[str] = None, want_wass: bool = False):
+    """dt_seg_loss_algebra on sums it is given (acc f64 [B,K,10] from ``loss_sums`` or from the fused evaluation head)
+    -> (parts fp32 [8] on the device, coef, wfocal, wbound, wass_a, wass_c).  No ATen arithmetic, no host sync."""
+    dev = acc.device
+    dice_kind = dice_kind or dice_kind_of(losses)
+    if dice_kind == "GWDICE" and not want_wass:
+        raise RuntimeError("loss_algebra: GWDICE needs the sums 8 and 9 of a loss_sums pass with its distance matrix")
+    # one fp32 workspace: parts[8] | coef[B*K*2] | wfocal[2] (+2 pad) | wbound[K -> 4] | wass_a[B] | wass_c[B]
+    o_coef, o_wf, o_wb, o_wa = 8, 8 + 2 * B * K, 8 + 2 * B * K + 4, 8 + 2 * B * K + 8
+    ws = torch.empty(o_wa + 2 * B, dtype=torch.float32, device=dev)
+    parts, coef, wf, wbound = ws[:8], ws[o_coef:o_wf], ws[o_wf:o_wf + 2], ws[o_wb:o_wb + K]
+    wass_a, wass_c = (ws[o_wa:o_wa + B], ws[o_wa + B:o_wa + 2 * B]) if want_wass else (None, None)
+    c = _lib.LossCfg(_KIND_CODE[dice_kind], 1 if use_boundary else 0, 1 if "FOCAL" in losses else 0,
+                     alpha if "BOUNDARY-RAMPED" in losses else 1.0, gamma)
+    _lib.check(_lib.load().dt_seg_loss_algebra(_p(acc), C.byref(c), B, K, H, W, _p(parts), _p(coef), _p(wf), _p(wbound),
+                                               _p(wass_a), _p(wass_c), _stream()), "dt_seg_loss_algebra")
+    return parts, coef, wf, wbound, wass_a, wass_c
+
+
 def loss_forward(logits: torch.Tensor, labels: torch.Tensor, distmap: Optional[torch.Tensor], cfg: dict):
     """reduction pass + device-side scalar algebra -> (parts fp32 [8] on the device, err flag, saved-for-backward).
     parts[i] follows PART_KEYS; parts[7] (= total) is the scalar to differentiate.  No ATen arithmetic, no host sync."""
@@ -95,23 +125,11 @@ def loss_forward(logits: torch.Tensor, labels: torch.Tensor, distmap: Optional[t
     B, K, H, W = logits.shape
     use_bd = ("BOUNDARY" in losses or "BOUNDARY-RAMPED" in losses) and distmap is not None
     dev = logits.device
-    dice_kind = [n for n in losses if n in _DICE_KINDS]
-    if not dice_kind:
-        if not cfg.get("allow_no_dice"):
-            raise AssertionError("a dice term (GDICE, DICE or GWDICE) is mandatory")  # segmodel.py:143
-        dice_kind = ["NONE"]   # the stand-alone loss callables of loss/callables.py
-    dice_kind = dice_kind[-1]   # segmodel.py:113-127: a later entry replaces self.dice_loss
+    dice_kind = dice_kind_of(losses, cfg.get("allow_no_dice"))
     wass_m = gwdice_matrix(K, dev) if dice_kind == "GWDICE" else None
     acc, _, err = loss_sums(logits, labels, distmap if use_bd else None, gamma, wass_m=wass_m)
-    # one fp32 workspace: parts[8] | coef[B*K*2] | wfocal[2] (+2 pad) | wbound[K -> 4] | wass_a[B] | wass_c[B]
-    o_coef, o_wf, o_wb, o_wa = 8, 8 + 2 * B * K, 8 + 2 * B * K + 4, 8 + 2 * B * K + 8
-    ws = torch.empty(o_wa + 2 * B, dtype=torch.float32, device=dev)
-    parts, coef, wf, wbound = ws[:8], ws[o_coef:o_wf], ws[o_wf:o_wf + 2], ws[o_wb:o_wb + K]
-    wass_a, wass_c = (ws[o_wa:o_wa + B], ws[o_wa + B:o_wa + 2 * B]) if wass_m is not None else (None, None)
-    c = _lib.LossCfg(_KIND_CODE[dice_kind], 1 if use_bd else 0, 1 if "FOCAL" in losses else 0,
-                     alpha if "BOUNDARY-RAMPED" in losses else 1.0, gamma)
-    _lib.check(_lib.load().dt_seg_loss_algebra(_p(acc), C.byref(c), B, K, H, W, _p(parts), _p(coef), _p(wf), _p(wbound),
-                                               _p(wass_a), _p(wass_c), _stream()), "dt_seg_loss_algebra")
+    parts, coef, wf, wbound, wass_a, wass_c = loss_algebra(acc, losses, B, K, H, W, use_bd, alpha, gamma,
+                                                           dice_kind=dice_kind, want_wass=wass_m is not None)
     saved = (logits, labels, distmap if use_bd else None, coef, wf, wbound if use_bd else None, wass_m, wass_c, wass_a)
     return parts, err, saved
 

@@ -154,8 +154,9 @@ class Bf16Schedule:
 
     # ------------------------------------------------------------------ bf16 inference leg
     def forward_bf16_eval(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor,
-                          want_argmax: Optional[str] = None):
-        """eval-mode forward with bf16 activations/weights and fp32 accumulation (stem and head stay fp32)."""
+                          want_argmax: Optional[str] = None, decoder_only: bool = False):
+        """eval-mode forward with bf16 activations/weights and fp32 accumulation (stem and head stay fp32).
+        decoder_only: stop in front of the head and return the bf16 decoder output [B,H,W,16] it would read."""
         sp = self.spec
         if x_nchw.dim() != 4 or x_nchw.shape[1] != sp.in_channels:
             raise RuntimeError(f"expected input [B,{sp.in_channels},H,W], got {tuple(x_nchw.shape)}")
@@ -207,6 +208,8 @@ class Bf16Schedule:
             else:
                 d, d_ss = y2, ss2
             dh, dw = h2, w2
+        if decoder_only:
+            return d
         hd = sp.head
         K = hd.cout
         logits = torch.empty((B, K, dh, dw), dtype=torch.float32, device=dev)
@@ -214,6 +217,16 @@ class Bf16Schedule:
         am8 = torch.empty((B, dh, dw), dtype=torch.uint8, device=dev) if want_argmax == "uint8" else None
         self._call("dt_head_fwd_bf16", d, hd.w(params), hd.bias(params), logits, am64, am8, B, dh, dw, hd.cin, K)
         return logits, (am64 if am64 is not None else am8)
+
+    def forward_bf16_eval_head(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor, labels, lu=None,
+                               dist=None, gamma: float = 2.0, counts=None, err=None, want_argmax: bool = False):
+        """``forward_bf16_eval`` ending in the fused evaluation head (dt_head_eval_bf16) instead of dt_head_fwd_bf16
+        -> what ``ops.head_eval`` returns"""
+        from ..ops import head_eval
+        d = self.forward_bf16_eval(x_nchw, params, bnstate, decoder_only=True)
+        hd = self.spec.head
+        return head_eval(d, hd.w(params).view(hd.cout, hd.k, hd.k, hd.cin), hd.bias(params), labels, lu, dist, gamma,
+                         counts, err, want_argmax)
 
     # ------------------------------------------------------------------ bf16 training (BASELINE configs[2])
     def forward_bf16_train(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor,

@@ -126,7 +126,7 @@ class Fp32Schedule:
     # ------------------------------------------------------------------ forward
     def forward(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor, training: bool,
                 save: bool, want_argmax: Optional[str] = None, nhwc: bool = False, enc_training: Optional[bool] = None,
-                enc_frozen: bool = False, recal: Optional[torch.Tensor] = None):
+                enc_frozen: bool = False, recal: Optional[torch.Tensor] = None, decoder_only: bool = False):
         """nhwc=True: the input already is the kernels' layout [B,H,W,C] (the tiled-inference gather produces it):
         no NCHW -> NHWC pass.  enc_training: BatchNorm mode of the encoder (stem + layers 1-4; default: `training`) —
         False with training=True is fine-tuning on the encoder's running statistics.  enc_frozen: the encoder's weights
@@ -135,9 +135,13 @@ class Fp32Schedule:
         recal: device float[1] momentum -> BatchNorm recalibration pass (`update_bn` of stochastic weight averaging): every
         BatchNorm layer, encoder included, normalises with batch statistics and folds them into its running statistics
         with THAT momentum (dt_bn_finalize_dev); nothing is saved.  With the Unet decoder the pass ends once the last
-        BatchNorm's statistics are final — no normalise pass of the last convolution, no head — and returns (None, None)."""
+        BatchNorm's statistics are final — no normalise pass of the last convolution, no head — and returns (None, None).
+        decoder_only (inference only): stop in front of the head and return the decoder output [B,H,W,16] it would read
+        (``forward_eval_head`` hands it to the fused evaluation head)."""
         sp = self.spec
         self._recal = None
+        if decoder_only and (training or save or recal is not None or enc_training):
+            raise RuntimeError("decoder_only forward: inference only (eval-mode BatchNorm, nothing saved)")
         if recal is not None:
             if not training or save or enc_frozen:
                 raise RuntimeError("recalibration forward: training statistics, nothing saved, no frozen-encoder form")
@@ -314,6 +318,8 @@ class Fp32Schedule:
             keep(f"D{i}", x=d, x_virtual=d_ss is not None, skip=skip, y1=y1, z1=z1, y2=y2, z2=z2, H=h1, W=w1)
             d, dh, dw, d_ss = nxt, h2, w2, nxt_ss
 
+        if decoder_only:
+            return d
         # ---- head
         hd = sp.head
         K = hd.cout
@@ -337,6 +343,16 @@ class Fp32Schedule:
             sv.d["enc_frozen"] = bool(enc_frozen)
             self.saved = sv
         return logits, (am64 if am64 is not None else am8)
+
+    def forward_eval_head(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor, labels, lu=None,
+                          dist=None, gamma: float = 2.0, counts=None, err=None, want_argmax: bool = False):
+        """eval-mode forward (the inference kernels of ``forward(training=False)``) that ends in the fused evaluation head
+        instead of dt_head_fwd: no logits tensor, no int64 arg-max map -> what ``ops.head_eval`` returns"""
+        from ..ops import head_eval
+        d = self.forward(x_nchw, params, bnstate, False, save=False, decoder_only=True)
+        hd = self.spec.head
+        return head_eval(d, hd.w(params).view(hd.cout, hd.k, hd.k, hd.cin), hd.bias(params), labels, lu, dist, gamma,
+                         counts, err, want_argmax)
 
     # ------------------------------------------------------------------ Unet++ decoder (smp UnetPlusPlus)
     def _forward_unetpp(self, feats, params, bn: BnView, B, training, save, keep):

@@ -316,6 +316,61 @@ def head_fwd(x, w_ohwi, bias, argmax: Optional[str] = None):
     return logits, (a64 if a64 is not None else a8)
 
 
+def head_eval(x, w_ohwi, bias, labels, lu=None, dist=None, gamma: float = 2.0, counts=None, err=None,
+              want_argmax: bool = False):
+    """fused evaluation head (dt_head_eval / dt_head_eval_bf16 by the dtype of x): head convolution, softmax, the loss
+    and F-score sums, arg-max and the confusion counts in one pass over the decoder output x [B,H,W,16].
+    -> (acc f64 [B,K,10] with slots 8, 9 zero, counts int64 [2,K,K] (+= when given), uint8 arg-max map or None,
+    err int32[1] (set, never cleared, when given)).  labels / lu int64 [B,H,W]; dist fp32 [B,K,H,W] or None."""
+    _gpu(x, w_ohwi, bias, labels, lu, dist)
+    lib = _lib.load()
+    if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"head_eval: x must be fp32 or bf16 [B,H,W,C], got {x.dtype} {tuple(x.shape)}")
+    B, H, W, Cin = x.shape
+    K = w_ohwi.shape[0]
+    dev = x.device
+
+    def i64(t, what):
+        if tuple(t.shape) != (B, H, W):
+            raise RuntimeError(f"head_eval: {what} {tuple(t.shape)} must be [{B},{H},{W}]")
+        return (t if t.dtype == torch.int64 else t.long()).contiguous()
+
+    labels = i64(labels, "labels")
+    lu = None if lu is None else i64(lu, "lu")
+    if dist is not None:
+        if tuple(dist.shape) != (B, K, H, W):
+            raise RuntimeError(f"head_eval: dist {tuple(dist.shape)} must be [{B},{K},{H},{W}]")
+        dist = dist.contiguous().float()
+    if counts is None:
+        counts = torch.zeros((2, K, K), dtype=torch.int64, device=dev)
+    elif counts.dtype != torch.int64 or tuple(counts.shape) != (2, K, K) or counts.device != dev or not counts.is_contiguous():
+        raise RuntimeError(f"head_eval: counts must be a contiguous int64 [2,{K},{K}] on {dev}")
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif err.dtype != torch.int32 or err.numel() < 1 or err.device != dev:
+        raise RuntimeError(f"head_eval: err must be int32[1] on {dev}")
+    n = lib.dt_head_eval_acc_doubles(B, K, H, W)
+    if n <= 0:
+        raise RuntimeError(f"head_eval: bad sizes B={B} K={K} H={H} W={W}")
+    acc = torch.empty(n, dtype=torch.float64, device=dev)
+    am = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if want_argmax else None
+    fn, name = (lib.dt_head_eval_bf16, "dt_head_eval_bf16") if x.dtype == torch.bfloat16 else (lib.dt_head_eval, "dt_head_eval")
+    _lib.check(fn(_p(x.contiguous()), _p(w_ohwi.contiguous().float()), _p(bias.contiguous().float()), _p(labels), _p(lu),
+                  _p(dist), float(gamma), _p(acc), _p(counts), _p(am), _p(err), B, H, W, Cin, K, _st()), name)
+    return acc[:B * K * 10].view(B, K, 10), counts, am, err
+
+
+def eval_accumulate(parts, weight: float, epoch):
+    """epoch f64[9] on the device: epoch[i] += weight * parts[i] (i < 8), epoch[8] += weight (dt_eval_accumulate)"""
+    _gpu(parts, epoch)
+    if parts.dtype != torch.float32 or parts.numel() < 8 or not parts.is_contiguous():
+        raise RuntimeError("eval_accumulate: parts must be a contiguous fp32 [8]")
+    if epoch.dtype != torch.float64 or epoch.numel() < 9 or not epoch.is_contiguous():
+        raise RuntimeError("eval_accumulate: epoch must be a contiguous fp64 [9]")
+    _lib.check(_lib.load().dt_eval_accumulate(_p(parts), float(weight), _p(epoch), _st()), "dt_eval_accumulate")
+    return epoch
+
+
 def head_bwd(x, w_ohwi, dlogits):
     _gpu(x, w_ohwi, dlogits)
     lib = _lib.load()

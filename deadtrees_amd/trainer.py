@@ -10,16 +10,18 @@ statistics, mean-reduced gradients — SURVEY §8e).
 """
 from __future__ import annotations
 
+import json
 import math
+import os
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence
 
 import torch
 
 from .data.distmap import distmaps_on_device
-from .loss.seg_loss import PART_KEYS, loss_backward, loss_forward
+from .loss.seg_loss import PART_KEYS, loss_algebra, loss_backward, loss_forward
 from .network.unet import UNetHIP
-from .ops import FlatAdam, WeightAverager
+from .ops import FlatAdam, WeightAverager, confusion_matrix, eval_accumulate
 
 
 class GradReducer:
@@ -81,6 +83,8 @@ class HipTrainer:
         self._graph = None
         self.averager = None if average is None else WeightAverager(model.flat_params.data, average)
         self._recal_graph = None
+        self._val_graphs: Dict = {}      # validation batches: one captured graph per key (shapes, precision, loss set)
+        self._val_state = None           # device accumulators of a validation epoch (the captured graphs write them)
 
     @torch.no_grad()
     def broadcast_parameters(self, src: int = 0):
@@ -140,6 +144,128 @@ class HipTrainer:
         if x is not g["x"]:
             g["x"].copy_(x)
         g["graph"].replay()
+
+    # ------------------------------------------------------------------ validation epoch
+    def _val_buffers(self):
+        """the device accumulators of a validation epoch: epoch f64[9] (weighted sums of the eight ``parts`` + the sum of
+        weights), confusion counts int64 [2,K,K], label flag int32[1].  Allocated once: captured graphs write them."""
+        dev, K = self.model.flat_params.device, self.model.spec.classes
+        st = self._val_state
+        if st is None or st["epoch"].device != dev:
+            st = self._val_state = {"epoch": torch.zeros(9, dtype=torch.float64, device=dev),
+                                    "counts": torch.zeros((2, K, K), dtype=torch.int64, device=dev),
+                                    "err": torch.zeros(1, dtype=torch.int32, device=dev)}
+            self._val_graphs = {}
+        return st
+
+    def _val_batch(self, img, mask, lu, distmap, alpha):
+        """one validation batch, launches only: eval-mode forward up to the decoder output, the fused evaluation head
+        (losses with GWDICE: logits, ``loss_forward`` and ``confusion_matrix``, the unfused chain), the scalar algebra
+        and the weighted accumulation into the epoch buffers.  Reads no module mode and writes no model state."""
+        m, eng, st = self.model, self.model.engine, self._val_buffers()
+        params = m.flat_params.detach()
+        B, K = img.shape[0], m.spec.classes
+        H, W = img.shape[2], img.shape[3]
+        x = img if img.dtype == torch.float32 else img.float()
+        boundary = any(n.startswith("BOUNDARY") for n in self.losses)
+        if boundary and distmap is None:
+            distmap = distmaps_on_device(mask, K)
+        dist = distmap if boundary else None
+        if "GWDICE" in self.losses:
+            if m.precision == "bf16":
+                logits, am = eng.forward_bf16_eval(x, params, m.bn_state, want_argmax="uint8")
+            else:
+                logits, am = eng.forward(x, params, m.bn_state, False, save=False, want_argmax="uint8")
+            parts, err, _ = loss_forward(logits, mask, dist, {"losses": self.losses, "alpha": alpha})
+            _, err_cm = confusion_matrix(am, mask, lu, K=K, counts=st["counts"])
+            torch.maximum(st["err"], torch.maximum(err, err_cm), out=st["err"])
+        else:
+            head = eng.forward_bf16_eval_head if m.precision == "bf16" else eng.forward_eval_head
+            acc, _, _, _ = head(x, params, m.bn_state, mask, lu, dist, 2.0, st["counts"], st["err"])
+            parts = loss_algebra(acc, self.losses, B, K, H, W, dist is not None, alpha)[0]
+        eval_accumulate(parts, float(B), st["epoch"])
+
+    def _val_graph_batch(self, img, mask, lu, distmap, alpha):
+        """``_val_batch`` through a captured graph per key, after two eager batches of that key (written the way
+        ``_recal_graph_batch`` is; a validation set whose last batch is smaller keeps one graph per batch size)"""
+        key = (tuple(img.shape), img.dtype, tuple(mask.shape), mask.dtype,
+               None if lu is None else (tuple(lu.shape), lu.dtype),
+               None if distmap is None else (tuple(distmap.shape), distmap.dtype),
+               self.model.precision, self.losses, float(alpha) if "BOUNDARY-RAMPED" in self.losses else None)
+        self._val_buffers()              # (a moved model drops the graphs)
+        g = self._val_graphs.setdefault(key, {"warm": 0})
+        if "graph" not in g:
+            if g["warm"] < 2:    # eager warm-up: lazy initialisation (workspaces, device tables) must not be captured
+                g["warm"] += 1
+                return self._val_batch(img, mask, lu, distmap, alpha)
+            g["img"], g["mask"] = img.clone(), mask.clone()
+            g["lu"] = None if lu is None else lu.clone()
+            g["distmap"] = None if distmap is None else distmap.clone()
+            graph = torch.cuda.CUDAGraph()
+            with self.model.engine.capture_workspaces() as g["ws"]:
+                torch.cuda.synchronize()
+                with torch.cuda.graph(graph):
+                    self._val_batch(g["img"], g["mask"], g["lu"], g["distmap"], alpha)
+            g["graph"] = graph
+        for name, t in (("img", img), ("mask", mask), ("lu", lu), ("distmap", distmap)):
+            if t is not None and t is not g[name]:
+                g[name].copy_(t)
+        g["graph"].replay()
+
+    @torch.no_grad()
+    def validate(self, loader, to_device=None, stage: str = "val", alpha: float = 1.0) -> dict:
+        """One validation epoch: eval-mode BatchNorm in this trainer's precision; per batch the loss terms of
+        ``self.losses`` and both F-scores as ``SemSegment.validation_step`` logs them, the confusion counts over all pixels
+        and over ``lu == 1``.  Batches are ``(img, mask[, distmap[, lu[, stats]]])`` tuples or the datamodule's dicts;
+        boundary terms get device distance maps when the loader supplies none.
+
+        Every epoch value is the mean of the per-batch values weighted by batch size (Lightning's
+        ``self.log(on_step=False, on_epoch=True)``): "{stage}/dice" is the weighted mean of per-batch F-scores, not the
+        F-score of pooled counts.  Returns Python floats under "{stage}/total_loss", "/dice_loss", "/dice",
+        "/dice_with_bg", "/focal_loss" and "/boundary_loss" (when those terms are on), "/batches", "/samples", and the
+        four matrices of ``SemSegment.confusion_matrices`` ("cm_px", "cm_norm", "cm_px_masked", "cm_norm_masked").
+
+        Everything accumulates on the device; the host reads one buffer when the epoch is over (with world > 1 after one
+        all-reduce, so every rank sees the same numbers).  graph=True replays a captured batch (one host synchronisation
+        per new key, when it is captured).  A label outside [0, K) raises the AssertionError of ``_check_labels``.
+        Left as found: the train / eval flags of the model and of ``model.encoder``, the freeze, ``bn_state``,
+        ``num_batches_tracked``, the parameters and the captured training graph."""
+        from .network.segmodel import create_combined_batch
+        m = self.model
+        K = m.spec.classes
+        st = self._val_buffers()
+        for t in st.values():
+            t.zero_()
+        run = self._val_graph_batch if self.use_graph else self._val_batch
+        batches = 0
+        for batch in loader:
+            batch = create_combined_batch(batch) if isinstance(batch, dict) else tuple(batch)
+            if len(batch) < 2:
+                raise ValueError("validate: a batch is (img, mask[, distmap[, lu[, stats]]])")
+            img, mask = batch[0], batch[1]
+            distmap = batch[2] if len(batch) > 2 else None
+            lu = batch[3] if len(batch) > 3 else None
+            if to_device:
+                img, mask = img.to(to_device), mask.to(to_device)
+                distmap = distmap.to(to_device) if distmap is not None else None
+                lu = lu.to(to_device) if lu is not None else None
+            m._require_gpu(img)
+            if mask.dtype != torch.int64:
+                mask = mask.long()
+            if lu is not None and lu.dtype != torch.int64:
+                lu = lu.long()
+            run(img, mask, lu, distmap, alpha)
+            batches += 1
+        if batches == 0:
+            raise ValueError("validate: no batches")
+        # the one transfer of the epoch: nine doubles, the counts (exact in fp64 below 2^53) and the label flag
+        buf = torch.cat([st["epoch"], st["counts"].reshape(-1).double(), st["err"].double()])
+        if self.reducer and self.world > 1:
+            self.reducer.dist.all_reduce(buf, op=self.reducer.dist.ReduceOp.SUM, group=self.reducer.group)
+        host = buf.cpu()
+        if float(host[-1]) != 0.0:
+            raise AssertionError(f"labels outside [0, {K}) were seen this epoch (class2one_hot)")
+        return epoch_metrics(host[:9], host[9:9 + 2 * K * K].reshape(2, K, K), self.losses, stage, batches)
 
     def step(self, img: torch.Tensor, mask: torch.Tensor, distmap: Optional[torch.Tensor] = None,
              alpha: float = 1.0):
@@ -345,16 +471,224 @@ def resolve_swa(swa, epochs: int, base_lr: float) -> Optional[SWAConfig]:
     return SWAConfig(int(cfg.swa_start), lr, int(cfg.anneal_epochs), cfg.anneal_strategy)
 
 
+_EPOCH_SLOTS = {"dice_loss": 0, "boundary_loss": 1, "focal_loss": 2, "dice": 4, "dice_with_bg": 5, "total_loss": 6}
+
+
+def validation_keys(losses: Sequence[str], stage: str = "val") -> tuple:
+    """the scalar keys ``HipTrainer.validate`` returns for a loss list (what a monitor may name)"""
+    names = ["total_loss", "dice_loss", "dice", "dice_with_bg"]
+    if "FOCAL" in losses:
+        names.append("focal_loss")
+    if any(n.startswith("BOUNDARY") for n in losses):
+        names.append("boundary_loss")
+    return tuple(f"{stage}/{n}" for n in names + ["batches", "samples"])
+
+
+def epoch_metrics(epoch, counts, losses: Sequence[str], stage: str, batches: int) -> dict:
+    """host side of a validation epoch.  epoch: nine doubles — sum_b w_b * parts_b[i] for the eight ``parts`` of the
+    loss algebra and sum_b w_b (w_b = batch size); the epoch value of a key is their quotient, Lightning's mean of
+    ``self.log(on_step=False, on_epoch=True)`` values weighted by batch size.  counts [2,K,K] -> the four matrices of
+    ``SemSegment.confusion_matrices``."""
+    epoch = [float(v) for v in epoch]
+    wsum = epoch[8]
+    if not wsum > 0.0:
+        raise ValueError("epoch_metrics: the weights sum to zero")
+    out = {}
+    for key in validation_keys(losses, stage):
+        name = key[len(stage) + 1:]
+        if name in _EPOCH_SLOTS:
+            out[key] = epoch[_EPOCH_SLOTS[name]] / wsum
+    out[f"{stage}/batches"] = float(batches)
+    out[f"{stage}/samples"] = wsum
+    cm = torch.as_tensor(counts).double()
+    for name, mat in (("", cm[0]), ("_masked", cm[1])):
+        out[f"cm_px{name}"] = mat.to(torch.int64)
+        out[f"cm_norm{name}"] = mat / mat.sum(dim=1, keepdim=True).clamp_min(1.0)
+    return out
+
+
+@dataclass
+class CheckpointConfig:
+    """``ModelCheckpoint`` of the reference's configs/callbacks/default.yaml: keep the ``save_top_k`` best files by
+    ``monitor`` under ``dirpath`` (``filename`` is formatted with ``epoch``; ".ckpt" is appended) and ``last.ckpt``"""
+    dirpath: str
+    monitor: str = "val/dice"
+    mode: str = "max"
+    save_top_k: int = 1
+    save_last: bool = True
+    filename: str = "epoch_{epoch:03d}"
+
+
+@dataclass
+class EarlyStoppingConfig:
+    """``EarlyStopping`` of the reference's configs/callbacks/default.yaml"""
+    monitor: str = "val/dice"
+    mode: str = "max"
+    patience: int = 200
+    min_delta: float = 0.0
+
+
+def _check_monitor(what: str, monitor, mode, losses, stage: str = "val"):
+    if mode not in ("min", "max"):
+        raise ValueError(f"{what}: mode {mode!r}: use 'min' or 'max'")
+    keys = [k for k in validation_keys(losses, stage) if not k.endswith(("/batches", "/samples"))]
+    if monitor not in keys:
+        raise ValueError(f"{what}: monitor {monitor!r} is not a validation metric of losses {tuple(losses)}: {keys}")
+
+
+def resolve_checkpoint(cfg, losses: Sequence[str]) -> Optional[CheckpointConfig]:
+    """``fit``'s checkpoint argument -> a checked CheckpointConfig (None stays None)"""
+    if cfg is None:
+        return None
+    if not isinstance(cfg, CheckpointConfig):
+        raise ValueError(f"fit(checkpoint=...): None or a CheckpointConfig, not {type(cfg).__name__}")
+    _check_monitor("checkpoint", cfg.monitor, cfg.mode, losses)
+    if isinstance(cfg.save_top_k, bool) or int(cfg.save_top_k) != cfg.save_top_k or cfg.save_top_k < 0:
+        raise ValueError(f"save_top_k {cfg.save_top_k!r}: an integer >= 0")
+    if not cfg.dirpath:
+        raise ValueError("checkpoint: dirpath is required")
+    try:
+        name = cfg.filename.format(epoch=0)
+    except (KeyError, IndexError, ValueError) as e:
+        raise ValueError(f"checkpoint: filename {cfg.filename!r} must format with epoch alone") from e
+    if not name or os.sep in name or name == "last":
+        raise ValueError(f"checkpoint: filename {cfg.filename!r}: a plain file name other than 'last'")
+    return CheckpointConfig(str(cfg.dirpath), cfg.monitor, cfg.mode, int(cfg.save_top_k), bool(cfg.save_last), cfg.filename)
+
+
+def resolve_early_stopping(cfg, losses: Sequence[str]) -> Optional[EarlyStoppingConfig]:
+    """``fit``'s early_stopping argument -> a checked EarlyStoppingConfig (None stays None)"""
+    if cfg is None:
+        return None
+    if not isinstance(cfg, EarlyStoppingConfig):
+        raise ValueError(f"fit(early_stopping=...): None or an EarlyStoppingConfig, not {type(cfg).__name__}")
+    _check_monitor("early_stopping", cfg.monitor, cfg.mode, losses)
+    if isinstance(cfg.patience, bool) or int(cfg.patience) != cfg.patience or cfg.patience < 0:
+        raise ValueError(f"patience {cfg.patience!r}: an integer >= 0")
+    if not float(cfg.min_delta) >= 0.0:
+        raise ValueError(f"min_delta {cfg.min_delta!r} must not be negative")
+    return EarlyStoppingConfig(cfg.monitor, cfg.mode, int(cfg.patience), float(cfg.min_delta))
+
+
+class ModelSelection:
+    """Best-checkpoint bookkeeping and early stopping over the validated epochs of ``fit`` — the rules of Lightning's
+    ``ModelCheckpoint`` / ``EarlyStopping``, restated from their documentation (unpinned: Lightning is not installed):
+
+    top-k: a score enters only if fewer than k are kept or it is STRICTLY better than the worst kept one (a tie keeps
+    the earlier file); the dropped file is deleted; a non-finite score is never kept.  ``last.ckpt`` is rewritten after
+    every validated epoch.  Early stopping: an improvement is ``score - min_delta > best`` (mode max; mirrored for min);
+    otherwise a counter goes up and training stops after the epoch in which it reaches ``patience``; a non-finite
+    monitored value stops at once.
+
+    save(path) writes one checkpoint file; write=False (ranks other than 0) takes the same decisions without files."""
+
+    def __init__(self, checkpoint: Optional[CheckpointConfig], early_stopping: Optional[EarlyStoppingConfig],
+                 save: Callable[[str], None], write: bool = True):
+        self.ck, self.es, self.save, self.write = checkpoint, early_stopping, save, write
+        self.kept: List = []             # [(score, path)] of the top-k files
+        self.best_model_path: Optional[str] = None
+        self.best_model_score: Optional[float] = None
+        self.last_model_path: Optional[str] = None
+        self.es_best = None if early_stopping is None else (-math.inf if early_stopping.mode == "max" else math.inf)
+        self.wait = 0
+        self.stopped_epoch: Optional[int] = None
+        if checkpoint is not None and write:
+            os.makedirs(checkpoint.dirpath, exist_ok=True)
+
+    @staticmethod
+    def _better(a: float, b: float, mode: str) -> bool:
+        return a > b if mode == "max" else a < b
+
+    def _monitored(self, cfg, metrics: dict) -> float:
+        if cfg.monitor not in metrics:
+            raise KeyError(f"monitor {cfg.monitor!r} is not among the validation metrics {sorted(metrics)}")
+        return float(metrics[cfg.monitor])
+
+    def update(self, epoch: int, metrics: dict) -> bool:
+        """after a validated epoch: write / delete files, count patience -> True when training should stop"""
+        ck, es = self.ck, self.es
+        if ck is not None:
+            score = self._monitored(ck, metrics)
+            if ck.save_top_k > 0 and math.isfinite(score):
+                worst = None
+                for e in self.kept:      # the worst kept score; among equals the latest file goes first
+                    if worst is None or not self._better(e[0], worst[0], ck.mode):
+                        worst = e
+                if len(self.kept) < ck.save_top_k or self._better(score, worst[0], ck.mode):
+                    path = os.path.join(ck.dirpath, ck.filename.format(epoch=epoch) + ".ckpt")
+                    if self.write:
+                        self.save(path)
+                    self.kept.append((score, path))
+                    if len(self.kept) > ck.save_top_k:
+                        self.kept.remove(worst)
+                        if self.write and os.path.exists(worst[1]):
+                            os.remove(worst[1])
+                    best = self.kept[0]
+                    for e in self.kept[1:]:
+                        if self._better(e[0], best[0], ck.mode):
+                            best = e
+                    self.best_model_score, self.best_model_path = best
+            if ck.save_last:
+                self.last_model_path = os.path.join(ck.dirpath, "last.ckpt")
+                if self.write:
+                    self.save(self.last_model_path)
+        if es is None:
+            return False
+        score = self._monitored(es, metrics)
+        if not math.isfinite(score):
+            self.stopped_epoch = epoch
+            return True
+        improved = score - es.min_delta > self.es_best if es.mode == "max" else score + es.min_delta < self.es_best
+        if improved:
+            self.es_best, self.wait = score, 0
+        else:
+            self.wait += 1
+            if self.wait >= es.patience:
+                self.stopped_epoch = epoch
+                return True
+        return False
+
+
+def checkpoint_writer(trainer: "HipTrainer", pl_module=None, training_conf: Optional[dict] = None) -> Callable[[str], None]:
+    """path -> one ``.ckpt`` in ``SemSegment.save_checkpoint``'s payload (``SemSegment.load_from_checkpoint`` and
+    ``PyTorchInference(path)`` read it).  With a ``pl_module`` that has ``save_checkpoint``: that method.  Otherwise
+    the same payload from the model's own configuration: architecture, channels and class count of its spec, the
+    trainer's loss list, ``encoder_weights`` None (the file holds the encoder's tensors; nothing is to be fetched again)."""
+    if pl_module is not None and hasattr(pl_module, "save_checkpoint"):
+        return pl_module.save_checkpoint
+    from .utils.config import default_network, default_training
+    model = trainer.model
+    K = model.spec.classes
+    classes = ["background", "deadtree"] if K == 2 else ["background"] + [f"class{i}" for i in range(1, K)]
+    net = dict(default_network(architecture=model.spec.decoder_kind, in_channels=model.spec.in_channels, classes=classes,
+                               losses=list(trainer.losses)))
+    hp = {"network": net, "training": dict(default_training(**(training_conf or {})))}
+
+    def save(path):
+        sd = {f"model.{k}": v for k, v in model.smp_state_dict().items()}
+        torch.save({"state_dict": sd, "hyper_parameters_json": json.dumps(hp)}, str(path))
+    return save
+
+
 def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: int = 10, to_device=None,
-        on_epoch_end=None, callbacks=None, pl_module=None, swa=None):
+        on_epoch_end=None, callbacks=None, pl_module=None, swa=None, val_loader=None, check_val_every_n_epoch: int = 1,
+        checkpoint=None, early_stopping=None):
     """Minimal stand-in for ``Trainer.fit`` on the hot path (reference deadtrees/train.py:113): per-batch
     ``HipTrainer.step`` and the per-epoch ``CosineAnnealingLR(T_max)`` of segmodel.py:426-428.
 
     callbacks: objects with ``on_train_epoch_start(trainer, pl_module)`` (e.g. ``MultiStage``), called at the start of
     every epoch with views of this trainer and of ``pl_module`` (a ``SemSegment``; default: a view of the trainer's model
     with ``encoder_weights`` taken from the model and ``hparams.training`` = learning_rate / cosineannealing_tmax).
-    There is no validation loop here, so an encoder put in eval mode stays there (Lightning puts the whole module back
-    in train mode after every validation run).
+
+    val_loader: after every ``check_val_every_n_epoch``-th epoch ``trainer.validate(val_loader)`` runs (with that epoch's
+    boundary ramp ``alpha``) and its scalar metrics go into the epoch's history record.  Validation leaves every module
+    mode as it found it, so an encoder put in eval mode stays there (Lightning >= 1.5 puts the whole module back in
+    train mode after a validation run).  checkpoint: a ``CheckpointConfig`` — the best ``save_top_k`` files by its monitor
+    and ``last.ckpt``, in ``SemSegment.save_checkpoint``'s format (``pl_module.save_checkpoint`` when it has one), written
+    by rank 0; the history then ends with a {"checkpoint/best_model_path", "checkpoint/best_model_score"} record.
+    early_stopping: an ``EarlyStoppingConfig`` — the loop ends after the epoch in which patience runs out (or the
+    monitored value is not finite).  The rules are those of ``ModelSelection``.  Validation sees the current weights,
+    not the SWA average (as under Lightning's SWA callback); the SWA swap and recalibration run after the loop.
 
     swa: None | True | SWAConfig — the loop of torch's SWA documentation on a ``HipTrainer(average="swa")``: epochs before
     ``swa_start`` keep the cosine schedule (or whatever a callback put in its place); from ``swa_start`` the rate follows
@@ -366,6 +700,19 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
     swa = resolve_swa(swa, epochs, base_lr)
     if swa is not None and (getattr(trainer, "averager", None) is None or trainer.averager.mode != "swa"):
         raise ValueError("fit(swa=...) needs HipTrainer(average='swa')")
+    if checkpoint is not None or early_stopping is not None:      # (a plain loop asks nothing new of `trainer`)
+        checkpoint = resolve_checkpoint(checkpoint, trainer.losses)
+        early_stopping = resolve_early_stopping(early_stopping, trainer.losses)
+    if int(check_val_every_n_epoch) != check_val_every_n_epoch or check_val_every_n_epoch < 1:
+        raise ValueError(f"check_val_every_n_epoch {check_val_every_n_epoch!r}: an integer >= 1")
+    if val_loader is None and (checkpoint is not None or early_stopping is not None):
+        raise ValueError("fit(checkpoint=... / early_stopping=...) monitor a validation metric: give val_loader")
+    select = None
+    if checkpoint is not None or early_stopping is not None:
+        rank0 = trainer.world == 1 or trainer.reducer.dist.get_rank(trainer.reducer.group) == 0
+        select = ModelSelection(checkpoint, early_stopping,
+                                checkpoint_writer(trainer, pl_module, {"learning_rate": base_lr, "cosineannealing_tmax": t_max}),
+                                write=rank0)
     swa_from = None       # the rate the schedule had reached when SWA took over
     history = []
     sched = {"base_lr": float(base_lr), "t_max": int(t_max), "start": 0}
@@ -386,12 +733,12 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
             lr = swa_lr(epoch - swa.swa_start, swa_from, swa.swa_lr, swa.anneal_epochs, swa.anneal_strategy)
         trainer.opt.lr = lr
         losses = []
+        alpha = min((epoch + 1) * 0.01, 0.99)
         for batch in loader:
             img, mask, distmap, _, _ = create_combined_batch(batch) if isinstance(batch, dict) else batch
             if to_device:
                 img, mask = img.to(to_device), mask.to(to_device)
                 distmap = distmap.to(to_device) if distmap is not None else None
-            alpha = min((epoch + 1) * 0.01, 0.99)
             losses.append(trainer.step(img, mask, distmap, alpha=alpha))
         mean = float(torch.stack(losses).mean()) if losses else float("nan")
         history.append({"epoch": epoch, "lr": trainer.opt.lr, "train/total_loss": mean})
@@ -399,9 +746,20 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
             if epoch >= swa.swa_start:
                 trainer.update_average()
             history[-1]["swa/n_averaged"] = trainer.averager.n_averaged
+        stop = False
+        if val_loader is not None and (epoch + 1) % check_val_every_n_epoch == 0:
+            val = trainer.validate(val_loader, to_device=to_device, alpha=alpha)
+            history[-1].update({k: v for k, v in val.items() if not k.startswith("cm_")})
+            if select is not None:
+                stop = select.update(epoch, val)
         if on_epoch_end:
             on_epoch_end(history[-1])
+        if stop:
+            break
     if swa is not None:
         trainer.swap_in_average()
         history.append({"swa/bn_batches": trainer.update_bn(loader, to_device=to_device)})
+    if checkpoint is not None:
+        history.append({"checkpoint/best_model_path": select.best_model_path,
+                        "checkpoint/best_model_score": select.best_model_score})
     return history

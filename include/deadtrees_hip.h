@@ -383,6 +383,26 @@ int dt_gwdice_posgrad(const int64_t* labels, const float* sample_coef, float* po
 int dt_confusion_matrix(const int64_t* pred_i64, const uint8_t* pred_u8, const int64_t* target, const int64_t* lu,
                         int K, int64_t n, int64_t* counts, int32_t* err_flag, void* stream);
 
+/* Fused evaluation head (validation / test epochs): ONE pass over the decoder output x[B,H,W,Cin = 16] does what
+ * dt_head_fwd -> dt_seg_loss_fwd -> dt_confusion_matrix do in three, and the logits never reach memory:
+ *   acc    fp64 [B][K][DT_LOSS_NACC] (overwritten): slots 0-7 as above; 8, 9 (GWDICE: they need a pass over every
+ *          sample's logits first) are written as zero.  Room for dt_head_eval_acc_doubles(B,K,H,W) doubles: one
+ *          partial row per workgroup behind the result, fixed-order second stage, no float atomics.
+ *   counts int64 [2][K][K] (+=) as dt_confusion_matrix (lu may be NULL), arg-max ties -> lowest class.
+ *   argmax_u8 [B,H,W] optional.  A label outside [0,K) sets err_flag[0] = 1 and enters no confusion count.
+ * The logits come from the same device function as dt_head_fwd's: arg-max map, counts and the slots 0, 6, 7 equal
+ * the three-kernel chain exactly, the real-valued slots to fp32 summation order.  2 <= K <= 4, dist [B,K,H,W] or NULL. */
+int64_t dt_head_eval_acc_doubles(int B, int K, int H, int W);
+int dt_head_eval(const float* x, const float* w_ohwi, const float* bias, const int64_t* labels, const int64_t* lu,
+                 const float* dist, float gamma, double* acc, int64_t* counts, uint8_t* argmax_u8, int32_t* err_flag,
+                 int B, int H, int W, int Cin, int K, void* stream);
+int dt_head_eval_bf16(const void* x_bf16, const float* w_ohwi, const float* bias, const int64_t* labels,
+                      const int64_t* lu, const float* dist, float gamma, double* acc, int64_t* counts,
+                      uint8_t* argmax_u8, int32_t* err_flag, int B, int H, int W, int Cin, int K, void* stream);
+/* Epoch mean of the per-batch scalars on the device: epoch[i] += weight * parts[i] for i < 8 (parts of
+ * dt_seg_loss_algebra), epoch[8] += weight; fp64, one launch, no host synchronisation. */
+int dt_eval_accumulate(const float* parts, double weight, double* epoch, void* stream);
+
 /* Ensemble vote (deployment/inference.py:65-116 PyTorchEnsembleInference.run): per-pixel torch.mode over the
  * uint8 class maps of M models, maps[M][n]; ties -> the smallest class (torch.mode).  n % 4 == 0, 2 <= K <= 8.
  * Writes uint8 and/or int64 maps (either pointer may be NULL); classes >= K set err_flag[0]. */

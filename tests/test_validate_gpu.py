@@ -1,0 +1,209 @@
+"""``HipTrainer.validate`` and ``fit(val_loader=..., checkpoint=..., early_stopping=...)`` on the device.
+
+UNetHIP at 3 x 64 x 64, K = 2, three validation batches of sizes 2, 2, 1 (unequal weights).  The yardstick is the
+per-batch unfused chain ``predict_logits -> seg_loss -> confusion_matrix`` averaged on the host in fp64 with the batch
+sizes as weights: F-scores and all four matrices must be EQUAL (one logit function, exact integer sums), the loss terms
+agree to rel 1e-5 / abs 1e-6 (fp32 summation order differs between the fused and the unfused pass)."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+K = 2
+SIZES = (2, 2, 1)
+SCALARS = ("total_loss", "dice_loss", "focal_loss", "boundary_loss")
+ALPHA = 0.37
+
+
+def _model(seed=0):
+    from deadtrees_amd.network.unet import UNetHIP
+    m = UNetHIP(in_channels=3, classes=K)
+    m.reset_parameters(seed=seed)
+    return m.to(DEV)
+
+
+def _batches(sizes=SIZES, first_seed=10):
+    """(img, mask, None, lu) tuples on the device: no distance maps (boundary terms build them on the device)"""
+    from deadtrees_amd.data.synthetic import synth_batch
+    out = []
+    for i, b in enumerate(sizes):
+        img, mask = synth_batch(b, 64, 64, 3, K, seed=first_seed + i, p_fg=0.3)
+        lu = torch.randint(0, 3, mask.shape, generator=torch.Generator().manual_seed(first_seed + i))
+        out.append((img.to(DEV), mask.to(DEV), None, lu.to(DEV)))
+    return out
+
+
+def _trainer(precision="fp32", losses=("GDICE", "FOCAL"), graph=False, warm=2, seed=0):
+    """a trainer whose model has taken `warm` training steps (running statistics off their initial 0 / 1)"""
+    from deadtrees_amd.trainer import HipTrainer
+    tr = HipTrainer(_model(seed), precision=precision, losses=losses, graph=graph)
+    for img, mask, _, _ in _batches((2,) * warm, first_seed=50):
+        tr.step(img, mask)
+    return tr
+
+
+def _unfused_epoch(model, batches, precision, losses, alpha):
+    """the comparator: per batch predict_logits -> seg_loss -> confusion_matrix; host fp64 mean weighted by batch size"""
+    from deadtrees_amd import ops
+    from deadtrees_amd.data.distmap import distmaps_on_device
+    from deadtrees_amd.loss.seg_loss import seg_loss
+    sums, wsum, counts = {}, 0.0, None
+    for img, mask, _, lu in batches:
+        logits = model.predict_logits(img, precision=precision)
+        dist = distmaps_on_device(mask, K) if any(n.startswith("BOUNDARY") for n in losses) else None
+        total, parts, err = seg_loss(logits, mask, dist, losses, alpha=alpha)
+        assert int(err) == 0
+        counts, _ = ops.confusion_matrix(logits.argmax(1), mask, lu, K=K, counts=counts)
+        w = float(img.shape[0])
+        for k, v in parts.items():
+            sums[k] = sums.get(k, 0.0) + w * float(v)
+        wsum += w
+    out = {k: v / wsum for k, v in sums.items()}
+    cm = counts.cpu().double()
+    for name, m in (("", cm[0]), ("_masked", cm[1])):
+        out[f"cm_px{name}"] = m.to(torch.int64)
+        out[f"cm_norm{name}"] = m / m.sum(dim=1, keepdim=True).clamp_min(1.0)
+    return out
+
+
+def _compare(val, ref, losses):
+    assert val["val/dice"] == ref["dice"] and val["val/dice_with_bg"] == ref["dice_with_bg"]
+    for name in ("cm_px", "cm_norm", "cm_px_masked", "cm_norm_masked"):
+        assert torch.equal(val[name], ref[name]), name
+    assert int(val["cm_px"].sum()) == sum(SIZES) * 64 * 64
+    expected = {"total_loss", "dice_loss"} | ({"focal_loss"} if "FOCAL" in losses else set()) | \
+               ({"boundary_loss"} if any(n.startswith("BOUNDARY") for n in losses) else set())
+    assert {k[4:] for k in val if k.startswith("val/")} == expected | {"dice", "dice_with_bg", "batches", "samples"}
+    for name in expected:
+        assert val[f"val/{name}"] == pytest.approx(ref[name], rel=1e-5, abs=1e-6), name
+    assert val["val/batches"] == 3.0 and val["val/samples"] == 5.0
+    assert all(isinstance(v, float) for k, v in val.items() if k.startswith("val/"))
+
+
+@pytest.mark.parametrize("losses", [("GDICE", "FOCAL"), ("GDICE", "FOCAL", "BOUNDARY"), ("GWDICE", "FOCAL")],
+                         ids=["gdice_focal", "boundary", "gwdice_fallback"])
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_validate_against_the_unfused_chain(precision, losses):
+    tr = _trainer(precision, losses)
+    batches = _batches()
+    ref = _unfused_epoch(tr.model, batches, precision, losses, ALPHA)
+    val = tr.validate(batches, alpha=ALPHA)
+    _compare(val, ref, losses)
+    # a second epoch starts from zero: the same numbers again, bit for bit
+    again = tr.validate(batches, alpha=ALPHA)
+    assert {k: v for k, v in again.items() if k.startswith("val/")} == {k: v for k, v in val.items() if k.startswith("val/")}
+    assert torch.equal(again["cm_px"], val["cm_px"])
+
+
+def test_validate_accepts_dict_batches_stage_and_to_device():
+    tr = _trainer()
+    batches = _batches()
+    val = tr.validate(batches)
+    cpu = [{"main": (img.cpu(), mask.cpu(), None, lu.cpu(), [{"file": "a"}] * img.shape[0])} for img, mask, _, lu in batches]
+    test = tr.validate(cpu, to_device=DEV, stage="test")
+    assert test["test/dice"] == val["val/dice"] and test["test/total_loss"] == val["val/total_loss"]
+    assert torch.equal(test["cm_px_masked"], val["cm_px_masked"])
+    with pytest.raises(ValueError):
+        tr.validate([])
+
+
+def test_a_label_outside_the_classes_raises_the_label_assertion():
+    tr = _trainer()
+    batches = _batches()
+    bad = batches[1][1].clone()
+    bad[0, 5, 7] = K
+    batches[1] = (batches[1][0], bad, None, batches[1][3])
+    with pytest.raises(AssertionError, match="labels outside"):
+        tr.validate(batches)
+    assert "val/dice" in tr.validate(_batches())          # the flag does not stick
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_validate_leaves_modes_statistics_and_parameters_as_found(precision):
+    tr = _trainer(precision)
+    m = tr.model
+    m.encoder.eval()
+    m.encoder.requires_grad_(False)
+    before = (m.bn_state.clone(), m.flat_params.detach().clone(), m.num_batches_tracked.clone())
+    tr.validate(_batches())
+    assert m.training and not m.encoder.training and m.encoder_frozen
+    assert torch.equal(m.bn_state, before[0]) and torch.equal(m.flat_params.detach(), before[1])
+    assert torch.equal(m.num_batches_tracked, before[2])
+    m.eval()
+    tr.validate(_batches())
+    assert not m.training and not m.encoder.training
+
+
+def test_validate_does_not_disturb_the_captured_training_graph():
+    train = _batches((2, 2, 2, 2), first_seed=70)
+    out = []
+    for with_val in (False, True):
+        tr = _trainer(graph=True, warm=0, seed=3)
+        for img, mask, _, _ in train[:3]:
+            tr.step(img, mask)
+        assert "graph" in tr._graph
+        graph = tr._graph["graph"]
+        if with_val:
+            for _ in range(3):                        # eager warm-up, capture and replay of the validation batches
+                tr.validate(_batches())
+            assert any("graph" in g for g in tr._val_graphs.values())
+        loss = float(tr.step(train[3][0], train[3][1]))
+        assert tr._graph["graph"] is graph
+        out.append((loss, tr.model.flat_params.detach().clone(), tr.model.bn_state.clone(), tr.opt.m.clone()))
+    assert out[0][0] == out[1][0]
+    for a, b in zip(out[0][1:], out[1][1:]):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("precision,losses", [("fp32", ("GDICE", "FOCAL", "BOUNDARY-RAMPED")), ("bf16", ("GDICE", "FOCAL")),
+                                              ("fp32", ("GWDICE", "FOCAL"))])
+def test_graph_replayed_validation_equals_eager(precision, losses):
+    batches = _batches()
+    eager = _trainer(precision, losses).validate(batches, alpha=ALPHA)
+    tr = _trainer(precision, losses, graph=True)
+    for i in range(3):
+        val = tr.validate(batches, alpha=ALPHA)
+        assert {k: v for k, v in val.items() if k.startswith("val/")} == \
+               {k: v for k, v in eager.items() if k.startswith("val/")}, i
+        assert torch.equal(val["cm_px"], eager["cm_px"]) and torch.equal(val["cm_px_masked"], eager["cm_px_masked"])
+    # batch sizes 2 and 1: two keys; the size-2 graph exists after its two eager batches, the size-1 one after two epochs
+    assert len(tr._val_graphs) == 2 and all("graph" in g for g in tr._val_graphs.values())
+    if "BOUNDARY-RAMPED" in losses:                   # alpha is read by the captured blend: it belongs to the key
+        other = tr.validate(batches, alpha=0.9)
+        assert len(tr._val_graphs) == 4 and other["val/total_loss"] != val["val/total_loss"]
+        assert other["val/dice"] == val["val/dice"]
+
+
+def test_fit_with_validation_checkpoint_and_early_stopping(tmp_path):
+    from deadtrees_amd.network.segmodel import SemSegment
+    from deadtrees_amd.trainer import CheckpointConfig, EarlyStoppingConfig, HipTrainer, fit
+    tr = _trainer(warm=0)
+    train = [(img, mask, None, lu, None) for img, mask, _, lu in _batches((2, 2), first_seed=90)]
+    val_batches = _batches()
+    seen = []
+    hist = fit(tr, train, 2, val_loader=val_batches, checkpoint=CheckpointConfig(str(tmp_path)),
+               early_stopping=EarlyStoppingConfig(patience=5), on_epoch_end=lambda rec: seen.append(dict(rec)))
+    assert len(hist) == 3 and [h["epoch"] for h in hist[:2]] == [0, 1]
+    for rec in hist[:2]:
+        assert {"val/total_loss", "val/dice_loss", "val/focal_loss", "val/dice", "val/dice_with_bg", "val/batches",
+                "val/samples", "train/total_loss", "lr"} <= set(rec)
+        assert not any(k.startswith("cm_") for k in rec)
+    assert seen == hist[:2]                                   # the callback sees the validation metrics of its epoch
+    best_path, best_score = hist[2]["checkpoint/best_model_path"], hist[2]["checkpoint/best_model_score"]
+    scores = [h["val/dice"] for h in hist[:2]]
+    assert best_score == max(scores)
+    best_epoch = scores.index(best_score)                     # a tie keeps the earlier file
+    assert best_path == str(tmp_path / f"epoch_{best_epoch:03d}.ckpt")
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted([f"epoch_{best_epoch:03d}.ckpt", "last.ckpt"])
+    # the best file loads through the reference-shaped module, and scores what was recorded
+    mod = SemSegment.load_from_checkpoint(best_path)
+    assert list(mod.hparams["network"]["losses"]) == ["GDICE", "FOCAL"] and len(mod.classes) == K
+    again = HipTrainer(mod.model.to(DEV)).validate(val_batches)
+    assert again["val/dice"] == best_score
+    assert again["val/total_loss"] == hist[best_epoch]["val/total_loss"]
+    # last.ckpt holds the weights the loop ended with
+    last = SemSegment.load_from_checkpoint(str(tmp_path / "last.ckpt"))
+    assert torch.equal(last.model.flat_params.detach(), tr.model.flat_params.detach().cpu())
+    # without a validation loader nothing changes
+    plain = fit(_trainer(warm=0), train, 1)
+    assert len(plain) == 1 and not any(k.startswith(("val/", "checkpoint/")) for k in plain[0])
