@@ -1,11 +1,11 @@
-"""``DeadtreesDataModule`` surface (reference deadtrees/data/deadtreedata.py:192-405) with a synthetic source.
+"""``DeadtreesDataModule`` surface (reference deadtrees/data/deadtreedata.py:192-405) with two sources.
 
-The reference streams webdataset shards through albumentations on CPU workers; neither package nor any shard
-is available here, and at >400 tiles/s/GPU the real loader is the limiter anyway (§8 f2).  This
-module keeps the constructor / ``setup`` / ``*_dataloader`` surface and the batch formats
-(``{"main": (img, mask, distmap, lu, stats)}`` for train/val :348-395, a bare tuple for test :397-405) and
-fills them with synthetic tiles of the reference's shape; ``val_transform`` is the reference normalisation
-(:148-154) in numpy.
+The reference streams webdataset shards through albumentations on CPU workers; neither package is available here
+(SURVEY §8c), and at >400 tiles/s/GPU that loader is the limiter anyway (§8 f2).  This module keeps the constructor /
+``setup`` / ``*_dataloader`` surface and the batch formats (``{"main": (img, mask, distmap, lu, stats)}`` for train/val
+:348-395, a bare tuple for test :397-405).  Without shards it fills them with synthetic tiles of the reference's shape;
+with ``*.tar`` shards it reads them once (``shards.py``, stdlib ``tarfile`` + PIL) into device-resident pools and one HIP
+kernel makes every batch (``pool.py``).  ``val_transform`` is the reference normalisation (:148-154) in numpy.
 """
 from __future__ import annotations
 
@@ -126,34 +126,99 @@ class _SyntheticLoader:
 
 
 class DeadtreesDataModule:
+    """Two sources behind the reference's surface.  Without shards: synthetic tiles (``_SyntheticLoader``).  With
+    ``*.tar`` shards in ``data_dir`` (one directory + ``pattern``, split by ``split_shards``; or a list of three
+    directories, the reference's train / val / test layout): ``setup`` decodes every shard once into device-resident
+    pools (``data/pool.py``) and the ``*_dataloader()`` methods return ``PoolLoader``s, whose batches one HIP gather
+    kernel makes.  ``rank`` / ``world``: under data parallelism every rank reads ``shards_for_rank`` of the train shards;
+    ``seed`` seeds the epoch plans; ``max_resident_bytes`` bounds each pool (default: half of the free device memory)."""
+
     def __init__(self, data_dir=None, pattern=None, pattern_extra=None, batch_size_extra=None,
                  train_dataloader_conf=None, val_dataloader_conf=None, test_dataloader_conf=None,
-                 synthetic_batches: int = 8, tile_size: int = 256, device: Optional[str] = None):
+                 synthetic_batches: int = 8, tile_size: int = 256, device: Optional[str] = None,
+                 rank: int = 0, world: int = 1, seed: int = 0, max_resident_bytes: Optional[int] = None):
         self.data_dir, self.pattern = data_dir, pattern
         self.train_conf = dict(train_dataloader_conf or {})
         self.val_conf = dict(val_dataloader_conf or {})
         self.test_conf = dict(test_dataloader_conf or {})
         self.synthetic_batches, self.tile_size, self.device = synthetic_batches, tile_size, device
         self.in_channels, self.classes = 3, 2
+        self.rank, self.world, self.seed, self.max_resident_bytes = rank, world, seed, max_resident_bytes
+        self.pools = None
+        self.layout, self.data_shards = _find_shards(data_dir, pattern)
+        if self.data_shards is not None and (pattern_extra or batch_size_extra):
+            raise NotImplementedError("pattern_extra / batch_size_extra (the reference's combined-dataset cycle of extra "
+                                      "shard sets) are not built: one shard set per datamodule")
 
     def setup(self, stage=None, split_fractions=None, in_channels: int = 3, classes: int = 2):
-        if data_dir_has_shards(self.data_dir):
-            raise NotImplementedError("webdataset shards need the `webdataset`/`albumentations` packages "
-                                      "(absent here); only the synthetic source is built")
         self.in_channels, self.classes = in_channels, classes
+        if self.data_shards is None:
+            return
+        from .pool import DevicePool
+        from .shards import shards_for_rank, split_shards
+        if self.layout == "single_directory":
+            fractions = DeadtreeDatasetConfig.fractions if split_fractions is None else split_fractions
+            train, valid, test = split_shards(self.data_shards, fractions)
+        else:
+            train, valid, test = ([str(s) for s in part] for part in self.data_shards)
+        self.shard_split = {"train": shards_for_rank(train, self.rank, self.world), "val": valid, "test": test or None}
+        self.pools = {name: DevicePool(shards, device=self.device, max_resident_bytes=self.max_resident_bytes)
+                      for name, shards in self.shard_split.items() if shards}
 
     def _loader(self, conf, seed, wrap):
         return _SyntheticLoader(self.synthetic_batches, int(conf.get("batch_size", 8)), self.tile_size,
                                 self.in_channels, self.classes, seed, wrap, self.device, True)
 
-    def train_dataloader(self):
-        return self._loader(self.train_conf, 1000, True)
+    def _pool_loader(self, name, conf, train, wrap, trainer=None, distmap=True):
+        from .pool import PoolLoader
+        if self.pools is None:
+            raise RuntimeError("DeadtreesDataModule: call setup() before asking for a loader")
+        if name not in self.pools:
+            raise RuntimeError(f"DeadtreesDataModule: the split has no {name} shards")
+        if not self.pools[name].on_device:
+            raise RuntimeError("deadtrees_amd loaders run the HIP gather kernel on a device-resident pool: no HIP device, "
+                               "no CPU fallback")
+        return PoolLoader(self.pools[name], int(conf.get("batch_size", 8)), train=train, in_channels=self.in_channels,
+                          classes=self.classes, seed=self.seed, wrap=wrap, distmap=distmap, trainer=trainer)
+
+    def train_dataloader(self, trainer=None, distmap: Optional[bool] = None):
+        """trainer: a ``HipTrainer(graph=True)`` whose captured step the loader feeds in place (``PoolLoader``); its
+        batches then carry no distance maps unless ``distmap=True`` — the trainer computes them inside the captured step
+        when a boundary loss needs them."""
+        if self.data_shards is None:
+            return self._loader(self.train_conf, 1000, True)
+        return self._pool_loader("train", self.train_conf, True, True, trainer,
+                                 (trainer is None) if distmap is None else distmap)
 
     def val_dataloader(self):
-        return self._loader(self.val_conf, 2000, True)
+        if self.data_shards is None:
+            return self._loader(self.val_conf, 2000, True)
+        return self._pool_loader("val", self.val_conf, False, True)
 
     def test_dataloader(self):
-        return self._loader(self.test_conf, 3000, False)
+        if self.data_shards is None:
+            return self._loader(self.test_conf, 3000, False)
+        return self._pool_loader("test", self.test_conf, False, False)
+
+
+def _find_shards(data_dir, pattern):
+    """(layout, shards): ("single_directory", sorted paths) for one directory, ("train/val/test", three sorted lists) for
+    a list of three (reference deadtreedata.py:207-212); (None, None) when there is no shard (the synthetic source)"""
+    from pathlib import Path
+    if not data_dir:
+        return None, None
+    pattern = pattern or "*.tar"
+    if isinstance(data_dir, (list, tuple)):
+        if len(data_dir) != 3:
+            raise ValueError("data_dir as a list is the train / val / test layout: three directories")
+        parts = [sorted(str(p) for p in Path(d).glob(pattern)) for d in data_dir]
+        if not any(parts):
+            return None, None
+        if not (parts[0] and parts[1]):
+            raise ValueError(f"train / val / test layout: no shards matching {pattern!r} in the train or val directory")
+        return "train/val/test", parts
+    shards = sorted(str(p) for p in Path(str(data_dir)).glob(pattern))
+    return ("single_directory", shards) if shards else (None, None)
 
 
 def data_dir_has_shards(data_dir) -> bool:

@@ -1,0 +1,210 @@
+"""Device-resident sample pool, epoch plan and the loader that turns both into batches with one kernel launch each.
+
+The reference decodes, augments and ships every sample every epoch on 2-4 loader processes (the host
+loader bounds real data well below what the training step consumes).  A sample is a 256 x 256 tile: 4 image bands, a mask
+and a land-use map, 384 KiB as uint8 — 10^5 samples are 39 GB and fit in HBM several times over.  So every shard is decoded
+once (``shards.read_shard``), the split stays resident as uint8 (``DevicePool``), the host draws one small plan per epoch
+(``epoch_plan``: sample order and augmentation parameters) and ``PoolLoader`` makes every batch with ``dt_pool_gather_batch``
+(csrc/pool.hip), if asked straight into the tensors a captured training step reads (``HipTrainer.static_batch()``).
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from .distmap import distmaps_on_device
+from .shards import read_shard, shard_len
+from .synthetic import MEAN, STD
+
+
+def _device_or_none(device):
+    if device is not None:
+        return torch.device(device)
+    return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+
+
+class DevicePool:
+    """One split, contiguous: ``images`` uint8 [N,H,W,4], ``masks`` / ``lu`` uint8 [N,H,W], ``sums`` [N] (the exact sum
+    of the 4*H*W bytes of every image: what RandomBrightnessContrast(brightness_by_max=False) needs, invariant under flips
+    and turns, so computed once at decode time) and the host list ``stats`` of ``{"file", "frac"}`` dicts.
+
+    With a HIP device the arrays are device tensors (``sums`` travels as the int64 bit pattern of the uint64 values; they
+    stay below 2^63) filled through pinned host memory, one shard at a time.  Without one the pool keeps numpy arrays
+    (``sums`` uint64), so shard handling can be set up and inspected anywhere; making batches needs the device."""
+
+    def __init__(self, shards: Sequence, device=None, max_resident_bytes: Optional[int] = None, workers: int = 8):
+        shards = [str(s) for s in shards]
+        if not shards:
+            raise ValueError("DevicePool: no shards")
+        self.shards = shards
+        self.device = dev = _device_or_none(device)
+        on_gpu = dev is not None and dev.type == "cuda"
+        if max_resident_bytes is None and on_gpu:
+            max_resident_bytes = torch.cuda.mem_get_info(dev)[0] // 2
+        alloc = None
+        if on_gpu:      # decode into pinned memory: the upload is then one DMA per array
+            def alloc(shape, dtype):
+                return torch.empty(shape, dtype=torch.uint8, pin_memory=True).numpy()
+        first = read_shard(shards[0], alloc=alloc, workers=workers)
+        counts = [len(first["keys"])] + [shard_len(s) for s in shards[1:]]
+        N = int(sum(counts))
+        H, W = first["masks"].shape[1:]
+        self.n, self.height, self.width = N, int(H), int(W)
+        need = N * (H * W * 6 + 8)
+        if max_resident_bytes is not None and need > max_resident_bytes:
+            raise ValueError(f"DevicePool: {N} samples of {H}x{W} need {need} bytes resident, max_resident_bytes is "
+                             f"{int(max_resident_bytes)} (streaming a split that does not fit is not supported)")
+        if on_gpu:
+            self.images = torch.empty((N, H, W, 4), dtype=torch.uint8, device=dev)
+            self.masks = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+            self.lu = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+            self.sums = torch.empty(N, dtype=torch.int64, device=dev)
+            self.device = self.images.device        # (with its index)
+        else:
+            self.images, self.masks = np.empty((N, H, W, 4), np.uint8), np.empty((N, H, W), np.uint8)
+            self.lu, self.sums = np.empty((N, H, W), np.uint8), np.empty(N, np.uint64)
+        self.stats = []
+        at = 0
+        for i, path in enumerate(shards):
+            part = first if i == 0 else read_shard(path, alloc=alloc, workers=workers)
+            n = len(part["keys"])
+            if part["masks"].shape[1:] != (H, W):
+                raise ValueError(f"{path}: tiles are {part['masks'].shape[1]}x{part['masks'].shape[2]}, "
+                                 f"those of {shards[0]} are {H}x{W}")
+            if n != counts[i]:
+                raise ValueError(f"{path}: {n} samples decoded, {counts[i]} listed")
+            if on_gpu:
+                for name in ("images", "masks", "lu"):
+                    getattr(self, name)[at:at + n].copy_(torch.from_numpy(part[name]), non_blocking=True)
+                self.sums[at:at + n].copy_(torch.from_numpy(part["sums"].view(np.int64)))
+                torch.cuda.current_stream(dev).synchronize()      # the pinned staging arrays are released after this
+            else:
+                for name in ("images", "masks", "lu", "sums"):
+                    getattr(self, name)[at:at + n] = part[name]
+            self.stats.extend(part["stats"])
+            at += n
+            first = None if i == 0 else first
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def on_device(self) -> bool:
+        return isinstance(self.images, torch.Tensor)
+
+    @property
+    def nbytes(self) -> int:
+        return self.n * (self.height * self.width * 6 + 8)
+
+
+def epoch_plan(n: int, batch_size: int, epoch: int, seed: int, train: bool, square: bool = True):
+    """The whole epoch on the host: (idx int32 [M], geo int32 [M,2], bc float32 [M,2]) with M = (n // batch_size) *
+    batch_size — the last partial batch is dropped, as by the reference's ``.batched(bs, partial=False)``.
+    train: idx is the head of a permutation of n from ``np.random.default_rng([seed, epoch])`` and the augmentation draws
+    are ``draw_train_params`` on the same generator; on non-square tiles a drawn turn k becomes ``k & 2`` (0 or a half
+    turn; the generator's stream does not depend on the tile shape).  Otherwise idx is ``arange``, geo zeros and bc
+    (1, 0).  Deterministic in (seed, epoch)."""
+    from .deadtreedata import draw_train_params
+    if batch_size < 1:
+        raise ValueError(f"batch_size {batch_size}")
+    m = (n // batch_size) * batch_size
+    if not train:
+        return (torch.arange(m, dtype=torch.int32), torch.zeros((m, 2), dtype=torch.int32),
+                torch.tensor([1.0, 0.0]).repeat(m, 1))
+    rng = np.random.default_rng([int(seed), int(epoch)])
+    idx = torch.from_numpy(rng.permutation(n)[:m].astype(np.int32))
+    if m == 0:
+        return idx, torch.zeros((0, 2), dtype=torch.int32), torch.zeros((0, 2), dtype=torch.float32)
+    geo, bc = draw_train_params(m, rng)
+    if not square:
+        geo[:, 1] &= 2
+    return idx, geo, bc
+
+
+class PoolLoader:
+    """Batches of a ``DevicePool`` in the reference's format: ``{"main": (img f32 [B,C,H,W], mask i64 [B,H,W], distmap,
+    lu i64 [B,H,W], stats)}`` (``wrap=False``: the bare tuple of ``test_dataloader``).  One ``epoch_plan`` per epoch is
+    uploaded (three small copies); each batch is then one ``dt_pool_gather_batch`` launch on slices of it — no host
+    synchronisation and no host-to-device copy per batch.  ``classes == 2`` merges mask labels above 1 into 1.
+    ``distmap``: attach ``distmaps_on_device`` maps (False: ``None``; ``HipTrainer`` computes them itself when a
+    boundary loss needs them).
+
+    ``trainer``: once ``trainer.static_batch()`` exists and its image and mask buffers have this loader's shapes, the
+    gather writes into THOSE tensors and yields them, so the captured step finds its input in place; such batches are
+    overwritten by the next one.  Before that (and without a trainer) every batch is a fresh set of tensors.
+
+    Every ``__iter__`` starts the next epoch (0, 1, 2, ...), so a plain ``for batch in loader`` per epoch reshuffles;
+    ``set_epoch(e)`` makes the next iteration epoch e.  The kernel's error flag (never raised by a plan of
+    ``epoch_plan``) is read once, after the last batch of an epoch."""
+
+    def __init__(self, pool: DevicePool, batch_size: int, train: bool = False, in_channels: int = 3, classes: int = 2,
+                 seed: int = 0, wrap: bool = True, distmap: bool = True, trainer=None, mean=MEAN, std=STD):
+        if not pool.on_device:
+            raise RuntimeError("PoolLoader runs the HIP gather kernel on a device-resident pool: no HIP device, "
+                               "no CPU fallback")
+        if not 1 <= in_channels <= 4:
+            raise ValueError(f"in_channels {in_channels}: the pool holds 4 bands")
+        self.pool, self.batch_size, self.train = pool, int(batch_size), bool(train)
+        self.in_channels, self.classes, self.seed = int(in_channels), int(classes), int(seed)
+        self.wrap, self.distmap, self.trainer = bool(wrap), bool(distmap), trainer
+        self.mean, self.std = tuple(mean), tuple(std)
+        self.epoch = None            # the epoch of the running / last iteration
+        self._next_epoch = 0
+        self._eval_plan = None
+        self._err = torch.zeros(1, dtype=torch.int32, device=pool.device)
+
+    def __len__(self):
+        return len(self.pool) // self.batch_size
+
+    def set_epoch(self, epoch: int):
+        self._next_epoch = int(epoch)
+
+    def plan(self, epoch: int):
+        """the host plan of ``epoch`` (what ``__iter__`` uploads)"""
+        p = self.pool
+        return epoch_plan(len(p), self.batch_size, epoch, self.seed, self.train, p.height == p.width)
+
+    def _static_out(self):
+        sb = self.trainer.static_batch() if self.trainer is not None else None
+        if sb is None:
+            return None
+        img, mask = sb[0], sb[1]
+        p, dev = self.pool, self.pool.device
+        ok = (tuple(img.shape) == (self.batch_size, self.in_channels, p.height, p.width) and img.dtype == torch.float32
+              and tuple(mask.shape) == (self.batch_size, p.height, p.width) and mask.dtype == torch.int64
+              and img.is_contiguous() and mask.is_contiguous() and img.device == dev and mask.device == dev)
+        return (img, mask) if ok else None
+
+    def __iter__(self):
+        from .. import ops
+        p, bs = self.pool, self.batch_size
+        self.epoch = epoch = self._next_epoch
+        self._next_epoch = epoch + 1
+        if self.train or self._eval_plan is None:
+            host = self.plan(epoch)
+            dev_plan = tuple(t.to(p.device, non_blocking=True) for t in host)
+            if not self.train:
+                self._eval_plan = (host, dev_plan)
+        else:
+            host, dev_plan = self._eval_plan
+        order = host[0].tolist()
+        idx, geo, bc = dev_plan
+        for k in range(len(self)):
+            lo, hi = k * bs, (k + 1) * bs
+            static = self._static_out()
+            out = None
+            if static is not None:      # lu is not an input of the step: it gets a tensor of its own
+                out = (static[0], static[1], torch.empty((bs, p.height, p.width), dtype=torch.int64, device=p.device))
+            img, mask, lu, _ = ops.pool_gather_batch(p.images, p.masks, p.lu, p.sums, idx[lo:hi], geo[lo:hi], bc[lo:hi],
+                                                     self.mean, self.std, self.in_channels, self.classes == 2, out=out,
+                                                     err=self._err)
+            dist = distmaps_on_device(mask, self.classes) if self.distmap else None
+            item = (img, mask, dist, lu, [p.stats[i] for i in order[lo:hi]])
+            yield {"main": item} if self.wrap else item
+        flag = int(self._err.item())     # the one read of the epoch
+        if flag:
+            self._err.zero_()
+            raise RuntimeError(f"pool gather: error flag {flag} (1: sample index outside the pool, 2: odd turn of a "
+                               "non-square tile); those samples were zero-filled")

@@ -888,6 +888,49 @@ def augment_labels(labels, geo):
     return out
 
 
+def pool_gather_batch(images, masks, lu, sums, idx, geo, bc, mean, std, c_dst, merge_above=False, out=None, err=None):
+    """One batch out of a device-resident pool in one launch (csrc/pool.hip): images uint8 [N,H,W,4], masks / lu uint8
+    [N,H,W] (lu may be None), sums int64 [N] (the exact byte sum of every image; the bits of the ABI's uint64), idx int32
+    [B], geo int32 [B,2], bc fp32 [B,2] -> (img fp32 [B,c_dst,H,W] contiguous, mask int64 [B,H,W], lu int64 [B,H,W] or
+    None, err int32 [1]).  The arithmetic is that of ``augment_normalize_u8`` / ``augment_labels`` on ``images[idx]``.
+    out: (img, mask, lu) tensors to write into (e.g. ``HipTrainer.static_batch()``'s); err: a flag to OR into.  No host
+    synchronisation: a bad index or an odd turn of a non-square tile zeroes that sample and sets a bit of ``err``."""
+    _gpu(images, masks, lu, sums, idx, geo, bc)
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 4 or not images.is_contiguous():
+        raise RuntimeError("pool_gather_batch: images must be contiguous uint8 [N,H,W,4]")
+    N, H, W, _ = images.shape
+    for name, t in (("masks", masks), ("lu", lu)):
+        if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != (N, H, W) or not t.is_contiguous()):
+            raise RuntimeError(f"pool_gather_batch: {name} must be contiguous uint8 [N,H,W]")
+    if sums.dtype != torch.int64 or tuple(sums.shape) != (N,) or not sums.is_contiguous():
+        raise RuntimeError("pool_gather_batch: sums must be contiguous int64 [N]")
+    B = idx.shape[0]
+    if (idx.dtype != torch.int32 or idx.dim() != 1 or geo.dtype != torch.int32 or tuple(geo.shape) != (B, 2)
+            or bc.dtype != torch.float32 or tuple(bc.shape) != (B, 2)
+            or not (idx.is_contiguous() and geo.is_contiguous() and bc.is_contiguous())):
+        raise RuntimeError("pool_gather_batch: idx must be int32 [B], geo int32 [B,2] and bc float32 [B,2], contiguous")
+    dev = images.device
+    if out is None:
+        out = (torch.empty((B, c_dst, H, W), dtype=torch.float32, device=dev),
+               torch.empty((B, H, W), dtype=torch.int64, device=dev),
+               None if lu is None else torch.empty((B, H, W), dtype=torch.int64, device=dev))
+    img, mask, lu_out = out
+    for name, t, shape, dt in (("img", img, (B, c_dst, H, W), torch.float32), ("mask", mask, (B, H, W), torch.int64),
+                               ("lu", lu_out, (B, H, W), torch.int64)):
+        if (t is None) != (name == "lu" and lu is None):
+            raise RuntimeError("pool_gather_batch: out needs img and mask, and lu exactly when the pool has one")
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev):
+            raise RuntimeError(f"pool_gather_batch: out {name} must be contiguous {dt} {list(shape)} on {dev}")
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    m = (C.c_float * c_dst)(*[float(v) for v in mean[:c_dst]])
+    s = (C.c_float * c_dst)(*[float(v) for v in std[:c_dst]])
+    _lib.check(_lib.load().dt_pool_gather_batch(_p(images), _p(masks), _p(lu), _p(sums), _p(idx), _p(geo), _p(bc), _p(img),
+                                                _p(mask), _p(lu_out), _p(err), N, B, H, W, c_dst, int(bool(merge_above)),
+                                                m, s, _st()), "dt_pool_gather_batch")
+    return img, mask, lu_out, err
+
+
 def ensemble_vote(maps_u8: torch.Tensor, K: int, dtype: str = "int64"):
     """uint8 class maps [M, ...] of M models -> per-pixel mode [...] (ties -> smallest class, torch.mode);
     returns (map, err flag).  deployment/inference.py:65-116."""

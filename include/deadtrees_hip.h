@@ -275,6 +275,22 @@ int dt_augment_normalize_u8(const uint8_t* src, float* dst, const int32_t* geo, 
                             int B, int H, int W, int Csrc, int Cdst, const float* mean, const float* std, void* stream);
 int dt_augment_labels(const int64_t* src, int64_t* dst, const int32_t* geo, int B, int H, int W, void* stream);
 
+/* Batch gather from a device-resident sample pool: images uint8 [N][H][W][4] (4-byte aligned), masks / lu uint8 [N][H][W]
+ * (lu and lu_out may both be NULL), sums uint64 [N] = the exact sum of the 4*H*W image bytes of every sample.  For
+ * b < B the sample idx[b] goes through the flip / turn geo[b] and the brightness-contrast bc[b] of
+ * dt_augment_normalize_u8, with its arithmetic bit for bit, into img_out fp32 PLANAR [B][Cdst][H][W]; mask_out / lu_out
+ * int64 [B][H][W] take the same pixel map.  merge_above != 0: mask labels above 1 become 1 (the reference's
+ * classes == 2 rule, data/deadtreedata.py:179-180); lu is never merged.  One launch, no scratch memory.
+ * The pool is never read out of range: a sample with idx[b] outside [0, N), or with an odd turn while H != W, is
+ * written as zeros and ORs DT_POOL_ERR_INDEX / DT_POOL_ERR_TURN into err_flag[0] (int32, zeroed by the caller).
+ * mean/std: HOST arrays of Cdst floats. */
+#define DT_POOL_ERR_INDEX 1
+#define DT_POOL_ERR_TURN 2
+int dt_pool_gather_batch(const uint8_t* images, const uint8_t* masks, const uint8_t* lu, const uint64_t* sums,
+                         const int32_t* idx, const int32_t* geo, const float* bc, float* img_out, int64_t* mask_out,
+                         int64_t* lu_out, int32_t* err_flag, int64_t N, int B, int H, int W, int Cdst, int merge_above,
+                         const float* mean, const float* std, void* stream);
+
 /* Data gradient of a 3x3 stride-1 layer with the BatchNorm-backward REDUCTION of the layer it feeds fused into the
  * epilogue (instead of a separate dt_bn_bwd_reduce pass over the tensor it has just written): out0 = conv(src0, w)
  * like dt_conv2d (no concat / split / accumulate / upsample), and red[2][P][Cout] (P = dt_conv2d_stat_rows(desc))
