@@ -37,6 +37,14 @@ class LossCfg(C.Structure):
     _fields_ = [("dice_kind", I32), ("use_boundary", I32), ("use_focal", I32), ("boundary_weight", F32), ("gamma", F32)]
 
 
+class PoolSource(C.Structure):
+    """dt_pool_source: one pool of dt_pool_gather_combined's table"""
+    _fields_ = [("images", C.c_void_p), ("masks", C.c_void_p), ("lu", C.c_void_p), ("sums", C.c_void_p), ("n", I64)]
+
+
+POOL_MAX_SOURCES = 8      # DT_POOL_MAX_SOURCES
+
+
 # name -> (restype, argtypes).  Must list every symbol of include/deadtrees_hip.h
 # (tests/test_abi.py cross-checks this table against the header).
 SIGNATURES = {
@@ -131,6 +139,8 @@ SIGNATURES = {
     "dt_augment_labels": (C.c_int, [c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, c_f]),
     "dt_pool_gather_batch": (C.c_int, [c_f] * 11 + [I64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_float), C.POINTER(C.c_float), c_f]),
+    "dt_pool_gather_combined": (C.c_int, [C.POINTER(PoolSource), C.c_int] + [c_f] * 8 + [C.c_int] * 5 +
+                                [C.POINTER(C.c_float), C.POINTER(C.c_float), c_f]),
     "dt_conv2d_bn_bwd": (C.c_int, [_P, c_f, c_f, c_f, c_f, C.POINTER(BnBwdFuse), c_f]),
     "dt_conv2d_bf16_bn_bwd": (C.c_int, [_P, c_f, c_f, c_f, c_f, C.POINTER(BnBwdFuse), c_f]),
     "dt_maxpool3x3s2_bwd_bn_rows": (C.c_int, [C.c_int] * 4),

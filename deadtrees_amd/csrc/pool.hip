@@ -16,6 +16,9 @@
 //
 // The kernel never reads outside the pool: a sample whose index is outside [0, N), or that asks for an odd turn of a
 // non-square tile, is written as zeros and raises a bit of err_flag.
+//
+// dt_pool_gather_combined makes the same batch out of several pools (the reference's main + extra shard sets): slot b
+// takes sample idx[b] of pool src[b].  Both kernels share pool_gather_slot, so their arithmetic cannot drift apart.
 #include "common.h"
 #include "views.h"
 
@@ -23,17 +26,19 @@ typedef long long i64x2 __attribute__((ext_vector_type(2)));
 
 #define POOL_ERR_INDEX 1   // err_flag bits (include/deadtrees_hip.h: DT_POOL_ERR_*)
 #define POOL_ERR_TURN 2
+#define POOL_ERR_SOURCE 4
 
+// One slot of a batch: sample s of the pool (images, masks, lu, sums) into slot blockIdx.y of the outputs.  bad: the
+// error bits the caller found for s (the index, or the source, is out of range); everything here is uniform per workgroup
 template <bool VEC>
-__global__ __launch_bounds__(256) void pool_gather_batch_kernel(
+__device__ __forceinline__ void pool_gather_slot(
     const uint32_t* __restrict__ images, const uint8_t* __restrict__ masks, const uint8_t* __restrict__ lu,
-    const unsigned long long* __restrict__ sums, const int32_t* __restrict__ idx, const int32_t* __restrict__ geo,
+    const unsigned long long* __restrict__ sums, const int64_t s, const int bad, const int32_t* __restrict__ geo,
     const float* __restrict__ bc, float* __restrict__ img_out, int64_t* __restrict__ mask_out, int64_t* __restrict__ lu_out,
-    int32_t* __restrict__ err_flag, int64_t N, int H, int W, int Cd, int merge_above, f32x4 mean, f32x4 stdv) {
+    int32_t* __restrict__ err_flag, int H, int W, int Cd, int merge_above, f32x4 mean, f32x4 stdv) {
   const int b = blockIdx.y;
-  const int64_t s = idx[b];
   const int flip = geo[2 * b], rot = geo[2 * b + 1];
-  const int err = ((s < 0 || s >= N) ? POOL_ERR_INDEX : 0) | (((rot & 1) && H != W) ? POOL_ERR_TURN : 0);
+  const int err = bad | (((rot & 1) && H != W) ? POOL_ERR_TURN : 0);
   if (err && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(err_flag, err);
   const bool live = err == 0;      // uniform per workgroup; a dead sample reads nothing and writes zeros
   const float alpha = bc[2 * b], beta = bc[2 * b + 1];
@@ -110,6 +115,39 @@ __global__ __launch_bounds__(256) void pool_gather_batch_kernel(
   }
 }
 
+template <bool VEC>
+__global__ __launch_bounds__(256) void pool_gather_batch_kernel(
+    const uint32_t* __restrict__ images, const uint8_t* __restrict__ masks, const uint8_t* __restrict__ lu,
+    const unsigned long long* __restrict__ sums, const int32_t* __restrict__ idx, const int32_t* __restrict__ geo,
+    const float* __restrict__ bc, float* __restrict__ img_out, int64_t* __restrict__ mask_out, int64_t* __restrict__ lu_out,
+    int32_t* __restrict__ err_flag, int64_t N, int H, int W, int Cd, int merge_above, f32x4 mean, f32x4 stdv) {
+  const int64_t s = idx[blockIdx.y];
+  pool_gather_slot<VEC>(images, masks, lu, sums, s, (s < 0 || s >= N) ? POOL_ERR_INDEX : 0, geo, bc, img_out, mask_out,
+                        lu_out, err_flag, H, W, Cd, merge_above, mean, stdv);
+}
+
+// The same slot out of one of several pools: src[b] picks a row of the table, which is a kernel argument — the row index is
+// a scalar (blockIdx.y -> one scalar load of src), so the row's four pointers and its n arrive by scalar loads from the
+// kernarg segment: no vector work, no private copy of the table.
+struct pool_table {
+  dt_pool_source s[DT_POOL_MAX_SOURCES];
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void pool_gather_combined_kernel(
+    const pool_table tab, const int n_sources, const int32_t* __restrict__ src, const int32_t* __restrict__ idx,
+    const int32_t* __restrict__ geo, const float* __restrict__ bc, float* __restrict__ img_out,
+    int64_t* __restrict__ mask_out, int64_t* __restrict__ lu_out, int32_t* __restrict__ err_flag, int H, int W, int Cd,
+    int merge_above, f32x4 mean, f32x4 stdv) {
+  const int j = src[blockIdx.y];
+  const int64_t s = idx[blockIdx.y];
+  const bool known = j >= 0 && j < n_sources;
+  const dt_pool_source& p = tab.s[known ? j : 0];        // (row 0 always exists; a slot with an unknown source reads nothing)
+  const int bad = !known ? POOL_ERR_SOURCE : ((s < 0 || s >= p.n) ? POOL_ERR_INDEX : 0);
+  pool_gather_slot<VEC>((const uint32_t*)p.images, p.masks, p.lu, (const unsigned long long*)p.sums, s, bad, geo, bc,
+                        img_out, mask_out, lu_out, err_flag, H, W, Cd, merge_above, mean, stdv);
+}
+
 extern "C" int dt_pool_gather_batch(const uint8_t* images, const uint8_t* masks, const uint8_t* lu, const uint64_t* sums,
                                     const int32_t* idx, const int32_t* geo, const float* bc, float* img_out,
                                     int64_t* mask_out, int64_t* lu_out, int32_t* err_flag, int64_t N, int B, int H, int W,
@@ -138,6 +176,45 @@ extern "C" int dt_pool_gather_batch(const uint8_t* images, const uint8_t* masks,
     hipLaunchKernelGGL(pool_gather_batch_kernel<false>, grid, block, 0, st, (const uint32_t*)images, masks, lu,
                        (const unsigned long long*)sums, idx, geo, bc, img_out, mask_out, lu_out, err_flag, N, H, W, Cdst,
                        merge_above, m, s);
+  DT_LAUNCH_CHECK();
+  return DT_OK;
+}
+
+extern "C" int dt_pool_gather_combined(const dt_pool_source* sources, int n_sources, const int32_t* src, const int32_t* idx,
+                                       const int32_t* geo, const float* bc, float* img_out, int64_t* mask_out,
+                                       int64_t* lu_out, int32_t* err_flag, int B, int H, int W, int Cdst, int merge_above,
+                                       const float* mean, const float* stdv, void* stream) {
+  DT_REQUIRE(sources && src && idx && geo && bc && img_out && mask_out && err_flag && mean && stdv,
+             "pool_gather_combined: null argument");
+  DT_REQUIRE(n_sources >= 1 && n_sources <= DT_POOL_MAX_SOURCES, "pool_gather_combined: 1 .. %d sources",
+             DT_POOL_MAX_SOURCES);
+  DT_REQUIRE(B > 0 && H > 0 && W > 0 && Cdst > 0 && Cdst <= 4, "pool_gather_combined: bad sizes");
+  DT_REQUIRE(B <= 65535, "pool_gather_combined: B must be <= 65535");
+  pool_table tab = {};
+  for (int j = 0; j < n_sources; ++j) {
+    const dt_pool_source& p = sources[j];
+    DT_REQUIRE(p.images && p.masks && p.sums && p.n > 0, "pool_gather_combined: source %d: null array or no samples", j);
+    DT_REQUIRE(!lu_out || p.lu, "pool_gather_combined: lu_out needs lu in every source (source %d has none)", j);
+    DT_REQUIRE(((uintptr_t)p.images & 3) == 0, "pool_gather_combined: the image pool must be 4-byte aligned (source %d)", j);
+    tab.s[j] = p;
+    if (!lu_out) tab.s[j].lu = nullptr;
+  }
+  f32x4 m = {0, 0, 0, 0}, s = {1, 1, 1, 1};
+  for (int c = 0; c < Cdst; ++c) {
+    m[c] = mean[c];
+    s[c] = stdv[c];
+  }
+  const bool vec = (W & 3) == 0 && (((uintptr_t)img_out | (uintptr_t)mask_out | (uintptr_t)lu_out) & 15) == 0;
+  int gx = dt_cdiv((int64_t)H * ((W + 3) / 4), 256);
+  if (gx > 1024) gx = 1024;
+  const dim3 grid(gx, B), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (vec)
+    hipLaunchKernelGGL(pool_gather_combined_kernel<true>, grid, block, 0, st, tab, n_sources, src, idx, geo, bc, img_out,
+                       mask_out, lu_out, err_flag, H, W, Cdst, merge_above, m, s);
+  else
+    hipLaunchKernelGGL(pool_gather_combined_kernel<false>, grid, block, 0, st, tab, n_sources, src, idx, geo, bc, img_out,
+                       mask_out, lu_out, err_flag, H, W, Cdst, merge_above, m, s);
   DT_LAUNCH_CHECK();
   return DT_OK;
 }

@@ -131,7 +131,13 @@ class DeadtreesDataModule:
     directories, the reference's train / val / test layout): ``setup`` decodes every shard once into device-resident
     pools (``data/pool.py``) and the ``*_dataloader()`` methods return ``PoolLoader``s, whose batches one HIP gather
     kernel makes.  ``rank`` / ``world``: under data parallelism every rank reads ``shards_for_rank`` of the train shards;
-    ``seed`` seeds the epoch plans; ``max_resident_bytes`` bounds each pool (default: half of the free device memory)."""
+    ``seed`` seeds the epoch plans; ``max_resident_bytes`` bounds each pool (default: half of the free device memory).
+
+    ``pattern_extra`` / ``batch_size_extra`` (reference :218-238, 318-395; its ``deadtrees_multi_datasets*`` configs): further
+    shard sets of the one directory.  Each is split train / val in the main set's proportion into pools of its own
+    (``extra_pools``); the train and val loaders then are ``CombinedPoolLoader``s whose batches hold ``batch_size -
+    sum(batch_size_extra)`` main samples under ``"main"`` and ``batch_size_extra[i]`` samples of set i under ``"extra_i"``,
+    the shorter sets cycling, all from one kernel launch.  The test loader stays the main set alone."""
 
     def __init__(self, data_dir=None, pattern=None, pattern_extra=None, batch_size_extra=None,
                  train_dataloader_conf=None, val_dataloader_conf=None, test_dataloader_conf=None,
@@ -145,10 +151,32 @@ class DeadtreesDataModule:
         self.in_channels, self.classes = 3, 2
         self.rank, self.world, self.seed, self.max_resident_bytes = rank, world, seed, max_resident_bytes
         self.pools = None
+        self.extra_pools = []
         self.layout, self.data_shards = _find_shards(data_dir, pattern)
-        if self.data_shards is not None and (pattern_extra or batch_size_extra):
-            raise NotImplementedError("pattern_extra / batch_size_extra (the reference's combined-dataset cycle of extra "
-                                      "shard sets) are not built: one shard set per datamodule")
+        self.pattern_extra = [str(p) for p in (pattern_extra or [])]
+        self.batch_size_extra = [int(b) for b in (batch_size_extra or [])]
+        self.data_shards_extra = []
+        if self.pattern_extra or self.batch_size_extra:
+            if isinstance(data_dir, (list, tuple)):
+                raise ValueError("Combining pattern_extra with train/val/test layout not allowed")
+            if not self.batch_size_extra:
+                raise ValueError("<pattern_extra> provided but no <batch_size_extra> ratio found")
+            if not self.pattern_extra:
+                raise ValueError("<batch_size_extra> provided but no <pattern_extra> found")
+            if len(self.batch_size_extra) != len(self.pattern_extra):
+                raise ValueError("Len of <pattern_extra> and <batch_size_extra> don't match")
+            if min(self.batch_size_extra) < 1:
+                raise ValueError(f"batch_size_extra {self.batch_size_extra}: every extra set gives at least one sample")
+            if self.data_shards is None:
+                raise NotImplementedError("pattern_extra / batch_size_extra with the synthetic source (no shard matches "
+                                          "`pattern` in data_dir) are not built: extra sets are shard sets")
+            from pathlib import Path
+            for p in self.pattern_extra:
+                shards = sorted(str(q) for q in Path(str(data_dir)).glob(p))
+                if not shards:
+                    raise NotImplementedError(f"pattern_extra {p!r} matches no shard in {data_dir}: an extra set without "
+                                              "samples cannot be cycled")
+                self.data_shards_extra.append(shards)
 
     def setup(self, stage=None, split_fractions=None, in_channels: int = 3, classes: int = 2):
         self.in_channels, self.classes = in_channels, classes
@@ -164,6 +192,27 @@ class DeadtreesDataModule:
         self.shard_split = {"train": shards_for_rank(train, self.rank, self.world), "val": valid, "test": test or None}
         self.pools = {name: DevicePool(shards, device=self.device, max_resident_bytes=self.max_resident_bytes)
                       for name, shards in self.shard_split.items() if shards}
+        # every extra set is split train / val in the proportion of the main split (reference :318-346)
+        self.extra_pools, self.extra_shard_split = [], []
+        train_frac = len(train) / (len(train) + len(valid))
+        main = self.pools["train"]
+        for pattern, shards in zip(self.pattern_extra, self.data_shards_extra):
+            if len(shards) < 2:
+                raise ValueError(f"pattern_extra {pattern!r} matches {len(shards)} shard: a train and a val part need "
+                                 "one shard each")
+            e_train, e_valid, _ = split_shards(shards, [train_frac, 1 - train_frac])
+            if not e_train or not e_valid:
+                raise ValueError(f"pattern_extra {pattern!r}: the split of its {len(shards)} shards leaves the "
+                                 f"{'train' if not e_train else 'val'} part empty")
+            split = {"train": shards_for_rank(e_train, self.rank, self.world), "val": e_valid}
+            pools = {name: DevicePool(part, device=self.device, max_resident_bytes=self.max_resident_bytes)
+                     for name, part in split.items()}
+            for name, pool in pools.items():
+                if (pool.height, pool.width) != (main.height, main.width):
+                    raise ValueError(f"pattern_extra {pattern!r}: {name} tiles are {pool.height}x{pool.width}, those of "
+                                     f"the main set {main.height}x{main.width}")
+            self.extra_shard_split.append(split)
+            self.extra_pools.append(pools)
 
     def _loader(self, conf, seed, wrap):
         return _SyntheticLoader(self.synthetic_batches, int(conf.get("batch_size", 8)), self.tile_size,
@@ -181,18 +230,38 @@ class DeadtreesDataModule:
         return PoolLoader(self.pools[name], int(conf.get("batch_size", 8)), train=train, in_channels=self.in_channels,
                           classes=self.classes, seed=self.seed, wrap=wrap, distmap=distmap, trainer=trainer)
 
+    def _combined_loader(self, name, conf, train, trainer=None, distmap=True):
+        from .pool import CombinedPoolLoader
+        if self.pools is None:
+            raise RuntimeError("DeadtreesDataModule: call setup() before asking for a loader")
+        batch_size = int(conf.get("batch_size", 8))
+        main = batch_size - sum(self.batch_size_extra)
+        if main < 1:
+            raise ValueError(f"{name} batch_size {batch_size} leaves {main} main samples beside batch_size_extra "
+                             f"{self.batch_size_extra}")
+        pools = [self.pools[name]] + [e[name] for e in self.extra_pools]
+        if not all(p.on_device for p in pools):
+            raise RuntimeError("deadtrees_amd loaders run the HIP gather kernel on a device-resident pool: no HIP device, "
+                               "no CPU fallback")
+        return CombinedPoolLoader(pools, [main] + self.batch_size_extra, train=train, in_channels=self.in_channels,
+                                  classes=self.classes, seed=self.seed, distmap=distmap, trainer=trainer)
+
     def train_dataloader(self, trainer=None, distmap: Optional[bool] = None):
         """trainer: a ``HipTrainer(graph=True)`` whose captured step the loader feeds in place (``PoolLoader``); its
         batches then carry no distance maps unless ``distmap=True`` — the trainer computes them inside the captured step
         when a boundary loss needs them."""
         if self.data_shards is None:
             return self._loader(self.train_conf, 1000, True)
-        return self._pool_loader("train", self.train_conf, True, True, trainer,
-                                 (trainer is None) if distmap is None else distmap)
+        distmap = (trainer is None) if distmap is None else distmap
+        if self.data_shards_extra:
+            return self._combined_loader("train", self.train_conf, True, trainer, distmap)
+        return self._pool_loader("train", self.train_conf, True, True, trainer, distmap)
 
     def val_dataloader(self):
         if self.data_shards is None:
             return self._loader(self.val_conf, 2000, True)
+        if self.data_shards_extra:
+            return self._combined_loader("val", self.val_conf, False)
         return self._pool_loader("val", self.val_conf, False, True)
 
     def test_dataloader(self):

@@ -6,6 +6,11 @@ and a land-use map, 384 KiB as uint8 — 10^5 samples are 39 GB and fit in HBM s
 once (``shards.read_shard``), the split stays resident as uint8 (``DevicePool``), the host draws one small plan per epoch
 (``epoch_plan``: sample order and augmentation parameters) and ``PoolLoader`` makes every batch with ``dt_pool_gather_batch``
 (csrc/pool.hip), if asked straight into the tensors a captured training step reads (``HipTrainer.static_batch()``).
+
+The reference's training configurations add extra shard sets to the main one (``pattern_extra`` / ``batch_size_extra``:
+every batch is some main samples followed by a fixed number of each extra set, the shorter sets cycling).  Those are
+several pools, one plan (``combined_plan``) and ``CombinedPoolLoader``, whose batches are still one launch each
+(``dt_pool_gather_combined``).
 """
 from __future__ import annotations
 
@@ -99,13 +104,15 @@ class DevicePool:
         return self.n * (self.height * self.width * 6 + 8)
 
 
-def epoch_plan(n: int, batch_size: int, epoch: int, seed: int, train: bool, square: bool = True):
+def epoch_plan(n: int, batch_size: int, epoch: int, seed: int, train: bool, square: bool = True, stream: Sequence = ()):
     """The whole epoch on the host: (idx int32 [M], geo int32 [M,2], bc float32 [M,2]) with M = (n // batch_size) *
     batch_size — the last partial batch is dropped, as by the reference's ``.batched(bs, partial=False)``.
     train: idx is the head of a permutation of n from ``np.random.default_rng([seed, epoch])`` and the augmentation draws
     are ``draw_train_params`` on the same generator; on non-square tiles a drawn turn k becomes ``k & 2`` (0 or a half
     turn; the generator's stream does not depend on the tile shape).  Otherwise idx is ``arange``, geo zeros and bc
-    (1, 0).  Deterministic in (seed, epoch)."""
+    (1, 0).  Deterministic in (seed, epoch).  ``stream``: further integers of the generator's seed,
+    ``default_rng([seed, epoch, *stream])`` — independent draws for the same (seed, epoch), as ``combined_plan`` needs them
+    for its extra sources and their cycles."""
     from .deadtreedata import draw_train_params
     if batch_size < 1:
         raise ValueError(f"batch_size {batch_size}")
@@ -113,7 +120,7 @@ def epoch_plan(n: int, batch_size: int, epoch: int, seed: int, train: bool, squa
     if not train:
         return (torch.arange(m, dtype=torch.int32), torch.zeros((m, 2), dtype=torch.int32),
                 torch.tensor([1.0, 0.0]).repeat(m, 1))
-    rng = np.random.default_rng([int(seed), int(epoch)])
+    rng = np.random.default_rng([int(seed), int(epoch), *(int(v) for v in stream)])
     idx = torch.from_numpy(rng.permutation(n)[:m].astype(np.int32))
     if m == 0:
         return idx, torch.zeros((0, 2), dtype=torch.int32), torch.zeros((0, 2), dtype=torch.float32)
@@ -208,3 +215,156 @@ class PoolLoader:
             self._err.zero_()
             raise RuntimeError(f"pool gather: error flag {flag} (1: sample index outside the pool, 2: odd turn of a "
                                "non-square tile); those samples were zero-filled")
+
+
+def combined_plan(ns: Sequence[int], batch_sizes: Sequence[int], epoch: int, seed: int, train: bool, square: bool = True):
+    """One epoch over several sources, the reference's ``CombinedLoader(..., "max_size_cycle")`` over loaders batched
+    with ``partial=False`` (deadtreedata.py:348-395): source j has ``len_j = ns[j] // batch_sizes[j]`` batches, the epoch
+    ``L = max(len_j)``, and a source that runs out starts over.  Returns ``(L, src int32 [M], idx int32 [M], geo int32
+    [M,2], bc float32 [M,2])`` on the host, ``M = L * sum(batch_sizes)``: batch k is rows ``[k*B, (k+1)*B)``, in it
+    ``batch_sizes[0]`` rows of source 0, then those of source 1, and so on.
+
+    Source j at batch k is in cycle ``c = k // len_j`` at position ``p = k % len_j``; its rows are rows ``[p*bs_j,
+    (p+1)*bs_j)`` of ``epoch_plan(ns[j], bs_j, epoch, seed, train, square, stream=S)`` with ``S = ()`` for (j, c) == (0, 0)
+    and ``S = (j, c)`` otherwise: the main part of the first ``len_0`` batches is a plain ``PoolLoader`` epoch, every cycle
+    the head of a fresh permutation.  Without ``train`` every cycle is ``arange`` with neutral parameters.  A source too
+    small for one batch raises ``ValueError`` (there is nothing to cycle)."""
+    ns, batch_sizes = [int(n) for n in ns], [int(b) for b in batch_sizes]
+    if not ns or len(ns) != len(batch_sizes):
+        raise ValueError(f"combined_plan: {len(ns)} sources, {len(batch_sizes)} batch sizes")
+    if min(batch_sizes) < 1:
+        raise ValueError(f"combined_plan: batch sizes {batch_sizes}")
+    lens = [n // b for n, b in zip(ns, batch_sizes)]
+    for j, (n, b) in enumerate(zip(ns, batch_sizes)):
+        if lens[j] == 0:
+            raise ValueError(f"combined_plan: source {j} holds {n} samples, fewer than its batch size {b}")
+    L, B = max(lens), sum(batch_sizes)
+    src = torch.empty((L, B), dtype=torch.int32)
+    idx = torch.empty((L, B), dtype=torch.int32)
+    geo = torch.empty((L, B, 2), dtype=torch.int32)
+    bc = torch.empty((L, B, 2), dtype=torch.float32)
+    at = 0
+    for j, (n, b, ln) in enumerate(zip(ns, batch_sizes, lens)):
+        src[:, at:at + b] = j
+        for c in range(-(-L // ln)):
+            stream = () if (j, c) == (0, 0) else (j, c)
+            k0, k1 = c * ln, min((c + 1) * ln, L)
+            for dst, part in zip((idx, geo, bc), epoch_plan(n, b, epoch, seed, train, square, stream=stream)):
+                dst[k0:k1, at:at + b] = part[:(k1 - k0) * b].reshape((k1 - k0, b) + tuple(part.shape[1:]))
+        at += b
+    return L, src.reshape(-1), idx.reshape(-1), geo.reshape(-1, 2), bc.reshape(-1, 2)
+
+
+class CombinedBatch(dict):
+    """``{"main": (...), "extra_0": (...), ...}`` of the reference's five-tuples whose tensors are views of ONE contiguous
+    tensor per field; ``combined`` is the five-tuple of those whole tensors (stats concatenated in key order) — what
+    ``create_combined_batch`` would ``torch.cat`` together, and what it hands back instead."""
+
+    def __init__(self, combined, batch_sizes: Sequence[int]):
+        super().__init__()
+        img, mask, dist, lu, stats = combined
+        self.combined = (img, mask, dist, lu, stats)
+        at = 0
+        for j, b in enumerate(batch_sizes):
+            part = slice(at, at + b)
+            self["main" if j == 0 else f"extra_{j - 1}"] = (
+                img[part], mask[part], None if dist is None else dist[part], None if lu is None else lu[part],
+                stats[part])
+            at += b
+        if at != img.shape[0]:
+            raise ValueError(f"CombinedBatch: batch sizes {list(batch_sizes)} for {img.shape[0]} samples")
+
+
+class CombinedPoolLoader:
+    """``PoolLoader`` over several pools (the main set and the extra sets of ``pattern_extra``): every batch is a
+    ``CombinedBatch`` of ``batch_sizes[0]`` main samples followed by ``batch_sizes[j]`` samples of every extra pool, made
+    by one ``dt_pool_gather_combined`` launch on slices of the epoch's ``combined_plan`` (four small uploads per epoch:
+    src, idx, geo, bc).  ``len()`` is the longest source's batch count; shorter ones cycle.  Distance maps are computed
+    once, on the combined mask.  ``trainer``, the epoch counter, ``set_epoch`` and the one read of the error flag per
+    epoch are those of ``PoolLoader``; the buffers of ``trainer.static_batch()`` are written when they have the shape of
+    the combined batch."""
+
+    def __init__(self, pools: Sequence[DevicePool], batch_sizes: Sequence[int], train: bool = False, in_channels: int = 3,
+                 classes: int = 2, seed: int = 0, distmap: bool = True, trainer=None, mean=MEAN, std=STD):
+        from .._lib import POOL_MAX_SOURCES
+        pools, batch_sizes = list(pools), [int(b) for b in batch_sizes]
+        if not pools or len(pools) != len(batch_sizes):
+            raise ValueError(f"CombinedPoolLoader: {len(pools)} pools, {len(batch_sizes)} batch sizes")
+        if len(pools) > POOL_MAX_SOURCES:
+            raise ValueError(f"CombinedPoolLoader: at most {POOL_MAX_SOURCES} pools, not {len(pools)}")
+        if not all(p.on_device for p in pools):
+            raise RuntimeError("CombinedPoolLoader runs the HIP gather kernel on device-resident pools: no HIP device, "
+                               "no CPU fallback")
+        if not 1 <= in_channels <= 4:
+            raise ValueError(f"in_channels {in_channels}: the pool holds 4 bands")
+        first = pools[0]
+        for j, p in enumerate(pools):
+            if (p.height, p.width) != (first.height, first.width) or p.device != first.device:
+                raise ValueError(f"CombinedPoolLoader: pool {j} holds {p.height}x{p.width} tiles on {p.device}, pool 0 "
+                                 f"{first.height}x{first.width} on {first.device}")
+        self.pools, self.batch_sizes, self.train = pools, batch_sizes, bool(train)
+        self.batch_size = sum(batch_sizes)
+        self.in_channels, self.classes, self.seed = int(in_channels), int(classes), int(seed)
+        self.distmap, self.trainer = bool(distmap), trainer
+        self.mean, self.std = tuple(mean), tuple(std)
+        self.epoch = None
+        self._next_epoch = 0
+        self._eval_plan = None
+        self._len = self.plan(0)[0]          # (raises for a pool too small for one batch)
+        self._sources = [(p.images, p.masks, p.lu, p.sums) for p in pools]
+        self._err = torch.zeros(1, dtype=torch.int32, device=first.device)
+
+    def __len__(self):
+        return self._len
+
+    def set_epoch(self, epoch: int):
+        self._next_epoch = int(epoch)
+
+    def plan(self, epoch: int):
+        """the host plan of ``epoch``: ``combined_plan`` of the pools' sizes"""
+        p = self.pools[0]
+        return combined_plan([len(q) for q in self.pools], self.batch_sizes, epoch, self.seed, self.train,
+                             p.height == p.width)
+
+    def _static_out(self):
+        sb = self.trainer.static_batch() if self.trainer is not None else None
+        if sb is None:
+            return None
+        img, mask = sb[0], sb[1]
+        p, dev = self.pools[0], self.pools[0].device
+        ok = (tuple(img.shape) == (self.batch_size, self.in_channels, p.height, p.width) and img.dtype == torch.float32
+              and tuple(mask.shape) == (self.batch_size, p.height, p.width) and mask.dtype == torch.int64
+              and img.is_contiguous() and mask.is_contiguous() and img.device == dev and mask.device == dev)
+        return (img, mask) if ok else None
+
+    def __iter__(self):
+        from .. import ops
+        p, bs = self.pools[0], self.batch_size
+        self.epoch = epoch = self._next_epoch
+        self._next_epoch = epoch + 1
+        if self.train or self._eval_plan is None:
+            host = self.plan(epoch)[1:]
+            dev_plan = tuple(t.to(p.device, non_blocking=True) for t in host)
+            if not self.train:
+                self._eval_plan = (host, dev_plan)
+        else:
+            host, dev_plan = self._eval_plan
+        which, order = host[0].tolist(), host[1].tolist()
+        src, idx, geo, bc = dev_plan
+        for k in range(len(self)):
+            lo, hi = k * bs, (k + 1) * bs
+            static = self._static_out()
+            out = None
+            if static is not None:      # lu is not an input of the step: it gets a tensor of its own
+                out = (static[0], static[1], torch.empty((bs, p.height, p.width), dtype=torch.int64, device=p.device))
+            img, mask, lu, _ = ops.pool_gather_combined(self._sources, src[lo:hi], idx[lo:hi], geo[lo:hi], bc[lo:hi],
+                                                        self.mean, self.std, self.in_channels, self.classes == 2,
+                                                        out=out, err=self._err)
+            dist = distmaps_on_device(mask, self.classes) if self.distmap else None
+            stats = [self.pools[j].stats[i] for j, i in zip(which[lo:hi], order[lo:hi])]
+            yield CombinedBatch((img, mask, dist, lu, stats), self.batch_sizes)
+        flag = int(self._err.item())     # the one read of the epoch
+        if flag:
+            self._err.zero_()
+            raise RuntimeError(f"pool gather: error flag {flag} (1: sample index outside its pool, 2: odd turn of a "
+                               "non-square tile, 4: source outside the pool list); those samples were zero-filled")

@@ -76,7 +76,11 @@ def concat_extra(img, mask, distmap, lu, stats, *, extra):
 
 
 def create_combined_batch(batch: Dict[str, Any]):
-    """reference segmodel.py:43-54: ``{"main": (...), "extra_i": (...)}`` -> concatenated tensors"""
+    """reference segmodel.py:43-54: ``{"main": (...), "extra_i": (...)}`` -> concatenated tensors.  A batch whose parts are
+    already views of one tensor per field (``data.pool.CombinedBatch``) hands those tensors back: nothing to concatenate"""
+    combined = getattr(batch, "combined", None)
+    if combined is not None:
+        return combined
     img, mask, distmap, lu, stats = batch["main"]
     extra = [v for k, v in batch.items() if k.startswith("extra")]
     if extra:

@@ -931,6 +931,70 @@ def pool_gather_batch(images, masks, lu, sums, idx, geo, bc, mean, std, c_dst, m
     return img, mask, lu_out, err
 
 
+def pool_gather_combined(sources, src, idx, geo, bc, mean, std, c_dst, merge_above=False, out=None, err=None):
+    """One batch out of several device-resident pools in one launch (``dt_pool_gather_combined``, csrc/pool.hip).
+    sources: a list of ``(images, masks, lu, sums)`` tensor tuples as ``pool_gather_batch`` takes them, all of one tile
+    size (lu: None in every source or in none); slot b is sample ``idx[b]`` of ``sources[src[b]]``: src, idx int32 [B], geo
+    int32 [B,2], bc fp32 [B,2].  Returns what ``pool_gather_batch`` returns, with its arithmetic bit for bit.  A source
+    number outside the list sets bit 4 of ``err``, an index outside its source bit 1, an odd turn of a non-square tile bit
+    2; those slots are zeros."""
+    if not 1 <= len(sources) <= _lib.POOL_MAX_SOURCES:
+        raise RuntimeError(f"pool_gather_combined: 1 .. {_lib.POOL_MAX_SOURCES} sources, not {len(sources)}")
+    sources = [tuple(t) for t in sources]
+    if any(len(t) != 4 for t in sources):
+        raise RuntimeError("pool_gather_combined: a source is (images, masks, lu, sums)")
+    with_lu = sources[0][2] is not None
+    _gpu(src, idx, geo, bc, *(x for t in sources for x in t))
+    dev = sources[0][0].device
+    H, W = sources[0][0].shape[1:3] if sources[0][0].dim() == 4 else (0, 0)
+    table = (_lib.PoolSource * len(sources))()
+    for j, (images, masks, lu, sums) in enumerate(sources):
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 4 or not images.is_contiguous():
+            raise RuntimeError(f"pool_gather_combined: source {j}: images must be contiguous uint8 [N,H,W,4]")
+        N = images.shape[0]
+        if tuple(images.shape[1:3]) != (H, W):
+            raise RuntimeError(f"pool_gather_combined: source {j} holds {images.shape[1]}x{images.shape[2]} tiles, "
+                               f"source 0 {H}x{W}")
+        if (lu is not None) != with_lu:
+            raise RuntimeError("pool_gather_combined: lu in every source or in none")
+        for name, t in (("masks", masks), ("lu", lu)):
+            if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != (N, H, W) or not t.is_contiguous()):
+                raise RuntimeError(f"pool_gather_combined: source {j}: {name} must be contiguous uint8 [N,H,W]")
+        if sums.dtype != torch.int64 or tuple(sums.shape) != (N,) or not sums.is_contiguous():
+            raise RuntimeError(f"pool_gather_combined: source {j}: sums must be contiguous int64 [N]")
+        if any(t is not None and t.device != dev for t in (images, masks, lu, sums)):
+            raise RuntimeError(f"pool_gather_combined: source {j} is not on {dev}")
+        table[j] = _lib.PoolSource(_p(images), _p(masks), _p(lu), _p(sums), N)
+    B = idx.shape[0]
+    if (idx.dtype != torch.int32 or idx.dim() != 1 or src.dtype != torch.int32 or tuple(src.shape) != (B,)
+            or geo.dtype != torch.int32 or tuple(geo.shape) != (B, 2) or bc.dtype != torch.float32
+            or tuple(bc.shape) != (B, 2)
+            or not (src.is_contiguous() and idx.is_contiguous() and geo.is_contiguous() and bc.is_contiguous())):
+        raise RuntimeError("pool_gather_combined: src and idx must be int32 [B], geo int32 [B,2] and bc float32 [B,2], "
+                           "contiguous")
+    if any(t.device != dev for t in (src, idx, geo, bc)):
+        raise RuntimeError(f"pool_gather_combined: src, idx, geo and bc must be on {dev}")
+    if out is None:
+        out = (torch.empty((B, c_dst, H, W), dtype=torch.float32, device=dev),
+               torch.empty((B, H, W), dtype=torch.int64, device=dev),
+               torch.empty((B, H, W), dtype=torch.int64, device=dev) if with_lu else None)
+    img, mask, lu_out = out
+    for name, t, shape, dt in (("img", img, (B, c_dst, H, W), torch.float32), ("mask", mask, (B, H, W), torch.int64),
+                               ("lu", lu_out, (B, H, W), torch.int64)):
+        if (t is None) != (name == "lu" and not with_lu):
+            raise RuntimeError("pool_gather_combined: out needs img and mask, and lu exactly when the pools have one")
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev):
+            raise RuntimeError(f"pool_gather_combined: out {name} must be contiguous {dt} {list(shape)} on {dev}")
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    m = (C.c_float * c_dst)(*[float(v) for v in mean[:c_dst]])
+    s = (C.c_float * c_dst)(*[float(v) for v in std[:c_dst]])
+    _lib.check(_lib.load().dt_pool_gather_combined(table, len(sources), _p(src), _p(idx), _p(geo), _p(bc), _p(img),
+                                                   _p(mask), _p(lu_out), _p(err), B, H, W, c_dst,
+                                                   int(bool(merge_above)), m, s, _st()), "dt_pool_gather_combined")
+    return img, mask, lu_out, err
+
+
 def ensemble_vote(maps_u8: torch.Tensor, K: int, dtype: str = "int64"):
     """uint8 class maps [M, ...] of M models -> per-pixel mode [...] (ties -> smallest class, torch.mode);
     returns (map, err flag).  deployment/inference.py:65-116."""

@@ -291,6 +291,27 @@ int dt_pool_gather_batch(const uint8_t* images, const uint8_t* masks, const uint
                          int64_t* lu_out, int32_t* err_flag, int64_t N, int B, int H, int W, int Cdst, int merge_above,
                          const float* mean, const float* std, void* stream);
 
+/* One batch out of SEVERAL pools in one launch (the reference's main + extra shard sets, data/deadtreedata.py:348-395):
+ * sources is a HOST array of n_sources (1 .. DT_POOL_MAX_SOURCES) pools laid out as dt_pool_gather_batch takes them, all
+ * of one tile size H x W; slot b < B reads sample idx[b] of source src[b] (both int32 [B] on the device) with the
+ * arithmetic, pixel map and stores of dt_pool_gather_batch, bit for bit.  lu_out non-NULL requires lu in every source;
+ * with lu_out NULL the sources' lu are not read.  src[b] outside [0, n_sources) ORs DT_POOL_ERR_SOURCE into err_flag[0],
+ * idx[b] outside [0, sources[src[b]].n) DT_POOL_ERR_INDEX, an odd turn while H != W DT_POOL_ERR_TURN; such a slot reads
+ * nothing and is written as zeros.  The table travels as a kernel argument: no copy, no scratch memory. */
+#define DT_POOL_MAX_SOURCES 8
+#define DT_POOL_ERR_SOURCE 4
+typedef struct dt_pool_source {
+  const uint8_t* images;
+  const uint8_t* masks;
+  const uint8_t* lu;
+  const uint64_t* sums;
+  int64_t n;
+} dt_pool_source;
+int dt_pool_gather_combined(const dt_pool_source* sources, int n_sources, const int32_t* src, const int32_t* idx,
+                            const int32_t* geo, const float* bc, float* img_out, int64_t* mask_out, int64_t* lu_out,
+                            int32_t* err_flag, int B, int H, int W, int Cdst, int merge_above, const float* mean,
+                            const float* std, void* stream);
+
 /* Data gradient of a 3x3 stride-1 layer with the BatchNorm-backward REDUCTION of the layer it feeds fused into the
  * epilogue (instead of a separate dt_bn_bwd_reduce pass over the tensor it has just written): out0 = conv(src0, w)
  * like dt_conv2d (no concat / split / accumulate / upsample), and red[2][P][Cout] (P = dt_conv2d_stat_rows(desc))
