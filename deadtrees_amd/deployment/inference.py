@@ -57,6 +57,11 @@ class PyTorchInference(Inference):
         self._channels = model.in_channels
         self._model = model.model
 
+    @property
+    def classes(self):
+        """the model's class count (the K of the raster statistics), like the ensemble's"""
+        return self._model.spec.classes
+
     def run(self, input_tensor, device: str = "cuda"):
         if not isinstance(input_tensor, torch.Tensor):
             raise TypeError("no pytorch tensor provided")

@@ -235,6 +235,17 @@ class Tiler:
         """the merged class map cropped to the raster size (what ``write_file`` stores)"""
         return self._outdata[0:self._tile_info.size[0], 0:self._tile_info.size[1]]
 
+    def stats(self, zones=None, classes: int = 3, n_zones: Optional[int] = None):
+        """``RasterStats`` of ``result`` (``stats.zonal_counts_host``): what ``infer_tile(..., stats=True)`` returns, for a
+        caller of the reference's own ``get_batches`` / ``put_batches`` loop.  ``zones``: uint8 [h, w] on the raster's grid
+        (``n_zones`` defaults to ``zones.max() + 1``); ``classes``: the model's class count"""
+        from .stats import RasterStats, check_zones, zonal_counts_host
+        if self._outdata is None:
+            raise RuntimeError("Tiler: load_file / load_array first")
+        result = self.result
+        zones, Z = check_zones(zones, result.shape, n_zones)
+        return RasterStats(zonal_counts_host(np.ascontiguousarray(result), zones, classes, Z))
+
     def write_file(self, outfile: Union[str, Path]) -> None:
         """reference tiler.py:136-142 (LZW-compressed tiled GeoTIFF through rioxarray)"""
         if self._target is None:
@@ -246,25 +257,33 @@ class Tiler:
 
 def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, rank: int = 0, world: int = 1,
                   device: str = "cuda", tile_shape: Optional[Tuple[int, int]] = None, skip_blank: bool = True,
-                  overlap: int = 0, blend: str = "crop", return_probs: bool = False, tta=None):
+                  overlap: int = 0, blend: str = "crop", return_probs: bool = False, tta=None, stats: bool = False,
+                  zones=None, n_zones: Optional[int] = None):
     """the directory loop of scripts/inference.py:71-115 over in-memory rasters (GeoTIFF I/O needs rioxarray, absent
     here): ``rasters`` yields ``array`` or ``(key, array)``; rank r of ``world`` takes rasters r, r + world, ... (tiles are
     independent: no collective).  Yields ``(key, class_map)`` in input order of the rank's share; rasters whose band 1
     holds only 0 / 255 (``is_valid_tile``, :60-62) are skipped like the reference does — ``(key, None)`` — without a
     forward pass (device reduction over the uploaded raster, ``ops.band_has_data``).  ``overlap`` / ``blend`` /
-    ``return_probs`` / ``tta``: as in ``infer_tile`` (every raster stays on its rank, so overlap needs no exchange)."""
+    ``return_probs`` / ``tta`` / ``stats`` / ``n_zones``: as in ``infer_tile`` (every raster stays on its rank, so overlap
+    needs no exchange); ``zones``: a callable ``key -> uint8 [h, w] array or None``, or a mapping (a missing key is None).
+    The second item of every pair is whatever ``infer_tile`` returned: with ``stats=True`` ``(map, RasterStats)`` — the
+    ``RasterStats`` of a rank's share add up (``+``) to that rank's part of the regional totals."""
+    if zones is not None and not stats:
+        raise ValueError("infer_rasters: zones need stats=True")
     for i, item in enumerate(rasters):
         if i % world != rank:
             continue
         key, arr = item if isinstance(item, tuple) else (i, item)
+        z = None if zones is None else zones(key) if callable(zones) else zones.get(key)
         yield key, infer_tile(inference, arr, subtile=subtile, batch_size=batch_size, device=device, tile_shape=tile_shape,
-                              skip_blank=skip_blank, overlap=overlap, blend=blend, return_probs=return_probs, tta=tta)
+                              skip_blank=skip_blank, overlap=overlap, blend=blend, return_probs=return_probs, tta=tta,
+                              stats=stats, zones=z, n_zones=n_zones)
 
 
 def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size: int = 64, rank: int = 0,
                world: int = 1, device: str = "cuda", group=None, tile_shape: Optional[Tuple[int, int]] = None,
                on_device: Optional[bool] = None, skip_blank: bool = False, overlap: int = 0, blend: str = "crop",
-               return_probs: bool = False, tta=None):
+               return_probs: bool = False, tta=None, stats: bool = False, zones=None, n_zones: Optional[int] = None):
     """whole-tile inference of scripts/inference.py:80-115 on the MI355X path: split -> (uint8 H2D, normalise on the
     device) -> forward + fused argmax -> uint8 D2H -> merge.  With world > 1 the sub-tile batches j = rank (mod world)
     are processed locally and the uint8 class maps are all-gathered (no other collective: tiles are independent).
@@ -280,9 +299,28 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     ``tta`` (``tta_views``: ``"flips"``, ``"d4"`` or (flip, rot) pairs) averages every window's softmax over its views
     before the blend; an ensemble (an inference object with ``members``) votes over its models — ``vote="hard"``: the
     majority of the members' raster maps, ``vote="soft"``: all members add into one accumulator.  Both always take the
-    stitched device path, ``overlap=0`` included (``_infer_tile_multipass``); ``batch_size`` counts forward tiles."""
+    stitched device path, ``overlap=0`` included (``_infer_tile_multipass``); ``batch_size`` counts forward tiles.
+
+    ``stats=True`` returns ``(map, RasterStats)`` (``(map, probs, RasterStats)`` with ``return_probs``; a blank raster under
+    ``skip_blank`` is still None): the class counts of the map (``deployment/stats.py``), K = ``inference.classes``.
+    ``zones``: a uint8 [h, w] array on the raster's grid (forest mask, land use, a previous year's map — the counts are then
+    the year-to-year transition matrix) splits the counts by zone, ``n_zones`` (<= 8) defaults to ``zones.max() + 1``.  On
+    every device path the zones are uploaded next to the raster and ONE ``ops.zonal_counts`` runs on the final device map
+    before its download; the host path (``on_device=False``, ``world > 1``, CPU) counts the merged map with
+    ``zonal_counts_host``.  The map is the one the call without ``stats`` returns."""
     if blend not in ("crop", "average"):
         raise ValueError(f"blend {blend!r}: use 'crop' or 'average'")
+    want_stats = None
+    if not stats:
+        if zones is not None or n_zones is not None:
+            raise ValueError("infer_tile: zones / n_zones need stats=True")
+    else:
+        from .stats import check_zones
+        zones, Z = check_zones(zones, np.shape(arr_chw_u8)[1:], n_zones)
+        K = getattr(inference, "classes", None)
+        if K is None:
+            raise ValueError("infer_tile: stats=True needs an inference object with a `classes` count")
+        want_stats = (zones, int(K), Z)
     members = getattr(inference, "members", None)
     if tta is not None or members is not None:
         views = tta_views(tta)
@@ -298,7 +336,7 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
             raise ValueError("infer_tile: test-time augmentation and ensembles run on the device and need inference objects "
                              "with run_windows")
         return _infer_tile_multipass(inference, models, vote, arr_chw_u8, subtile, overlap, blend, batch_size, device,
-                                     skip_blank, return_probs, None if tta is None else views)
+                                     skip_blank, return_probs, None if tta is None else views, want_stats)
     if overlap:
         _check_overlap(subtile, overlap)
         if world != 1:
@@ -308,7 +346,7 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
         if on_device is False or not hasattr(inference, "run_windows"):
             raise ValueError("infer_tile: overlap stitching runs on the device and needs an inference object with run_windows")
         return _infer_tile_stitched(inference, arr_chw_u8, subtile, overlap, blend, batch_size, device, skip_blank,
-                                    return_probs)
+                                    return_probs, want_stats)
     if return_probs:
         raise ValueError("infer_tile: return_probs needs overlap > 0 and blend='average'")
     if tile_shape is None:
@@ -323,7 +361,8 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     if on_device:
         if world != 1:
             raise ValueError("infer_tile: the on-device split / merge is the single-rank form")
-        return _infer_tile_on_device(inference, arr_chw_u8, subtile, batch_size, device, tile_shape, skip_blank)
+        return _infer_tile_on_device(inference, arr_chw_u8, subtile, batch_size, device, tile_shape, skip_blank,
+                                     want_stats)
     if skip_blank and bool(np.isin(arr_chw_u8[0], [0, 255]).all()):    # scripts/inference.py:60-62 is_valid_tile
         return None
     t = Tiler(tile_shape=tile_shape, subtile_shape=(subtile, subtile))
@@ -344,11 +383,38 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
             for j, o in lst:
                 outs[j] = o
     t.put_batches(np.concatenate(outs, axis=0))
+    if want_stats is not None:
+        return t.result, t.stats(*want_stats)
     return t.result
 
 
+def _upload_zones(want_stats, device):
+    """the zones map of a ``stats=True`` call on the device (None without one), uploaded next to the raster"""
+    if want_stats is None or want_stats[0] is None:
+        return None
+    return torch.from_numpy(np.ascontiguousarray(want_stats[0])).to(device, non_blocking=True)
+
+
+def _download(out: torch.Tensor, probs: Optional[torch.Tensor], want_stats, zones_dev):
+    """the end of every device path: the D2H copy of the final map ``out`` (uint8 [h, w], contiguous) and of the
+    probabilities when there are any.  With ``want_stats`` = (zones, K, Z) one ``ops.zonal_counts`` is enqueued on ``out``
+    BEFORE the download (no synchronisation of its own); the counts and the flag are read after the map has arrived"""
+    if want_stats is None:
+        return out.cpu().numpy() if probs is None else (out.cpu().numpy(), probs.cpu().numpy())
+    from .. import ops
+    from .stats import RasterStats
+    _, K, Z = want_stats
+    counts, err = ops.zonal_counts(out, zones_dev, K, Z)
+    result = (out.cpu().numpy(),) if probs is None else (out.cpu().numpy(), probs.cpu().numpy())
+    flag = int(err.cpu())
+    if flag:          # cannot happen with checked zones: the map is an argmax over K classes
+        raise RuntimeError(f"infer_tile: raster statistics met a value out of range (flag {flag}: 1 class >= {K}, "
+                           f"2 zone >= {Z})")
+    return result + (RasterStats(counts.cpu().numpy()),)
+
+
 def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch_size: int, device: str,
-                          tile_shape: Tuple[int, int], skip_blank: bool = False) -> Optional[np.ndarray]:
+                          tile_shape: Tuple[int, int], skip_blank: bool = False, want_stats=None):
     """single-rank form of ``infer_tile`` with the block split / merge on the device: ONE uint8 H2D copy of the raster, the
     sub-tiles of ``Tiler.get_batches`` (same ones, same row-major order: the [0:ceil(h/d), 0:ceil(w/d)] blocks of the
     zero-padded tile, reference tiler.py:121-134 + utils/data_handling.py:9-20) as a strided view -> NHWC uint8 batches
@@ -364,6 +430,7 @@ def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch
     if 0 < nch < C:                 # band planes the network never reads (N of an RGBN raster under an RGB model) stay on the host
         arr_chw_u8, C = arr_chw_u8[:nch], nch
     x = torch.from_numpy(np.ascontiguousarray(arr_chw_u8)).to(device, non_blocking=True)
+    zones_dev = _upload_zones(want_stats, device)
     if skip_blank:
         from .. import ops
         if int(ops.band_has_data(x[0])) == 0:       # is_valid_tile on the uploaded raster: nothing but 0 / 255 in band 1
@@ -380,11 +447,11 @@ def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch
         outs = [inference.run_u8(blocks[j:j + batch_size], device=device) for j in range(0, nby * nbx, batch_size)]
     maps = (outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)).to(torch.uint8)
     merged = maps.view(nby, nbx, d, d).permute(0, 2, 1, 3).reshape(nby * d, nbx * d)
-    return merged[:h, :w].contiguous().cpu().numpy()
+    return _download(merged[:h, :w].contiguous(), None, want_stats, zones_dev)
 
 
 def _infer_tile_stitched(inference, arr_chw_u8: np.ndarray, d: int, overlap: int, blend: str, batch_size: int, device: str,
-                         skip_blank: bool = False, return_probs: bool = False):
+                         skip_blank: bool = False, return_probs: bool = False, want_stats=None):
     """``infer_tile`` with overlapping windows: ONE uint8 H2D copy of the raster, per batch of windows one gather
     (``dt_window_normalize_u8``) + forward + one stitch kernel into a raster-sized buffer in HBM, ONE uint8 D2H copy of the
     map (plus the fp32 probabilities when asked for).  Batches run in ascending window order, which is what makes the
@@ -398,6 +465,7 @@ def _infer_tile_stitched(inference, arr_chw_u8: np.ndarray, d: int, overlap: int
     if 0 < nch < C:                 # band planes the network never reads stay on the host
         arr_chw_u8, C = arr_chw_u8[:nch], nch
     x = torch.from_numpy(np.ascontiguousarray(arr_chw_u8)).to(device, non_blocking=True)
+    zones_dev = _upload_zones(want_stats, device)
     if skip_blank and int(ops.band_has_data(x[0])) == 0:
         return None
     n = ny * nx
@@ -405,7 +473,7 @@ def _infer_tile_stitched(inference, arr_chw_u8: np.ndarray, d: int, overlap: int
         out = torch.empty((h, w), dtype=torch.uint8, device=x.device)      # the kept regions tile it: every byte is written
         for j in range(0, n, batch_size):
             ops.stitch_classes(inference.run_windows(x, d, overlap, j, min(batch_size, n - j), want="classes"), out, overlap, j)
-        return out.cpu().numpy()
+        return _download(out, None, want_stats, zones_dev)
     acc = None
     for j in range(0, n, batch_size):
         logits = inference.run_windows(x, d, overlap, j, min(batch_size, n - j), want="logits")
@@ -414,12 +482,12 @@ def _infer_tile_stitched(inference, arr_chw_u8: np.ndarray, d: int, overlap: int
         ops.stitch_accumulate(logits, acc, overlap, j)
     if return_probs:
         classes, probs = ops.stitch_finalize(acc, want_probs=True)
-        return classes.cpu().numpy(), probs.cpu().numpy()
-    return ops.stitch_finalize(acc).cpu().numpy()
+        return _download(classes, probs, want_stats, zones_dev)
+    return _download(ops.stitch_finalize(acc), None, want_stats, zones_dev)
 
 
 def _infer_tile_multipass(inference, models, vote: Optional[str], arr_chw_u8: np.ndarray, d: int, overlap: int, blend: str,
-                          batch_size: int, device: str, skip_blank: bool, return_probs: bool, views):
+                          batch_size: int, device: str, skip_blank: bool, return_probs: bool, views, want_stats=None):
     """``infer_tile`` with test-time augmentation (``views``: canonical pairs, or None for the plain window) and / or an
     ensemble (``models``; ``vote`` None for a single model).  One uint8 H2D copy of the raster; per model and batch of
     windows one (views) gather + forward + one stitch kernel; one uint8 D2H copy of the map.
@@ -439,6 +507,7 @@ def _infer_tile_multipass(inference, models, vote: Optional[str], arr_chw_u8: np
     if 0 < nch < C:                 # band planes the network never reads stay on the host
         arr_chw_u8, C = arr_chw_u8[:nch], nch
     x = torch.from_numpy(np.ascontiguousarray(arr_chw_u8)).to(device, non_blocking=True)
+    zones_dev = _upload_zones(want_stats, device)
     if skip_blank and int(ops.band_has_data(x[0])) == 0:
         return None
     T = len(views) if views is not None else 1
@@ -468,15 +537,15 @@ def _infer_tile_multipass(inference, models, vote: Optional[str], arr_chw_u8: np
     if vote == "hard":
         maps = torch.stack([class_map(m) for m in models], dim=0)
         if len(models) == 1:
-            return maps[0].cpu().numpy()
+            return _download(maps[0], None, want_stats, zones_dev)
         out, _ = ops.ensemble_vote(maps, int(inference.classes), dtype="uint8")
-        return out.cpu().numpy()
+        return _download(out, None, want_stats, zones_dev)
     if vote is None and not return_probs:
-        return class_map(models[0]).cpu().numpy()
+        return _download(class_map(models[0]), None, want_stats, zones_dev)
     acc = None
     for m in models:
         acc = accumulate(m, acc)
     if return_probs:
         classes, probs = ops.stitch_finalize(acc, want_probs=True)
-        return classes.cpu().numpy(), probs.cpu().numpy()
-    return ops.stitch_finalize(acc).cpu().numpy()
+        return _download(classes, probs, want_stats, zones_dev)
+    return _download(ops.stitch_finalize(acc), None, want_stats, zones_dev)

@@ -1011,6 +1011,36 @@ def ensemble_vote(maps_u8: torch.Tensor, K: int, dtype: str = "int64"):
     return (out64 if out64 is not None else out8), err
 
 
+def zonal_counts(classes_u8: torch.Tensor, zones_u8: torch.Tensor = None, K: int = 3, Z: int = 1, counts=None, err=None):
+    """class counts per zone of a uint8 class map on the device (``dt_zonal_counts_u8``): counts int64 [Z,K] (+=),
+    ``counts[z, c]`` = pixels with zone z and class c; ``zones_u8`` None: every pixel is zone 0 and Z must be 1.  Any shape
+    (``zones_u8`` the same one); a non-contiguous view is made contiguous, a contiguous one is read where it lies, whatever
+    its storage offset.  ``counts`` / ``err`` (int32 [1]) are allocated zeroed when not given and accumulated into
+    otherwise.  No host synchronisation: a class >= K ORs 1 into ``err``, a zone >= Z ORs 2, and such a pixel enters no
+    count.  Returns (counts, err)."""
+    _gpu(classes_u8, zones_u8, counts, err)
+    if classes_u8.dtype != torch.uint8 or (zones_u8 is not None and zones_u8.dtype != torch.uint8):
+        raise RuntimeError("zonal_counts: classes and zones must be uint8")
+    if zones_u8 is not None and (tuple(zones_u8.shape) != tuple(classes_u8.shape) or zones_u8.device != classes_u8.device):
+        raise RuntimeError(f"zonal_counts: classes {tuple(classes_u8.shape)} and zones {tuple(zones_u8.shape)} must have "
+                           "the same shape and device")
+    K, Z = int(K), int(Z)
+    dev = classes_u8.device
+    if counts is None:
+        counts = torch.zeros((max(Z, 0), max(K, 0)), dtype=torch.int64, device=dev)
+    elif counts.dtype != torch.int64 or tuple(counts.shape) != (Z, K) or counts.device != dev or not counts.is_contiguous():
+        raise RuntimeError(f"zonal_counts: counts must be contiguous int64 [{Z},{K}] on {dev}")
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif err.dtype != torch.int32 or tuple(err.shape) != (1,) or err.device != dev:
+        raise RuntimeError(f"zonal_counts: err must be int32 [1] on {dev}")
+    classes_u8 = classes_u8.contiguous()
+    zones_u8 = None if zones_u8 is None else zones_u8.contiguous()
+    _lib.check(_lib.load().dt_zonal_counts_u8(_p(classes_u8), _p(zones_u8), classes_u8.numel(), K, Z, _p(counts), _p(err),
+                                              _st()), "dt_zonal_counts_u8")
+    return counts, err
+
+
 def signed_distmap(labels: torch.Tensor, K: int):
     """int64 labels [B,H,W] -> (fp32 distance maps [B,K,H,W], err flag) — the boundary-loss maps of
     loss/losses.py:159-178 as attached by data/deadtreedata.py:182-185, computed exactly on the device."""

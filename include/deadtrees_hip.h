@@ -446,6 +446,15 @@ int dt_eval_accumulate(const float* parts, double weight, double* epoch, void* s
 int dt_ensemble_vote(const uint8_t* maps, int M, int64_t n, int K, uint8_t* out_u8, int64_t* out_i64,
                      int32_t* err_flag, void* stream);
 
+/* Raster statistics (scripts/computestats_inference.py, scripts/aggregate_results.py, deployment/server.py:112): class
+ * counts per zone of a uint8 class map in device memory.  counts int64 [Z][K] (+=, as dt_confusion_matrix: one buffer
+ * can collect many rasters): counts[z][c] += the number of pixels i < n with zones[i] == z and classes[i] == c.  zones
+ * may be NULL: Z must then be 1 and every pixel is zone 0.  2 <= K <= 8, 1 <= Z <= 8, n >= 1; any n and any byte
+ * alignment of either pointer (the two may differ).  A class >= K ORs 1 into err_flag[0], a zone >= Z ORs 2; such a
+ * pixel enters no count, all others are counted.  Integer arithmetic only: exact and independent of the order. */
+int dt_zonal_counts_u8(const uint8_t* classes, const uint8_t* zones, int64_t n, int K, int Z, int64_t* counts,
+                       int32_t* err_flag, void* stream);
+
 /* Signed Euclidean distance maps of the boundary loss, computed on the device in place of the
  * loader's scipy pass: data/deadtreedata.py:182-185 -> loss/losses.py:159-178 one_hot2dist(resolution=[1,1]).
  * labels int64 [B,H,W] -> dist fp32 [B,K,H,W]; per class: floor(edt to the class) outside it, 1 - floor(edt to the
