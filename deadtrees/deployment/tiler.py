@@ -2,3 +2,4 @@
 from deadtrees_amd.deployment.tiler import TileInfo, Tiler, divisible_without_remainder, inspect_tile  # noqa: F401
 from deadtrees_amd.deployment.tiler import blend_ramp, window_grid  # noqa: F401  (overlap-stitch geometry)
 from deadtrees_amd.deployment.tiler import tta_views  # noqa: F401  (test-time augmentation views)
+from deadtrees_amd.deployment.tiler import PatchConfig, PatchTable  # noqa: F401  (dead-tree patches of a map)

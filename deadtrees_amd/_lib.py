@@ -163,6 +163,11 @@ SIGNATURES = {
     "dt_weight_images_bf16_all": (C.c_int, [c_f, c_f, c_f, c_f, c_f, c_f, C.c_int, C.c_int, c_f]),
     "dt_ensemble_vote": (C.c_int, [c_f, C.c_int, I64, C.c_int, c_f, c_f, c_f, c_f]),
     "dt_zonal_counts_u8": (C.c_int, [c_f, c_f, I64, C.c_int, C.c_int, c_f, c_f, c_f]),
+    "dt_patch_tile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dt_label_patches_u8": (C.c_int, [c_f, C.c_int, C.c_int, C.c_int, C.c_int, c_f, c_f, c_f]),
+    "dt_patch_areas": (C.c_int, [c_f, C.c_int, C.c_int, c_f, c_f]),
+    "dt_sieve_patches_u8": (C.c_int, [c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, c_f]),
+    "dt_patch_measure": (C.c_int, [c_f, c_f, C.c_int, C.c_int, c_f, C.c_int, c_f, c_f, c_f, c_f, c_f]),
     "dt_signed_distmap_workspace": (I64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "dt_signed_distmap": (C.c_int, [c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, c_f]),
     "dt_conv2d_bf16_stat_rows": (C.c_int, [_P]),

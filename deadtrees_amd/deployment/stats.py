@@ -62,9 +62,11 @@ def zonal_counts_host(classes, zones=None, K: int = 3, Z: int = 1) -> np.ndarray
 
 class RasterStats:
     """the counts table of one raster (or of a sum of rasters) and the reference's figures read off it.  ``counts`` int64
-    [Z, K]: rows zones, columns classes; class 0 is background, classes >= 1 are dead trees"""
+    [Z, K]: rows zones, columns classes; class 0 is background, classes >= 1 are dead trees.  ``patches``: the raster's
+    ``PatchTable`` (``deployment/patches.py``) when one was asked for, else None; a sum of rasters has none, because the
+    tables of different rasters do not share a grid"""
 
-    def __init__(self, counts, pixel_area_m2: float = PIXEL_AREA_M2):
+    def __init__(self, counts, pixel_area_m2: float = PIXEL_AREA_M2, patches=None):
         counts = np.array(counts, dtype=np.int64)
         if counts.ndim != 2 or counts.shape[0] < 1 or counts.shape[1] < 2:
             raise ValueError(f"RasterStats: counts must be [Z >= 1, K >= 2], got shape {counts.shape}")
@@ -73,6 +75,15 @@ class RasterStats:
         counts.setflags(write=False)
         self._counts = counts
         self.pixel_area_m2 = float(pixel_area_m2)
+        if patches is not None:
+            from .patches import PatchTable
+            if not isinstance(patches, PatchTable):
+                raise ValueError(f"RasterStats: patches must be a PatchTable or None, got {type(patches).__name__}")
+        self._patches = patches
+
+    @property
+    def patches(self):
+        return self._patches
 
     @property
     def counts(self) -> np.ndarray:
@@ -117,13 +128,17 @@ class RasterStats:
     def __eq__(self, other) -> bool:
         if not isinstance(other, RasterStats):
             return NotImplemented
+        if (self._patches is None) != (other._patches is None):
+            return False
         return (self._counts.shape == other._counts.shape and bool((self._counts == other._counts).all())
-                and self.pixel_area_m2 == other.pixel_area_m2)
+                and self.pixel_area_m2 == other.pixel_area_m2
+                and (self._patches is None or self._patches == other._patches))
 
     __hash__ = None
 
     def __repr__(self) -> str:
-        return f"RasterStats(counts={self._counts.tolist()}, pixel_area_m2={self.pixel_area_m2!r})"
+        tail = "" if self._patches is None else f", patches={self._patches!r}"
+        return f"RasterStats(counts={self._counts.tolist()}, pixel_area_m2={self.pixel_area_m2!r}{tail})"
 
 
 def check_zones(zones, shape, n_zones: Optional[int] = None):

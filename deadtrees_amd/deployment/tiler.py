@@ -26,6 +26,8 @@ from typing import List, Optional, Tuple, Union
 import numpy as np
 import torch
 
+from .patches import PatchConfig, PatchTable, check_patches  # noqa: F401  (the ``patches`` argument of infer_tile)
+
 
 def divisible_without_remainder(a, b):
     if b == 0:
@@ -235,16 +237,26 @@ class Tiler:
         """the merged class map cropped to the raster size (what ``write_file`` stores)"""
         return self._outdata[0:self._tile_info.size[0], 0:self._tile_info.size[1]]
 
-    def stats(self, zones=None, classes: int = 3, n_zones: Optional[int] = None):
+    def stats(self, zones=None, classes: int = 3, n_zones: Optional[int] = None, patches=None):
         """``RasterStats`` of ``result`` (``stats.zonal_counts_host``): what ``infer_tile(..., stats=True)`` returns, for a
         caller of the reference's own ``get_batches`` / ``put_batches`` loop.  ``zones``: uint8 [h, w] on the raster's grid
-        (``n_zones`` defaults to ``zones.max() + 1``); ``classes``: the model's class count"""
+        (``n_zones`` defaults to ``zones.max() + 1``); ``classes``: the model's class count.  ``patches`` (True or a
+        ``PatchConfig``): the statistics carry the ``PatchTable`` of the map (``patches.patches_host``); a configuration
+        that sieves changes ``result`` itself, and the counts are those of the sieved map"""
+        from .patches import patches_host
         from .stats import RasterStats, check_zones, zonal_counts_host
         if self._outdata is None:
             raise RuntimeError("Tiler: load_file / load_array first")
+        config = check_patches(patches)
         result = self.result
         zones, Z = check_zones(zones, result.shape, n_zones)
-        return RasterStats(zonal_counts_host(np.ascontiguousarray(result), zones, classes, Z))
+        table = None
+        if config is not None:
+            sieved, table = patches_host(result, classes, config)
+            if config.sieves:
+                self._outdata[0:result.shape[0], 0:result.shape[1]] = sieved
+                result = self.result
+        return RasterStats(zonal_counts_host(np.ascontiguousarray(result), zones, classes, Z), patches=table)
 
     def write_file(self, outfile: Union[str, Path]) -> None:
         """reference tiler.py:136-142 (LZW-compressed tiled GeoTIFF through rioxarray)"""
@@ -258,18 +270,20 @@ class Tiler:
 def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, rank: int = 0, world: int = 1,
                   device: str = "cuda", tile_shape: Optional[Tuple[int, int]] = None, skip_blank: bool = True,
                   overlap: int = 0, blend: str = "crop", return_probs: bool = False, tta=None, stats: bool = False,
-                  zones=None, n_zones: Optional[int] = None):
+                  zones=None, n_zones: Optional[int] = None, patches=None):
     """the directory loop of scripts/inference.py:71-115 over in-memory rasters (GeoTIFF I/O needs rioxarray, absent
     here): ``rasters`` yields ``array`` or ``(key, array)``; rank r of ``world`` takes rasters r, r + world, ... (tiles are
     independent: no collective).  Yields ``(key, class_map)`` in input order of the rank's share; rasters whose band 1
     holds only 0 / 255 (``is_valid_tile``, :60-62) are skipped like the reference does — ``(key, None)`` — without a
     forward pass (device reduction over the uploaded raster, ``ops.band_has_data``).  ``overlap`` / ``blend`` /
-    ``return_probs`` / ``tta`` / ``stats`` / ``n_zones``: as in ``infer_tile`` (every raster stays on its rank, so overlap
+    ``return_probs`` / ``tta`` / ``stats`` / ``n_zones`` / ``patches``: as in ``infer_tile`` (every raster stays on its rank, so overlap
     needs no exchange); ``zones``: a callable ``key -> uint8 [h, w] array or None``, or a mapping (a missing key is None).
     The second item of every pair is whatever ``infer_tile`` returned: with ``stats=True`` ``(map, RasterStats)`` — the
     ``RasterStats`` of a rank's share add up (``+``) to that rank's part of the regional totals."""
     if zones is not None and not stats:
         raise ValueError("infer_rasters: zones need stats=True")
+    if check_patches(patches) is not None and not stats:
+        raise ValueError("infer_rasters: patches need stats=True")
     for i, item in enumerate(rasters):
         if i % world != rank:
             continue
@@ -277,13 +291,14 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
         z = None if zones is None else zones(key) if callable(zones) else zones.get(key)
         yield key, infer_tile(inference, arr, subtile=subtile, batch_size=batch_size, device=device, tile_shape=tile_shape,
                               skip_blank=skip_blank, overlap=overlap, blend=blend, return_probs=return_probs, tta=tta,
-                              stats=stats, zones=z, n_zones=n_zones)
+                              stats=stats, zones=z, n_zones=n_zones, patches=patches)
 
 
 def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size: int = 64, rank: int = 0,
                world: int = 1, device: str = "cuda", group=None, tile_shape: Optional[Tuple[int, int]] = None,
                on_device: Optional[bool] = None, skip_blank: bool = False, overlap: int = 0, blend: str = "crop",
-               return_probs: bool = False, tta=None, stats: bool = False, zones=None, n_zones: Optional[int] = None):
+               return_probs: bool = False, tta=None, stats: bool = False, zones=None, n_zones: Optional[int] = None,
+               patches=None):
     """whole-tile inference of scripts/inference.py:80-115 on the MI355X path: split -> (uint8 H2D, normalise on the
     device) -> forward + fused argmax -> uint8 D2H -> merge.  With world > 1 the sub-tile batches j = rank (mod world)
     are processed locally and the uint8 class maps are all-gathered (no other collective: tiles are independent).
@@ -307,20 +322,31 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     the year-to-year transition matrix) splits the counts by zone, ``n_zones`` (<= 8) defaults to ``zones.max() + 1``.  On
     every device path the zones are uploaded next to the raster and ONE ``ops.zonal_counts`` runs on the final device map
     before its download; the host path (``on_device=False``, ``world > 1``, CPU) counts the merged map with
-    ``zonal_counts_host``.  The map is the one the call without ``stats`` returns."""
+    ``zonal_counts_host``.  The map is the one the call without ``stats`` returns.
+
+    ``patches=True`` or a ``PatchConfig(connectivity=8, min_pixels=0)`` (needs ``stats=True``): the ``RasterStats`` carries
+    the map's ``PatchTable`` as ``.patches`` (``deployment/patches.py``: one row per connected dead-tree patch).  On every
+    device path the final map is labelled, measured and — with ``min_pixels > 1`` — sieved in HBM before the counts and the
+    download (``ops.label_patches`` / ``patch_areas`` / ``sieve_patches`` / ``patch_table``); the host path runs the same
+    contract in numpy / scipy.  With a sieve the returned map is the sieved one and ``counts`` are the counts of the
+    RETURNED map; the probabilities of ``return_probs`` are not touched by the sieve.  With ``min_pixels <= 1`` the map is
+    bit-identical to the call without ``patches``."""
     if blend not in ("crop", "average"):
         raise ValueError(f"blend {blend!r}: use 'crop' or 'average'")
     want_stats = None
+    config = check_patches(patches)
     if not stats:
         if zones is not None or n_zones is not None:
             raise ValueError("infer_tile: zones / n_zones need stats=True")
+        if config is not None:
+            raise ValueError("infer_tile: patches need stats=True")
     else:
         from .stats import check_zones
         zones, Z = check_zones(zones, np.shape(arr_chw_u8)[1:], n_zones)
         K = getattr(inference, "classes", None)
         if K is None:
             raise ValueError("infer_tile: stats=True needs an inference object with a `classes` count")
-        want_stats = (zones, int(K), Z)
+        want_stats = (zones, int(K), Z, config)
     members = getattr(inference, "members", None)
     if tta is not None or members is not None:
         views = tta_views(tta)
@@ -384,7 +410,8 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
                 outs[j] = o
     t.put_batches(np.concatenate(outs, axis=0))
     if want_stats is not None:
-        return t.result, t.stats(*want_stats)
+        st = t.stats(*want_stats)           # before the map is read: a sieve changes it
+        return t.result, st
     return t.result
 
 
@@ -397,20 +424,40 @@ def _upload_zones(want_stats, device):
 
 def _download(out: torch.Tensor, probs: Optional[torch.Tensor], want_stats, zones_dev):
     """the end of every device path: the D2H copy of the final map ``out`` (uint8 [h, w], contiguous) and of the
-    probabilities when there are any.  With ``want_stats`` = (zones, K, Z) one ``ops.zonal_counts`` is enqueued on ``out``
-    BEFORE the download (no synchronisation of its own); the counts and the flag are read after the map has arrived"""
+    probabilities when there are any.  With ``want_stats`` = (zones, K, Z, patch config) one ``ops.zonal_counts`` is enqueued
+    on ``out`` BEFORE the download (no synchronisation of its own); the counts and the flag are read after the map has
+    arrived.  With a patch configuration ``out`` is labelled, its patch areas are taken and — if the configuration sieves —
+    it is sieved IN PLACE, all before the counts; the roots are compacted and measured behind the download (the compaction
+    reads the row count back).  Labels, the area plane (reused as the root -> row plane) and the compaction's flags are
+    the workspace: about 12 bytes per pixel next to the map"""
     if want_stats is None:
         return out.cpu().numpy() if probs is None else (out.cpu().numpy(), probs.cpu().numpy())
     from .. import ops
     from .stats import RasterStats
-    _, K, Z = want_stats
-    counts, err = ops.zonal_counts(out, zones_dev, K, Z)
-    result = (out.cpu().numpy(),) if probs is None else (out.cpu().numpy(), probs.cpu().numpy())
+    _, K, Z, config = want_stats
+    labels = area = table = None
+    err = torch.zeros(1, dtype=torch.int32, device=out.device)
+    if config is not None:
+        labels, _ = ops.label_patches(out, K, config.connectivity, err=err)
+        area = ops.patch_areas(labels)
+        if config.sieves:
+            ops.sieve_patches(out, labels, area, config.min_pixels)
+    counts, _ = ops.zonal_counts(out, zones_dev, K, Z, err=err)
+    host = torch.empty(out.shape, dtype=out.dtype, pin_memory=True) if config is not None else None
+    if host is not None:
+        host.copy_(out, non_blocking=True)                      # enqueued; the table's read-back waits for it
+        table = ops.patch_table(labels, out, area, reuse_area_plane=True)
+        torch.cuda.current_stream(out.device).synchronize()
+        result = (host.numpy(),)
+    else:
+        result = (out.cpu().numpy(),)
+    if probs is not None:
+        result += (probs.cpu().numpy(),)
     flag = int(err.cpu())
     if flag:          # cannot happen with checked zones: the map is an argmax over K classes
         raise RuntimeError(f"infer_tile: raster statistics met a value out of range (flag {flag}: 1 class >= {K}, "
                            f"2 zone >= {Z})")
-    return result + (RasterStats(counts.cpu().numpy()),)
+    return result + (RasterStats(counts.cpu().numpy(), patches=table),)
 
 
 def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch_size: int, device: str,

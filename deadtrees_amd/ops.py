@@ -1041,6 +1041,107 @@ def zonal_counts(classes_u8: torch.Tensor, zones_u8: torch.Tensor = None, K: int
     return counts, err
 
 
+def _patch_tile():
+    th, tw = C.c_int(0), C.c_int(0)
+    _lib.check(_lib.load().dt_patch_tile(C.byref(th), C.byref(tw)), "dt_patch_tile")
+    return th.value, tw.value
+
+
+def __getattr__(name):
+    # PATCH_TILE = (th, tw): the tile of dt_label_patches_u8's local launch, asked of the library on first use
+    if name == "PATCH_TILE":
+        globals()["PATCH_TILE"] = _patch_tile()
+        return globals()["PATCH_TILE"]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def _patch_planes(what, classes_u8=None, **planes):
+    """the argument checks of the patch wrappers: a uint8 [h, w] class map and int32 planes of its shape on its device;
+    returns them contiguous (a contiguous view is read where it lies, whatever its storage offset)"""
+    first = classes_u8 if classes_u8 is not None else next(iter(planes.values()))
+    _gpu(classes_u8, *planes.values())
+    if classes_u8 is not None and classes_u8.dtype != torch.uint8:
+        raise RuntimeError(f"{what}: classes must be uint8")
+    if first.dim() != 2 or first.numel() == 0:
+        raise RuntimeError(f"{what}: expected a non-empty [h, w] map, got shape {tuple(first.shape)}")
+    for name, t in planes.items():
+        if t.dtype != torch.int32 or tuple(t.shape) != tuple(first.shape) or t.device != first.device:
+            raise RuntimeError(f"{what}: {name} must be int32 {list(first.shape)} on {first.device}")
+    return first.shape[0], first.shape[1]
+
+
+def label_patches(classes_u8: torch.Tensor, K: int, connectivity: int = 8, err=None):
+    """patch labels of a uint8 class map [h, w] on the device (``dt_label_patches_u8``, contract in
+    ``deployment/patches.py``): int32 [h, w], 0 on background, elsewhere 1 + the row-major index of the first pixel of the
+    pixel's patch (same class 1 <= c < K, 4- or 8-connected).  A non-contiguous view is made contiguous, a contiguous one
+    is read where it lies.  No host synchronisation: a class >= K ORs 1 into ``err`` (int32 [1], allocated zeroed when not
+    given) and is background.  Returns (labels, err)."""
+    h, w = _patch_planes("label_patches", classes_u8)
+    dev = classes_u8.device
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif err.dtype != torch.int32 or tuple(err.shape) != (1,) or err.device != dev:
+        raise RuntimeError(f"label_patches: err must be int32 [1] on {dev}")
+    labels = torch.empty((h, w), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().dt_label_patches_u8(_p(classes_u8.contiguous()), h, w, int(K), int(connectivity), _p(labels),
+                                               _p(err), _st()), "dt_label_patches_u8")
+    return labels, err
+
+
+def patch_areas(labels: torch.Tensor) -> torch.Tensor:
+    """int32 [h * w]: the pixel count of every patch at its root's index (label - 1), 0 elsewhere (``dt_patch_areas``)"""
+    h, w = _patch_planes("patch_areas", labels=labels)
+    area = torch.zeros(h * w, dtype=torch.int32, device=labels.device)
+    _lib.check(_lib.load().dt_patch_areas(_p(labels.contiguous()), h, w, _p(area), _st()), "dt_patch_areas")
+    return area
+
+
+def sieve_patches(classes_u8: torch.Tensor, labels: torch.Tensor, area_plane: torch.Tensor, min_pixels: int) -> None:
+    """IN PLACE (``dt_sieve_patches_u8``): the pixels of every patch with fewer than ``min_pixels`` pixels become class 0 /
+    label 0 and the root's entry of ``area_plane`` becomes 0; a removed patch is not filled from its neighbours.  The three
+    tensors are written where they lie, so they must be contiguous; ``min_pixels <= 1`` changes nothing"""
+    h, w = _patch_planes("sieve_patches", classes_u8, labels=labels)
+    _gpu(area_plane)
+    if (area_plane.dtype != torch.int32 or area_plane.numel() != h * w or area_plane.device != labels.device
+            or not area_plane.is_contiguous()):
+        raise RuntimeError(f"sieve_patches: area_plane must be contiguous int32 [{h * w}] on {labels.device}")
+    if not (classes_u8.is_contiguous() and labels.is_contiguous()):
+        raise RuntimeError("sieve_patches: works in place and needs a contiguous class map and label plane")
+    _lib.check(_lib.load().dt_sieve_patches_u8(_p(classes_u8), _p(labels), _p(area_plane), h, w, int(min_pixels), _st()),
+               "dt_sieve_patches_u8")
+
+
+def patch_table(labels: torch.Tensor, classes_u8: torch.Tensor, area_plane: torch.Tensor = None,
+                reuse_area_plane: bool = False):
+    """the ``PatchTable`` (host arrays) of a label plane and its class map, sieved or not.  ``area_plane``
+    (``patch_areas``; computed here when not given) names the surviving roots — its non-zero entries, which
+    ``torch.nonzero`` compacts in ascending order — and gives the area column; ``dt_patch_measure`` fills class, bounding
+    box and coordinate sums.  The row count is the ONE scalar read back before the table itself.  ``reuse_area_plane=True``
+    turns the caller's ``area_plane`` into the root -> row plane instead of allocating one (its content is lost)."""
+    from .deployment.patches import PatchTable
+    h, w = _patch_planes("patch_table", classes_u8, labels=labels)
+    dev = labels.device
+    if area_plane is None:
+        area_plane, reuse_area_plane = patch_areas(labels), True
+    elif (area_plane.dtype != torch.int32 or area_plane.numel() != h * w or area_plane.device != dev
+          or not area_plane.is_contiguous()):
+        raise RuntimeError(f"patch_table: area_plane must be contiguous int32 [{h * w}] on {dev}")
+    area_plane = area_plane.view(-1)
+    root = torch.nonzero(area_plane).view(-1)                  # int64, ascending; synchronises: n is read here
+    n = int(root.numel())
+    area = area_plane[root].to(torch.int64)
+    cls = torch.empty(n, dtype=torch.uint8, device=dev)
+    bbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    sum_y = torch.empty(n, dtype=torch.int64, device=dev)
+    sum_x = torch.empty(n, dtype=torch.int64, device=dev)
+    if n:
+        dense = area_plane if reuse_area_plane else torch.empty(h * w, dtype=torch.int32, device=dev)
+        dense[root] = torch.arange(n, dtype=torch.int32, device=dev)
+        _lib.check(_lib.load().dt_patch_measure(_p(labels.contiguous()), _p(classes_u8.contiguous()), h, w, _p(dense), n,
+                                                _p(cls), _p(bbox), _p(sum_y), _p(sum_x), _st()), "dt_patch_measure")
+    return PatchTable(*(t.cpu().numpy() for t in (root, cls, area, bbox, sum_y, sum_x)), shape=(h, w))
+
+
 def signed_distmap(labels: torch.Tensor, K: int):
     """int64 labels [B,H,W] -> (fp32 distance maps [B,K,H,W], err flag) — the boundary-loss maps of
     loss/losses.py:159-178 as attached by data/deadtreedata.py:182-185, computed exactly on the device."""

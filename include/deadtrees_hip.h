@@ -455,6 +455,28 @@ int dt_ensemble_vote(const uint8_t* maps, int M, int64_t n, int K, uint8_t* out_
 int dt_zonal_counts_u8(const uint8_t* classes, const uint8_t* zones, int64_t n, int K, int Z, int64_t* counts,
                        int32_t* err_flag, void* stream);
 
+/* Dead-tree patches (deployment/patches.py states the contract): connected components of a uint8 class map [h][w] in
+ * device memory, h * w <= 2^31 - 2.  A patch is a maximal set of pixels of one class c, 1 <= c < K, connected through
+ * 4- or 8-neighbourhoods; class 0 is background.  No entry point synchronises; all integers: exact, order independent.
+ *
+ * dt_label_patches_u8: labels int32 [h][w] (overwritten): 0 on background, elsewhere 1 + min(y * w + x) over the pixel's
+ *   patch.  2 <= K <= 8, connectivity 4 or 8.  A class >= K ORs 1 into err_flag[0] and is background.  Three launches:
+ *   union-find per tile in LDS, lock-free unions across the tile borders, path flattening; dt_patch_tile gives the tile.
+ * dt_patch_areas: area_plane int32 [h * w], ZEROED BY THE CALLER: += the pixel count of every patch at its root's index
+ *   (label - 1); other entries are not touched.
+ * dt_sieve_patches_u8: in place; the pixels of every patch with area < min_pixels become class 0 / label 0 and the root's
+ *   area entry becomes 0 (no fill from the neighbours); min_pixels <= 1 changes nothing.
+ * dt_patch_measure: the table of n patches.  dense_plane int32 [h * w] holds at every root's index the row of that root
+ *   (other entries are not read).  Overwrites cls uint8 [n] (the class), bbox int32 [n][4] (y0, x0, y1, x1, inclusive),
+ *   sum_y / sum_x int64 [n] (sums of the pixels' row / column numbers). */
+int dt_patch_tile(int* th, int* tw);
+int dt_label_patches_u8(const uint8_t* classes, int h, int w, int K, int connectivity, int32_t* labels, int32_t* err_flag,
+                        void* stream);
+int dt_patch_areas(const int32_t* labels, int h, int w, int32_t* area_plane, void* stream);
+int dt_sieve_patches_u8(uint8_t* classes, int32_t* labels, int32_t* area_plane, int h, int w, int min_pixels, void* stream);
+int dt_patch_measure(const int32_t* labels, const uint8_t* classes, int h, int w, const int32_t* dense_plane, int n,
+                     uint8_t* cls, int32_t* bbox, int64_t* sum_y, int64_t* sum_x, void* stream);
+
 /* Signed Euclidean distance maps of the boundary loss, computed on the device in place of the
  * loader's scipy pass: data/deadtreedata.py:182-185 -> loss/losses.py:159-178 one_hot2dist(resolution=[1,1]).
  * labels int64 [B,H,W] -> dist fp32 [B,K,H,W]; per class: floor(edt to the class) outside it, 1 - floor(edt to the
