@@ -18,7 +18,8 @@
 // non-square tile, is written as zeros and raises a bit of err_flag.
 //
 // dt_pool_gather_combined makes the same batch out of several pools (the reference's main + extra shard sets): slot b
-// takes sample idx[b] of pool src[b].  Both kernels share pool_gather_slot, so their arithmetic cannot drift apart.
+// takes sample idx[b] of pool src[b].  There is ONE kernel and one host path: the pools are the rows of a table that
+// travels as a kernel argument, and the single pool of dt_pool_gather_batch is a table of one row read without src.
 #include "common.h"
 #include "views.h"
 
@@ -115,31 +116,20 @@ __device__ __forceinline__ void pool_gather_slot(
   }
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void pool_gather_batch_kernel(
-    const uint32_t* __restrict__ images, const uint8_t* __restrict__ masks, const uint8_t* __restrict__ lu,
-    const unsigned long long* __restrict__ sums, const int32_t* __restrict__ idx, const int32_t* __restrict__ geo,
-    const float* __restrict__ bc, float* __restrict__ img_out, int64_t* __restrict__ mask_out, int64_t* __restrict__ lu_out,
-    int32_t* __restrict__ err_flag, int64_t N, int H, int W, int Cd, int merge_above, f32x4 mean, f32x4 stdv) {
-  const int64_t s = idx[blockIdx.y];
-  pool_gather_slot<VEC>(images, masks, lu, sums, s, (s < 0 || s >= N) ? POOL_ERR_INDEX : 0, geo, bc, img_out, mask_out,
-                        lu_out, err_flag, H, W, Cd, merge_above, mean, stdv);
-}
-
-// The same slot out of one of several pools: src[b] picks a row of the table, which is a kernel argument — the row index is
-// a scalar (blockIdx.y -> one scalar load of src), so the row's four pointers and its n arrive by scalar loads from the
+// Slot b out of row src[b] of the table (row 0 without src: the single pool), which is a kernel argument — the row index
+// is a scalar (blockIdx.y -> one scalar load of src), so the row's four pointers and its n arrive by scalar loads from the
 // kernarg segment: no vector work, no private copy of the table.
 struct pool_table {
   dt_pool_source s[DT_POOL_MAX_SOURCES];
 };
 
 template <bool VEC>
-__global__ __launch_bounds__(256) void pool_gather_combined_kernel(
+__global__ __launch_bounds__(256) void pool_gather_kernel(
     const pool_table tab, const int n_sources, const int32_t* __restrict__ src, const int32_t* __restrict__ idx,
     const int32_t* __restrict__ geo, const float* __restrict__ bc, float* __restrict__ img_out,
     int64_t* __restrict__ mask_out, int64_t* __restrict__ lu_out, int32_t* __restrict__ err_flag, int H, int W, int Cd,
     int merge_above, f32x4 mean, f32x4 stdv) {
-  const int j = src[blockIdx.y];
+  const int j = src ? src[blockIdx.y] : 0;
   const int64_t s = idx[blockIdx.y];
   const bool known = j >= 0 && j < n_sources;
   const dt_pool_source& p = tab.s[known ? j : 0];        // (row 0 always exists; a slot with an unknown source reads nothing)
@@ -148,54 +138,22 @@ __global__ __launch_bounds__(256) void pool_gather_combined_kernel(
                         img_out, mask_out, lu_out, err_flag, H, W, Cd, merge_above, mean, stdv);
 }
 
-extern "C" int dt_pool_gather_batch(const uint8_t* images, const uint8_t* masks, const uint8_t* lu, const uint64_t* sums,
-                                    const int32_t* idx, const int32_t* geo, const float* bc, float* img_out,
-                                    int64_t* mask_out, int64_t* lu_out, int32_t* err_flag, int64_t N, int B, int H, int W,
-                                    int Cdst, int merge_above, const float* mean, const float* stdv, void* stream) {
-  DT_REQUIRE(images && masks && sums && idx && geo && bc && img_out && mask_out && err_flag && mean && stdv,
-             "pool_gather_batch: null argument");
-  DT_REQUIRE((lu == nullptr) == (lu_out == nullptr), "pool_gather_batch: lu and lu_out go together");
-  DT_REQUIRE(N > 0 && B > 0 && H > 0 && W > 0 && Cdst > 0 && Cdst <= 4, "pool_gather_batch: bad sizes");
-  DT_REQUIRE(B <= 65535, "pool_gather_batch: B must be <= 65535");
-  DT_REQUIRE(((uintptr_t)images & 3) == 0, "pool_gather_batch: the image pool must be 4-byte aligned");
-  f32x4 m = {0, 0, 0, 0}, s = {1, 1, 1, 1};
-  for (int c = 0; c < Cdst; ++c) {
-    m[c] = mean[c];
-    s[c] = stdv[c];
-  }
-  const bool vec = (W & 3) == 0 && (((uintptr_t)img_out | (uintptr_t)mask_out | (uintptr_t)lu_out) & 15) == 0;
-  int gx = dt_cdiv((int64_t)H * ((W + 3) / 4), 256);
-  if (gx > 1024) gx = 1024;
-  const dim3 grid(gx, B), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (vec)
-    hipLaunchKernelGGL(pool_gather_batch_kernel<true>, grid, block, 0, st, (const uint32_t*)images, masks, lu,
-                       (const unsigned long long*)sums, idx, geo, bc, img_out, mask_out, lu_out, err_flag, N, H, W, Cdst,
-                       merge_above, m, s);
-  else
-    hipLaunchKernelGGL(pool_gather_batch_kernel<false>, grid, block, 0, st, (const uint32_t*)images, masks, lu,
-                       (const unsigned long long*)sums, idx, geo, bc, img_out, mask_out, lu_out, err_flag, N, H, W, Cdst,
-                       merge_above, m, s);
-  DT_LAUNCH_CHECK();
-  return DT_OK;
-}
-
-extern "C" int dt_pool_gather_combined(const dt_pool_source* sources, int n_sources, const int32_t* src, const int32_t* idx,
-                                       const int32_t* geo, const float* bc, float* img_out, int64_t* mask_out,
-                                       int64_t* lu_out, int32_t* err_flag, int B, int H, int W, int Cdst, int merge_above,
-                                       const float* mean, const float* stdv, void* stream) {
-  DT_REQUIRE(sources && src && idx && geo && bc && img_out && mask_out && err_flag && mean && stdv,
-             "pool_gather_combined: null argument");
-  DT_REQUIRE(n_sources >= 1 && n_sources <= DT_POOL_MAX_SOURCES, "pool_gather_combined: 1 .. %d sources",
-             DT_POOL_MAX_SOURCES);
-  DT_REQUIRE(B > 0 && H > 0 && W > 0 && Cdst > 0 && Cdst <= 4, "pool_gather_combined: bad sizes");
-  DT_REQUIRE(B <= 65535, "pool_gather_combined: B must be <= 65535");
+// Everything both entries do; who: the entry's name, for the messages.  src may be NULL with one source.
+static int pool_gather_launch(const char* who, const dt_pool_source* sources, int n_sources, const int32_t* src,
+                              const int32_t* idx, const int32_t* geo, const float* bc, float* img_out, int64_t* mask_out,
+                              int64_t* lu_out, int32_t* err_flag, int B, int H, int W, int Cdst, int merge_above,
+                              const float* mean, const float* stdv, void* stream) {
+  DT_REQUIRE(sources && idx && geo && bc && img_out && mask_out && err_flag && mean && stdv, "%s: null argument", who);
+  DT_REQUIRE(n_sources >= 1 && n_sources <= DT_POOL_MAX_SOURCES, "%s: 1 .. %d sources", who, DT_POOL_MAX_SOURCES);
+  DT_REQUIRE(src || n_sources == 1, "%s: null argument (src may be NULL with one source only)", who);
+  DT_REQUIRE(B > 0 && H > 0 && W > 0 && Cdst > 0 && Cdst <= 4, "%s: bad sizes", who);
+  DT_REQUIRE(B <= 65535, "%s: B must be <= 65535", who);
   pool_table tab = {};
   for (int j = 0; j < n_sources; ++j) {
     const dt_pool_source& p = sources[j];
-    DT_REQUIRE(p.images && p.masks && p.sums && p.n > 0, "pool_gather_combined: source %d: null array or no samples", j);
-    DT_REQUIRE(!lu_out || p.lu, "pool_gather_combined: lu_out needs lu in every source (source %d has none)", j);
-    DT_REQUIRE(((uintptr_t)p.images & 3) == 0, "pool_gather_combined: the image pool must be 4-byte aligned (source %d)", j);
+    DT_REQUIRE(p.images && p.masks && p.sums && p.n > 0, "%s: source %d: null array or no samples", who, j);
+    DT_REQUIRE(!lu_out || p.lu, "%s: lu_out needs lu in every source (source %d has none)", who, j);
+    DT_REQUIRE(((uintptr_t)p.images & 3) == 0, "%s: the image pool must be 4-byte aligned (source %d)", who, j);
     tab.s[j] = p;
     if (!lu_out) tab.s[j].lu = nullptr;
   }
@@ -210,11 +168,30 @@ extern "C" int dt_pool_gather_combined(const dt_pool_source* sources, int n_sour
   const dim3 grid(gx, B), block(256);
   hipStream_t st = (hipStream_t)stream;
   if (vec)
-    hipLaunchKernelGGL(pool_gather_combined_kernel<true>, grid, block, 0, st, tab, n_sources, src, idx, geo, bc, img_out,
-                       mask_out, lu_out, err_flag, H, W, Cdst, merge_above, m, s);
+    hipLaunchKernelGGL(pool_gather_kernel<true>, grid, block, 0, st, tab, n_sources, src, idx, geo, bc, img_out, mask_out,
+                       lu_out, err_flag, H, W, Cdst, merge_above, m, s);
   else
-    hipLaunchKernelGGL(pool_gather_combined_kernel<false>, grid, block, 0, st, tab, n_sources, src, idx, geo, bc, img_out,
-                       mask_out, lu_out, err_flag, H, W, Cdst, merge_above, m, s);
+    hipLaunchKernelGGL(pool_gather_kernel<false>, grid, block, 0, st, tab, n_sources, src, idx, geo, bc, img_out, mask_out,
+                       lu_out, err_flag, H, W, Cdst, merge_above, m, s);
   DT_LAUNCH_CHECK();
   return DT_OK;
+}
+
+extern "C" int dt_pool_gather_batch(const uint8_t* images, const uint8_t* masks, const uint8_t* lu, const uint64_t* sums,
+                                    const int32_t* idx, const int32_t* geo, const float* bc, float* img_out,
+                                    int64_t* mask_out, int64_t* lu_out, int32_t* err_flag, int64_t N, int B, int H, int W,
+                                    int Cdst, int merge_above, const float* mean, const float* stdv, void* stream) {
+  DT_REQUIRE((lu == nullptr) == (lu_out == nullptr), "pool_gather_batch: lu and lu_out go together");
+  DT_REQUIRE(N > 0, "pool_gather_batch: bad sizes");
+  const dt_pool_source one = {images, masks, lu, sums, N};
+  return pool_gather_launch("pool_gather_batch", &one, 1, nullptr, idx, geo, bc, img_out, mask_out, lu_out, err_flag, B, H,
+                            W, Cdst, merge_above, mean, stdv, stream);
+}
+
+extern "C" int dt_pool_gather_combined(const dt_pool_source* sources, int n_sources, const int32_t* src, const int32_t* idx,
+                                       const int32_t* geo, const float* bc, float* img_out, int64_t* mask_out,
+                                       int64_t* lu_out, int32_t* err_flag, int B, int H, int W, int Cdst, int merge_above,
+                                       const float* mean, const float* stdv, void* stream) {
+  return pool_gather_launch("pool_gather_combined", sources, n_sources, src, idx, geo, bc, img_out, mask_out, lu_out,
+                            err_flag, B, H, W, Cdst, merge_above, mean, stdv, stream);
 }

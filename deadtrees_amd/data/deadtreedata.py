@@ -218,33 +218,38 @@ class DeadtreesDataModule:
         return _SyntheticLoader(self.synthetic_batches, int(conf.get("batch_size", 8)), self.tile_size,
                                 self.in_channels, self.classes, seed, wrap, self.device, True)
 
-    def _pool_loader(self, name, conf, train, wrap, trainer=None, distmap=True):
-        from .pool import PoolLoader
+    def _need_setup(self):
         if self.pools is None:
             raise RuntimeError("DeadtreesDataModule: call setup() before asking for a loader")
+
+    def _device_pools(self, name, extra=False):
+        """the ``name`` pool, followed by those of the extra sets if asked: after setup(), in the split, on the device"""
+        self._need_setup()
         if name not in self.pools:
             raise RuntimeError(f"DeadtreesDataModule: the split has no {name} shards")
-        if not self.pools[name].on_device:
+        pools = [self.pools[name]] + ([e[name] for e in self.extra_pools] if extra else [])
+        if not all(p.on_device for p in pools):
             raise RuntimeError("deadtrees_amd loaders run the HIP gather kernel on a device-resident pool: no HIP device, "
                                "no CPU fallback")
-        return PoolLoader(self.pools[name], int(conf.get("batch_size", 8)), train=train, in_channels=self.in_channels,
-                          classes=self.classes, seed=self.seed, wrap=wrap, distmap=distmap, trainer=trainer)
+        return pools
+
+    def _pool_loader(self, name, conf, train, wrap, trainer=None, distmap=True):
+        from .pool import PoolLoader
+        return PoolLoader(self._device_pools(name)[0], int(conf.get("batch_size", 8)), train=train,
+                          in_channels=self.in_channels, classes=self.classes, seed=self.seed, wrap=wrap, distmap=distmap,
+                          trainer=trainer)
 
     def _combined_loader(self, name, conf, train, trainer=None, distmap=True):
         from .pool import CombinedPoolLoader
-        if self.pools is None:
-            raise RuntimeError("DeadtreesDataModule: call setup() before asking for a loader")
+        self._need_setup()
         batch_size = int(conf.get("batch_size", 8))
         main = batch_size - sum(self.batch_size_extra)
         if main < 1:
             raise ValueError(f"{name} batch_size {batch_size} leaves {main} main samples beside batch_size_extra "
                              f"{self.batch_size_extra}")
-        pools = [self.pools[name]] + [e[name] for e in self.extra_pools]
-        if not all(p.on_device for p in pools):
-            raise RuntimeError("deadtrees_amd loaders run the HIP gather kernel on a device-resident pool: no HIP device, "
-                               "no CPU fallback")
-        return CombinedPoolLoader(pools, [main] + self.batch_size_extra, train=train, in_channels=self.in_channels,
-                                  classes=self.classes, seed=self.seed, distmap=distmap, trainer=trainer)
+        return CombinedPoolLoader(self._device_pools(name, extra=True), [main] + self.batch_size_extra, train=train,
+                                  in_channels=self.in_channels, classes=self.classes, seed=self.seed, distmap=distmap,
+                                  trainer=trainer)
 
     def train_dataloader(self, trainer=None, distmap: Optional[bool] = None):
         """trainer: a ``HipTrainer(graph=True)`` whose captured step the loader feeds in place (``PoolLoader``); its

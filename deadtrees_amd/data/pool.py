@@ -4,13 +4,14 @@ The reference decodes, augments and ships every sample every epoch on 2-4 loader
 loader bounds real data well below what the training step consumes).  A sample is a 256 x 256 tile: 4 image bands, a mask
 and a land-use map, 384 KiB as uint8 — 10^5 samples are 39 GB and fit in HBM several times over.  So every shard is decoded
 once (``shards.read_shard``), the split stays resident as uint8 (``DevicePool``), the host draws one small plan per epoch
-(``epoch_plan``: sample order and augmentation parameters) and ``PoolLoader`` makes every batch with ``dt_pool_gather_batch``
-(csrc/pool.hip), if asked straight into the tensors a captured training step reads (``HipTrainer.static_batch()``).
+(``epoch_plan``: sample order and augmentation parameters) and ``PoolLoader`` makes every batch with one launch of the
+gather kernel (csrc/pool.hip), if asked straight into the tensors a captured training step reads
+(``HipTrainer.static_batch()``).
 
 The reference's training configurations add extra shard sets to the main one (``pattern_extra`` / ``batch_size_extra``:
 every batch is some main samples followed by a fixed number of each extra set, the shorter sets cycling).  Those are
-several pools, one plan (``combined_plan``) and ``CombinedPoolLoader``, whose batches are still one launch each
-(``dt_pool_gather_combined``).
+several pools, one plan (``combined_plan``) and ``CombinedPoolLoader``, whose batches are still one launch each of the
+same kernel: both loaders are one implementation (``_GatherLoader``), and a single pool is its one-source case.
 """
 from __future__ import annotations
 
@@ -130,93 +131,6 @@ def epoch_plan(n: int, batch_size: int, epoch: int, seed: int, train: bool, squa
     return idx, geo, bc
 
 
-class PoolLoader:
-    """Batches of a ``DevicePool`` in the reference's format: ``{"main": (img f32 [B,C,H,W], mask i64 [B,H,W], distmap,
-    lu i64 [B,H,W], stats)}`` (``wrap=False``: the bare tuple of ``test_dataloader``).  One ``epoch_plan`` per epoch is
-    uploaded (three small copies); each batch is then one ``dt_pool_gather_batch`` launch on slices of it — no host
-    synchronisation and no host-to-device copy per batch.  ``classes == 2`` merges mask labels above 1 into 1.
-    ``distmap``: attach ``distmaps_on_device`` maps (False: ``None``; ``HipTrainer`` computes them itself when a
-    boundary loss needs them).
-
-    ``trainer``: once ``trainer.static_batch()`` exists and its image and mask buffers have this loader's shapes, the
-    gather writes into THOSE tensors and yields them, so the captured step finds its input in place; such batches are
-    overwritten by the next one.  Before that (and without a trainer) every batch is a fresh set of tensors.
-
-    Every ``__iter__`` starts the next epoch (0, 1, 2, ...), so a plain ``for batch in loader`` per epoch reshuffles;
-    ``set_epoch(e)`` makes the next iteration epoch e.  The kernel's error flag (never raised by a plan of
-    ``epoch_plan``) is read once, after the last batch of an epoch."""
-
-    def __init__(self, pool: DevicePool, batch_size: int, train: bool = False, in_channels: int = 3, classes: int = 2,
-                 seed: int = 0, wrap: bool = True, distmap: bool = True, trainer=None, mean=MEAN, std=STD):
-        if not pool.on_device:
-            raise RuntimeError("PoolLoader runs the HIP gather kernel on a device-resident pool: no HIP device, "
-                               "no CPU fallback")
-        if not 1 <= in_channels <= 4:
-            raise ValueError(f"in_channels {in_channels}: the pool holds 4 bands")
-        self.pool, self.batch_size, self.train = pool, int(batch_size), bool(train)
-        self.in_channels, self.classes, self.seed = int(in_channels), int(classes), int(seed)
-        self.wrap, self.distmap, self.trainer = bool(wrap), bool(distmap), trainer
-        self.mean, self.std = tuple(mean), tuple(std)
-        self.epoch = None            # the epoch of the running / last iteration
-        self._next_epoch = 0
-        self._eval_plan = None
-        self._err = torch.zeros(1, dtype=torch.int32, device=pool.device)
-
-    def __len__(self):
-        return len(self.pool) // self.batch_size
-
-    def set_epoch(self, epoch: int):
-        self._next_epoch = int(epoch)
-
-    def plan(self, epoch: int):
-        """the host plan of ``epoch`` (what ``__iter__`` uploads)"""
-        p = self.pool
-        return epoch_plan(len(p), self.batch_size, epoch, self.seed, self.train, p.height == p.width)
-
-    def _static_out(self):
-        sb = self.trainer.static_batch() if self.trainer is not None else None
-        if sb is None:
-            return None
-        img, mask = sb[0], sb[1]
-        p, dev = self.pool, self.pool.device
-        ok = (tuple(img.shape) == (self.batch_size, self.in_channels, p.height, p.width) and img.dtype == torch.float32
-              and tuple(mask.shape) == (self.batch_size, p.height, p.width) and mask.dtype == torch.int64
-              and img.is_contiguous() and mask.is_contiguous() and img.device == dev and mask.device == dev)
-        return (img, mask) if ok else None
-
-    def __iter__(self):
-        from .. import ops
-        p, bs = self.pool, self.batch_size
-        self.epoch = epoch = self._next_epoch
-        self._next_epoch = epoch + 1
-        if self.train or self._eval_plan is None:
-            host = self.plan(epoch)
-            dev_plan = tuple(t.to(p.device, non_blocking=True) for t in host)
-            if not self.train:
-                self._eval_plan = (host, dev_plan)
-        else:
-            host, dev_plan = self._eval_plan
-        order = host[0].tolist()
-        idx, geo, bc = dev_plan
-        for k in range(len(self)):
-            lo, hi = k * bs, (k + 1) * bs
-            static = self._static_out()
-            out = None
-            if static is not None:      # lu is not an input of the step: it gets a tensor of its own
-                out = (static[0], static[1], torch.empty((bs, p.height, p.width), dtype=torch.int64, device=p.device))
-            img, mask, lu, _ = ops.pool_gather_batch(p.images, p.masks, p.lu, p.sums, idx[lo:hi], geo[lo:hi], bc[lo:hi],
-                                                     self.mean, self.std, self.in_channels, self.classes == 2, out=out,
-                                                     err=self._err)
-            dist = distmaps_on_device(mask, self.classes) if self.distmap else None
-            item = (img, mask, dist, lu, [p.stats[i] for i in order[lo:hi]])
-            yield {"main": item} if self.wrap else item
-        flag = int(self._err.item())     # the one read of the epoch
-        if flag:
-            self._err.zero_()
-            raise RuntimeError(f"pool gather: error flag {flag} (1: sample index outside the pool, 2: odd turn of a "
-                               "non-square tile); those samples were zero-filled")
-
-
 def combined_plan(ns: Sequence[int], batch_sizes: Sequence[int], epoch: int, seed: int, train: bool, square: bool = True):
     """One epoch over several sources, the reference's ``CombinedLoader(..., "max_size_cycle")`` over loaders batched
     with ``partial=False`` (deadtreedata.py:348-395): source j has ``len_j = ns[j] // batch_sizes[j]`` batches, the epoch
@@ -275,56 +189,63 @@ class CombinedBatch(dict):
             raise ValueError(f"CombinedBatch: batch sizes {list(batch_sizes)} for {img.shape[0]} samples")
 
 
-class CombinedPoolLoader:
-    """``PoolLoader`` over several pools (the main set and the extra sets of ``pattern_extra``): every batch is a
-    ``CombinedBatch`` of ``batch_sizes[0]`` main samples followed by ``batch_sizes[j]`` samples of every extra pool, made
-    by one ``dt_pool_gather_combined`` launch on slices of the epoch's ``combined_plan`` (four small uploads per epoch:
-    src, idx, geo, bc).  ``len()`` is the longest source's batch count; shorter ones cycle.  Distance maps are computed
-    once, on the combined mask.  ``trainer``, the epoch counter, ``set_epoch`` and the one read of the error flag per
-    epoch are those of ``PoolLoader``; the buffers of ``trainer.static_batch()`` are written when they have the shape of
-    the combined batch."""
+class _GatherLoader:
+    """What ``PoolLoader`` and ``CombinedPoolLoader`` are: the batches of one or several ``DevicePool``s, each made by
+    one ``ops.pool_gather_combined`` launch on slices of the epoch's host plan (``_host_plan``), which is uploaded once per
+    epoch; no host synchronisation and no host-to-device copy per batch.  ``classes == 2`` merges mask labels above 1
+    into 1.  ``distmap``: attach ``distmaps_on_device`` maps, computed once on the whole batch (False: ``None``;
+    ``HipTrainer`` computes them itself when a boundary loss needs them).
+
+    ``trainer``: once ``trainer.static_batch()`` exists and its image and mask buffers have this loader's shapes, the
+    gather writes into THOSE tensors and yields them, so the captured step finds its input in place; such batches are
+    overwritten by the next one.  Before that (and without a trainer) every batch is a fresh set of tensors.
+
+    Every ``__iter__`` starts the next epoch (0, 1, 2, ...), so a plain ``for batch in loader`` per epoch reshuffles;
+    ``set_epoch(e)`` makes the next iteration epoch e.  The kernel's error flag (never raised by a plan of ``epoch_plan``
+    or ``combined_plan``) is read once, after the last batch of an epoch."""
 
     def __init__(self, pools: Sequence[DevicePool], batch_sizes: Sequence[int], train: bool = False, in_channels: int = 3,
                  classes: int = 2, seed: int = 0, distmap: bool = True, trainer=None, mean=MEAN, std=STD):
         from .._lib import POOL_MAX_SOURCES
+        who = type(self).__name__
         pools, batch_sizes = list(pools), [int(b) for b in batch_sizes]
         if not pools or len(pools) != len(batch_sizes):
-            raise ValueError(f"CombinedPoolLoader: {len(pools)} pools, {len(batch_sizes)} batch sizes")
+            raise ValueError(f"{who}: {len(pools)} pools, {len(batch_sizes)} batch sizes")
         if len(pools) > POOL_MAX_SOURCES:
-            raise ValueError(f"CombinedPoolLoader: at most {POOL_MAX_SOURCES} pools, not {len(pools)}")
+            raise ValueError(f"{who}: at most {POOL_MAX_SOURCES} pools, not {len(pools)}")
         if not all(p.on_device for p in pools):
-            raise RuntimeError("CombinedPoolLoader runs the HIP gather kernel on device-resident pools: no HIP device, "
-                               "no CPU fallback")
+            raise RuntimeError(f"{who} runs the HIP gather kernel on device-resident pools: no HIP device, no CPU fallback")
         if not 1 <= in_channels <= 4:
             raise ValueError(f"in_channels {in_channels}: the pool holds 4 bands")
         first = pools[0]
         for j, p in enumerate(pools):
             if (p.height, p.width) != (first.height, first.width) or p.device != first.device:
-                raise ValueError(f"CombinedPoolLoader: pool {j} holds {p.height}x{p.width} tiles on {p.device}, pool 0 "
+                raise ValueError(f"{who}: pool {j} holds {p.height}x{p.width} tiles on {p.device}, pool 0 "
                                  f"{first.height}x{first.width} on {first.device}")
         self.pools, self.batch_sizes, self.train = pools, batch_sizes, bool(train)
         self.batch_size = sum(batch_sizes)
         self.in_channels, self.classes, self.seed = int(in_channels), int(classes), int(seed)
         self.distmap, self.trainer = bool(distmap), trainer
         self.mean, self.std = tuple(mean), tuple(std)
-        self.epoch = None
+        self.epoch = None            # the epoch of the running / last iteration
         self._next_epoch = 0
         self._eval_plan = None
-        self._len = self.plan(0)[0]          # (raises for a pool too small for one batch)
         self._sources = [(p.images, p.masks, p.lu, p.sums) for p in pools]
         self._err = torch.zeros(1, dtype=torch.int32, device=first.device)
-
-    def __len__(self):
-        return self._len
 
     def set_epoch(self, epoch: int):
         self._next_epoch = int(epoch)
 
-    def plan(self, epoch: int):
-        """the host plan of ``epoch``: ``combined_plan`` of the pools' sizes"""
-        p = self.pools[0]
-        return combined_plan([len(q) for q in self.pools], self.batch_sizes, epoch, self.seed, self.train,
-                             p.height == p.width)
+    def __len__(self):
+        raise NotImplementedError
+
+    def _host_plan(self, epoch: int):
+        """``(src, idx, geo, bc)`` of ``epoch`` on the host; src is None with one pool (every row is pool 0)"""
+        raise NotImplementedError
+
+    def _batch(self, item):
+        """the yielded form of the five-tuple of whole tensors"""
+        raise NotImplementedError
 
     def _static_out(self):
         sb = self.trainer.static_batch() if self.trainer is not None else None
@@ -343,13 +264,14 @@ class CombinedPoolLoader:
         self.epoch = epoch = self._next_epoch
         self._next_epoch = epoch + 1
         if self.train or self._eval_plan is None:
-            host = self.plan(epoch)[1:]
-            dev_plan = tuple(t.to(p.device, non_blocking=True) for t in host)
+            host = self._host_plan(epoch)
+            dev_plan = tuple(None if t is None else t.to(p.device, non_blocking=True) for t in host)
             if not self.train:
                 self._eval_plan = (host, dev_plan)
         else:
             host, dev_plan = self._eval_plan
-        which, order = host[0].tolist(), host[1].tolist()
+        order = host[1].tolist()
+        which = [0] * len(order) if host[0] is None else host[0].tolist()
         src, idx, geo, bc = dev_plan
         for k in range(len(self)):
             lo, hi = k * bs, (k + 1) * bs
@@ -357,14 +279,68 @@ class CombinedPoolLoader:
             out = None
             if static is not None:      # lu is not an input of the step: it gets a tensor of its own
                 out = (static[0], static[1], torch.empty((bs, p.height, p.width), dtype=torch.int64, device=p.device))
-            img, mask, lu, _ = ops.pool_gather_combined(self._sources, src[lo:hi], idx[lo:hi], geo[lo:hi], bc[lo:hi],
-                                                        self.mean, self.std, self.in_channels, self.classes == 2,
-                                                        out=out, err=self._err)
+            img, mask, lu, _ = ops.pool_gather_combined(self._sources, None if src is None else src[lo:hi], idx[lo:hi],
+                                                        geo[lo:hi], bc[lo:hi], self.mean, self.std, self.in_channels,
+                                                        self.classes == 2, out=out, err=self._err)
             dist = distmaps_on_device(mask, self.classes) if self.distmap else None
             stats = [self.pools[j].stats[i] for j, i in zip(which[lo:hi], order[lo:hi])]
-            yield CombinedBatch((img, mask, dist, lu, stats), self.batch_sizes)
+            yield self._batch((img, mask, dist, lu, stats))
         flag = int(self._err.item())     # the one read of the epoch
         if flag:
             self._err.zero_()
             raise RuntimeError(f"pool gather: error flag {flag} (1: sample index outside its pool, 2: odd turn of a "
                                "non-square tile, 4: source outside the pool list); those samples were zero-filled")
+
+
+class PoolLoader(_GatherLoader):
+    """Batches of one ``DevicePool`` in the reference's format: ``{"main": (img f32 [B,C,H,W], mask i64 [B,H,W], distmap,
+    lu i64 [B,H,W], stats)}`` (``wrap=False``: the bare tuple of ``test_dataloader``), after one ``epoch_plan`` per epoch
+    (three small uploads: idx, geo, bc; one pool needs no src).  ``len()`` is ``len(pool) // batch_size``: a pool smaller
+    than one batch yields nothing.  Everything else is ``_GatherLoader``'s."""
+
+    def __init__(self, pool: DevicePool, batch_size: int, train: bool = False, in_channels: int = 3, classes: int = 2,
+                 seed: int = 0, wrap: bool = True, distmap: bool = True, trainer=None, mean=MEAN, std=STD):
+        self.pool, self.wrap = pool, bool(wrap)
+        super().__init__([pool], [batch_size], train, in_channels, classes, seed, distmap, trainer, mean, std)
+
+    def plan(self, epoch: int):
+        """the host plan of ``epoch`` (what ``__iter__`` uploads)"""
+        p = self.pool
+        return epoch_plan(len(p), self.batch_size, epoch, self.seed, self.train, p.height == p.width)
+
+    def __len__(self):
+        return len(self.pool) // self.batch_size
+
+    def _host_plan(self, epoch: int):
+        return (None,) + self.plan(epoch)
+
+    def _batch(self, item):
+        return {"main": item} if self.wrap else item
+
+
+class CombinedPoolLoader(_GatherLoader):
+    """Several pools (the main set and the extra sets of ``pattern_extra``): every batch is a ``CombinedBatch`` of
+    ``batch_sizes[0]`` main samples followed by ``batch_sizes[j]`` samples of every extra pool, rows of the epoch's
+    ``combined_plan`` (four small uploads per epoch: src, idx, geo, bc; three with one pool).  ``len()`` is the longest
+    source's batch count; shorter ones cycle, and a pool smaller than its batch size is a ``ValueError``.  Everything
+    else is ``_GatherLoader``'s."""
+
+    def plan(self, epoch: int):
+        """the host plan of ``epoch``: ``combined_plan`` of the pools' sizes"""
+        p = self.pools[0]
+        return combined_plan([len(q) for q in self.pools], self.batch_sizes, epoch, self.seed, self.train,
+                             p.height == p.width)
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._len = self.plan(0)[0]          # (raises for a pool too small for one batch)
+
+    def __len__(self):
+        return self._len
+
+    def _host_plan(self, epoch: int):
+        _, src, *rows = self.plan(epoch)
+        return (src if len(self.pools) > 1 else None, *rows)
+
+    def _batch(self, item):
+        return CombinedBatch(item, self.batch_sizes)

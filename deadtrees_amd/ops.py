@@ -888,61 +888,16 @@ def augment_labels(labels, geo):
     return out
 
 
-def pool_gather_batch(images, masks, lu, sums, idx, geo, bc, mean, std, c_dst, merge_above=False, out=None, err=None):
-    """One batch out of a device-resident pool in one launch (csrc/pool.hip): images uint8 [N,H,W,4], masks / lu uint8
-    [N,H,W] (lu may be None), sums int64 [N] (the exact byte sum of every image; the bits of the ABI's uint64), idx int32
-    [B], geo int32 [B,2], bc fp32 [B,2] -> (img fp32 [B,c_dst,H,W] contiguous, mask int64 [B,H,W], lu int64 [B,H,W] or
-    None, err int32 [1]).  The arithmetic is that of ``augment_normalize_u8`` / ``augment_labels`` on ``images[idx]``.
-    out: (img, mask, lu) tensors to write into (e.g. ``HipTrainer.static_batch()``'s); err: a flag to OR into.  No host
-    synchronisation: a bad index or an odd turn of a non-square tile zeroes that sample and sets a bit of ``err``."""
-    _gpu(images, masks, lu, sums, idx, geo, bc)
-    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 4 or not images.is_contiguous():
-        raise RuntimeError("pool_gather_batch: images must be contiguous uint8 [N,H,W,4]")
-    N, H, W, _ = images.shape
-    for name, t in (("masks", masks), ("lu", lu)):
-        if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != (N, H, W) or not t.is_contiguous()):
-            raise RuntimeError(f"pool_gather_batch: {name} must be contiguous uint8 [N,H,W]")
-    if sums.dtype != torch.int64 or tuple(sums.shape) != (N,) or not sums.is_contiguous():
-        raise RuntimeError("pool_gather_batch: sums must be contiguous int64 [N]")
-    B = idx.shape[0]
-    if (idx.dtype != torch.int32 or idx.dim() != 1 or geo.dtype != torch.int32 or tuple(geo.shape) != (B, 2)
-            or bc.dtype != torch.float32 or tuple(bc.shape) != (B, 2)
-            or not (idx.is_contiguous() and geo.is_contiguous() and bc.is_contiguous())):
-        raise RuntimeError("pool_gather_batch: idx must be int32 [B], geo int32 [B,2] and bc float32 [B,2], contiguous")
-    dev = images.device
-    if out is None:
-        out = (torch.empty((B, c_dst, H, W), dtype=torch.float32, device=dev),
-               torch.empty((B, H, W), dtype=torch.int64, device=dev),
-               None if lu is None else torch.empty((B, H, W), dtype=torch.int64, device=dev))
-    img, mask, lu_out = out
-    for name, t, shape, dt in (("img", img, (B, c_dst, H, W), torch.float32), ("mask", mask, (B, H, W), torch.int64),
-                               ("lu", lu_out, (B, H, W), torch.int64)):
-        if (t is None) != (name == "lu" and lu is None):
-            raise RuntimeError("pool_gather_batch: out needs img and mask, and lu exactly when the pool has one")
-        if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev):
-            raise RuntimeError(f"pool_gather_batch: out {name} must be contiguous {dt} {list(shape)} on {dev}")
-    if err is None:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-    m = (C.c_float * c_dst)(*[float(v) for v in mean[:c_dst]])
-    s = (C.c_float * c_dst)(*[float(v) for v in std[:c_dst]])
-    _lib.check(_lib.load().dt_pool_gather_batch(_p(images), _p(masks), _p(lu), _p(sums), _p(idx), _p(geo), _p(bc), _p(img),
-                                                _p(mask), _p(lu_out), _p(err), N, B, H, W, c_dst, int(bool(merge_above)),
-                                                m, s, _st()), "dt_pool_gather_batch")
-    return img, mask, lu_out, err
-
-
-def pool_gather_combined(sources, src, idx, geo, bc, mean, std, c_dst, merge_above=False, out=None, err=None):
-    """One batch out of several device-resident pools in one launch (``dt_pool_gather_combined``, csrc/pool.hip).
-    sources: a list of ``(images, masks, lu, sums)`` tensor tuples as ``pool_gather_batch`` takes them, all of one tile
-    size (lu: None in every source or in none); slot b is sample ``idx[b]`` of ``sources[src[b]]``: src, idx int32 [B], geo
-    int32 [B,2], bc fp32 [B,2].  Returns what ``pool_gather_batch`` returns, with its arithmetic bit for bit.  A source
-    number outside the list sets bit 4 of ``err``, an index outside its source bit 1, an odd turn of a non-square tile bit
-    2; those slots are zeros."""
+def _pool_gather(who, sources, src, idx, geo, bc, mean, std, c_dst, merge_above, out, err):
+    """the one validator and launch behind ``pool_gather_batch`` (one source, ``src`` None) and ``pool_gather_combined``;
+    who: the caller's name, for the messages"""
     if not 1 <= len(sources) <= _lib.POOL_MAX_SOURCES:
-        raise RuntimeError(f"pool_gather_combined: 1 .. {_lib.POOL_MAX_SOURCES} sources, not {len(sources)}")
+        raise RuntimeError(f"{who}: 1 .. {_lib.POOL_MAX_SOURCES} sources, not {len(sources)}")
     sources = [tuple(t) for t in sources]
     if any(len(t) != 4 for t in sources):
-        raise RuntimeError("pool_gather_combined: a source is (images, masks, lu, sums)")
+        raise RuntimeError(f"{who}: a source is (images, masks, lu, sums)")
+    if src is None and len(sources) != 1:
+        raise RuntimeError(f"{who}: src may be None with one source only, not with {len(sources)} sources")
     with_lu = sources[0][2] is not None
     _gpu(src, idx, geo, bc, *(x for t in sources for x in t))
     dev = sources[0][0].device
@@ -950,30 +905,29 @@ def pool_gather_combined(sources, src, idx, geo, bc, mean, std, c_dst, merge_abo
     table = (_lib.PoolSource * len(sources))()
     for j, (images, masks, lu, sums) in enumerate(sources):
         if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 4 or not images.is_contiguous():
-            raise RuntimeError(f"pool_gather_combined: source {j}: images must be contiguous uint8 [N,H,W,4]")
+            raise RuntimeError(f"{who}: source {j}: images must be contiguous uint8 [N,H,W,4]")
         N = images.shape[0]
         if tuple(images.shape[1:3]) != (H, W):
-            raise RuntimeError(f"pool_gather_combined: source {j} holds {images.shape[1]}x{images.shape[2]} tiles, "
-                               f"source 0 {H}x{W}")
+            raise RuntimeError(f"{who}: source {j} holds {images.shape[1]}x{images.shape[2]} tiles, source 0 {H}x{W}")
         if (lu is not None) != with_lu:
-            raise RuntimeError("pool_gather_combined: lu in every source or in none")
+            raise RuntimeError(f"{who}: lu in every source or in none")
         for name, t in (("masks", masks), ("lu", lu)):
             if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != (N, H, W) or not t.is_contiguous()):
-                raise RuntimeError(f"pool_gather_combined: source {j}: {name} must be contiguous uint8 [N,H,W]")
+                raise RuntimeError(f"{who}: source {j}: {name} must be contiguous uint8 [N,H,W]")
         if sums.dtype != torch.int64 or tuple(sums.shape) != (N,) or not sums.is_contiguous():
-            raise RuntimeError(f"pool_gather_combined: source {j}: sums must be contiguous int64 [N]")
+            raise RuntimeError(f"{who}: source {j}: sums must be contiguous int64 [N]")
         if any(t is not None and t.device != dev for t in (images, masks, lu, sums)):
-            raise RuntimeError(f"pool_gather_combined: source {j} is not on {dev}")
+            raise RuntimeError(f"{who}: source {j} is not on {dev}")
         table[j] = _lib.PoolSource(_p(images), _p(masks), _p(lu), _p(sums), N)
     B = idx.shape[0]
-    if (idx.dtype != torch.int32 or idx.dim() != 1 or src.dtype != torch.int32 or tuple(src.shape) != (B,)
-            or geo.dtype != torch.int32 or tuple(geo.shape) != (B, 2) or bc.dtype != torch.float32
-            or tuple(bc.shape) != (B, 2)
-            or not (src.is_contiguous() and idx.is_contiguous() and geo.is_contiguous() and bc.is_contiguous())):
-        raise RuntimeError("pool_gather_combined: src and idx must be int32 [B], geo int32 [B,2] and bc float32 [B,2], "
+    if (idx.dtype != torch.int32 or idx.dim() != 1 or geo.dtype != torch.int32 or tuple(geo.shape) != (B, 2)
+            or bc.dtype != torch.float32 or tuple(bc.shape) != (B, 2)
+            or (src is not None and (src.dtype != torch.int32 or tuple(src.shape) != (B,) or not src.is_contiguous()))
+            or not (idx.is_contiguous() and geo.is_contiguous() and bc.is_contiguous())):
+        raise RuntimeError(f"{who}: src (if given) and idx must be int32 [B], geo int32 [B,2] and bc float32 [B,2], "
                            "contiguous")
-    if any(t.device != dev for t in (src, idx, geo, bc)):
-        raise RuntimeError(f"pool_gather_combined: src, idx, geo and bc must be on {dev}")
+    if any(t is not None and t.device != dev for t in (src, idx, geo, bc)):
+        raise RuntimeError(f"{who}: src, idx, geo and bc must be on {dev}")
     if out is None:
         out = (torch.empty((B, c_dst, H, W), dtype=torch.float32, device=dev),
                torch.empty((B, H, W), dtype=torch.int64, device=dev),
@@ -982,9 +936,9 @@ def pool_gather_combined(sources, src, idx, geo, bc, mean, std, c_dst, merge_abo
     for name, t, shape, dt in (("img", img, (B, c_dst, H, W), torch.float32), ("mask", mask, (B, H, W), torch.int64),
                                ("lu", lu_out, (B, H, W), torch.int64)):
         if (t is None) != (name == "lu" and not with_lu):
-            raise RuntimeError("pool_gather_combined: out needs img and mask, and lu exactly when the pools have one")
+            raise RuntimeError(f"{who}: out needs img and mask, and lu exactly when the pools have one")
         if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev):
-            raise RuntimeError(f"pool_gather_combined: out {name} must be contiguous {dt} {list(shape)} on {dev}")
+            raise RuntimeError(f"{who}: out {name} must be contiguous {dt} {list(shape)} on {dev}")
     if err is None:
         err = torch.zeros(1, dtype=torch.int32, device=dev)
     m = (C.c_float * c_dst)(*[float(v) for v in mean[:c_dst]])
@@ -993,6 +947,28 @@ def pool_gather_combined(sources, src, idx, geo, bc, mean, std, c_dst, merge_abo
                                                    _p(mask), _p(lu_out), _p(err), B, H, W, c_dst,
                                                    int(bool(merge_above)), m, s, _st()), "dt_pool_gather_combined")
     return img, mask, lu_out, err
+
+
+def pool_gather_batch(images, masks, lu, sums, idx, geo, bc, mean, std, c_dst, merge_above=False, out=None, err=None):
+    """One batch out of a device-resident pool in one launch (csrc/pool.hip): images uint8 [N,H,W,4], masks / lu uint8
+    [N,H,W] (lu may be None), sums int64 [N] (the exact byte sum of every image; the bits of the ABI's uint64), idx int32
+    [B], geo int32 [B,2], bc fp32 [B,2] -> (img fp32 [B,c_dst,H,W] contiguous, mask int64 [B,H,W], lu int64 [B,H,W] or
+    None, err int32 [1]).  The arithmetic is that of ``augment_normalize_u8`` / ``augment_labels`` on ``images[idx]``.
+    out: (img, mask, lu) tensors to write into (e.g. ``HipTrainer.static_batch()``'s); err: a flag to OR into.  No host
+    synchronisation: a bad index or an odd turn of a non-square tile zeroes that sample and sets a bit of ``err``.
+    This is ``pool_gather_combined`` with one source and no ``src``."""
+    return _pool_gather("pool_gather_batch", [(images, masks, lu, sums)], None, idx, geo, bc, mean, std, c_dst,
+                        merge_above, out, err)
+
+
+def pool_gather_combined(sources, src, idx, geo, bc, mean, std, c_dst, merge_above=False, out=None, err=None):
+    """One batch out of several device-resident pools in one launch (``dt_pool_gather_combined``, csrc/pool.hip).
+    sources: a list of ``(images, masks, lu, sums)`` tensor tuples as ``pool_gather_batch`` takes them, all of one tile
+    size (lu: None in every source or in none); slot b is sample ``idx[b]`` of ``sources[src[b]]``: src, idx int32 [B], geo
+    int32 [B,2], bc fp32 [B,2]; with one source src may be None.  Returns what ``pool_gather_batch`` returns.  A source
+    number outside the list sets bit 4 of ``err``, an index outside its source bit 1, an odd turn of a non-square tile bit
+    2; those slots are zeros."""
+    return _pool_gather("pool_gather_combined", sources, src, idx, geo, bc, mean, std, c_dst, merge_above, out, err)
 
 
 def ensemble_vote(maps_u8: torch.Tensor, K: int, dtype: str = "int64"):

@@ -283,7 +283,8 @@ int dt_augment_labels(const int64_t* src, int64_t* dst, const int32_t* geo, int 
  * classes == 2 rule, data/deadtreedata.py:179-180); lu is never merged.  One launch, no scratch memory.
  * The pool is never read out of range: a sample with idx[b] outside [0, N), or with an odd turn while H != W, is
  * written as zeros and ORs DT_POOL_ERR_INDEX / DT_POOL_ERR_TURN into err_flag[0] (int32, zeroed by the caller).
- * mean/std: HOST arrays of Cdst floats. */
+ * mean/std: HOST arrays of Cdst floats.  This is dt_pool_gather_combined with one source and src == NULL: the same kernel,
+ * the same checks. */
 #define DT_POOL_ERR_INDEX 1
 #define DT_POOL_ERR_TURN 2
 int dt_pool_gather_batch(const uint8_t* images, const uint8_t* masks, const uint8_t* lu, const uint64_t* sums,
@@ -297,7 +298,8 @@ int dt_pool_gather_batch(const uint8_t* images, const uint8_t* masks, const uint
  * arithmetic, pixel map and stores of dt_pool_gather_batch, bit for bit.  lu_out non-NULL requires lu in every source;
  * with lu_out NULL the sources' lu are not read.  src[b] outside [0, n_sources) ORs DT_POOL_ERR_SOURCE into err_flag[0],
  * idx[b] outside [0, sources[src[b]].n) DT_POOL_ERR_INDEX, an odd turn while H != W DT_POOL_ERR_TURN; such a slot reads
- * nothing and is written as zeros.  The table travels as a kernel argument: no copy, no scratch memory. */
+ * nothing and is written as zeros.  The table travels as a kernel argument: no copy, no scratch memory.  src may be NULL
+ * exactly when n_sources == 1: every slot then reads source 0 (what dt_pool_gather_batch does). */
 #define DT_POOL_MAX_SOURCES 8
 #define DT_POOL_ERR_SOURCE 4
 typedef struct dt_pool_source {

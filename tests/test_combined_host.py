@@ -201,6 +201,23 @@ def test_combined_plan_errors():
     assert L == 3 and not src.any() and len(set(idx.tolist())) == 6
 
 
+@pytest.mark.parametrize("n,b", [(37, 4), (8, 8), (9, 2), (5, 1)])
+def test_combined_plan_of_one_source_is_the_epoch_plan(n, b):
+    """what lets ``PoolLoader`` and ``CombinedPoolLoader`` be one loader: one source makes ``combined_plan`` the plain
+    ``epoch_plan``, value for value and dtype for dtype"""
+    from deadtrees_amd.data.pool import combined_plan, epoch_plan
+    seed = 11
+    for train in (True, False):
+        for square in (True, False):
+            for epoch in (0, 3):
+                L, src, *rows = combined_plan([n], [b], epoch, seed, train, square)
+                want = epoch_plan(n, b, epoch, seed, train, square)
+                assert L == n // b and src.dtype == torch.int32 and tuple(src.shape) == (L * b,) and not src.any()
+                assert len(rows) == len(want) == 3
+                for got, ref in zip(rows, want):
+                    assert got.dtype == ref.dtype and torch.equal(got, ref)
+
+
 # ------------------------------------------------------------------ batch type
 def test_combined_batch_passes_through_create_combined_batch():
     from deadtrees.network.segmodel import create_combined_batch as shim

@@ -108,6 +108,46 @@ def test_combined_gather_is_bit_identical_to_the_single_pool_kernel(h, w, c_dst,
     _assert_slots_equal_single_source((img2, mask2, None), sources, src, idx, geo, bc, c_dst, merge, with_lu=False)
 
 
+@pytest.mark.parametrize("c_dst", [3, 4])
+@pytest.mark.parametrize("h,w", SHAPES)
+def test_one_source_without_src_is_the_zero_src_and_the_single_pool_call(h, w, c_dst):
+    from deadtrees_amd import ops
+    from deadtrees_amd.data.synthetic import MEAN, STD
+    sources = _sources(h, w)
+    one = sources[0]
+    src, _, geo, bc = _calls(h, w)[0]
+    idx0 = torch.tensor([7, 1, 4, 1, 0, 8, 3], dtype=torch.int32, device=DEV)
+    got = ops.pool_gather_combined([one], None, idx0, geo, bc, MEAN, STD, c_dst, 1)
+    zero = ops.pool_gather_combined([one], torch.zeros_like(src), idx0, geo, bc, MEAN, STD, c_dst, 1)
+    single = ops.pool_gather_batch(*one, idx0, geo, bc, MEAN, STD, c_dst, 1)
+    assert tuple(got[0].shape) == (7, c_dst, h, w) and bool(got[0].any()) and int(got[1].max()) == 1
+    for other in (zero, single):
+        assert all(torch.equal(a, b) for a, b in zip(got[:3], other[:3]))
+        assert int(got[3]) == 0 and int(other[3]) == 0
+    with pytest.raises(RuntimeError, match="one source"):
+        ops.pool_gather_combined(sources[:2], None, idx0, geo, bc, MEAN, STD, c_dst, 1)
+    # the C entry dt_pool_gather_batch itself (ops reaches the kernel through dt_pool_gather_combined): its one row
+    import ctypes as C
+    from deadtrees_amd import _lib
+    images, masks, lu, sums = one
+    img, mask, lu_out, flag = (torch.full_like(t, 7) for t in got)
+    mean, std = ((C.c_float * c_dst)(*v[:c_dst]) for v in (MEAN, STD))
+
+    def entry(lu_in, n):
+        p = _lib.ptr
+        return _lib.load().dt_pool_gather_batch(p(images), p(masks), p(lu_in), p(sums), p(idx0), p(geo), p(bc), p(img),
+                                                p(mask), p(lu_out), p(flag.zero_()), n, 7, h, w, c_dst, 1, mean, std,
+                                                _lib.stream())
+    _lib.check(entry(lu, images.shape[0]), "dt_pool_gather_batch")
+    assert all(torch.equal(a, b) for a, b in zip((img, mask, lu_out), got[:3])) and int(flag) == 0
+    _lib.check(entry(lu, 8), "dt_pool_gather_batch")             # N = 8 puts sample 8 (slot 5) outside the pool
+    assert int(flag) == 1 and not img[5].any() and torch.equal(img[:5], got[0][:5]) and torch.equal(mask[6], got[1][6])
+    with pytest.raises(RuntimeError, match="pool_gather_batch: lu and lu_out go together"):
+        _lib.check(entry(None, images.shape[0]), "dt_pool_gather_batch")
+    with pytest.raises(RuntimeError, match="pool_gather_batch: "):
+        _lib.check(entry(lu, 0), "dt_pool_gather_batch")
+
+
 def test_combined_gather_checks_its_arguments():
     from deadtrees_amd import ops
     from deadtrees_amd.data.synthetic import MEAN, STD
@@ -346,3 +386,21 @@ def test_combined_loader_feeds_the_captured_step_in_place(shard_dir):
     replay.set_epoch(1)
     want = list(replay)[-1].combined
     assert torch.equal(last[0], want[0]) and torch.equal(last[1], want[1])
+
+
+def test_combined_loader_of_one_pool_is_the_pool_loader(shard_dir):
+    """the 18-sample train pool alone: both loaders are one implementation and must yield the same epochs"""
+    from deadtrees_amd.data.pool import CombinedBatch, CombinedPoolLoader, PoolLoader
+    pool = _datamodule(shard_dir).pools["train"]
+    b = 4
+    kw = dict(train=True, in_channels=3, classes=2, seed=SEED)
+    combined, single = CombinedPoolLoader([pool], [b], **kw), PoolLoader(pool, b, **kw)
+    assert len(combined) == len(single) == 4
+    for epoch in (0, 1):
+        pairs = list(zip(combined, single, strict=True))
+        assert len(pairs) == 4 and combined.epoch == single.epoch == epoch
+        for whole, item in pairs:
+            assert isinstance(whole, CombinedBatch) and list(whole) == ["main"] and list(item) == ["main"]
+            for f in range(4):
+                assert tuple(whole.combined[f].shape)[0] == b and torch.equal(whole.combined[f], item["main"][f])
+            assert whole.combined[4] == item["main"][4] and len(item["main"][4]) == b
