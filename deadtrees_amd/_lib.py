@@ -205,6 +205,11 @@ SIGNATURES = {
     "dt_adam_advance_ranges": (C.c_int, [c_f, c_f, C.c_int, c_f, c_f, F64, F64, c_f, c_f]),
     "dt_weight_average": (C.c_int, [c_f, c_f, I64, c_f, c_f, C.c_int, F64, c_f]),
     "dt_cma_advance": (C.c_int, [c_f, c_f, c_f]),
+    "dt_pwconv_affine": (C.c_int, [c_f] * 9 + [C.c_int] * 8 + [c_f]),
+    "dt_dwconv3x3_rows": (C.c_int, [C.c_int, C.c_int]),
+    "dt_dwconv3x3_affine": (C.c_int, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, c_f]),
+    "dt_scse_gates": (C.c_int, [c_f] * 6 + [C.c_int] * 5 + [c_f]),
+    "dt_bn_eval_affine_bias": (C.c_int, [c_f, c_f, c_f, c_f, c_f, F32, C.c_int, c_f, c_f, c_f]),
     "dt_adam_step_ranges": (C.c_int, [c_f, c_f, c_f, c_f, c_f, C.c_int, I64, c_f, F64, F64, F32, c_f, c_f, c_f]),
 }
 

@@ -216,8 +216,12 @@ class EngineCore:
     # ------------------------------------------------------------------ BatchNorm coefficients (fp32 in both precisions)
     def _bn_eval_affine(self, c: ConvSpec, params, bn: BnView):
         """(scale, shift) of conv c from its running statistics; skipped while the coefficients of the previous
-        inference call are still valid (`_affine_fresh`, see forward)"""
-        if not self._affine_fresh:
+        inference call are still valid (`_affine_fresh`, see forward).  A convolution bias in front of the BatchNorm
+        (EfficientUnet++ blocks) is folded into the shift: shift + scale * bias"""
+        if not self._affine_fresh and c.has_cbias:
+            self._call("dt_bn_eval_affine_bias", c.gamma(params), c.beta(params), bn.running_mean(c), bn.running_var(c),
+                       c.conv_bias(params), BN_EPS, c.cout, bn.scale(c), bn.shift(c))
+        elif not self._affine_fresh:
             self._call("dt_bn_eval_affine", c.gamma(params), c.beta(params), bn.running_mean(c), bn.running_var(c),
                        BN_EPS, c.cout, bn.scale(c), bn.shift(c))
         return bn.ss(c)
@@ -256,7 +260,7 @@ class EngineCore:
         if tab is None:
             rows, blocks, off, offs = [], 0, 0, {}
             for c in self.spec.convs:
-                if c is self.spec.stem or c is self.spec.head or c.k != 3 or c.stride != 1 or c.pad != 1:
+                if c is self.spec.stem or c is self.spec.head or c.k != 3 or c.stride != 1 or c.pad != 1 or c.depthwise:
                     continue
                 cin, cout = (c.cout, c.cin) if dgrad else (c.cin, c.cout)
                 if cin % 16 or cout % 64:

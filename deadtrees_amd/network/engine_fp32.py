@@ -140,6 +140,9 @@ class Fp32Schedule:
         (``forward_eval_head`` hands it to the fused evaluation head)."""
         sp = self.spec
         self._recal = None
+        if sp.decoder_kind == "efficientunetplusplus" and (training or save or recal is not None or enc_training or enc_frozen):
+            raise NotImplementedError("decoder 'efficientunetplusplus' is inference only: its inverted-residual blocks have no "
+                                      "batch-statistics forward and no backward kernels (eval-mode BatchNorm, nothing saved)")
         if decoder_only and (training or save or recal is not None or enc_training):
             raise RuntimeError("decoder_only forward: inference only (eval-mode BatchNorm, nothing saved)")
         if recal is not None:
@@ -261,6 +264,9 @@ class Fp32Schedule:
         if sp.decoder_kind == "unetplusplus":
             d, dh, dw = self._forward_unetpp(feats, params, bn, B, training, save, keep)
             dec_blocks = []
+        elif sp.decoder_kind == "efficientunetplusplus":
+            d, dh, dw = self._forward_effunetpp(feats, params, bn, B)
+            dec_blocks = []
         else:
             d, dh, dw = feats[4], ch, cw
             dec_blocks = sp.decoder
@@ -373,6 +379,71 @@ class Fp32Schedule:
             z2 = self._bn_act(y2, ss2, of=blk.conv2)
             keep("P" + blk.name, x=low, skip=skip, parts=parts, y1=y1, y2=y2, z2=z2, H=h1, W=w1)
             nodes[blk.name] = z2
+        out = nodes[sp.decoder[-1].name]
+        return out, out.shape[1], out.shape[2]
+
+    # ------------------------------------------------------------------ EfficientUnet++ decoder (inference only)
+    def _pwconv(self, c: ConvSpec, params, bn: BnView, src0, src1, up0, B, H, W, act=False, gate=None, res=None, out=None):
+        """1x1 convolution c + eval BatchNorm (bias folded in) [+ Hardswish] [+ res] over the virtual input src0 (up-sampled
+        when up0) | src1, gated on load by (gc, s) — one dt_pwconv_affine launch"""
+        scale, shift = self._bn_eval_affine(c, params, bn)
+        C0 = src0.shape[-1]
+        C1 = 0 if src1 is None else src1.shape[-1]
+        assert C0 + C1 == c.cin, (c.key, C0, C1, c.cin)
+        if out is None:
+            out = torch.empty((B, H, W, c.cout), dtype=torch.float32, device=src0.device)
+        gc, gs = gate if gate is not None else (None, None)
+        e0 = self._pb()
+        self._call("dt_pwconv_affine", src0, src1, c.w(params), out, scale, shift, gc, gs, res, B, H, W, C0, C1,
+                   1 if up0 else 0, c.cout, 1 if act else 0)
+        if e0 is not None:
+            n = B * H * W
+            self._pe(e0, "pwconv_affine_kernel" + ("<gated>" if gate is not None else ""), 2.0 * n * c.cin * c.cout,
+                     4.0 * n * (C0 / (4 if up0 else 1) + C1 + c.cout * (2 if res is not None else 1) + (gate is not None))
+                     + 4.0 * c.cin * c.cout)
+        return out
+
+    def _mbconv(self, mb, params, bn: BnView, src0, src1, up0, B, H, W):
+        """one inverted-residual block (reference efficientunetplusplus/decoder.py:55-60) in four or five launches:
+        pw1 (+ Hardswish) -> depthwise (+ Hardswish, sSE logits, pooled partial sums) -> cSE gates -> [skip projection] ->
+        pw2 with the scSE gate applied while it stages its input and the residual in its epilogue"""
+        lib, dev = self.lib, src0.device
+        mid = mb.mid
+        a = self._pwconv(mb.pw1, params, bn, src0, src1, up0, B, H, W, act=True)
+        scale, shift = self._bn_eval_affine(mb.dw, params, bn)
+        P = self._rows("dt_dwconv3x3_rows", H, W)
+        b = torch.empty_like(a)
+        s = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        pool = torch.empty(B * mid * (1 + P), dtype=torch.float32, device=dev)    # gates [B,mid] | partial rows [B,P,mid]
+        gc, part = pool[:B * mid], pool[B * mid:]
+        e0 = self._pb()
+        self._call("dt_dwconv3x3_affine", a, mb.dw.w(params), scale, shift, mb.sse.w(params), mb.sse.bias(params), b, s,
+                   part, B, H, W, mid)
+        self._pe(e0, "dwconv3x3_affine_kernel", 2.0 * 9 * a.numel() + 2.0 * a.numel(), 4.0 * (2 * a.numel() + s.numel()))
+        del a
+        e0 = self._pb()
+        self._call("dt_scse_gates", part, mb.cse1.w(params), mb.cse1.bias(params), mb.cse2.w(params), mb.cse2.bias(params),
+                   gc, B, P, mid, mb.cse1.cout, H * W)
+        self._pe(e0, "scse_gates_kernel", 4.0 * B * mid * mb.cse1.cout, 4.0 * (part.numel() + 2 * mid * mb.cse1.cout))
+        if mb.skip is not None:      # the projection lands in the output tensor; pw2 then adds onto it in place
+            out = self._pwconv(mb.skip, params, bn, src0, src1, up0, B, H, W)
+            return self._pwconv(mb.pw2, params, bn, b, None, False, B, H, W, gate=(gc, s), res=out, out=out)
+        assert src1 is None and not up0
+        return self._pwconv(mb.pw2, params, bn, b, None, False, B, H, W, gate=(gc, s), res=src0)
+
+    def _forward_effunetpp(self, feats, params, bn: BnView, B):
+        """the reference's EfficientUnetPlusPlusDecoder (network/extra/efficientunetplusplus/decoder.py:156-184): the nodes
+        and wiring of _forward_unetpp, every node two inverted-residual blocks; conv1 reads the up-sampled lower node and
+        the concatenated skip as one virtual input (twice: pw1 and the skip projection)"""
+        sp = self.spec
+        nodes = {f"f{k}": feats[4 - k] for k in range(5)}     # f0 = deepest encoder feature ... f4 = stem output
+        for blk in sp.decoder:
+            low = nodes[blk.low]
+            H, W = 2 * low.shape[1], 2 * low.shape[2]
+            skip = None if not blk.cat else self._cat_channels([nodes[n] for n in blk.cat])[0]
+            z = self._mbconv(blk.conv1, params, bn, low, skip, True, B, H, W)
+            del skip
+            nodes[blk.name] = self._mbconv(blk.conv2, params, bn, z, None, False, B, H, W)
         out = nodes[sp.decoder[-1].name]
         return out, out.shape[1], out.shape[2]
 

@@ -137,10 +137,15 @@ class UNetHIP(nn.Module):
 
     def __init__(self, encoder_name: str = "resnet34", encoder_depth: int = 5, encoder_weights=None,
                  decoder_channels=(256, 128, 64, 32, 16), in_channels: int = 3, classes: int = 2,
-                 decoder: str = "unet", decoder_use_batchnorm=True, decoder_attention_type=None, **unused):
+                 decoder: str = "unet", decoder_use_batchnorm=True, decoder_attention_type=None, squeeze_ratio: int = 1,
+                 expansion_ratio: int = 1, **unused):
         """decoder "unet": smp.Unet; "resunet": the reference's in-tree ResUnet (network/extra/resunet/model.py:57-103 —
         residual decoder blocks with a 1x1 identity_conv, 1x1 segmentation head); "unetplusplus": smp.UnetPlusPlus (dense
-        nested decoder x_{depth}_{layer}, 3x3 head).  The two alternatives run on the fp32 path."""
+        nested decoder x_{depth}_{layer}, 3x3 head); "efficientunetplusplus": the reference's in-tree EfficientUnet++ decoder
+        on this encoder (network/extra/efficientunetplusplus/decoder.py: the same dense nodes, two inverted-residual blocks
+        with scSE each; ``squeeze_ratio`` / ``expansion_ratio`` as there) — INFERENCE ONLY: fp32, eval-mode BatchNorm; a
+        training-mode forward, bf16, ``update_bn`` and ``HipTrainer`` raise NotImplementedError (``inference_only``).
+        The alternatives run on the fp32 path."""
         super().__init__()
         if decoder_use_batchnorm is not True or decoder_attention_type is not None:
             raise NotImplementedError("only decoder_use_batchnorm=True / decoder_attention_type=None have HIP kernels")
@@ -148,7 +153,9 @@ class UNetHIP(nn.Module):
             raise NotImplementedError(f"encoder {encoder_name!r}: only resnet34 has HIP kernels")
         if encoder_depth != 5 or tuple(decoder_channels) != (256, 128, 64, 32, 16):
             raise NotImplementedError("only encoder_depth=5 / decoder_channels=(256,128,64,32,16)")
-        self.spec = build_spec(in_channels, classes, decoder)
+        self.spec = build_spec(in_channels, classes, decoder, squeeze_ratio, expansion_ratio)
+        # no backward and no bf16 kernels for the inverted-residual blocks: such a model only predicts
+        self.inference_only = decoder == "efficientunetplusplus"
         self.flat_params = nn.Parameter(torch.zeros(self.spec.n_params, dtype=torch.float32))
         self.register_buffer("bn_state", torch.zeros(BnView.state_floats(self.spec), dtype=torch.float32),
                              persistent=False)
@@ -205,16 +212,16 @@ class UNetHIP(nn.Module):
             if c.key.startswith("encoder."):
                 continue
             k = c.state_k
-            shape = (c.cout, c.cin, k, k)
+            shape = (c.cout, c.w_cin, k, k)
             w = torch.empty(shape)
             if c is self.spec.head:
                 nn.init.xavier_uniform_(w)
             else:
                 nn.init.kaiming_uniform_(w, mode="fan_in", nonlinearity="relu")
             sd[c.key] = w
-            if c.bn_key is None:
-                sd[c.key.replace(".weight", ".bias")] = torch.zeros(c.cout)
-            else:
+            if c.has_bias:
+                sd[c.bias_key] = torch.zeros(c.cout)
+            if c.bn_key is not None:
                 sd[f"{c.bn_key}.weight"] = torch.ones(c.cout)
                 sd[f"{c.bn_key}.bias"] = torch.zeros(c.cout)
         self.load_smp_state_dict(sd)
@@ -237,16 +244,16 @@ class UNetHIP(nn.Module):
         sd = {}
         for c in self.spec.convs:
             k = c.state_k
-            fan_in = c.cin * k * k
-            sd[c.key] = torch.randn((c.cout, c.cin, k, k), generator=g) * (2.0 / fan_in) ** 0.5
+            fan_in = c.w_cin * k * k
+            sd[c.key] = torch.randn((c.cout, c.w_cin, k, k), generator=g) * (2.0 / fan_in) ** 0.5
+            if c.has_bias:
+                sd[c.bias_key] = torch.zeros(c.cout)
             if c.bn_key is not None:
                 sd[f"{c.bn_key}.weight"] = torch.ones(c.cout)
                 sd[f"{c.bn_key}.bias"] = torch.zeros(c.cout)
                 sd[f"{c.bn_key}.running_mean"] = torch.zeros(c.cout)
                 sd[f"{c.bn_key}.running_var"] = torch.ones(c.cout)
                 sd[f"{c.bn_key}.num_batches_tracked"] = torch.tensor(0)
-            else:
-                sd[c.key.replace(".weight", ".bias")] = torch.zeros(c.cout)
         self.load_smp_state_dict(sd)
 
     @torch.no_grad()
@@ -267,10 +274,10 @@ class UNetHIP(nn.Module):
             return t
 
         for c in self.spec.convs:
-            w = get(c.key, (c.cout, c.cin, c.state_k, c.state_k))
+            w = get(c.key, (c.cout, c.w_cin, c.state_k, c.state_k))
             if w is not None:
                 if c.state_k != c.k:     # 1x1 head held as the centre tap of the 3x3 head kernel
-                    full = torch.zeros((c.cout, c.cin, c.k, c.k), dtype=torch.float32)
+                    full = torch.zeros((c.cout, c.w_cin, c.k, c.k), dtype=torch.float32)
                     full[:, :, c.k // 2, c.k // 2] = w[:, :, 0, 0]
                     w = full
                 if c.layout == "hwio":
@@ -286,10 +293,10 @@ class UNetHIP(nn.Module):
                 k = f"{c.bn_key}.num_batches_tracked"
                 if k in sd:
                     nbt[c.index] = int(sd[k])
-            else:
-                t = get(c.key.replace(".weight", ".bias"), (c.cout,))
+            if c.has_bias:
+                t = get(c.bias_key, (c.cout,))
                 if t is not None:
-                    c.bias(flat).copy_(t)
+                    c.conv_bias(flat).copy_(t)
         if strict and missing:
             raise RuntimeError(f"missing keys in state_dict: {missing[:8]}{'...' if len(missing) > 8 else ''}")
         self.flat_params.data.copy_(flat.to(self.flat_params.device))
@@ -307,7 +314,9 @@ class UNetHIP(nn.Module):
         out = {}
         for c in self.spec.convs:
             if c.bn_key is not None:
-                out[prefix + c.key] = c.w(flat).reshape(c.k, c.k, c.cin, c.cout).permute(3, 2, 0, 1).contiguous()
+                out[prefix + c.key] = c.w(flat).reshape(c.k, c.k, c.w_cin, c.cout).permute(3, 2, 0, 1).contiguous()
+                if c.has_cbias:
+                    out[prefix + c.bias_key] = c.conv_bias(flat).clone()
                 out[prefix + f"{c.bn_key}.weight"] = c.gamma(flat).clone()
                 out[prefix + f"{c.bn_key}.bias"] = c.beta(flat).clone()
                 out[prefix + f"{c.bn_key}.running_mean"] = bn.running_mean(c).clone()
@@ -315,7 +324,7 @@ class UNetHIP(nn.Module):
                 out[prefix + f"{c.bn_key}.num_batches_tracked"] = nbt[c.index].clone()
             else:
                 out[prefix + c.key] = self._oihw(c.w(flat), c)
-                out[prefix + c.key.replace(".weight", ".bias")] = c.bias(flat).clone()
+                out[prefix + c.bias_key] = c.bias(flat).clone()
         return out
 
     @staticmethod
@@ -381,8 +390,29 @@ class UNetHIP(nn.Module):
         if self.flat_params.device != x.device:
             raise RuntimeError(f"model on {self.flat_params.device}, input on {x.device}: call model.to(device)")
 
+    def _require_trainable(self, what: str):
+        """the inverted-residual blocks have forward inference kernels only: refuse BEFORE anything runs"""
+        if self.inference_only:
+            raise NotImplementedError(f"{what}: decoder {self.spec.decoder_kind!r} is inference only in this build — its "
+                                      "blocks (depthwise 3x3, scSE, Hardswish) have no backward / batch-statistics and no "
+                                      "bf16 kernels; use model.eval() with fp32 prediction")
+
+    @property
+    def precision(self) -> str:
+        return self._precision
+
+    @precision.setter
+    def precision(self, value: str):
+        if value == "bf16":
+            self._require_trainable('precision="bf16" (missing bf16 path)')
+        self._precision = value
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.training:
+            self._require_trainable("training-mode forward (missing backward path)")
         self._require_gpu(x)
+        if self.inference_only:     # never through autograd: there is no backward to hand the graph
+            return self.engine.forward(x.float(), self.flat_params.detach(), self.bn_state, False, save=False)[0]
         x = x.float()
         if torch.is_grad_enabled() and self.flat_params.requires_grad:
             return _UNetFunction.apply(x, self.flat_params, self)
@@ -396,6 +426,8 @@ class UNetHIP(nn.Module):
         """forward + argmax fused in the head kernel (deployment/inference.py:60-62), eval-mode BN.
         precision "bf16": bf16 activations/weights with fp32 accumulation (the AMP setting of the reference's
         training protocol) — class maps agree with fp32 wherever the logit margin exceeds bf16 rounding."""
+        if precision == "bf16":
+            self._require_trainable('precision="bf16" (missing bf16 path)')
         self._require_gpu(x)
         if precision == "bf16":
             if nhwc:
@@ -417,6 +449,8 @@ class UNetHIP(nn.Module):
     def predict_logits(self, x: torch.Tensor, precision: str = "fp32", nhwc: bool = False) -> torch.Tensor:
         """the fp32 NCHW logits ``predict_classes`` takes its argmax of (same forward, eval-mode BN, same ``precision`` /
         ``nhwc`` meaning): what the overlap-stitch blend reads"""
+        if precision == "bf16":
+            self._require_trainable('precision="bf16" (missing bf16 path)')
         self._require_gpu(x)
         if precision == "bf16":
             if nhwc:
@@ -434,6 +468,7 @@ class UNetHIP(nn.Module):
     @torch.no_grad()
     def forward_bf16(self, x: torch.Tensor) -> torch.Tensor:
         """eval-mode logits (fp32 tensor) from the bf16 path"""
+        self._require_trainable('precision="bf16" (missing bf16 path)')
         self._require_gpu(x)
         logits, _ = self.engine.forward_bf16_eval(x.float(), self.flat_params.detach(), self.bn_state)
         return logits
@@ -471,6 +506,7 @@ class UNetHIP(nn.Module):
     def recalibrate_batch(self, x: torch.Tensor, precision: Optional[str] = None):
         """one batch of ``update_bn``: advance the device batch count (momentum = 1 / count), then the statistics-only
         forward.  Launches the same kernels with the same arguments for every batch of one shape: capturable."""
+        self._require_trainable("update_bn (missing batch-statistics forward)")
         self._require_gpu(x)
         n_dev, mom = self._recal_state()
         eng = self.engine
@@ -493,6 +529,7 @@ class UNetHIP(nn.Module):
         precision: "fp32" / "bf16" (default: ``self.precision``).  Batches: tensors, ``(img, ...)`` tuples or the
         datamodule's dicts.  One deliberate difference from torch: an empty iterable raises ``ValueError`` BEFORE any
         state changes (torch would leave every BatchNorm at mean 0 / variance 1)."""
+        self._require_trainable("update_bn (missing batch-statistics forward)")
         precision = precision or self.precision
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"precision {precision!r}: use 'fp32' or 'bf16'")

@@ -90,11 +90,18 @@ def create_combined_batch(batch: Dict[str, Any]):
 
 _SUPPORTED_ELSEWHERE = ("resunetplusplus", "resunet++",
                         "efficientunetplusplus", "efficientunet++")
+_INFERENCE_ONLY = ("efficientunetplusplus", "efficientunet++")
 
 
 class SemSegment(_Base):
-    def __init__(self, network, training):
+    def __init__(self, network, training, inference_only: bool = False):
+        """inference_only=True: a module that only predicts — it also accepts the architectures whose blocks have forward
+        inference kernels but no backward (``efficientunet++`` on resnet34; ``squeeze_ratio`` / ``expansion_ratio`` in
+        `network` as the reference's EfficientUnetPlusPlus takes them), comes back in eval mode, and its training hooks
+        (``train()``, ``training_step``, ``configure_optimizers``) raise NotImplementedError.  The plain constructor
+        promises a trainable module and keeps refusing them."""
         super().__init__()
+        self.inference_only = bool(inference_only)
         network = to_attrdict(network)
         training = to_attrdict(training)
         architecture = network.architecture.lower().strip()
@@ -106,6 +113,9 @@ class SemSegment(_Base):
         elif architecture in ("unetplusplus", "unet++"):   # smp.UnetPlusPlus (segmodel.py:64-65): dense nested decoder
             def Model(**kw):
                 return UNetHIP(decoder="unetplusplus", **kw)
+        elif inference_only and architecture in _INFERENCE_ONLY:
+            def Model(**kw):                # the reference's in-tree EfficientUnet++ decoder (segmodel.py:68-71)
+                return UNetHIP(decoder="efficientunetplusplus", **kw)
         elif architecture in _SUPPORTED_ELSEWHERE:
             raise NotImplementedError(
                 f"architecture {architecture!r} exists in the reference but has no MI355X kernels in this build "
@@ -160,6 +170,19 @@ class SemSegment(_Base):
         # device-side confusion counts [2,K,K] per stage (all pixels / lu == 1), instead of concatenating every
         # int64 mask of the epoch (reference validation_epoch_end / test_epoch_end, segmodel.py:291-407)
         self._cm = {}
+        if self.inference_only:
+            super().train(False)
+
+    # ------------------------------------------------------------------ inference-only modules
+    def _refuse_training(self, what: str):
+        if self.inference_only:
+            raise NotImplementedError(f"{what}: this SemSegment was built with inference_only=True (architecture "
+                                      f"{self.hparams['network']['architecture']!r} has no training path in this build)")
+
+    def train(self, mode: bool = True):
+        if mode:
+            self._refuse_training("train()")
+        return super().train(mode)
 
     # ------------------------------------------------------------------ reference helpers
     @property
@@ -227,6 +250,7 @@ class SemSegment(_Base):
 
     # ------------------------------------------------------------------ steps
     def training_step(self, batch, batch_idx):
+        self._refuse_training("training_step")
         img, mask, distmap, _, stats = create_combined_batch(batch)
         logits = self.model(img)
         loss = self.calculate_loss(logits, mask, "train", distmap=distmap)
@@ -294,6 +318,7 @@ class SemSegment(_Base):
                 w.writerows(dict(self.stats[name]).items())
 
     def configure_optimizers(self):
+        self._refuse_training("configure_optimizers")
         opt = torch.optim.Adam(self.parameters(), lr=self.hparams["training"]["learning_rate"])
         sch = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=self.hparams["training"]["cosineannealing_tmax"])
         return [opt], [sch]
@@ -318,8 +343,13 @@ class SemSegment(_Base):
             ck = None
         if ck is not None and "hyper_parameters_json" in ck:
             hp = json.loads(ck["hyper_parameters_json"])
-            m = cls(hp["network"], hp["training"])
-            m.model.load_smp_state_dict({k[len("model."):]: v for k, v in ck["state_dict"].items()})
+            sd = {k[len("model."):]: v for k, v in ck["state_dict"].items()}
+            from ..utils.ckpt import EFFUNETPP_KEY, infer_mbconv_ratios
+            net, only = hp["network"], EFFUNETPP_KEY in sd
+            if only:     # inverted-residual decoder: an inference-only module, its two ratios read off the tensor shapes
+                net = dict(net, **infer_mbconv_ratios(sd))
+            m = cls(net, hp["training"], inference_only=only)
+            m.model.load_smp_state_dict(sd)
             return m
         # a checkpoint written by the reference's Lightning trainer: tensors through the restricted reader (nothing
         # in the file is imported or executed), network configuration from the tensor shapes, default training conf
@@ -328,7 +358,7 @@ class SemSegment(_Base):
         sd = lightning_state_dict(path)
         net = infer_network_conf(sd)
         net["losses"] = ["GDICE", "FOCAL"]
-        m = cls(net, default_training())
+        m = cls(net, default_training(), inference_only=net["architecture"] in _INFERENCE_ONLY)
         m.model.load_smp_state_dict(sd)
         return m
 

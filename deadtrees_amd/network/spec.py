@@ -36,10 +36,27 @@ class ConvSpec:
     index: int = 0
     layout: str = "hwio"     # flat-buffer layout of the weight: "hwio" (convolution kernels) or "ohwi" (head kernel)
     sd_k: int = 0            # kernel size in the state_dict when it differs from k (1x1 head held as a 3x3 centre tap)
+    depthwise: bool = False  # groups = cin = cout: weight [C,1,k,k] in the state_dict, [k*k][C] in the flat buffer
+    has_cbias: bool = False  # a convolution bias IN FRONT of the BatchNorm (the EfficientUnet++ blocks' nn.Conv2d defaults)
+    cb_off: int = 0          # its offset in the flat parameter buffer
 
     @property
     def state_k(self) -> int:
         return self.sd_k or self.k
+
+    @property
+    def w_cin(self) -> int:
+        """input channels per group: the I of the OIHW / HWIO weight"""
+        return 1 if self.depthwise else self.cin
+
+    @property
+    def bias_key(self) -> str:
+        return self.key[:-len("weight")] + "bias"
+
+    @property
+    def has_bias(self) -> bool:
+        """a bias tensor under ``bias_key``: every convolution without BatchNorm, and the biased ones in front of one"""
+        return self.bn_key is None or self.has_cbias
 
     # ---- this convolution's ranges of any tensor laid out like the flat parameter buffer (params, grads, the bf16 /
     # flipped weight images) and its output size: the ONE place that spells the flat-buffer layout
@@ -55,6 +72,10 @@ class ConvSpec:
 
     bias = beta
 
+    def conv_bias(self, flat):
+        """the convolution's own bias: in front of a BatchNorm (has_cbias) or, without one, what ``beta`` holds"""
+        return flat[self.cb_off:self.cb_off + self.cout] if self.has_cbias else self.beta(flat)
+
     def out_size(self, n: int) -> int:
         return (n + 2 * self.pad - self.k) // self.stride + 1
 
@@ -67,8 +88,36 @@ class BlockSpec:
 
 
 @dataclass
+class MBConvSpec:
+    """inverted-residual block of the EfficientUnet++ decoder (reference efficientunetplusplus/decoder.py:9-60):
+    pw1 + BN + Hardswish, depthwise 3x3 + BN + Hardswish, scSE (cse1 / cse2 / sse), pw2 + BN, plus the input or skip + BN"""
+    pw1: ConvSpec
+    dw: ConvSpec
+    cse1: ConvSpec
+    cse2: ConvSpec
+    sse: ConvSpec
+    pw2: ConvSpec
+    skip: Optional[ConvSpec] = None
+
+    @property
+    def cin(self) -> int:
+        return self.pw1.cin
+
+    @property
+    def mid(self) -> int:
+        return self.pw1.cout
+
+    @property
+    def cout(self) -> int:
+        return self.pw2.cout
+
+    def convs(self):
+        return [c for c in (self.pw1, self.dw, self.cse1, self.cse2, self.sse, self.pw2, self.skip) if c is not None]
+
+
+@dataclass
 class DecBlockSpec:
-    conv1: ConvSpec
+    conv1: ConvSpec                  # EfficientUnet++: MBConvSpec
     conv2: ConvSpec
     in_ch: int = 0
     skip_ch: int = 0
@@ -82,8 +131,11 @@ class DecBlockSpec:
 class UNetSpec:
     in_channels: int
     classes: int
-    decoder_kind: str = "unet"     # "unet" (smp Unet decoder), "resunet" (reference network/extra/resunet/decoder.py) or
+    decoder_kind: str = "unet"     # "unet" (smp Unet decoder), "resunet" (reference network/extra/resunet/decoder.py),
                                    # "unetplusplus" (smp UnetPlusPlus: dense wiring of extra/efficientunetplusplus/decoder.py)
+                                   # or "efficientunetplusplus" (that file's own decoder: inverted-residual blocks, inference only)
+    squeeze_ratio: int = 1         # EfficientUnet++: cSE hidden width = mid // squeeze_ratio
+    expansion_ratio: int = 1       # EfficientUnet++: mid = expansion_ratio * block input channels
     stem: ConvSpec = None
     layers: List[List[BlockSpec]] = field(default_factory=list)
     decoder: List[DecBlockSpec] = field(default_factory=list)
@@ -95,16 +147,39 @@ class UNetSpec:
     buckets: list = field(default_factory=list)  # gradient-ready order: [(name, lo, hi)] ranges of the flat buffer
 
 
-def build_spec(in_channels: int = 3, classes: int = 2, decoder: str = "unet") -> UNetSpec:
-    if decoder not in ("unet", "resunet", "unetplusplus"):
-        raise ValueError(f"decoder {decoder!r}: 'unet', 'resunet' or 'unetplusplus'")
-    s = UNetSpec(in_channels, classes, decoder)
+DENSE_DECODERS = ("unetplusplus", "efficientunetplusplus")
+
+
+def build_spec(in_channels: int = 3, classes: int = 2, decoder: str = "unet", squeeze_ratio: int = 1,
+               expansion_ratio: int = 1) -> UNetSpec:
+    if decoder not in ("unet", "resunet") + DENSE_DECODERS:
+        raise ValueError(f"decoder {decoder!r}: 'unet', 'resunet', 'unetplusplus' or 'efficientunetplusplus'")
+    eff = decoder == "efficientunetplusplus"
+    if not eff and (squeeze_ratio != 1 or expansion_ratio != 1):
+        raise ValueError("squeeze_ratio / expansion_ratio belong to decoder 'efficientunetplusplus'")
+    if squeeze_ratio < 1 or expansion_ratio < 1 or 16 % squeeze_ratio:
+        raise ValueError(f"squeeze_ratio {squeeze_ratio} must divide 16, expansion_ratio {expansion_ratio} must be positive")
+    s = UNetSpec(in_channels, classes, decoder, squeeze_ratio, expansion_ratio)
     convs: List[ConvSpec] = []
 
-    def conv(key, bn_key, cin, cout, k, stride, pad):
-        c = ConvSpec(key, bn_key, cin, cout, k, stride, pad)
+    def conv(key, bn_key, cin, cout, k, stride, pad, **kw):
+        c = ConvSpec(key, bn_key, cin, cout, k, stride, pad, **kw)
         convs.append(c)
         return c
+
+    def mbconv(p, cin, cout):
+        """keys: the nn.Sequential indices of the reference's block (0 pw1, 1 BN, 3 depthwise, 4 BN, 6 scSE, 7 pw2, 8 BN)"""
+        mid = expansion_ratio * cin
+        b = f"{p}.block"
+        return MBConvSpec(
+            pw1=conv(f"{b}.0.weight", f"{b}.1", cin, mid, 1, 1, 0, has_cbias=True),
+            dw=conv(f"{b}.3.weight", f"{b}.4", mid, mid, 3, 1, 1, has_cbias=True, depthwise=True),
+            cse1=conv(f"{b}.6.cSE.1.weight", None, mid, mid // squeeze_ratio, 1, 1, 0),
+            cse2=conv(f"{b}.6.cSE.3.weight", None, mid // squeeze_ratio, mid, 1, 1, 0),
+            sse=conv(f"{b}.6.sSE.0.weight", None, mid, 1, 1, 1, 0),
+            pw2=conv(f"{b}.7.weight", f"{b}.8", mid, cout, 1, 1, 0, has_cbias=True),
+            skip=conv(f"{p}.skip_conv.0.weight", f"{p}.skip_conv.1", cin, cout, 1, 1, 0, has_cbias=True)
+            if cin != cout else None)
 
     s.stem = conv("encoder.conv1.weight", "encoder.bn1", in_channels, 64, 7, 2, 3)
     inpl = 64
@@ -124,7 +199,7 @@ def build_spec(in_channels: int = 3, classes: int = 2, decoder: str = "unet") ->
     enc = [512, 256, 128, 64, 64]
     in_ch = [enc[0]] + list(DECODER_CHANNELS[:-1])
     skip_ch = enc[1:] + [0]
-    if decoder == "unetplusplus":
+    if decoder in DENSE_DECODERS:
         # smp UnetPlusPlusDecoder: block x_{d}_{l} for l = 0..3, d = 0..l, plus x_0_4 (channel arithmetic and wiring as
         # executed in reference network/extra/efficientunetplusplus/decoder.py:133-184, which copies it); blocks in
         # FORWARD order, features f0..f4 = encoder outputs from the deepest (512 ch) to the stem (64 ch)
@@ -149,8 +224,11 @@ def build_spec(in_channels: int = 3, classes: int = 2, decoder: str = "unet") ->
         for (d, l), low, cat in order:
             ic, sc, oc = chans[(d, l)]
             p = f"decoder.blocks.x_{d}_{l}"
-            c1 = conv(f"{p}.conv1.0.weight", f"{p}.conv1.1", ic + sc, oc, 3, 1, 1)
-            c2 = conv(f"{p}.conv2.0.weight", f"{p}.conv2.1", oc, oc, 3, 1, 1)
+            if eff:     # the same nodes, two inverted-residual blocks each
+                c1, c2 = mbconv(f"{p}.conv1", ic + sc, oc), mbconv(f"{p}.conv2", oc, oc)
+            else:
+                c1 = conv(f"{p}.conv1.0.weight", f"{p}.conv1.1", ic + sc, oc, 3, 1, 1)
+                c2 = conv(f"{p}.conv2.0.weight", f"{p}.conv2.1", oc, oc, 3, 1, 1)
             s.decoder.append(DecBlockSpec(c1, c2, ic, sc, None, f"x_{d}_{l}", low, cat))
         in_ch, skip_ch = [], []     # the plain decoder loop below adds nothing
     for i, (ic, sc, oc) in enumerate(zip(in_ch, skip_ch, DECODER_CHANNELS)):
@@ -171,10 +249,14 @@ def build_spec(in_channels: int = 3, classes: int = 2, decoder: str = "unet") ->
     true = 0
     for i, c in enumerate(convs):
         c.index = i
-        c.w_size = c.k * c.k * c.cin * c.cout
+        c.w_size = c.k * c.k * c.w_cin * c.cout
         c.w_off = off
         off = _align4(off + c.w_size)
-        true += c.state_k * c.state_k * c.cin * c.cout
+        true += c.state_k * c.state_k * c.w_cin * c.cout
+        if c.has_cbias:
+            c.cb_off = off
+            off = _align4(off + c.cout)
+            true += c.cout
         if c.bn_key is not None:
             c.g_off = off
             off = _align4(off + c.cout)
@@ -198,7 +280,10 @@ def build_spec(in_channels: int = 3, classes: int = 2, decoder: str = "unet") ->
         hi = max(_align4(c.b_off + c.cout) for c in cs)
         return lo, hi
 
-    dec_convs = [c for d in s.decoder for c in (d.conv1, d.conv2, d.idc) if c is not None] + [s.head]
+    if eff:
+        dec_convs = [c for d in s.decoder for mb in (d.conv1, d.conv2) for c in mb.convs()] + [s.head]
+    else:
+        dec_convs = [c for d in s.decoder for c in (d.conv1, d.conv2, d.idc) if c is not None] + [s.head]
     s.buckets.append(("head+decoder",) + rng(dec_convs))
     for li in (3, 2, 1, 0):
         cs = [c for b in s.layers[li] for c in (b.conv1, b.conv2, b.down) if c is not None]
@@ -212,11 +297,11 @@ def smp_param_shapes(spec: UNetSpec):
     """{smp_key: shape} for every tensor of the smp state_dict (params and BN buffers)."""
     out = {}
     for c in spec.convs:
-        out[c.key] = (c.cout, c.cin, c.state_k, c.state_k)
+        out[c.key] = (c.cout, c.w_cin, c.state_k, c.state_k)
         if c.bn_key is not None:
             for n in ("weight", "bias", "running_mean", "running_var"):
                 out[f"{c.bn_key}.{n}"] = (c.cout,)
             out[f"{c.bn_key}.num_batches_tracked"] = ()
-        else:
-            out[c.key.replace(".weight", ".bias")] = (c.cout,)
+        if c.has_bias:
+            out[c.bias_key] = (c.cout,)
     return out

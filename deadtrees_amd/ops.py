@@ -371,6 +371,116 @@ def eval_accumulate(parts, weight: float, epoch):
     return epoch
 
 
+# ---------------------------------------------------------------------- inverted-residual block (csrc/mbconv.hip), inference
+def _f32c(what, t, shape=None):
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise RuntimeError(f"{what} must be a contiguous float32 tensor, got {t.dtype} {tuple(t.shape)}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{what} {tuple(t.shape)} must be {list(shape)}")
+    return t
+
+
+def pwconv_affine(src0, w_io, scale, shift, src1=None, up0=False, gate=None, act=False, res=None, out=None, hw=None):
+    """pointwise convolution through dt_pwconv_affine: out = act(a @ w_io * scale + shift) [+ res], a = the virtual input
+    cat(src0 or its nearest x2 up-sampling, src1) [B,H,W,C0+C1], optionally gated: a[p,k] *= gc[b,k] + sigmoid(s[p]) with
+    gate = (gc [B,K], s [B,H,W]).  act: Hardswish.  res [B,H,W,Cout] may be `out` itself.  hw: (H, W) of the output when
+    src0 is up-sampled to an odd size (src0 then is [B,(H+1)//2,(W+1)//2,C0]; default: twice its size)."""
+    _gpu(src0, src1, w_io, scale, shift, res, out)
+    if src0.dim() != 4:
+        raise RuntimeError(f"pwconv_affine: src0 must be [B,H,W,C], got {tuple(src0.shape)}")
+    B, Hs, Ws, C0 = src0.shape
+    H, W = (hw if hw is not None else (2 * Hs, 2 * Ws)) if up0 else (Hs, Ws)
+    if up0 and ((H + 1) // 2 != Hs or (W + 1) // 2 != Ws):
+        raise RuntimeError(f"pwconv_affine: src0 {Hs}x{Ws} is not the half-size source of a {H}x{W} output")
+    _f32c("pwconv_affine: src0", src0)
+    C1 = 0
+    if src1 is not None:
+        C1 = src1.shape[-1]
+        _f32c("pwconv_affine: src1", src1, (B, H, W, C1))
+    K = C0 + C1
+    if w_io.dim() != 2 or w_io.shape[0] != K:
+        raise RuntimeError(f"pwconv_affine: w_io {tuple(w_io.shape)} must be [{K}, Cout]")
+    N = w_io.shape[1]
+    _f32c("pwconv_affine: w_io", w_io)
+    _f32c("pwconv_affine: scale", scale, (N,))
+    _f32c("pwconv_affine: shift", shift, (N,))
+    gc = gs = None
+    if gate is not None:
+        gc, gs = gate
+        _gpu(gc, gs)
+        _f32c("pwconv_affine: channel gate", gc, (B, K))
+        _f32c("pwconv_affine: spatial gate", gs, (B, H, W))
+    if out is None:
+        out = torch.empty((B, H, W, N), dtype=torch.float32, device=src0.device)
+    _f32c("pwconv_affine: out", out, (B, H, W, N))
+    if res is not None:
+        _f32c("pwconv_affine: res", res, (B, H, W, N))
+    _lib.check(_lib.load().dt_pwconv_affine(_p(src0), _p(src1), _p(w_io), _p(out), _p(scale), _p(shift), _p(gc), _p(gs),
+                                            _p(res), B, H, W, C0, C1, 1 if up0 else 0, N, 1 if act else 0, _st()),
+               "dt_pwconv_affine")
+    return out
+
+
+def dwconv3x3_affine(x, w_tc, scale, shift, sse_w, sse_b):
+    """depthwise 3x3 (stride 1, pad 1) through dt_dwconv3x3_affine: b = hardswish(dw(x) * scale + shift) plus the two side
+    outputs of the same pass -> (b [B,H,W,C], s [B,H,W] = sse_w . b + sse_b, pool): pool is one buffer, the [B,C] channel
+    gates ``scse_gates`` writes in front and the [B,P,C] per-workgroup channel sums of b behind them (``pool_rows``)."""
+    _gpu(x, w_tc, scale, shift, sse_w, sse_b)
+    lib = _lib.load()
+    if x.dim() != 4:
+        raise RuntimeError(f"dwconv3x3_affine: x must be [B,H,W,C], got {tuple(x.shape)}")
+    B, H, W, Cc = x.shape
+    _f32c("dwconv3x3_affine: x", x)
+    _f32c("dwconv3x3_affine: w_tc", w_tc, (9, Cc))
+    for what, t in (("scale", scale), ("shift", shift), ("sse_w", sse_w)):
+        _f32c(f"dwconv3x3_affine: {what}", t, (Cc,))
+    _f32c("dwconv3x3_affine: sse_b", sse_b, (1,))
+    P = lib.dt_dwconv3x3_rows(H, W)
+    if P <= 0:
+        raise RuntimeError(f"dt_dwconv3x3_rows: {lib.dt_last_error().decode()}")
+    out = torch.empty_like(x)
+    s = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+    pool = torch.empty(B * Cc * (1 + P), dtype=torch.float32, device=x.device)
+    _lib.check(lib.dt_dwconv3x3_affine(_p(x), _p(w_tc), _p(scale), _p(shift), _p(sse_w), _p(sse_b), _p(out), _p(s),
+                                       _p(pool[B * Cc:]), B, H, W, Cc, _st()), "dt_dwconv3x3_affine")
+    return out, s, pool
+
+
+def pool_rows(pool, B, Cc):
+    """the [B,P,C] partial channel sums of a ``dwconv3x3_affine`` pool buffer"""
+    return pool[B * Cc:].view(B, -1, Cc)
+
+
+def scse_gates(pool, B, Cc, HW, w1_io, b1, w2_io, b2):
+    """cSE gate through dt_scse_gates: the rows of `pool` (``dwconv3x3_affine``) reduced per image in a fixed order to the
+    mean over HW pixels, then gc = sigmoid(W2 relu(W1 mean + b1) + b2) -> [B,C], written into the front of `pool`"""
+    _gpu(pool, w1_io, b1, w2_io, b2)
+    _f32c("scse_gates: pool", pool)
+    if pool.numel() % (B * Cc) or pool.numel() < 2 * B * Cc:
+        raise RuntimeError(f"scse_gates: pool of {pool.numel()} floats is not [B*C + B*P*C] for B={B}, C={Cc}")
+    P = pool.numel() // (B * Cc) - 1
+    if w1_io.dim() != 2 or w1_io.shape[0] != Cc:
+        raise RuntimeError(f"scse_gates: w1_io {tuple(w1_io.shape)} must be [{Cc}, hidden]")
+    Ch = w1_io.shape[1]
+    _f32c("scse_gates: w1_io", w1_io)
+    _f32c("scse_gates: b1", b1, (Ch,))
+    _f32c("scse_gates: w2_io", w2_io, (Ch, Cc))
+    _f32c("scse_gates: b2", b2, (Cc,))
+    _lib.check(_lib.load().dt_scse_gates(_p(pool[B * Cc:]), _p(w1_io), _p(b1), _p(w2_io), _p(b2), _p(pool), B, P, Cc, Ch,
+                                         HW, _st()), "dt_scse_gates")
+    return pool[:B * Cc].view(B, Cc)
+
+
+def bn_eval_affine_bias(gamma, beta, running_mean, running_var, bias, eps=1e-5):
+    """eval BatchNorm behind a biased convolution as per-channel (scale, shift): dt_bn_eval_affine_bias"""
+    _gpu(gamma, beta, running_mean, running_var, bias)
+    n = gamma.numel()
+    scale, shift = torch.empty_like(gamma), torch.empty_like(gamma)
+    _lib.check(_lib.load().dt_bn_eval_affine_bias(_p(gamma), _p(beta), _p(running_mean), _p(running_var), _p(bias),
+                                                  float(eps), n, _p(scale), _p(shift), _st()), "dt_bn_eval_affine_bias")
+    return scale, shift
+
+
 def head_bwd(x, w_ohwi, dlogits):
     _gpu(x, w_ohwi, dlogits)
     lib = _lib.load()

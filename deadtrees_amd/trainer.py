@@ -62,6 +62,8 @@ class HipTrainer:
         graph=True: after two eager steps the whole step (forward, loss, backward, clip, Adam) is captured into a
         HIP graph and replayed — ~750 kernel launches become one, which matters once the bf16 step is shorter than
         the Python launch path."""
+        if getattr(model, "inference_only", False):
+            model._require_trainable("HipTrainer (missing backward path)")
         if not model.flat_params.is_cuda:
             raise RuntimeError("HipTrainer needs the model on an MI355X (model.to('cuda'))")
         self.model = model
@@ -653,15 +655,19 @@ def checkpoint_writer(trainer: "HipTrainer", pl_module=None, training_conf: Opti
     """path -> one ``.ckpt`` in ``SemSegment.save_checkpoint``'s payload (``SemSegment.load_from_checkpoint`` and
     ``PyTorchInference(path)`` read it).  With a ``pl_module`` that has ``save_checkpoint``: that method.  Otherwise
     the same payload from the model's own configuration: architecture, channels and class count of its spec, the
-    trainer's loss list, ``encoder_weights`` None (the file holds the encoder's tensors; nothing is to be fetched again)."""
+    trainer's loss list, ``encoder_weights`` None (the file holds the encoder's tensors; nothing is to be fetched again).
+    `trainer` may be the ``UNetHIP`` itself: an inference-only model (EfficientUnet++ decoder, say one converted from a
+    reference checkpoint) has no trainer; its file records the default loss list and the decoder's two ratios."""
     if pl_module is not None and hasattr(pl_module, "save_checkpoint"):
         return pl_module.save_checkpoint
     from .utils.config import default_network, default_training
-    model = trainer.model
+    model = trainer if isinstance(trainer, UNetHIP) else trainer.model
     K = model.spec.classes
     classes = ["background", "deadtree"] if K == 2 else ["background"] + [f"class{i}" for i in range(1, K)]
     net = dict(default_network(architecture=model.spec.decoder_kind, in_channels=model.spec.in_channels, classes=classes,
-                               losses=list(trainer.losses)))
+                               losses=list(getattr(trainer, "losses", ("GDICE", "FOCAL")))))
+    if model.spec.decoder_kind == "efficientunetplusplus":
+        net.update(squeeze_ratio=model.spec.squeeze_ratio, expansion_ratio=model.spec.expansion_ratio)
     hp = {"network": net, "training": dict(default_training(**(training_conf or {})))}
 
     def save(path):

@@ -138,9 +138,24 @@ def lightning_state_dict(path, prefix: str = "model.") -> Dict[str, torch.Tensor
     return out
 
 
+EFFUNETPP_KEY = "decoder.blocks.x_0_0.conv1.block.0.weight"     # the first 1x1 of an inverted-residual decoder
+
+
+def infer_mbconv_ratios(sd: Dict[str, torch.Tensor]) -> Dict[str, int]:
+    """squeeze_ratio / expansion_ratio of an EfficientUnet++ decoder from its tensors: the first 1x1 is [mid, in, 1, 1]
+    with mid = expansion_ratio * in, the first cSE layer [mid // squeeze_ratio, mid, 1, 1]"""
+    pw1 = sd[EFFUNETPP_KEY]
+    cse = sd[EFFUNETPP_KEY.replace("block.0.weight", "block.6.cSE.1.weight")]
+    mid, cin, hidden = int(pw1.shape[0]), int(pw1.shape[1]), int(cse.shape[0])
+    if mid % cin or hidden <= 0 or mid % hidden:
+        raise RuntimeError(f"EfficientUnet++ decoder: inconsistent block shapes {tuple(pw1.shape)} / {tuple(cse.shape)}")
+    return {"squeeze_ratio": mid // hidden, "expansion_ratio": mid // cin}
+
+
 def infer_network_conf(sd: Dict[str, torch.Tensor]) -> Dict[str, Any]:
     """in_channels / classes / encoder of an smp ``Unet`` from its tensors (the pickled hyper-parameters are not
-    trusted or needed): stem weight [64, Cin, 7, 7], head weight [K, 16, 3, 3]; resnet34 has 3/4/6/3 blocks."""
+    trusted or needed): stem weight [64, Cin, 7, 7], head weight [K, 16, 3, 3]; resnet34 has 3/4/6/3 blocks.  A decoder
+    of inverted-residual blocks (``EFFUNETPP_KEY``) -> architecture "efficientunet++" with its two ratios."""
     stem, head = sd.get("encoder.conv1.weight"), sd.get("segmentation_head.0.weight")
     if stem is None or head is None:
         raise RuntimeError("checkpoint is not an smp Unet with a torchvision-ResNet encoder")
@@ -149,5 +164,8 @@ def infer_network_conf(sd: Dict[str, torch.Tensor]) -> Dict[str, Any]:
         raise NotImplementedError(f"encoder with blocks {blocks}: only resnet34 has HIP kernels")
     K = int(head.shape[0])
     classes = ["background", "deadtree"] if K == 2 else ["background", "conifers", "deciduous"][:K]
-    return {"architecture": "unet", "encoder_name": "resnet34", "encoder_depth": 5, "encoder_weights": None,
-            "in_channels": int(stem.shape[1]), "classes": classes}
+    net = {"architecture": "unet", "encoder_name": "resnet34", "encoder_depth": 5, "encoder_weights": None,
+           "in_channels": int(stem.shape[1]), "classes": classes}
+    if EFFUNETPP_KEY in sd:
+        net.update(architecture="efficientunet++", **infer_mbconv_ratios(sd))
+    return net

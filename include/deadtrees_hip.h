@@ -678,6 +678,36 @@ int dt_weight_average(float* avg, const float* p, int64_t n, int64_t* count_dev,
  * dt_bn_finalize_dev reads that momentum from the device. */
 int dt_cma_advance(int64_t* n_dev, float* momentum_dev, void* stream);
 
+/* ------------------------------------------------------------------ inverted-residual block (EfficientUnet++ decoder), inference
+ * Reference: network/extra/efficientunetplusplus/decoder.py InvertedResidual — ATen chain conv2d(1x1) -> batch_norm(eval)
+ * -> hardswish_ -> conv2d(3x3, groups=C) -> batch_norm -> hardswish_ -> scSE (adaptive_avg_pool2d, two 1x1 conv2d, relu_,
+ * sigmoid; 1x1 conv2d C -> 1, sigmoid; x * cSE + x * sSE) -> conv2d(1x1) -> batch_norm, plus x or batch_norm(conv2d(1x1, x)).
+ * Everything NHWC fp32.  A block is pwconv -> dwconv -> gates -> [pwconv: skip projection] -> pwconv(gate, res).
+ *
+ * Pointwise convolution as a GEMM over pixels:  out[p,n] = act(sum_k a[p,k] w[k,n] * scale[n] + shift[n]) + res[p,n]
+ *   a = the virtual input cat(src0', src1) of [B,H,W,C0+C1]: src0' = src0 [B,H,W,C0] (up0 = 0) or the nearest x2
+ *       up-sampling of src0 [B,(H+1)/2,(W+1)/2,C0] (up0 = 1); src1 [B,H,W,C1] or NULL with C1 = 0;
+ *       with gates (both or neither): a[p,k] *= gate_c[b,k] + sigmoid(gate_s[p]), gate_c [B,C0+C1], gate_s [B,H,W]
+ *   w_io [C0+C1][Cout]; scale / shift [Cout]: eval BatchNorm with the convolution's bias folded in
+ *   act 0 none, 1 Hardswish; res optional, layout of out, may alias out.  C0, C1, Cout multiples of 16.
+ * One fixed-order sum per output element: a pixel's result does not depend on the batch it arrives in. */
+int dt_pwconv_affine(const float* src0, const float* src1, const float* w_io, float* out, const float* scale,
+                     const float* shift, const float* gate_c, const float* gate_s, const float* res, int B, int H, int W,
+                     int C0, int C1, int up0, int Cout, int act, void* stream);
+/* Depthwise 3x3, stride 1, pad 1:  out = hardswish(dw(x) * scale[c] + shift[c]), x / out [B,H,W,C], w_tc [9][C].  The same
+ * pass writes the sSE logits s[p] = sse_w . out[p,:] + sse_b[0] ([B,H,W]) and, per workgroup, one row of channel sums of out:
+ * part [B][P][C], P = dt_dwconv3x3_rows(H, W) — fixed order, no float atomics.  C a multiple of 16, at most 1536. */
+int dt_dwconv3x3_rows(int H, int W);
+int dt_dwconv3x3_affine(const float* x, const float* w_tc, const float* scale, const float* shift, const float* sse_w,
+                        const float* sse_b, float* out, float* s, float* part, int B, int H, int W, int C, void* stream);
+/* cSE gate: mean[b,c] = (sum of the P rows of image b, in one order) / HW;
+ * gc [B,C] = sigmoid(W2 relu(W1 mean + b1) + b2), w1_io [C][Ch], w2_io [Ch][C], Ch = C / squeeze_ratio.  One launch. */
+int dt_scse_gates(const float* part, const float* w1_io, const float* b1, const float* w2_io, const float* b2, float* gc,
+                  int B, int P, int C, int Ch, int HW, void* stream);
+/* dt_bn_eval_affine behind a convolution WITH bias: shift = beta - mean * scale + scale * bias */
+int dt_bn_eval_affine_bias(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                           const float* bias, float eps, int C, float* scale, float* shift, void* stream);
+
 /* ------------------------------------------------------------------ library options */
 /* Kernel-selection switches (host side, process wide; every choice computes the same values):
  *   "bf16_dma": 0 = register-staged bf16 convolutions only, 1 (default) = the LDS-DMA staged 512-pixel kernel where
