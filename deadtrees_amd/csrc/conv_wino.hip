@@ -37,6 +37,19 @@
 #define WN_MAX_WGS 256                 // CUs of an MI355X
 #define WN_OOB 0x80000000u             // byte offset beyond every buffer this kernel takes (host check: < 2 GiB)
 
+// The accumulators are dead between a tile's epilogue and the next tile's first MFMAs (which take a zero C operand), so
+// nothing ties them to the accumulator half of the register file across the epilogue's basic blocks: hipcc then copies all
+// 256 to ordinary registers at the top of the epilogue and spills the staged patch registers to make room.  An empty asm
+// that "rewrites" the 16 tiles in place right before a row of them is read keeps them where the MFMAs left them and the
+// reads next to their use (no instruction is emitted; two statements: an asm takes at most 30 operands).
+#define WN_PIN_ACC()                                                                                                \
+  if constexpr (ZC) {                                                                                               \
+    asm volatile("" : "+a"(acc[0]), "+a"(acc[1]), "+a"(acc[2]), "+a"(acc[3]), "+a"(acc[4]), "+a"(acc[5]),           \
+                      "+a"(acc[6]), "+a"(acc[7]));                                                                  \
+    asm volatile("" : "+a"(acc[8]), "+a"(acc[9]), "+a"(acc[10]), "+a"(acc[11]), "+a"(acc[12]), "+a"(acc[13]),       \
+                      "+a"(acc[14]), "+a"(acc[15]));                                                                \
+  }
+
 struct WinoArgs {
   const float* src0;
   const float* src1;
@@ -77,7 +90,9 @@ struct WinoArgs {
 // writes of step s+1.  One barrier per step; at a tile's last step the epilogue runs with the next tile's operands
 // already in flight.
 // PACK (compile time: the 16x16-map path pays nothing for it): see WinoArgs::pack
-template <bool TF, int EPI, bool PACK = false>
+// FULL (compile time, host: !pack and both map sides multiples of 16): every output of every tile lies inside the map, so the
+// epilogue carries no per-output validity (no WN_OOB offsets, compares or selects); the staging side keeps its padding logic
+template <bool TF, int EPI, bool PACK = false, bool FULL = false>
 __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, const int total_tiles) {
   __shared__ __attribute__((aligned(1024))) float lds[4 * WN_BUF + 256 + (TF ? 2 * WN_TF_MAXC : 0)];
   float* Vb = lds;
@@ -152,8 +167,10 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
     const int c0 = __builtin_amdgcn_readfirstlane(8 * l_chunk);
     const bool use0 = c0 < a.C0;   // wave-uniform
     const unsigned cb = (unsigned)(use0 ? c0 : c0 - a.C0) * 4u;
-    const u32x2 v = use0 ? __builtin_amdgcn_raw_buffer_load_b64(rs0, off0[i] + cb, 0, 0)
-                         : __builtin_amdgcn_raw_buffer_load_b64(rs1, off1[i] + cb, 0, 0);
+    // the chunk's channel offset travels in the instruction's scalar offset (one VALU add per load less; the range check
+    // that turns WN_OOB into a zero is on the per-lane part, as in the epilogue's stores)
+    const u32x2 v = use0 ? __builtin_amdgcn_raw_buffer_load_b64(rs0, off0[i], (int)cb, 0)
+                         : __builtin_amdgcn_raw_buffer_load_b64(rs1, off1[i], (int)cb, 0);
     d[SET][i] = __builtin_bit_cast(f32x2, v);
     if (i == 0) dc0[SET] = c0;
   };
@@ -264,11 +281,18 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
     }
   };
 
+  // ZC: the accumulators are never cleared — the first MFMA of each position in a tile's first step takes a literal zero as
+  // its C operand (256 register moves per tile less).  Forms 3 and 6 and the ragged / packed form 1 keep the clear: without
+  // it their epilogues (three operand streams; two code paths; validity + the virtual activation) came out of hipcc with
+  // hundreds to thousands of spilled registers.  Per-instantiation figures: profiles/README.md.
+  constexpr bool ZC = EPI == 0 || EPI == 2 || EPI == 4 || EPI == 5 || (EPI == 1 && FULL);
   f32x16 acc[16];
+  if constexpr (!ZC) {
 #pragma unroll
-  for (int p = 0; p < 16; ++p)
+    for (int p = 0; p < 16; ++p)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc[p][i] = 0.f;
+      for (int i = 0; i < 16; ++i) acc[p][i] = 0.f;
+  }
   float ps1 = 0.f, ps2 = 0.f;
 
   const int aoff = kh * WN_PS + (32 * wm + r) * 4;
@@ -304,9 +328,11 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the weight planes of step 0
 
   // ---- one step.  PAR = s & 1: operand images PAR are multiplied; images PAR^1 receive step s+1; register set PAR^1
-  // (loaded during step s-1) is transformed; register set PAR is loaded for step s+2.
-  auto step = [&](auto par_tag) {
+  // (loaded during step s-1) is transformed; register set PAR is loaded for step s+2.  FIRST (compile time): a tile's
+  // first step — the accumulators start from the MFMA's inline-constant zero instead of being cleared after the epilogue.
+  auto step = [&](auto par_tag, auto first_tag) {
     constexpr int PAR = decltype(par_tag)::value;
+    constexpr bool FIRST = decltype(first_tag)::value;
     using SN = std::integral_constant<int, PAR ^ 1>;
     const float* Vc = Vb + PAR * WN_BUF + aoff;
     const float* Uc = Ub + PAR * WN_BUF + boff;
@@ -318,7 +344,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
     dt_static_for<0, 64>([&](auto kc) {
       constexpr int k = decltype(kc)::value;
       constexpr int p = k >> 2, j = k & 3, cur = p & 1;
-      acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][j], fb[cur][j], acc[p], 0, 0, 0);
+      if constexpr (FIRST && j == 0) {
+        constexpr f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][j], fb[cur][j], zero, 0, 0, 0);
+      } else {
+        acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][j], fb[cur][j], acc[p], 0, 0, 0);
+      }
       if (j == 0 && p + 1 < 16) {
         fa[cur ^ 1] = *reinterpret_cast<const f32x4*>(Vc + (p + 1) * 2 * WN_PS);
         fb[cur ^ 1] = *reinterpret_cast<const f32x4*>(Uc + (p + 1) * 2 * WN_PS);
@@ -417,7 +448,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const bool ok = ysrc + (i >> 2) < Hs && xsrc + (i & 3) < Ws;
-        yall[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsyl, ok ? llane : WN_OOB,
+        yall[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsyl, (FULL || ok) ? llane : WN_OOB,
                                                                                  lbase + (i >> 2) * rowl4 + (i & 3) * ldl4, 0));
       }
 #pragma unroll
@@ -429,13 +460,14 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
         for (int ii = 0; ii < 4; ++ii) {
           const int i = 4 * qr + ii;
           const bool ok = ysrc + (i >> 2) < Hs && xsrc + (i & 3) < Ws;
-          off[ii] = ok ? llane : WN_OOB;
+          off[ii] = (FULL || ok) ? llane : WN_OOB;
           soff[ii] = lbase + (i >> 2) * rowl4 + (i & 3) * ldl4;
           yv[ii] = yall[i];
         }
 #pragma unroll
         for (int ii = 0; ii < 4; ++ii) {
           const int i = 4 * qr + ii;
+          WN_PIN_ACC();
           float t0[4], t1[4];
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
@@ -445,7 +477,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
           const float y0 = t0[0] + t0[1] + t0[2], y1 = t0[1] - t0[2] - t0[3];
           const float y2 = t1[0] + t1[1] + t1[2], y3 = t1[1] - t1[2] - t1[3];
           const float v = (y0 + y1) + (y2 + y3);                    // dt_upsample2x_bwd's order: (a + b) + (c + d)
-          const bool ok = off[ii] != WN_OOB;
+          const bool ok = FULL || off[ii] != WN_OOB;
           const float g = (ok && (yv[ii] * b_sc + b_sh) > 0.f) ? v : 0.f;
           s1 += g;
           s2 += g * ((yv[ii] - b_mu) * b_is);
@@ -458,6 +490,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
     for (int qr = 0; qr < 4; ++qr) {
       // 4 accumulator rows (4 Winograd tiles x 4 pixels) at a time: the reads of this quarter are in flight while its
       // output transforms are computed; the scheduling fence keeps hipcc from hoisting all 256 accumulator reads
+      // (the skip's tiles of form 6 keep the general code: without validity this path cost that kernel two more spilled registers)
+      constexpr bool FULLP = FULL && EPI != 6;
       unsigned off[16];
       int soff[16];
       float prev[(EPI == 2 || EPI == 3) ? 16 : 1], yv[(EPI == 1 || EPI == 3 || EPI == 5) ? 16 : 1], zv[(EPI == 3) ? 16 : 1];
@@ -467,7 +501,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int py = 2 * (i >> 2) + (e >> 1), px = 2 * (i & 3) + (e & 1);
-          const bool ok = img_ok && ybase + py < a.Hin && xlane + px < a.Win;
+          const bool ok = FULLP || (img_ok && ybase + py < a.Hin && xlane + px < a.Win);
           off[4 * ii + e] = ok ? lane_base : WN_OOB;
           soff[4 * ii + e] = tile_base + py * row4 + px * ld4;
         }
@@ -489,6 +523,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
 #pragma unroll
       for (int ii = 0; ii < 4; ++ii) {
         const int i = 4 * qr + ii;
+        WN_PIN_ACC();
         float t0[4], t1[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -502,7 +537,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
       }
 #pragma unroll
       for (int x = 0; x < 16; ++x) {
-        const bool ok = off[x] != WN_OOB;
+        const bool ok = FULLP || off[x] != WN_OOB;
         float v = y[x];
         if constexpr (EPI == 2 || EPI == 3) v += prev[x];
         if constexpr (EPI == 4 || EPI == 5) {   // the arithmetic of bn_act_kernel: mul, add (, + residual), ReLU that keeps NaN
@@ -527,10 +562,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
       }
       __builtin_amdgcn_sched_barrier(0);
     }
+    if constexpr (!ZC) {
 #pragma unroll
-    for (int p = 0; p < 16; ++p)
+      for (int p = 0; p < 16; ++p)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) acc[p][i] = 0.f;
+        for (int i = 0; i < 16; ++i) acc[p][i] = 0.f;
+    }
     if (a.stats != nullptr && a.pstats) {
       ps1 += s1;
       ps2 += s2;
@@ -553,13 +590,21 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(const WinoArgs a, 
   // Structured as tiles x chunk pairs (the chunk count is even: host check), not as one flat step loop with a
   // conditional epilogue: across a two-way join hipcc no longer keeps the 256 accumulators in place (hundreds of spills).
   // The staging contexts above run ahead across the tile boundaries regardless.
+  // ZC: the tile's first chunk pair is peeled — its first step starts the accumulators (16 channels = 2 chunks: the peel is the
+  // whole loop).
   for (int round = 0; round < my_tiles; ++round) {
-    for (int c = 0; c < nch; c += 2) {
+    if constexpr (ZC) {
       // every wave has waited for its own weight planes (vmcnt in step / prologue) and waits here for its own V writes
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      step(S0{});
+      step(S0{}, std::true_type{});
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      step(S1{});
+      step(S1{}, std::false_type{});
+    }
+    for (int c = ZC ? 2 : 0; c < nch; c += 2) {
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      step(S0{}, std::false_type{});
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      step(S1{}, std::false_type{});
     }
     epilogue(round);
   }
@@ -736,10 +781,21 @@ int dt_conv_wino_launch(const dt_conv_desc* d, const float* src0, const float* s
   const int epi = affine ? (a.bnb.y != nullptr ? 5 : 4) : (bnb ? 1 : 0) + (join ? 2 : 0);
   const bool tf = in_scale != nullptr;
   DT_REQUIRE(!tf || epi == 0 || epi == 2, "conv_winograd: the input transform goes with the plain / join epilogues only");
-#define WN_LAUNCH(TFv, EPIv)                                                                              \
-  do {                                                                                                    \
-    if (a.pack) hipLaunchKernelGGL((conv3x3_wino_kernel<TFv, EPIv, true>), g, blk, 0, st, a, total);      \
-    else hipLaunchKernelGGL((conv3x3_wino_kernel<TFv, EPIv, false>), g, blk, 0, st, a, total);            \
+  // whole tiles (every map of the training step): the epilogue without per-output validity (FULL); the inference forms 4 / 5
+  // keep the one general path
+  const bool full = !a.pack && (d->Hin % 16) == 0 && (d->Win % 16) == 0;
+#define WN_LAUNCH_ONE(TFv, EPIv, PACKv, FULLv) \
+  hipLaunchKernelGGL((conv3x3_wino_kernel<TFv, EPIv, PACKv, FULLv>), g, blk, 0, st, a, total)
+#define WN_LAUNCH(TFv, EPIv)                                  \
+  do {                                                        \
+    if (a.pack) WN_LAUNCH_ONE(TFv, EPIv, true, false);        \
+    else if (full) WN_LAUNCH_ONE(TFv, EPIv, false, true);     \
+    else WN_LAUNCH_ONE(TFv, EPIv, false, false);              \
+  } while (0)
+#define WN_LAUNCH_INFER(EPIv)                                 \
+  do {                                                        \
+    if (a.pack) WN_LAUNCH_ONE(false, EPIv, true, false);      \
+    else WN_LAUNCH_ONE(false, EPIv, false, false);            \
   } while (0)
   if (tf && epi == 2) WN_LAUNCH(true, 2);
   else if (tf) WN_LAUNCH(true, 0);
@@ -747,8 +803,10 @@ int dt_conv_wino_launch(const dt_conv_desc* d, const float* src0, const float* s
   else if (epi == 1) WN_LAUNCH(false, 1);
   else if (epi == 2) WN_LAUNCH(false, 2);
   else if (epi == 3) WN_LAUNCH(false, 3);
-  else if (epi == 4) WN_LAUNCH(false, 4);
-  else WN_LAUNCH(false, 5);
+  else if (epi == 4) WN_LAUNCH_INFER(4);
+  else WN_LAUNCH_INFER(5);
+#undef WN_LAUNCH_INFER
+#undef WN_LAUNCH_ONE
 #undef WN_LAUNCH
   DT_LAUNCH_CHECK();
   return DT_OK;
@@ -841,8 +899,11 @@ static int wn_updgrad_launch(const dt_conv_desc* d, const float* dy, const float
   a.nt0 = 0; a.n_tiles = (x_only ? d->cout_split : d->Cout) / 64; a.stat_ld = d->cout_split;
   a.P = wn_updgrad_rows(d, &a.pstats, x_only);
   const int total = sp_tiles * a.n_tiles;
-  hipLaunchKernelGGL((conv3x3_wino_kernel<false, 6, false>), dim3((unsigned)(total < WN_MAX_WGS ? total : WN_MAX_WGS)),
-                     dim3(256), 0, st, a, total);
+  const dim3 g((unsigned)(total < WN_MAX_WGS ? total : WN_MAX_WGS));
+  if ((d->Hin % 16) == 0 && (d->Win % 16) == 0)   // whole tiles: every half-resolution pixel of a tile is in range too
+    hipLaunchKernelGGL((conv3x3_wino_kernel<false, 6, false, true>), g, dim3(256), 0, st, a, total);
+  else
+    hipLaunchKernelGGL((conv3x3_wino_kernel<false, 6, false, false>), g, dim3(256), 0, st, a, total);
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
