@@ -58,6 +58,21 @@ static inline int dt_ew_grid(int64_t n_items, int64_t cap) {
   const int64_t g = (n_items + 255) / 256;
   return (int)(g < cap ? (g > 0 ? g : 1) : cap);
 }
+// the caps of the element-wise files.  A fused BatchNorm-backward pass writes one partial row per workgroup, so a cap is
+// part of its result: a call site keeps the cap it has
+#define EW_CAP (256 * 16)        // 16 workgroups per CU, grid-stride beyond
+#define EW_CAP_WIDE (256 * 32)   // the 2 x 2 pool blocks of the bf16 path and the channel-slice copies
+// grid of the channel-slice copies: n / 256 + 1 workgroups, one more than dt_ew_grid gives for exact multiples of 256
+static inline int dt_slice_grid(int64_t n_items) {
+  const int64_t g = n_items / 256 + 1;
+  return (int)(g < EW_CAP_WIDE ? g : EW_CAP_WIDE);
+}
+
+// ---- C channels in groups of `per` (4 fp32 or 8 bf16 = 16 bytes): the groups must divide the 256 threads of a workgroup
+// wherever a thread keeps ONE group for the whole launch (fixed coefficients, partial rows combined inside the workgroup)
+static inline bool dt_groups_divide_256(int C, int per) {
+  return C > 0 && C % per == 0 && C / per <= 256 && 256 % (C / per) == 0;
+}
 
 // ---- rows (pixels) per workgroup of the BatchNorm-backward reductions of both precisions: 256 for small maps, grown so
 // that a launch has at most ~2048 row blocks — the in-workgroup reduction and the second-stage row count then stay small
@@ -77,5 +92,9 @@ static inline bool dt_aligned16(const P*... p) {
 }
 static inline bool dt_fuse_aligned16(const dt_bn_bwd_fuse* f) {
   return dt_aligned16(f->mean, f->invstd, f->act_scale, f->act_shift);
+}
+// every array a fused BatchNorm-backward reduction with a virtual activation reads is there
+static inline bool dt_fuse_complete(const dt_bn_bwd_fuse* f) {
+  return f && f->y && f->mean && f->invstd && f->act_scale && f->act_shift;
 }
 #define DT_REQUIRE_COEF_ALIGNED(ok, tag) DT_REQUIRE(ok, tag ": per-channel arrays must be 16-byte aligned")

@@ -9,6 +9,49 @@
 
 #include <math.h>
 
+// ------------------------------------------------------------------ shared steps of the BatchNorm-backward passes
+// ReLU mask from the raw output (virtual activation z = relu(y * asc + ash)): g where the activation is > 0, else 0
+__device__ __forceinline__ void relu_mask_from_y(f32x4& g, const f32x4 yv, const f32x4 asc, const f32x4 ash) {
+  const f32x4 a = yv * asc + ash;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) g[k] = a[k] > 0.f ? g[k] : 0.f;
+}
+// the two sums of one pixel's channel quad
+__device__ __forceinline__ void bnb_sums(const f32x4 g, const f32x4 yv, const f32x4 mu, const f32x4 is, f32x4& sg, f32x4& sx) {
+  sg += g;
+  sx += g * ((yv - mu) * is);
+}
+// both: what a pass that has just written the gradient g of a virtual activation adds to its BatchNorm-backward sums
+__device__ __forceinline__ void bnb_masked_sums(f32x4 g, const f32x4 yv, const f32x4 asc, const f32x4 ash, const f32x4 mu,
+                                                const f32x4 is, f32x4& sg, f32x4& sx) {
+  relu_mask_from_y(g, yv, asc, ash);
+  bnb_sums(g, yv, mu, is, sg, sx);
+}
+
+// Partial rows of a BatchNorm-backward reduction: red[2][P][C], row `row` of plane 0 = this workgroup's sum g per channel,
+// of plane 1 = its sum g * xhat (-> dt_bn_bwd_finish_sums).  Thread t holds the sums of one channel quad; the 256 / L threads
+// t, t + L, t + 2 L, ... hold the same quad (L quads per workgroup, a divisor of 256) and are combined by a pairwise tree
+// in a fixed order -> deterministic; the first of them writes, to channel quad cq.
+__device__ __forceinline__ void bnb_store_partial_rows(const f32x4 sg, const f32x4 sx, int L, int cq, int row, int P, int C4,
+                                                       float* __restrict__ red) {
+  __shared__ f32x4 sh[2][256];
+  const int t = threadIdx.x, rl = t / L, RL = 256 / L;
+  sh[0][t] = sg;
+  sh[1][t] = sx;
+  __syncthreads();
+  for (int s = RL >> 1; s >= 1; s >>= 1) {
+    if (rl < s) {
+      sh[0][t] += sh[0][t + s * L];
+      sh[1][t] += sh[1][t + s * L];
+    }
+    __syncthreads();
+  }
+  if (rl == 0) {
+    reinterpret_cast<f32x4*>(red)[(size_t)row * C4 + cq] = sh[0][t];
+    reinterpret_cast<f32x4*>(red)[((size_t)P + row) * C4 + cq] = sh[1][t];
+  }
+}
+
 // ------------------------------------------------------------------ generic row-block reduction
 // in [planes][P][N] -> out [planes][PB][N], PB = ceil(P/RB): block (col-block, row-block, plane) sums RB rows.
 // 256 threads = Q column-quads x (256/Q) row-lanes, 4 independent accumulators per thread for memory-level
@@ -238,7 +281,7 @@ extern "C" int64_t dt_channel_sums_workspace(int64_t n_pix, int C) {
 
 extern "C" int dt_channel_sums(const float* g, float* workspace, int64_t n_pix, int C, float* out, void* stream) {
   DT_REQUIRE(g && workspace && out && n_pix > 0 && C > 0, "channel_sums: bad args");
-  DT_REQUIRE((C & 3) == 0 && C / 4 <= 256 && 256 % (C / 4) == 0, "channel_sums: C/4 must divide 256 (C=%d)", C);
+  DT_REQUIRE(dt_groups_divide_256(C, 4), "channel_sums: C/4 must divide 256 (C=%d)", C);
   hipStream_t st = (hipStream_t)stream;
   const int P = dt_cdiv(n_pix, CS_RB);
   hipLaunchKernelGGL(channel_sums_kernel, dim3(P), dim3(256), 0, st, (const f32x4*)g, workspace, n_pix, C / 4);
@@ -284,9 +327,8 @@ extern "C" int dt_channel_slice(const float* src, float* dst, int64_t n_pix, int
   DT_REQUIRE((C_narrow & 3) == 0 && (C_wide & 3) == 0 && (offset & 3) == 0 && offset >= 0 && offset + C_narrow <= C_wide,
              "channel_slice: channel counts and offset must be multiples of 4 inside the wide tensor");
   const int64_t n4 = n_pix * (C_narrow / 4);
-  const int grid = (int)(n4 / 256 + 1 < 8192 ? n4 / 256 + 1 : 8192);
-  hipLaunchKernelGGL(channel_slice_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f32x4*)src, (f32x4*)dst,
-                     n4, C_narrow / 4, C_wide / 4, offset / 4, to_wide, accumulate);
+  hipLaunchKernelGGL(channel_slice_kernel, dim3(dt_slice_grid(n4)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)src,
+                     (f32x4*)dst, n4, C_narrow / 4, C_wide / 4, offset / 4, to_wide, accumulate);
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
@@ -336,8 +378,6 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const f32x4* __restrict__ y
   }
 }
 
-#define EW_CAP (256 * 16)   // grid cap of the passes below: 16 workgroups per CU, grid-stride beyond
-
 extern "C" int dt_bn_act(const float* y, const float* scale, const float* shift, const float* res,
                          const float* rscale, const float* rshift, float* out, int64_t n_pix, int C, int relu,
                          void* stream) {
@@ -368,7 +408,6 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const f32x4* __restr
                                                             const float* __restrict__ act_shift,
                                                             float* __restrict__ red, int64_t n_pix, int C4, int Q,
                                                             int P, int64_t RB) {
-  __shared__ f32x4 sh[2][256];
   const int t = threadIdx.x;
   const int q = t % Q, rl = t / Q, RL = 256 / Q;
   const int cq = blockIdx.x * Q + q;
@@ -398,15 +437,11 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const f32x4* __restr
         g1[k] = a1[k] > 0.f ? g1[k] : 0.f;
       }
     } else if (from_y) {
-      const f32x4 a0 = y0 * asc + ash, a1 = y1 * asc + ash;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        g0[k] = a0[k] > 0.f ? g0[k] : 0.f;
-        g1[k] = a1[k] > 0.f ? g1[k] : 0.f;
-      }
+      relu_mask_from_y(g0, y0, asc, ash);
+      relu_mask_from_y(g1, y1, asc, ash);
     }
-    sg0 += g0; sx0 += g0 * ((y0 - mu) * is);
-    sg1 += g1; sx1 += g1 * ((y1 - mu) * is);
+    bnb_sums(g0, y0, mu, is, sg0, sx0);
+    bnb_sums(g1, y1, mu, is, sg1, sx1);
   }
   for (; p < p1; p += RL) {
     const size_t o0 = (size_t)p * C4 + cq;
@@ -416,27 +451,11 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const f32x4* __restr
 #pragma unroll
       for (int k = 0; k < 4; ++k) g0[k] = a0[k] > 0.f ? g0[k] : 0.f;
     } else if (from_y) {
-      const f32x4 a0 = y[o0] * asc + ash;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) g0[k] = a0[k] > 0.f ? g0[k] : 0.f;
+      relu_mask_from_y(g0, y[o0], asc, ash);
     }
-    sg0 += g0; sx0 += g0 * ((y[o0] - mu) * is);
+    bnb_sums(g0, y[o0], mu, is, sg0, sx0);
   }
-  sh[0][t] = sg0 + sg1;
-  sh[1][t] = sx0 + sx1;
-  __syncthreads();
-  // pairwise tree over the row lanes (thread t = rl * Q + q): fixed order -> deterministic
-  for (int s = RL >> 1; s >= 1; s >>= 1) {
-    if (rl < s) {
-      sh[0][t] += sh[0][t + s * Q];
-      sh[1][t] += sh[1][t + s * Q];
-    }
-    __syncthreads();
-  }
-  if (rl == 0) {
-    reinterpret_cast<f32x4*>(red)[(size_t)blockIdx.y * C4 + cq] = sh[0][t];
-    reinterpret_cast<f32x4*>(red)[((size_t)P + blockIdx.y) * C4 + cq] = sh[1][t];
-  }
+  bnb_store_partial_rows(sg0 + sg1, sx0 + sx1, Q, cq, blockIdx.y, P, C4, red);   // thread t = rl * Q + q
 }
 
 extern "C" int dt_bn_bwd_reduce(const float* dout, const float* out_act, const float* y, const float* mean,
@@ -751,11 +770,9 @@ __global__ __launch_bounds__(256) void maxpool_bwd_quad_bn_kernel(const f32x4* _
                                                                   const float* __restrict__ act_scale,
                                                                   const float* __restrict__ act_shift, float* __restrict__ red,
                                                                   int acc, int B, int H, int W, int C4, int Ho, int Wo, int P) {
-  __shared__ f32x4 sh[2][256];
   const int64_t total = (int64_t)B * Ho * Wo * C4;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const int t = threadIdx.x;
-  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + t;
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int c4 = (int)(i0 % C4);
   const f32x4 mu = reinterpret_cast<const f32x4*>(mean)[c4], is = reinterpret_cast<const f32x4*>(invstd)[c4];
   const f32x4 asc = reinterpret_cast<const f32x4*>(act_scale)[c4], ash = reinterpret_cast<const f32x4*>(act_shift)[c4];
@@ -794,40 +811,20 @@ __global__ __launch_bounds__(256) void maxpool_bwd_quad_bn_kernel(const f32x4* _
       f32x4 v = g[e];
       if (acc) v = dx[xs[e]] + v;
       dx[xs[e]] = v;
-      const f32x4 yv = y[xs[e]];
-      const f32x4 a = yv * asc + ash;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = a[k] > 0.f ? v[k] : 0.f;
-      sg += v;
-      sx += v * ((yv - mu) * is);
+      bnb_masked_sums(v, y[xs[e]], asc, ash, mu, is, sg, sx);
     }
   }
-  sh[0][t] = sg;
-  sh[1][t] = sx;
-  __syncthreads();
-  const int rl = t / C4, RL = 256 / C4;     // threads t, t + C4, ... share the channel quad
-  for (int s2 = RL >> 1; s2 >= 1; s2 >>= 1) {
-    if (rl < s2) {
-      sh[0][t] += sh[0][t + s2 * C4];
-      sh[1][t] += sh[1][t + s2 * C4];
-    }
-    __syncthreads();
-  }
-  if (t < C4) {
-    reinterpret_cast<f32x4*>(red)[(size_t)blockIdx.x * C4 + t] = sh[0][t];
-    reinterpret_cast<f32x4*>(red)[((size_t)P + blockIdx.x) * C4 + t] = sh[1][t];
-  }
+  bnb_store_partial_rows(sg, sx, C4, threadIdx.x, blockIdx.x, P, C4, red);   // the writers, t < C4, hold channel quad t
 }
 
 extern "C" int dt_maxpool3x3s2_bwd_bn_rows(int B, int H, int W, int C) {
-  if (((H | W) & 1) != 0 || C <= 0 || (C & 3) != 0 || C / 4 > 256 || 256 % (C / 4) != 0) return 0;   // even maps only
+  if (((H | W) & 1) != 0 || !dt_groups_divide_256(C, 4)) return 0;   // even maps only
   return dt_ew_grid((int64_t)B * (H / 2) * (W / 2) * (C / 4), EW_CAP);
 }
 
 extern "C" int dt_maxpool3x3s2_bwd_bn(const float* dout, const uint8_t* argmax, float* dx, int accumulate,
                                       const dt_bn_bwd_fuse* fuse, float* red, int B, int H, int W, int C, void* stream) {
-  DT_REQUIRE(dout && argmax && dx && fuse && red && fuse->y && fuse->mean && fuse->invstd && fuse->act_scale &&
-                 fuse->act_shift && B > 0 && H > 0 && W > 0, "maxpool_bwd_bn: bad args");
+  DT_REQUIRE(dout && argmax && dx && red && dt_fuse_complete(fuse) && B > 0 && H > 0 && W > 0, "maxpool_bwd_bn: bad args");
   const int P = dt_maxpool3x3s2_bwd_bn_rows(B, H, W, C);
   DT_REQUIRE(P > 0, "maxpool_bwd_bn: even maps, C/4 a divisor of 256 (H=%d W=%d C=%d)", H, W, C);
   hipLaunchKernelGGL(maxpool_bwd_quad_bn_kernel, dim3(P), dim3(256), 0, (hipStream_t)stream, (const f32x4*)dout,
@@ -898,11 +895,10 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_bn_kernel(const f32x4* __r
                                                                 const float* __restrict__ act_shift,
                                                                 float* __restrict__ red, int B, int H, int W, int C4,
                                                                 int P) {
-  __shared__ f32x4 sh[2][256];
   const int64_t total = (int64_t)B * H * W * C4;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;   // multiple of C4 (host check): fixed channel quad
-  const int W2 = 2 * W, t = threadIdx.x;
-  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + t;
+  const int W2 = 2 * W;
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int c4 = (int)(i0 % C4);
   const f32x4 mu = reinterpret_cast<const f32x4*>(mean)[c4], is = reinterpret_cast<const f32x4*>(invstd)[c4];
   const f32x4 asc = reinterpret_cast<const f32x4*>(act_scale)[c4], ash = reinterpret_cast<const f32x4*>(act_shift)[c4];
@@ -914,30 +910,11 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_bn_kernel(const f32x4* __r
     const int yy = (int)(r % H);
     const int b = (int)(r / H);
     const int64_t base = (((int64_t)b * 2 * H + 2 * yy) * W2 + 2 * x) * C4 + c4;
-    f32x4 g = (dup[base] + dup[base + C4]) + (dup[base + (int64_t)W2 * C4] + dup[base + (int64_t)W2 * C4 + C4]);
+    const f32x4 g = (dup[base] + dup[base + C4]) + (dup[base + (int64_t)W2 * C4] + dup[base + (int64_t)W2 * C4 + C4]);
     dx[i] = g;
-    const f32x4 yv = y[i];
-    const f32x4 a = yv * asc + ash;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) g[k] = a[k] > 0.f ? g[k] : 0.f;
-    sg += g;
-    sx += g * ((yv - mu) * is);
+    bnb_masked_sums(g, y[i], asc, ash, mu, is, sg, sx);
   }
-  sh[0][t] = sg;
-  sh[1][t] = sx;
-  __syncthreads();
-  const int rl = t / C4, RL = 256 / C4;     // threads t, t + C4, ... share the channel quad
-  for (int s = RL >> 1; s >= 1; s >>= 1) {
-    if (rl < s) {
-      sh[0][t] += sh[0][t + s * C4];
-      sh[1][t] += sh[1][t + s * C4];
-    }
-    __syncthreads();
-  }
-  if (t < C4) {
-    reinterpret_cast<f32x4*>(red)[(size_t)blockIdx.x * C4 + t] = sh[0][t];
-    reinterpret_cast<f32x4*>(red)[((size_t)P + blockIdx.x) * C4 + t] = sh[1][t];
-  }
+  bnb_store_partial_rows(sg, sx, C4, threadIdx.x, blockIdx.x, P, C4, red);   // the writers, t < C4, hold channel quad t
 }
 
 extern "C" int dt_upsample2x_bwd_bn_rows(int B, int H, int W, int C) {
@@ -946,11 +923,10 @@ extern "C" int dt_upsample2x_bwd_bn_rows(int B, int H, int W, int C) {
 
 extern "C" int dt_upsample2x_bwd_bn(const float* dup, float* dx, const dt_bn_bwd_fuse* fuse, float* red, int B, int H,
                                     int W, int C, void* stream) {
-  DT_REQUIRE(dup && dx && fuse && red && fuse->y && fuse->mean && fuse->invstd && fuse->act_scale && fuse->act_shift &&
-                 B > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0,
+  DT_REQUIRE(dup && dx && red && dt_fuse_complete(fuse) && B > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0,
              "upsample2x_bwd_bn: bad args");
   const int C4 = C / 4;
-  DT_REQUIRE(C4 <= 256 && 256 % C4 == 0, "upsample2x_bwd_bn: C/4 must divide 256 (C=%d)", C);
+  DT_REQUIRE(dt_groups_divide_256(C, 4), "upsample2x_bwd_bn: C/4 must divide 256 (C=%d)", C);
   const int P = dt_upsample2x_bwd_bn_rows(B, H, W, C);
   hipLaunchKernelGGL(upsample2x_bwd_bn_kernel, dim3(P), dim3(256), 0, (hipStream_t)stream, (const f32x4*)dup,
                      (f32x4*)dx, (const f32x4*)fuse->y, fuse->mean, fuse->invstd, fuse->act_scale, fuse->act_shift, red,

@@ -27,6 +27,107 @@ __device__ __forceinline__ void ldc8(const float* __restrict__ p, int c, float (
   }
 }
 
+// Round-once store: p[i] = bf16(v), or with acc bf16(p[i] + v) — the sum with what is there is taken in fp32 and rounded
+// ONCE (a node of a dense decoder collects the gradients of several consumers: one rounding per contribution)
+__device__ __forceinline__ void store8(bf16x8* p, size_t i, const float (&v)[8], int acc) {
+  bf16x8 o;
+  if (acc) {
+    float prev[8];
+    load8(p, i, prev);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = (__bf16)(prev[k] + v[k]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = (__bf16)v[k];
+  }
+  p[i] = o;
+}
+
+// ------------------------------------------------------------------ shared steps of the BatchNorm-backward passes
+// ReLU mask from the raw output (virtual activation): the consumers saw bf16(relu(y * asc + ash)), so the mask is the
+// sign of that ROUNDED value — g where it is > 0, else 0
+__device__ __forceinline__ float relu_mask_from_y(float g, float yv, float asc, float ash) {
+  const float a = (float)(__bf16)(yv * asc + ash);
+  return a > 0.f ? g : 0.f;
+}
+// what a pass that has just written the gradient adds to its BatchNorm-backward sums: g is the ROUNDED value it stored
+__device__ __forceinline__ void bnb_masked_sums(const float (&g)[8], const float (&yv)[8], const float (&asc)[8],
+                                                const float (&ash)[8], const float (&mu)[8], const float (&is)[8],
+                                                float (&sg)[8], float (&sx)[8]) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float gm = relu_mask_from_y(g[k], yv[k], asc[k], ash[k]);
+    sg[k] += gm;
+    sx[k] += gm * ((yv[k] - mu[k]) * is[k]);
+  }
+}
+
+// Partial rows of a BatchNorm-backward reduction: red[2][P][C] fp32, row `row` of plane 0 = this workgroup's sum g per
+// channel, of plane 1 = its sum g * xhat (-> dt_bn_bwd_finish_sums).  Thread t holds the sums of one channel group; the
+// 256 / L threads t, t + L, t + 2 L, ... hold the same group (L groups per workgroup, a divisor of 256) and are combined by a
+// pairwise tree in a fixed order -> deterministic; the first of them writes, to channel group cq.
+__device__ __forceinline__ void bnb_store_partial_rows(const float (&sg)[8], const float (&sx)[8], int L, int cq, int row,
+                                                       int P, int C8, float* __restrict__ red) {
+  __shared__ float sh[16][256];   // [sum kind * 8 + k][thread]: conflict-free columns
+  const int t = threadIdx.x, rl = t / L, RL = 256 / L;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    sh[k][t] = sg[k];
+    sh[8 + k][t] = sx[k];
+  }
+  __syncthreads();
+  for (int s = RL >> 1; s >= 1; s >>= 1) {
+    if (rl < s) {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) sh[k][t] += sh[k][t + s * L];
+    }
+    __syncthreads();
+  }
+  if (rl == 0) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      red[(size_t)row * C8 * 8 + cq * 8 + k] = sh[k][t];
+      red[((size_t)P + row) * C8 * 8 + cq * 8 + k] = sh[8 + k][t];
+    }
+  }
+}
+
+// Max-pool 3x3 / stride 2 / pad 1 backward on an even map: the gradients g[0..3] of the input pixels (2q, 2p), (2q, 2p+1),
+// (2q+1, 2p), (2q+1, 2p+1) from window i = (q, p) of dout / amax and its right, lower and diagonal neighbours — these four
+// windows and no other contain the block, and each is loaded once.  A neighbour outside the map contributes nothing: its
+// index words are ones no tap has (0xff).  Each pixel adds its windows in the per-pixel kernel's order (oy, then ox,
+// ascending): bit-identical to it.
+__device__ __forceinline__ void pool_block_grads(const bf16x8* __restrict__ dout, const uint2* __restrict__ amax, int64_t i,
+                                                 int q, int p, int Ho, int Wo, int C8, float (&g)[4][8]) {
+  const bool q1 = q + 1 < Ho, p1 = p + 1 < Wo;
+  const int64_t o00 = i, o01 = i + C8, o10 = i + (int64_t)Wo * C8, o11 = o10 + C8;
+  float d00[8], d01[8], d10[8], d11[8];
+  const uint2 none = make_uint2(0xffffffffu, 0xffffffffu);
+  load8(dout, o00, d00);
+  load8(dout, p1 ? o01 : o00, d01);
+  load8(dout, q1 ? o10 : o00, d10);
+  load8(dout, (q1 && p1) ? o11 : o00, d11);
+  const uint2 a00 = amax[o00], a01 = p1 ? amax[o01] : none, a10 = q1 ? amax[o10] : none,
+              a11 = (q1 && p1) ? amax[o11] : none;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int sh = 8 * (k & 3);
+    const unsigned t00 = ((k < 4 ? a00.x : a00.y) >> sh) & 0xffu, t01 = ((k < 4 ? a01.x : a01.y) >> sh) & 0xffu,
+                   t10 = ((k < 4 ? a10.x : a10.y) >> sh) & 0xffu, t11 = ((k < 4 ? a11.x : a11.y) >> sh) & 0xffu;
+    float u00 = 0.f, u01 = 0.f, u10 = 0.f, u11 = 0.f;
+    if (t00 == 4u) u00 += d00[k];
+    if (t00 == 5u) u01 += d00[k];
+    if (t01 == 3u) u01 += d01[k];
+    if (t00 == 7u) u10 += d00[k];
+    if (t10 == 1u) u10 += d10[k];
+    if (t00 == 8u) u11 += d00[k];
+    if (t01 == 6u) u11 += d01[k];
+    if (t10 == 2u) u11 += d10[k];
+    if (t11 == 0u) u11 += d11[k];
+    g[0][k] = u00; g[1][k] = u01; g[2][k] = u10; g[3][k] = u11;
+  }
+}
+
 // ------------------------------------------------------------------ BN backward, pass 1 (rows per workgroup: bnb_rb)
 
 __global__ __launch_bounds__(256) void bn_bwd_reduce_bf16_kernel(const bf16x8* __restrict__ dout,
@@ -38,7 +139,6 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_bf16_kernel(const bf16x8* _
                                                                  const float* __restrict__ act_shift,
                                                                  float* __restrict__ red, int64_t n_pix, int C8, int Q,
                                                                  int P, int64_t RB) {
-  __shared__ float sh[16][256];   // [sum kind * 8 + k][thread]: conflict-free columns
   const int t = threadIdx.x;
   const int q = t % Q, rl = t / Q, RL = 256 / Q;
   const int cq = blockIdx.x * Q + q;
@@ -69,11 +169,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_bf16_kernel(const bf16x8* _
       for (int k = 0; k < 8; ++k) g[k] = a[k] > 0.f ? g[k] : 0.f;
     } else if (from_y) {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        // the consumers saw bf16(relu(y*sc+sh)): the mask is the sign of that rounded value
-        const float a = (float)(__bf16)(yv[k] * asc[k] + ash[k]);
-        g[k] = a > 0.f ? g[k] : 0.f;
-      }
+      for (int k = 0; k < 8; ++k) g[k] = relu_mask_from_y(g[k], yv[k], asc[k], ash[k]);
     }
   };
   int64_t p = p0 + rl;
@@ -106,27 +202,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_bf16_kernel(const bf16x8* _
       sx[k] += g[k] * ((yv[k] - mu[k]) * is[k]);
     }
   }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    sh[k][t] = sg[k];
-    sh[8 + k][t] = sx[k];
-  }
-  __syncthreads();
-  // pairwise tree over the row lanes (thread t = rl * Q + q): fixed order -> deterministic
-  for (int s = RL >> 1; s >= 1; s >>= 1) {
-    if (rl < s) {
-#pragma unroll
-      for (int k = 0; k < 16; ++k) sh[k][t] += sh[k][t + s * Q];
-    }
-    __syncthreads();
-  }
-  if (rl == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      red[(size_t)blockIdx.y * C8 * 8 + cq * 8 + k] = sh[k][t];
-      red[((size_t)P + blockIdx.y) * C8 * 8 + cq * 8 + k] = sh[8 + k][t];
-    }
-  }
+  bnb_store_partial_rows(sg, sx, Q, cq, blockIdx.y, P, C8, red);   // thread t = rl * Q + q
 }
 
 extern "C" int dt_bn_bwd_rows_bf16(int64_t n_pix) { return dt_cdiv(n_pix, bnb_rb(n_pix)); }
@@ -232,13 +308,13 @@ extern "C" int dt_bn_bwd_apply_bf16(const void* dout, const void* out_act, const
   DT_REQUIRE(dout && y && mean && invstd && gamma && red && dgamma && dbeta && dy && n_pix > 0 && C > 0 &&
                  (C & 7) == 0 && P > 0,
              "bn_bwd_apply_bf16: bad args");
-  DT_REQUIRE(256 % (C / 8) == 0, "bn_bwd_apply_bf16: C/8 must divide 256 (C=%d)", C);
+  DT_REQUIRE(dt_groups_divide_256(C, 8), "bn_bwd_apply_bf16: C/8 must divide 256 (C=%d)", C);
   DT_REQUIRE_COEF_ALIGNED(dt_aligned16(mean, invstd, gamma, dgamma, dbeta, act_scale, act_shift), "bn_bwd_apply_bf16");
   hipStream_t st = (hipStream_t)stream;
   int rc = dt_bn_bwd_finish_sums(red, P, C, dgamma, dbeta, st);
   if (rc != DT_OK) return rc;
   const int64_t n8 = n_pix * C / 8;
-  const int g = dt_ew_grid(n8, 4096);
+  const int g = dt_ew_grid(n8, EW_CAP);
   hipLaunchKernelGGL(bn_bwd_apply_bf16_kernel, dim3((unsigned)g), dim3(256), 0, st, (const bf16x8*)dout,
                      (const bf16x8*)out_act, (const bf16x8*)y, mean, invstd, gamma, dgamma, dbeta, act_scale, act_shift,
                      (bf16x8*)dy, (bf16x8*)dres, dres_accumulate, n8, C / 8, (float)(1.0 / (double)n_pix));
@@ -296,7 +372,7 @@ extern "C" int dt_maxpool3x3s2_bf16_amax(const void* x, void* out, uint8_t* argm
   DT_REQUIRE(x && out && argmax && B > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0, "maxpool_bf16_amax: bad args");
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const int64_t total = (int64_t)B * Ho * Wo * (C / 8);
-  const int g = dt_ew_grid(total, 4096);
+  const int g = dt_ew_grid(total, EW_CAP);
   hipLaunchKernelGGL(maxpool_bf16_amax_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)x,
                      (bf16x8*)out, (uint2*)argmax, B, H, W, C / 8, Ho, Wo);
   DT_LAUNCH_CHECK();
@@ -333,22 +409,11 @@ __global__ __launch_bounds__(256) void maxpool_bwd_bf16_kernel(const bf16x8* __r
         }
       }
     }
-    bf16x8 o;
-    if (acc) {
-      float prev[8];
-      load8(dx, i, prev);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (__bf16)(prev[k] + g[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (__bf16)g[k];
-    }
-    dx[i] = o;
+    store8(dx, i, g, acc);
   }
 }
 
-// even maps: one thread per 2 x 2 block of input pixels — each of the (at most four) windows it lies in is loaded once
-// (bf16 twin of maxpool_bwd_quad_kernel, elementwise.hip; same per-pixel summation order: bit-identical)
+// even maps: one thread per 2 x 2 block of input pixels (pool_block_grads)
 __global__ __launch_bounds__(256) void maxpool_bwd_bf16_quad_kernel(const bf16x8* __restrict__ dout,
                                                                     const uint2* __restrict__ amax, bf16x8* __restrict__ dx,
                                                                     int acc, int B, int H, int W, int C8, int Ho, int Wo) {
@@ -361,56 +426,16 @@ __global__ __launch_bounds__(256) void maxpool_bwd_bf16_quad_kernel(const bf16x8
     rr /= Wo;
     const int q = (int)(rr % Ho);
     const int b = (int)(rr / Ho);
-    const bool q1 = q + 1 < Ho, p1 = p + 1 < Wo;
-    const int64_t o00 = i, o01 = i + C8, o10 = i + (int64_t)Wo * C8, o11 = o10 + C8;
-    float d00[8], d01[8], d10[8], d11[8];
-    const uint2 none = make_uint2(0xffffffffu, 0xffffffffu);    // an index no tap has
-    load8(dout, o00, d00);
-    load8(dout, p1 ? o01 : o00, d01);
-    load8(dout, q1 ? o10 : o00, d10);
-    load8(dout, (q1 && p1) ? o11 : o00, d11);
-    const uint2 a00 = amax[o00], a01 = p1 ? amax[o01] : none, a10 = q1 ? amax[o10] : none,
-                a11 = (q1 && p1) ? amax[o11] : none;
-    float g00[8], g01[8], g10[8], g11[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int sh = 8 * (k & 3);
-      const unsigned t00 = ((k < 4 ? a00.x : a00.y) >> sh) & 0xffu, t01 = ((k < 4 ? a01.x : a01.y) >> sh) & 0xffu,
-                     t10 = ((k < 4 ? a10.x : a10.y) >> sh) & 0xffu, t11 = ((k < 4 ? a11.x : a11.y) >> sh) & 0xffu;
-      float u00 = 0.f, u01 = 0.f, u10 = 0.f, u11 = 0.f;
-      if (t00 == 4u) u00 += d00[k];
-      if (t00 == 5u) u01 += d00[k];
-      if (t01 == 3u) u01 += d01[k];
-      if (t00 == 7u) u10 += d00[k];
-      if (t10 == 1u) u10 += d10[k];
-      if (t00 == 8u) u11 += d00[k];
-      if (t01 == 6u) u11 += d01[k];
-      if (t10 == 2u) u11 += d10[k];
-      if (t11 == 0u) u11 += d11[k];
-      g00[k] = u00; g01[k] = u01; g10[k] = u10; g11[k] = u11;
-    }
+    float g[4][8];
+    pool_block_grads(dout, amax, i, q, p, Ho, Wo, C8, g);
     const int64_t x00 = (((int64_t)b * H + 2 * q) * W + 2 * p) * C8 + c8, x10 = x00 + (int64_t)W * C8;
     const int64_t xs[4] = {x00, x00 + C8, x10, x10 + C8};
-    const float* gs[4] = {g00, g01, g10, g11};
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      bf16x8 o;
-      if (acc) {
-        float prev[8];
-        load8(dx, xs[e], prev);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = (__bf16)(prev[k] + gs[e][k]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = (__bf16)gs[e][k];
-      }
-      dx[xs[e]] = o;
-    }
+    for (int e = 0; e < 4; ++e) store8(dx, xs[e], g[e], acc);
   }
 }
 
-// with the BatchNorm-backward sums of the pooled layer (the stem) from the ROUNDED gradient it writes and the mask of
-// bf16(y * scale + shift), like bn_bwd_reduce_bf16_kernel (fp32 twin: maxpool_bwd_quad_bn_kernel)
+// with the BatchNorm-backward sums of the pooled layer (the stem) from the ROUNDED gradient it writes
 __global__ __launch_bounds__(256) void maxpool_bwd_bf16_quad_bn_kernel(const bf16x8* __restrict__ dout,
                                                                        const uint2* __restrict__ amax, bf16x8* __restrict__ dx,
                                                                        const bf16x8* __restrict__ y,
@@ -420,11 +445,9 @@ __global__ __launch_bounds__(256) void maxpool_bwd_bf16_quad_bn_kernel(const bf1
                                                                        const float* __restrict__ act_shift,
                                                                        float* __restrict__ red, int acc, int B, int H, int W,
                                                                        int C8, int Ho, int Wo, int P) {
-  __shared__ float sh[16][256];
   const int64_t total = (int64_t)B * Ho * Wo * C8;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;   // multiple of C8 (host check)
-  const int t = threadIdx.x;
-  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + t;
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int c8 = (int)(i0 % C8);
   float mu[8], is[8], asc[8], ash[8], sg[8], sx[8];
   ldc8(mean, c8 * 8, mu);
@@ -433,91 +456,42 @@ __global__ __launch_bounds__(256) void maxpool_bwd_bf16_quad_bn_kernel(const bf1
   ldc8(act_shift, c8 * 8, ash);
 #pragma unroll
   for (int k = 0; k < 8; ++k) sg[k] = sx[k] = 0.f;
-  const uint2 none = make_uint2(0xffffffffu, 0xffffffffu);
   for (int64_t i = i0; i < total; i += stride) {
     int64_t rr = i / C8;
     const int p = (int)(rr % Wo);
     rr /= Wo;
     const int q = (int)(rr % Ho);
     const int b = (int)(rr / Ho);
-    const bool q1 = q + 1 < Ho, p1 = p + 1 < Wo;
-    const int64_t o00 = i, o01 = i + C8, o10 = i + (int64_t)Wo * C8, o11 = o10 + C8;
-    float d00[8], d01[8], d10[8], d11[8];
-    load8(dout, o00, d00);
-    load8(dout, p1 ? o01 : o00, d01);
-    load8(dout, q1 ? o10 : o00, d10);
-    load8(dout, (q1 && p1) ? o11 : o00, d11);
-    const uint2 a00 = amax[o00], a01 = p1 ? amax[o01] : none, a10 = q1 ? amax[o10] : none,
-                a11 = (q1 && p1) ? amax[o11] : none;
     float g[4][8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int shf = 8 * (k & 3);
-      const unsigned t00 = ((k < 4 ? a00.x : a00.y) >> shf) & 0xffu, t01 = ((k < 4 ? a01.x : a01.y) >> shf) & 0xffu,
-                     t10 = ((k < 4 ? a10.x : a10.y) >> shf) & 0xffu, t11 = ((k < 4 ? a11.x : a11.y) >> shf) & 0xffu;
-      float u00 = 0.f, u01 = 0.f, u10 = 0.f, u11 = 0.f;
-      if (t00 == 4u) u00 += d00[k];
-      if (t00 == 5u) u01 += d00[k];
-      if (t01 == 3u) u01 += d01[k];
-      if (t00 == 7u) u10 += d00[k];
-      if (t10 == 1u) u10 += d10[k];
-      if (t00 == 8u) u11 += d00[k];
-      if (t01 == 6u) u11 += d01[k];
-      if (t10 == 2u) u11 += d10[k];
-      if (t11 == 0u) u11 += d11[k];
-      g[0][k] = u00; g[1][k] = u01; g[2][k] = u10; g[3][k] = u11;
-    }
+    pool_block_grads(dout, amax, i, q, p, Ho, Wo, C8, g);
     const int64_t x00 = (((int64_t)b * H + 2 * q) * W + 2 * p) * C8 + c8, x10 = x00 + (int64_t)W * C8;
     const int64_t xs[4] = {x00, x00 + C8, x10, x10 + C8};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float prev[8], yv[8];
+      float prev[8], yv[8], gr[8];
       if (acc) load8(dx, xs[e], prev);
       load8(y, xs[e], yv);
       bf16x8 o;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         o[k] = (__bf16)(acc ? prev[k] + g[e][k] : g[e][k]);
-        const float act = (float)(__bf16)(yv[k] * asc[k] + ash[k]);
-        const float gm = act > 0.f ? (float)o[k] : 0.f;
-        sg[k] += gm;
-        sx[k] += gm * ((yv[k] - mu[k]) * is[k]);
+        gr[k] = (float)o[k];
       }
+      bnb_masked_sums(gr, yv, asc, ash, mu, is, sg, sx);
       dx[xs[e]] = o;
     }
   }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    sh[k][t] = sg[k];
-    sh[8 + k][t] = sx[k];
-  }
-  __syncthreads();
-  const int rl = t / C8, RL = 256 / C8;
-  for (int s2 = RL >> 1; s2 >= 1; s2 >>= 1) {
-    if (rl < s2) {
-#pragma unroll
-      for (int k = 0; k < 16; ++k) sh[k][t] += sh[k][t + s2 * C8];
-    }
-    __syncthreads();
-  }
-  if (t < C8) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      red[(size_t)blockIdx.x * C8 * 8 + t * 8 + k] = sh[k][t];
-      red[((size_t)P + blockIdx.x) * C8 * 8 + t * 8 + k] = sh[8 + k][t];
-    }
-  }
+  bnb_store_partial_rows(sg, sx, C8, threadIdx.x, blockIdx.x, P, C8, red);   // the writers, t < C8, hold channel group t
 }
 
 extern "C" int dt_maxpool3x3s2_bwd_bn_bf16_rows(int B, int H, int W, int C) {
-  if (((H | W) & 1) != 0 || C <= 0 || (C & 7) != 0 || C / 8 > 256 || 256 % (C / 8) != 0) return 0;   // even maps only
-  return dt_ew_grid((int64_t)B * (H / 2) * (W / 2) * (C / 8), 4096);
+  if (((H | W) & 1) != 0 || !dt_groups_divide_256(C, 8)) return 0;   // even maps only
+  return dt_ew_grid((int64_t)B * (H / 2) * (W / 2) * (C / 8), EW_CAP);
 }
 
 extern "C" int dt_maxpool3x3s2_bwd_bn_bf16(const void* dout, const uint8_t* argmax, void* dx, int accumulate,
                                            const dt_bn_bwd_fuse* fuse, float* red, int B, int H, int W, int C, void* stream) {
-  DT_REQUIRE(dout && argmax && dx && fuse && red && fuse->y && fuse->mean && fuse->invstd && fuse->act_scale &&
-                 fuse->act_shift && B > 0 && H > 0 && W > 0, "maxpool_bwd_bn_bf16: bad args");
+  DT_REQUIRE(dout && argmax && dx && red && dt_fuse_complete(fuse) && B > 0 && H > 0 && W > 0, "maxpool_bwd_bn_bf16: bad args");
   const int P = dt_maxpool3x3s2_bwd_bn_bf16_rows(B, H, W, C);
   DT_REQUIRE(P > 0, "maxpool_bwd_bn_bf16: even maps, C/8 a divisor of 256 (H=%d W=%d C=%d)", H, W, C);
   DT_REQUIRE_COEF_ALIGNED(dt_fuse_aligned16(fuse), "maxpool_bwd_bn_bf16");
@@ -533,14 +507,14 @@ extern "C" int dt_maxpool3x3s2_bwd_bf16(const void* dout, const uint8_t* argmax,
   DT_REQUIRE(dout && argmax && dx && B > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0, "maxpool_bwd_bf16: bad args");
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   if (((H | W) & 1) == 0) {
-    const int gq = dt_ew_grid((int64_t)B * Ho * Wo * (C / 8), 8192);
+    const int gq = dt_ew_grid((int64_t)B * Ho * Wo * (C / 8), EW_CAP_WIDE);
     hipLaunchKernelGGL(maxpool_bwd_bf16_quad_kernel, dim3((unsigned)gq), dim3(256), 0, (hipStream_t)stream,
                        (const bf16x8*)dout, (const uint2*)argmax, (bf16x8*)dx, accumulate, B, H, W, C / 8, Ho, Wo);
     DT_LAUNCH_CHECK();
     return DT_OK;
   }
   const int64_t total = (int64_t)B * H * W * (C / 8);
-  const int g = dt_ew_grid(total, 4096);
+  const int g = dt_ew_grid(total, EW_CAP);
   hipLaunchKernelGGL(maxpool_bwd_bf16_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)dout,
                      (const uint2*)argmax, (bf16x8*)dx, accumulate, B, H, W, C / 8, Ho, Wo);
   DT_LAUNCH_CHECK();
@@ -589,7 +563,7 @@ extern "C" int64_t dt_channel_sums_bf16_workspace(int64_t n_pix, int C) { return
 
 extern "C" int dt_channel_sums_bf16(const void* g, float* workspace, int64_t n_pix, int C, float* out, void* stream) {
   DT_REQUIRE(g && workspace && out && n_pix > 0 && C > 0, "channel_sums_bf16: bad args");
-  DT_REQUIRE((C & 7) == 0 && C <= 256 && 256 % (C / 8) == 0, "channel_sums_bf16: C/8 must divide 256, C <= 256 (C=%d)", C);
+  DT_REQUIRE(C <= 256 && dt_groups_divide_256(C, 8), "channel_sums_bf16: C/8 must divide 256, C <= 256 (C=%d)", C);
   hipStream_t st = (hipStream_t)stream;
   const int P = dt_cdiv(n_pix, CSB_RB);
   hipLaunchKernelGGL(channel_sums_bf16_kernel, dim3(P), dim3(256), 0, st, (const bf16x8*)g, workspace, n_pix, C / 8);
@@ -618,24 +592,16 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_bf16_kernel(const bf16x8* 
     load8(dup, base + C8, bq);
     load8(dup, base + (int64_t)W2 * C8, c);
     load8(dup, base + (int64_t)W2 * C8 + C8, d);
-    bf16x8 o;
-    if (acc) {   // a node of a dense decoder collects the gradients of several consumers: one rounding per contribution
-      float prev[8];
-      load8(dx, i, prev);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (__bf16)(prev[k] + ((a[k] + bq[k]) + (c[k] + d[k])));
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (__bf16)((a[k] + bq[k]) + (c[k] + d[k]));
-    }
-    dx[i] = o;
+    for (int k = 0; k < 8; ++k) a[k] = (a[k] + bq[k]) + (c[k] + d[k]);
+    store8(dx, i, a, acc);
   }
 }
 
 static int upsample2x_bwd_bf16_launch(const void* dup, void* dx, int acc, int B, int H, int W, int C, void* stream) {
   DT_REQUIRE(dup && dx && B > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0, "upsample2x_bwd_bf16: bad args");
   const int64_t total = (int64_t)B * H * W * (C / 8);
-  const int g = dt_ew_grid(total, 4096);
+  const int g = dt_ew_grid(total, EW_CAP);
   hipLaunchKernelGGL(upsample2x_bwd_bf16_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream,
                      (const bf16x8*)dup, (bf16x8*)dx, acc, B, H, W, C / 8);
   DT_LAUNCH_CHECK();
@@ -652,7 +618,7 @@ extern "C" int dt_upsample2x_bwd_acc_bf16(const void* dup, void* dx, int accumul
 }
 
 // ------------------------------------------------------------------ channel-slice copies of bf16 tensors (Unet++ under AMP)
-// bf16 twin of dt_channel_slice: wide[n, off : off + Cn] = narrow[n, :]  /  narrow[n, :] (+)= wide[n, off : off + Cn];
+// wide[n, off : off + Cn] = narrow[n, :]  /  narrow[n, :] (+)= wide[n, off : off + Cn];
 // channel counts and the offset multiples of 8 (16-byte units); the accumulating form adds in fp32 and rounds once
 __global__ __launch_bounds__(256) void channel_slice_bf16_kernel(const bf16x8* __restrict__ src, bf16x8* __restrict__ dst,
                                                                  int64_t n8, int Cn8, int Cw8, int off8, int to_wide, int acc) {
@@ -666,13 +632,9 @@ __global__ __launch_bounds__(256) void channel_slice_bf16_kernel(const bf16x8* _
     } else if (!acc) {
       dst[i] = src[w];
     } else {
-      float a[8], b[8];
+      float a[8];
       load8(src, w, a);
-      load8(dst, i, b);
-      bf16x8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (__bf16)(b[k] + a[k]);
-      dst[i] = o;
+      store8(dst, i, a, 1);
     }
   }
 }
@@ -683,15 +645,13 @@ extern "C" int dt_channel_slice_bf16(const void* src, void* dst, int64_t n_pix, 
   DT_REQUIRE((C_narrow & 7) == 0 && (C_wide & 7) == 0 && (offset & 7) == 0 && offset >= 0 && offset + C_narrow <= C_wide,
              "channel_slice_bf16: channel counts and offset must be multiples of 8 inside the wide tensor");
   const int64_t n8 = n_pix * (C_narrow / 8);
-  const int grid = (int)(n8 / 256 + 1 < 8192 ? n8 / 256 + 1 : 8192);
-  hipLaunchKernelGGL(channel_slice_bf16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)src,
+  hipLaunchKernelGGL(channel_slice_bf16_kernel, dim3(dt_slice_grid(n8)), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)src,
                      (bf16x8*)dst, n8, C_narrow / 8, C_wide / 8, offset / 8, to_wide, accumulate);
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
 
-// 2x2 sum + BatchNorm-backward reduction of the producing layer (bf16 twin of upsample2x_bwd_bn_kernel): sums from the
-// ROUNDED gradient and the mask of bf16(y*scale+shift), like bn_bwd_reduce_bf16_kernel
+// 2x2 sum + BatchNorm-backward reduction of the producing layer: sums from the ROUNDED gradient it writes
 __global__ __launch_bounds__(256) void upsample2x_bwd_bn_bf16_kernel(const bf16x8* __restrict__ dup, bf16x8* __restrict__ dx,
                                                                      const bf16x8* __restrict__ y,
                                                                      const float* __restrict__ mean,
@@ -700,11 +660,10 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_bn_bf16_kernel(const bf16x
                                                                      const float* __restrict__ act_shift,
                                                                      float* __restrict__ red, int B, int H, int W, int C8,
                                                                      int P) {
-  __shared__ float sh[16][256];
   const int64_t total = (int64_t)B * H * W * C8;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;   // multiple of C8 (host check)
-  const int W2 = 2 * W, t = threadIdx.x;
-  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + t;
+  const int W2 = 2 * W;
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int c8 = (int)(i0 % C8);
   float mu[8], is[8], asc[8], ash[8], sg[8], sx[8];
   ldc8(mean, c8 * 8, mu);
@@ -730,47 +689,24 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_bn_bf16_kernel(const bf16x
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       o[k] = (__bf16)((a[k] + bq[k]) + (c[k] + d[k]));
-      const float act = (float)(__bf16)(yv[k] * asc[k] + ash[k]);
-      const float g = act > 0.f ? (float)o[k] : 0.f;
-      sg[k] += g;
-      sx[k] += g * ((yv[k] - mu[k]) * is[k]);
+      a[k] = (float)o[k];
     }
+    bnb_masked_sums(a, yv, asc, ash, mu, is, sg, sx);
     dx[i] = o;
   }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    sh[k][t] = sg[k];
-    sh[8 + k][t] = sx[k];
-  }
-  __syncthreads();
-  const int rl = t / C8, RL = 256 / C8;
-  for (int s = RL >> 1; s >= 1; s >>= 1) {
-    if (rl < s) {
-#pragma unroll
-      for (int k = 0; k < 16; ++k) sh[k][t] += sh[k][t + s * C8];
-    }
-    __syncthreads();
-  }
-  if (t < C8) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      red[(size_t)blockIdx.x * C8 * 8 + t * 8 + k] = sh[k][t];
-      red[((size_t)P + blockIdx.x) * C8 * 8 + t * 8 + k] = sh[8 + k][t];
-    }
-  }
+  bnb_store_partial_rows(sg, sx, C8, threadIdx.x, blockIdx.x, P, C8, red);   // the writers, t < C8, hold channel group t
 }
 
 extern "C" int dt_upsample2x_bwd_bn_bf16_rows(int B, int H, int W, int C) {
-  return dt_ew_grid((int64_t)B * H * W * (C / 8), 4096);
+  return dt_ew_grid((int64_t)B * H * W * (C / 8), EW_CAP);
 }
 
 extern "C" int dt_upsample2x_bwd_bn_bf16(const void* dup, void* dx, const dt_bn_bwd_fuse* fuse, float* red, int B, int H,
                                          int W, int C, void* stream) {
-  DT_REQUIRE(dup && dx && fuse && red && fuse->y && fuse->mean && fuse->invstd && fuse->act_scale && fuse->act_shift &&
-                 B > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0,
+  DT_REQUIRE(dup && dx && red && dt_fuse_complete(fuse) && B > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0,
              "upsample2x_bwd_bn_bf16: bad args");
   const int C8 = C / 8;
-  DT_REQUIRE(C8 <= 256 && 256 % C8 == 0, "upsample2x_bwd_bn_bf16: C/8 must divide 256 (C=%d)", C);
+  DT_REQUIRE(dt_groups_divide_256(C, 8), "upsample2x_bwd_bn_bf16: C/8 must divide 256 (C=%d)", C);
   DT_REQUIRE_COEF_ALIGNED(dt_fuse_aligned16(fuse), "upsample2x_bwd_bn_bf16");
   const int P = dt_upsample2x_bwd_bn_bf16_rows(B, H, W, C);
   hipLaunchKernelGGL(upsample2x_bwd_bn_bf16_kernel, dim3(P), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)dup,
@@ -798,7 +734,7 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const f32x4* __restric
 
 extern "C" int dt_f32_to_bf16(const float* x, void* out, int64_t n, void* stream) {
   DT_REQUIRE(x && out && n > 0 && (n & 7) == 0, "f32_to_bf16: n must be a multiple of 8");
-  const int g = dt_ew_grid(n / 8, 4096);
+  const int g = dt_ew_grid(n / 8, EW_CAP);
   hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const f32x4*)x,
                      (bf16x8*)out, n / 8);
   DT_LAUNCH_CHECK();

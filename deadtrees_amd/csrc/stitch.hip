@@ -14,7 +14,7 @@
 #include "conv_host.h"
 #include "views.h"
 
-#define ST_CAP (256 * 16)   // grid cap, as EW_CAP of elementwise.hip: 16 workgroups per CU, grid-stride beyond
+#define ST_CAP (256 * 16)   // grid cap, as EW_CAP (conv_host.h): 16 workgroups per CU, grid-stride beyond
 
 static inline int stitch_windows(int L, int d, int o) {
   const int s = d - o;

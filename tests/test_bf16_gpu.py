@@ -330,6 +330,19 @@ def _bf(t):
 def test_bn_backward_bf16(n_pix, C, mode):
     """dt_bn_bwd_reduce_bf16 / _apply_bf16 against the fp64 batch-norm backward on the same bf16 operands:
     dgamma/dbeta to fp32-reduction accuracy, dy and the residual gradient to one bf16 rounding."""
+    _bn_backward_bf16(n_pix, C, mode)
+
+
+@pytest.mark.parametrize("n_pix", [3, 257])
+@pytest.mark.parametrize("C", [8, 2048])
+@pytest.mark.parametrize("mode", ["stored_act", "virtual_act", "linear"])
+def test_bn_backward_bf16_partial_row_extremes(n_pix, C, mode):
+    """the partial-row epilogue of dt_bn_bwd_reduce_bf16 at its ends: one channel group per workgroup (256 lanes share
+    it, the deepest tree) and 64 groups per workgroup; 3 rows, and 257 = one row past a row block (the single-row tail)"""
+    _bn_backward_bf16(n_pix, C, mode)
+
+
+def _bn_backward_bf16(n_pix, C, mode):
     ops = _ops()
     g = torch.Generator().manual_seed(n_pix % 97 + C)
     y = torch.randn((n_pix, C), generator=g) * (0.5 + torch.rand(C, generator=g)) + 0.3 * torch.randn(C, generator=g)

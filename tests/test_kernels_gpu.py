@@ -334,13 +334,17 @@ def test_conv_wgrad_upsample_concat():
     assert rel_err(dw.cpu().permute(3, 2, 0, 1), wt.grad) < 3e-6
 
 
-@pytest.mark.parametrize("C,shape", [(64, (2, 16, 16)), (16, (3, 40, 24)), (512, (2, 2, 2))])
-def test_batchnorm_train_forward_backward(C, shape):
+def _batchnorm_train_forward_backward(C, shape, virtual_act=False, fp64_stats=False):
+    """fp64 torch batch norm (training) + residual + ReLU against bn_finalize / bn_act / bn_backward with the stored
+    activation; virtual_act: no residual, and the backward takes its ReLU mask from y * scale + shift instead;
+    fp64_stats: mean / invstd handed over from fp64 instead of bn_finalize (the backward alone is under test)"""
     ops = _ops()
     g = torch.Generator().manual_seed(C)
     B, H, W = shape
     y = (torch.randn((B, C, H, W), generator=g, dtype=torch.float64) * 1.5 + 0.3).requires_grad_(True)
     res = torch.randn((B, C, H, W), generator=g, dtype=torch.float64)
+    if virtual_act:
+        res = torch.zeros_like(res)
     gamma = (1 + 0.2 * torch.randn(C, generator=g, dtype=torch.float64)).requires_grad_(True)
     beta = (0.1 * torch.randn(C, generator=g, dtype=torch.float64)).requires_grad_(True)
     rm = torch.zeros(C, dtype=torch.float64)
@@ -352,18 +356,41 @@ def test_batchnorm_train_forward_backward(C, shape):
     yg = nhwc(y.detach())
     stats = torch.stack([yg.sum(dim=(0, 1, 2)), (yg * yg).sum(dim=(0, 1, 2))]).reshape(2, 1, C).contiguous()
     rmg, rvg = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
-    mean, invstd, scale, shift = ops.bn_finalize(stats, B * H * W, gamma.detach().float().to(DEV),
-                                                 beta.detach().float().to(DEV), rmg, rvg)
+    if fp64_stats:
+        m64, g64 = y.detach().mean(dim=(0, 2, 3)), gamma.detach()
+        is64 = 1.0 / torch.sqrt(y.detach().var(dim=(0, 2, 3), unbiased=False) + 1e-5)
+        mean, invstd, scale, shift = (t.float().to(DEV) for t in (m64, is64, g64 * is64, beta.detach() - m64 * g64 * is64))
+    else:
+        mean, invstd, scale, shift = ops.bn_finalize(stats, B * H * W, gamma.detach().float().to(DEV),
+                                                     beta.detach().float().to(DEV), rmg, rvg)
     z = ops.bn_act(yg, scale, shift, res=nhwc(res), relu=True)
     assert rel_err(to_nchw(z), out.detach()) < 1e-5
-    np.testing.assert_allclose(rmg.cpu().double(), rm, rtol=1e-5, atol=1e-6)
-    np.testing.assert_allclose(rvg.cpu().double(), rv, rtol=1e-5, atol=1e-6)
-    dy, dgamma, dbeta, dres = ops.bn_backward(nhwc(dout), z, yg, mean, invstd, gamma.detach().float().to(DEV),
-                                              want_dres=True)
+    if not fp64_stats:
+        np.testing.assert_allclose(rmg.cpu().double(), rm, rtol=1e-5, atol=1e-6)
+        np.testing.assert_allclose(rvg.cpu().double(), rv, rtol=1e-5, atol=1e-6)
+    mask = dict(act_scale=scale, act_shift=shift) if virtual_act else {}
+    dy, dgamma, dbeta, dres = ops.bn_backward(nhwc(dout), None if virtual_act else z, yg, mean, invstd,
+                                              gamma.detach().float().to(DEV), want_dres=True, **mask)
     assert rel_err(to_nchw(dy), y.grad) < 2e-5
     assert rel_err(dgamma.cpu(), gamma.grad) < 2e-5
     assert rel_err(dbeta.cpu(), beta.grad) < 2e-5
     assert rel_err(to_nchw(dres), dout * (out.detach() > 0)) < 1e-6
+
+
+@pytest.mark.parametrize("C,shape", [(64, (2, 16, 16)), (16, (3, 40, 24)), (512, (2, 2, 2))])
+def test_batchnorm_train_forward_backward(C, shape):
+    _batchnorm_train_forward_backward(C, shape)
+
+
+@pytest.mark.parametrize("virtual_act", [False, True], ids=["stored_act", "virtual_act"])
+@pytest.mark.parametrize("n_pix", [3, 257])
+@pytest.mark.parametrize("C", [4, 1024])
+def test_batchnorm_backward_partial_row_extremes(C, n_pix, virtual_act):
+    """the partial-row epilogue of dt_bn_bwd_reduce at its ends: one channel quad per workgroup (256 lanes share it,
+    the deepest tree) and 64 quads per workgroup; 3 rows, and 257 = one row past a row block (the single-row tail).
+    The statistics come from fp64 (as in test_bn_backward_bf16): E[x^2] - m^2 from fp32 partial sums, which is how this
+    file feeds bn_finalize, does not resolve the variance of a 3-pixel batch, and the forward is not what is tested"""
+    _batchnorm_train_forward_backward(C, (1, 1, n_pix), virtual_act, fp64_stats=True)
 
 
 @pytest.mark.parametrize("H,W", [(20, 28), (21, 27), (2, 2), (64, 6)])
@@ -504,6 +531,18 @@ def test_conv_with_fused_bn_backward_reduction(B, H, W, Cin, Cout):
 def test_upsample_backward_with_fused_bn_reduction(dtype, B, H, W, C):
     """dt_upsample2x_bwd_bn(_bf16): dx bit-identical to dt_upsample2x_bwd(_bf16); partial sums = BatchNorm-backward
     reduction of (dx, y) with the virtual-activation mask."""
+    _upsample_backward_with_fused_bn_reduction(dtype, B, H, W, C)
+
+
+@pytest.mark.parametrize("dtype,C", [(torch.float32, 4), (torch.float32, 1024), (torch.bfloat16, 8), (torch.bfloat16, 2048)],
+                         ids=["fp32-C4", "fp32-C1024", "bf16-C8", "bf16-C2048"])
+def test_upsample_backward_fused_bn_partial_row_extremes(dtype, C):
+    """the shared partial-row epilogue at its ends: ONE channel group per workgroup (all 256 lanes in one tree) and 256
+    groups (no tree at all), on a 2 x 2 map"""
+    _upsample_backward_with_fused_bn_reduction(dtype, 1, 2, 2, C)
+
+
+def _upsample_backward_with_fused_bn_reduction(dtype, B, H, W, C):
     ops = _ops()
     g = torch.Generator().manual_seed(B + H + C)
     dup = torch.randn((B, 2 * H, 2 * W, C), generator=g).to(dtype)
@@ -565,19 +604,31 @@ def test_conv_gradient_join_with_fused_bn_backward_reduction(B, H, W, Cin, Cout)
 def test_maxpool_backward_with_fused_batchnorm_sums(acc):
     """dt_maxpool3x3s2_bwd_bn: the gradient is bit-identical to dt_maxpool3x3s2_bwd, the partial rows sum to the
     BatchNorm-backward reduction of the pooled layer over that gradient (mask from y * scale + shift) — fp32 and bf16"""
+    _maxpool_backward_with_fused_batchnorm_sums(torch.Generator().manual_seed(31), acc, 2, 64, 20, 28, (False, True))
+
+
+@pytest.mark.parametrize("acc", [False, True])
+@pytest.mark.parametrize("H,W", [(2, 2), (2, 6)])
+@pytest.mark.parametrize("bf,Cc", [(False, 4), (False, 1024), (True, 8), (True, 2048)],
+                         ids=["fp32-C4", "fp32-C1024", "bf16-C8", "bf16-C2048"])
+def test_maxpool_backward_fused_batchnorm_partial_row_extremes(bf, Cc, H, W, acc):
+    """the shared partial-row epilogue at its ends (one channel group per workgroup / 256 groups) on maps whose last
+    2 x 2 block has no right or lower neighbour window"""
+    _maxpool_backward_with_fused_batchnorm_sums(torch.Generator().manual_seed(Cc + H * W), acc, 1, Cc, H, W, (bf,))
+
+
+def _maxpool_backward_with_fused_batchnorm_sums(g, acc, B, Cc, H, W, precisions):
     import ctypes as C
     from deadtrees_amd import _lib
     ops = _ops()
     lib = _lib.load()
-    g = torch.Generator().manual_seed(31)
-    B, Cc, H, W = 2, 64, 20, 28
     st = torch.cuda.current_stream().cuda_stream
     yraw = torch.randn((B, H, W, Cc), generator=g)
     sc, sh = 1 + 0.3 * torch.randn(Cc, generator=g), 0.2 * torch.randn(Cc, generator=g)
     mu, istd = 0.1 * torch.randn(Cc, generator=g), 1 + 0.2 * torch.rand(Cc, generator=g)
     x = F.relu(yraw * sc + sh)
     coef = [t.to(DEV) for t in (mu, istd, sc, sh)]
-    for bf in (False, True):
+    for bf in precisions:
         dt = torch.bfloat16 if bf else torch.float32
         xd = x.to(dt).to(DEV)
         yd = yraw.to(dt).to(DEV)
