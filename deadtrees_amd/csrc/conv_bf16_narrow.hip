@@ -32,7 +32,6 @@
 #define NR_HW (NR_TW + 2)
 #define NR_HH (NR_TH + 2)
 #define NR_PIX (NR_HH * NR_HW)   // 340 halo pixels
-#define NR_CUS 256
 
 template <int CB, int NB>
 struct NrGeom {
@@ -338,68 +337,14 @@ int dt_conv_bf16_narrow_supported(const dt_conv_desc* d) {
 
 static int nr_tiles(const dt_conv_desc* d) { return d->B * dt_cdiv(d->Ho, NR_TH) * dt_cdiv(d->Wo, NR_TW); }
 
-// Workgroups of an instantiation that fit one CU, from its own code object: registers (512 per lane and SIMD, granule 8,
-// one wave of the workgroup per SIMD) and LDS (160 KiB).  The kernel is latency-bound by the bytes it keeps in flight
-// (PMC round 3: waves parked 53 % of the time at 3 workgroups per CU = 33 KB in flight per CU -> 3.6 TB/s), so the
-// persistent grid takes every slot there is — and exactly those, so that all workgroups walk the same number of tiles.
-template <class K>
-static int nr_occupancy(K kernel) {
-  hipFuncAttributes at;
-  if (hipFuncGetAttributes(&at, reinterpret_cast<const void*>(kernel)) != hipSuccess) return 2;
-  const int regs = ((at.numRegs + 7) / 8) * 8;
-  int by_regs = regs > 0 ? 512 / regs : 8;
-  const int by_lds = at.sharedSizeBytes > 0 ? (int)(163840 / at.sharedSizeBytes) : 8;
-  int occ = by_regs < by_lds ? by_regs : by_lds;
-  if (occ > 8) occ = 8;
-  if (occ < 1) occ = 1;
-  return occ;
-}
-
-template <int CB, int NB>
-static int nr_occ_of(bool tf, int bnb) {   // bnb: 0 none, 1 fused BatchNorm-backward sums, 2 with the up-sample backward
-  static int cache[4] = {0, 0, 0, 0};
-  const int v = tf ? 1 : (bnb ? 1 + bnb : 0);
-  if (cache[v] == 0)
-    cache[v] = tf ? nr_occupancy(conv3x3_bf16_narrow_kernel<CB, NB, true, false>)
-                  : (bnb == 2 ? nr_occupancy(conv3x3_bf16_narrow_kernel<CB, NB, false, true, true>)
-                     : bnb  ? nr_occupancy(conv3x3_bf16_narrow_kernel<CB, NB, false, true>)
-                            : nr_occupancy(conv3x3_bf16_narrow_kernel<CB, NB, false, false>));
-  return cache[v];
-}
-
-static int nr_per_cu(const dt_conv_desc* d, bool tf, int bnb) {
-  if (d->C0 == 16 && d->Cout == 16) return nr_occ_of<1, 1>(tf, bnb);
-  if (d->C0 == 16) return nr_occ_of<1, 2>(tf, bnb);
-  if (d->Cout == 16) return nr_occ_of<2, 1>(tf, bnb);
-  return nr_occ_of<2, 2>(tf, bnb);
-}
-
-// rows of the statistics buffer: an upper bound of every variant's persistent grid (8 workgroups per CU), the same for
-// all variants of a layer shape (dt_conv2d_bf16_stat_rows is asked before the variant is known)
-int dt_conv_bf16_narrow_rows(const dt_conv_desc* d) {
-  const int t = nr_tiles(d);
-  return t < 8 * NR_CUS ? t : 8 * NR_CUS;
-}
-
-int dt_conv_bf16_narrow_grid(const dt_conv_desc* d, int tf, int bnb) {
-  const int t = nr_tiles(d), per_cu = nr_per_cu(d, tf != 0, bnb);
-  return t < per_cu * NR_CUS ? t : per_cu * NR_CUS;
-}
-
-template <int CB, int NB>
-static int nr_launch(const ConvBfArgs& a, int grid, int total, bool tf, int bnb, hipStream_t st) {
-  const dim3 g((unsigned)grid), blk(256);
-  if (tf && bnb) return DT_EINVAL;
-  if (tf) hipLaunchKernelGGL((conv3x3_bf16_narrow_kernel<CB, NB, true, false>), g, blk, 0, st, a, total);
-  else if (bnb == 2) hipLaunchKernelGGL((conv3x3_bf16_narrow_kernel<CB, NB, false, true, true>), g, blk, 0, st, a, total);
-  else if (bnb) hipLaunchKernelGGL((conv3x3_bf16_narrow_kernel<CB, NB, false, true>), g, blk, 0, st, a, total);
-  else hipLaunchKernelGGL((conv3x3_bf16_narrow_kernel<CB, NB, false, false>), g, blk, 0, st, a, total);
-  return DT_OK;
-}
+// rows of the statistics buffer, the same for all variants of a layer shape (dt_conv2d_bf16_stat_rows is asked before the
+// variant is known)
+int dt_conv_bf16_narrow_rows(const dt_conv_desc* d) { return dt_persist_rows(nr_tiles(d)); }
 
 int dt_conv_bf16_narrow_launch(const dt_conv_desc* d, ConvBfArgs a, hipStream_t st, bool upsample_bwd) {
   DT_REQUIRE(dt_conv_bf16_narrow_supported(d), "conv_bf16_narrow: layer shape not supported");
   const bool tf = a.in_scale != nullptr;
+  // 0 none, 1 fused BatchNorm-backward sums, 2 with the up-sample backward
   const int bnb = a.bnb.y != nullptr ? (upsample_bwd ? 2 : 1) : 0;
   DT_REQUIRE(!upsample_bwd || (bnb == 2 && ((d->Ho | d->Wo) & 1) == 0),
              "conv_bf16_narrow: the up-sample backward form needs the fused sums and an even map");
@@ -408,14 +353,18 @@ int dt_conv_bf16_narrow_launch(const dt_conv_desc* d, ConvBfArgs a, hipStream_t 
   DT_REQUIRE(!(tf && bnb), "conv_bf16_narrow: no input transform on the BatchNorm-backward form");
   a.tiles_x = dt_cdiv(d->Wo, NR_TW);
   a.tiles_y = dt_cdiv(d->Ho, NR_TH);
-  const int total = nr_tiles(d), grid = dt_conv_bf16_narrow_grid(d, tf, bnb);
+  const int total = nr_tiles(d);
   a.P = dt_conv_bf16_narrow_rows(d);
-  int rc;
-  if (d->C0 == 16 && d->Cout == 16) rc = nr_launch<1, 1>(a, grid, total, tf, bnb, st);
-  else if (d->C0 == 16) rc = nr_launch<1, 2>(a, grid, total, tf, bnb, st);
-  else if (d->Cout == 16) rc = nr_launch<2, 1>(a, grid, total, tf, bnb, st);
-  else rc = nr_launch<2, 2>(a, grid, total, tf, bnb, st);
-  if (rc != DT_OK) return rc;
+  // variants (TF, BNB, UPB)
+  DT_TRY(dt_narrow_blocks(d->C0, d->Cout, [&](auto cb, auto nb) {
+    constexpr int CB = decltype(cb)::value, NB = decltype(nb)::value;
+    if (tf && bnb) return DT_EINVAL;
+    if (tf) dt_persist_launch<conv3x3_bf16_narrow_kernel<CB, NB, true, false>>(a, total, st);
+    else if (bnb == 2) dt_persist_launch<conv3x3_bf16_narrow_kernel<CB, NB, false, true, true>>(a, total, st);
+    else if (bnb) dt_persist_launch<conv3x3_bf16_narrow_kernel<CB, NB, false, true>>(a, total, st);
+    else dt_persist_launch<conv3x3_bf16_narrow_kernel<CB, NB, false, false>>(a, total, st);
+    return DT_OK;
+  }));
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
@@ -638,19 +587,8 @@ int dt_wgrad_bf16_narrow_supported(const dt_conv_desc* d) {
   return 1;
 }
 
-template <int CB, int NB>
-static int nrw_occ(bool tf) {
-  static int cache[2] = {0, 0};
-  if (cache[tf] == 0)
-    cache[tf] = tf ? nr_occupancy(conv3x3_wgrad_bf16_narrow_kernel<CB, NB, true>)
-                   : nr_occupancy(conv3x3_wgrad_bf16_narrow_kernel<CB, NB, false>);
-  return cache[tf];
-}
-
 size_t dt_wgrad_bf16_narrow_workspace(const dt_conv_desc* d) {
-  const int t = nr_tiles(d);
-  const size_t parts = (size_t)(t < 8 * NR_CUS ? t : 8 * NR_CUS);
-  return parts * 9 * d->C0 * d->Cout * sizeof(float);
+  return (size_t)dt_persist_rows(nr_tiles(d)) * 9 * d->C0 * d->Cout * sizeof(float);
 }
 
 // -> number of slabs written to `ws` (one per workgroup), or a negative error code
@@ -663,23 +601,11 @@ int dt_wgrad_bf16_narrow_launch(const dt_conv_desc* d, const void* src0, const v
   a.tiles_x = dt_cdiv(d->Wo, NR_TW); a.tiles_y = dt_cdiv(d->Ho, NR_TH);
   const int total = nr_tiles(d);
   const bool tf = in_scale != nullptr;
-  int occ;
-  if (d->C0 == 16 && d->Cout == 16) occ = nrw_occ<1, 1>(tf);
-  else if (d->C0 == 16) occ = nrw_occ<1, 2>(tf);
-  else if (d->Cout == 16) occ = nrw_occ<2, 1>(tf);
-  else occ = nrw_occ<2, 2>(tf);
-  const int grid = total < occ * NR_CUS ? total : occ * NR_CUS;
-  const dim3 g((unsigned)grid), blk(256);
-#define NRW_LAUNCH(CBv, NBv)                                                                                     \
-  do {                                                                                                           \
-    if (tf) hipLaunchKernelGGL((conv3x3_wgrad_bf16_narrow_kernel<CBv, NBv, true>), g, blk, 0, st, a, total);      \
-    else hipLaunchKernelGGL((conv3x3_wgrad_bf16_narrow_kernel<CBv, NBv, false>), g, blk, 0, st, a, total);       \
-  } while (0)
-  if (d->C0 == 16 && d->Cout == 16) NRW_LAUNCH(1, 1);
-  else if (d->C0 == 16) NRW_LAUNCH(1, 2);
-  else if (d->Cout == 16) NRW_LAUNCH(2, 1);
-  else NRW_LAUNCH(2, 2);
-#undef NRW_LAUNCH
+  const int grid = dt_narrow_blocks(d->C0, d->Cout, [&](auto cb, auto nb) {
+    constexpr int CB = decltype(cb)::value, NB = decltype(nb)::value;
+    return tf ? dt_persist_launch<conv3x3_wgrad_bf16_narrow_kernel<CB, NB, true>>(a, total, st)
+              : dt_persist_launch<conv3x3_wgrad_bf16_narrow_kernel<CB, NB, false>>(a, total, st);
+  });
   DT_LAUNCH_CHECK();
   return grid;
 }

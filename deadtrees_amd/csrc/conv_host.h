@@ -1,4 +1,5 @@
-// Host-side plumbing shared by the kernel files: descriptor checks, environment switches, grid sizing, alignment checks.
+// Host-side plumbing shared by the kernel files: descriptor checks, environment switches, grid sizing, the launcher
+// of the persistent kernels, alignment checks.
 // Nothing here reaches device code.
 #pragma once
 #include <stdlib.h>
@@ -66,6 +67,56 @@ static inline int dt_ew_grid(int64_t n_items, int64_t cap) {
 static inline int dt_slice_grid(int64_t n_items) {
   const int64_t g = n_items / 256 + 1;
   return (int)(g < EW_CAP_WIDE ? g : EW_CAP_WIDE);
+}
+
+// ---- persistent grids of the narrow-layer kernels (conv_narrow.hip, conv_bf16_narrow.hip): every workgroup slot of the
+// device, each workgroup walking tiles blockIdx.x, + grid, ... and writing ONE statistics row / weight-gradient slab.
+// DT_CUS is a constant on purpose: dt_persist_rows sizes the buffers before any launch, and the grid decides which row a
+// tile's sums land in, so both are part of the result
+#define DT_CUS 256
+#define DT_PERSIST_MAX_PER_CU 8
+// rows / slabs of a layer with `tiles` tiles: an upper bound of every variant's grid, asked before the variant is known
+static inline int dt_persist_rows(int tiles) {
+  return tiles < DT_PERSIST_MAX_PER_CU * DT_CUS ? tiles : DT_PERSIST_MAX_PER_CU * DT_CUS;
+}
+// Workgroups of an instantiation that fit one CU, from its own code object: registers (512 per lane and SIMD, granule 8,
+// one wave of the workgroup per SIMD) and LDS (160 KiB).  The kernel is latency-bound by the bytes it keeps in flight
+// (PMC round 3: waves parked 53 % of the time at 3 workgroups per CU = 33 KB in flight per CU -> 3.6 TB/s), so the
+// persistent grid takes every slot there is — and exactly those, so that all workgroups walk the same number of tiles.
+static inline int dt_occupancy(const void* kernel) {
+  hipFuncAttributes at;
+  if (hipFuncGetAttributes(&at, kernel) != hipSuccess) return 2;
+  const int regs = ((at.numRegs + 7) / 8) * 8;
+  const int by_regs = regs > 0 ? 512 / regs : DT_PERSIST_MAX_PER_CU;
+  const int by_lds = at.sharedSizeBytes > 0 ? (int)(163840 / at.sharedSizeBytes) : DT_PERSIST_MAX_PER_CU;
+  const int occ = by_regs < by_lds ? by_regs : by_lds;
+  return occ > DT_PERSIST_MAX_PER_CU ? DT_PERSIST_MAX_PER_CU : (occ < 1 ? 1 : occ);
+}
+// asked once per instantiation and process (a function-local static: thread-safe, and the cache belongs to the kernel)
+template <auto K>
+static int dt_wgs_per_cu() {
+  static const int per_cu = dt_occupancy(reinterpret_cast<const void*>(K));
+  return per_cu;
+}
+// launches K(a, total) on min(total, slots) workgroups of 256 threads -> the grid
+template <auto K, class Args>
+static int dt_persist_launch(const Args& a, int total, hipStream_t st) {
+  const int slots = dt_wgs_per_cu<K>() * DT_CUS, grid = total < slots ? total : slots;
+  hipLaunchKernelGGL(K, dim3((unsigned)grid), dim3(256), 0, st, a, total);
+  return grid;
+}
+
+// ---- the narrow layers' channel counts as compile-time block counts: f(CB, NB) with std::integral_constant arguments,
+// CB = 1 for up to 16 input channels and 2 above, NB alike for the output channels.  A launcher that has no <2, 2>
+// instantiation leaves it out with `if constexpr`
+template <class F>
+static inline int dt_narrow_blocks(int C0, int Cout, F&& f) {
+  using one = std::integral_constant<int, 1>;
+  using two = std::integral_constant<int, 2>;
+  if (C0 <= 16 && Cout <= 16) return f(one{}, one{});
+  if (C0 <= 16) return f(one{}, two{});
+  if (Cout <= 16) return f(two{}, one{});
+  return f(two{}, two{});
 }
 
 // ---- C channels in groups of `per` (4 fp32 or 8 bf16 = 16 bytes): the groups must divide the 256 threads of a workgroup

@@ -529,13 +529,13 @@ int dt_wgrad_n16_launch(const dt_conv_desc* d, const float* src0, const float* d
     DT_LAUNCH_CHECK();
     return DT_OK;
   }
-  const int cit = d->C0 > 16 ? 2 : 1, cot = d->Cout > 16 ? 2 : 1;
-  if (cit == 1 && cot == 1)
-    hipLaunchKernelGGL((conv_wgrad_n16_kernel<1, 1>), dim3(a.ksplit), dim3(256), 0, st, a);
-  else if (cit == 2 && cot == 1)
-    hipLaunchKernelGGL((conv_wgrad_n16_kernel<2, 1>), dim3(a.ksplit), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((conv_wgrad_n16_kernel<1, 2>), dim3(a.ksplit), dim3(256), 0, st, a);
+  // (output blocks named first: <1, 1>, <2, 1>, <1, 2> is the order the instantiations have in the code object)
+  dt_narrow_blocks(d->Cout, d->C0, [&](auto cot, auto cit) {
+    constexpr int CIT = decltype(cit)::value, COT = decltype(cot)::value;
+    // no 32 x 32 accumulator tile: dt_conv2d_wgrad_n16_supported leaves that shape to conv_wgrad.hip
+    if constexpr (CIT * COT < 4) hipLaunchKernelGGL((conv_wgrad_n16_kernel<CIT, COT>), dim3(a.ksplit), dim3(256), 0, st, a);
+    return DT_OK;
+  });
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
@@ -787,42 +787,7 @@ extern "C" int dt_conv2d_narrow_supported(const dt_conv_desc* d) {
 static int nl_tiles(const dt_conv_desc* d) { return d->B * dt_cdiv(d->Ho, N16_TH) * dt_cdiv(d->Wo, N16_TW); }
 
 // rows of the statistics buffer: the same for every variant of a layer shape (an upper bound of the persistent grid)
-int dt_conv2d_narrow_rows(const dt_conv_desc* d) {
-  const int t = nl_tiles(d);
-  return t < 8 * 256 ? t : 8 * 256;
-}
-
-template <class K>
-static int nl_occupancy(K kernel) {
-  hipFuncAttributes at;
-  if (hipFuncGetAttributes(&at, reinterpret_cast<const void*>(kernel)) != hipSuccess) return 2;
-  const int regs = ((at.numRegs + 7) / 8) * 8;
-  const int by_regs = regs > 0 ? 512 / regs : 8;
-  const int by_lds = at.sharedSizeBytes > 0 ? (int)(163840 / at.sharedSizeBytes) : 8;
-  int occ = by_regs < by_lds ? by_regs : by_lds;
-  return occ > 8 ? 8 : (occ < 1 ? 1 : occ);
-}
-
-template <int CB, int NB>
-static int nl_launch(const NarrowLeanArgs& a, int total, bool tf, int epi, hipStream_t st) {
-  // variants: 0 plain, 1 input transform, 2 BatchNorm-backward sums, 3 inference affine, 4 input transform + affine
-  static int occ[5] = {0, 0, 0, 0, 0};
-  const int v = epi == 1 ? 2 : (epi == 4 ? (tf ? 4 : 3) : (tf ? 1 : 0));
-#define NL_CASE(vv, TFv, EPIv)                                                                              \
-  if (v == vv) {                                                                                            \
-    if (occ[vv] == 0) occ[vv] = nl_occupancy(conv3x3_f32_narrow_kernel<CB, NB, TFv, EPIv>);                   \
-    const int grid = total < occ[vv] * 256 ? total : occ[vv] * 256;                                          \
-    hipLaunchKernelGGL((conv3x3_f32_narrow_kernel<CB, NB, TFv, EPIv>), dim3((unsigned)grid), dim3(256), 0, st, a, total); \
-    return DT_OK;                                                                                           \
-  }
-  NL_CASE(0, false, 0)
-  NL_CASE(1, true, 0)
-  NL_CASE(2, false, 1)
-  NL_CASE(3, false, 4)
-  NL_CASE(4, true, 4)
-#undef NL_CASE
-  return DT_EINVAL;
-}
+int dt_conv2d_narrow_rows(const dt_conv_desc* d) { return dt_persist_rows(nl_tiles(d)); }
 
 int dt_conv2d_narrow_launch_upc(const dt_conv_desc* d, const NarrowLeanArgs& a, int total, bool tf, int epi, hipStream_t st);
 
@@ -848,20 +813,23 @@ int dt_conv2d_narrow_launch(const dt_conv_desc* d, const float* src0, const floa
   a.tiles_x = dt_cdiv(d->Wo, N16_TW); a.tiles_y = dt_cdiv(d->Ho, N16_TH);
   a.P = dt_conv2d_narrow_rows(d);
   const int total = nl_tiles(d), epi = affine ? 4 : (bnb ? 1 : 0);
-  int rc;
   if (epi != 1 && dt_conv2d_narrow_subpixel(d)) {
     // nearest-upsampled input: the sub-pixel form (4 combined taps per output parity instead of 9); 32 -> 32 would
     // need 256 weight registers and keeps the 9-tap form
-    rc = dt_conv2d_narrow_launch_upc(d, a, total, tf, epi, st);
-    if (rc != DT_OK) return rc;
+    DT_TRY(dt_conv2d_narrow_launch_upc(d, a, total, tf, epi, st));
     DT_LAUNCH_CHECK();
     return DT_OK;
   }
-  if (d->C0 == 16 && d->Cout == 16) rc = nl_launch<1, 1>(a, total, tf, epi, st);
-  else if (d->C0 == 16) rc = nl_launch<1, 2>(a, total, tf, epi, st);
-  else if (d->Cout == 16) rc = nl_launch<2, 1>(a, total, tf, epi, st);
-  else rc = nl_launch<2, 2>(a, total, tf, epi, st);
-  if (rc != DT_OK) return rc;
+  // variants (TF, EPI): plain, input transform, BatchNorm-backward sums, inference affine, input transform + affine
+  dt_narrow_blocks(d->C0, d->Cout, [&](auto cb, auto nb) {
+    constexpr int CB = decltype(cb)::value, NB = decltype(nb)::value;
+    if (epi == 0 && !tf) dt_persist_launch<conv3x3_f32_narrow_kernel<CB, NB, false, 0>>(a, total, st);
+    else if (epi == 0) dt_persist_launch<conv3x3_f32_narrow_kernel<CB, NB, true, 0>>(a, total, st);
+    else if (epi == 1) dt_persist_launch<conv3x3_f32_narrow_kernel<CB, NB, false, 1>>(a, total, st);
+    else if (!tf) dt_persist_launch<conv3x3_f32_narrow_kernel<CB, NB, false, 4>>(a, total, st);
+    else dt_persist_launch<conv3x3_f32_narrow_kernel<CB, NB, true, 4>>(a, total, st);
+    return DT_OK;
+  });
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
@@ -1090,32 +1058,21 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f32_upc_kernel(const NarrowLea
 }
 
 // the sub-pixel form serves the up-sampled layers without fused BatchNorm-backward sums (forward / inference of dec4.conv1)
-template <int CB, int NB>
-static int nl_launch_upc(const NarrowLeanArgs& a, int total, bool tf, int epi, hipStream_t st) {
-  static int occ[4] = {0, 0, 0, 0};
-  const int v = (epi == 4 ? 2 : 0) + (tf ? 1 : 0);
-#define NLU_CASE(vv, TFv, EPIv)                                                                          \
-  if (v == vv) {                                                                                         \
-    if (occ[vv] == 0) occ[vv] = nl_occupancy(conv3x3_f32_upc_kernel<CB, NB, TFv, EPIv>);                   \
-    const int grid = total < occ[vv] * 256 ? total : occ[vv] * 256;                                       \
-    hipLaunchKernelGGL((conv3x3_f32_upc_kernel<CB, NB, TFv, EPIv>), dim3((unsigned)grid), dim3(256), 0, st, a, total); \
-    return DT_OK;                                                                                        \
-  }
-  NLU_CASE(0, false, 0)
-  NLU_CASE(1, true, 0)
-  NLU_CASE(2, false, 4)
-  NLU_CASE(3, true, 4)
-#undef NLU_CASE
-  return DT_EINVAL;
-}
-
 int dt_conv2d_narrow_launch_upc(const dt_conv_desc* d, const NarrowLeanArgs& a, int total, bool tf, int epi, hipStream_t st) {
-  if (d->C0 == 16 && d->Cout == 16) return nl_launch_upc<1, 1>(a, total, tf, epi, st);
-  if (d->C0 == 16) return nl_launch_upc<1, 2>(a, total, tf, epi, st);
-  if (d->Cout == 16) return nl_launch_upc<2, 1>(a, total, tf, epi, st);
-  // 32 -> 32 would need 256 weight registers (it spills): dt_conv2d_narrow_subpixel keeps that shape on the 9-tap kernel
-  dt_set_error("conv_narrow: no sub-pixel form for 32 -> 32 channels");
-  return DT_ENOSYS;
+  return dt_narrow_blocks(d->C0, d->Cout, [&](auto cb, auto nb) {
+    constexpr int CB = decltype(cb)::value, NB = decltype(nb)::value;
+    if constexpr (CB * NB == 4) {
+      // 32 -> 32 would need 256 weight registers (it spills): dt_conv2d_narrow_subpixel keeps that shape on the 9-tap kernel
+      dt_set_error("conv_narrow: no sub-pixel form for 32 -> 32 channels");
+      return DT_ENOSYS;
+    } else {
+      if (epi != 4 && !tf) dt_persist_launch<conv3x3_f32_upc_kernel<CB, NB, false, 0>>(a, total, st);
+      else if (epi != 4) dt_persist_launch<conv3x3_f32_upc_kernel<CB, NB, true, 0>>(a, total, st);
+      else if (!tf) dt_persist_launch<conv3x3_f32_upc_kernel<CB, NB, false, 4>>(a, total, st);
+      else dt_persist_launch<conv3x3_f32_upc_kernel<CB, NB, true, 4>>(a, total, st);
+      return DT_OK;
+    }
+  });
 }
 
 // ================================================================================================================
@@ -1313,23 +1270,7 @@ static int upcd_tiles(const dt_conv_desc* d) { return d->B * dt_cdiv(d->Hin / 2,
 
 extern "C" int dt_conv2d_upsampled_dgrad_rows(const dt_conv_desc* d) {
   if (!dt_conv2d_upsampled_dgrad_supported(d)) return 0;
-  const int t = upcd_tiles(d);
-  return t < 8 * 256 ? t : 8 * 256;
-}
-
-template <int CIB, int COB>
-static int upcd_launch(const UpcDgradArgs& a, int total, bool bnb, hipStream_t st) {
-  static int occ[2] = {0, 0};
-  if (bnb) {
-    if (occ[1] == 0) occ[1] = nl_occupancy(conv3x3_f32_upc_dgrad_kernel<CIB, COB, true>);
-    const int grid = total < occ[1] * 256 ? total : occ[1] * 256;
-    hipLaunchKernelGGL((conv3x3_f32_upc_dgrad_kernel<CIB, COB, true>), dim3((unsigned)grid), dim3(256), 0, st, a, total);
-  } else {
-    if (occ[0] == 0) occ[0] = nl_occupancy(conv3x3_f32_upc_dgrad_kernel<CIB, COB, false>);
-    const int grid = total < occ[0] * 256 ? total : occ[0] * 256;
-    hipLaunchKernelGGL((conv3x3_f32_upc_dgrad_kernel<CIB, COB, false>), dim3((unsigned)grid), dim3(256), 0, st, a, total);
-  }
-  return DT_OK;
+  return dt_persist_rows(upcd_tiles(d));
 }
 
 // gx = d loss / d x for y = conv3x3(nearest_upsample_x2(x)): replaces dt_conv2d (data-gradient form) + dt_upsample2x_bwd
@@ -1349,9 +1290,15 @@ extern "C" int dt_conv2d_upsampled_dgrad(const dt_conv_desc* d, const float* dy,
   a.P = dt_conv2d_upsampled_dgrad_rows(d);
   const int total = upcd_tiles(d);
   hipStream_t st = (hipStream_t)stream;
-  if (d->C0 == 16 && d->Cout == 16) upcd_launch<1, 1>(a, total, bnb, st);
-  else if (d->C0 == 32 && d->Cout == 16) upcd_launch<2, 1>(a, total, bnb, st);
-  else upcd_launch<1, 2>(a, total, bnb, st);
+  // (output blocks named first: <1, 1>, <2, 1>, <1, 2> is the order the instantiations have in the code object)
+  dt_narrow_blocks(d->Cout, d->C0, [&](auto cob, auto cib) {
+    constexpr int CIB = decltype(cib)::value, COB = decltype(cob)::value;
+    if constexpr (CIB * COB < 4) {   // no 32 -> 32 (it spills): ..._dgrad_supported asks for C0 * Cout <= 512
+      if (bnb) dt_persist_launch<conv3x3_f32_upc_dgrad_kernel<CIB, COB, true>>(a, total, st);
+      else dt_persist_launch<conv3x3_f32_upc_dgrad_kernel<CIB, COB, false>>(a, total, st);
+    }
+    return DT_OK;
+  });
   DT_LAUNCH_CHECK();
   return DT_OK;
 }

@@ -107,14 +107,15 @@ def test_conv_dgrad_stride2_via_zero_insert(Cin, Cout, k, p):
     assert rel_err(to_nchw(dx), x.grad) < 2e-6
 
 
-@pytest.mark.parametrize("h,w_,Cin,Cout", [(20, 24, 32, 16), (21, 19, 32, 16), (64, 64, 16, 16), (9, 40, 16, 32), (4, 16, 32, 16)])
+@pytest.mark.parametrize("h,w_,Cin,Cout", [(20, 24, 32, 16), (21, 19, 32, 16), (64, 64, 16, 16), (9, 40, 16, 32), (4, 16, 32, 16),
+                                            (125, 115, 32, 16)])   # B = 9: 2304 tiles, more than the 2048-row bound of the grid
 def test_conv_n16_with_virtual_upsample(h, w_, Cin, Cout):
     """dec.4.conv1: nearest x2 upsample (no skip) feeding the narrow-layer kernels, with BN statistics.  Round 3: the
     sub-pixel form (conv3x3_f32_upc_kernel: 4 combined taps per output parity from the low-resolution halo) — ragged
     maps, borders (the padding of the up-sampled image = out-of-range source pixels), every channel combination it takes"""
     ops = _ops()
     g = torch.Generator().manual_seed(77 + h)
-    B = 2
+    B = 9 if h > 100 else 2
     a = torch.randn((B, Cin, h, w_), generator=g)
     wt = torch.randn((Cout, Cin, 3, 3), generator=g) * 0.08
     ref = F.conv2d(F.interpolate(a, scale_factor=2, mode="nearest").double(), wt.double(), padding=1)
@@ -203,14 +204,15 @@ def test_conv_affine_epilogue_equals_conv_then_bn_act(k, s, p, Cin, Cout, h, w_,
     assert bool(torch.isnan(z).any())
 
 
-@pytest.mark.parametrize("h,w_,Cin,Cout", [(20, 24, 32, 16), (21, 19, 32, 16), (64, 64, 16, 16), (9, 40, 16, 32), (4, 16, 32, 16)])
+@pytest.mark.parametrize("h,w_,Cin,Cout", [(20, 24, 32, 16), (21, 19, 32, 16), (64, 64, 16, 16), (9, 40, 16, 32), (4, 16, 32, 16),
+                                            (125, 115, 32, 16)])   # B = 9: 2304 tiles, more than the 2048-row bound of the grid
 def test_conv_upsampled_dgrad_subpixel(h, w_, Cin, Cout):
     """dec.4.conv1 backward: autograd of conv3x3(interpolate(x, 2, nearest)) w.r.t. x in one 4x4 / stride-2 kernel
     (conv3x3_f32_upc_dgrad_kernel, 16 combined weight matrices), with the BatchNorm-backward sums of the layer that
     produced x in the epilogue — ragged maps and borders; against float64 autograd"""
     ops = _ops()
     g = torch.Generator().manual_seed(177 + h)
-    B = 2
+    B = 9 if h > 100 else 2
     yraw = torch.randn((B, Cin, h, w_), generator=g)
     sc = 1 + 0.3 * torch.randn(Cin, generator=g)
     sh = 0.2 * torch.randn(Cin, generator=g)
