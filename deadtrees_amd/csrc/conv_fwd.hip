@@ -723,6 +723,11 @@ static int conv2d_impl(const dt_conv_desc* d, const float* src0, const float* sr
   const ConvPlan p = conv_plan(d, aff_scale != nullptr, out_bf16 != nullptr);
   if (p.family == CONV_NARROW) return dt_conv2d_narrow_launch(d, src0, w, out0, stats, in_scale, in_shift, st, fuse);
   if (p.family == CONV_N16) return dt_conv2d_n16_launch(d, src0, w, out0, stats, in_scale, in_shift, st, fuse);
+  // the pipelined staging of conv_fwd_kernel loads channels in 16-byte quads guarded by their first channel only (input:
+  // cc < C, weights: n0 + 4 q < Cout): with a count that is no multiple of 4 the last quad would read up to 12 bytes past
+  // the tensor, into lanes that meet zero weights (0 x NaN) or masked stores.  The stem stages element by element.
+  DT_REQUIRE(p.family == CONV_STEM || ((d->C0 | d->C1 | d->Cout) & 3) == 0,
+             "conv: the tiled kernels need C0, C1 and Cout in multiples of 4 (%d, %d, %d)", d->C0, d->C1, d->Cout);
   ConvArgs a;
   a.bnb = fuse ? *fuse : dt_bn_bwd_fuse{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   a.src0 = src0; a.src1 = src1; a.w = w; a.out0 = out0; a.out1 = out1; a.stats = stats;

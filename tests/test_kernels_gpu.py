@@ -32,20 +32,22 @@ def rel_err(a, b):
 
 
 CONV_CASES = [
-    # B, H, W, Cin, Cout, k, stride, pad
-    (2, 32, 32, 64, 64, 3, 1, 1),
-    (1, 40, 24, 16, 16, 3, 1, 1),     # ragged tiles, narrow channels (dec.4 shape)
-    (2, 16, 16, 128, 96, 3, 1, 1),    # TW=16 path, Cout not multiple of 64
-    (3, 8, 8, 32, 48, 3, 1, 1),       # TW=8 path
-    (2, 2, 2, 64, 64, 3, 1, 1),       # tiny map (layer4 of a 64x64 tile)
-    (2, 32, 32, 64, 128, 3, 2, 1),    # layer2.0.conv1
-    (2, 12, 20, 32, 64, 3, 2, 1),
-    (2, 32, 32, 64, 128, 1, 2, 0),    # downsample
-    (2, 64, 96, 3, 64, 7, 2, 3),      # stem
-    (1, 32, 32, 4, 64, 7, 2, 3),      # stem, RGBN
-    (1, 34, 70, 512, 64, 3, 1, 1),    # many input chunks, width > 2 tiles
-    (2, 48, 80, 32, 16, 3, 1, 1),     # dec.4.conv1 shape: 16-wide MFMA kernel, two input chunks
-    (1, 24, 40, 8, 12, 3, 1, 1),      # 16-wide kernel with ragged channel counts
+    # B, H, W, Cin, Cout, k, stride, pad -> the instantiation dt_conv2d_config reports (conv_fwd_kernel<KS, STRIDE, TW, TN, CK>).
+    # Every grid here is far below the 512 workgroups of the 64-wide tiles: no case but the stems runs TN = 64
+    # (tests/test_conv_variants_gpu.py has one case per variant of the dispatch table, the 64-wide ones included)
+    (2, 32, 32, 64, 64, 3, 1, 1),     # <3,1,32,32,16>, 16 workgroups
+    (1, 40, 24, 16, 16, 3, 1, 1),     # conv_fwd_n16_kernel (8 x 32 tile, 16 channels): ragged tiles; 24 wide, so not the lean kernel
+    (2, 16, 16, 128, 96, 3, 1, 1),    # <3,1,16,32,16>: TW = 16, three full 32-channel tiles
+    (3, 8, 8, 32, 48, 3, 1, 1),       # <3,1,8,32,8>: TW = 8, 8-channel K steps, half-empty last channel tile
+    (2, 2, 2, 64, 64, 3, 1, 1),       # <3,1,8,32,16>: tiny map (layer4 of a 64x64 tile)
+    (2, 32, 32, 64, 128, 3, 2, 1),    # <3,2,16,32,8>: layer2.0.conv1
+    (2, 12, 20, 32, 64, 3, 2, 1),     # <3,2,16,32,8>, ragged 6 x 10 output
+    (2, 32, 32, 64, 128, 1, 2, 0),    # <1,2,16,32,16>: downsample
+    (2, 64, 96, 3, 64, 7, 2, 3),      # <7,2,32,64,4>: stem
+    (1, 32, 32, 4, 64, 7, 2, 3),      # <7,2,16,64,4>: stem, RGBN
+    (1, 34, 70, 512, 64, 3, 1, 1),    # <3,1,32,32,16>: 32 input chunks, width > 2 tiles, two channel tiles
+    (2, 48, 80, 32, 16, 3, 1, 1),     # dec.4.conv1 shape: conv3x3_f32_narrow_kernel<2,1> (the lean kernel, ck 1021)
+    (1, 24, 40, 8, 12, 3, 1, 1),      # conv_fwd_n16_kernel with ragged channel counts
     # round 3: the lean persistent kernel of the narrow layers (conv3x3_f32_narrow_kernel: Cin, Cout in {16, 32}, maps of
     # at least 8 x 32) — every channel combination, ragged edges, many tiles per persistent workgroup
     (2, 40, 64, 16, 16, 3, 1, 1), (2, 37, 70, 32, 16, 3, 1, 1), (3, 64, 64, 32, 32, 3, 1, 1), (2, 16, 32, 16, 32, 3, 1, 1),
@@ -293,18 +295,19 @@ def test_conv_dgrad_stride1():
 
 
 WGRAD_CASES = [
-    (2, 32, 32, 64, 64, 3, 1, 1),
-    (2, 16, 16, 128, 256, 3, 1, 1),
-    (1, 40, 24, 16, 16, 3, 1, 1),
-    (2, 32, 64, 32, 16, 3, 1, 1),
-    (2, 8, 8, 64, 32, 3, 1, 1),
-    (2, 4, 4, 32, 128, 3, 1, 1),
-    (2, 32, 32, 64, 128, 3, 2, 1),
-    (2, 32, 32, 64, 128, 1, 2, 0),
-    (2, 64, 96, 3, 64, 7, 2, 3),
-    (1, 32, 32, 4, 64, 7, 2, 3),
-    (2, 36, 72, 16, 32, 3, 1, 1),     # 16-granular weight-gradient kernel, (1,2) tile arrangement
-    (1, 20, 44, 12, 8, 3, 1, 1),
+    # -> conv_wgrad_kernel<KS, STRIDE, TW, TPX, WCI, WCO> as wg_cfg of csrc/conv_wgrad.hip arranges it, or the kernel named
+    (2, 32, 32, 64, 64, 3, 1, 1),     # <3,1,32,64,2,2>
+    (2, 16, 16, 128, 256, 3, 1, 1),   # <3,1,16,64,2,2>
+    (1, 40, 24, 16, 16, 3, 1, 1),     # conv_wgrad_n16_kernel<1,1>
+    (2, 32, 64, 32, 16, 3, 1, 1),     # conv_wgrad_n16_kernel<2,1>
+    (2, 8, 8, 64, 32, 3, 1, 1),       # <3,1,16,128,2,1>
+    (2, 4, 4, 32, 128, 3, 1, 1),      # <3,1,16,128,1,2>
+    (2, 32, 32, 64, 128, 3, 2, 1),    # <3,2,16,64,1,2>
+    (2, 32, 32, 64, 128, 1, 2, 0),    # <1,2,16,64,2,2>
+    (2, 64, 96, 3, 64, 7, 2, 3),      # conv_wgrad_stem_kernel
+    (1, 32, 32, 4, 64, 7, 2, 3),      # conv_wgrad_stem_kernel, RGBN
+    (2, 36, 72, 16, 32, 3, 1, 1),     # conv_wgrad_n16_kernel<1,2>: 16 input, 32 output channels
+    (1, 20, 44, 12, 8, 3, 1, 1),      # conv_wgrad_n16_kernel<1,1> with ragged channel counts
 ]
 
 
