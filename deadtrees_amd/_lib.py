@@ -43,6 +43,9 @@ class PoolSource(C.Structure):
 
 
 POOL_MAX_SOURCES = 8      # DT_POOL_MAX_SOURCES
+# columns of dt_raster_cut_u8's census rows (DT_CENSUS_*)
+CENSUS_COLS, CENSUS_DEAD, CENSUS_VMIN, CENSUS_VMAX, CENSUS_B0MIN, CENSUS_B0MAX, CENSUS_MID = 16, 0, 1, 2, 3, 4, 5
+CENSUS_SUM, CENSUS_SUMSQ = 6, 10
 
 
 # name -> (restype, argtypes).  Must list every symbol of include/deadtrees_hip.h
@@ -163,6 +166,7 @@ SIGNATURES = {
     "dt_weight_images_bf16_all": (C.c_int, [c_f, c_f, c_f, c_f, c_f, c_f, C.c_int, C.c_int, c_f]),
     "dt_ensemble_vote": (C.c_int, [c_f, C.c_int, I64, C.c_int, c_f, c_f, c_f, c_f]),
     "dt_zonal_counts_u8": (C.c_int, [c_f, c_f, I64, C.c_int, C.c_int, c_f, c_f, c_f]),
+    "dt_raster_cut_u8": (C.c_int, [c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, c_f, I64, c_f, c_f, c_f, c_f, c_f, c_f]),
     "dt_patch_tile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dt_label_patches_u8": (C.c_int, [c_f, C.c_int, C.c_int, C.c_int, C.c_int, c_f, c_f, c_f]),
     "dt_patch_areas": (C.c_int, [c_f, C.c_int, C.c_int, c_f, c_f]),

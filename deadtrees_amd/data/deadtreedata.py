@@ -137,13 +137,40 @@ class DeadtreesDataModule:
     shard sets of the one directory.  Each is split train / val in the main set's proportion into pools of its own
     (``extra_pools``); the train and val loaders then are ``CombinedPoolLoader``s whose batches hold ``batch_size -
     sum(batch_size_extra)`` main samples under ``"main"`` and ``batch_size_extra[i]`` samples of set i under ``"extra_i"``,
-    the shorter sets cycling, all from one kernel launch.  The test loader stays the main set alone."""
+    the shorter sets cycling, all from one kernel launch.  The test loader stays the main set alone.
+
+    ``rasters`` (instead of ``data_dir``): the ortho rasters themselves, a sequence or re-iterable of ``(key, rgbn, mask |
+    None, lu | None)`` items as ``DevicePool.from_rasters`` takes them (``data/rasters.py``).  ``setup`` sorts the raster
+    keys and splits them with ``split_shards`` — by raster, never by sub-tile, so neighbouring sub-tiles do not straddle
+    train and val — takes ``shards_for_rank`` of the train part and fills the three pools with ``from_rasters``.
+    ``raster_conf``: ``tile_size`` (default: this module's), ``source_dim`` (2048), ``select`` ("dead"), and for the
+    random set ``oversample`` (2) and ``seed`` (42).  ``batch_size_extra=[k]`` adds the random set of
+    ``raster_training_sets`` (zero masks) as the one extra pool of the train and val loaders.  ``mean`` / ``std`` (default:
+    the reference's constants) go to the loaders; ``normalise="rasters"`` computes them with ``band_stats`` over the train
+    part (``raster_conf["reference_denominator"]``, default True)."""
 
     def __init__(self, data_dir=None, pattern=None, pattern_extra=None, batch_size_extra=None,
                  train_dataloader_conf=None, val_dataloader_conf=None, test_dataloader_conf=None,
                  synthetic_batches: int = 8, tile_size: int = 256, device: Optional[str] = None,
-                 rank: int = 0, world: int = 1, seed: int = 0, max_resident_bytes: Optional[int] = None):
+                 rank: int = 0, world: int = 1, seed: int = 0, max_resident_bytes: Optional[int] = None,
+                 rasters=None, raster_conf=None, mean=None, std=None, normalise: Optional[str] = None):
         self.data_dir, self.pattern = data_dir, pattern
+        self.rasters, self.raster_conf = rasters, dict(raster_conf or {})
+        self.mean = tuple(MEAN if mean is None else mean)
+        self.std = tuple(STD if std is None else std)
+        self.normalise = normalise
+        if normalise not in (None, "rasters"):
+            raise ValueError(f"normalise {normalise!r}: None (the mean / std given) or 'rasters'")
+        if rasters is None and (normalise or raster_conf):
+            raise ValueError("normalise='rasters' and raster_conf need rasters=")
+        if rasters is not None:
+            if data_dir or pattern or pattern_extra:
+                raise ValueError("rasters= is an alternative to data_dir / pattern / pattern_extra: give one source")
+            if batch_size_extra and len(batch_size_extra) > 1:
+                raise ValueError(f"rasters= has one extra set, the random sub-tiles: batch_size_extra {list(batch_size_extra)} "
+                                 "has more than one entry")
+            if iter(rasters) is rasters:
+                raise ValueError("rasters= is read more than once: pass a sequence or a re-iterable, not an iterator")
         self.train_conf = dict(train_dataloader_conf or {})
         self.val_conf = dict(val_dataloader_conf or {})
         self.test_conf = dict(test_dataloader_conf or {})
@@ -156,7 +183,11 @@ class DeadtreesDataModule:
         self.pattern_extra = [str(p) for p in (pattern_extra or [])]
         self.batch_size_extra = [int(b) for b in (batch_size_extra or [])]
         self.data_shards_extra = []
-        if self.pattern_extra or self.batch_size_extra:
+        if rasters is not None:
+            self.layout, self.data_shards = "rasters", []
+            if self.batch_size_extra and min(self.batch_size_extra) < 1:
+                raise ValueError(f"batch_size_extra {self.batch_size_extra}: every extra set gives at least one sample")
+        elif self.pattern_extra or self.batch_size_extra:
             if isinstance(data_dir, (list, tuple)):
                 raise ValueError("Combining pattern_extra with train/val/test layout not allowed")
             if not self.batch_size_extra:
@@ -182,6 +213,8 @@ class DeadtreesDataModule:
         self.in_channels, self.classes = in_channels, classes
         if self.data_shards is None:
             return
+        if self.rasters is not None:
+            return self._setup_rasters(split_fractions)
         from .pool import DevicePool
         from .shards import shards_for_rank, split_shards
         if self.layout == "single_directory":
@@ -214,6 +247,54 @@ class DeadtreesDataModule:
             self.extra_shard_split.append(split)
             self.extra_pools.append(pools)
 
+    def _raster_part(self, keys):
+        """the items of the rasters ``keys``, in that order when ``rasters`` can be indexed, else in its own order"""
+        if hasattr(self.rasters, "__getitem__"):
+            at = {str(item[0]): i for i, item in enumerate(self.rasters)}
+            return [self.rasters[at[k]] for k in keys]
+        wanted, src = set(keys), self.rasters
+
+        class Part:
+            def __iter__(self):
+                return (item for item in src if str(item[0]) in wanted)
+        return Part()
+
+    def _setup_rasters(self, split_fractions):
+        from .rasters import OVERSAMPLE_FACTOR, band_stats, pool_from_rasters, raster_training_sets
+        from .shards import shards_for_rank, split_shards
+        keys = sorted(str(item[0]) for item in self.rasters)
+        if len(set(keys)) != len(keys):
+            raise ValueError("rasters=: the raster keys are not unique")
+        fractions = DeadtreeDatasetConfig.fractions if split_fractions is None else split_fractions
+        train, valid, test = split_shards(keys, fractions)
+        self.shard_split = {"train": shards_for_rank(train, self.rank, self.world), "val": valid, "test": test or None}
+        conf = self.raster_conf
+        select = conf.get("select", "dead")
+        kw = dict(tile_size=int(conf.get("tile_size", self.tile_size)), source_dim=int(conf.get("source_dim", 2048)),
+                  device=self.device, max_resident_bytes=self.max_resident_bytes)
+        if self.batch_size_extra and select != "dead":
+            raise ValueError("batch_size_extra with rasters= adds the random set, which is drawn beside the 'dead' set: "
+                             f"select is {select!r}")
+        self.pools, extra, censuses = {}, {}, None
+        for name, part in self.shard_split.items():
+            if not part:
+                continue
+            items = self._raster_part(part)
+            if self.batch_size_extra and name != "test":
+                sets = raster_training_sets(items, oversample=int(conf.get("oversample", OVERSAMPLE_FACTOR)),
+                                            seed=int(conf.get("seed", 42)), **kw)
+                self.pools[name], extra[name], record = sets["dead"], sets["random"], sets
+            else:
+                record = {}
+                self.pools[name] = pool_from_rasters(items, select=select, masks="keep", record=record, **kw)
+            if name == "train":
+                censuses = record["censuses"]
+        self.extra_pools, self.extra_shard_split = ([extra], [dict(self.shard_split)]) if self.batch_size_extra else ([], [])
+        if self.normalise == "rasters":
+            stats = band_stats(censuses, kw["source_dim"], kw["tile_size"],
+                               reference_denominator=bool(conf.get("reference_denominator", True)))
+            self.mean, self.std, self.band_stats = tuple(stats["mean"]), tuple(stats["std"]), stats
+
     def _loader(self, conf, seed, wrap):
         return _SyntheticLoader(self.synthetic_batches, int(conf.get("batch_size", 8)), self.tile_size,
                                 self.in_channels, self.classes, seed, wrap, self.device, True)
@@ -237,7 +318,7 @@ class DeadtreesDataModule:
         from .pool import PoolLoader
         return PoolLoader(self._device_pools(name)[0], int(conf.get("batch_size", 8)), train=train,
                           in_channels=self.in_channels, classes=self.classes, seed=self.seed, wrap=wrap, distmap=distmap,
-                          trainer=trainer)
+                          trainer=trainer, mean=self.mean, std=self.std)
 
     def _combined_loader(self, name, conf, train, trainer=None, distmap=True):
         from .pool import CombinedPoolLoader
@@ -249,7 +330,7 @@ class DeadtreesDataModule:
                              f"{self.batch_size_extra}")
         return CombinedPoolLoader(self._device_pools(name, extra=True), [main] + self.batch_size_extra, train=train,
                                   in_channels=self.in_channels, classes=self.classes, seed=self.seed, distmap=distmap,
-                                  trainer=trainer)
+                                  trainer=trainer, mean=self.mean, std=self.std)
 
     def train_dataloader(self, trainer=None, distmap: Optional[bool] = None):
         """trainer: a ``HipTrainer(graph=True)`` whose captured step the loader feeds in place (``PoolLoader``); its
@@ -258,14 +339,14 @@ class DeadtreesDataModule:
         if self.data_shards is None:
             return self._loader(self.train_conf, 1000, True)
         distmap = (trainer is None) if distmap is None else distmap
-        if self.data_shards_extra:
+        if self.batch_size_extra:
             return self._combined_loader("train", self.train_conf, True, trainer, distmap)
         return self._pool_loader("train", self.train_conf, True, True, trainer, distmap)
 
     def val_dataloader(self):
         if self.data_shards is None:
             return self._loader(self.val_conf, 2000, True)
-        if self.data_shards_extra:
+        if self.batch_size_extra:
             return self._combined_loader("val", self.val_conf, False)
         return self._pool_loader("val", self.val_conf, False, True)
 

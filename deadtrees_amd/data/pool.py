@@ -93,6 +93,28 @@ class DevicePool:
             at += n
             first = None if i == 0 else first
 
+    @classmethod
+    def from_rasters(cls, items, tile_size: int = 256, source_dim: int = 2048, select="dead", masks: str = "keep",
+                     device=None, max_resident_bytes: Optional[int] = None):
+        """A pool filled straight from ortho rasters instead of shards (``data/rasters.py`` states the contract, the
+        array arithmetic of the reference's scripts/createdataset.py).  ``items`` yields ``(key, rgbn uint8 [4,h,w], mask
+        uint8 [h,w] | None, lu uint8 [h,w] | None)`` with h, w <= ``source_dim``; a field may also be a path that PIL opens.
+        Every raster is zero-padded to ``source_dim`` and cut into ``tile_size`` sub-tiles named ``f"{key}_{i:03}"``.
+        ``select``: ``"dead"`` (sub-tiles whose rounded dead-pixel percentage is > 0), ``"valid"`` (every non-blank one)
+        or a callable ``(names, census) -> bool[n]``; blank sub-tiles (min == max over the four bands) are never taken.
+        ``masks="zero"`` writes zero masks (the reference's random set) and reports ``frac`` 0.0.
+
+        The result is an ordinary pool: the same attributes, ``stats = [{"file": name, "frac": percentage}]`` and
+        ``shards = []``.  With a HIP device every raster is one uint8 upload through pinned memory, one census launch
+        (csrc/raster_cut.hip), one read-back of n x 128 bytes, the selection on the host and one cut launch into the
+        pool's next rows.  The pool's tensors double when they are full and are trimmed to size at the end; before any
+        growth the rows then needed are checked against ``max_resident_bytes`` (default: half of the free device memory)
+        and the constructor's ``ValueError`` is raised.  Peak device memory: while a growth or the final trim copies,
+        the old and the new tensors live side by side, at most three times the final pool's ``nbytes``, plus one staged
+        raster (6 * source_dim^2 bytes).  Without a device the numpy contract fills a host pool."""
+        from .rasters import pool_from_rasters
+        return pool_from_rasters(items, tile_size, source_dim, select, masks, device, max_resident_bytes)
+
     def __len__(self):
         return self.n
 

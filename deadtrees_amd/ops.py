@@ -1127,6 +1127,58 @@ def zonal_counts(classes_u8: torch.Tensor, zones_u8: torch.Tensor = None, K: int
     return counts, err
 
 
+def raster_cut(rgbn: torch.Tensor, mask: Optional[torch.Tensor] = None, lu: Optional[torch.Tensor] = None,
+               source_dim: int = 2048, tile_size: int = 256, slot: Optional[torch.Tensor] = None, out=None, census=True):
+    """Sub-tile cut and census of one raster on the device (``dt_raster_cut_u8``, csrc/raster_cut.hip; the contract is
+    ``data.rasters.cut_raster_host``).  rgbn uint8 [4,h,w], mask / lu uint8 [h,w] or None (zeros / ones), each contiguous
+    at any storage offset.  ``slot`` int32 [n] on the device, n = (source_dim // tile_size)^2, with ``out = (images
+    [R,t,t,4], masks [R,t,t], lu [R,t,t], sums int64 [R])`` contiguous pool tensors: sub-tile i goes into row ``slot[i]``;
+    a negative entry (or one >= R) writes nothing, rows no entry names are not touched, and no two entries may name one
+    row.  ``census``: True allocates the int64 [n,16] table (columns ``_lib.CENSUS_*``), a tensor is overwritten, False /
+    None leaves it out (``slot`` is then required).  No host synchronisation.  Returns the census tensor or None."""
+    _gpu(rgbn, mask, lu, slot)
+    S, t = int(source_dim), int(tile_size)
+    if rgbn.dtype != torch.uint8 or rgbn.dim() != 3 or rgbn.shape[0] != 4:
+        raise RuntimeError(f"raster_cut: rgbn must be uint8 [4,h,w], not {rgbn.dtype} {tuple(rgbn.shape)}")
+    h, w = int(rgbn.shape[1]), int(rgbn.shape[2])
+    dev = rgbn.device
+    for name, m in (("mask", mask), ("lu", lu)):
+        if m is not None and (m.dtype != torch.uint8 or tuple(m.shape) != (h, w) or m.device != dev):
+            raise RuntimeError(f"raster_cut: {name} must be uint8 [{h},{w}] on {dev}")
+    n = (S // t) ** 2 if t > 0 else 0
+    rows = 0
+    images = masks = lu_out = sums = None
+    if slot is not None:
+        if slot.dtype != torch.int32 or tuple(slot.shape) != (n,) or slot.device != dev or not slot.is_contiguous():
+            raise RuntimeError(f"raster_cut: slot must be contiguous int32 [{n}] on {dev}")
+        if out is None or len(out) != 4:
+            raise RuntimeError("raster_cut: slot needs out = (images, masks, lu, sums)")
+        images, masks, lu_out, sums = out
+        _gpu(images, masks, lu_out, sums)
+        rows = int(images.shape[0])
+        want = ((images, torch.uint8, (rows, t, t, 4)), (masks, torch.uint8, (rows, t, t)),
+                (lu_out, torch.uint8, (rows, t, t)), (sums, torch.int64, (rows,)))
+        for x, dtype, shape in want:
+            if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
+                raise RuntimeError(f"raster_cut: out must be contiguous (images u8 [R,{t},{t},4], masks u8 [R,{t},{t}], "
+                                   f"lu u8 [R,{t},{t}], sums i64 [R]) on {dev}; got {x.dtype} {tuple(x.shape)}")
+    elif out is not None:
+        raise RuntimeError("raster_cut: out without slot")
+    if census is True:
+        census = torch.empty((n, _lib.CENSUS_COLS), dtype=torch.int64, device=dev)
+    elif census is False:
+        census = None
+    if census is not None and (census.dtype != torch.int64 or tuple(census.shape) != (n, _lib.CENSUS_COLS)
+                               or census.device != dev or not census.is_contiguous()):
+        raise RuntimeError(f"raster_cut: census must be contiguous int64 [{n},{_lib.CENSUS_COLS}] on {dev}")
+    rgbn = rgbn.contiguous()
+    mask = None if mask is None else mask.contiguous()
+    lu = None if lu is None else lu.contiguous()
+    _lib.check(_lib.load().dt_raster_cut_u8(_p(rgbn), _p(mask), _p(lu), h, w, S, t, _p(slot), rows, _p(images), _p(masks),
+                                            _p(lu_out), _p(sums), _p(census), _st()), "dt_raster_cut_u8")
+    return census
+
+
 def _patch_tile():
     th, tw = C.c_int(0), C.c_int(0)
     _lib.check(_lib.load().dt_patch_tile(C.byref(th), C.byref(tw)), "dt_patch_tile")

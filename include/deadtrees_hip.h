@@ -479,6 +479,34 @@ int dt_sieve_patches_u8(uint8_t* classes, int32_t* labels, int32_t* area_plane, 
 int dt_patch_measure(const int32_t* labels, const uint8_t* classes, int h, int w, const int32_t* dense_plane, int n,
                      uint8_t* cls, int32_t* bbox, int64_t* sum_y, int64_t* sum_x, void* stream);
 
+/* Training samples from an ortho raster (the array arithmetic of scripts/createdataset.py:53-194 and
+ * scripts/computestats.py:111-161; deadtrees_amd/data/rasters.py states the contract in numpy).  rgbn_chw uint8 [4][h][w]
+ * with 1 <= h, w <= S is the top-left corner of a zero [4][S][S] array; mask / lu uint8 [h][w] are padded the same way.
+ * mask NULL: all zeros.  lu NULL: ones everywhere, the padded area included.  The array is cut into n = (S / t)^2 sub-tiles
+ * of t x t, sub-tile i = by * (S / t) + bx at (by * t, bx * t); t % 32 == 0, S % t == 0, S <= 32768.  Source pointers may
+ * have any byte alignment.
+ * census (may be NULL) int64 [n][DT_CENSUS_COLS], overwritten, one row per sub-tile of the PADDED array: DT_CENSUS_DEAD the
+ *   non-zero mask pixels; VMIN / VMAX over the four bands; B0MIN / B0MAX of band 0; MID the image bytes not in {0, 255};
+ *   SUM + c / SUMSQ + c the sum and the sum of squares of the bytes of band c; the remaining columns are zero.
+ * slot (may be NULL: census only) int32 [n] on the device: sub-tile i is written into row slot[i] of a pool of pool_rows
+ *   rows in dt_pool_gather_batch's layout: images [.][t][t][4] interleaved, masks / lu_out [.][t][t] (all three 4-byte
+ *   aligned), sums[.] = SUM + 0 .. SUM + 3 added up.  slot[i] < 0 or >= pool_rows writes nothing for sub-tile i; rows that no
+ *   slot names are not touched; two sub-tiles must not name one row.  slot and census must not both be NULL.
+ * Two launches (the preset of census and sums[], then the pass), integers only: exact and independent of how the work is
+ * split; no floating point, no scratch memory, no synchronisation. */
+#define DT_CENSUS_COLS 16
+#define DT_CENSUS_DEAD 0
+#define DT_CENSUS_VMIN 1
+#define DT_CENSUS_VMAX 2
+#define DT_CENSUS_B0MIN 3
+#define DT_CENSUS_B0MAX 4
+#define DT_CENSUS_MID 5
+#define DT_CENSUS_SUM 6
+#define DT_CENSUS_SUMSQ 10
+int dt_raster_cut_u8(const uint8_t* rgbn_chw, const uint8_t* mask, const uint8_t* lu, int h, int w, int S, int t,
+                     const int32_t* slot, int64_t pool_rows, uint8_t* images, uint8_t* masks, uint8_t* lu_out,
+                     uint64_t* sums, int64_t* census, void* stream);
+
 /* Signed Euclidean distance maps of the boundary loss, computed on the device in place of the
  * loader's scipy pass: data/deadtreedata.py:182-185 -> loss/losses.py:159-178 one_hot2dist(resolution=[1,1]).
  * labels int64 [B,H,W] -> dist fp32 [B,K,H,W]; per class: floor(edt to the class) outside it, 1 - floor(edt to the
