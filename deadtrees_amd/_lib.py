@@ -108,15 +108,11 @@ SIGNATURES = {
                                         C.POINTER(F32), C.POINTER(F32), c_f]),
     "dt_stitch_window_count": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "dt_window_normalize_u8": (C.c_int, [c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                         C.c_int, C.POINTER(F32), C.POINTER(F32), c_f]),
-    "dt_stitch_accumulate": (C.c_int, [c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f]),
+                                         C.c_int, C.POINTER(F32), C.POINTER(F32), C.POINTER(C.c_int), C.c_int, c_f]),
+    "dt_stitch_accumulate": (C.c_int, [c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(C.c_int), C.c_int, C.c_int, c_f]),
     "dt_stitch_finalize": (C.c_int, [c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, c_f]),
     "dt_stitch_classes_u8": (C.c_int, [c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f]),
-    "dt_window_normalize_u8_views": (C.c_int, [c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                               C.c_int, C.c_int, C.POINTER(F32), C.POINTER(F32), C.POINTER(C.c_int),
-                                               C.c_int, c_f]),
-    "dt_stitch_accumulate_views": (C.c_int, [c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                             C.POINTER(C.c_int), C.c_int, C.c_int, c_f]),
     "dt_band_has_data": (C.c_int, [c_f, I64, c_f, c_f]),
     "dt_head_fwd": (C.c_int, [c_f, c_f, c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f]),
     "dt_head_bwd_rows": (C.c_int, [C.c_int, C.c_int, C.c_int]),

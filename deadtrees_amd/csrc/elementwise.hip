@@ -1009,7 +1009,8 @@ extern "C" int dt_normalize_u8(const uint8_t* src, float* dst, int64_t n_pix, in
 extern "C" int dt_split_normalize_u8(const uint8_t* raster_chw, float* dst_nhwc, int Csrc, int h, int w, int d, int nbx,
                                      int first_block, int n_blocks, int Cdst, const float* mean, const float* stdv,
                                      void* stream) {
-  return dt_window_normalize_u8(raster_chw, dst_nhwc, Csrc, h, w, d, d, nbx, first_block, n_blocks, Cdst, mean, stdv, stream);
+  return dt_window_normalize_u8(raster_chw, dst_nhwc, Csrc, h, w, d, d, nbx, first_block, n_blocks, Cdst, mean, stdv, NULL,
+                                0, stream);
 }
 
 // scripts/inference.py:60-62 `is_valid_tile`: a raster whose first band holds only 0 / 255 is skipped.  flag[0] (int32,

@@ -7,8 +7,10 @@
 // (i * s, j * s) (row-major), pixels beyond the raster are the tiler's zero byte.  o <= d/2 means d <= 2s: a raster pixel
 // lies in at most 2 windows per axis, 4 in all.  At o = 0 this is the d x d block grid of dt_split_normalize_u8.
 //
-// Test-time augmentation: the *_views entries gather T <= 8 dihedral views (views.h) of every window and average the
-// views' softmax probabilities before the blend; several models accumulate into one raster (soft vote).
+// Test-time augmentation: the gather cuts T <= 8 dihedral views (views.h) of every window and the accumulate averages the
+// views' softmax probabilities before the blend; several models accumulate into one raster (soft vote).  A plain window is
+// the identity view: the gather and the accumulate are ONE kernel body each, in two instantiations — VIEWS = false, the
+// lean form of the caller without views (and with ramp weights), and VIEWS = true, the general one.
 //
 // All kernels stream: one thread per pixel in a grid-stride loop, coalesced along x, no atomics, no LDS.
 #include "conv_host.h"
@@ -21,33 +23,63 @@ static inline int stitch_windows(int L, int d, int o) {
   const int n = (L - o + s - 1) / s;
   return n > 1 ? n : 1;
 }
-static inline bool stitch_geometry_ok(int d, int o) { return d > 0 && o >= 0 && (o & 1) == 0 && 2 * o <= d; }
+// the geometry rules of every entry point, in the one place that words them
+static inline int stitch_geometry_check(int d, int o, const char* tag) {
+  DT_REQUIRE(d > 0, "%s: bad sizes", tag);
+  DT_REQUIRE(o >= 0 && (o & 1) == 0, "%s: overlap must be even and >= 0", tag);
+  DT_REQUIRE(2 * o <= d, "%s: overlap must be <= d/2", tag);
+  return DT_OK;
+}
+// ... and the window grid of an h x w raster with the range first .. first + count - 1 inside it
+static inline int stitch_grid_check(int h, int w, int d, int o, int first, int count, const char* tag, int* ny, int* nx) {
+  DT_TRY(stitch_geometry_check(d, o, tag));
+  *ny = stitch_windows(h, d, o);
+  *nx = stitch_windows(w, d, o);
+  DT_REQUIRE((int64_t)first + count <= (int64_t)*ny * *nx, "%s: window range outside the grid", tag);
+  return DT_OK;
+}
+
+// f(std::integral_constant<int, K>) for the class count K in 1..4 (checked by the caller): the kernels take K as a
+// template argument
+template <class F>
+static inline void stitch_for_classes(int K, F&& f) {
+  switch (K) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
 
 // T <= 8 views travel by value in the kernel arguments, 4 bits each: view v = (flip, rot) sits at bits 4v .. 4v + 3 as
 // flip | rot << 2.  `views` is the host array (flip_0, rot_0, flip_1, rot_1, ...).  inverse: pack the view that undoes
 // each one instead: rot90^k is undone by rot90^(4-k); a view with a flip is its own inverse (flip . rot90^-k = rot90^k . flip).
+// views == NULL (n_views must be 0 then) is the one identity view: T = 1, packed 0.
 #define ST_MAX_VIEWS 8
-static inline int stitch_pack_views(const int* views, int T, bool inverse, const char* tag, uint32_t* packed) {
-  DT_REQUIRE(views != nullptr, "%s: null views", tag);
-  DT_REQUIRE(T >= 1 && T <= ST_MAX_VIEWS, "%s: the number of views must be in 1..8", tag);
-  uint32_t p = 0;
-  for (int v = 0; v < T; ++v) {
+static inline int stitch_pack_views(const int* views, int n_views, bool inverse, const char* tag, int* T, uint32_t* packed) {
+  *T = 1;
+  *packed = 0;
+  if (views == nullptr) {
+    DT_REQUIRE(n_views == 0, "%s: null views need n_views == 0 (the identity view)", tag);
+    return DT_OK;
+  }
+  DT_REQUIRE(n_views >= 1 && n_views <= ST_MAX_VIEWS, "%s: the number of views must be in 1..8", tag);
+  for (int v = 0; v < n_views; ++v) {
     const int flip = views[2 * v], rot = views[2 * v + 1];
     DT_REQUIRE(flip >= 0 && flip <= 2, "%s: flip of view %d must be in 0..2", tag, v);
     DT_REQUIRE(rot >= 0 && rot <= 3, "%s: rot of view %d must be in 0..3", tag, v);
     const int r = (inverse && flip == 0) ? (4 - rot) & 3 : rot;
-    p |= (uint32_t)(flip | (r << 2)) << (4 * v);
+    *packed |= (uint32_t)(flip | (r << 2)) << (4 * v);
   }
-  *packed = p;
+  *T = n_views;
   return DT_OK;
 }
 __device__ __forceinline__ int stitch_view_flip(uint32_t packed, int v) { return (int)(packed >> (4 * v)) & 3; }
 __device__ __forceinline__ int stitch_view_rot(uint32_t packed, int v) { return (int)(packed >> (4 * v + 2)) & 3; }
 
 extern "C" int dt_stitch_window_count(int L, int d, int overlap) {
-  DT_REQUIRE(L > 0 && d > 0, "stitch_window_count: bad sizes");
-  DT_REQUIRE(overlap >= 0 && (overlap & 1) == 0, "stitch_window_count: overlap must be even and >= 0");
-  DT_REQUIRE(2 * overlap <= d, "stitch_window_count: overlap must be <= d/2");
+  DT_REQUIRE(L > 0, "stitch_window_count: bad sizes");
+  DT_TRY(stitch_geometry_check(d, overlap, "stitch_window_count"));
   return stitch_windows(L, d, overlap);
 }
 
@@ -69,87 +101,55 @@ __device__ __forceinline__ void window_pixel_normalize(const uint8_t* __restrict
   }
 }
 
+// VIEWS = false: output tile k is window first + k (T and views are not read).  VIEWS = true: T views per window, output
+// tile k * T + v is view v of window first + k, [count][T][d][d][Cd].  The output pixel (y, x) of a view is the window pixel
+// aug_source_pixel names, through the arithmetic above: every view is a bit-exact permutation of the plain window (zero
+// padding beyond the raster included: it applies to the window pixel).  Stores stay coalesced; the byte loads of a
+// transposing view (rot odd) walk a raster column.
+template <bool VIEWS>
 __global__ __launch_bounds__(256) void window_normalize_u8_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst,
                                                                   int h, int w, int d, int wstride, int nwx, int first,
-                                                                  int64_t n_pix, int Cd, f32x4 mean, f32x4 stdv) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const int64_t plane = (int64_t)h * w;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pix; i += stride) {
-    const int x = (int)(i % d), y = (int)((i / d) % d), blk = first + (int)(i / ((int64_t)d * d));
-    window_pixel_normalize(src, dst + i * Cd, h, w, plane, wstride, nwx, blk, y, x, Cd, mean, stdv);
-  }
-}
-
-// The same gather for T views per window: output tile k * T + v is view v of window first + k, [count][T][d][d][Cd].  The
-// output pixel (y, x) of a view is the window pixel aug_source_pixel names, through the arithmetic above: every view is a
-// bit-exact permutation of the plain window (zero padding beyond the raster included: it applies to the window pixel).
-// Stores stay coalesced; the byte loads of a transposing view (rot odd) walk a raster column.
-__global__ __launch_bounds__(256) void window_normalize_u8_views_kernel(const uint8_t* __restrict__ src,
-                                                                        float* __restrict__ dst, int h, int w, int d,
-                                                                        int wstride, int nwx, int first, int64_t n_pix,
-                                                                        int Cd, f32x4 mean, f32x4 stdv, int T,
-                                                                        uint32_t views) {
+                                                                  int64_t n_pix, int Cd, f32x4 mean, f32x4 stdv, int T,
+                                                                  uint32_t views) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t plane = (int64_t)h * w;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pix; i += stride) {
     const int x = (int)(i % d), y = (int)((i / d) % d);
     const int64_t tile = i / ((int64_t)d * d);
-    const int v = (int)(tile % T), blk = first + (int)(tile / T);
-    int sy, sx;
-    aug_source_pixel(stitch_view_flip(views, v), stitch_view_rot(views, v), y, x, d, d, &sy, &sx);
-    window_pixel_normalize(src, dst + i * Cd, h, w, plane, wstride, nwx, blk, sy, sx, Cd, mean, stdv);
-  }
-}
-
-static inline int window_normalize_check(const void* raster_chw, const void* dst_nhwc, int Csrc, int h, int w, int d,
-                                         int stride, int nwx, int first, int count, int Cdst, const float* mean,
-                                         const float* stdv, const char* tag) {
-  DT_REQUIRE(raster_chw && dst_nhwc && mean && stdv && h > 0 && w > 0 && d > 0 && nwx > 0 && first >= 0 && count > 0 &&
-                 Cdst > 0 && Cdst <= 4 && Cdst <= Csrc,
-             "%s: bad args", tag);
-  DT_REQUIRE(stride > 0 && stride <= d, "%s: stride must be in (0, d]", tag);
-  const int o = d - stride;
-  DT_REQUIRE((o & 1) == 0, "%s: overlap d - stride must be even", tag);
-  DT_REQUIRE(2 * o <= d, "%s: overlap d - stride must be <= d/2", tag);
-  DT_REQUIRE(nwx == stitch_windows(w, d, o), "%s: nwx is not the window count of the raster width", tag);
-  DT_REQUIRE((int64_t)first + count <= (int64_t)stitch_windows(h, d, o) * nwx, "%s: window range outside the grid", tag);
-  return DT_OK;
-}
-static inline void stitch_coefficients(const float* mean, const float* stdv, int Cdst, f32x4* m, f32x4* s) {
-  *m = f32x4{0, 0, 0, 0};
-  *s = f32x4{1, 1, 1, 1};
-  for (int c = 0; c < Cdst; ++c) {
-    (*m)[c] = mean[c];
-    (*s)[c] = stdv[c];
+    if constexpr (VIEWS) {
+      const int v = (int)(tile % T), blk = first + (int)(tile / T);
+      int sy, sx;
+      aug_source_pixel(stitch_view_flip(views, v), stitch_view_rot(views, v), y, x, d, d, &sy, &sx);
+      window_pixel_normalize(src, dst + i * Cd, h, w, plane, wstride, nwx, blk, sy, sx, Cd, mean, stdv);
+    } else {
+      window_pixel_normalize(src, dst + i * Cd, h, w, plane, wstride, nwx, first + (int)tile, y, x, Cd, mean, stdv);
+    }
   }
 }
 
 extern "C" int dt_window_normalize_u8(const uint8_t* raster_chw, float* dst_nhwc, int Csrc, int h, int w, int d, int stride,
                                       int nwx, int first, int count, int Cdst, const float* mean, const float* stdv,
-                                      void* stream) {
-  DT_TRY(window_normalize_check(raster_chw, dst_nhwc, Csrc, h, w, d, stride, nwx, first, count, Cdst, mean, stdv,
-                                "window_normalize_u8"));
-  f32x4 m, s;
-  stitch_coefficients(mean, stdv, Cdst, &m, &s);
-  const int64_t n_pix = (int64_t)count * d * d;
-  hipLaunchKernelGGL(window_normalize_u8_kernel, dim3(dt_ew_grid(n_pix, ST_CAP)), dim3(256), 0, (hipStream_t)stream,
-                     raster_chw, dst_nhwc, h, w, d, stride, nwx, first, n_pix, Cdst, m, s);
-  DT_LAUNCH_CHECK();
-  return DT_OK;
-}
-
-extern "C" int dt_window_normalize_u8_views(const uint8_t* raster_chw, float* dst_nhwc, int Csrc, int h, int w, int d,
-                                            int stride, int nwx, int first, int count, int Cdst, const float* mean,
-                                            const float* stdv, const int* views, int n_views, void* stream) {
-  DT_TRY(window_normalize_check(raster_chw, dst_nhwc, Csrc, h, w, d, stride, nwx, first, count, Cdst, mean, stdv,
-                                "window_normalize_u8_views"));
+                                      const int* views, int n_views, void* stream) {
+  const char* tag = "window_normalize_u8";
+  DT_REQUIRE(raster_chw && dst_nhwc && mean && stdv && h > 0 && w > 0 && d > 0 && nwx > 0 && first >= 0 && count > 0 &&
+                 Cdst > 0 && Cdst <= 4 && Cdst <= Csrc,
+             "%s: bad args", tag);
+  DT_REQUIRE(stride > 0 && stride <= d, "%s: stride must be in (0, d]", tag);
+  DT_TRY(stitch_geometry_check(d, d - stride, tag));
+  DT_REQUIRE(nwx == stitch_windows(w, d, d - stride), "%s: nwx is not the window count of the raster width", tag);
+  int ny, nx, T;
+  DT_TRY(stitch_grid_check(h, w, d, d - stride, first, count, tag, &ny, &nx));
   uint32_t packed;
-  DT_TRY(stitch_pack_views(views, n_views, false, "window_normalize_u8_views", &packed));
-  f32x4 m, s;
-  stitch_coefficients(mean, stdv, Cdst, &m, &s);
-  const int64_t n_pix = (int64_t)count * n_views * d * d;
-  hipLaunchKernelGGL(window_normalize_u8_views_kernel, dim3(dt_ew_grid(n_pix, ST_CAP)), dim3(256), 0, (hipStream_t)stream,
-                     raster_chw, dst_nhwc, h, w, d, stride, nwx, first, n_pix, Cdst, m, s, n_views, packed);
+  DT_TRY(stitch_pack_views(views, n_views, false, tag, &T, &packed));
+  f32x4 m{0, 0, 0, 0}, s{1, 1, 1, 1};
+  for (int c = 0; c < Cdst; ++c) {
+    m[c] = mean[c];
+    s[c] = stdv[c];
+  }
+  const int64_t n_pix = (int64_t)count * T * d * d;
+  const auto kernel = views ? window_normalize_u8_kernel<true> : window_normalize_u8_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(dt_ew_grid(n_pix, ST_CAP)), dim3(256), 0, (hipStream_t)stream, raster_chw, dst_nhwc, h, w,
+                     d, stride, nwx, first, n_pix, Cdst, m, s, T, packed);
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
@@ -185,59 +185,22 @@ __device__ __forceinline__ float stitch_softmax_terms(const float* __restrict__ 
 // are skipped.  Per visited window: softmax over K (accurate expf, max subtracted), acc[k] += weight * p_k.  Every pixel's
 // sum is thus built in ONE order, one fp32 add per window, whatever the batch size and however the windows are split into
 // calls (calls in ascending window order): the accumulator is bit-identical across batchings.
-// logits fp32 NCHW [count][K][d][d]; acc fp32 planar [K][h][w], zeroed before the first call.
-template <int K>
-__global__ __launch_bounds__(256) void stitch_accumulate_kernel(const float* __restrict__ logits, float* __restrict__ acc,
-                                                                int h, int w, int d, int o, int ny, int nx, int first,
-                                                                int count, int row0, int64_t n_pix) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const int64_t plane = (int64_t)h * w, wplane = (int64_t)d * d;
-  const int s = d - o;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pix; i += stride) {
-    const int gx = (int)(i % w), gy = row0 + (int)(i / w);
-    const int iy1 = min(gy / s, ny - 1), ix1 = min(gx / s, nx - 1);
-    const int iy0 = (iy1 > 0 && gy < (iy1 - 1) * s + d) ? iy1 - 1 : iy1;
-    const int ix0 = (ix1 > 0 && gx < (ix1 - 1) * s + d) ? ix1 - 1 : ix1;
-    const int64_t pix = (int64_t)gy * w + gx;
-    float a[K];
-    bool touched = false;
-    for (int iy = iy0; iy <= iy1; ++iy) {
-      for (int ix = ix0; ix <= ix1; ++ix) {
-        const int k = iy * nx + ix - first;
-        if (k < 0 || k >= count) continue;
-        if (!touched) {
-#pragma unroll
-          for (int c = 0; c < K; ++c) a[c] = acc[c * plane + pix];
-          touched = true;
-        }
-        const int y = gy - iy * s, x = gx - ix * s;
-        float l[K];
-        const float sum = stitch_softmax_terms<K>(logits + (int64_t)k * K * wplane + (int64_t)y * d + x, wplane, l);
-        const float wgt = stitch_ramp(y, d, o) * stitch_ramp(x, d, o);
-#pragma unroll
-        for (int c = 0; c < K; ++c) a[c] += wgt * (l[c] / sum);
-      }
-    }
-    if (touched) {
-#pragma unroll
-      for (int c = 0; c < K; ++c) acc[c * plane + pix] = a[c];
-    }
-  }
-}
-
-// The same walk with T views per window: logits fp32 [count][T][K][d][d], tile k * T + v is the network's answer to view v
-// of window first + k.  Window pixel (y, x) sits in view v at aug_source_pixel of the INVERSE view (inv_views, packed by the
-// host).  Per covering window: the T softmax vectors are summed in ascending v, times 1.0f / T, then acc += weight * mean.
-// One order per pixel (windows ascending, views ascending within a window): bit-identical across batchings as above, and at
-// T = 1 with the identity view the sum is 0 + p, the factor 1.0f: the bits of stitch_accumulate_kernel.
+// acc fp32 planar [K][h][w], zeroed before the first call.
+//
+// VIEWS = false: logits fp32 NCHW [count][K][d][d], ramp weights; T, inv_views and keep are not read.
+// VIEWS = true: logits fp32 [count][T][K][d][d], tile k * T + v is the network's answer to view v of window first + k.
+// Window pixel (y, x) sits in view v at aug_source_pixel of the INVERSE view (inv_views, packed by the host).  Per covering
+// window: the T softmax vectors are summed in ascending v, times 1.0f / T, then acc += weight * mean.  One order per pixel
+// (windows ascending, views ascending within a window): bit-identical across batchings as above, and at T = 1 with the
+// identity view the sum is 0 + p, the factor 1.0f: the bits of the VIEWS = false instantiation.
 // keep = 0: ramp weights.  keep = 1: weight 1 inside the window's kept region of crop mode (stitch_classes_u8_kernel), 0
 // outside, so exactly one window contributes per pixel; a window of weight 0 is not read.
 // Lanes adjacent in raster x read a transposing view (rot odd) d floats apart.
-template <int K>
-__global__ __launch_bounds__(256) void stitch_accumulate_views_kernel(const float* __restrict__ logits,
-                                                                      float* __restrict__ acc, int h, int w, int d, int o,
-                                                                      int ny, int nx, int first, int count, int row0,
-                                                                      int64_t n_pix, int T, uint32_t inv_views, int keep) {
+template <int K, bool VIEWS>
+__global__ __launch_bounds__(256) void stitch_accumulate_kernel(const float* __restrict__ logits, float* __restrict__ acc,
+                                                                int h, int w, int d, int o, int ny, int nx, int first,
+                                                                int count, int row0, int64_t n_pix, int T,
+                                                                uint32_t inv_views, int keep) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t plane = (int64_t)h * w, wplane = (int64_t)d * d;
   const int s = d - o, half = o / 2;
@@ -256,33 +219,38 @@ __global__ __launch_bounds__(256) void stitch_accumulate_views_kernel(const floa
         if (k < 0 || k >= count) continue;
         const int y = gy - iy * s, x = gx - ix * s;
         float wgt;
-        if (keep) {
+        if (VIEWS && keep) {
           const bool in = y >= (iy > 0 ? half : 0) && y < d - (iy < ny - 1 ? half : 0) && x >= (ix > 0 ? half : 0) &&
                           x < d - (ix < nx - 1 ? half : 0);
           wgt = in ? 1.f : 0.f;
         } else {
           wgt = stitch_ramp(y, d, o) * stitch_ramp(x, d, o);
         }
-        if (wgt == 0.f) continue;
+        if (VIEWS && wgt == 0.f) continue;
         if (!touched) {
 #pragma unroll
           for (int c = 0; c < K; ++c) a[c] = acc[c * plane + pix];
           touched = true;
         }
-        float m[K];
+        float m[K], l[K];
+        if constexpr (VIEWS) {
 #pragma unroll
-        for (int c = 0; c < K; ++c) m[c] = 0.f;
-        for (int v = 0; v < T; ++v) {
-          int vy, vx;
-          aug_source_pixel(stitch_view_flip(inv_views, v), stitch_view_rot(inv_views, v), y, x, d, d, &vy, &vx);
-          float l[K];
-          const float sum =
-              stitch_softmax_terms<K>(logits + ((int64_t)k * T + v) * K * wplane + (int64_t)vy * d + vx, wplane, l);
+          for (int c = 0; c < K; ++c) m[c] = 0.f;
+          for (int v = 0; v < T; ++v) {
+            int vy, vx;
+            aug_source_pixel(stitch_view_flip(inv_views, v), stitch_view_rot(inv_views, v), y, x, d, d, &vy, &vx);
+            const float sum =
+                stitch_softmax_terms<K>(logits + ((int64_t)k * T + v) * K * wplane + (int64_t)vy * d + vx, wplane, l);
 #pragma unroll
-          for (int c = 0; c < K; ++c) m[c] += l[c] / sum;
+            for (int c = 0; c < K; ++c) m[c] += l[c] / sum;
+          }
+#pragma unroll
+          for (int c = 0; c < K; ++c) a[c] += wgt * (m[c] * inv_t);
+        } else {
+          const float sum = stitch_softmax_terms<K>(logits + (int64_t)k * K * wplane + (int64_t)y * d + x, wplane, l);
+#pragma unroll
+          for (int c = 0; c < K; ++c) a[c] += wgt * (l[c] / sum);
         }
-#pragma unroll
-        for (int c = 0; c < K; ++c) a[c] += wgt * (m[c] * inv_t);
       }
     }
     if (touched) {
@@ -292,71 +260,30 @@ __global__ __launch_bounds__(256) void stitch_accumulate_views_kernel(const floa
   }
 }
 
-// argument rules of both accumulate entries, and the raster rows [row0, row0 + n_pix / w) under the batch's window rows
-static inline int stitch_accumulate_check(const void* logits, const void* acc, int K, int h, int w, int d, int overlap,
-                                          int first, int count, const char* tag, int* ny, int* nx, int* row0,
-                                          int64_t* n_pix) {
+extern "C" int dt_stitch_accumulate(const float* logits, float* acc, int K, int h, int w, int d, int overlap, int first,
+                                    int count, const int* views, int n_views, int weight_mode, void* stream) {
+  const char* tag = "stitch_accumulate";
   DT_REQUIRE(logits && acc && h > 0 && w > 0 && d > 0 && first >= 0 && count > 0, "%s: bad args", tag);
   DT_REQUIRE(K >= 1 && K <= 4, "%s: K must be in 1..4", tag);
-  DT_REQUIRE(overlap >= 0 && (overlap & 1) == 0, "%s: overlap must be even and >= 0", tag);
-  DT_REQUIRE(2 * overlap <= d, "%s: overlap must be <= d/2", tag);
-  const int s = d - overlap;
-  *ny = stitch_windows(h, d, overlap);
-  *nx = stitch_windows(w, d, overlap);
-  DT_REQUIRE((int64_t)first + count <= (int64_t)*ny * *nx, "%s: window range outside the grid", tag);
-  *row0 = (first / *nx) * s;
-  const int64_t row1_full = (int64_t)((first + count - 1) / *nx) * s + d;
-  const int row1 = row1_full < h ? (int)row1_full : h;
-  *n_pix = (int64_t)(row1 - *row0) * w;
-  return DT_OK;
-}
-
-extern "C" int dt_stitch_accumulate(const float* logits, float* acc, int K, int h, int w, int d, int overlap, int first,
-                                    int count, void* stream) {
-  int ny, nx, row0;
-  int64_t n_pix;
-  DT_TRY(stitch_accumulate_check(logits, acc, K, h, w, d, overlap, first, count, "stitch_accumulate", &ny, &nx, &row0,
-                                 &n_pix));
-  const dim3 grid(dt_ew_grid(n_pix, ST_CAP)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define ST_ACC(KK)                                                                                                      \
-  hipLaunchKernelGGL(stitch_accumulate_kernel<KK>, grid, block, 0, st, logits, acc, h, w, d, overlap, ny, nx, first, count, \
-                     row0, n_pix)
-  switch (K) {
-    case 1: ST_ACC(1); break;
-    case 2: ST_ACC(2); break;
-    case 3: ST_ACC(3); break;
-    default: ST_ACC(4); break;
-  }
-#undef ST_ACC
-  DT_LAUNCH_CHECK();
-  return DT_OK;
-}
-
-extern "C" int dt_stitch_accumulate_views(const float* logits, float* acc, int K, int h, int w, int d, int overlap,
-                                          int first, int count, const int* views, int n_views, int weight_mode,
-                                          void* stream) {
-  int ny, nx, row0;
-  int64_t n_pix;
-  DT_TRY(stitch_accumulate_check(logits, acc, K, h, w, d, overlap, first, count, "stitch_accumulate_views", &ny, &nx, &row0,
-                                 &n_pix));
+  int ny, nx, T;
+  DT_TRY(stitch_grid_check(h, w, d, overlap, first, count, tag, &ny, &nx));
   uint32_t inv;
-  DT_TRY(stitch_pack_views(views, n_views, true, "stitch_accumulate_views", &inv));
+  DT_TRY(stitch_pack_views(views, n_views, true, tag, &T, &inv));
   DT_REQUIRE(weight_mode == DT_STITCH_WEIGHT_RAMP || weight_mode == DT_STITCH_WEIGHT_KEEP,
-             "stitch_accumulate_views: weight_mode must be DT_STITCH_WEIGHT_RAMP or DT_STITCH_WEIGHT_KEEP");
+             "%s: weight_mode must be DT_STITCH_WEIGHT_RAMP or DT_STITCH_WEIGHT_KEEP", tag);
   const int keep = weight_mode == DT_STITCH_WEIGHT_KEEP;
-  const dim3 grid(dt_ew_grid(n_pix, ST_CAP)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define ST_ACC(KK)                                                                                                       \
-  hipLaunchKernelGGL(stitch_accumulate_views_kernel<KK>, grid, block, 0, st, logits, acc, h, w, d, overlap, ny, nx, first, \
-                     count, row0, n_pix, n_views, inv, keep)
-  switch (K) {
-    case 1: ST_ACC(1); break;
-    case 2: ST_ACC(2); break;
-    case 3: ST_ACC(3); break;
-    default: ST_ACC(4); break;
-  }
-#undef ST_ACC
+  // the raster rows [row0, row1) under the batch's window rows
+  const int s = d - overlap, row0 = (first / nx) * s;
+  const int64_t row1_full = (int64_t)((first + count - 1) / nx) * s + d;
+  const int row1 = row1_full < h ? (int)row1_full : h;
+  const int64_t n_pix = (int64_t)(row1 - row0) * w;
+  const bool lean = views == nullptr && !keep;   // no views, ramp weights: nothing of the general form is needed
+  stitch_for_classes(K, [&](auto kk) {
+    constexpr int KK = decltype(kk)::value;
+    const auto kernel = lean ? stitch_accumulate_kernel<KK, false> : stitch_accumulate_kernel<KK, true>;
+    hipLaunchKernelGGL(kernel, dim3(dt_ew_grid(n_pix, ST_CAP)), dim3(256), 0, (hipStream_t)stream, logits, acc, h, w, d,
+                       overlap, ny, nx, first, count, row0, n_pix, T, inv, keep);
+  });
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
@@ -394,16 +321,10 @@ extern "C" int dt_stitch_finalize(const float* acc, uint8_t* classes, float* pro
   DT_REQUIRE(acc && classes && h > 0 && w > 0, "stitch_finalize: bad args");
   DT_REQUIRE(K >= 1 && K <= 4, "stitch_finalize: K must be in 1..4");
   const int64_t n_pix = (int64_t)h * w;
-  const dim3 grid(dt_ew_grid(n_pix, ST_CAP)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define ST_FIN(KK) hipLaunchKernelGGL(stitch_finalize_kernel<KK>, grid, block, 0, st, acc, classes, probs, n_pix)
-  switch (K) {
-    case 1: ST_FIN(1); break;
-    case 2: ST_FIN(2); break;
-    case 3: ST_FIN(3); break;
-    default: ST_FIN(4); break;
-  }
-#undef ST_FIN
+  stitch_for_classes(K, [&](auto kk) {
+    hipLaunchKernelGGL(stitch_finalize_kernel<decltype(kk)::value>, dim3(dt_ew_grid(n_pix, ST_CAP)), dim3(256), 0,
+                       (hipStream_t)stream, acc, classes, probs, n_pix);
+  });
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
@@ -432,11 +353,9 @@ __global__ __launch_bounds__(256) void stitch_classes_u8_kernel(const uint8_t* _
 extern "C" int dt_stitch_classes_u8(const uint8_t* maps, uint8_t* classes, int h, int w, int d, int overlap, int first,
                                     int count, void* stream) {
   DT_REQUIRE(maps && classes && h > 0 && w > 0 && d > 0 && first >= 0 && count > 0, "stitch_classes_u8: bad args");
-  DT_REQUIRE(overlap >= 0 && (overlap & 1) == 0, "stitch_classes_u8: overlap must be even and >= 0");
-  DT_REQUIRE(2 * overlap <= d, "stitch_classes_u8: overlap must be <= d/2");
-  const int ny = stitch_windows(h, d, overlap), nx = stitch_windows(w, d, overlap), s = d - overlap;
-  DT_REQUIRE((int64_t)first + count <= (int64_t)ny * nx, "stitch_classes_u8: window range outside the grid");
-  const int i0 = first / nx, i1 = (first + count - 1) / nx;
+  int ny, nx;
+  DT_TRY(stitch_grid_check(h, w, d, overlap, first, count, "stitch_classes_u8", &ny, &nx));
+  const int s = d - overlap, i0 = first / nx, i1 = (first + count - 1) / nx;
   const int row0 = i0 * s + (i0 > 0 ? overlap / 2 : 0);
   const int64_t row1_full = (int64_t)i1 * s + d - (i1 < ny - 1 ? overlap / 2 : 0);
   const int row1 = row1_full < h ? (int)row1_full : h;

@@ -94,7 +94,7 @@ class PyTorchInference(Inference):
         the block grid): windows ``first`` .. ``first + count - 1`` through ONE gather (``dt_window_normalize_u8``) and the
         forward -> ``want="classes"``: uint8 class maps [count,d,d] (fused argmax, for ``ops.stitch_classes``);
         ``want="logits"``: fp32 NCHW logits [count,K,d,d] (for ``ops.stitch_accumulate``).  ``views`` (T (flip, rot) pairs,
-        ``tiler.tta_views``): every window goes through the network once per view (``dt_window_normalize_u8_views``) ->
+        ``tiler.tta_views``): every window goes through the network once per view (the same gather cuts the views) ->
         logits [count,T,K,d,d], still in view orientation (``ops.stitch_accumulate(views=...)`` maps them back); a class
         map cannot be averaged, so ``want="classes"`` with views is a ``ValueError``"""
         if want not in ("classes", "logits"):

@@ -314,7 +314,7 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     ``tta`` (``tta_views``: ``"flips"``, ``"d4"`` or (flip, rot) pairs) averages every window's softmax over its views
     before the blend; an ensemble (an inference object with ``members``) votes over its models — ``vote="hard"``: the
     majority of the members' raster maps, ``vote="soft"``: all members add into one accumulator.  Both always take the
-    stitched device path, ``overlap=0`` included (``_infer_tile_multipass``); ``batch_size`` counts forward tiles.
+    stitched device path, ``overlap=0`` included (``_infer_tile_stitched``); ``batch_size`` counts forward tiles.
 
     ``stats=True`` returns ``(map, RasterStats)`` (``(map, probs, RasterStats)`` with ``return_probs``; a blank raster under
     ``skip_blank`` is still None): the class counts of the map (``deployment/stats.py``), K = ``inference.classes``.
@@ -348,31 +348,23 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
             raise ValueError("infer_tile: stats=True needs an inference object with a `classes` count")
         want_stats = (zones, int(K), Z, config)
     members = getattr(inference, "members", None)
-    if tta is not None or members is not None:
-        views = tta_views(tta)
+    if overlap or tta is not None or members is not None:
+        views = None if tta is None else tta_views(tta)
         _check_overlap(subtile, overlap)
         if world != 1:
-            raise ValueError("infer_tile: test-time augmentation and ensembles are the single-rank form (shard by raster: "
-                             "infer_rasters)")
+            raise ValueError("infer_tile: overlap stitching, test-time augmentation and ensembles are the single-rank form "
+                             "(shard by raster: infer_rasters)")
         vote = getattr(inference, "vote", "hard") if members is not None else None
         if return_probs and (blend != "average" or vote == "hard"):
             raise ValueError("infer_tile: return_probs needs blend='average' and, for an ensemble, vote='soft'")
         models = list(members) if members is not None else [inference]
         if on_device is False or not all(hasattr(m, "run_windows") for m in models):
-            raise ValueError("infer_tile: test-time augmentation and ensembles run on the device and need inference objects "
-                             "with run_windows")
-        return _infer_tile_multipass(inference, models, vote, arr_chw_u8, subtile, overlap, blend, batch_size, device,
-                                     skip_blank, return_probs, None if tta is None else views, want_stats)
-    if overlap:
-        _check_overlap(subtile, overlap)
-        if world != 1:
-            raise ValueError("infer_tile: overlap stitching is the single-rank form (shard by raster: infer_rasters)")
-        if return_probs and blend != "average":
-            raise ValueError("infer_tile: return_probs needs blend='average'")
-        if on_device is False or not hasattr(inference, "run_windows"):
-            raise ValueError("infer_tile: overlap stitching runs on the device and needs an inference object with run_windows")
-        return _infer_tile_stitched(inference, arr_chw_u8, subtile, overlap, blend, batch_size, device, skip_blank,
-                                    return_probs, want_stats)
+            raise ValueError("infer_tile: overlap stitching, test-time augmentation and ensembles run on the device and need "
+                             "inference objects with run_windows")
+        if arr_chw_u8.dtype != np.uint8:
+            raise ValueError(f"infer_tile: the stitched device path reads a uint8 raster, got {arr_chw_u8.dtype}")
+        return _infer_tile_stitched(inference, models, vote, arr_chw_u8, subtile, overlap, blend, batch_size, device,
+                                    skip_blank, return_probs, views, want_stats)
     if return_probs:
         raise ValueError("infer_tile: return_probs needs overlap > 0 and blend='average'")
     if tile_shape is None:
@@ -415,11 +407,24 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     return t.result
 
 
-def _upload_zones(want_stats, device):
-    """the zones map of a ``stats=True`` call on the device (None without one), uploaded next to the raster"""
-    if want_stats is None or want_stats[0] is None:
-        return None
-    return torch.from_numpy(np.ascontiguousarray(want_stats[0])).to(device, non_blocking=True)
+def _upload(inference, arr_chw_u8: np.ndarray, device: str, skip_blank: bool, want_stats):
+    """the start of every device path: ONE uint8 H2D copy of the band planes the network reads (the N of an RGBN raster
+    under an RGB model stays on the host), the zones map of a ``stats=True`` call uploaded next to it (None without one),
+    and ``skip_blank``'s ``is_valid_tile`` on the uploaded raster.  Returns ``(raster, zones)`` on the device, or None for
+    a raster with nothing but 0 / 255 in band 1"""
+    C = arr_chw_u8.shape[0]
+    nch = int(getattr(inference, "in_channels", C) or C)
+    if 0 < nch < C:
+        arr_chw_u8 = arr_chw_u8[:nch]
+    x = torch.from_numpy(np.ascontiguousarray(arr_chw_u8)).to(device, non_blocking=True)
+    zones_dev = None
+    if want_stats is not None and want_stats[0] is not None:
+        zones_dev = torch.from_numpy(np.ascontiguousarray(want_stats[0])).to(device, non_blocking=True)
+    if skip_blank:
+        from .. import ops
+        if int(ops.band_has_data(x[0])) == 0:
+            return None
+    return x, zones_dev
 
 
 def _download(out: torch.Tensor, probs: Optional[torch.Tensor], want_stats, zones_dev):
@@ -473,15 +478,11 @@ def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch
     if tile_shape[0] % d or tile_shape[1] % d:
         raise ValueError(f"Shapes unaligned: {tuple(tile_shape)} / {d}")
     nby, nbx = -(-h // d), -(-w // d)
-    nch = int(getattr(inference, "in_channels", C) or C)
-    if 0 < nch < C:                 # band planes the network never reads (N of an RGBN raster under an RGB model) stay on the host
-        arr_chw_u8, C = arr_chw_u8[:nch], nch
-    x = torch.from_numpy(np.ascontiguousarray(arr_chw_u8)).to(device, non_blocking=True)
-    zones_dev = _upload_zones(want_stats, device)
-    if skip_blank:
-        from .. import ops
-        if int(ops.band_has_data(x[0])) == 0:       # is_valid_tile on the uploaded raster: nothing but 0 / 255 in band 1
-            return None
+    up = _upload(inference, arr_chw_u8, device, skip_blank, want_stats)
+    if up is None:
+        return None
+    x, zones_dev = up
+    C = x.shape[0]
     if hasattr(inference, "run_blocks"):
         # round 3: split + zero padding + Normalize + NHWC in one gather per batch (dt_split_normalize_u8), no ATen passes
         outs = [inference.run_blocks(x, d, j, min(batch_size, nby * nbx - j)) for j in range(0, nby * nbx, batch_size)]
@@ -497,98 +498,52 @@ def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch
     return _download(merged[:h, :w].contiguous(), None, want_stats, zones_dev)
 
 
-def _infer_tile_stitched(inference, arr_chw_u8: np.ndarray, d: int, overlap: int, blend: str, batch_size: int, device: str,
-                         skip_blank: bool = False, return_probs: bool = False, want_stats=None):
-    """``infer_tile`` with overlapping windows: ONE uint8 H2D copy of the raster, per batch of windows one gather
-    (``dt_window_normalize_u8``) + forward + one stitch kernel into a raster-sized buffer in HBM, ONE uint8 D2H copy of the
-    map (plus the fp32 probabilities when asked for).  Batches run in ascending window order, which is what makes the
-    average-mode accumulator independent of ``batch_size``."""
+def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.ndarray, d: int, overlap: int, blend: str,
+                         batch_size: int, device: str, skip_blank: bool, return_probs: bool, views, want_stats=None):
+    """``infer_tile`` on the window grid: overlapping windows, test-time augmentation (``views``: canonical pairs, or None
+    for the plain window), an ensemble (``models``; ``vote`` None for a single model) and their combinations.  ONE uint8 H2D
+    copy of the raster; per model and batch of windows one gather (``dt_window_normalize_u8``) + forward + one stitch kernel
+    into a raster-sized buffer in HBM; ONE uint8 D2H copy of the map (plus the fp32 probabilities when asked for).  Batches
+    run in ascending window order, which is what makes the accumulator independent of ``batch_size``.
+
+    A model's own raster result: plain crop mode scatters the fused argmax (``stitch_classes``); everything else
+    accumulates probabilities (``weight="ramp"`` for ``blend="average"``, ``weight="keep"`` for crop with views) and
+    finalizes.  Hard vote: one ``ops.ensemble_vote`` over the members' raster maps.  Soft vote: ONE accumulator, members
+    outer / window batches inner, no 1/M (finalize normalises) — each pixel's terms arrive model-major, windows ascending,
+    views ascending, for every batch size."""
     from .. import ops
-    if arr_chw_u8.dtype != np.uint8:
-        raise ValueError(f"infer_tile: overlap stitching reads a uint8 raster, got {arr_chw_u8.dtype}")
-    C, h, w = arr_chw_u8.shape
-    ny, nx, _ = window_grid(h, w, d, overlap)
-    nch = int(getattr(inference, "in_channels", C) or C)
-    if 0 < nch < C:                 # band planes the network never reads stay on the host
-        arr_chw_u8, C = arr_chw_u8[:nch], nch
-    x = torch.from_numpy(np.ascontiguousarray(arr_chw_u8)).to(device, non_blocking=True)
-    zones_dev = _upload_zones(want_stats, device)
-    if skip_blank and int(ops.band_has_data(x[0])) == 0:
-        return None
-    n = ny * nx
-    if blend == "crop":
-        out = torch.empty((h, w), dtype=torch.uint8, device=x.device)      # the kept regions tile it: every byte is written
-        for j in range(0, n, batch_size):
-            ops.stitch_classes(inference.run_windows(x, d, overlap, j, min(batch_size, n - j), want="classes"), out, overlap, j)
-        return _download(out, None, want_stats, zones_dev)
-    acc = None
-    for j in range(0, n, batch_size):
-        logits = inference.run_windows(x, d, overlap, j, min(batch_size, n - j), want="logits")
-        if acc is None:
-            acc = torch.zeros((logits.shape[1], h, w), dtype=torch.float32, device=x.device)
-        ops.stitch_accumulate(logits, acc, overlap, j)
-    if return_probs:
-        classes, probs = ops.stitch_finalize(acc, want_probs=True)
-        return _download(classes, probs, want_stats, zones_dev)
-    return _download(ops.stitch_finalize(acc), None, want_stats, zones_dev)
-
-
-def _infer_tile_multipass(inference, models, vote: Optional[str], arr_chw_u8: np.ndarray, d: int, overlap: int, blend: str,
-                          batch_size: int, device: str, skip_blank: bool, return_probs: bool, views, want_stats=None):
-    """``infer_tile`` with test-time augmentation (``views``: canonical pairs, or None for the plain window) and / or an
-    ensemble (``models``; ``vote`` None for a single model).  One uint8 H2D copy of the raster; per model and batch of
-    windows one (views) gather + forward + one stitch kernel; one uint8 D2H copy of the map.
-
-    A model's own raster result follows the single-model rule — plain crop mode scatters the fused argmax
-    (``stitch_classes``); everything else accumulates probabilities (``weight="ramp"`` for ``blend="average"``,
-    ``weight="keep"`` for crop with views) and finalizes.  Hard vote: one ``ops.ensemble_vote`` over the members' raster
-    maps.  Soft vote: ONE accumulator, members outer / window batches inner, no 1/M (finalize normalises) — each pixel's
-    terms arrive model-major, windows ascending, views ascending, for every batch size."""
-    from .. import ops
-    if arr_chw_u8.dtype != np.uint8:
-        raise ValueError(f"infer_tile: the stitched device path reads a uint8 raster, got {arr_chw_u8.dtype}")
-    C, h, w = arr_chw_u8.shape
+    _, h, w = arr_chw_u8.shape
     ny, nx, _ = window_grid(h, w, d, overlap)
     n = ny * nx
-    nch = int(getattr(inference, "in_channels", C) or C)
-    if 0 < nch < C:                 # band planes the network never reads stay on the host
-        arr_chw_u8, C = arr_chw_u8[:nch], nch
-    x = torch.from_numpy(np.ascontiguousarray(arr_chw_u8)).to(device, non_blocking=True)
-    zones_dev = _upload_zones(want_stats, device)
-    if skip_blank and int(ops.band_has_data(x[0])) == 0:
+    up = _upload(inference, arr_chw_u8, device, skip_blank, want_stats)
+    if up is None:
         return None
-    T = len(views) if views is not None else 1
-    per = max(1, batch_size // T)                   # batch_size counts forward tiles
+    x, zones_dev = up
+    kw = {} if views is None else {"views": views}   # a duck-typed run_windows without TTA need not take the keyword
+    per = batch_size if views is None else max(1, batch_size // len(views))     # batch_size counts forward tiles
     weight = "ramp" if blend == "average" else "keep"
 
     def accumulate(model, acc):
         for j in range(0, n, per):
-            cnt = min(per, n - j)
-            if views is None:
-                logits = model.run_windows(x, d, overlap, j, cnt, want="logits").unsqueeze(1)   # [count,1,K,d,d]: identity
-            else:
-                logits = model.run_windows(x, d, overlap, j, cnt, want="logits", views=views)
+            logits = model.run_windows(x, d, overlap, j, min(per, n - j), want="logits", **kw)
             if acc is None:
-                acc = torch.zeros((logits.shape[2], h, w), dtype=torch.float32, device=x.device)
-            ops.stitch_accumulate(logits, acc, overlap, j, views=views or ((0, 0),), weight=weight)
+                acc = torch.zeros((logits.shape[-3], h, w), dtype=torch.float32, device=x.device)
+            ops.stitch_accumulate(logits, acc, overlap, j, views=views, weight=weight)
         return acc
 
     def class_map(model):
         if views is None and blend == "crop":
-            out = torch.empty((h, w), dtype=torch.uint8, device=x.device)
+            out = torch.empty((h, w), dtype=torch.uint8, device=x.device)      # the kept regions tile it: every byte is written
             for j in range(0, n, batch_size):
                 ops.stitch_classes(model.run_windows(x, d, overlap, j, min(batch_size, n - j), want="classes"), out, overlap, j)
             return out
         return ops.stitch_finalize(accumulate(model, None))
 
-    if vote == "hard":
-        maps = torch.stack([class_map(m) for m in models], dim=0)
-        if len(models) == 1:
-            return _download(maps[0], None, want_stats, zones_dev)
-        out, _ = ops.ensemble_vote(maps, int(inference.classes), dtype="uint8")
-        return _download(out, None, want_stats, zones_dev)
-    if vote is None and not return_probs:
-        return _download(class_map(models[0]), None, want_stats, zones_dev)
+    if vote != "soft" and not return_probs:          # one map per model (return_probs under a hard vote was refused)
+        maps = [class_map(m) for m in models]
+        if len(maps) > 1:
+            maps = [ops.ensemble_vote(torch.stack(maps, dim=0), int(inference.classes), dtype="uint8")[0]]
+        return _download(maps[0], None, want_stats, zones_dev)
     acc = None
     for m in models:
         acc = accumulate(m, acc)

@@ -857,7 +857,10 @@ def _stitch_grid(h: int, w: int, d: int, overlap: int, what: str):
 
 
 def _views_array(views):
-    """a sequence of (flip, rot) pairs -> (ctypes int array (flip_0, rot_0, ...), T); the library validates the values"""
+    """a sequence of (flip, rot) pairs -> (ctypes int array (flip_0, rot_0, ...), T); the library validates the values.
+    ``None`` (the plain window: the one identity view) -> (None, 0), the library's NULL form"""
+    if views is None:
+        return None, 0
     flat = [int(v) for pair in views for v in pair]
     if len(flat) != 2 * len(views):
         raise RuntimeError("views must be a sequence of (flip, rot) pairs")
@@ -868,8 +871,7 @@ def window_normalize_u8(raster_chw_u8, d: int, overlap: int, first: int, count: 
     """``split_normalize_u8`` with window origins ``d - overlap`` apart: band-major uint8 raster [C,h,w] on the device -> the
     fp32 NHWC windows [count,d,d,c_dst] ``first`` .. of the row-major overlap-stitch grid (``tiler.window_grid``); overlap 0
     is the block grid, bit-identical to ``split_normalize_u8``.  ``views`` (T pairs (flip, rot), ``tiler.tta_views``): T
-    tiles per window, [count*T,d,d,c_dst], tile k*T + v = rot90^rot(flip(window first + k)) bit for bit
-    (``dt_window_normalize_u8_views``)."""
+    tiles per window, [count*T,d,d,c_dst], tile k*T + v = rot90^rot(flip(window first + k)) bit for bit."""
     _gpu(raster_chw_u8)
     if raster_chw_u8.dtype != torch.uint8 or raster_chw_u8.dim() != 3:
         raise RuntimeError("window_normalize_u8: raster must be uint8 [C,h,w]")
@@ -879,16 +881,10 @@ def window_normalize_u8(raster_chw_u8, d: int, overlap: int, first: int, count: 
         raise RuntimeError(f"window_normalize_u8: windows {first}..{first + count - 1} outside the {ny} x {nx} grid")
     m = (C.c_float * c_dst)(*[float(v) for v in mean[:c_dst]])
     s = (C.c_float * c_dst)(*[float(v) for v in std[:c_dst]])
-    if views is None:
-        out = torch.empty((count, d, d, c_dst), dtype=torch.float32, device=raster_chw_u8.device)
-        _lib.check(_lib.load().dt_window_normalize_u8(_p(raster_chw_u8.contiguous()), _p(out), cs, h, w, d, d - overlap, nx,
-                                                      first, count, c_dst, m, s, _st()), "dt_window_normalize_u8")
-        return out
     arr, T = _views_array(views)
     out = torch.empty((count * max(T, 1), d, d, c_dst), dtype=torch.float32, device=raster_chw_u8.device)
-    _lib.check(_lib.load().dt_window_normalize_u8_views(_p(raster_chw_u8.contiguous()), _p(out), cs, h, w, d, d - overlap, nx,
-                                                        first, count, c_dst, m, s, arr, T, _st()),
-               "dt_window_normalize_u8_views")
+    _lib.check(_lib.load().dt_window_normalize_u8(_p(raster_chw_u8.contiguous()), _p(out), cs, h, w, d, d - overlap, nx,
+                                                  first, count, c_dst, m, s, arr, T, _st()), "dt_window_normalize_u8")
     return out
 
 
@@ -897,36 +893,28 @@ STITCH_WEIGHTS = {"ramp": 0, "keep": 1}      # DT_STITCH_WEIGHT_* of include/dea
 
 def stitch_accumulate(logits, acc, overlap: int, first: int, views=None, weight: str = "ramp"):
     """average-mode blend: fp32 NCHW logits [count,K,d,d] of the windows ``first`` .. -> ``acc`` fp32 [K,h,w] (zeroed before
-    the first call) += ramp weight * softmax, in place.  Calls in ascending window order give a bit-identical accumulator
+    the first call) += weight * softmax, in place.  Calls in ascending window order give a bit-identical accumulator
     for every split of the windows into calls.  Returns ``acc``.
 
     ``views`` (T pairs (flip, rot)): logits are [count,T,K,d,d], tile [k, v] the network's answer to view v of window
-    ``first + k``; the T softmax vectors are mapped back, averaged (view order, times 1/T) and then weighted
-    (``dt_stitch_accumulate_views``).  ``weight="keep"`` (views given): 1 inside the window's crop-mode region
-    (``tiler.window_keep``), 0 outside.  Several models may add into one ``acc``, each in ascending window order."""
+    ``first + k``; the T softmax vectors are mapped back, averaged (view order, times 1/T) and then weighted; without views
+    the window is its own identity view.  ``weight="ramp"``: the blend ramp (``tiler.blend_ramp``); ``weight="keep"``: 1
+    inside the window's crop-mode region (``tiler.window_keep``), 0 outside.  Several models may add into one ``acc``,
+    each in ascending window order."""
     _gpu(logits, acc)
-    if views is None:
-        if weight != "ramp":
-            raise RuntimeError("stitch_accumulate: weight needs views (pass views=[(0, 0)] for the plain window)")
-        if logits.dtype != torch.float32 or logits.dim() != 4 or logits.shape[2] != logits.shape[3]:
-            raise RuntimeError("stitch_accumulate: logits must be float32 [count,K,d,d]")
-        count, K, d, _ = logits.shape
-    else:
-        if weight not in STITCH_WEIGHTS:
-            raise RuntimeError(f"stitch_accumulate: weight {weight!r}: use 'ramp' or 'keep'")
-        arr, T = _views_array(views)
-        if logits.dtype != torch.float32 or logits.dim() != 5 or logits.shape[3] != logits.shape[4] or logits.shape[1] != T:
-            raise RuntimeError(f"stitch_accumulate: logits must be float32 [count,{T},K,d,d]")
-        count, _, K, d, _ = logits.shape
+    if weight not in STITCH_WEIGHTS:
+        raise RuntimeError(f"stitch_accumulate: weight {weight!r}: use 'ramp' or 'keep'")
+    arr, T = _views_array(views)
+    shape = ("count", "K", "d", "d") if views is None else ("count", T, "K", "d", "d")
+    if (logits.dtype != torch.float32 or logits.dim() != len(shape) or logits.shape[-1] != logits.shape[-2]
+            or (views is not None and logits.shape[1] != T)):
+        raise RuntimeError(f"stitch_accumulate: logits must be float32 [{','.join(map(str, shape))}]")
+    count, (K, d) = logits.shape[0], logits.shape[-3:-1]
     if acc.dtype != torch.float32 or acc.dim() != 3 or acc.shape[0] != K or not acc.is_contiguous():
         raise RuntimeError(f"stitch_accumulate: acc must be contiguous float32 [{K},h,w]")
-    if views is None:
-        _lib.check(_lib.load().dt_stitch_accumulate(_p(logits.contiguous()), _p(acc), K, acc.shape[1], acc.shape[2], d, overlap,
-                                                    first, count, _st()), "dt_stitch_accumulate")
-    else:
-        _lib.check(_lib.load().dt_stitch_accumulate_views(_p(logits.contiguous()), _p(acc), K, acc.shape[1], acc.shape[2], d,
-                                                          overlap, first, count, arr, T, STITCH_WEIGHTS[weight], _st()),
-                   "dt_stitch_accumulate_views")
+    _lib.check(_lib.load().dt_stitch_accumulate(_p(logits.contiguous()), _p(acc), K, acc.shape[1], acc.shape[2], d, overlap,
+                                                first, count, arr, T, STITCH_WEIGHTS[weight], _st()),
+               "dt_stitch_accumulate")
     return acc
 
 

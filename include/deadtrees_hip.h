@@ -220,17 +220,31 @@ int dt_split_normalize_u8(const uint8_t* raster_chw, float* dst_nhwc, int Csrc, 
  * origin at (i * s, j * s), row-major; pixels beyond the raster are the tiler's zero byte; o = 0 is the block grid of
  * dt_split_normalize_u8.  A raster pixel lies in at most 2 windows per axis.  K <= 4 classes. */
 int dt_stitch_window_count(int L, int d, int overlap);
+/* Test-time augmentation on the stitched path.  A view is (flip: 0 none, 1 horizontal, 2 vertical; rot: k of np.rot90),
+ * view = rot90^k(flip(window)) as in dt_augment_normalize_u8; windows are square, so all eight are legal.  `views` is a
+ * HOST array of n_views pairs (flip_0, rot_0, flip_1, rot_1, ...), 1 <= n_views <= 8; it is read during the call and
+ * travels to the kernel by value.  views == NULL with n_views == 0 is the plain window: the one identity view (NULL with
+ * any other n_views is an argument error). */
 /* dt_split_normalize_u8 with window origins `stride` = d - o apart (same arithmetic: bit-identical at stride == d, which is
  * how dt_split_normalize_u8 is served): windows first .. first + count - 1 of the grid that is nwx = n(w) windows wide ->
- * fp32 NHWC [count][d][d][Cdst]. */
+ * fp32 NHWC [count][d][d][Cdst] without views; with views [count][n_views][d][d][Cdst], tile k * n_views + v is view v of
+ * window first + k - a bit-exact permutation of the plain window (zero padding included). */
 int dt_window_normalize_u8(const uint8_t* raster_chw, float* dst_nhwc, int Csrc, int h, int w, int d, int stride, int nwx,
-                           int first, int count, int Cdst, const float* mean, const float* stdv, void* stream);
-/* average mode.  logits: fp32 NCHW [count][K][d][d] of the windows first .. first + count - 1; acc: fp32 planar [K][h][w],
- * zeroed before the first call.  acc[k][gy][gx] += r(y) * r(x) * softmax_k(logits) for every window of the range that
- * covers the pixel, r(t) = min(1, (t + 1) / (o + 1), (d - t) / (o + 1)).  One thread owns a pixel and adds its windows in
- * ascending index: with calls in ascending window order the accumulator is bit-identical for every split into calls. */
+                           int first, int count, int Cdst, const float* mean, const float* stdv, const int* views,
+                           int n_views, void* stream);
+/* average mode.  logits: fp32 NCHW [count][K][d][d] of the windows first .. first + count - 1 ([count][n_views][K][d][d]
+ * of the gather's tiles with views); acc: fp32 planar [K][h][w], zeroed before the first call.  For every window of the
+ * range that covers the pixel, in ascending index: the softmax of every view is read where the window pixel sits in that
+ * view, the probability vectors are summed in view order and multiplied by 1.0f / n_views (without views: the window's
+ * own softmax, the same bits as the one view (0, 0)), then acc[k][gy][gx] += weight * mean_k.  weight_mode
+ * DT_STITCH_WEIGHT_RAMP: r(y) * r(x), r(t) = min(1, (t + 1) / (o + 1), (d - t) / (o + 1)); DT_STITCH_WEIGHT_KEEP: 1 inside
+ * the window's kept region of dt_stitch_classes_u8 and 0 outside, i.e. exactly one window per pixel.  One thread owns a
+ * pixel: with calls in ascending window order the accumulator is bit-identical for every split into calls.  Several
+ * models may add into one acc (soft vote), each in ascending window order; dt_stitch_finalize normalises. */
+#define DT_STITCH_WEIGHT_RAMP 0
+#define DT_STITCH_WEIGHT_KEEP 1
 int dt_stitch_accumulate(const float* logits, float* acc, int K, int h, int w, int d, int overlap, int first, int count,
-                         void* stream);
+                         const int* views, int n_views, int weight_mode, void* stream);
 /* classes uint8 [h][w] = argmax_k acc (ties -> lowest k, the head kernel's rule); probs (may be NULL): fp32 [K][h][w] =
  * acc_k / sum_k acc. */
 int dt_stitch_finalize(const float* acc, uint8_t* classes, float* probs, int K, int h, int w, void* stream);
@@ -239,25 +253,6 @@ int dt_stitch_finalize(const float* acc, uint8_t* classes, float* probs, int K, 
  * raster — and writes them into classes uint8 [h][w]. */
 int dt_stitch_classes_u8(const uint8_t* maps, uint8_t* classes, int h, int w, int d, int overlap, int first, int count,
                          void* stream);
-/* Test-time augmentation on the stitched path.  A view is (flip: 0 none, 1 horizontal, 2 vertical; rot: k of np.rot90),
- * view = rot90^k(flip(window)) as in dt_augment_normalize_u8; windows are square, so all eight are legal.  `views` is a
- * HOST array of n_views <= 8 pairs (flip_0, rot_0, flip_1, rot_1, ...); it is read during the call and travels to the
- * kernel by value.
- * dt_window_normalize_u8 for n_views views per window: fp32 NHWC [count][n_views][d][d][Cdst], tile k * n_views + v is
- * view v of window first + k — a bit-exact permutation of the plain window (zero padding included). */
-int dt_window_normalize_u8_views(const uint8_t* raster_chw, float* dst_nhwc, int Csrc, int h, int w, int d, int stride,
-                                 int nwx, int first, int count, int Cdst, const float* mean, const float* stdv,
-                                 const int* views, int n_views, void* stream);
-/* dt_stitch_accumulate for logits fp32 [count][n_views][K][d][d] of those tiles: per covering window (ascending index) the
- * softmax of every view is read where the window pixel sits in that view, the n_views probability vectors are summed in
- * view order and multiplied by 1.0f / n_views, then acc_k += weight * mean_k.  weight_mode DT_STITCH_WEIGHT_RAMP: the
- * r(y) * r(x) of dt_stitch_accumulate (one view (0, 0): bit-identical to it); DT_STITCH_WEIGHT_KEEP: 1 inside the
- * window's kept region of dt_stitch_classes_u8 and 0 outside, i.e. exactly one window per pixel.  Several models may add
- * into one acc (soft vote), each in ascending window order; dt_stitch_finalize normalises. */
-#define DT_STITCH_WEIGHT_RAMP 0
-#define DT_STITCH_WEIGHT_KEEP 1
-int dt_stitch_accumulate_views(const float* logits, float* acc, int K, int h, int w, int d, int overlap, int first,
-                               int count, const int* views, int n_views, int weight_mode, void* stream);
 
 /* scripts/inference.py:60-62 is_valid_tile: flag[0] (int32, zero it first) = 1 iff some byte of band[n] is neither 0 nor
  * 255 (a raster whose first band is all 0 / 255 is skipped by the reference's driver). */

@@ -7,9 +7,11 @@ synchronise, median of ``--runs`` timed runs of ``--reps`` calls each) and windo
                                                           # that predates them (``--root`` = that tree) — the baseline
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python scripts/bench_overlap.py --runs 1 --reps 2
     python scripts/bench_overlap.py --kernel-stats OUT/.../*_kernel_stats.csv     # the gather + stitch kernels' rows
+    python scripts/bench_overlap.py --digest [--root TREE]                         # sha256 of every setting's result
 """
 import argparse
 import csv
+import hashlib
 import json
 import os
 import statistics
@@ -43,6 +45,9 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--tag", default="")
     ap.add_argument("--kernel-stats", default=None)
+    ap.add_argument("--digest", action="store_true",
+                    help="print a sha256 of each setting's downloaded map (and probabilities, average mode) instead of timing: "
+                         "two trees compute the same raster when the digests agree")
     a = ap.parse_args()
     if a.kernel_stats:
         return kernel_stats(a.kernel_stats)
@@ -89,6 +94,14 @@ def main():
         def call():
             return tiler.infer_tile(Inf(), ortho, subtile=d, batch_size=a.batch, device="cuda:0", **kw)
 
+        if a.digest:
+            want_probs = dict(return_probs=True) if overlap and blend == "average" else {}     # overlap 0 is the block path
+            res = tiler.infer_tile(Inf(), ortho, subtile=d, batch_size=a.batch, device="cuda:0", **kw, **want_probs)
+            parts = res if isinstance(res, tuple) else (res,)
+            print(json.dumps({"tag": a.tag, "setting": setting, "arrays": [[str(p.dtype), list(p.shape)] for p in parts],
+                              "sha256": hashlib.sha256(b"".join(np.ascontiguousarray(p).tobytes() for p in parts)).hexdigest()}),
+                  flush=True)
+            continue
         for _ in range(3):
             out = call()
         times = []

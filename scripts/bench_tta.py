@@ -6,8 +6,10 @@ batch in isolation (hipEvents, median of ``--kernel-iters`` launches) next to th
 
     python scripts/bench_tta.py                      # every configuration, one JSON line each
     python scripts/bench_tta.py --only kernels       # the isolated kernel timings alone (--only rasters: the others)
+    python scripts/bench_tta.py --digest [--root TREE]   # sha256 of every raster configuration's map and probabilities
 """
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -26,9 +28,14 @@ def main():
     ap.add_argument("--kernel-iters", type=int, default=20)
     ap.add_argument("--only", choices=("all", "rasters", "kernels"), default="all")
     ap.add_argument("--tag", default="")
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                    help="tree to import deadtrees_amd from (default: this one)")
+    ap.add_argument("--digest", action="store_true",
+                    help="print a sha256 of each raster configuration's downloaded map and probabilities instead of timing: "
+                         "two trees compute the same raster when the digests agree")
     a = ap.parse_args()
 
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    sys.path.insert(0, a.root)
     import numpy as np
     import torch
     from deadtrees_amd import ops
@@ -77,6 +84,14 @@ def main():
                     return tiler.infer_tile(inference, ortho, subtile=d, batch_size=a.batch, device="cuda:0", overlap=o,
                                             blend="average", tta=tta)
 
+                if a.digest:
+                    parts = tiler.infer_tile(inference, ortho, subtile=d, batch_size=a.batch, device="cuda:0", overlap=o,
+                                             blend="average", tta=tta, return_probs=True)
+                    print(json.dumps({"tag": a.tag, "what": "digest", "models": M, "tta": tta or "none",
+                                      "arrays": [[str(p.dtype), list(p.shape)] for p in parts],
+                                      "sha256": hashlib.sha256(b"".join(np.ascontiguousarray(p).tobytes()
+                                                                        for p in parts)).hexdigest()}), flush=True)
+                    continue
                 for _ in range(2):
                     out = call()
                 times = []
@@ -94,7 +109,7 @@ def main():
                                   "forward_tiles_per_s": round(n_win * T * M / ms * 1e3, 1),
                                   "class1_share": round(float(out.mean()), 4)}), flush=True)
 
-    if a.only in ("all", "kernels"):
+    if a.only in ("all", "kernels") and not a.digest:
         raster = torch.from_numpy(ortho[:3].copy()).to(dev)
         m = models[0]
 

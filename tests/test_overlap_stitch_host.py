@@ -147,28 +147,56 @@ def test_host_side_validation_without_gpu():
     assert lib.dt_stitch_window_count(300, 128, 66) == EINVAL and b"d/2" in err()
     assert lib.dt_stitch_window_count(0, 128, 32) == EINVAL
     # gather: stride = d - o
-    assert lib.dt_window_normalize_u8(p, p, 4, 300, 470, 128, 97, 5, 0, 1, 3, mean, mean, None) == EINVAL and b"even" in err()
-    assert lib.dt_window_normalize_u8(p, p, 4, 300, 470, 128, 62, 7, 0, 1, 3, mean, mean, None) == EINVAL and b"d/2" in err()
-    assert lib.dt_window_normalize_u8(p, p, 4, 300, 470, 128, 129, 4, 0, 1, 3, mean, mean, None) == EINVAL
-    assert lib.dt_window_normalize_u8(p, p, 4, 300, 470, 128, 96, 4, 0, 1, 3, mean, mean, None) == EINVAL and b"nwx" in err()
+    assert lib.dt_window_normalize_u8(p, p, 4, 300, 470, 128, 97, 5, 0, 1, 3, mean, mean, None, 0, None) == EINVAL and b"even" in err()
+    assert lib.dt_window_normalize_u8(p, p, 4, 300, 470, 128, 62, 7, 0, 1, 3, mean, mean, None, 0, None) == EINVAL and b"d/2" in err()
+    assert lib.dt_window_normalize_u8(p, p, 4, 300, 470, 128, 129, 4, 0, 1, 3, mean, mean, None, 0, None) == EINVAL
+    assert lib.dt_window_normalize_u8(p, p, 4, 300, 470, 128, 96, 4, 0, 1, 3, mean, mean, None, 0, None) == EINVAL and b"nwx" in err()
     ny, nx, s = window_grid(300, 470, 128, 32)
-    assert lib.dt_window_normalize_u8(p, p, 4, 300, 470, 128, s, nx, 1, ny * nx, 3, mean, mean, None) == EINVAL
+    assert lib.dt_window_normalize_u8(p, p, 4, 300, 470, 128, s, nx, 1, ny * nx, 3, mean, mean, None, 0, None) == EINVAL
     assert b"outside the grid" in err()
-    assert lib.dt_window_normalize_u8(None, p, 4, 300, 470, 128, s, nx, 0, 1, 3, mean, mean, None) == EINVAL
+    assert lib.dt_window_normalize_u8(None, p, 4, 300, 470, 128, s, nx, 0, 1, 3, mean, mean, None, 0, None) == EINVAL
     assert lib.dt_split_normalize_u8(p, p, 4, 300, 470, 128, 4, 0, 13, 3, mean, mean, None) == EINVAL   # 3 x 4 blocks
     # accumulate / finalize / crop scatter
-    assert lib.dt_stitch_accumulate(p, p, 2, 300, 470, 128, 33, 0, 1, None) == EINVAL and b"even" in err()
-    assert lib.dt_stitch_accumulate(p, p, 2, 300, 470, 128, 66, 0, 1, None) == EINVAL and b"d/2" in err()
-    assert lib.dt_stitch_accumulate(p, p, 5, 300, 470, 128, 32, 0, 1, None) == EINVAL and b"K" in err()
-    assert lib.dt_stitch_accumulate(p, p, 2, 300, 470, 128, 32, ny * nx - 1, 2, None) == EINVAL
+    assert lib.dt_stitch_accumulate(p, p, 2, 300, 470, 128, 33, 0, 1, None, 0, 0, None) == EINVAL and b"even" in err()
+    assert lib.dt_stitch_accumulate(p, p, 2, 300, 470, 128, 66, 0, 1, None, 0, 0, None) == EINVAL and b"d/2" in err()
+    assert lib.dt_stitch_accumulate(p, p, 5, 300, 470, 128, 32, 0, 1, None, 0, 0, None) == EINVAL and b"K" in err()
+    assert lib.dt_stitch_accumulate(p, p, 2, 300, 470, 128, 32, ny * nx - 1, 2, None, 0, 0, None) == EINVAL
     assert b"outside the grid" in err()
-    assert lib.dt_stitch_accumulate(p, None, 2, 300, 470, 128, 32, 0, 1, None) == EINVAL
+    assert lib.dt_stitch_accumulate(p, None, 2, 300, 470, 128, 32, 0, 1, None, 0, 0, None) == EINVAL
     assert lib.dt_stitch_finalize(p, p, None, 5, 300, 470, None) == EINVAL and b"K" in err()
     assert lib.dt_stitch_finalize(p, None, None, 2, 300, 470, None) == EINVAL
     assert lib.dt_stitch_classes_u8(p, p, 300, 470, 128, 33, 0, 1, None) == EINVAL and b"even" in err()
     assert lib.dt_stitch_classes_u8(p, p, 300, 470, 128, 66, 0, 1, None) == EINVAL and b"d/2" in err()
     assert lib.dt_stitch_classes_u8(p, p, 300, 470, 128, 32, 0, ny * nx + 1, None) == EINVAL
     assert b"outside the grid" in err()
+
+
+def test_host_side_validation_of_the_merged_entries_without_gpu():
+    """the gather and the accumulate take the views themselves: NULL views are the identity view and need n_views == 0, a
+    view list needs 1..8 pairs, the weight mode is one of the two constants — all refused by the argument checks, before
+    any launch"""
+    from deadtrees_amd import _lib
+    lib = _lib.load()
+    EINVAL = -22
+    p = ctypes.c_void_p(4096)
+    mean = (ctypes.c_float * 3)(0.5, 0.5, 0.5)
+    ny, nx, s = window_grid(300, 470, 128, 32)
+    ident = (ctypes.c_int * 18)()                      # up to nine identity views
+
+    def gather(views, n_views):
+        return lib.dt_window_normalize_u8(p, p, 4, 300, 470, 128, s, nx, 0, 1, 3, mean, mean, views, n_views, None)
+
+    def accumulate(views, n_views, mode=0):
+        return lib.dt_stitch_accumulate(p, p, 2, 300, 470, 128, 32, 0, 1, views, n_views, mode, None)
+
+    for call in (gather, accumulate):
+        for n_views in (1, 8, -1):
+            assert call(None, n_views) == EINVAL and b"n_views == 0" in lib.dt_last_error(), n_views
+        for n_views in (0, 9, -1):
+            assert call(ident, n_views) == EINVAL and b"1..8" in lib.dt_last_error(), n_views
+    for views, n_views in ((None, 0), (ident, 1)):
+        for mode in (2, -1):
+            assert accumulate(views, n_views, mode) == EINVAL and b"weight_mode" in lib.dt_last_error(), (n_views, mode)
 
 
 def test_infer_tile_rejects_bad_overlap_requests_before_touching_a_device():

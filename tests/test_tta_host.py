@@ -96,10 +96,10 @@ def test_host_side_validation_of_the_views_entries_without_gpu():
         return (ctypes.c_int * max(1, len(flat)))(*flat), len(pairs)
 
     def gather(arr, T, stride=s, nwx=nx, first=0, count=1):
-        return lib.dt_window_normalize_u8_views(p, p, 4, 300, 470, 128, stride, nwx, first, count, 3, mean, mean, arr, T, None)
+        return lib.dt_window_normalize_u8(p, p, 4, 300, 470, 128, stride, nwx, first, count, 3, mean, mean, arr, T, None)
 
     def accumulate(arr, T, mode=0, overlap=32, K=2, first=0, count=1):
-        return lib.dt_stitch_accumulate_views(p, p, K, 300, 470, 128, overlap, first, count, arr, T, mode, None)
+        return lib.dt_stitch_accumulate(p, p, K, 300, 470, 128, overlap, first, count, arr, T, mode, None)
 
     for call in (gather, accumulate):
         assert call(*views()) == EINVAL and b"1..8" in lib.dt_last_error()

@@ -235,7 +235,18 @@ def test_degenerate_forms_are_todays_results_bit_for_bit(h, w, d, o, K):
     want = ops.stitch_classes(clean.argmax(dim=1).to(torch.uint8), torch.empty((h, w), dtype=torch.uint8, device=DEV), o, 0)
     got = ops.stitch_finalize(_accumulate([clean.unsqueeze(1)], h, w, o, 4, views=((0, 0),), weight="keep"))
     assert torch.equal(got, want)
-    if o == 0:                                                                     # block grid: both weights are 1
+    # keep without views: plain [n, K, d, d] logits are the identity-view form bit for bit, split into calls of 3 and in one
+    # call, and finalize to the same crop-mode scatter
+    for batch in (3, n):
+        plain = torch.zeros((K, h, w), dtype=torch.float32, device=DEV)
+        for j in range(0, n, batch):
+            ops.stitch_accumulate(one[j:j + batch, 0], plain, o, j, views=None, weight="keep")
+        assert torch.equal(plain, _accumulate([one], h, w, o, batch, views=((0, 0),), weight="keep")), batch
+    plain = torch.zeros((K, h, w), dtype=torch.float32, device=DEV)
+    for j in range(0, n, 4):
+        ops.stitch_accumulate(clean[j:j + 4], plain, o, j, views=None, weight="keep")
+    assert torch.equal(ops.stitch_finalize(plain), want)
+    if o == 0:                                                                    # block grid: both weights are 1
         assert torch.equal(_accumulate([lg], h, w, o, 4, weight="ramp"), _accumulate([lg], h, w, o, 4, weight="keep"))
     with pytest.raises(RuntimeError):
         ops.stitch_accumulate(lg, old, o, 0, views=D4, weight="max")
