@@ -22,7 +22,7 @@
 
 // ------------------------------------------------------------------ head forward
 
-// 4 consecutive channels of pixel `pix_elem_off` from an fp32 or bf16 NHWC tensor
+// 4 consecutive channels at element offset `elem_off` (a pixel's first channel + 4 q) of an fp32 or bf16 NHWC tensor
 template <bool XB>
 __device__ __forceinline__ f32x4 head_load4(const void* x, size_t elem_off) {
   if constexpr (XB) {
@@ -95,6 +95,102 @@ __device__ __forceinline__ int head_argmax(const float (&z)[K]) {
   return best;
 }
 
+// ---- downstream of the logits: ONE definition of every step the loss kernels and head_eval_kernel share
+// Channel softmax: max, expf(z - max), sum in class order, times 1 / sum.  `p` may be `z` itself.
+template <int K>
+__device__ __forceinline__ void loss_softmax(const float (&z)[K], float (&p)[K]) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < K; ++k) m = fmaxf(m, z[k]);
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    p[k] = expf(z[k] - m);
+    sum += p[k];
+  }
+  const float inv = 1.f / sum;
+#pragma unroll
+  for (int k = 0; k < K; ++k) p[k] = p[k] * inv;
+}
+
+// GWDICE applies softmax to the PROBABILITIES once more (gwdl.py:104 on segmodel.py:176's y_hat): q[k] = expf(p[k])
+// UN-normalised and the return value 1 / sum.  Where the caller multiplies that in is part of its rounding — the three
+// callers differ and say so.  `q` may be `p` itself.
+template <int K>
+__device__ __forceinline__ float gwdice_exps(const float (&p)[K], float (&q)[K]) {
+  float qs = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    q[k] = expf(p[k]);
+    qs += q[k];
+  }
+  return 1.f / qs;
+}
+
+// THE definition of the per-pixel sums 0-7 of DT_LOSS_NACC (N = DT_LOSS_NACC in seg_loss_fwd_kernel, 8 in
+// head_eval_kernel, whose slots 0, 6, 7 must EQUAL the unfused chain's).  Pixel p of image b in the [B][K][HW] tensors
+// `dist` and `probs`; either may be null.
+template <int K, int N>
+__device__ __forceinline__ void loss_pixel_sums(float (&acc)[K][N], const float (&pr)[K], int64_t lab, float gamma,
+                                                const float* __restrict__ dist, float* __restrict__ probs, size_t b,
+                                                size_t HW, size_t p) {
+  static_assert(N >= 8, "slots 0-7");
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const float pk = pr[k];
+    if (probs) probs[(b * K + k) * HW + p] = pk;
+    const float tk = (lab == k) ? 1.f : 0.f;
+    const float lp = logf(pk + 1e-10f);
+    const float om = 1.f - pk;
+    const float wgt = (gamma == 2.f) ? om * om : (gamma == 0.f ? 1.f : powf(om, gamma));
+    const float hard = pk > 0.5f ? 1.f : 0.f;
+    acc[k][0] += tk;
+    acc[k][1] += pk * tk;
+    acc[k][2] += pk;
+    acc[k][3] += wgt * tk * lp;
+    acc[k][4] += tk * lp;
+    if (dist) acc[k][5] += pk * dist[(b * K + k) * HW + p];
+    acc[k][6] += tk * hard;
+    acc[k][7] += hard;
+  }
+}
+
+// A workgroup's sums -> its fp64 partial row [K][DT_LOSS_NACC]: wave64 shuffle per slot, LDS, the four waves added in a
+// fixed order.  Slots j >= N are written as zero.  Has one __syncthreads(): every thread of the workgroup calls it.
+template <int K, int N>
+__device__ __forceinline__ void loss_store_partial_row(const float (&acc)[K][N], double* __restrict__ part_row, int t) {
+  static_assert(N <= DT_LOSS_NACC, "a row has DT_LOSS_NACC slots per class");
+  __shared__ double sh[4][K * N];
+  const int lane = t & 63, wave = t >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const double v = wave_sum_d((double)acc[k][j]);
+      if (lane == 0) sh[wave][k * N + j] = v;
+    }
+  __syncthreads();
+  if (t < K * DT_LOSS_NACC) {
+    const int k = t / DT_LOSS_NACC, j = t % DT_LOSS_NACC;
+    const int i = k * N + j;
+    part_row[t] = j < N ? (sh[0][i] + sh[1][i]) + (sh[2][i] + sh[3][i]) : 0.0;
+  }
+}
+
+// ---- the class count as a compile-time constant: f(std::integral_constant<int, K>) for K = KMIN .. HEAD_MAXK (the
+// callers' DT_REQUIRE checked the range).  KMIN = 2 where a kernel has no single-class instantiation
+template <int KMIN, class F>
+static inline void head_classes(int K, F&& f) {
+  switch (K) {
+    case 1:
+      if constexpr (KMIN <= 1) f(std::integral_constant<int, 1>{});
+      break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, HEAD_MAXK>{}); break;
+  }
+}
+
 template <int K, bool XB = false>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const void* __restrict__ x, const float* __restrict__ w,
                                                        const float* __restrict__ bias, float* __restrict__ logits,
@@ -134,12 +230,9 @@ static int head_fwd_launch(const void* x, const float* w, const float* bias, flo
   DT_REQUIRE(K >= 1 && K <= HEAD_MAXK, "head_fwd: K=%d unsupported (1..%d)", K, HEAD_MAXK);
   const int grid = B * dt_cdiv(H, HEAD_TH) * dt_cdiv(W, HEAD_TW);
   hipStream_t st = (hipStream_t)stream;
-  switch (K) {
-    case 1: hipLaunchKernelGGL((head_fwd_kernel<1, XB>), dim3(grid), dim3(256), 0, st, x, w, bias, logits, am64, am8, B, H, W); break;
-    case 2: hipLaunchKernelGGL((head_fwd_kernel<2, XB>), dim3(grid), dim3(256), 0, st, x, w, bias, logits, am64, am8, B, H, W); break;
-    case 3: hipLaunchKernelGGL((head_fwd_kernel<3, XB>), dim3(grid), dim3(256), 0, st, x, w, bias, logits, am64, am8, B, H, W); break;
-    default: hipLaunchKernelGGL((head_fwd_kernel<4, XB>), dim3(grid), dim3(256), 0, st, x, w, bias, logits, am64, am8, B, H, W); break;
-  }
+  head_classes<1>(K, [&](auto kc) {
+    hipLaunchKernelGGL((head_fwd_kernel<decltype(kc)::value, XB>), dim3(grid), dim3(256), 0, st, x, w, bias, logits, am64, am8, B, H, W);
+  });
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
@@ -379,12 +472,9 @@ static int head_bwd_launch(const void* x, const float* w, const float* dl, void*
   DT_REQUIRE(Cin == HEAD_CIN && K >= 1 && K <= HEAD_MAXK, "head_bwd: unsupported Cin/K");
   const int total = head_bwd_tiles(B, H, W), grid = dt_head_bwd_rows(B, H, W);
   hipStream_t st = (hipStream_t)stream;
-  switch (K) {
-    case 1: hipLaunchKernelGGL((head_bwd_kernel<1, XB>), dim3(grid), dim3(256), 0, st, x, w, dl, dx, red, B, H, W, total); break;
-    case 2: hipLaunchKernelGGL((head_bwd_kernel<2, XB>), dim3(grid), dim3(256), 0, st, x, w, dl, dx, red, B, H, W, total); break;
-    case 3: hipLaunchKernelGGL((head_bwd_kernel<3, XB>), dim3(grid), dim3(256), 0, st, x, w, dl, dx, red, B, H, W, total); break;
-    default: hipLaunchKernelGGL((head_bwd_kernel<4, XB>), dim3(grid), dim3(256), 0, st, x, w, dl, dx, red, B, H, W, total); break;
-  }
+  head_classes<1>(K, [&](auto kc) {
+    hipLaunchKernelGGL((head_bwd_kernel<decltype(kc)::value, XB>), dim3(grid), dim3(256), 0, st, x, w, dl, dx, red, B, H, W, total);
+  });
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
@@ -476,31 +566,16 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float* __restri
     for (int l = 0; l < K; ++l) Mw[k][l] = wassM ? wassM[k * K + l] : 0.f;
   for (int64_t p = p0 + threadIdx.x; p < p1; p += 256) {
     float z[K], pr[K];
-    float m = -INFINITY;
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-      z[k] = lg[(size_t)k * HW + p];
-      m = fmaxf(m, z[k]);
-    }
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      pr[k] = expf(z[k] - m);
-      sum += pr[k];
-    }
-    const float inv = 1.f / sum;
+    for (int k = 0; k < K; ++k) z[k] = lg[(size_t)k * HW + p];
+    loss_softmax<K>(z, pr);
     const int64_t lab = labels[(size_t)b * HW + p];
     if (lab < 0 || lab >= K) err[0] = 1;
     if (wassM) {
-      // GWDICE applies softmax to the PROBABILITIES once more (gwdl.py:104 on segmodel.py:176's y_hat) and
-      // weights them with the label-distance row of the pixel's class (gwdl.py:131-178)
-      float q[K], qs = 0.f;
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        q[k] = expf(pr[k] * inv);
-        qs += q[k];
-      }
-      const float qi = 1.f / qs;
+      // GWDICE weights the second softmax with the label-distance row of the pixel's class (gwdl.py:131-178);
+      // rounding: (M * q) * qi per term
+      float q[K];
+      const float qi = gwdice_exps<K>(pr, q);
 #pragma unroll
       for (int k = 0; k < K; ++k) {
         float wass = 0.f;
@@ -512,39 +587,9 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float* __restri
         }
       }
     }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const float pk = pr[k] * inv;
-      if (probs) probs[((size_t)b * K + k) * HW + p] = pk;
-      const float tk = (lab == k) ? 1.f : 0.f;
-      const float lp = logf(pk + 1e-10f);
-      const float om = 1.f - pk;
-      const float wgt = (gamma == 2.f) ? om * om : (gamma == 0.f ? 1.f : powf(om, gamma));
-      const float hard = pk > 0.5f ? 1.f : 0.f;
-      acc[k][0] += tk;
-      acc[k][1] += pk * tk;
-      acc[k][2] += pk;
-      acc[k][3] += wgt * tk * lp;
-      acc[k][4] += tk * lp;
-      if (dist) acc[k][5] += pk * dist[((size_t)b * K + k) * HW + p];
-      acc[k][6] += tk * hard;
-      acc[k][7] += hard;
-    }
+    loss_pixel_sums<K>(acc, pr, lab, gamma, dist, probs, b, HW, p);
   }
-  __shared__ double sh[4][K * DT_LOSS_NACC];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int j = 0; j < DT_LOSS_NACC; ++j) {
-      const double v = wave_sum_d((double)acc[k][j]);
-      if (lane == 0) sh[wave][k * DT_LOSS_NACC + j] = v;
-    }
-  __syncthreads();
-  if (threadIdx.x < K * DT_LOSS_NACC) {
-    const int i = threadIdx.x;
-    part[(size_t)blockIdx.x * K * DT_LOSS_NACC + i] = (sh[0][i] + sh[1][i]) + (sh[2][i] + sh[3][i]);
-  }
+  loss_store_partial_row<K>(acc, part + (size_t)blockIdx.x * K * DT_LOSS_NACC, threadIdx.x);
 }
 
 __global__ void seg_loss_finalize_kernel(const double* __restrict__ part, double* __restrict__ acc, int wg_per_img,
@@ -576,11 +621,9 @@ extern "C" int dt_seg_loss_fwd(const float* logits, const int64_t* labels, const
   double* part = acc + (size_t)B * K * DT_LOSS_NACC;
   hipStream_t st = (hipStream_t)stream;
   const int grid = B * wpi;
-  switch (K) {
-    case 2: hipLaunchKernelGGL(seg_loss_fwd_kernel<2>, dim3(grid), dim3(256), 0, st, logits, labels, dist, wass_m, gw_possum, gamma, part, probs, err_flag, HW, wpi); break;
-    case 3: hipLaunchKernelGGL(seg_loss_fwd_kernel<3>, dim3(grid), dim3(256), 0, st, logits, labels, dist, wass_m, gw_possum, gamma, part, probs, err_flag, HW, wpi); break;
-    default: hipLaunchKernelGGL(seg_loss_fwd_kernel<4>, dim3(grid), dim3(256), 0, st, logits, labels, dist, wass_m, gw_possum, gamma, part, probs, err_flag, HW, wpi); break;
-  }
+  head_classes<2>(K, [&](auto kc) {
+    hipLaunchKernelGGL(seg_loss_fwd_kernel<decltype(kc)::value>, dim3(grid), dim3(256), 0, st, logits, labels, dist, wass_m, gw_possum, gamma, part, probs, err_flag, HW, wpi);
+  });
   DT_LAUNCH_CHECK();
   hipLaunchKernelGGL(seg_loss_finalize_kernel, dim3(B), dim3(64), 0, st, part, acc, wpi, K * DT_LOSS_NACC);
   DT_LAUNCH_CHECK();
@@ -606,33 +649,19 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restri
     const int64_t b = i / HW, p = i - b * HW;
     const float* lg = logits + (size_t)b * K * HW;
     float z[K], pr[K], g[K];
-    float m = -INFINITY;
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-      z[k] = lg[(size_t)k * HW + p];
-      m = fmaxf(m, z[k]);
-    }
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      pr[k] = expf(z[k] - m);
-      sum += pr[k];
-    }
-    const float inv = 1.f / sum;
+    for (int k = 0; k < K; ++k) z[k] = lg[(size_t)k * HW + p];
+    loss_softmax<K>(z, pr);
     const int64_t lab = labels[i];
     float dot = 0.f;
     float gw[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) gw[k] = 0.f;
     if (wassM && lab >= 0 && lab < K) {
-      // d loss / d p through the second softmax q = softmax(p):  g_l = (wassC[b] + gwG[p]) * M[lab][l]
-      float q[K], qs = 0.f, gq = 0.f;
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        q[k] = expf(pr[k] * inv);
-        qs += q[k];
-      }
-      const float qi = 1.f / qs, c = wassC[b] + gwG[p];
+      // d loss / d p through the second softmax q = softmax(p):  g_l = (wassC[b] + gwG[p]) * M[lab][l];
+      // rounding: q normalised first
+      float q[K], gq = 0.f;
+      const float qi = gwdice_exps<K>(pr, q), c = wassC[b] + gwG[p];
 #pragma unroll
       for (int k = 0; k < K; ++k) {
         q[k] *= qi;
@@ -644,8 +673,7 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restri
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      const float pk = pr[k] * inv;
-      pr[k] = pk;
+      const float pk = pr[k];
       const float tk = (lab == k) ? 1.f : 0.f;
       float gk = coef[((size_t)b * K + k) * 2] * tk + coef[((size_t)b * K + k) * 2 + 1];
       if (wf != 0.f && tk != 0.f) {
@@ -681,11 +709,9 @@ extern "C" int dt_seg_loss_bwd(const float* logits, const int64_t* labels, const
   const int64_t HW = (int64_t)H * W, total = (int64_t)B * HW;
   const int g = dt_ew_grid(total, 256 * 16);
   hipStream_t st = (hipStream_t)stream;
-  switch (K) {
-    case 2: hipLaunchKernelGGL(seg_loss_bwd_kernel<2>, dim3((unsigned)g), dim3(256), 0, st, logits, labels, dist, coef, wfocal, wbound, gscale, wass_m, wass_coef, gw_posgrad, dlogits, HW, total); break;
-    case 3: hipLaunchKernelGGL(seg_loss_bwd_kernel<3>, dim3((unsigned)g), dim3(256), 0, st, logits, labels, dist, coef, wfocal, wbound, gscale, wass_m, wass_coef, gw_posgrad, dlogits, HW, total); break;
-    default: hipLaunchKernelGGL(seg_loss_bwd_kernel<4>, dim3((unsigned)g), dim3(256), 0, st, logits, labels, dist, coef, wfocal, wbound, gscale, wass_m, wass_coef, gw_posgrad, dlogits, HW, total); break;
-  }
+  head_classes<2>(K, [&](auto kc) {
+    hipLaunchKernelGGL(seg_loss_bwd_kernel<decltype(kc)::value>, dim3((unsigned)g), dim3(256), 0, st, logits, labels, dist, coef, wfocal, wbound, gscale, wass_m, wass_coef, gw_posgrad, dlogits, HW, total);
+  });
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
@@ -824,24 +850,11 @@ __global__ __launch_bounds__(256) void gwdice_possum_kernel(const float* __restr
   float v = 0.f;
   for (int b = 0; b < B; ++b) {
     const float* lg = logits + (size_t)b * K * HW;
-    float z[K], m = -INFINITY, sum = 0.f, qs = 0.f;
+    float z[K];   // logits, then probabilities, then the second softmax's exponentials
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-      z[k] = lg[(size_t)k * HW + p];
-      m = fmaxf(m, z[k]);
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      z[k] = expf(z[k] - m);
-      sum += z[k];
-    }
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      z[k] = expf(z[k] * inv);
-      qs += z[k];
-    }
-    const float qi = 1.f / qs;
+    for (int k = 0; k < K; ++k) z[k] = lg[(size_t)k * HW + p];
+    loss_softmax<K>(z, z);
+    const float qi = gwdice_exps<K>(z, z);   // rounding: (M * q) * qi per term
     const int64_t lab = labels[(size_t)b * HW + p];
     float wass = 0.f;
     if (lab >= 0 && lab < K) {
@@ -873,11 +886,9 @@ extern "C" int dt_gwdice_possum(const float* logits, const int64_t* labels, cons
   const int64_t HW = (int64_t)H * W;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(dt_cdiv(HW, 256));
-  switch (K) {
-    case 2: hipLaunchKernelGGL(gwdice_possum_kernel<2>, grid, dim3(256), 0, st, logits, labels, wass_m, possum, B, HW); break;
-    case 3: hipLaunchKernelGGL(gwdice_possum_kernel<3>, grid, dim3(256), 0, st, logits, labels, wass_m, possum, B, HW); break;
-    default: hipLaunchKernelGGL(gwdice_possum_kernel<4>, grid, dim3(256), 0, st, logits, labels, wass_m, possum, B, HW); break;
-  }
+  head_classes<2>(K, [&](auto kc) {
+    hipLaunchKernelGGL(gwdice_possum_kernel<decltype(kc)::value>, grid, dim3(256), 0, st, logits, labels, wass_m, possum, B, HW);
+  });
   DT_LAUNCH_CHECK();
   return DT_OK;
 }
@@ -962,7 +973,6 @@ __global__ __launch_bounds__(256) void head_eval_kernel(const void* __restrict__
   constexpr int NS = 8;                       // slots 0-7
   __shared__ float tile[HH * HW_][C + 1];
   __shared__ unsigned int hist[2 * K * K];
-  __shared__ double sh[4][K * NS];
   const int tiles_x = (W + HEAD_TW - 1) / HEAD_TW, tiles_img = tiles_x * ((H + HEAD_TH - 1) / HEAD_TH);
   const int b = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
   const int t = threadIdx.x;
@@ -1001,51 +1011,14 @@ __global__ __launch_bounds__(256) void head_eval_kernel(const void* __restrict__
         atomicAdd(&hist[(int)lab * K + best], 1u);
         if (lu && lu[o] == 1) atomicAdd(&hist[K * K + (int)lab * K + best], 1u);
       }
-      // the per-pixel arithmetic of seg_loss_fwd_kernel, expression for expression
+      // calls loss_softmax and loss_pixel_sums, the definition of the per-pixel sums (seg_loss_fwd_kernel's too)
       float pr[K];
-      float m = -INFINITY;
-#pragma unroll
-      for (int k = 0; k < K; ++k) m = fmaxf(m, z[k]);
-      float sum = 0.f;
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        pr[k] = expf(z[k] - m);
-        sum += pr[k];
-      }
-      const float inv = 1.f / sum;
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const float pk = pr[k] * inv;
-        const float tk = (lab == k) ? 1.f : 0.f;
-        const float lp = logf(pk + 1e-10f);
-        const float om = 1.f - pk;
-        const float wgt = (gamma == 2.f) ? om * om : (gamma == 0.f ? 1.f : powf(om, gamma));
-        const float hard = pk > 0.5f ? 1.f : 0.f;
-        acc[k][0] += tk;
-        acc[k][1] += pk * tk;
-        acc[k][2] += pk;
-        acc[k][3] += wgt * tk * lp;
-        acc[k][4] += tk * lp;
-        if (dist) acc[k][5] += pk * dist[((size_t)b * K + k) * HWs + p];
-        acc[k][6] += tk * hard;
-        acc[k][7] += hard;
-      }
+      loss_softmax<K>(z, pr);
+      loss_pixel_sums<K>(acc, pr, lab, gamma, dist, nullptr, b, HWs, p);
     }
   }
-  const int lane = t & 63, wave = t >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int j = 0; j < NS; ++j) {
-      const double v = wave_sum_d((double)acc[k][j]);
-      if (lane == 0) sh[wave][k * NS + j] = v;
-    }
-  __syncthreads();                            // also: every histogram update of this workgroup is done
-  if (t < K * DT_LOSS_NACC) {
-    const int k = t / DT_LOSS_NACC, j = t % DT_LOSS_NACC;
-    const int i = k * NS + j;
-    part[(size_t)blockIdx.x * K * DT_LOSS_NACC + t] = j < NS ? (sh[0][i] + sh[1][i]) + (sh[2][i] + sh[3][i]) : 0.0;
-  }
+  // its __syncthreads() also fences the histogram: every update of this workgroup is done before the flush below
+  loss_store_partial_row<K>(acc, part + (size_t)blockIdx.x * K * DT_LOSS_NACC, t);
   if (t < 2 * K * K && hist[t]) atomicAdd(&counts[t], (unsigned long long)hist[t]);
 }
 
@@ -1069,11 +1042,9 @@ static int head_eval_launch(const void* x, const float* w, const float* bias, co
   double* part = acc + (size_t)B * K * DT_LOSS_NACC;
   unsigned long long* cnt = (unsigned long long*)counts;
   hipStream_t st = (hipStream_t)stream;
-  switch (K) {
-    case 2: hipLaunchKernelGGL((head_eval_kernel<2, XB>), dim3(grid), dim3(256), 0, st, x, w, bias, labels, lu, dist, gamma, part, cnt, am8, err, H, W, chunks); break;
-    case 3: hipLaunchKernelGGL((head_eval_kernel<3, XB>), dim3(grid), dim3(256), 0, st, x, w, bias, labels, lu, dist, gamma, part, cnt, am8, err, H, W, chunks); break;
-    default: hipLaunchKernelGGL((head_eval_kernel<4, XB>), dim3(grid), dim3(256), 0, st, x, w, bias, labels, lu, dist, gamma, part, cnt, am8, err, H, W, chunks); break;
-  }
+  head_classes<2>(K, [&](auto kc) {
+    hipLaunchKernelGGL((head_eval_kernel<decltype(kc)::value, XB>), dim3(grid), dim3(256), 0, st, x, w, bias, labels, lu, dist, gamma, part, cnt, am8, err, H, W, chunks);
+  });
   DT_LAUNCH_CHECK();
   hipLaunchKernelGGL(seg_loss_finalize_kernel, dim3(B), dim3(64), 0, st, part, acc, chunks, K * DT_LOSS_NACC);
   DT_LAUNCH_CHECK();

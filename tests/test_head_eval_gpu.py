@@ -12,7 +12,12 @@ the reference alone, asserted below.  ``dist`` is drawn from [0, 20): the bound 
 only means something while the terms do not cancel (signed maps from the device distance transform run through the same
 kernel in tests/test_validate_gpu.py, and the unfused kernel's signed sums are bounded against sum |term| in
 tests/test_loss_kernels_gpu.py).  Shapes: one tile (8 x 32), partial tiles, 27 tiles per image (16 + a remainder
-chunk of 11 for the 16 tiles a workgroup walks), K = 2, 3, 4, bf16 input, and a call without lu and dist."""
+chunk of 11 for the 16 tiles a workgroup walks), K = 2, 3, 4, bf16 input, and a call without lu and dist.
+
+Focal gamma: 2.0 everywhere, and 0.0 / 0.5 (the ``gamma == 0`` shortcut and the ``powf`` branch of loss_pixel_sums, which
+the fused kernel shares with seg_loss_fwd_kernel) on ``partial`` and ``k4``.  There slot 3 is additionally held to
+1e-6 * sum |term| against fp64 ``(1 - p) ** gamma * t * log(p + 1e-10)``, the bound
+test_loss_kernels_gpu.py::test_accumulators_probs_and_scratch_layout puts on that slot."""
 import functools
 
 import pytest
@@ -30,6 +35,7 @@ CASES = {"one_tile":     (2, 2, 8, 32, False, True, ("GDICE", "FOCAL", "BOUNDARY
          "bf16":         (2, 2, 40, 70, True, True, ("GDICE", "FOCAL", "BOUNDARY")),
          "no_lu_dist":   (2, 3, 21, 17, False, False, ("GDICE", "FOCAL"))}
 ALPHA = 0.37
+GAMMA_CASES = [(name, 2.0) for name in CASES] + [(name, g) for name in ("partial", "k4") for g in (0.0, 0.5)]
 
 
 def _inputs(seed, B, K, H, W, bf16):
@@ -50,7 +56,7 @@ def _logits64(x, w, bias):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(name):
+def _case(name, gamma=2.0):
     """inputs + the fp64 reference of a case, computed once and shared (nothing below writes to them)"""
     from test_loss_kernels_gpu import _oracle64
     B, K, H, W, bf16, full, names = CASES[name]
@@ -66,10 +72,12 @@ def _case(name):
         lu = dist = None
     t = torch.stack([(labels == k) for k in range(K)], 1).double()
     lp = torch.log(p + 1e-10)
-    terms = [p * t, p, (1 - p) ** 2 * t * lp, t * lp, p * dist.double() if dist is not None else torch.zeros_like(p)]
+    wgt = torch.ones_like(p) if gamma == 0 else (1 - p) ** gamma
+    terms = [p * t, p, wgt * t * lp, t * lp, p * dist.double() if dist is not None else torch.zeros_like(p)]
     slots = torch.stack([v.sum(dim=(2, 3)) for v in terms], -1)          # [B,K,5]: slots 1..5
-    parts, _ = _oracle64(z, labels, names, dist, ALPHA)
-    return dict(x=x, w=w, bias=bias, labels=labels, lu=lu, dist=dist, K=K, names=names, slots=slots, parts=parts)
+    parts, _ = _oracle64(z, labels, names, dist, ALPHA, gamma)
+    return dict(x=x, w=w, bias=bias, labels=labels, lu=lu, dist=dist, K=K, names=names, slots=slots, parts=parts,
+                gamma=gamma, focal_mag=terms[2].abs().sum(dim=(2, 3)))
 
 
 def _dev(t):
@@ -94,7 +102,7 @@ def _unfused(c):
     from deadtrees_amd import ops
     from deadtrees_amd.loss.seg_loss import loss_sums
     logits, am = _head_fwd(_dev(c["x"]), _dev(c["w"]), _dev(c["bias"]))
-    acc, _, err = loss_sums(logits, _dev(c["labels"]), _dev(c["dist"]), 2.0)
+    acc, _, err = loss_sums(logits, _dev(c["labels"]), _dev(c["dist"]), c["gamma"])
     counts, err_cm = ops.confusion_matrix(am, _dev(c["labels"]), _dev(c["lu"]), K=c["K"])
     return acc, am, counts, max(int(err), int(err_cm))
 
@@ -102,13 +110,13 @@ def _unfused(c):
 def _fused(c, **kw):
     from deadtrees_amd import ops
     return ops.head_eval(_dev(c["x"]), _dev(c["w"]), _dev(c["bias"]), _dev(c["labels"]), _dev(c["lu"]), _dev(c["dist"]),
-                         2.0, want_argmax=True, **kw)
+                         c["gamma"], want_argmax=True, **kw)
 
 
 def _parts(acc, c):
     from deadtrees_amd.loss.seg_loss import PART_KEYS, loss_algebra
     B, H, W, _ = c["x"].shape
-    parts = loss_algebra(acc, c["names"], B, c["K"], H, W, c["dist"] is not None, ALPHA)[0]
+    parts = loss_algebra(acc, c["names"], B, c["K"], H, W, c["dist"] is not None, ALPHA, c["gamma"])[0]
     assert float(parts[7]) == float(parts[6])
     return {k: float(parts[i]) for i, k in enumerate(PART_KEYS)}
 
@@ -117,10 +125,13 @@ def _rel_err(got, want):
     return float(((got - want).abs() / want.abs().clamp_min(1e-30)).max())
 
 
-@pytest.mark.parametrize("name", list(CASES))
-def test_fused_head_against_the_unfused_chain_and_fp64(name):
+@pytest.mark.parametrize("name,gamma", GAMMA_CASES,
+                         ids=[name if g == 2.0 else f"{name}-gamma{g}" for name, g in GAMMA_CASES])
+def test_fused_head_against_the_unfused_chain_and_fp64(name, gamma):
     from conftest import parity_report
-    c = _case(name)
+    c = _case(name, gamma)
+    if gamma != 2.0:
+        name = f"{name} gamma={gamma}"
     K = c["K"]
     acc, counts, am, err = _fused(c)
     acc_u, am_u, counts_u, err_u = _unfused(c)
@@ -143,6 +154,11 @@ def test_fused_head_against_the_unfused_chain_and_fp64(name):
     for idx in torch.cartesian_prod(*[torch.arange(s) for s in want.shape]).tolist():
         b, k, j = idx
         assert float(got[b, k, j]) == pytest.approx(float(want[b, k, j]), rel=1e-5, abs=1e-6), (name, b, k, j + 1)
+    if gamma != 2.0:
+        err3, bound3 = (got[..., 2] - want[..., 2]).abs(), 1e-6 * c["focal_mag"]
+        parity_report(f"[head_eval {name}] slot 3 worst |err| / sum|term| vs fp64: "
+                      f"{float((err3 / c['focal_mag'].clamp_min(1e-300)).max()):.2e} (bound 1e-6)")
+        assert not bool((err3 > bound3).any()), (name, err3.tolist(), bound3.tolist())
     # ---- the eight parts after the algebra
     parts, parts_u = _parts(acc, c), _parts(acc_u, c)
     worst = max(abs(parts[k] - v) / max(abs(v), 1e-30) for k, v in c["parts"].items())
