@@ -103,8 +103,10 @@ class EngineCore:
         # bf16 activation (2 + 2 B per element) lets conv2 and its weight gradient run the pure-DMA form: 2,235 vs 2,203
         self._mat_z1_bf16 = os.environ.get("DT_BF16_MAT_Z1", "1") != "0"
         self._mat_dec_bf16 = os.environ.get("DT_BF16_MAT_DEC", "1") != "0"
-        # when a dict: the bf16 training pass stores a copy of every intermediate tensor it produces under the
-        # names of oracle/unet_bf16_ref.py (teacher-forced parity test); None in production
+        # when a dict: the training pass of either precision (fp32: forward / backward, bf16: forward_bf16_train /
+        # backward_bf16) stores a copy of every intermediate tensor it produces and does not keep for the backward anyway,
+        # under the names of oracle/unet_bf16_ref.py (teacher-forced parity tests); None in production — then the pass
+        # launches and allocates nothing for it.  Not under graph capture (the copies are allocations of the pass).
         self.trace: Optional[dict] = None
 
     # ------------------------------------------------------------------ the launch path
@@ -125,6 +127,8 @@ class EngineCore:
     # ------------------------------------------------------------------ helpers
     def _tr(self, name: str, t: Optional[torch.Tensor]):
         if self.trace is not None and t is not None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("engine.trace is for eager passes: set it to None before capturing a graph")
             self.trace[name] = t.clone()
 
     def _buf(self, name: str, numel: int, dtype=torch.float32, device=None) -> torch.Tensor:

@@ -220,6 +220,7 @@ class Fp32Schedule:
         amax = torch.empty((B, hp, wp, 64), dtype=torch.uint8, device=dev) if enc_save else None
         self._call("dt_maxpool3x3s2", f1, pool, amax, B, h, w_, 64)
         keep_enc("pool", amax=amax, H=h, W=w_)
+        self._tr("pool", pool)
 
         feats = [f1]
         cur, ch, cw = pool, hp, wp
@@ -289,6 +290,7 @@ class Fp32Schedule:
                 out = self._bn_act(y2, ss2, res=idy, res_ss=(self._const_vec(1.0, ic.cout, dev), ic.bias(params)),
                                    relu=2, of=blk.conv2)
                 del idy
+                self._tr(f"D{i}.out", out)
                 keep(f"D{i}", x=d, skip=skip, y1=y1, y2=y2, H=h1, W=w1)
                 d, dh, dw, d_ss = out, h2, w2, None
                 continue
@@ -607,9 +609,11 @@ class Fp32Schedule:
         for blk in reversed(sp.decoder):
             d = S["P" + blk.name]
             g = G.pop(blk.name)
+            self._tr(f"P{blk.name}.g", g)
             dev = g.device
             Hh, Ww = d["H"], d["W"]
             dy2 = self._bn_bwd(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True)
+            self._tr(f"P{blk.name}.dy2", dy2)
             del g
             self._wgrad(blk.conv2, grads, d["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
             dz1 = torch.empty_like(d["y1"])
@@ -618,7 +622,9 @@ class Fp32Schedule:
             else:
                 red1 = self._dgrad(blk.conv2, params, dy2, B, Hh, Ww, dz1)
             del dy2
+            self._tr(f"P{blk.name}.dz1", dz1)
             dy1 = self._bn_bwd(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
+            self._tr(f"P{blk.name}.dy1", dy1)
             del dz1
             self._wgrad(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1)
             cx = blk.in_ch
@@ -627,8 +633,10 @@ class Fp32Schedule:
             if d["skip"] is not None:
                 dskip = torch.empty_like(d["skip"])
                 self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup, dskip, split=cx)
+                self._tr(f"P{blk.name}.dskip", dskip)
             else:
                 self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup)
+            self._tr(f"P{blk.name}.dup", dup)
             del dy1
             glow, acc = slot(blk.low, d["x"].shape, dev)
             self._call("dt_upsample2x_bwd", dup, glow, acc, B, Hh // 2, Ww // 2, cx)
@@ -644,9 +652,11 @@ class Fp32Schedule:
             S["P" + blk.name] = None
         for k in range(1, 5):
             skip_grads[4 - k] = G[f"f{k}"]      # f_k of the decoder = feats[4 - k]
+            self._tr(f"Pf{k}.g", G[f"f{k}"])
+        self._tr("Pf0.g", G["f0"])
         return G["f0"]
 
-    def _backward_resunet_block(self, blk, d, g, params, grads, bn: BnView, B, Hh, Ww, skip_grads, skip_slot):
+    def _backward_resunet_block(self, i, blk, d, g, params, grads, bn: BnView, B, Hh, Ww, skip_grads, skip_slot):
         """reverse of one ResUnet decoder block (forward: see the decoder loop): g = gradient of the block output
         [B,Hh,Ww,cout] -> returns the gradient of the block's low-resolution input; writes the skip gradient."""
         lib, dev = self.lib, g.device
@@ -659,12 +669,15 @@ class Fp32Schedule:
         self._call("dt_channel_sums", g, ws, n_pix, ic.cout, ic.bias(grads))
         # main branch: relu(bn2(conv2(relu(bn1(conv1(xin))))))  (both activations virtual: masks from y*scale+shift)
         dy2 = self._bn_bwd(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True)
+        self._tr(f"D{i}.dy2", dy2)
         self._wgrad(blk.conv2, grads, d["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
         dz1 = torch.empty_like(d["y1"])
         red1 = self._dgrad_bn(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, d["y1"], bn) if self._fuse_bn else \
             self._dgrad(blk.conv2, params, dy2, B, Hh, Ww, dz1)
         del dy2
+        self._tr(f"D{i}.dz1", dz1)
         dy1 = self._bn_bwd(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
+        self._tr(f"D{i}.dy1", dy1)
         del dz1
         self._wgrad(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1)
         dup = torch.empty((B, Hh, Ww, cx), dtype=torch.float32, device=dev)
@@ -677,6 +690,7 @@ class Fp32Schedule:
             one, zero = self._const_vec(1.0, sk, dev), self._const_vec(0.0, sk, dev)
             self._bn_act(dskip, (one, zero), res=dskip_id, relu=0, out=dskip)
             skip_grads[skip_slot] = dskip
+            self._tr(f"D{i}.dskip", dskip)
             del dskip_id
         else:
             self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup)
@@ -685,6 +699,7 @@ class Fp32Schedule:
         gx = torch.empty_like(d["x"])
         self._call("dt_upsample2x_bwd", dup, gx, 0, B, Hh // 2, Ww // 2, cx)
         self._call("dt_upsample2x_bwd", dup_id, gx, 1, B, Hh // 2, Ww // 2, cx)
+        self._tr(f"D{i}.g", gx)      # (the two branches' up-sampled parts are never summed at full resolution: no D{i}.dup)
         return gx
 
     # ------------------------------------------------------------------ backward
@@ -719,6 +734,7 @@ class Fp32Schedule:
         self._call("dt_head_bwd", h["x"], hd.w(params), dlogits, g, red, B, H, W, hd.cin, K)
         self._pe(e0, "head_bwd_kernel", 4.0 * 9 * hd.cin * K * B * H * W, 4.0 * B * H * W * (2 * hd.cin + K))
         self._call("dt_head_bwd_finalize", red, P, hd.w(grads), hd.bias(grads), hd.cin, K)
+        self._tr("head.g", g)
 
         # ---- decoder (reverse)
         skip_grads = [None] * 5  # gradient of feats[0..4] = f1..f5
@@ -731,12 +747,13 @@ class Fp32Schedule:
             d = S[f"D{i}"]
             Hh, Ww = d["H"], d["W"]
             if sp.decoder_kind == "resunet":
-                g = self._backward_resunet_block(blk, d, g, params, grads, bn, B, Hh, Ww, skip_grads, 3 - i)
+                g = self._backward_resunet_block(i, blk, d, g, params, grads, bn, B, Hh, Ww, skip_grads, 3 - i)
                 S[f"D{i}"] = None
                 continue
             # conv2 + BN + ReLU (activation stored only for the last block)
             # mask recomputed from y2 * scale + shift even where z2 was stored (identical to bn_act's; one read less)
             dy2 = self._bn_bwd(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True, reduced=g_red)
+            self._tr(f"D{i}.dy2", dy2)
             if d.get("z1") is not None:
                 self._wgrad(blk.conv2, grads, d["z1"], None, 0, B, Hh, Ww, dy2)
             else:
@@ -747,7 +764,9 @@ class Fp32Schedule:
             else:
                 red1 = self._dgrad(blk.conv2, params, dy2, B, Hh, Ww, dz1)
             del dy2
+            self._tr(f"D{i}.dz1", dz1)
             dy1 = self._bn_bwd(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
+            self._tr(f"D{i}.dy1", dy1)
             del dz1
             x_ss = bn.ss(sp.decoder[i - 1].conv2) if d["x_virtual"] else None
             self._wgrad(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1, in_ss=x_ss)
@@ -761,6 +780,7 @@ class Fp32Schedule:
             if d["skip"] is None and i >= 1 and self._fuse_bn and self._upsampled_dgrad(blk, below[0], params, bn, dy1,
                                                                                        below[1], d, B, Hh, Ww):
                 g, g_red = d["g"], d["g_red"]
+                self._tr(f"D{i}.g", g)
                 del dy1
                 S[f"D{i}"] = None
                 continue
@@ -773,6 +793,8 @@ class Fp32Schedule:
                     g, g_red, dskip = got
                     if dskip is not None:
                         skip_grads[3 - i] = dskip
+                    self._tr(f"D{i}.dskip", dskip)
+                    self._tr(f"D{i}.g", g)
                     del dy1
                     S[f"D{i}"] = None
                     continue
@@ -782,8 +804,10 @@ class Fp32Schedule:
                 dskip = torch.empty_like(d["skip"])
                 self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup, dskip, split=cx)
                 skip_grads[3 - i] = None if frozen else dskip
+                self._tr(f"D{i}.dskip", dskip)
             else:
                 self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup)
+            self._tr(f"D{i}.dup", dup)
             del dy1
             g = torch.empty_like(d["x"])
             g_red = None
@@ -796,6 +820,7 @@ class Fp32Schedule:
             else:
                 self._call("dt_upsample2x_bwd", dup, g, 0, B, Hh // 2, Ww // 2, cx)
             del dup
+            self._tr(f"D{i}.g", g)
             S[f"D{i}"] = None
         self._bucket_done(sp.buckets[0])
         if frozen:      # frozen encoder weights: backward stops at the decoder (no encoder data / weight gradient)
@@ -822,11 +847,15 @@ class Fp32Schedule:
                                        dres_acc=gin_has, reduced=g_red)
                     gin_has = True
                     dyd = None
+                    self._tr(f"L{li}B{bi}.gres", gin)
                 else:
                     gd = torch.empty_like(r["out"])
                     dy2 = self._bn_bwd(blk.conv2, params, grads, bn, g, r["out"], r["y2"], dres=gd, reduced=g_red)
                     dyd = self._bn_bwd(blk.down, params, grads, bn, gd, None, r["yd"])
+                    self._tr(f"L{li}B{bi}.gres", gd)
+                    self._tr(f"L{li}B{bi}.dyd", dyd)
                     del gd
+                self._tr(f"L{li}B{bi}.dy2", dy2)
                 if r.get("z1") is not None:
                     self._wgrad(blk.conv2, grads, r["z1"], None, 0, B, Hh, Ww, dy2)
                 else:
@@ -837,7 +866,9 @@ class Fp32Schedule:
                 else:
                     red1 = self._dgrad(blk.conv2, params, dy2, B, Hh, Ww, dz1)
                 del dy2
+                self._tr(f"L{li}B{bi}.dz1", dz1)
                 dy1 = self._bn_bwd(blk.conv1, params, grads, bn, dz1, None, r["y1"], virtual_act=True, reduced=red1)
+                self._tr(f"L{li}B{bi}.dy1", dy1)
                 del dz1
                 self._wgrad(blk.conv1, grads, r["x"], None, 0, B, Hin, Win, dy1)
                 g_red = None
@@ -851,10 +882,12 @@ class Fp32Schedule:
                     self._dgrad(blk.conv1, params, dy1, B, Hin, Win, gin, acc=gin_has)
                 gin_has = True
                 del dy1
+                self._tr(f"L{li}B{bi}.gin1", gin)
                 if dyd is not None:
                     self._wgrad(blk.down, grads, r["x"], None, 0, B, Hin, Win, dyd)
                     self._dgrad(blk.down, params, dyd, B, Hin, Win, gin, acc=True)
                     del dyd
+                    self._tr(f"L{li}B{bi}.gin", gin)
                 g = gin
                 S[f"L{li}B{bi}"] = None
             if li > 0:
@@ -873,7 +906,9 @@ class Fp32Schedule:
             stem_red = (red, P)
         else:
             self._call("dt_maxpool3x3s2_bwd", g, pl["amax"], gf1, 1, B, pl["H"], pl["W"], 64)
+        self._tr("gf1", gf1)
         dy = self._bn_bwd(sp.stem, params, grads, bn, gf1, None, stem["y"], virtual_act=True, reduced=stem_red)
+        self._tr("stem.dy", dy)
         self._wgrad(sp.stem, grads, stem["x"], None, 0, B, stem["Hin"], stem["Win"], dy)
         self._join_side()
         if self.grad_hook:

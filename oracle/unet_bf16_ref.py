@@ -1,4 +1,5 @@
-"""Rounding-aware CPU oracle of the bf16 training path (BASELINE configs[2]).
+"""Rounding-aware CPU oracle of the bf16 training path (BASELINE configs[2]) and, with ``rounding=False``, the
+unit-by-unit oracle of the fp32 training path (second contract, at the end of this docstring).
 
 TEST INFRASTRUCTURE (see oracle/__init__.py).  PARITY UNPINNED for topology like ``unet_ref.py`` (same
 restated smp ``Unet``/``resnet34`` graph — the module passed in IS a ``UNetR34Ref``); what this file adds is
@@ -49,6 +50,18 @@ Two ways to use it (tests/test_bf16_gpu.py):
   O(1) error in exactly the unit that has it.
 
 Follows deadtrees_amd/network/engine_bf16.py ``forward_bf16_train`` / ``backward_bf16`` step by step.
+
+The second contract: ``rounding=False`` (tests/test_fp32_e2e_gpu.py, tests/test_fp32_oracle_cpu.py)
+  Every rounding point above becomes the identity; what stays is the unit structure and the unit names, which are
+  those of the fp32 engine as well (deadtrees_amd/network/engine_fp32.py ``forward`` / ``backward``), and the fp32
+  arithmetic both engines share: BatchNorm coefficients are fp32 vectors, ``y * scale + shift`` is an fp32 multiply
+  followed by an fp32 add (no fma), so the ReLU mask recomputed from a forced ``y``, ``scale``, ``shift`` is the
+  kernels' mask bit for bit.  Teacher-forced in fp64 this pins every unit of the fp32 training step: one unit's
+  output from the HIP path's own inputs of that unit, to fp32 accumulation accuracy (no mask can flip, nothing
+  cascades).  Un-rounded, a fused form and the chain it replaces are the same arithmetic in fp64, so a tensor the
+  fp32 engine never materialises (``D{i}.dup`` where the up-sampling's backward rides in the data-gradient epilogue)
+  is simply left unforced: it is listed in ``unforced`` and the oracle goes on with its own value.
+  ``rounding=True`` (the default) looks ``rbf`` up at call time, so replacing the module's ``rbf`` still reaches it.
 """
 from __future__ import annotations
 
@@ -75,8 +88,9 @@ def _aff32(y, sc, sh):
 
 class Bf16TrainOracle:
     def __init__(self, ref: UNetR34Ref, dtype=torch.float64, forced: Optional[Dict[str, torch.Tensor]] = None,
-                 update_running: bool = True, record: bool = False):
+                 update_running: bool = True, record: bool = False, rounding: bool = True):
         self.ref, self.dt = ref, dtype
+        self.rounding = rounding     # False: no bf16 rounding anywhere — the fp32 engine's contract (module docstring)
         self.forced = forced
         self.rec: Optional[Dict[str, torch.Tensor]] = {} if record else None   # every named tensor of a free run
         self.update_running = update_running
@@ -108,8 +122,12 @@ class Bf16TrainOracle:
         return tuple(self._t(f"{name}.{k}", v) for k, v in zip(("scale", "shift", "mean", "invstd"), ss))
 
     # ------------------------------------------------------------------ helpers
+    def _r(self, x):
+        """a rounding point of the bf16 path (``rbf`` looked up in the module at call time); the identity un-rounded"""
+        return rbf(x) if self.rounding else x
+
     def _w(self, conv):
-        return rbf(conv.weight.detach()).to(self.dt)
+        return self._r(conv.weight.detach()).to(self.dt)
 
     def _conv_bn(self, conv, bn, x, name):
         """x: already the bf16-valued operand.  -> y (bf16 values), (scale, shift, mean, invstd) fp32"""
@@ -130,11 +148,11 @@ class Bf16TrainOracle:
             with torch.no_grad():
                 bn.running_mean.mul_(0.9).add_(0.1 * mean32)
                 bn.running_var.mul_(0.9).add_(0.1 * unb.float())
-        y = self._t(f"{name}", rbf(v).to(self.dt))
+        y = self._t(f"{name}", self._r(v).to(self.dt))
         return y, self._tss(f"{name}.bn", (sc, sh, mean32, is32))
 
     def _virt(self, y, ss):
-        return rbf(F.relu(_aff32(y, ss[0], ss[1]))).to(self.dt)
+        return self._r(F.relu(_aff32(y, ss[0], ss[1]))).to(self.dt)
 
     # ------------------------------------------------------------------ forward
     def forward(self, img: torch.Tensor) -> torch.Tensor:
@@ -145,7 +163,7 @@ class Bf16TrainOracle:
         s2d = (W // 2) > 16 and H % 2 == 0 and W % 2 == 0
         x = img.float()
         if s2d:
-            v = F.conv2d(rbf(x).to(dt), self._w(enc.conv1), stride=2, padding=3)
+            v = F.conv2d(self._r(x).to(dt), self._w(enc.conv1), stride=2, padding=3)
         else:
             v = F.conv2d(x.to(dt), enc.conv1.weight.detach().to(dt), stride=2, padding=3)
         y, ss = self._finish_bn(v, enc.bn1, "stem.y")
@@ -170,7 +188,7 @@ class Bf16TrainOracle:
                 else:
                     yd, ssd = None, None
                     f = f + xin.float()
-                out = self._t(f"{n}.out", rbf(F.relu(f)).to(dt))
+                out = self._t(f"{n}.out", self._r(F.relu(f)).to(dt))
                 S[n] = dict(x=xin, y1=y1, ss1=ss1, y2=y2, ss2=ss2, yd=yd, ssd=ssd, out=out)
                 cur = out
             feats.append(cur)
@@ -206,9 +224,9 @@ class Bf16TrainOracle:
                 # convolution of the (up-sampled, concatenated) input is stored as bf16 WITHOUT its bias; the join is
                 # bf16(relu(y2 * scale + shift) + (idy * 1 + bias)) in fp32 (dt_bn_act_bf16, relu = 2)
                 idc = blk.identity_conv
-                idy = rbf(F.conv2d(xin.to(dt), self._w(idc))).float()
+                idy = self._r(F.conv2d(xin.to(dt), self._w(idc))).float()
                 f = F.relu(_aff32(y2, ss2[0], ss2[1])) + (idy * 1.0 + idc.bias.detach().float()[None, :, None, None])
-                out = self._t(f"{n}.out", rbf(f).to(dt))
+                out = self._t(f"{n}.out", self._r(f).to(dt))
                 S[n] = dict(xin=xin, cx=xa.shape[1], y1=y1, ss1=ss1, y2=y2, ss2=ss2, z2=None)
                 d, d_ss = out, None
                 continue
@@ -245,7 +263,7 @@ class Bf16TrainOracle:
         gi = (bn.weight.detach().float() * ss[3])[None, :, None, None]
         kb = (dbet * float(torch.tensor(1.0 / n, dtype=torch.float32)))[None, :, None, None]
         kg = (dgam * float(torch.tensor(1.0 / n, dtype=torch.float32)))[None, :, None, None]
-        dy = rbf(gi * (g.float() - kb - xh32 * kg)).to(dt)
+        dy = self._r(gi * (g.float() - kb - xh32 * kg)).to(dt)
         return dy, g
 
     def _wgrad(self, conv, name, x, dy):
@@ -284,20 +302,20 @@ class Bf16TrainOracle:
             dy2 = self._t(f"{n}.dy2", dy2)
             z1 = self._virt(d["y1"], d["ss1"])
             self._wgrad(blk.conv2[0], f"{p}.conv2.0.weight", z1, dy2)
-            dz1 = self._t(f"{n}.dz1", rbf(self._dgrad(blk.conv2[0], z1.shape, dy2)).to(dt))
+            dz1 = self._t(f"{n}.dz1", self._r(self._dgrad(blk.conv2[0], z1.shape, dy2)).to(dt))
             dy1, _ = self._bn_bwd(blk.conv1[1], f"{p}.conv1.1", dz1, d["y1"], d["ss1"], virtual=True)
             dy1 = self._t(f"{n}.dy1", dy1)
             self._wgrad(blk.conv1[0], f"{p}.conv1.0.weight", d["xin"], dy1)
-            dxin = rbf(self._dgrad(blk.conv1[0], d["xin"].shape, dy1)).to(dt)
+            dxin = self._r(self._dgrad(blk.conv1[0], d["xin"].shape, dy1)).to(dt)
             cx = d["cx"]
             dskip = self._t(f"{n}.dskip", dxin[:, cx:].contiguous()) if cat else None
             dup = self._t(f"{n}.dup", dxin[:, :cx].contiguous()).float()
             quad = (dup[:, :, 0::2, 0::2] + dup[:, :, 0::2, 1::2]) + (dup[:, :, 1::2, 0::2] + dup[:, :, 1::2, 1::2])
-            G[low] = rbf(quad).to(dt) if low not in G else rbf(G[low].float() + quad).to(dt)
+            G[low] = self._r(quad).to(dt) if low not in G else self._r(G[low].float() + quad).to(dt)
             off = 0
             for cname, Cn in zip(cat, d["widths"]):
                 part = dskip[:, off:off + Cn]
-                G[cname] = part.contiguous() if cname not in G else rbf(G[cname].float() + part.float()).to(dt)
+                G[cname] = part.contiguous() if cname not in G else self._r(G[cname].float() + part.float()).to(dt)
                 off += Cn
         for k in range(1, 5):
             skip_grads[4 - k] = self._t(f"Pf{k}.g", G[f"f{k}"])
@@ -314,18 +332,18 @@ class Bf16TrainOracle:
         dy2 = self._t(f"{n}.dy2", dy2)
         z1 = self._virt(d["y1"], d["ss1"])
         self._wgrad(blk.conv2[0], f"{p}.conv2.0.weight", z1, dy2)
-        dz1 = self._t(f"{n}.dz1", rbf(self._dgrad(blk.conv2[0], z1.shape, dy2)).to(dt))
+        dz1 = self._t(f"{n}.dz1", self._r(self._dgrad(blk.conv2[0], z1.shape, dy2)).to(dt))
         dy1, _ = self._bn_bwd(blk.conv1[1], f"{p}.conv1.1", dz1, d["y1"], d["ss1"], virtual=True)
         dy1 = self._t(f"{n}.dy1", dy1)
         self._wgrad(blk.conv1[0], f"{p}.conv1.0.weight", xin, dy1)
-        da = rbf(self._dgrad(blk.conv1[0], xin.shape, dy1)).float()
-        db = rbf(self._dgrad(idc, xin.shape, g)).float()
+        da = self._r(self._dgrad(blk.conv1[0], xin.shape, dy1)).float()
+        db = self._r(self._dgrad(idc, xin.shape, g)).float()
         if xin.shape[1] > cx:
-            skip_grads[slot] = self._t(f"{n}.dskip", rbf(da[:, cx:] + db[:, cx:]).to(dt))
-        dup = self._t(f"{n}.dup", rbf(da[:, :cx] + db[:, :cx]).to(dt))
+            skip_grads[slot] = self._t(f"{n}.dskip", self._r(da[:, cx:] + db[:, cx:]).to(dt))
+        dup = self._t(f"{n}.dup", self._r(da[:, :cx] + db[:, :cx]).to(dt))
         a, b_, c, e = (dup[:, :, 0::2, 0::2].float(), dup[:, :, 0::2, 1::2].float(), dup[:, :, 1::2, 0::2].float(),
                        dup[:, :, 1::2, 1::2].float())
-        return self._t(f"{n}.g", rbf((a + b_) + (c + e)).to(dt))
+        return self._t(f"{n}.g", self._r((a + b_) + (c + e)).to(dt))
 
     # ------------------------------------------------------------------ backward
     def backward(self, dlogits: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -337,7 +355,7 @@ class Bf16TrainOracle:
         dl = dlogits.to(dt)
         self.grads["segmentation_head.0.weight"] = conv2d_weight(hx.to(dt), head.weight.shape, dl, padding=head.padding).float()
         self.grads["segmentation_head.0.bias"] = dl.sum(dim=(0, 2, 3)).float()
-        g = self._t("head.g", rbf(conv2d_input(hx.shape, head.weight.detach().to(dt), dl, padding=head.padding)).to(dt))
+        g = self._t("head.g", self._r(conv2d_input(hx.shape, head.weight.detach().to(dt), dl, padding=head.padding)).to(dt))
 
         skip_grads = [None] * 5
         dense = isinstance(dec.blocks, torch.nn.ModuleDict)
@@ -354,7 +372,7 @@ class Bf16TrainOracle:
             dy2 = self._t(f"{n}.dy2", dy2)
             z1 = self._virt(d["y1"], d["ss1"])
             self._wgrad(blk.conv2[0], f"{p}.conv2.0.weight", z1, dy2)
-            dz1 = self._t(f"{n}.dz1", rbf(self._dgrad(blk.conv2[0], z1.shape, dy2)).to(dt))
+            dz1 = self._t(f"{n}.dz1", self._r(self._dgrad(blk.conv2[0], z1.shape, dy2)).to(dt))
             dy1, _ = self._bn_bwd(blk.conv1[1], f"{p}.conv1.1", dz1, d["y1"], d["ss1"], virtual=True)
             dy1 = self._t(f"{n}.dy1", dy1)
             self._wgrad(blk.conv1[0], f"{p}.conv1.0.weight", d["xin"], dy1)
@@ -368,16 +386,16 @@ class Bf16TrainOracle:
                 # on the fp32 accumulators of the data gradient (dt_conv2d_bf16_upsampled_dgrad) — ONE rounding, no
                 # full-resolution gradient tensor
                 u = dxin_acc.to(dt)
-                g = self._t(f"{n}.g", rbf((u[:, :, 0::2, 0::2] + u[:, :, 0::2, 1::2]) +
+                g = self._t(f"{n}.g", self._r((u[:, :, 0::2, 0::2] + u[:, :, 0::2, 1::2]) +
                                           (u[:, :, 1::2, 0::2] + u[:, :, 1::2, 1::2])).to(dt))
                 continue
-            dxin = rbf(dxin_acc).to(dt)
+            dxin = self._r(dxin_acc).to(dt)
             dup = self._t(f"{n}.dup", dxin[:, :cx].contiguous())
             if dxin.shape[1] > cx:
                 skip_grads[3 - i] = self._t(f"{n}.dskip", dxin[:, cx:].contiguous())
             a, b_, c, e = (dup[:, :, 0::2, 0::2].float(), dup[:, :, 0::2, 1::2].float(), dup[:, :, 1::2, 0::2].float(),
                            dup[:, :, 1::2, 1::2].float())
-            g = self._t(f"{n}.g", rbf((a + b_) + (c + e)).to(dt))
+            g = self._t(f"{n}.g", self._r((a + b_) + (c + e)).to(dt))
 
         for li in (3, 2, 1, 0):
             layer = getattr(enc, f"layer{li + 1}")
@@ -390,7 +408,7 @@ class Bf16TrainOracle:
                 dy2, gm = self._bn_bwd(blk.bn2, f"{p}.bn2", g, s["y2"], s["ss2"], mask_from=s["out"])
                 dy2 = self._t(f"{n}.dy2", dy2)
                 if blk.downsample is None:
-                    gin = gm if gin is None else rbf(gin.float() + gm.float()).to(dt)
+                    gin = gm if gin is None else self._r(gin.float() + gm.float()).to(dt)
                     gin = self._t(f"{n}.gres", gin)
                     dyd = None
                 else:
@@ -399,27 +417,27 @@ class Bf16TrainOracle:
                     dyd = self._t(f"{n}.dyd", dyd)
                 z1 = self._virt(s["y1"], s["ss1"])
                 self._wgrad(blk.conv2, f"{p}.conv2.weight", z1, dy2)
-                dz1 = self._t(f"{n}.dz1", rbf(self._dgrad(blk.conv2, z1.shape, dy2)).to(dt))
+                dz1 = self._t(f"{n}.dz1", self._r(self._dgrad(blk.conv2, z1.shape, dy2)).to(dt))
                 dy1, _ = self._bn_bwd(blk.bn1, f"{p}.bn1", dz1, s["y1"], s["ss1"], virtual=True)
                 dy1 = self._t(f"{n}.dy1", dy1)
                 self._wgrad(blk.conv1, f"{p}.conv1.weight", s["x"], dy1)
                 dx = self._dgrad(blk.conv1, s["x"].shape, dy1)
-                gin = rbf(dx).to(dt) if gin is None else rbf(dx.float() + gin.float()).to(dt)
+                gin = self._r(dx).to(dt) if gin is None else self._r(dx.float() + gin.float()).to(dt)
                 gin = self._t(f"{n}.gin1", gin)
                 if dyd is not None:
                     self._wgrad(blk.downsample[0], f"{p}.downsample.0.weight", s["x"], dyd)
                     dxd = self._dgrad(blk.downsample[0], s["x"].shape, dyd)
-                    gin = self._t(f"{n}.gin", rbf(dxd.float() + gin.float()).to(dt))
+                    gin = self._t(f"{n}.gin", self._r(dxd.float() + gin.float()).to(dt))
                 g = gin
 
         pl, st = S["pool"], S["stem"]
         Bq, Cq, Hq, Wq = pl["shape"]
         scat = torch.zeros((Bq, Cq, Hq * Wq), dtype=torch.float32)
         scat.scatter_add_(2, pl["idx"].reshape(Bq, Cq, -1), g.float().reshape(Bq, Cq, -1))
-        gf1 = self._t("gf1", rbf(skip_grads[0].float() + scat.reshape(Bq, Cq, Hq, Wq)).to(dt))
+        gf1 = self._t("gf1", self._r(skip_grads[0].float() + scat.reshape(Bq, Cq, Hq, Wq)).to(dt))
         dy, _ = self._bn_bwd(enc.bn1, "encoder.bn1", gf1, st["y"], st["ss"], mask_from=st["z"])
         dy = self._t("stem.dy", dy)
-        xs = rbf(st["x"]) if st["s2d"] else st["x"]
+        xs = self._r(st["x"]) if st["s2d"] else st["x"]
         self.grads["encoder.conv1.weight"] = conv2d_weight(xs.to(dt), enc.conv1.weight.shape, dy.to(dt), stride=2,
                                                            padding=3).float()
         self.saved = None
