@@ -1,9 +1,11 @@
 """The bf16 schedule of the U-Net engine: bf16 activations / weight images, fp32 accumulation, fp32 BatchNorm statistics
 and coefficients (the launches of ``engine_core``), fp32 master parameters and gradients.  ``forward_bf16_eval``,
-``forward_bf16_train`` and ``backward_bf16`` with their units; stem and head run in fp32."""
+``forward_bf16_train`` with their units, and ``backward_bf16``: the bf16 units of the reverse schedule in
+``engine_backward``; stem and head run in fp32."""
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
@@ -350,7 +352,8 @@ class Bf16Schedule:
     # ------------------------------------------------------------------ backward units
     def _bn_bwd_bf16(self, c: ConvSpec, params, grads, bn: BnView, dout, out_act, y, dres=None, dres_acc=False,
                      virtual_act=False, reduced=None):
-        """fp32 twin: _bn_bwd.  reduced = (red, P): the partial sums came out of the kernel that wrote dout"""
+        """virtual_act: the activation was never stored, its ReLU mask is recomputed from y * scale + shift.
+        reduced = (red, P): the partial sums came out of the kernel that wrote dout"""
         Bq, Hq, Wq, Cq = y.shape
         n_pix = Bq * Hq * Wq
         mean, invstd = bn.mean(c), bn.invstd(c)
@@ -388,12 +391,12 @@ class Bf16Schedule:
         if e0 is not None:      # + the fp32 gradient out
             self._pe(e0, "conv_wgrad_bf16_kernel (+ split-K final)", *self._conv_work(desc, 2, 2.0 * c.w_size))
 
-    def _dgrad_bn_bf16(self, c: ConvSpec, dy, B, Hh, Ww, out0, bn_conv: ConvSpec, y, bn: BnView, act=None):
-        """stride-1 data gradient of conv c with the BatchNorm-backward reduction of bn_conv fused (fp32 twin:
-        _dgrad_bn; act = stored block output -> gradient join) -> (red, P)"""
+    def _dgrad_bn_bf16(self, c: ConvSpec, dy, B, H, W, out0, bn_conv: ConvSpec, y, bn: BnView, act=None):
+        """stride-1 data gradient of conv c into out0 with the BatchNorm-backward reduction of bn_conv (the layer whose raw
+        output y has out0's shape) fused; act = stored block output -> the gradient is added to out0 (join) -> (red, P)"""
         Cq = bn_conv.cout
         self.launches["dgrad"].append(c.key)
-        desc = self._desc(B, Hh, Ww, c.cout, 0, 0, Hh, Ww, c.cin, c.k, 1, c.k - 1 - c.pad, 0, 0 if act is None else 1)
+        desc = self._desc(B, H, W, c.cout, 0, 0, H, W, c.cin, c.k, 1, c.k - 1 - c.pad, 0, 0 if act is None else 1)
         P = self.lib.dt_conv2d_bf16_stat_rows(C.byref(desc))
         red = self._buf("bn_red_fused", self.lib.dt_bn_stats_floats(P, Cq), device=dy.device)
         fuse = bn.fuse(bn_conv, y, act)
@@ -418,91 +421,41 @@ class Bf16Schedule:
             desc = self._desc(B, Hin, Win, c.cout, 0, 2, Hin, Win, c.cin, c.k, 1, pad, split, 1 if acc else 0)
         self._conv_bf16(desc, dy, None, c.w(self._wbd[0]), out0, out1, None, None, w_chunked=c.w(self._wbd[1]))
 
-    # ------------------------------------------------------------------ the three decoders, reversed
-    def _backward_unetpp_bf16(self, S, G, params, grads, bn: BnView, B, skip_grads, dev):
-        """reverse of the dense decoder (fp32 twin: _backward_unetpp): blocks in reverse forward order; a node's gradient is
-        the sum over its consumers — as the up-sampled input of the block to its right (accumulating 2x2 sums) and as a
-        slice of the concatenated skip of the blocks further right (accumulating slice copies), one rounding each.
-        G: {node name: gradient so far}, on entry the last node's (the caller lets go of it: it is freed once consumed).
-        Fills skip_grads (gradients of f1..f4) and returns the gradient of f5."""
-        sp = self.spec
+    # ------------------------------------------------------------------ what the shared reverse schedule leaves to bf16
+    def _head_bwd_bf16(self, x, w, dlogits, g, red, B, H, W, cin, K):
+        self._call("dt_head_bwd_bf16", x, w, dlogits, g, red, B, H, W, cin, K)
 
-        def slot(name, shape):
-            t = G.get(name)
-            if t is None:
-                t = G[name] = torch.empty(shape, dtype=_BF, device=dev)
-                return t, 0
-            return t, 1
+    def _upsample_bwd_bf16(self, dup, g, B, h, w, cx):
+        self._call("dt_upsample2x_bwd_bf16", dup, g, B, h, w, cx)
 
-        for blk in reversed(sp.decoder):
-            d = S["P" + blk.name]
-            g = G.pop(blk.name)
-            self._tr(f"P{blk.name}.g", g)
-            Hh, Ww = d["H"], d["W"]
-            dy2 = self._bn_bwd_bf16(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True)
-            self._tr(f"P{blk.name}.dy2", dy2)
-            del g
-            self._wgrad_bf16(blk.conv2, grads, d["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
-            dz1 = torch.empty(d["y1"].shape, dtype=_BF, device=dev)
-            red1 = self._dgrad_bn_bf16(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, d["y1"], bn)
-            del dy2
-            self._tr(f"P{blk.name}.dz1", dz1)
-            dy1 = self._bn_bwd_bf16(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
-            self._tr(f"P{blk.name}.dy1", dy1)
-            del dz1
-            self._wgrad_bf16(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1)
-            cx = blk.in_ch
-            dup = torch.empty((B, Hh, Ww, cx), dtype=_BF, device=dev)
-            dskip = None
-            if d["skip"] is not None:
-                dskip = torch.empty(d["skip"].shape, dtype=_BF, device=dev)
-                self._dgrad_bf16(blk.conv1, dy1, B, Hh, Ww, dup, dskip, split=cx)
-                self._tr(f"P{blk.name}.dskip", dskip)
-            else:
-                self._dgrad_bf16(blk.conv1, dy1, B, Hh, Ww, dup)
-            self._tr(f"P{blk.name}.dup", dup)
-            del dy1
-            glow, acc = slot(blk.low, d["x"].shape)
-            self._call("dt_upsample2x_bwd_acc_bf16", dup, glow, acc, B, Hh // 2, Ww // 2, cx)
-            del dup
-            if dskip is not None:
-                Cw = dskip.shape[-1]
-                for name, (off, Cn) in zip(blk.cat, d["parts"]):
-                    if len(blk.cat) == 1 and name not in G:
-                        G[name] = dskip                      # the skip was the tensor itself: its gradient as is
-                        continue
-                    gm, acc = slot(name, (B, Hh, Ww, Cn))
-                    self._call("dt_channel_slice_bf16", dskip, gm, B * Hh * Ww, Cn, Cw, off, 0, acc)
-            S["P" + blk.name] = None
-        for k in range(1, 5):
-            skip_grads[4 - k] = G[f"f{k}"]      # f_k of the decoder = feats[4 - k]
-            self._tr(f"Pf{k}.g", G[f"f{k}"])
-        self._tr("Pf0.g", G["f0"])
-        return G["f0"]
+    def _fused_input_grad_bf16(self, blk, below, params, bn: BnView, dy1, d, B, Hh, Ww, frozen):
+        """Unet decoder block i >= 1 without a skip (dec4.conv1): data gradient, the 2x2 sums of the up-sampling's backward
+        and the BatchNorm-backward sums of the block `below` = (its conv2, its y2) in one launch of the narrow kernel — no
+        full-resolution gradient tensor -> (g, (red, P), None), or None where the layer is not covered (the generic chain
+        runs)"""
+        c1, cx, lib = blk.conv1, blk.in_ch, self.lib
+        if d["skip"] is not None:
+            return None
+        ddesc = self._desc(B, Hh, Ww, c1.cout, 0, 0, Hh, Ww, c1.cin, c1.k, 1, c1.k - 1 - c1.pad, 0, 0)
+        if not lib.dt_conv2d_bf16_upsampled_dgrad_supported(C.byref(ddesc)):
+            return None
+        self.launches["dgrad"].append(c1.key)
+        P = lib.dt_conv2d_bf16_stat_rows(C.byref(ddesc))
+        red = self._buf("bn_red_up", lib.dt_bn_stats_floats(P, cx), device=dy1.device)
+        g = torch.empty_like(d["x"])
+        ev = self._pb()
+        self._call("dt_conv2d_bf16_upsampled_dgrad", ddesc, dy1, c1.w(self._wbd[0]), g, red, bn.fuse(*below))
+        self._pe(ev, f"conv3x3_bf16_narrow_kernel<{c1.cout // 16}, {c1.cin // 16}, false, true, true>",
+                 2.0 * 9 * c1.cin * c1.cout * Hh * Ww * B, 2.0 * B * (Hh * Ww * c1.cout + (Hh // 2) * (Ww // 2) * cx * 2))
+        return g, (red, P), None
 
-    def _backward_resunet_block_bf16(self, i, blk, d, g, params, grads, bn: BnView, B, skip_grads):
-        """reverse of one ResUnet block (fp32 twin: _backward_resunet_block): g = gradient of the block output -> the
-        gradient of the block's low-resolution input; writes the skip gradient"""
-        lib, dev = self.lib, g.device
-        Hh, Ww = d["H"], d["W"]
+    def _resunet_join_bwd_bf16(self, i, blk, d, g, dy1, B, Hh, Ww, skip_grads):
+        """tail of a reversed ResUnet block: dy1 (one-element list, emptied here) and g through conv1 and the identity
+        convolution; the two branches' parts are added at full resolution (one rounding), then one up-sample backward"""
+        dy1, dev = dy1.pop(), g.device
         ic, cx = blk.idc, blk.in_ch
         sk = 0 if d["skip"] is None else d["skip"].shape[-1]
         n_pix = B * Hh * Ww
-        self._wgrad_bf16(ic, grads, d["x"], d["skip"], 1, B, Hh, Ww, g)     # identity branch: dW over the virtual input
-        cws = self._buf("chsum_ws", int(lib.dt_channel_sums_bf16_workspace(n_pix, ic.cout)), device=dev)
-        self._call("dt_channel_sums_bf16", g, cws, n_pix, ic.cout, ic.bias(grads))      # its bias gradient = sum g
-        # main branch: both activations virtual
-        dy2 = self._bn_bwd_bf16(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True)
-        self._tr(f"D{i}.dy2", dy2)
-        self._wgrad_bf16(blk.conv2, grads, d["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
-        dz1 = torch.empty(d["y1"].shape, dtype=_BF, device=dev)
-        red1 = self._dgrad_bn_bf16(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, d["y1"], bn)
-        del dy2
-        self._tr(f"D{i}.dz1", dz1)
-        dy1 = self._bn_bwd_bf16(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
-        self._tr(f"D{i}.dy1", dy1)
-        del dz1
-        self._wgrad_bf16(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1)
         dup = torch.empty((B, Hh, Ww, cx), dtype=_BF, device=dev)
         dup_id = torch.empty((B, Hh, Ww, cx), dtype=_BF, device=dev)
         one = self._const_vec(1.0, max(cx, sk, 8), dev)
@@ -530,195 +483,13 @@ class Bf16Schedule:
         self._tr(f"D{i}.g", gx)
         return gx
 
-    def _backward_unet_block_bf16(self, i, S, g, g_red, params, grads, bn: BnView, B, frozen, skip_grads):
-        """reverse of one smp Unet decoder block: g = gradient of its (possibly virtual) output activation, g_red the
-        BatchNorm-backward sums that came with it -> (gradient of the block below's activation, its sums or None)"""
-        sp, lib, dev = self.spec, self.lib, g.device
-        blk, d = sp.decoder[i], S[f"D{i}"]
-        Hh, Ww = d["H"], d["W"]
-        # the ReLU mask is recomputed from y2 * scale + shift even where z2 was stored (same arithmetic as bn_act:
-        # identical mask, one tensor less to read in the reduce / apply passes)
-        dy2 = self._bn_bwd_bf16(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True, reduced=g_red)
-        self._tr(f"D{i}.dy2", dy2)
-        if d.get("z1") is not None:
-            self._wgrad_bf16(blk.conv2, grads, d["z1"], None, 0, B, Hh, Ww, dy2)
-        else:
-            self._wgrad_bf16(blk.conv2, grads, d["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
-        dz1 = torch.empty(d["y1"].shape, dtype=_BF, device=dev)
-        red1 = self._dgrad_bn_bf16(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, d["y1"], bn)
-        del dy2
-        self._tr(f"D{i}.dz1", dz1)
-        dy1 = self._bn_bwd_bf16(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
-        self._tr(f"D{i}.dy1", dy1)
-        del dz1
-        x_ss = bn.ss(sp.decoder[i - 1].conv2) if d["x_virtual"] else None
-        self._wgrad_bf16(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1, in_ss=x_ss)
-        cx = blk.in_ch
-        if frozen and i == 0:      # block 0's input and skip are encoder features: no data gradient at all
-            return g, g_red
-        # the new g is the gradient of relu(bn(y2)) of block i-1 (also where z2 was stored: the mask is recomputed from
-        # y2 * scale + shift either way): that block's BatchNorm-backward sums ride in the pass that writes it
-        below = bn.fuse(sp.decoder[i - 1].conv2, S[f"D{i - 1}"]["y2"]) if i >= 1 else None
-        if d["skip"] is None and i >= 1:
-            # dec4.conv1: data gradient, the 2x2 sums of the up-sampling's backward and the BatchNorm-backward sums of
-            # the block below in one launch of the narrow kernel — no full-resolution gradient tensor
-            c1 = blk.conv1
-            ddesc = self._desc(B, Hh, Ww, c1.cout, 0, 0, Hh, Ww, c1.cin, c1.k, 1, c1.k - 1 - c1.pad, 0, 0)
-            if lib.dt_conv2d_bf16_upsampled_dgrad_supported(C.byref(ddesc)):
-                self.launches["dgrad"].append(c1.key)
-                P = lib.dt_conv2d_bf16_stat_rows(C.byref(ddesc))
-                red = self._buf("bn_red_up", lib.dt_bn_stats_floats(P, cx), device=dev)
-                g = torch.empty(d["x"].shape, dtype=_BF, device=dev)
-                ev = self._pb()
-                self._call("dt_conv2d_bf16_upsampled_dgrad", ddesc, dy1, c1.w(self._wbd[0]), g, red, below)
-                self._pe(ev, f"conv3x3_bf16_narrow_kernel<{c1.cout // 16}, {c1.cin // 16}, false, true, true>",
-                         2.0 * 9 * c1.cin * c1.cout * Hh * Ww * B,
-                         2.0 * B * (Hh * Ww * c1.cout + (Hh // 2) * (Ww // 2) * cx * 2))
-                del dy1
-                self._tr(f"D{i}.g", g)
-                return g, (red, P)
-        dup = torch.empty((B, Hh, Ww, cx), dtype=_BF, device=dev)
-        if d["skip"] is not None:
-            # (frozen encoder: the split kernel still writes the skip's part, to a tensor nobody reads)
-            dskip = torch.empty(d["skip"].shape, dtype=_BF, device=dev)
-            self._dgrad_bf16(blk.conv1, dy1, B, Hh, Ww, dup, dskip, split=cx)
-            skip_grads[3 - i] = None if frozen else dskip
-            self._tr(f"D{i}.dskip", dskip)
-        else:
-            self._dgrad_bf16(blk.conv1, dy1, B, Hh, Ww, dup)
-        self._tr(f"D{i}.dup", dup)
-        del dy1
-        g = torch.empty(d["x"].shape, dtype=_BF, device=dev)
-        g_red = None
-        if i >= 1:
-            P = lib.dt_upsample2x_bwd_bn_bf16_rows(B, Hh // 2, Ww // 2, cx)
-            red = self._buf("bn_red_up", lib.dt_bn_stats_floats(P, cx), device=dev)
-            self._call("dt_upsample2x_bwd_bn_bf16", dup, g, below, red, B, Hh // 2, Ww // 2, cx)
-            g_red = (red, P)
-        else:
-            self._call("dt_upsample2x_bwd_bf16", dup, g, B, Hh // 2, Ww // 2, cx)
-        del dup
-        self._tr(f"D{i}.g", g)
-        return g, g_red
-
     # ------------------------------------------------------------------ backward
     def backward_bf16(self, dlogits: torch.Tensor, params: torch.Tensor, grads: torch.Tensor,
                       saved: Optional[_Saved] = None):
-        """reverse pass of forward_bf16_train: bf16 activation gradients, fp32 parameter gradients"""
-        sp, lib = self.spec, self.lib
-        S = self._saved_of(saved)
-        B, bn = S["B"], BnView(sp, S["bnws"])
-        frozen = bool(S.get("enc_frozen", False))
-        self.launches = {"dgrad": [], "wgrad": []}
-        dev = dlogits.device
+        """reverse pass of forward_bf16_train (``engine_backward``): bf16 activation gradients, fp32 parameter gradients"""
+        self._saved_of(saved)      # no saved forward: refused before anything is launched
         self._wbd = (self._bf16_weights(params, dgrad=True), self._bf16_weights(params, dgrad=True, chunked=True))
-
-        # ---- head (fp32) -> bf16 gradient of the last decoder activation
-        hd, hsv = sp.head, S["head"]
-        H, W, K = hsv["H"], hsv["W"], sp.head.cout
-        g = torch.empty(hsv["x"].shape, dtype=_BF, device=dev)
-        P = lib.dt_head_bwd_rows(B, H, W)
-        red = self._buf("head_red", lib.dt_head_bwd_red_floats(B, H, W, hd.cin, K), device=dev)
-        self._call("dt_head_bwd_bf16", hsv["x"], hd.w(params), dlogits.contiguous(), g, red, B, H, W, hd.cin, K)
-        self._call("dt_head_bwd_finalize", red, P, hd.w(grads), hd.bias(grads), hd.cin, K)
-        self._tr("head.g", g)
-
-        skip_grads = [None] * 5
-        g_red = None
-        self._head_tap_fix(grads)
-        if sp.decoder_kind == "unetplusplus":
-            G = {sp.decoder[-1].name: g}
-            del g
-            g = self._backward_unetpp_bf16(S, G, params, grads, bn, B, skip_grads, dev)
-            del G
-        for i in (range(4, -1, -1) if sp.decoder_kind != "unetplusplus" else ()):
-            if sp.decoder_kind == "resunet":
-                g = self._backward_resunet_block_bf16(i, sp.decoder[i], S[f"D{i}"], g, params, grads, bn, B, skip_grads)
-            else:
-                g, g_red = self._backward_unet_block_bf16(i, S, g, g_red, params, grads, bn, B, frozen, skip_grads)
-            S[f"D{i}"] = None
-        self._bucket_done(sp.buckets[0])
-        if frozen:      # frozen encoder weights: backward stops at the decoder (no encoder data / weight gradient)
-            self._join_side()
-            self.saved = None
-            return
-
-        for li in (3, 2, 1, 0):
-            blocks = sp.layers[li]
-            for bi in range(len(blocks) - 1, -1, -1):
-                blk, r = blocks[bi], S[f"L{li}B{bi}"]
-                Hin, Win, Hh, Ww = r["Hin"], r["Win"], r["H"], r["W"]
-                gin, gin_has = None, False
-                if bi == 0 and li > 0 and skip_grads[li] is not None:
-                    gin, gin_has = skip_grads[li], True
-                if gin is None:
-                    gin = torch.empty(r["x"].shape, dtype=_BF, device=dev)
-                if blk.down is None:
-                    dy2 = self._bn_bwd_bf16(blk.conv2, params, grads, bn, g, r["out"], r["y2"], dres=gin, dres_acc=gin_has,
-                                            reduced=g_red)
-                    gin_has = True
-                    dyd = None
-                    self._tr(f"L{li}B{bi}.gres", gin)
-                else:
-                    gd = torch.empty(r["out"].shape, dtype=_BF, device=dev)
-                    dy2 = self._bn_bwd_bf16(blk.conv2, params, grads, bn, g, r["out"], r["y2"], dres=gd, reduced=g_red)
-                    dyd = self._bn_bwd_bf16(blk.down, params, grads, bn, gd, None, r["yd"])
-                    self._tr(f"L{li}B{bi}.gres", gd)
-                    self._tr(f"L{li}B{bi}.dyd", dyd)
-                    del gd
-                self._tr(f"L{li}B{bi}.dy2", dy2)
-                if r.get("z1") is not None:
-                    self._wgrad_bf16(blk.conv2, grads, r["z1"], None, 0, B, Hh, Ww, dy2)
-                else:
-                    self._wgrad_bf16(blk.conv2, grads, r["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
-                dz1 = torch.empty(r["y1"].shape, dtype=_BF, device=dev)
-                red1 = self._dgrad_bn_bf16(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, r["y1"], bn)
-                del dy2
-                self._tr(f"L{li}B{bi}.dz1", dz1)
-                dy1 = self._bn_bwd_bf16(blk.conv1, params, grads, bn, dz1, None, r["y1"], virtual_act=True, reduced=red1)
-                self._tr(f"L{li}B{bi}.dy1", dy1)
-                del dz1
-                self._wgrad_bf16(blk.conv1, grads, r["x"], None, 0, B, Hin, Win, dy1)
-                g_red = None
-                if bi > 0 and blk.down is None and gin_has:
-                    # last writer of block bi-1's output gradient: its bn2 reduction (mask: stored output) rides along
-                    rp = S[f"L{li}B{bi - 1}"]
-                    g_red = self._dgrad_bn_bf16(blk.conv1, dy1, B, Hin, Win, gin, blocks[bi - 1].conv2, rp["y2"], bn,
-                                                act=rp["out"])
-                else:
-                    self._dgrad_bf16(blk.conv1, dy1, B, Hin, Win, gin, acc=gin_has)
-                gin_has = True
-                del dy1
-                self._tr(f"L{li}B{bi}.gin1", gin)
-                if dyd is not None:
-                    self._wgrad_bf16(blk.down, grads, r["x"], None, 0, B, Hin, Win, dyd)
-                    self._dgrad_bf16(blk.down, dyd, B, Hin, Win, gin, acc=True)
-                    del dyd
-                    self._tr(f"L{li}B{bi}.gin", gin)
-                g = gin
-                S[f"L{li}B{bi}"] = None
-            if li > 0:
-                self._bucket_done(sp.buckets[4 - li])
-
-        pl, stem = S["pool"], S["stem"]
-        gf1 = skip_grads[0]
-        stem_red = None
-        P = lib.dt_maxpool3x3s2_bwd_bn_bf16_rows(B, pl["H"], pl["W"], 64) if self._fuse_pool_bn else 0
-        if P > 0:      # even maps: the stem's BatchNorm-backward sums ride in the pass that writes its activation gradient
-            red = self._buf("bn_red_pool", lib.dt_bn_stats_floats(P, 64), device=dev)
-            self._call("dt_maxpool3x3s2_bwd_bn_bf16", g, pl["amax"], gf1, 1, bn.fuse(sp.stem, stem["y"]), red, B, pl["H"],
-                       pl["W"], 64)
-            stem_red = (red, P)
-        else:
-            self._call("dt_maxpool3x3s2_bwd_bf16", g, pl["amax"], gf1, 1, B, pl["H"], pl["W"], 64)
-        self._tr("gf1", gf1)
-        dy = self._bn_bwd_bf16(sp.stem, params, grads, bn, gf1, None, stem["y"], virtual_act=True, reduced=stem_red)
-        self._tr("stem.dy", dy)
-        self._stem_wgrad_bf16(stem, dy, grads, B)
-        self._join_side()
-        if self.grad_hook:
-            self.grad_hook(*sp.buckets[4])
-        self.saved = None
+        self._backward(BF16_UNITS, dlogits, params, grads, saved)
 
     def _stem_wgrad_bf16(self, stem, dy, grads, B):
         stc, lib, dev = self.spec.stem, self.lib, dy.device
@@ -738,3 +509,18 @@ class Bf16Schedule:
             nbytes = lib.dt_conv2d_wgrad_workspace(C.byref(sdesc))
             ws = self._buf("wgrad_ws", nbytes // 4, device=dev)
             self._call("dt_conv2d_wgrad_stem_dy_bf16", sdesc, stem["x"], dy, stc.w(grads), ws, ws.numel() * 4)
+
+
+# the bf16 units of the shared reverse schedule: plain functions of the engine (no engine holds, or is held by, this object)
+BF16_UNITS = SimpleNamespace(
+    dtype=_BF,
+    bn_bwd=Bf16Schedule._bn_bwd_bf16, wgrad=Bf16Schedule._wgrad_bf16, dgrad=Bf16Schedule._dgrad_bf16,
+    dgrad_bn=Bf16Schedule._dgrad_bn_bf16, head_bwd=Bf16Schedule._head_bwd_bf16, upsample_bwd=Bf16Schedule._upsample_bwd_bf16,
+    stem_wgrad=Bf16Schedule._stem_wgrad_bf16, fused_input_grad=Bf16Schedule._fused_input_grad_bf16,
+    resunet_join=Bf16Schedule._resunet_join_bwd_bf16,
+    upsample_bwd_acc="dt_upsample2x_bwd_acc_bf16", upsample_bwd_bn="dt_upsample2x_bwd_bn_bf16",
+    channel_sums="dt_channel_sums_bf16", channel_slice="dt_channel_slice_bf16", maxpool_bwd="dt_maxpool3x3s2_bwd_bf16",
+    maxpool_bwd_bn="dt_maxpool3x3s2_bwd_bn_bf16",
+    # BatchNorm-backward sums in the epilogue of: conv2's data gradient / the up-sampling's backward; the encoder's gradient
+    # join; the max-pool backward
+    fuse_bn=lambda eng: True, fuse_join=lambda eng: True, fuse_pool=lambda eng: eng._fuse_pool_bn)

@@ -1,8 +1,10 @@
-"""The fp32 schedule of the U-Net engine: ``forward`` / ``backward`` and their units (convolution + BatchNorm statistics,
-the fused inference forms, BatchNorm backward, weight / data gradients), the Unet++ and ResUnet halves."""
+"""The fp32 schedule of the U-Net engine: ``forward`` and its units (convolution + BatchNorm statistics, the fused inference
+forms, the Unet++ / EfficientUnet++ decoders); ``backward``: the fp32 units (BatchNorm backward, weight / data gradients,
+the fused input gradients) of the reverse schedule in ``engine_backward``."""
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
@@ -528,16 +530,16 @@ class Fp32Schedule:
             self._pe(e0, name, *self._conv_work(desc, extra_bytes=(4.0 if act is None else 8.0) * out0.numel()))
         return red, P
 
-    def _upsampled_dgrad(self, blk, prev_conv: ConvSpec, params, bn: BnView, dy1, y2p, d, B, Hh, Ww) -> bool:
+    def _upsampled_dgrad(self, blk, prev_conv: ConvSpec, params, bn: BnView, dy1, y2p, d, B, Hh, Ww):
         """decoder block without a skip: gradient of the block input (low resolution) straight from dy1 — the data
         gradient of conv1 and the backward of the nearest x2 upsample in one sub-pixel kernel, the BatchNorm-backward
-        sums of the previous block's conv2 in its epilogue.  Fills d["g"], d["g_red"]; False where the layer shape is
-        not covered (the generic chain runs)."""
+        sums of the previous block's conv2 in its epilogue.  -> (g, (red, P), None), or None where the layer shape is
+        not covered"""
         c = blk.conv1
         cx = blk.in_ch
         desc = self._desc(B, Hh, Ww, cx, 0, 1, Hh, Ww, c.cout, c.k, c.stride, c.pad, 0, 0)
         if not self.lib.dt_conv2d_upsampled_dgrad_supported(C.byref(desc)):
-            return False
+            return None
         self.launches["dgrad"].append(c.key)
         P = self.lib.dt_conv2d_upsampled_dgrad_rows(C.byref(desc))
         red = self._buf("bn_red_up", self.lib.dt_bn_stats_floats(P, cx), device=dy1.device)
@@ -547,8 +549,7 @@ class Fp32Schedule:
         self._call("dt_conv2d_upsampled_dgrad", desc, dy1, c.w(params), g, red, fuse)
         self._pe(ev, "conv3x3_f32_upc_dgrad_kernel", 2.0 * 9 * cx * c.cout * Hh * Ww * B,
                  4.0 * B * Hh * Ww * c.cout + 4.0 * B * (Hh // 2) * (Ww // 2) * cx * 2)
-        d["g"], d["g_red"] = g, (red, P)
-        return True
+        return g, (red, P), None
 
     def _wino_upsampled_dgrad(self, blk, prev_conv: ConvSpec, bn: BnView, dy1, y2p, d, B, Hh, Ww, x_only: bool):
         """decoder blocks 1-3: the Winograd data gradient of conv1 with the up-sampling's backward (2x2 sums) and the
@@ -578,7 +579,7 @@ class Fp32Schedule:
                      4.0 * B * Hh * Ww * (c1.cout + (c1.cin - cx)) + 4.0 * B * (Hh // 2) * (Ww // 2) * cx * 2)
         return g, (red, P), dskip
 
-    def _dgrad(self, c: ConvSpec, params, dy, B, Hin, Win, out0, out1=None, split=0, acc=False):
+    def _dgrad(self, c: ConvSpec, dy, B, Hin, Win, out0, out1=None, split=0, acc=False):
         """gradient wrt the conv's logical input [B,Hin,Win,cin] (before virtual upsample handling)."""
         self.launches["dgrad"].append(c.key)
         Ho, Wo = dy.shape[1], dy.shape[2]
@@ -591,110 +592,52 @@ class Fp32Schedule:
             desc = self._desc(B, Hin, Win, c.cout, 0, 2, Hin, Win, c.cin, c.k, 1, pad, split, 1 if acc else 0)
         self._conv(desc, dy, None, wd, out0, out1, None, u=self._u(c, dgrad=True) if c.stride == 1 else None)
 
-    def _backward_unetpp(self, S, g_head, params, grads, bn: BnView, B, skip_grads):
-        """reverse of _forward_unetpp: the blocks in reverse forward order (every consumer of a node comes before the
-        node); a node's gradient is the sum over its consumers — as the upsampled input of the block to its right
-        (dt_upsample2x_bwd, accumulating) and as a slice of the concatenated skip of the blocks further right
-        (dt_channel_slice, accumulating).  Fills skip_grads (gradients of f1..f4) and returns the gradient of f5."""
-        sp = self.spec
-        G = {sp.decoder[-1].name: g_head}
+    # ------------------------------------------------------------------ what the shared reverse schedule leaves to fp32
+    def _head_bwd(self, x, w, dlogits, g, red, B, H, W, cin, K):
+        e0 = self._pb()
+        self._call("dt_head_bwd", x, w, dlogits, g, red, B, H, W, cin, K)
+        self._pe(e0, "head_bwd_kernel", 4.0 * 9 * cin * K * B * H * W, 4.0 * B * H * W * (2 * cin + K))
 
-        def slot(name, shape, dev):
-            t = G.get(name)
-            if t is None:
-                t = G[name] = torch.empty(shape, dtype=torch.float32, device=dev)
-                return t, 0
-            return t, 1
+    def _upsample_bwd(self, dup, g, B, h, w, cx):
+        self._call("dt_upsample2x_bwd", dup, g, 0, B, h, w, cx)
 
-        for blk in reversed(sp.decoder):
-            d = S["P" + blk.name]
-            g = G.pop(blk.name)
-            self._tr(f"P{blk.name}.g", g)
-            dev = g.device
-            Hh, Ww = d["H"], d["W"]
-            dy2 = self._bn_bwd(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True)
-            self._tr(f"P{blk.name}.dy2", dy2)
-            del g
-            self._wgrad(blk.conv2, grads, d["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
-            dz1 = torch.empty_like(d["y1"])
-            if self._fuse_bn:
-                red1 = self._dgrad_bn(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, d["y1"], bn)
-            else:
-                red1 = self._dgrad(blk.conv2, params, dy2, B, Hh, Ww, dz1)
-            del dy2
-            self._tr(f"P{blk.name}.dz1", dz1)
-            dy1 = self._bn_bwd(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
-            self._tr(f"P{blk.name}.dy1", dy1)
-            del dz1
-            self._wgrad(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1)
-            cx = blk.in_ch
-            dup = torch.empty((B, Hh, Ww, cx), dtype=torch.float32, device=dev)
-            dskip = None
-            if d["skip"] is not None:
-                dskip = torch.empty_like(d["skip"])
-                self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup, dskip, split=cx)
-                self._tr(f"P{blk.name}.dskip", dskip)
-            else:
-                self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup)
-            self._tr(f"P{blk.name}.dup", dup)
-            del dy1
-            glow, acc = slot(blk.low, d["x"].shape, dev)
-            self._call("dt_upsample2x_bwd", dup, glow, acc, B, Hh // 2, Ww // 2, cx)
-            del dup
-            if dskip is not None:
-                Cw = dskip.shape[-1]
-                for name, (off, Cn) in zip(blk.cat, d["parts"]):
-                    if len(blk.cat) == 1 and name not in G:
-                        G[name] = dskip                      # the skip was the tensor itself: its gradient as is
-                        continue
-                    gm, acc = slot(name, (B, Hh, Ww, Cn), dev)
-                    self._call("dt_channel_slice", dskip, gm, B * Hh * Ww, Cn, Cw, off, 0, acc)
-            S["P" + blk.name] = None
-        for k in range(1, 5):
-            skip_grads[4 - k] = G[f"f{k}"]      # f_k of the decoder = feats[4 - k]
-            self._tr(f"Pf{k}.g", G[f"f{k}"])
-        self._tr("Pf0.g", G["f0"])
-        return G["f0"]
+    def _fused_input_grad(self, blk, below, params, bn: BnView, dy1, d, B, Hh, Ww, frozen):
+        """Unet decoder block i >= 1: the gradient of the block input from ONE kernel that carries the up-sampling's
+        backward and the BatchNorm-backward sums of the block `below` = (its conv2, its y2) in its epilogue -> (g, (red, P),
+        dskip | None), or None where no such form covers the layer (the generic chain runs)"""
+        if not self._fuse_bn:
+            return None
+        if d["skip"] is None:
+            return self._upsampled_dgrad(blk, below[0], params, bn, dy1, below[1], d, B, Hh, Ww)
+        if not self.winograd:
+            return None
+        # frozen encoder: the form that leaves the skip's gradient out, else (or where it does not apply) the full one
+        got = self._wino_upsampled_dgrad(blk, below[0], bn, dy1, below[1], d, B, Hh, Ww, x_only=True) if frozen else None
+        if got is None:
+            got = self._wino_upsampled_dgrad(blk, below[0], bn, dy1, below[1], d, B, Hh, Ww, x_only=False)
+        return got
 
-    def _backward_resunet_block(self, i, blk, d, g, params, grads, bn: BnView, B, Hh, Ww, skip_grads, skip_slot):
-        """reverse of one ResUnet decoder block (forward: see the decoder loop): g = gradient of the block output
-        [B,Hh,Ww,cout] -> returns the gradient of the block's low-resolution input; writes the skip gradient."""
-        lib, dev = self.lib, g.device
+    def _resunet_join(self, i, blk, d, g, dy1, B, Hh, Ww, skip_grads):
+        """tail of a reversed ResUnet block: dy1 (one-element list, emptied here) and g through conv1 and the identity
+        convolution; the two branches' up-sampled parts meet in two accumulating up-sample backwards"""
+        dy1, dev = dy1.pop(), g.device
         ic, cx = blk.idc, blk.in_ch
         sk = 0 if d["skip"] is None else d["skip"].shape[-1]
-        n_pix = B * Hh * Ww
-        # identity branch: weight gradient over the virtual (up-sampled + concatenated) input, bias gradient = sum g
-        self._wgrad(ic, grads, d["x"], d["skip"], 1, B, Hh, Ww, g)
-        ws = self._buf("chsum_ws", int(lib.dt_channel_sums_workspace(n_pix, ic.cout)), device=dev)
-        self._call("dt_channel_sums", g, ws, n_pix, ic.cout, ic.bias(grads))
-        # main branch: relu(bn2(conv2(relu(bn1(conv1(xin))))))  (both activations virtual: masks from y*scale+shift)
-        dy2 = self._bn_bwd(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True)
-        self._tr(f"D{i}.dy2", dy2)
-        self._wgrad(blk.conv2, grads, d["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
-        dz1 = torch.empty_like(d["y1"])
-        red1 = self._dgrad_bn(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, d["y1"], bn) if self._fuse_bn else \
-            self._dgrad(blk.conv2, params, dy2, B, Hh, Ww, dz1)
-        del dy2
-        self._tr(f"D{i}.dz1", dz1)
-        dy1 = self._bn_bwd(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
-        self._tr(f"D{i}.dy1", dy1)
-        del dz1
-        self._wgrad(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1)
         dup = torch.empty((B, Hh, Ww, cx), dtype=torch.float32, device=dev)
         dup_id = torch.empty_like(dup)
         if sk:
             dskip, dskip_id = torch.empty_like(d["skip"]), torch.empty_like(d["skip"])
-            self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup, dskip, split=cx)
-            self._dgrad(ic, params, g, B, Hh, Ww, dup_id, dskip_id, split=cx)
+            self._dgrad(blk.conv1, dy1, B, Hh, Ww, dup, dskip, split=cx)
+            self._dgrad(ic, g, B, Hh, Ww, dup_id, dskip_id, split=cx)
             # dskip += dskip_id (the split data-gradient kernels accumulate into their first output only)
             one, zero = self._const_vec(1.0, sk, dev), self._const_vec(0.0, sk, dev)
             self._bn_act(dskip, (one, zero), res=dskip_id, relu=0, out=dskip)
-            skip_grads[skip_slot] = dskip
+            skip_grads[3 - i] = dskip
             self._tr(f"D{i}.dskip", dskip)
             del dskip_id
         else:
-            self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup)
-            self._dgrad(ic, params, g, B, Hh, Ww, dup_id)
+            self._dgrad(blk.conv1, dy1, B, Hh, Ww, dup)
+            self._dgrad(ic, g, B, Hh, Ww, dup_id)
         del dy1
         gx = torch.empty_like(d["x"])
         self._call("dt_upsample2x_bwd", dup, gx, 0, B, Hh // 2, Ww // 2, cx)
@@ -702,215 +645,31 @@ class Fp32Schedule:
         self._tr(f"D{i}.g", gx)      # (the two branches' up-sampled parts are never summed at full resolution: no D{i}.dup)
         return gx
 
+    def _stem_wgrad(self, stem, dy, grads, B):
+        self._wgrad(self.spec.stem, grads, stem["x"], None, 0, B, stem["Hin"], stem["Win"], dy)
+
     # ------------------------------------------------------------------ backward
     def backward(self, dlogits: torch.Tensor, params: torch.Tensor, grads: torch.Tensor, saved: Optional[_Saved] = None):
-        """Hand-scheduled reverse pass.  Writes every parameter gradient into ``grads`` (flat, same layout
-        as ``params``) and calls ``grad_hook(name, lo, hi)`` as each bucket of the flat buffer completes.
+        """Hand-scheduled reverse pass (``engine_backward``).  Writes every parameter gradient into ``grads`` (flat, same
+        layout as ``params``) and calls ``grad_hook(name, lo, hi)`` as each bucket of the flat buffer completes.
         ``saved``: the activations of the forward pass this gradient belongs to (default: the engine's last one)."""
-        sp, lib = self.spec, self.lib
-        S = self._saved_of(saved)
-        self._bwd_training = bool(S.get("training", True))
-        self._bwd_enc_training = bool(S.get("enc_training", self._bwd_training))
-        frozen = bool(S.get("enc_frozen", False))
-        self.launches = {"dgrad": [], "wgrad": []}
-        B = S["B"]
-        bn = BnView(sp, S["bnws"])
-        dev = dlogits.device
-        dlogits = dlogits.contiguous()
+        self._saved_of(saved)      # no saved forward: refused before anything is launched
         # data-gradient weight images of every layer ([tap'][co][ci], taps reversed) in one launch
-        self._wd_all = self._buf("wd_all", sp.n_params, device=dev)
+        self._wd_all = self._buf("wd_all", self.spec.n_params, device=dlogits.device)
         self._weight_images(params, self._wd_all, 0)
         self._ud_all = self._wino_images(self._wd_all, "wino_ud", True) if self.winograd else None
+        self._backward(FP32_UNITS, dlogits, params, grads, saved)
 
-        # ---- head
-        hd = sp.head
-        h = S["head"]
-        H, W = h["H"], h["W"]
-        K = hd.cout
-        g = torch.empty_like(h["x"])
-        P = lib.dt_head_bwd_rows(B, H, W)
-        red = self._buf("head_red", lib.dt_head_bwd_red_floats(B, H, W, hd.cin, K), device=dev)
-        e0 = self._pb()
-        self._call("dt_head_bwd", h["x"], hd.w(params), dlogits, g, red, B, H, W, hd.cin, K)
-        self._pe(e0, "head_bwd_kernel", 4.0 * 9 * hd.cin * K * B * H * W, 4.0 * B * H * W * (2 * hd.cin + K))
-        self._call("dt_head_bwd_finalize", red, P, hd.w(grads), hd.bias(grads), hd.cin, K)
-        self._tr("head.g", g)
 
-        # ---- decoder (reverse)
-        skip_grads = [None] * 5  # gradient of feats[0..4] = f1..f5
-        g_red = None             # BatchNorm-backward partial sums that already came with g (fused producers)
-        self._head_tap_fix(grads)
-        if sp.decoder_kind == "unetplusplus":
-            g = self._backward_unetpp(S, g, params, grads, bn, B, skip_grads)
-        for i in (range(4, -1, -1) if sp.decoder_kind != "unetplusplus" else ()):
-            blk = sp.decoder[i]
-            d = S[f"D{i}"]
-            Hh, Ww = d["H"], d["W"]
-            if sp.decoder_kind == "resunet":
-                g = self._backward_resunet_block(i, blk, d, g, params, grads, bn, B, Hh, Ww, skip_grads, 3 - i)
-                S[f"D{i}"] = None
-                continue
-            # conv2 + BN + ReLU (activation stored only for the last block)
-            # mask recomputed from y2 * scale + shift even where z2 was stored (identical to bn_act's; one read less)
-            dy2 = self._bn_bwd(blk.conv2, params, grads, bn, g, None, d["y2"], virtual_act=True, reduced=g_red)
-            self._tr(f"D{i}.dy2", dy2)
-            if d.get("z1") is not None:
-                self._wgrad(blk.conv2, grads, d["z1"], None, 0, B, Hh, Ww, dy2)
-            else:
-                self._wgrad(blk.conv2, grads, d["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
-            dz1 = torch.empty_like(d["y1"])
-            if self._fuse_bn:
-                red1 = self._dgrad_bn(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, d["y1"], bn)
-            else:
-                red1 = self._dgrad(blk.conv2, params, dy2, B, Hh, Ww, dz1)
-            del dy2
-            self._tr(f"D{i}.dz1", dz1)
-            dy1 = self._bn_bwd(blk.conv1, params, grads, bn, dz1, None, d["y1"], virtual_act=True, reduced=red1)
-            self._tr(f"D{i}.dy1", dy1)
-            del dz1
-            x_ss = bn.ss(sp.decoder[i - 1].conv2) if d["x_virtual"] else None
-            self._wgrad(blk.conv1, grads, d["x"], d["skip"], 1, B, Hh, Ww, dy1, in_ss=x_ss)
-            cx = blk.in_ch
-            if frozen and i == 0:      # block 0's input and skip are encoder features: no data gradient at all
-                del dy1
-                S[f"D{i}"] = None
-                continue
-            # g becomes the gradient of relu(bn(y2)) of decoder block i-1 (never stored)
-            below = (sp.decoder[i - 1].conv2, S[f"D{i - 1}"]["y2"]) if i >= 1 else None
-            if d["skip"] is None and i >= 1 and self._fuse_bn and self._upsampled_dgrad(blk, below[0], params, bn, dy1,
-                                                                                       below[1], d, B, Hh, Ww):
-                g, g_red = d["g"], d["g_red"]
-                self._tr(f"D{i}.g", g)
-                del dy1
-                S[f"D{i}"] = None
-                continue
-            if d["skip"] is not None and i >= 1 and self._fuse_bn and self.winograd:
-                # frozen encoder: the form that leaves the skip's gradient out, else (or where it does not apply) the full one
-                got = self._wino_upsampled_dgrad(blk, below[0], bn, dy1, below[1], d, B, Hh, Ww, x_only=True) if frozen else None
-                if got is None:
-                    got = self._wino_upsampled_dgrad(blk, below[0], bn, dy1, below[1], d, B, Hh, Ww, x_only=False)
-                if got is not None:
-                    g, g_red, dskip = got
-                    if dskip is not None:
-                        skip_grads[3 - i] = dskip
-                    self._tr(f"D{i}.dskip", dskip)
-                    self._tr(f"D{i}.g", g)
-                    del dy1
-                    S[f"D{i}"] = None
-                    continue
-            dup = torch.empty((B, Hh, Ww, cx), dtype=torch.float32, device=dev)
-            if d["skip"] is not None:
-                # (frozen encoder without the Winograd form: the split kernel writes the skip's part to a scratch tensor)
-                dskip = torch.empty_like(d["skip"])
-                self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup, dskip, split=cx)
-                skip_grads[3 - i] = None if frozen else dskip
-                self._tr(f"D{i}.dskip", dskip)
-            else:
-                self._dgrad(blk.conv1, params, dy1, B, Hh, Ww, dup)
-            self._tr(f"D{i}.dup", dup)
-            del dy1
-            g = torch.empty_like(d["x"])
-            g_red = None
-            if i >= 1 and self._fuse_bn:     # also where z2 was stored (DT_MATERIALIZE_Z2): the mask is recomputed from y2
-                # the BatchNorm-backward reduction of the block below rides along in the pass that writes g
-                P = lib.dt_upsample2x_bwd_bn_rows(B, Hh // 2, Ww // 2, cx)
-                red = self._buf("bn_red_up", lib.dt_bn_stats_floats(P, cx), device=dev)
-                self._call("dt_upsample2x_bwd_bn", dup, g, bn.fuse(*below), red, B, Hh // 2, Ww // 2, cx)
-                g_red = (red, P)
-            else:
-                self._call("dt_upsample2x_bwd", dup, g, 0, B, Hh // 2, Ww // 2, cx)
-            del dup
-            self._tr(f"D{i}.g", g)
-            S[f"D{i}"] = None
-        self._bucket_done(sp.buckets[0])
-        if frozen:      # frozen encoder weights: backward stops at the decoder (no encoder data / weight gradient)
-            self._join_side()
-            self.saved = None
-            return
-
-        # g = gradient wrt f5 ; encoder layers in reverse
-        for li in (3, 2, 1, 0):
-            blocks = sp.layers[li]
-            for bi in range(len(blocks) - 1, -1, -1):
-                blk = blocks[bi]
-                r = S[f"L{li}B{bi}"]
-                Hin, Win, Hh, Ww = r["Hin"], r["Win"], r["H"], r["W"]
-                # gradient buffer of the block input; a decoder skip gradient may already live there
-                gin = None
-                gin_has = False
-                if bi == 0 and li > 0 and skip_grads[li] is not None:
-                    gin, gin_has = skip_grads[li], True   # block input of layer(li+1).0 is f_{li+1} = feats[li]
-                if gin is None:
-                    gin = torch.empty_like(r["x"])
-                if blk.down is None:
-                    dy2 = self._bn_bwd(blk.conv2, params, grads, bn, g, r["out"], r["y2"], dres=gin,
-                                       dres_acc=gin_has, reduced=g_red)
-                    gin_has = True
-                    dyd = None
-                    self._tr(f"L{li}B{bi}.gres", gin)
-                else:
-                    gd = torch.empty_like(r["out"])
-                    dy2 = self._bn_bwd(blk.conv2, params, grads, bn, g, r["out"], r["y2"], dres=gd, reduced=g_red)
-                    dyd = self._bn_bwd(blk.down, params, grads, bn, gd, None, r["yd"])
-                    self._tr(f"L{li}B{bi}.gres", gd)
-                    self._tr(f"L{li}B{bi}.dyd", dyd)
-                    del gd
-                self._tr(f"L{li}B{bi}.dy2", dy2)
-                if r.get("z1") is not None:
-                    self._wgrad(blk.conv2, grads, r["z1"], None, 0, B, Hh, Ww, dy2)
-                else:
-                    self._wgrad(blk.conv2, grads, r["y1"], None, 0, B, Hh, Ww, dy2, in_ss=bn.ss(blk.conv1))
-                dz1 = torch.empty_like(r["y1"])
-                if self._fuse_bn:
-                    red1 = self._dgrad_bn(blk.conv2, dy2, B, Hh, Ww, dz1, blk.conv1, r["y1"], bn)
-                else:
-                    red1 = self._dgrad(blk.conv2, params, dy2, B, Hh, Ww, dz1)
-                del dy2
-                self._tr(f"L{li}B{bi}.dz1", dz1)
-                dy1 = self._bn_bwd(blk.conv1, params, grads, bn, dz1, None, r["y1"], virtual_act=True, reduced=red1)
-                self._tr(f"L{li}B{bi}.dy1", dy1)
-                del dz1
-                self._wgrad(blk.conv1, grads, r["x"], None, 0, B, Hin, Win, dy1)
-                g_red = None
-                if self.fuse_join_fp32 and bi > 0 and blk.down is None and gin_has:
-                    # gin becomes the output gradient of block bi-1: this join is its last writer, so the
-                    # BatchNorm-backward sums of that block's bn2 (mask: its stored output) ride along
-                    rp = S[f"L{li}B{bi - 1}"]
-                    g_red = self._dgrad_bn(blk.conv1, dy1, B, Hin, Win, gin, blocks[bi - 1].conv2, rp["y2"], bn,
-                                           act=rp["out"])
-                else:
-                    self._dgrad(blk.conv1, params, dy1, B, Hin, Win, gin, acc=gin_has)
-                gin_has = True
-                del dy1
-                self._tr(f"L{li}B{bi}.gin1", gin)
-                if dyd is not None:
-                    self._wgrad(blk.down, grads, r["x"], None, 0, B, Hin, Win, dyd)
-                    self._dgrad(blk.down, params, dyd, B, Hin, Win, gin, acc=True)
-                    del dyd
-                    self._tr(f"L{li}B{bi}.gin", gin)
-                g = gin
-                S[f"L{li}B{bi}"] = None
-            if li > 0:
-                self._bucket_done(sp.buckets[4 - li])
-
-        # ---- maxpool + stem
-        pl = S["pool"]
-        stem = S["stem"]
-        gf1 = skip_grads[0]
-        stem_red = None
-        P = lib.dt_maxpool3x3s2_bwd_bn_rows(B, pl["H"], pl["W"], 64) if (self._fuse_bn and self._fuse_pool_bn) else 0
-        if P > 0:      # even maps: the stem's BatchNorm-backward sums ride in the pass that writes its activation gradient
-            red = self._buf("bn_red_pool", lib.dt_bn_stats_floats(P, 64), device=dev)
-            self._call("dt_maxpool3x3s2_bwd_bn", g, pl["amax"], gf1, 1, bn.fuse(sp.stem, stem["y"]), red, B, pl["H"],
-                       pl["W"], 64)
-            stem_red = (red, P)
-        else:
-            self._call("dt_maxpool3x3s2_bwd", g, pl["amax"], gf1, 1, B, pl["H"], pl["W"], 64)
-        self._tr("gf1", gf1)
-        dy = self._bn_bwd(sp.stem, params, grads, bn, gf1, None, stem["y"], virtual_act=True, reduced=stem_red)
-        self._tr("stem.dy", dy)
-        self._wgrad(sp.stem, grads, stem["x"], None, 0, B, stem["Hin"], stem["Win"], dy)
-        self._join_side()
-        if self.grad_hook:
-            self.grad_hook(*sp.buckets[4])
-        self.saved = None
+# the fp32 units of the shared reverse schedule: plain functions of the engine (no engine holds, or is held by, this object)
+FP32_UNITS = SimpleNamespace(
+    dtype=torch.float32,
+    bn_bwd=Fp32Schedule._bn_bwd, wgrad=Fp32Schedule._wgrad, dgrad=Fp32Schedule._dgrad, dgrad_bn=Fp32Schedule._dgrad_bn,
+    head_bwd=Fp32Schedule._head_bwd, upsample_bwd=Fp32Schedule._upsample_bwd, stem_wgrad=Fp32Schedule._stem_wgrad,
+    fused_input_grad=Fp32Schedule._fused_input_grad, resunet_join=Fp32Schedule._resunet_join,
+    upsample_bwd_acc="dt_upsample2x_bwd", upsample_bwd_bn="dt_upsample2x_bwd_bn", channel_sums="dt_channel_sums",
+    channel_slice="dt_channel_slice", maxpool_bwd="dt_maxpool3x3s2_bwd", maxpool_bwd_bn="dt_maxpool3x3s2_bwd_bn",
+    # BatchNorm-backward sums in the epilogue of: conv2's data gradient / the up-sampling's backward; the encoder's gradient
+    # join; the max-pool backward
+    fuse_bn=lambda eng: eng._fuse_bn, fuse_join=lambda eng: eng.fuse_join_fp32,
+    fuse_pool=lambda eng: eng._fuse_bn and eng._fuse_pool_bn)

@@ -6,7 +6,9 @@ script needs nothing from the tree under test but its public surface.  A line ho
 ``ConvDesc`` / ``LossCfg`` by field; ``BnBwdFuse`` as its null pattern; every pointer argument (known from
 ``_lib.SIGNATURES``) as null, as buffer name + byte offset when it lies inside ``flat_params``, the gradient buffer or
 ``bn_state``, else as "device"; the stream as main or side; the return value.  Per configuration it also prints a SHA-256
-of logits (class map for inference), gradient buffer, ``bn_state`` and parameters.
+of logits (class map for inference), gradient buffer, ``bn_state`` and parameters.  The last line of a configuration is its
+extra output: the ``profile`` list (name, FLOPs, bytes) of a profiled one, (key, shape, dtype, SHA-256) of every tensor of
+``engine.trace`` in insertion order of a traced one, the error of one the tree refuses (``{"refused": ...}``).
 
 Usage (GPU box, a few seconds per configuration at B = 2 / 64 x 64):
     python scripts/diag_launch_trace.py OUTDIR [configuration ...]      -> OUTDIR/<configuration>.jsonl, OUTDIR/hashes.json
@@ -102,15 +104,23 @@ def configurations():
     """{name: (decoder kind, environment for the engine's construction, action(model, img, mask) -> extra output)}"""
     from deadtrees_amd.trainer import HipTrainer
 
-    def step(precision, prepare=None, profile=False):
+    def step(precision, prepare=None, profile=False, trace=False):
         def run(m, img, mask):
-            if prepare:
-                prepare(m)
-            tr = HipTrainer(m, precision=precision)
             if profile:
                 m.engine.profile = []
-            tr.step(img, mask)
-            prof, m.engine.profile = m.engine.profile, None
+            if trace:
+                m.engine.trace = {}
+            try:
+                if prepare:
+                    prepare(m)
+                HipTrainer(m, precision=precision).step(img, mask)
+            except (NotImplementedError, RuntimeError) as e:      # a configuration the tree refuses: refused alike
+                return {"refused": f"{type(e).__name__}: {e}"}
+            finally:
+                prof, m.engine.profile = m.engine.profile, None
+                traced, m.engine.trace = m.engine.trace, None
+            if trace:       # every traced tensor in insertion order
+                return [[k, list(t.shape), str(t.dtype), sha(t)] for k, t in traced.items()]
             return None if prof is None else [[p[0], p[1], p[4]] for p in prof]
         return run
 
@@ -140,6 +150,11 @@ def configurations():
         cfg[f"{kind}.step_bf16"] = (kind, {}, step("bf16"))
         cfg[f"{kind}.predict_fp32"] = (kind, {}, predict("fp32"))
         cfg[f"{kind}.predict_bf16"] = (kind, {}, predict("bf16"))
+        cfg[f"{kind}.traced_step_fp32"] = (kind, {}, step("fp32", trace=True))
+        cfg[f"{kind}.traced_step_bf16"] = (kind, {}, step("bf16", trace=True))
+        if kind != "unet":
+            cfg[f"{kind}.frozen_eval_encoder_step_fp32"] = (kind, {}, step("fp32", frozen_eval))
+            cfg[f"{kind}.frozen_eval_encoder_step_bf16"] = (kind, {}, step("bf16", frozen_eval))
     cfg["unet.direct_step_fp32"] = ("unet", {}, step("fp32", lambda m: setattr(m.engine, "winograd", False)))
     cfg["unet.frozen_eval_encoder_step_fp32"] = ("unet", {}, step("fp32", frozen_eval))
     cfg["unet.frozen_eval_encoder_step_bf16"] = ("unet", {}, step("bf16", frozen_eval))
@@ -147,6 +162,12 @@ def configurations():
     cfg["unet.recalibrate_fp32"] = ("unet", {}, recal("fp32"))
     cfg["unet.recalibrate_bf16"] = ("unet", {}, recal("bf16"))
     cfg["unet.virtual_activations_step_fp32"] = ("unet", {"DT_MATERIALIZE_Z1": "0", "DT_MATERIALIZE_Z2": "0"}, step("fp32"))
+    cfg["unet.no_bn_fuse_step_fp32"] = ("unet", {"DT_NO_BN_FUSE": "1"}, step("fp32"))
+    cfg["unet.no_join_fuse_step_fp32"] = ("unet", {"DT_FUSE_JOIN_FP32": "0"}, step("fp32"))
+    cfg["unet.no_pool_bn_step_fp32"] = ("unet", {"DT_FUSE_POOL_BN": "0"}, step("fp32"))
+    cfg["unet.no_pool_bn_step_bf16"] = ("unet", {"DT_FUSE_POOL_BN": "0"}, step("bf16"))
+    cfg["unet.no_overlap_step_fp32"] = ("unet", {"DT_OVERLAP_WGRAD": "0"}, step("fp32"))
+    cfg["unet.overlap_step_bf16"] = ("unet", {"DT_OVERLAP_WGRAD_BF16": "1"}, step("bf16"))
     cfg["unet.profiled_step_fp32"] = ("unet", {}, step("fp32", profile=True))
     cfg["unet.profiled_step_bf16"] = ("unet", {}, step("bf16", profile=True))
     cfg["unet.profiled_predict_fp32"] = ("unet", {}, predict("fp32", profile=True))

@@ -128,8 +128,8 @@ CASES = [("unet", 2, 64, 96, 3, 2, "default"),       # ragged Winograd tiles at 
          ("unet", 2, 128, 128, 4, 3, "default"),     # whole 16x16 tiles (epilogue forms 0/2/1/3/6), RGBN, 3 classes
          ("unet", 2, 64, 96, 3, 2, "direct"),        # engine.winograd = False: the direct kernels, same wiring
          ("unet", 2, 64, 96, 3, 2, "unfused"),       # FUSION_ATTRS off on the instance: the plain chain
-         ("resunet", 2, 64, 96, 4, 3, "default"),    # _backward_resunet_block
-         ("unet++", 2, 64, 96, 3, 2, "default")]     # _backward_unetpp: accumulating slots, channel slices
+         ("resunet", 2, 64, 96, 4, 3, "default"),    # _bwd_resunet_block
+         ("unet++", 2, 64, 96, 3, 2, "default")]     # _bwd_unetpp: accumulating slots, channel slices
 
 
 @pytest.mark.parametrize("arch,B,H,W,C,K,engine", CASES)
