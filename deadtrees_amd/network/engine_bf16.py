@@ -1,7 +1,7 @@
-"""The bf16 schedule of the U-Net engine: bf16 activations / weight images, fp32 accumulation, fp32 BatchNorm statistics
-and coefficients (the launches of ``engine_core``), fp32 master parameters and gradients.  ``forward_bf16_eval``,
-``forward_bf16_train`` with their units, and ``backward_bf16``: the bf16 units of the reverse schedule in
-``engine_backward``; stem and head run in fp32."""
+"""The bf16 units of the U-Net engine: bf16 activations / weight images, fp32 accumulation, fp32 BatchNorm statistics
+and coefficients (the launches of ``engine_core``), fp32 master parameters and gradients; stem and head run in fp32.
+``forward_bf16_eval`` / ``forward_bf16_eval_head`` / ``forward_bf16_train`` run them under the forward schedule in
+``engine_forward``, ``backward_bf16`` under the reverse schedule in ``engine_backward``.  ``BF16_UNITS`` names them for both."""
 from __future__ import annotations
 
 import ctypes as C
@@ -18,11 +18,6 @@ _BF = torch.bfloat16
 
 
 class Bf16Schedule:
-    # per pass (set by the two forwards): the convolutions write BatchNorm partial sums (training) / the encoder's
-    # coefficients come from its running statistics although they do (frozen encoder in eval mode)
-    _bf16_train = False
-    _bf16_enc_eval = False
-
     # ------------------------------------------------------------------ convolution launches
     def _bf16_mt(self, desc) -> int:
         """kernel family dt_conv2d_bf16 picks for `desc`: 8 = LDS-DMA staged (conv_bf16_dma.hip), 16 = lean narrow-layer
@@ -55,7 +50,8 @@ class Bf16Schedule:
             self._pe(e0, name, *self._conv_work(desc, 2))
 
     def _stem_bf16(self, x, params, y, stats, B, H, W, Cin):
-        """7x7/2 stem of the bf16 path into `y` (bf16) with optional BatchNorm partial statistics -> stat rows P.
+        """7x7/2 stem of the bf16 path into `y` (bf16) with optional BatchNorm partial statistics -> (stat rows P, the
+        statistics buffer | None, the space-to-depth image when there are statistics: the weight gradient reuses it | None).
         Even tiles wider than 32 pixels run on the bf16 MFMA kernels through the 2x2 space-to-depth image
         (dt_stem_s2d_bf16 + a 4x4 window: K = 256 bf16 instead of 147 fp32); anything else on the fp32 stem kernel."""
         lib, stc = self.lib, self.spec.stem
@@ -70,28 +66,27 @@ class Bf16Schedule:
             P = lib.dt_conv2d_bf16_stat_rows(C.byref(desc))
             sbuf = self._buf("bn_stats", lib.dt_bn_stats_floats(P, stc.cout), device=x.device) if stats else None
             self._conv_bf16(desc, s2d, None, wp, y, None, sbuf, None)
-            self._stem_s2d = s2d if stats else None     # training: the weight gradient reuses the image
-            return P, sbuf
+            return P, sbuf, s2d if stats else None
         sdesc = self._desc(B, H, W, Cin, 0, 0, h, w_, stc.cout, stc.k, stc.stride, stc.pad)
         P = lib.dt_conv2d_stat_rows(C.byref(sdesc))
         sbuf = self._buf("bn_stats", lib.dt_bn_stats_floats(P, stc.cout), device=x.device) if stats else None
         self._call("dt_conv2d_out_bf16", sdesc, x, w7, y, sbuf)
-        self._stem_s2d = None
-        return P, sbuf
+        return P, sbuf, None
 
-    # ------------------------------------------------------------------ forward units (both forwards)
+    # ------------------------------------------------------------------ forward units
     def _bn_coeffs_bf16(self, c: ConvSpec, params, bn: BnView, stats, P, count):
-        """(scale, shift) of conv c for this pass: from its running statistics (inference, an encoder in eval mode — the
-        batch sums of its convolutions are not used), else from the batch statistics"""
-        if not self._bf16_train or (self._bf16_enc_eval and c.index in self._enc_index):
-            return self._bn_eval_affine(c, params, bn)
-        return self._bn_finalize(c, params, bn, stats, P, count)
+        """(scale, shift) of conv c for this pass: from the batch statistics, or (``_batch_stats``: inference, an encoder
+        in eval mode — the batch sums of its convolutions are not used) from its running statistics"""
+        if self._batch_stats(c):
+            return self._bn_finalize(c, params, bn, stats, P, count)
+        return self._bn_eval_affine(c, params, bn)
 
     def _conv_bn_bf16(self, c: ConvSpec, params, bn: BnView, src0, src1, mode0, B, Hin, Win, in_ss=None):
-        """y = conv(x) in bf16 (+ BatchNorm partial statistics when training) -> y, Ho, Wo, (scale, shift)"""
+        """y = conv(x) in bf16 -> y, Ho, Wo, (scale, shift).  Every convolution of a training pass (the decoder is on batch
+        statistics) writes BatchNorm partial sums — those of a frozen eval-mode encoder too, which ignores them"""
         desc = self._conv_desc(c, src0, src1, mode0, B, Hin, Win)
         stats = P = None
-        if self._bf16_train:
+        if self._pass.dec_batch:
             P = self._rows("dt_conv2d_bf16_stat_rows", desc)
             stats = self._buf("bn_stats", self.lib.dt_bn_stats_floats(P, c.cout), device=src0.device)
         y = torch.empty((B, desc.Ho, desc.Wo, c.cout), dtype=_BF, device=src0.device)
@@ -99,13 +94,13 @@ class Bf16Schedule:
         self._conv_bf16(desc, src0, src1, c.w(wb), y, None, stats, in_ss, w_chunked=c.w(wbc))
         return y, desc.Ho, desc.Wo, self._bn_coeffs_bf16(c, params, bn, stats, P, B * desc.Ho * desc.Wo)
 
-    def _bn_act_bf16(self, y, ss, res=None, res_ss=None, y_f32=False, of: Optional[ConvSpec] = None):
+    def _bn_act_bf16(self, y, ss, res=None, res_ss=None, of: Optional[ConvSpec] = None):
         """of: the convolution whose normalise pass this is (recalibration launch record)"""
         Bq, Hq, Wq, Cq = y.shape
         z = torch.empty((Bq, Hq, Wq, Cq), dtype=_BF, device=y.device)
         self._rec_act(of)
-        e0 = self._pb() if self._bf16_train else None      # the inference roofline lists the convolutions only
-        self._call("dt_bn_act_bf16", y, 1 if y_f32 else 0, ss[0], ss[1], res, *_pair(res_ss), z, Bq * Hq * Wq, Cq, 1)
+        e0 = self._pb() if self._pass.dec_batch else None      # the inference roofline lists the convolutions only
+        self._call("dt_bn_act_bf16", y, 0, ss[0], ss[1], res, *_pair(res_ss), z, Bq * Hq * Wq, Cq, 1)
         self._pe(e0, "bn_act_bf16_kernel", 0.0, 2.0 * y.numel() * (2 + (res is not None)))
         return z
 
@@ -121,233 +116,69 @@ class Bf16Schedule:
                    B * H * W, ic.cout, 2)
         return out
 
-    def _encoder_block_bf16(self, blk, params, bn: BnView, xin, B, ch, cw, z1_stored: bool, keep: bool):
-        """one resnet block -> (record for backward if `keep`, output, Ho, Wo); z1_stored: conv1's activation is
-        materialised"""
-        y1, h1, w1, ss1 = self._conv_bn_bf16(blk.conv1, params, bn, xin, None, 0, B, ch, cw)
-        z1 = self._bn_act_bf16(y1, ss1, of=blk.conv1) if z1_stored else None
-        y2, h2, w2, ss2 = self._conv_bn_bf16(blk.conv2, params, bn, y1 if z1 is None else z1, None, 0, B, h1, w1,
-                                             in_ss=ss1 if z1 is None else None)
-        if blk.down is not None:
-            yd, _, _, ssd = self._conv_bn_bf16(blk.down, params, bn, xin, None, 0, B, ch, cw)
-            out = self._bn_act_bf16(y2, ss2, res=yd, res_ss=ssd, of=blk.conv2)
-        else:
-            yd = None
-            out = self._bn_act_bf16(y2, ss2, res=xin, of=blk.conv2)
-        rec = dict(x=xin, y1=y1, z1=z1, y2=y2, yd=yd, out=out, Hin=ch, Win=cw, H=h2, W=w2) if keep else None
-        return rec, out, h2, w2
+    # ------------------------------------------------------------------ what the shared forward schedule leaves to bf16
+    def _stem_fwd_bf16(self, params, bn: BnView, x, B, H, W):
+        """stem: bf16 MFMA over the space-to-depth image (fp32-MFMA kernel for odd / tiny tiles), bf16 output, fp32
+        statistics -> (activation, Ho, Wo, record for the backward: with the image the weight gradient reuses)"""
+        stc = self.spec.stem
+        h, w_ = stc.out_size(H), stc.out_size(W)
+        y = torch.empty((B, h, w_, stc.cout), dtype=_BF, device=x.device)
+        P, stats, s2d = self._stem_bf16(x, params, y, self._pass.dec_batch, B, H, W, x.shape[-1])
+        f1 = self._bn_act_bf16(y, self._bn_coeffs_bf16(stc, params, bn, stats, P, B * h * w_), of=stc)
+        return f1, h, w_, dict(x=x, y=y, z=f1, Hin=H, Win=W, s2d=s2d)
 
-    def _forward_unetpp_bf16(self, feats, params, bn: BnView, B, sv: Optional[_Saved]):
-        """smp UnetPlusPlus under AMP (fp32 twin: _forward_unetpp): every node = DecoderBlock(up x2 of its lower node, cat of
-        the nodes / encoder feature on its level); node outputs are stored bf16 activations (several consumers), conv2
-        reads conv1's raw output with BatchNorm + ReLU applied while staging"""
-        sp = self.spec
-        nodes = {f"f{k}": feats[4 - k] for k in range(5)}
-        for blk in sp.decoder:
-            low = nodes[blk.low]
-            skip, parts = (None, []) if not blk.cat else self._cat_channels([nodes[n] for n in blk.cat])
-            y1, h1, w1, ss1 = self._conv_bn_bf16(blk.conv1, params, bn, low, skip, 1, B, 2 * low.shape[1], 2 * low.shape[2])
-            y2, h2, w2, ss2 = self._conv_bn_bf16(blk.conv2, params, bn, y1, None, 0, B, h1, w1, in_ss=ss1)
-            z2 = self._bn_act_bf16(y2, ss2, of=blk.conv2)
-            if sv is not None:
-                sv.d["P" + blk.name] = dict(x=low, skip=skip, parts=parts, y1=y1, y2=y2, z2=z2, H=h1, W=w1)
-            nodes[blk.name] = z2
-        return nodes[sp.decoder[-1].name]
+    def _maxpool_bf16(self, f1, pool, B, h, w_):
+        """-> the arg-max map the max-pool backward reads: in every training pass, frozen encoder included"""
+        if not self._pass.dec_batch:
+            self._call("dt_maxpool3x3s2_bf16", f1, pool, B, h, w_, 64)
+            return None
+        amax = torch.empty(pool.shape, dtype=torch.uint8, device=f1.device)
+        self._call("dt_maxpool3x3s2_bf16_amax", f1, pool, amax, B, h, w_, 64)
+        return amax
 
-    # ------------------------------------------------------------------ bf16 inference leg
+    def _head_fwd_bf16(self, d, w, bias, logits, am64, am8, B, H, W, cin, K):
+        self._call("dt_head_fwd_bf16", d, w, bias, logits, am64, am8, B, H, W, cin, K)
+
+    # ------------------------------------------------------------------ forward
+    def _bf16_fwd_weights(self, params):
+        self._wb = (self._bf16_weights(params), self._bf16_weights(params, chunked=True))
+
     def forward_bf16_eval(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor,
                           want_argmax: Optional[str] = None, decoder_only: bool = False):
-        """eval-mode forward with bf16 activations/weights and fp32 accumulation (stem and head stay fp32).
+        """eval-mode forward (``engine_forward``) with bf16 activations/weights and fp32 accumulation (stem and head stay
+        fp32) -> (logits, arg-max map | None).
         decoder_only: stop in front of the head and return the bf16 decoder output [B,H,W,16] it would read."""
-        sp = self.spec
-        if x_nchw.dim() != 4 or x_nchw.shape[1] != sp.in_channels:
-            raise RuntimeError(f"expected input [B,{sp.in_channels},H,W], got {tuple(x_nchw.shape)}")
-        B, Cin, H, W = x_nchw.shape
-        if H % 32 or W % 32:
-            raise RuntimeError(f"H and W must be divisible by 32 (encoder depth 5), got {H}x{W}")
-        self._bf16_train, self._bf16_enc_eval = False, False
-        dev = x_nchw.device
-        self._wb = (self._bf16_weights(params), self._bf16_weights(params, chunked=True))
-        bnws = self._buf("bnws", BnView.ws_floats(sp), device=dev)
-        bn = BnView(sp, bnws, bnstate)
-        akey = (params.data_ptr(), params._version, self._weights_epoch, bnstate.data_ptr(), bnstate._version,
-                self._bn_epoch, bnws.data_ptr())
-        # same coefficients as the previous inference call: skip 46 launches
-        self._affine_fresh = self._ws.get("affine_key") == akey
-        self._ws["affine_key"] = akey
-
-        x = torch.empty((B, H, W, Cin), dtype=torch.float32, device=dev)
-        self._call("dt_nchw_to_nhwc", x_nchw.contiguous(), x, B, Cin, H, W)
-        # stem: bf16 MFMA over the space-to-depth image (fp32-MFMA kernel for odd / tiny tiles), bf16 output
-        stc = sp.stem
-        h, w_ = stc.out_size(H), stc.out_size(W)
-        y = torch.empty((B, h, w_, stc.cout), dtype=_BF, device=dev)
-        self._stem_bf16(x, params, y, False, B, H, W, Cin)
-        f1 = self._bn_act_bf16(y, self._bn_eval_affine(stc, params, bn))
-        hp, wp = (h + 2 - 3) // 2 + 1, (w_ + 2 - 3) // 2 + 1
-        pool = torch.empty((B, hp, wp, 64), dtype=_BF, device=dev)
-        self._call("dt_maxpool3x3s2_bf16", f1, pool, B, h, w_, 64)
-        feats = [f1]
-        cur, ch, cw = pool, hp, wp
-        for blocks in sp.layers:
-            for blk in blocks:
-                _, cur, ch, cw = self._encoder_block_bf16(blk, params, bn, cur, B, ch, cw, z1_stored=False, keep=False)
-            feats.append(cur)
-        d, dh, dw, d_ss = feats[4], ch, cw, None
-        skips = [feats[3], feats[2], feats[1], feats[0], None]
-        if sp.decoder_kind == "unetplusplus":      # dense decoder: node outputs are stored tensors
-            d = self._forward_unetpp_bf16(feats, params, bn, B, None)
-            dh, dw = d.shape[1], d.shape[2]
-        for i, blk in enumerate(sp.decoder if sp.decoder_kind != "unetplusplus" else ()):
-            y1, h1, w1, ss1 = self._conv_bn_bf16(blk.conv1, params, bn, d, skips[i], 1, B, 2 * dh, 2 * dw, in_ss=d_ss)
-            y2, h2, w2, ss2 = self._conv_bn_bf16(blk.conv2, params, bn, y1, None, 0, B, h1, w1, in_ss=ss1)
-            if sp.decoder_kind == "resunet":     # relu(bn2(conv2(.))) + identity_conv(up + skip) (resunet/decoder.py:40-52)
-                d, d_ss = self._resunet_join_bf16(blk, params, d, skips[i], y2, ss2, B, h2, w2), None
-                dh, dw = h2, w2
-                continue
-            if i == len(sp.decoder) - 1:
-                d, d_ss = self._bn_act_bf16(y2, ss2), None
-            else:
-                d, d_ss = y2, ss2
-            dh, dw = h2, w2
-        if decoder_only:
-            return d
-        hd = sp.head
-        K = hd.cout
-        logits = torch.empty((B, K, dh, dw), dtype=torch.float32, device=dev)
-        am64 = torch.empty((B, dh, dw), dtype=torch.int64, device=dev) if want_argmax == "int64" else None
-        am8 = torch.empty((B, dh, dw), dtype=torch.uint8, device=dev) if want_argmax == "uint8" else None
-        self._call("dt_head_fwd_bf16", d, hd.w(params), hd.bias(params), logits, am64, am8, B, dh, dw, hd.cin, K)
-        return logits, (am64 if am64 is not None else am8)
+        self._bf16_fwd_weights(params)
+        return self._forward(BF16_UNITS, x_nchw, params, bnstate, False, False, False, want_argmax=want_argmax,
+                             decoder_only=decoder_only)
 
     def forward_bf16_eval_head(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor, labels, lu=None,
                                dist=None, gamma: float = 2.0, counts=None, err=None, want_argmax: bool = False):
         """``forward_bf16_eval`` ending in the fused evaluation head (dt_head_eval_bf16) instead of dt_head_fwd_bf16
         -> what ``ops.head_eval`` returns"""
-        from ..ops import head_eval
-        d = self.forward_bf16_eval(x_nchw, params, bnstate, decoder_only=True)
-        hd = self.spec.head
-        return head_eval(d, hd.w(params).view(hd.cout, hd.k, hd.k, hd.cin), hd.bias(params), labels, lu, dist, gamma,
-                         counts, err, want_argmax)
+        return self._forward_eval_head(BF16_UNITS, x_nchw, params, bnstate, labels, lu, dist, gamma, counts, err, want_argmax)
 
-    # ------------------------------------------------------------------ bf16 training (BASELINE configs[2])
     def forward_bf16_train(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor,
                            enc_training: bool = True, enc_frozen: bool = False, recal: Optional[torch.Tensor] = None):
-        """training-mode forward with bf16 activations / weights, fp32 accumulation, fp32 BatchNorm statistics
-        (taken from the accumulators), fp32 master parameters.  Stem and head run in fp32.
+        """training-mode forward (``engine_forward``, saved for ``backward_bf16``) with bf16 activations / weights, fp32
+        accumulation, fp32 BatchNorm statistics (taken from the accumulators), fp32 master parameters -> logits.  Stem and
+        head run in fp32.
         enc_frozen: the encoder's weights get no gradient — nothing of it is saved; enc_training=False (only with a
         frozen encoder here: the bf16 path has no frozen-statistics BatchNorm backward) normalises the encoder with its
         running statistics, which stay untouched.
         recal: device float[1] momentum -> BatchNorm recalibration pass, see `forward`: the same kernels on the same
         data as the training forward, nothing kept for backward (`self.saved` stays as it was), Unet: returns None after
         the last BatchNorm's statistics."""
-        sp = self.spec
-        self._recal = None
-        if recal is not None:
-            if enc_frozen or not enc_training:
-                raise RuntimeError("recalibration forward: every BatchNorm layer runs on batch statistics")
-            if recal.dtype != torch.float32 or recal.device != x_nchw.device:
-                raise RuntimeError("recalibration forward: the momentum is a float32 tensor on the input's device")
-            self._recal, self.recal_launches = recal, []
+        if recal is not None and (enc_frozen or not enc_training):
+            raise RuntimeError("recalibration forward: every BatchNorm layer runs on batch statistics")
         if not enc_training and not enc_frozen:
             raise NotImplementedError("bf16: an encoder in eval mode trains only with frozen weights "
                                       "(model.encoder.requires_grad_(False)); use fp32 for trainable weights on "
                                       "running statistics")
-        B, Cin, H, W = x_nchw.shape
-        if H % 32 or W % 32 or Cin != sp.in_channels:
-            raise RuntimeError(f"bad input {tuple(x_nchw.shape)}")
-        self._bf16_train, self._bf16_enc_eval = True, not enc_training
-        self._affine_fresh = False   # an eval-mode encoder's coefficients are computed in every pass
-        dev = x_nchw.device
-        self._bn_epoch += 1          # running statistics are rewritten on the device (invalidates cached eval affines)
         if self._bf16_images_fused:
             self._bf16_weights_all(params)
-        self._wb = (self._bf16_weights(params), self._bf16_weights(params, chunked=True))
-        sv = _Saved()
-        bnws = torch.empty(BnView.ws_floats(sp), dtype=torch.float32, device=dev)
-        sv.d["bnws"] = bnws
-        bn = BnView(sp, bnws, bnstate)
-
-        x = torch.empty((B, H, W, Cin), dtype=torch.float32, device=dev)
-        self._call("dt_nchw_to_nhwc", x_nchw.contiguous(), x, B, Cin, H, W)
-        # stem: bf16 MFMA over the space-to-depth image (fp32-MFMA kernel for odd / tiny tiles), fp32 statistics
-        stc = sp.stem
-        h, w_ = stc.out_size(H), stc.out_size(W)
-        ystem = torch.empty((B, h, w_, stc.cout), dtype=_BF, device=dev)
-        Pst, sstats = self._stem_bf16(x, params, ystem, True, B, H, W, Cin)
-        ss = self._bn_coeffs_bf16(stc, params, bn, sstats, Pst, B * h * w_)
-        f1 = self._bn_act_bf16(ystem, ss, of=stc)
-        if not enc_frozen:
-            sv.d["stem"] = dict(x=x, y=ystem, z=f1, Hin=H, Win=W, s2d=self._stem_s2d)
-        self._stem_s2d = None
-        hp, wp = (h + 2 - 3) // 2 + 1, (w_ + 2 - 3) // 2 + 1
-        pool = torch.empty((B, hp, wp, 64), dtype=_BF, device=dev)
-        amax = torch.empty((B, hp, wp, 64), dtype=torch.uint8, device=dev)
-        self._call("dt_maxpool3x3s2_bf16_amax", f1, pool, amax, B, h, w_, 64)
-        if not enc_frozen:
-            sv.d["pool"] = dict(amax=amax, H=h, W=w_)
-        self._tr("pool", pool)
-        feats = [f1]
-        cur, ch, cw = pool, hp, wp
-        for li, blocks in enumerate(sp.layers):
-            for bi, blk in enumerate(blocks):
-                # conv1's activation is stored: A/B switch DT_BF16_MAT_Z1 (see __init__)
-                rec, cur, ch, cw = self._encoder_block_bf16(blk, params, bn, cur, B, ch, cw, z1_stored=self._mat_z1_bf16,
-                                                            keep=not enc_frozen)
-                if rec is not None:
-                    sv.d[f"L{li}B{bi}"] = rec
-            feats.append(cur)
-        d, dh, dw, d_ss = feats[4], ch, cw, None
-        skips = [feats[3], feats[2], feats[1], feats[0], None]
-        if sp.decoder_kind == "unetplusplus":
-            d = self._forward_unetpp_bf16(feats, params, bn, B, sv)
-            dh, dw = d.shape[1], d.shape[2]
-        for i, blk in enumerate(sp.decoder if sp.decoder_kind != "unetplusplus" else ()):
-            if sp.decoder_kind == "resunet":
-                # reference network/extra/resunet/decoder.py:40-52 under AMP: conv1 -> conv2 (conv-BN-ReLU each, both
-                # activations virtual) + the 1x1 identity_conv (bias) of the up-sampled + concatenated input; no activation
-                # after the sum; the block output is a stored bf16 tensor
-                y1, h1, w1, ss1 = self._conv_bn_bf16(blk.conv1, params, bn, d, skips[i], 1, B, 2 * dh, 2 * dw)
-                y2, h2, w2, ss2 = self._conv_bn_bf16(blk.conv2, params, bn, y1, None, 0, B, h1, w1, in_ss=ss1)
-                out = self._resunet_join_bf16(blk, params, d, skips[i], y2, ss2, B, h2, w2)
-                self._tr(f"D{i}.out", out)
-                sv.d[f"D{i}"] = dict(x=d, skip=skips[i], y1=y1, y2=y2, H=h1, W=w1)
-                d, dh, dw, d_ss = out, h2, w2, None
-                continue
-            y1, h1, w1, ss1 = self._conv_bn_bf16(blk.conv1, params, bn, d, skips[i], 1, B, 2 * dh, 2 * dw, in_ss=d_ss)
-            # round 3: the activations of the 64+-channel decoder blocks are stored (bn_act, 4 B per element moved) so that
-            # conv2 / the next conv1 AND their weight gradients run the pure LDS-DMA kernels (a DMA cannot transform);
-            # with the register-staged weight gradient this was neutral (2,236 vs 2,234), DT_BF16_MAT_DEC=0 restores it
-            wide = self._mat_dec_bf16 and blk.conv2.cout % 64 == 0
-            z1 = self._bn_act_bf16(y1, ss1, of=blk.conv1) if wide else None
-            y2, h2, w2, ss2 = self._conv_bn_bf16(blk.conv2, params, bn, y1 if z1 is None else z1, None, 0, B, h1, w1,
-                                                 in_ss=ss1 if z1 is None else None)
-            if recal is not None and i == len(sp.decoder) - 1:
-                self._recal = None              # every BatchNorm's statistics are final: nothing else to launch
-                return None
-            if i == len(sp.decoder) - 1 or wide:
-                z2 = self._bn_act_bf16(y2, ss2, of=blk.conv2)
-                nxt, nxt_ss = z2, None
-            else:
-                z2 = None
-                nxt, nxt_ss = y2, ss2
-            sv.d[f"D{i}"] = dict(x=d, x_virtual=d_ss is not None, skip=skips[i], y1=y1, z1=z1, y2=y2, z2=z2, H=h1, W=w1)
-            d, dh, dw, d_ss = nxt, h2, w2, nxt_ss
-        hd = sp.head
-        K = hd.cout
-        logits = torch.empty((B, K, dh, dw), dtype=torch.float32, device=dev)
-        if recal is not None:
-            self.recal_launches.append(("head", hd.key))
-        self._call("dt_head_fwd_bf16", d, hd.w(params), hd.bias(params), logits, None, None, B, dh, dw, hd.cin, K)
-        if recal is not None:       # nothing of this pass is for a backward
-            self._recal = None
-            return logits
-        sv.d["head"] = dict(x=d, H=dh, W=dw)
-        sv.d["B"] = B
-        sv.d["bf16"] = True
-        sv.d["enc_frozen"] = bool(enc_frozen)
-        self.saved = sv
-        return logits
+        self._bf16_fwd_weights(params)
+        return self._forward(BF16_UNITS, x_nchw, params, bnstate, True, enc_training, recal is None, enc_frozen, recal)[0]
 
     # ------------------------------------------------------------------ backward units
     def _bn_bwd_bf16(self, c: ConvSpec, params, grads, bn: BnView, dout, out_act, y, dres=None, dres_acc=False,
@@ -511,9 +342,29 @@ class Bf16Schedule:
             self._call("dt_conv2d_wgrad_stem_dy_bf16", sdesc, stem["x"], dy, stc.w(grads), ws, ws.numel() * 4)
 
 
-# the bf16 units of the shared reverse schedule: plain functions of the engine (no engine holds, or is held by, this object)
+def _not_fused(eng, *args):
+    """the bf16 path has none of the fused inference forms: the generic block runs"""
+    return None
+
+
+# the bf16 units of the two shared schedules: plain functions of the engine (no engine holds, or is held by, this object)
 BF16_UNITS = SimpleNamespace(
     dtype=_BF,
+    # ---- forward: unit launchers, the hooks for what is not the same sequence in fp32, the rules read per pass / per block
+    conv_bn=Bf16Schedule._conv_bn_bf16, bn_act=Bf16Schedule._bn_act_bf16, stem=Bf16Schedule._stem_fwd_bf16,
+    maxpool=Bf16Schedule._maxpool_bf16, fused_encoder_block=_not_fused, fused_unet_block=_not_fused,
+    resunet_out=Bf16Schedule._resunet_join_bf16, head=Bf16Schedule._head_fwd_bf16,
+    fuse_eval=lambda eng, p: (False, False),
+    runs=lambda kind, inference: kind != "efficientunetplusplus",
+    # stored activations: none in inference but the last block's output; in a training pass conv1's of an encoder block
+    # (DT_BF16_MAT_Z1), and conv1's AND the output of the 64+-channel decoder blocks (DT_BF16_MAT_DEC) so that conv2 / the
+    # next conv1 and their weight gradients run the pure LDS-DMA kernels (a DMA cannot transform)
+    enc_z1_stored=lambda eng: eng._pass.dec_batch and eng._mat_z1_bf16,
+    dec_z1_stored=lambda eng, blk: eng._pass.dec_batch and eng._mat_dec_bf16 and blk.conv2.cout % 64 == 0,
+    dec_out_stored=lambda eng, i: eng._pass.dec_batch and eng._mat_dec_bf16 and eng.spec.decoder[i].conv2.cout % 64 == 0,
+    saved_tail=lambda p: dict(bf16=True, enc_frozen=p.enc_frozen),
+    decoder_output=lambda eng, x, params, bnstate: eng.forward_bf16_eval(x, params, bnstate, decoder_only=True),
+    # ---- backward
     bn_bwd=Bf16Schedule._bn_bwd_bf16, wgrad=Bf16Schedule._wgrad_bf16, dgrad=Bf16Schedule._dgrad_bf16,
     dgrad_bn=Bf16Schedule._dgrad_bn_bf16, head_bwd=Bf16Schedule._head_bwd_bf16, upsample_bwd=Bf16Schedule._upsample_bwd_bf16,
     stem_wgrad=Bf16Schedule._stem_wgrad_bf16, fused_input_grad=Bf16Schedule._fused_input_grad_bf16,

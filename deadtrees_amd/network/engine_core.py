@@ -1,6 +1,7 @@
 """What both precisions of the U-Net engine share: the library handle and the ONE launch path, the workspaces, the
 profiling bracket, the weight tables and weight-image caches, the weight-gradient side stream and the fp32 BatchNorm
-coefficient launches.  The schedules live in ``engine_fp32`` / ``engine_bf16``; ``engine.UNetEngine`` mixes them in."""
+coefficient launches, the per-pass record of the BatchNorm mode.  The unit launchers live in ``engine_fp32`` /
+``engine_bf16``, the two schedules in ``engine_forward`` / ``engine_backward``; ``engine.UNetEngine`` mixes them in."""
 from __future__ import annotations
 
 import contextlib
@@ -40,6 +41,18 @@ class _Saved:
 
     def __init__(self):
         self.d = {}
+
+
+class _Pass:
+    """the forward pass in flight (set by ``engine_forward._forward``, read by the units of either precision): the
+    BatchNorm mode — decoder / encoder layers on batch statistics, else on their running statistics —, what is kept for a
+    backward (`save`; of the encoder only `enc_save`: not with frozen weights), and where the fp32 inference forms with
+    BatchNorm + ReLU in the convolution's epilogue run (set from the units' ``fuse_eval`` rule)"""
+    __slots__ = ("dec_batch", "enc_batch", "save", "enc_save", "enc_frozen", "fuse_enc", "fuse_dec")
+
+    def __init__(self, dec_batch=False, enc_batch=False, save=False, enc_save=False, enc_frozen=False):
+        self.dec_batch, self.enc_batch, self.save, self.enc_save = bool(dec_batch), bool(enc_batch), bool(save), bool(enc_save)
+        self.enc_frozen, self.fuse_enc, self.fuse_dec = bool(enc_frozen), False, False
 
 
 class EngineCore:
@@ -95,7 +108,7 @@ class EngineCore:
         self._fuse_eval_opt = os.environ.get("DT_FUSE_EVAL", "1") != "0"
         self._bf16_images_fused = os.environ.get("DT_BF16_IMAGES_FUSED", "1") != "0"   # four bf16 weight images in one launch
         self._fuse_pool_bn = os.environ.get("DT_FUSE_POOL_BN", "1") != "0"   # stem BatchNorm-backward sums in the max-pool backward
-        self._fuse_eval = False
+        self._pass = _Pass()
         self._mat_z1 = os.environ.get("DT_MATERIALIZE_Z1", "1" if self.winograd else "0") != "0"
         # the same for the decoder block outputs that feed a Winograd conv1 (716.6 vs 712.8 tiles/s)
         self._mat_z2 = os.environ.get("DT_MATERIALIZE_Z2", "1" if self.winograd else "0") != "0"
@@ -218,6 +231,12 @@ class EngineCore:
         return self._desc(B, Hin, Win, C0, C1, mode0, c.out_size(Hin), c.out_size(Win), c.cout, c.k, c.stride, c.pad)
 
     # ------------------------------------------------------------------ BatchNorm coefficients (fp32 in both precisions)
+    def _batch_stats(self, c: ConvSpec) -> bool:
+        """the ONE rule for the BatchNorm mode of a layer in the forward pass in flight: batch statistics (True) or its
+        running statistics, by whether the layer belongs to the encoder"""
+        p = self._pass
+        return p.enc_batch if c.index in self._enc_index else p.dec_batch
+
     def _bn_eval_affine(self, c: ConvSpec, params, bn: BnView):
         """(scale, shift) of conv c from its running statistics; skipped while the coefficients of the previous
         inference call are still valid (`_affine_fresh`, see forward).  A convolution bias in front of the BatchNorm

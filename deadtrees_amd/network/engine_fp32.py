@@ -1,6 +1,7 @@
-"""The fp32 schedule of the U-Net engine: ``forward`` and its units (convolution + BatchNorm statistics, the fused inference
-forms, the Unet++ / EfficientUnet++ decoders); ``backward``: the fp32 units (BatchNorm backward, weight / data gradients,
-the fused input gradients) of the reverse schedule in ``engine_backward``."""
+"""The fp32 units of the U-Net engine.  ``forward`` / ``forward_eval_head``: convolution + BatchNorm statistics, the
+normalise pass, the fused inference forms and the EfficientUnet++ decoder under the forward schedule in ``engine_forward``;
+``backward``: BatchNorm backward, weight / data gradients and the fused input gradients under the reverse schedule in
+``engine_backward``.  ``FP32_UNITS`` names them for both schedules."""
 from __future__ import annotations
 
 import ctypes as C
@@ -56,16 +57,17 @@ class Fp32Schedule:
             self._pe(e0, name, *self._conv_work(desc))
 
     # ------------------------------------------------------------------ forward units
-    def _conv_bn(self, c: ConvSpec, params, bn: BnView, src0, src1, mode0, B, Hin, Win, training, in_ss=None,
-                 save_stats=False):
+    def _conv_bn(self, c: ConvSpec, params, bn: BnView, src0, src1, mode0, B, Hin, Win, in_ss=None):
         """y = conv(x); BN statistics -> per-channel scale/shift in the workspace.  Returns y, Ho, Wo, (scale, shift).
         in_ss: (scale, shift) of the layer that produced src0 when src0 is a RAW conv output whose
-        BatchNorm-apply + ReLU is fused into this conv's LDS staging (virtual activation)."""
+        BatchNorm-apply + ReLU is fused into this conv's LDS staging (virtual activation).
+        A layer on its running statistics (``_batch_stats``) launches without a statistics buffer; where it is saved, a
+        backward may follow: mean / invstd from the running statistics too."""
         desc = self._conv_desc(c, src0, src1, mode0, B, Hin, Win)
         Ho, Wo = desc.Ho, desc.Wo
         y = torch.empty((B, Ho, Wo, c.cout), dtype=torch.float32, device=src0.device)
         u = self._u(c)
-        if training:
+        if self._batch_stats(c):
             P = self._stat_rows(desc, u)
             stats = self._buf("bn_stats", self.lib.dt_bn_stats_floats(P, c.cout), device=src0.device)
             self._conv(desc, src0, src1, c.w(params), y, None, stats, in_ss, u=u)
@@ -73,13 +75,14 @@ class Fp32Schedule:
         else:
             self._conv(desc, src0, src1, c.w(params), y, None, None, in_ss, u=u)
             ss = self._bn_eval_affine(c, params, bn)
-            if save_stats:
+            p = self._pass
+            if p.enc_save if c.index in self._enc_index else p.save:
                 self._bn_eval_stats(c, bn)
         return y, Ho, Wo, ss
 
-    def _bn_act(self, y, ss, res=None, res_ss=None, relu=True, out=None, of: Optional[ConvSpec] = None):
-        """relu: True/1 = ReLU after the residual add, 2 = ReLU on the main branch only (ResUnet decoder), 0 = none.
-        of: the convolution whose normalise pass this is (recalibration launch record)"""
+    def _bn_act(self, y, ss, res=None, res_ss=None, of: Optional[ConvSpec] = None, relu=True, out=None):
+        """of: the convolution whose normalise pass this is (recalibration launch record).
+        relu: True/1 = ReLU after the residual add, 2 = ReLU on the main branch only (ResUnet decoder), 0 = none"""
         B, H, W, Cc = y.shape
         z = torch.empty_like(y) if out is None else out
         self._rec_act(of)
@@ -103,7 +106,7 @@ class Fp32Schedule:
     def _conv_affine_eval(self, c: ConvSpec, params, bn: BnView, src0, src1, mode0, B, Hin, Win, res=None, in_ss=None):
         """inference: relu(bn_eval(conv(x)) [+ res]) in ONE Winograd launch (dt_conv2d_winograd_affine) — no raw output, no
         bn_act pass.  Returns the activation, or None when the layer is not a Winograd layer (caller: conv + bn_act)."""
-        if not self._fuse_eval or c.k != 3 or c.stride != 1 or c.pad != 1:
+        if c.k != 3 or c.stride != 1 or c.pad != 1:
             return None
         desc = self._conv_desc(c, src0, src1, mode0, B, Hin, Win)
         u = self._u(c)
@@ -125,11 +128,84 @@ class Fp32Schedule:
                      *self._conv_work(desc, extra_bytes=4.0 * z.numel() if res is not None else 0.0))
         return z
 
+    # ------------------------------------------------------------------ what the shared forward schedule leaves to fp32
+    def _stem(self, params, bn: BnView, x, B, H, W):
+        """-> (stem activation, Ho, Wo, record for the backward | None: the inference form stores no raw output)"""
+        stc = self.spec.stem
+        if self._pass.fuse_enc:     # inference: BatchNorm + ReLU in the stem kernel's epilogue
+            return (*self._conv_affine_direct(stc, params, bn, x, None, 0, B, H, W), None)
+        y, h, w_, ss = self._conv_bn(stc, params, bn, x, None, 0, B, H, W)
+        f1 = self._bn_act(y, ss, of=stc)
+        return f1, h, w_, dict(x=x, y=y, z=f1, Hin=H, Win=W)
+
+    def _maxpool(self, f1, pool, B, h, w_):
+        """-> the arg-max map the max-pool backward reads: only when the encoder is saved"""
+        amax = torch.empty(pool.shape, dtype=torch.uint8, device=f1.device) if self._pass.enc_save else None
+        self._call("dt_maxpool3x3s2", f1, pool, amax, B, h, w_, 64)
+        return amax
+
+    def _fused_encoder_block(self, blk, params, bn: BnView, xin, B, ch, cw):
+        """inference form of a residual block -> (output, Ho, Wo), or None where a layer of it is not covered (the
+        generic block runs)"""
+        if blk.conv1.stride == 1 and blk.down is None:
+            z1 = self._conv_affine_eval(blk.conv1, params, bn, xin, None, 0, B, ch, cw)
+            out = None if z1 is None else self._conv_affine_eval(blk.conv2, params, bn, z1, None, 0, B, ch, cw, res=xin)
+            if out is not None:
+                return out, ch, cw
+        if blk.down is not None and blk.conv2.cout % 64 == 0:
+            # first block of layers 2-4: relu(bn1(conv1)) and bn_d(down(x)) from the direct kernel's epilogue, the
+            # join relu(bn2(conv2) + .) in the Winograd kernel's
+            z1, h1, w1 = self._conv_affine_direct(blk.conv1, params, bn, xin, None, 0, B, ch, cw)
+            rd, _, _ = self._conv_affine_direct(blk.down, params, bn, xin, None, 0, B, ch, cw, relu=False)
+            out = self._conv_affine_eval(blk.conv2, params, bn, z1, None, 0, B, h1, w1, res=rd)
+            if out is not None:
+                return out, h1, w1
+        return None
+
+    def _fused_unet_block(self, blk, params, bn: BnView, d, skip, B, Hin, Win):
+        """inference form of a Unet decoder block over up(d) | skip -> its activation, or None (the generic block runs)"""
+        z1 = self._conv_affine_eval(blk.conv1, params, bn, d, skip, 1, B, Hin, Win)
+        if z1 is not None:
+            return self._conv_affine_eval(blk.conv2, params, bn, z1, None, 0, B, Hin, Win)
+        # conv1 is neither a Winograd nor a narrow layer (dec3.conv1: 128 -> 32 from two sources): its raw output
+        # feeds conv2's lean kernel, which applies bn1 + ReLU while staging AND bn2 + ReLU in its epilogue
+        y1, _, _, ss1 = self._conv_bn(blk.conv1, params, bn, d, skip, 1, B, Hin, Win)
+        z2 = self._conv_affine_eval(blk.conv2, params, bn, y1, None, 0, B, Hin, Win, in_ss=ss1)
+        if z2 is None:
+            z2 = self._bn_act(self._conv_bn(blk.conv2, params, bn, y1, None, 0, B, Hin, Win, in_ss=ss1)[0],
+                              bn.ss(blk.conv2), of=blk.conv2)
+        return z2
+
+    def _resunet_out(self, blk, params, d, skip, y2, ss2, B, H, W):
+        """ResUnet decoder block output: relu(y2 * scale2 + shift2) + identity_conv(up(d) | skip) + bias — the 1x1 identity
+        convolution over the virtual input, the join in dt_bn_act (relu = 2) with the constant-one scale"""
+        ic, dev = blk.idc, y2.device
+        idy = torch.empty((B, H, W, ic.cout), dtype=torch.float32, device=dev)
+        self._conv(self._conv_desc(ic, d, skip, 1, B, H, W), d, skip, ic.w(params), idy)
+        out = self._bn_act(y2, ss2, res=idy, res_ss=(self._const_vec(1.0, ic.cout, dev), ic.bias(params)), of=blk.conv2,
+                           relu=2)
+        del idy
+        return out
+
+    def _head_fwd(self, d, w, bias, logits, am64, am8, B, H, W, cin, K):
+        e0 = self._pb()
+        self._call("dt_head_fwd", d, w, bias, logits, am64, am8, B, H, W, cin, K)
+        self._pe(e0, "head_fwd_kernel", 2.0 * 9 * cin * K * B * H * W, 4.0 * B * H * W * (cin + K))
+
+    def _fuse_eval_rule(self, p):
+        """(encoder, decoder) run the inference forms with BatchNorm + ReLU (+ residual) in the convolution's epilogue:
+        an eval-mode pass that saves nothing — and the encoder alone when it is frozen and in eval mode under a
+        training decoder (nothing of it is saved)"""
+        kind, opt = self.spec.decoder_kind, self._fuse_eval_opt and self.winograd
+        dec = bool(opt and not p.dec_batch and not p.save and kind not in ("resunet", "unetplusplus"))
+        return dec or bool(opt and p.enc_frozen and not p.enc_batch and kind == "unet"), dec
+
     # ------------------------------------------------------------------ forward
     def forward(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor, training: bool,
                 save: bool, want_argmax: Optional[str] = None, nhwc: bool = False, enc_training: Optional[bool] = None,
                 enc_frozen: bool = False, recal: Optional[torch.Tensor] = None, decoder_only: bool = False):
-        """nhwc=True: the input already is the kernels' layout [B,H,W,C] (the tiled-inference gather produces it):
+        """The forward schedule (``engine_forward``) on the fp32 units -> (logits, arg-max map | None).
+        nhwc=True: the input already is the kernels' layout [B,H,W,C] (the tiled-inference gather produces it):
         no NCHW -> NHWC pass.  enc_training: BatchNorm mode of the encoder (stem + layers 1-4; default: `training`) —
         False with training=True is fine-tuning on the encoder's running statistics.  enc_frozen: the encoder's weights
         get no gradient: nothing of the encoder is saved for backward, and an encoder in eval mode runs the fused
@@ -140,251 +216,21 @@ class Fp32Schedule:
         BatchNorm's statistics are final — no normalise pass of the last convolution, no head — and returns (None, None).
         decoder_only (inference only): stop in front of the head and return the decoder output [B,H,W,16] it would read
         (``forward_eval_head`` hands it to the fused evaluation head)."""
-        sp = self.spec
-        self._recal = None
-        if sp.decoder_kind == "efficientunetplusplus" and (training or save or recal is not None or enc_training or enc_frozen):
-            raise NotImplementedError("decoder 'efficientunetplusplus' is inference only: its inverted-residual blocks have no "
-                                      "batch-statistics forward and no backward kernels (eval-mode BatchNorm, nothing saved)")
         if decoder_only and (training or save or recal is not None or enc_training):
             raise RuntimeError("decoder_only forward: inference only (eval-mode BatchNorm, nothing saved)")
         if recal is not None:
             if not training or save or enc_frozen:
                 raise RuntimeError("recalibration forward: training statistics, nothing saved, no frozen-encoder form")
-            if recal.dtype != torch.float32 or recal.device != x_nchw.device:
-                raise RuntimeError("recalibration forward: the momentum is a float32 tensor on the input's device")
             enc_training = True
-        if nhwc:
-            if x_nchw.dim() != 4 or x_nchw.shape[3] != sp.in_channels:
-                raise RuntimeError(f"expected NHWC input [B,H,W,{sp.in_channels}], got {tuple(x_nchw.shape)}")
-            B, H, W, Cin = x_nchw.shape
-        else:
-            if x_nchw.dim() != 4 or x_nchw.shape[1] != sp.in_channels:
-                raise RuntimeError(f"expected input [B,{sp.in_channels},H,W], got {tuple(x_nchw.shape)}")
-            B, Cin, H, W = x_nchw.shape
-        if H % 32 or W % 32:
-            raise RuntimeError(f"H and W must be divisible by 32 (encoder depth 5), got {H}x{W}")
-        if x_nchw.dtype != torch.float32 or not x_nchw.is_cuda:
-            raise RuntimeError("input must be a float32 CUDA/HIP tensor")
-        dev = x_nchw.device
-        x_nchw = x_nchw.contiguous()
-        if recal is not None:
-            self._recal, self.recal_launches = recal, []
-        sv = _Saved() if save else None
-        dec_training = training
-        enc_training = training if enc_training is None else bool(enc_training)
-        enc_save = save and not enc_frozen
         self._u_all = self._wino_fwd_weights(params)
-        bnws = self._buf("bnws", BnView.ws_floats(sp), device=dev)
-        # repeated inference calls (tiled prediction): the 46 eval-mode scale/shift launches are skipped while neither the
-        # parameters nor the running statistics changed (torch's version counters + the epochs of the raw device writes)
-        if training or enc_training:
-            self._bn_epoch += 1
-        akey = None if (training or enc_training or save) else (params.data_ptr(), params._version, self._weights_epoch, bnstate.data_ptr(),
-                                                bnstate._version, self._bn_epoch, bnws.data_ptr())
-        self._affine_fresh = akey is not None and self._ws.get("affine_key") == akey
-        self._ws["affine_key"] = akey
-        self._fuse_eval = (self._fuse_eval_opt and not training and not save and self.winograd
-                           and sp.decoder_kind not in ("resunet", "unetplusplus"))
-        dec_fuse_eval = self._fuse_eval
-        # a frozen encoder in eval mode: its layers take the fused inference form (nothing of it is saved)
-        if enc_frozen and not enc_training and self._fuse_eval_opt and self.winograd and sp.decoder_kind == "unet":
-            self._fuse_eval = True
-        training = enc_training
-        if save:
-            # mean/invstd are needed by backward: keep a private copy target per forward
-            bnws = torch.empty(BnView.ws_floats(sp), dtype=torch.float32, device=dev)
-            sv.d["bnws"] = bnws
-        bn = BnView(sp, bnws, bnstate)
-
-        if nhwc:
-            x = x_nchw
-        else:
-            x = torch.empty((B, H, W, Cin), dtype=torch.float32, device=dev)
-            self._call("dt_nchw_to_nhwc", x_nchw, x, B, Cin, H, W)
-
-        def keep(key, **kw):
-            if save:
-                sv.d[key] = kw
-
-        def keep_enc(key, **kw):
-            if enc_save:
-                sv.d[key] = kw
-
-        # ---- stem
-        if self._fuse_eval:     # inference: BatchNorm + ReLU in the stem kernel's epilogue, no raw output
-            f1, h, w_ = self._conv_affine_direct(sp.stem, params, bn, x, None, 0, B, H, W)
-        else:
-            y, h, w_, ss = self._conv_bn(sp.stem, params, bn, x, None, 0, B, H, W, training, save_stats=enc_save)
-            f1 = self._bn_act(y, ss, of=sp.stem)
-            keep_enc("stem", x=x, y=y, z=f1, Hin=H, Win=W)
-        hp, wp = (h + 2 - 3) // 2 + 1, (w_ + 2 - 3) // 2 + 1
-        pool = torch.empty((B, hp, wp, 64), dtype=torch.float32, device=dev)
-        amax = torch.empty((B, hp, wp, 64), dtype=torch.uint8, device=dev) if enc_save else None
-        self._call("dt_maxpool3x3s2", f1, pool, amax, B, h, w_, 64)
-        keep_enc("pool", amax=amax, H=h, W=w_)
-        self._tr("pool", pool)
-
-        feats = [f1]
-        cur, ch, cw = pool, hp, wp
-        for li, blocks in enumerate(sp.layers):
-            for bi, blk in enumerate(blocks):
-                xin = cur
-                if self._fuse_eval and blk.conv1.stride == 1 and blk.down is None:
-                    z1 = self._conv_affine_eval(blk.conv1, params, bn, xin, None, 0, B, ch, cw)
-                    out = None if z1 is None else self._conv_affine_eval(blk.conv2, params, bn, z1, None, 0, B, ch, cw,
-                                                                         res=xin)
-                    if out is not None:
-                        cur = out
-                        continue
-                if self._fuse_eval and blk.down is not None and blk.conv2.cout % 64 == 0:
-                    # first block of layers 2-4: relu(bn1(conv1)) and bn_d(down(x)) from the direct kernel's epilogue, the
-                    # join relu(bn2(conv2) + .) in the Winograd kernel's
-                    z1, h1, w1 = self._conv_affine_direct(blk.conv1, params, bn, xin, None, 0, B, ch, cw)
-                    rd, _, _ = self._conv_affine_direct(blk.down, params, bn, xin, None, 0, B, ch, cw, relu=False)
-                    out = self._conv_affine_eval(blk.conv2, params, bn, z1, None, 0, B, h1, w1, res=rd)
-                    if out is not None:
-                        cur, ch, cw = out, h1, w1
-                        continue
-                y1, h1, w1, ss1 = self._conv_bn(blk.conv1, params, bn, xin, None, 0, B, ch, cw, training,
-                                                save_stats=enc_save)
-                # z1 = relu(bn1(y1)) is virtual: conv2 applies it while staging y1 (A/B switch DT_MATERIALIZE_Z1:
-                # a stored activation instead, read by the plain convolution / weight-gradient kernels)
-                z1 = self._bn_act(y1, ss1, of=blk.conv1) if self._mat_z1 else None
-                y2, h2, w2, ss2 = self._conv_bn(blk.conv2, params, bn, y1 if z1 is None else z1, None, 0, B,
-                                                h1, w1, training, in_ss=ss1 if z1 is None else None, save_stats=enc_save)
-                if blk.down is not None:
-                    yd, _, _, ssd = self._conv_bn(blk.down, params, bn, xin, None, 0, B, ch, cw, training,
-                                                  save_stats=enc_save)
-                    out = self._bn_act(y2, ss2, res=yd, res_ss=ssd, of=blk.conv2)
-                else:
-                    yd = None
-                    out = self._bn_act(y2, ss2, res=xin, of=blk.conv2)
-                keep_enc(f"L{li}B{bi}", x=xin, y1=y1, z1=z1, y2=y2, yd=yd, out=out, Hin=ch, Win=cw, H=h2, W=w2)
-                cur, ch, cw = out, h2, w2
-            feats.append(cur)
-        # feats = [f1, f2, f3, f4, f5]
-        training, self._fuse_eval = dec_training, dec_fuse_eval
-        if sp.decoder_kind == "unetplusplus":
-            d, dh, dw = self._forward_unetpp(feats, params, bn, B, training, save, keep)
-            dec_blocks = []
-        elif sp.decoder_kind == "efficientunetplusplus":
-            d, dh, dw = self._forward_effunetpp(feats, params, bn, B)
-            dec_blocks = []
-        else:
-            d, dh, dw = feats[4], ch, cw
-            dec_blocks = sp.decoder
-        d_ss = None   # (scale, shift) when d is a raw conv output with a virtual activation
-        skips = [feats[3], feats[2], feats[1], feats[0], None]
-        for i, blk in enumerate(dec_blocks):
-            skip = skips[i]
-            Hin, Win = 2 * dh, 2 * dw
-            if sp.decoder_kind == "resunet":
-                # reference network/extra/resunet/decoder.py:40-52: conv1 -> conv2 (conv-BN-ReLU each, extra/modules.py)
-                # plus the 1x1 identity_conv (with bias) of the up-sampled + concatenated input; no activation after
-                # the sum.  The block output is a real tensor (the next block and the head read it).
-                y1, h1, w1, ss1 = self._conv_bn(blk.conv1, params, bn, d, skip, 1, B, Hin, Win, training,
-                                                save_stats=save)
-                y2, h2, w2, ss2 = self._conv_bn(blk.conv2, params, bn, y1, None, 0, B, h1, w1, training,
-                                                in_ss=ss1, save_stats=save)
-                ic = blk.idc
-                idy = torch.empty((B, Hin, Win, ic.cout), dtype=torch.float32, device=dev)
-                self._conv(self._conv_desc(ic, d, skip, 1, B, Hin, Win), d, skip, ic.w(params), idy)
-                out = self._bn_act(y2, ss2, res=idy, res_ss=(self._const_vec(1.0, ic.cout, dev), ic.bias(params)),
-                                   relu=2, of=blk.conv2)
-                del idy
-                self._tr(f"D{i}.out", out)
-                keep(f"D{i}", x=d, skip=skip, y1=y1, y2=y2, H=h1, W=w1)
-                d, dh, dw, d_ss = out, h2, w2, None
-                continue
-            if self._fuse_eval and d_ss is None:
-                z1 = self._conv_affine_eval(blk.conv1, params, bn, d, skip, 1, B, Hin, Win)
-                if z1 is not None:
-                    z2 = self._conv_affine_eval(blk.conv2, params, bn, z1, None, 0, B, Hin, Win)
-                else:
-                    # conv1 is neither a Winograd nor a narrow layer (dec3.conv1: 128 -> 32 from two sources): its raw output
-                    # feeds conv2's lean kernel, which applies bn1 + ReLU while staging AND bn2 + ReLU in its epilogue
-                    y1, _, _, ss1 = self._conv_bn(blk.conv1, params, bn, d, skip, 1, B, Hin, Win, training)
-                    z2 = self._conv_affine_eval(blk.conv2, params, bn, y1, None, 0, B, Hin, Win, in_ss=ss1)
-                    if z2 is None:
-                        z2 = self._bn_act(self._conv_bn(blk.conv2, params, bn, y1, None, 0, B, Hin, Win, training,
-                                                        in_ss=ss1)[0], bn.ss(blk.conv2), of=blk.conv2)
-                if z2 is not None:
-                    d, dh, dw, d_ss = z2, Hin, Win, None
-                    continue
-            y1, h1, w1, ss1 = self._conv_bn(blk.conv1, params, bn, d, skip, 1, B, Hin, Win, training,
-                                            in_ss=d_ss, save_stats=save)
-            z1 = self._bn_act(y1, ss1, of=blk.conv1) if (self._mat_z1 and blk.conv2.cout % 64 == 0) else None
-            y2, h2, w2, ss2 = self._conv_bn(blk.conv2, params, bn, y1 if z1 is None else z1, None, 0, B, h1, w1,
-                                            training, in_ss=ss1 if z1 is None else None, save_stats=save)
-            if self._recal is not None and i == len(sp.decoder) - 1:
-                self._recal = None              # every BatchNorm's statistics are final: nothing else to launch
-                return None, None
-            if i == len(sp.decoder) - 1 or (self._mat_z2 and sp.decoder[i + 1].conv1.cout % 64 == 0):
-                z2 = self._bn_act(y2, ss2, of=blk.conv2)   # the head kernel (or a Winograd conv1) reads a materialised activation
-                nxt, nxt_ss = z2, None
-            else:
-                z2 = None                        # virtual: the next block's conv1 applies bn2+relu while staging
-                nxt, nxt_ss = y2, ss2
-            keep(f"D{i}", x=d, x_virtual=d_ss is not None, skip=skip, y1=y1, z1=z1, y2=y2, z2=z2, H=h1, W=w1)
-            d, dh, dw, d_ss = nxt, h2, w2, nxt_ss
-
-        if decoder_only:
-            return d
-        # ---- head
-        hd = sp.head
-        K = hd.cout
-        logits = torch.empty((B, K, dh, dw), dtype=torch.float32, device=dev)
-        am64 = am8 = None
-        if want_argmax == "int64":
-            am64 = torch.empty((B, dh, dw), dtype=torch.int64, device=dev)
-        elif want_argmax == "uint8":
-            am8 = torch.empty((B, dh, dw), dtype=torch.uint8, device=dev)
-        if self._recal is not None:
-            self.recal_launches.append(("head", hd.key))
-            self._recal = None
-        e0 = self._pb()
-        self._call("dt_head_fwd", d, hd.w(params), hd.bias(params), logits, am64, am8, B, dh, dw, hd.cin, K)
-        self._pe(e0, "head_fwd_kernel", 2.0 * 9 * hd.cin * K * B * dh * dw, 4.0 * B * dh * dw * (hd.cin + K))
-        keep("head", x=d, H=dh, W=dw)
-        if save:
-            sv.d["B"] = B
-            sv.d["training"] = bool(training)
-            sv.d["enc_training"] = bool(enc_training)
-            sv.d["enc_frozen"] = bool(enc_frozen)
-            self.saved = sv
-        return logits, (am64 if am64 is not None else am8)
+        return self._forward(FP32_UNITS, x_nchw, params, bnstate, training, training if enc_training is None else enc_training,
+                             save, enc_frozen, recal, want_argmax, nhwc, decoder_only)
 
     def forward_eval_head(self, x_nchw: torch.Tensor, params: torch.Tensor, bnstate: torch.Tensor, labels, lu=None,
                           dist=None, gamma: float = 2.0, counts=None, err=None, want_argmax: bool = False):
         """eval-mode forward (the inference kernels of ``forward(training=False)``) that ends in the fused evaluation head
-        instead of dt_head_fwd: no logits tensor, no int64 arg-max map -> what ``ops.head_eval`` returns"""
-        from ..ops import head_eval
-        d = self.forward(x_nchw, params, bnstate, False, save=False, decoder_only=True)
-        hd = self.spec.head
-        return head_eval(d, hd.w(params).view(hd.cout, hd.k, hd.k, hd.cin), hd.bias(params), labels, lu, dist, gamma,
-                         counts, err, want_argmax)
-
-    # ------------------------------------------------------------------ Unet++ decoder (smp UnetPlusPlus)
-    def _forward_unetpp(self, feats, params, bn: BnView, B, training, save, keep):
-        """dense decoder of smp.UnetPlusPlus (wiring: reference network/extra/efficientunetplusplus/decoder.py:156-184):
-        every node x_{d}_{l} = DecoderBlock(up x2 of its lower node, cat of the nodes / encoder feature on its level).
-        Node outputs are materialised activations (they feed several consumers); conv2 reads conv1's raw output with the
-        BatchNorm+ReLU fused into its staging like everywhere else."""
-        sp = self.spec
-        nodes = {f"f{k}": feats[4 - k] for k in range(5)}     # f0 = deepest encoder feature ... f4 = stem output
-        for blk in sp.decoder:
-            low = nodes[blk.low]
-            Hin, Win = 2 * low.shape[1], 2 * low.shape[2]
-            skip, parts = (None, []) if not blk.cat else self._cat_channels([nodes[n] for n in blk.cat])
-            y1, h1, w1, ss1 = self._conv_bn(blk.conv1, params, bn, low, skip, 1, B, Hin, Win, training,
-                                            save_stats=save)
-            y2, h2, w2, ss2 = self._conv_bn(blk.conv2, params, bn, y1, None, 0, B, h1, w1, training,
-                                            in_ss=ss1, save_stats=save)
-            z2 = self._bn_act(y2, ss2, of=blk.conv2)
-            keep("P" + blk.name, x=low, skip=skip, parts=parts, y1=y1, y2=y2, z2=z2, H=h1, W=w1)
-            nodes[blk.name] = z2
-        out = nodes[sp.decoder[-1].name]
-        return out, out.shape[1], out.shape[2]
+        instead of dt_head_fwd -> what ``ops.head_eval`` returns"""
+        return self._forward_eval_head(FP32_UNITS, x_nchw, params, bnstate, labels, lu, dist, gamma, counts, err, want_argmax)
 
     # ------------------------------------------------------------------ EfficientUnet++ decoder (inference only)
     def _pwconv(self, c: ConvSpec, params, bn: BnView, src0, src1, up0, B, H, W, act=False, gate=None, res=None, out=None):
@@ -661,9 +507,24 @@ class Fp32Schedule:
         self._backward(FP32_UNITS, dlogits, params, grads, saved)
 
 
-# the fp32 units of the shared reverse schedule: plain functions of the engine (no engine holds, or is held by, this object)
+# the fp32 units of the two shared schedules: plain functions of the engine (no engine holds, or is held by, this object)
 FP32_UNITS = SimpleNamespace(
     dtype=torch.float32,
+    # ---- forward: unit launchers, the hooks for what is not the same sequence in bf16, the rules read per pass / per block
+    conv_bn=Fp32Schedule._conv_bn, bn_act=Fp32Schedule._bn_act, stem=Fp32Schedule._stem, maxpool=Fp32Schedule._maxpool,
+    fused_encoder_block=Fp32Schedule._fused_encoder_block, fused_unet_block=Fp32Schedule._fused_unet_block,
+    resunet_out=Fp32Schedule._resunet_out, head=Fp32Schedule._head_fwd, effunetpp=Fp32Schedule._forward_effunetpp,
+    fuse_eval=Fp32Schedule._fuse_eval_rule,
+    # the decoder kinds it runs: the inverted-residual blocks have inference kernels only
+    runs=lambda kind, inference: kind != "efficientunetplusplus" or inference,
+    # conv1's activation of an encoder / Unet decoder block is stored (eval-mode passes too); block i's output is (the last
+    # one always is): where the NEXT block's conv1 runs on the Winograd kernels
+    enc_z1_stored=lambda eng: eng._mat_z1,
+    dec_z1_stored=lambda eng, blk: eng._mat_z1 and blk.conv2.cout % 64 == 0,
+    dec_out_stored=lambda eng, i: eng._mat_z2 and eng.spec.decoder[i + 1].conv1.cout % 64 == 0,
+    saved_tail=lambda p: dict(training=p.dec_batch, enc_training=p.enc_batch, enc_frozen=p.enc_frozen),
+    decoder_output=lambda eng, x, params, bnstate: eng.forward(x, params, bnstate, False, save=False, decoder_only=True),
+    # ---- backward
     bn_bwd=Fp32Schedule._bn_bwd, wgrad=Fp32Schedule._wgrad, dgrad=Fp32Schedule._dgrad, dgrad_bn=Fp32Schedule._dgrad_bn,
     head_bwd=Fp32Schedule._head_bwd, upsample_bwd=Fp32Schedule._upsample_bwd, stem_wgrad=Fp32Schedule._stem_wgrad,
     fused_input_grad=Fp32Schedule._fused_input_grad, resunet_join=Fp32Schedule._resunet_join,

@@ -5,7 +5,8 @@ TEST INFRASTRUCTURE (see oracle/__init__.py).  PARITY UNPINNED for topology like
 restated smp ``Unet``/``resnet34`` graph — the module passed in IS a ``UNetR34Ref``); what this file adds is
 the *numerics contract* of the mixed-precision path: the reference trains under Lightning AMP
 (reference protocol.md:27, configs/trainer/default.yaml ``precision``) where torch.autocast decides the
-rounding points; the HIP path (deadtrees_amd/network/engine_bf16.py ``forward_bf16_train`` / ``backward_bf16``)
+rounding points; the HIP path (``forward_bf16_train`` / ``backward_bf16``: deadtrees_amd/network/engine_forward.py /
+engine_backward.py on the units of engine_bf16.py)
 fixes them explicitly, and this oracle rounds to bf16 at exactly those points while accumulating in
 fp64 (or fp32), so a parity test can separate "bf16 numerics" from "a mis-scheduled layer":
 
@@ -49,11 +50,12 @@ Two ways to use it (tests/test_bf16_gpu.py):
   off by one bf16 ulp): a wrong scale/shift pairing, a dropped residual or a missed gradient join shows up as an
   O(1) error in exactly the unit that has it.
 
-Follows deadtrees_amd/network/engine_bf16.py ``forward_bf16_train`` / ``backward_bf16`` step by step.
+Follows the two schedules of the engine step by step: deadtrees_amd/network/engine_forward.py ``_forward`` and
+engine_backward.py ``_backward``, with the rounding points of the bf16 units (engine_bf16.py ``BF16_UNITS``).
 
 The second contract: ``rounding=False`` (tests/test_fp32_e2e_gpu.py, tests/test_fp32_oracle_cpu.py)
   Every rounding point above becomes the identity; what stays is the unit structure and the unit names, which are
-  those of the fp32 engine as well (deadtrees_amd/network/engine_fp32.py ``forward`` / ``backward``), and the fp32
+  those of the fp32 pass as well (the same two schedules on engine_fp32.py ``FP32_UNITS``), and the fp32
   arithmetic both engines share: BatchNorm coefficients are fp32 vectors, ``y * scale + shift`` is an fp32 multiply
   followed by an fp32 add (no fma), so the ReLU mask recomputed from a forced ``y``, ``scale``, ``shift`` is the
   kernels' mask bit for bit.  Teacher-forced in fp64 this pins every unit of the fp32 training step: one unit's

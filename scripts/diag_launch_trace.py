@@ -8,7 +8,8 @@ script needs nothing from the tree under test but its public surface.  A line ho
 ``bn_state``, else as "device"; the stream as main or side; the return value.  Per configuration it also prints a SHA-256
 of logits (class map for inference), gradient buffer, ``bn_state`` and parameters.  The last line of a configuration is its
 extra output: the ``profile`` list (name, FLOPs, bytes) of a profiled one, (key, shape, dtype, SHA-256) of every tensor of
-``engine.trace`` in insertion order of a traced one, the error of one the tree refuses (``{"refused": ...}``).
+``engine.trace`` in insertion order of a traced one, the error of one the tree refuses (``{"refused": ...}``), the
+``recal_launches`` of a recalibration, hashes of what an inference call returns.
 
 Usage (GPU box, a few seconds per configuration at B = 2 / 64 x 64):
     python scripts/diag_launch_trace.py OUTDIR [configuration ...]      -> OUTDIR/<configuration>.jsonl, OUTDIR/hashes.json
@@ -102,6 +103,7 @@ def build(kind, rec):
 
 def configurations():
     """{name: (decoder kind, environment for the engine's construction, action(model, img, mask) -> extra output)}"""
+    import torch
     from deadtrees_amd.trainer import HipTrainer
 
     def step(precision, prepare=None, profile=False, trace=False):
@@ -144,6 +146,30 @@ def configurations():
         m.encoder.requires_grad_(False)
         m.encoder.eval()
 
+    def predict_nhwc(precision):
+        return lambda m, img, mask: {"classes": sha(m.predict_classes(img.permute(0, 2, 3, 1).contiguous(), dtype="uint8",
+                                                                      precision=precision, nhwc=True))}
+
+    def predict_twice(m, img, mask):       # the second call of a precision skips the eval-affine launches
+        return [sha(m.predict_logits(img, precision=p)) for p in ("fp32", "fp32", "bf16", "bf16")]
+
+    def eval_head(precision):
+        def run(m, img, mask):
+            head = m.engine.forward_bf16_eval_head if precision == "bf16" else m.engine.forward_eval_head
+            acc, counts, am, err = head(img, m.flat_params.detach(), m.bn_state, mask, want_argmax=True)
+            return [sha(acc), sha(counts), sha(am), int(err)]
+        return run
+
+    def nograd_forward(train):
+        def run(m, img, mask):
+            m.train(train)
+            with torch.no_grad():
+                return {"logits": sha(m(img))}
+        return run
+
+    def corner(action):                    # 32 x 32: the stem output is 16 wide -> the fp32 stem kernel with bf16 output
+        return lambda m, img, mask: action(m, img[:, :, :32, :32].contiguous(), mask[:, :32, :32].contiguous())
+
     cfg = {}
     for kind in KINDS:
         cfg[f"{kind}.step_fp32"] = (kind, {}, step("fp32"))
@@ -172,6 +198,28 @@ def configurations():
     cfg["unet.profiled_step_bf16"] = ("unet", {}, step("bf16", profile=True))
     cfg["unet.profiled_predict_fp32"] = ("unet", {}, predict("fp32", profile=True))
     cfg["unet.profiled_predict_bf16"] = ("unet", {}, predict("bf16", profile=True))
+    # what the forward schedule has beyond a step and a prediction
+    for kind in KINDS:
+        cfg[f"{kind}.predict_twice"] = (kind, {}, predict_twice)
+        cfg[f"{kind}.eval_head_fp32"] = (kind, {}, eval_head("fp32"))
+        cfg[f"{kind}.eval_head_bf16"] = (kind, {}, eval_head("bf16"))
+        if kind != "unet":
+            cfg[f"{kind}.recalibrate_fp32"] = (kind, {}, recal("fp32"))
+            cfg[f"{kind}.recalibrate_bf16"] = (kind, {}, recal("bf16"))
+    cfg["efficientunetplusplus.predict_fp32"] = ("efficientunetplusplus", {}, predict("fp32"))
+    cfg["efficientunetplusplus.eval_head_fp32"] = ("efficientunetplusplus", {}, eval_head("fp32"))
+    cfg["unet.predict_nhwc_fp32"] = ("unet", {}, predict_nhwc("fp32"))
+    cfg["unet.predict_nhwc_bf16"] = ("unet", {}, predict_nhwc("bf16"))
+    cfg["unet.no_fuse_eval_predict_fp32"] = ("unet", {"DT_FUSE_EVAL": "0"}, predict("fp32"))
+    cfg["unet.direct_predict_fp32"] = ("unet", {"DT_FP32_WINOGRAD": "0"}, predict("fp32"))
+    cfg["unet.nograd_train_forward_fp32"] = ("unet", {}, nograd_forward(True))
+    cfg["unet.nograd_eval_forward_fp32"] = ("unet", {}, nograd_forward(False))
+    cfg["unet.no_mat_z1_step_bf16"] = ("unet", {"DT_BF16_MAT_Z1": "0"}, step("bf16"))
+    cfg["unet.no_mat_dec_step_bf16"] = ("unet", {"DT_BF16_MAT_DEC": "0"}, step("bf16"))
+    cfg["unet.images_unfused_step_bf16"] = ("unet", {"DT_BF16_IMAGES_FUSED": "0"}, step("bf16"))
+    cfg["unet.corner32_step_bf16"] = ("unet", {}, corner(step("bf16")))
+    cfg["unet.corner32_predict_bf16"] = ("unet", {}, corner(predict("bf16")))
+    cfg["unet.eval_encoder_step_bf16"] = ("unet", {}, step("bf16", lambda m: m.encoder.eval()))     # refused
     return cfg
 
 

@@ -1,6 +1,6 @@
 """End-to-end parity of the bf16 training path (BASELINE configs[2]) against the ROUNDING-AWARE oracle
-(oracle/unet_bf16_ref.py: bf16 roundings at exactly the points where forward_bf16_train / backward_bf16 store
-bf16, wide accumulation in between).
+(oracle/unet_bf16_ref.py: bf16 roundings at exactly the points where forward_bf16_train / backward_bf16 — the schedules
+of engine_forward / engine_backward on BF16_UNITS — store bf16, wide accumulation in between).
 
 Three levels, tightest first:
 

@@ -1,7 +1,8 @@
 """Every unit of the fp32 training step against fp64, teacher-forced (the fp32 twin of
 tests/test_bf16_e2e_gpu.py::test_bf16_train_step_teacher_forced_against_rounding_oracle).
 
-One HIP training step (``engine_fp32.forward`` / ``backward``) with ``engine.trace`` on; every intermediate tensor —
+One HIP training step (``forward`` / ``backward``: the schedules of ``engine_forward`` / ``engine_backward`` on
+``FP32_UNITS``) with ``engine.trace`` on; every intermediate tensor —
 forward activations and BatchNorm coefficients out of the saved activations, every activation gradient of the
 hand-scheduled backward out of the trace — is compared with what the un-rounded oracle (oracle/unet_bf16_ref.py,
 ``rounding=False``, fp64) computes from the HIP path's OWN inputs of that unit, and then replaces the oracle's tensor.
