@@ -98,7 +98,9 @@ class DevicePool:
                      device=None, max_resident_bytes: Optional[int] = None):
         """A pool filled straight from ortho rasters instead of shards (``data/rasters.py`` states the contract, the
         array arithmetic of the reference's scripts/createdataset.py).  ``items`` yields ``(key, rgbn uint8 [4,h,w], mask
-        uint8 [h,w] | None, lu uint8 [h,w] | None)`` with h, w <= ``source_dim``; a field may also be a path that PIL opens.
+        uint8 [h,w] | None, lu uint8 [h,w] | None)`` with h, w <= ``source_dim``; a field may also be a path that PIL opens,
+        and mask / lu a ``PolygonSet`` in the raster's pixel coordinates (``data/polygons.py``), which is burnt on the
+        device into its slot of the staged raster instead of being uploaded (on the host: ``rasterize_host``).
         Every raster is zero-padded to ``source_dim`` and cut into ``tile_size`` sub-tiles named ``f"{key}_{i:03}"``.
         ``select``: ``"dead"`` (sub-tiles whose rounded dead-pixel percentage is > 0), ``"valid"`` (every non-blank one)
         or a callable ``(names, census) -> bool[n]``; blank sub-tiles (min == max over the four bands) are never taken.

@@ -148,8 +148,11 @@ def _open(x, mode: str) -> np.ndarray:
     return np.ascontiguousarray(arr.transpose(2, 0, 1)) if mode == "RGBA" else arr
 
 
-def load_item(item):
-    """``(key, rgbn, mask | None, lu | None)`` with arrays or paths -> the same with uint8 arrays [4,h,w] / [h,w]"""
+def load_item(item, keep_polygons: bool = False):
+    """``(key, rgbn, mask | None, lu | None)`` with arrays or paths -> the same with uint8 arrays [4,h,w] / [h,w].  A mask
+    or lu given as a ``PolygonSet`` in the raster's pixel coordinates (``data/polygons.py``) is burnt by ``rasterize_host``,
+    or, with ``keep_polygons``, handed on as it is for the caller to burn on the device."""
+    from .polygons import PolygonSet, rasterize_host
     if len(item) != 4:
         raise ValueError(f"a raster item is (key, rgbn, mask | None, lu | None), not {len(item)} fields")
     key, rgbn, mask, lu = item
@@ -158,6 +161,9 @@ def load_item(item):
         raise ValueError(f"raster {key!r}: rgbn must be uint8 [4,h,w], not {rgbn.dtype} {rgbn.shape}")
     maps = []
     for name, m in (("mask", mask), ("lu", lu)):
+        if isinstance(m, PolygonSet):
+            maps.append(m if keep_polygons else rasterize_host(m, rgbn.shape[1], rgbn.shape[2]))
+            continue
         m = None if m is None else _open(m, "L")
         if m is not None and (m.dtype != np.uint8 or m.shape != rgbn.shape[1:]):
             raise ValueError(f"raster {key!r}: {name} must be uint8 {list(rgbn.shape[1:])}, not {m.dtype} {list(m.shape)}")
@@ -228,6 +234,7 @@ def pool_from_rasters(items, tile_size: int = 256, source_dim: int = 2048, selec
     """What ``DevicePool.from_rasters`` does (see there).  ``record``: a dict that receives ``keys`` (the raster keys in
     order), ``table`` (the ``subtile_table`` rows of all rasters) and ``censuses`` (``(census, (h, w))`` per raster, as
     ``band_stats`` takes them)."""
+    from .polygons import PolygonSet, rasterize
     from .pool import DevicePool, _device_or_none
     t, S = int(tile_size), int(source_dim)
     if masks not in ("keep", "zero"):
@@ -248,7 +255,7 @@ def pool_from_rasters(items, tile_size: int = 256, source_dim: int = 2048, selec
     else:
         parts, count = [], 0
     for item in items:
-        key, rgbn, mask, lu = load_item(item)
+        key, rgbn, mask, lu = load_item(item, keep_polygons=on_gpu)
         h, w = rgbn.shape[1:]
         _check_geometry(S, t, h, w)
         names = subtile_names(key, n)
@@ -258,11 +265,16 @@ def pool_from_rasters(items, tile_size: int = 256, source_dim: int = 2048, selec
             host[:at] = rgbn.reshape(-1)
             views = [None, None]
             for j, m in enumerate((mask, lu)):
-                if m is not None:
+                if m is not None and not isinstance(m, PolygonSet):
                     host[at:at + hw] = m.reshape(-1)
                     views[j] = (at, at + hw)
                     at += hw
             staged[:at].copy_(pinned[:at], non_blocking=True)                      # the one upload
+            for j, m in enumerate((mask, lu)):                                     # polygon planes are burnt into their
+                if isinstance(m, PolygonSet):                                      # slots behind it, not uploaded
+                    views[j] = (at, at + hw)
+                    rasterize(m, (h, w), out=staged[at:at + hw].view(h, w))
+                    at += hw
             d_rgbn = staged[:4 * hw].view(4, h, w)
             d_mask, d_lu = (None if v is None else staged[v[0]:v[1]].view(h, w) for v in views)
             ops.raster_cut(d_rgbn, d_mask, d_lu, S, t, census=census_dev)

@@ -240,9 +240,11 @@ class Tiler:
     def stats(self, zones=None, classes: int = 3, n_zones: Optional[int] = None, patches=None):
         """``RasterStats`` of ``result`` (``stats.zonal_counts_host``): what ``infer_tile(..., stats=True)`` returns, for a
         caller of the reference's own ``get_batches`` / ``put_batches`` loop.  ``zones``: uint8 [h, w] on the raster's grid
-        (``n_zones`` defaults to ``zones.max() + 1``); ``classes``: the model's class count.  ``patches`` (True or a
+        (``n_zones`` defaults to ``zones.max() + 1``) or a ``PolygonSet`` in its pixel coordinates (burnt by
+        ``rasterize_host``; ``n_zones`` defaults to the largest value + 1); ``classes``: the model's class count.  ``patches`` (True or a
         ``PatchConfig``): the statistics carry the ``PatchTable`` of the map (``patches.patches_host``); a configuration
         that sieves changes ``result`` itself, and the counts are those of the sieved map"""
+        from ..data.polygons import PolygonSet, rasterize_host
         from .patches import patches_host
         from .stats import RasterStats, check_zones, zonal_counts_host
         if self._outdata is None:
@@ -250,6 +252,8 @@ class Tiler:
         config = check_patches(patches)
         result = self.result
         zones, Z = check_zones(zones, result.shape, n_zones)
+        if isinstance(zones, PolygonSet):
+            zones = rasterize_host(zones, result.shape[0], result.shape[1])
         table = None
         if config is not None:
             sieved, table = patches_host(result, classes, config)
@@ -277,7 +281,8 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
     holds only 0 / 255 (``is_valid_tile``, :60-62) are skipped like the reference does — ``(key, None)`` — without a
     forward pass (device reduction over the uploaded raster, ``ops.band_has_data``).  ``overlap`` / ``blend`` /
     ``return_probs`` / ``tta`` / ``stats`` / ``n_zones`` / ``patches``: as in ``infer_tile`` (every raster stays on its rank, so overlap
-    needs no exchange); ``zones``: a callable ``key -> uint8 [h, w] array or None``, or a mapping (a missing key is None).
+    needs no exchange); ``zones``: a callable ``key -> uint8 [h, w] array, PolygonSet or None``, or a mapping (a missing
+    key is None).
     The second item of every pair is whatever ``infer_tile`` returned: with ``stats=True`` ``(map, RasterStats)`` — the
     ``RasterStats`` of a rank's share add up (``+``) to that rank's part of the regional totals."""
     if zones is not None and not stats:
@@ -322,7 +327,11 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     the year-to-year transition matrix) splits the counts by zone, ``n_zones`` (<= 8) defaults to ``zones.max() + 1``.  On
     every device path the zones are uploaded next to the raster and ONE ``ops.zonal_counts`` runs on the final device map
     before its download; the host path (``on_device=False``, ``world > 1``, CPU) counts the merged map with
-    ``zonal_counts_host``.  The map is the one the call without ``stats`` returns.
+    ``zonal_counts_host``.  The map is the one the call without ``stats`` returns.  ``zones`` may also be a ``PolygonSet``
+    in the raster's pixel coordinates (``data/polygons.py``: forest masks and stand boundaries arrive as polygons; zone ids
+    as values, 0 outside every polygon, ``n_zones`` defaults to the largest value + 1): on the device paths the plane is
+    burnt on the device (``ops.rasterize_polygons``) in place of its upload, on the host path by ``rasterize_host``; maps
+    and counts are those of the call with the burnt array.
 
     ``patches=True`` or a ``PatchConfig(connectivity=8, min_pixels=0)`` (needs ``stats=True``): the ``RasterStats`` carries
     the map's ``PatchTable`` as ``.patches`` (``deployment/patches.py``: one row per connected dead-tree patch).  On every
@@ -409,7 +418,8 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
 
 def _upload(inference, arr_chw_u8: np.ndarray, device: str, skip_blank: bool, want_stats):
     """the start of every device path: ONE uint8 H2D copy of the band planes the network reads (the N of an RGBN raster
-    under an RGB model stays on the host), the zones map of a ``stats=True`` call uploaded next to it (None without one),
+    under an RGB model stays on the host), the zones map of a ``stats=True`` call uploaded next to it (None without one;
+    a ``PolygonSet`` is rasterised on the device instead),
     and ``skip_blank``'s ``is_valid_tile`` on the uploaded raster.  Returns ``(raster, zones)`` on the device, or None for
     a raster with nothing but 0 / 255 in band 1"""
     C = arr_chw_u8.shape[0]
@@ -419,7 +429,11 @@ def _upload(inference, arr_chw_u8: np.ndarray, device: str, skip_blank: bool, wa
     x = torch.from_numpy(np.ascontiguousarray(arr_chw_u8)).to(device, non_blocking=True)
     zones_dev = None
     if want_stats is not None and want_stats[0] is not None:
-        zones_dev = torch.from_numpy(np.ascontiguousarray(want_stats[0])).to(device, non_blocking=True)
+        from ..data.polygons import PolygonSet, rasterize
+        if isinstance(want_stats[0], PolygonSet):          # burnt where it is read: the tables travel, not the plane
+            zones_dev = rasterize(want_stats[0], arr_chw_u8.shape[1:], device=x.device)
+        else:
+            zones_dev = torch.from_numpy(np.ascontiguousarray(want_stats[0])).to(device, non_blocking=True)
     if skip_blank:
         from .. import ops
         if int(ops.band_has_data(x[0])) == 0:

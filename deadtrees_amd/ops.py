@@ -1167,6 +1167,34 @@ def raster_cut(rgbn: torch.Tensor, mask: Optional[torch.Tensor] = None, lu: Opti
     return census
 
 
+def rasterize_polygons(edges: torch.Tensor, polys: torch.Tensor, shape, all_touched: bool = True,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Polygons burnt into a uint8 [h, w] map on the device (``dt_rasterize_polygons_u8``, csrc/polygons.hip; the contract
+    is ``data.polygons.rasterize_host``).  ``edges`` int32 [E, 4] and ``polys`` int32 [P, 8] are ``PolygonSet.tables()`` on
+    the device, contiguous; P = 0 gives zeros.  ``out``: a contiguous uint8 [h, w] tensor at any storage offset (a view
+    into a larger buffer: only its own bytes are written), allocated when not given; every byte of it is written.  One
+    launch, no host synchronisation.  Returns ``out``."""
+    _gpu(edges, polys, out)
+    h, w = int(shape[0]), int(shape[1])
+    dev = edges.device
+    if edges.dtype != torch.int32 or edges.dim() != 2 or edges.shape[1] != 4 or not edges.is_contiguous():
+        raise RuntimeError(f"rasterize_polygons: edges must be contiguous int32 [E,4], not {edges.dtype} {tuple(edges.shape)}")
+    if (polys.dtype != torch.int32 or polys.dim() != 2 or polys.shape[1] != 8 or not polys.is_contiguous()
+            or polys.device != dev):
+        raise RuntimeError(f"rasterize_polygons: polys must be contiguous int32 [P,8] on {dev}, not {polys.dtype} "
+                           f"{tuple(polys.shape)}")
+    if out is None:
+        if h < 1 or w < 1:
+            raise RuntimeError(f"rasterize_polygons: raster {h}x{w} must be at least 1x1")
+        out = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (h, w) or out.device != dev or not out.is_contiguous():
+        raise RuntimeError(f"rasterize_polygons: out must be contiguous uint8 [{h},{w}] on {dev}")
+    E, P = int(edges.shape[0]), int(polys.shape[0])
+    _lib.check(_lib.load().dt_rasterize_polygons_u8(_p(edges) if E else None, E, _p(polys) if P else None, P, h, w,
+                                                    1 if all_touched else 0, _p(out), _st()), "dt_rasterize_polygons_u8")
+    return out
+
+
 def _patch_tile():
     th, tw = C.c_int(0), C.c_int(0)
     _lib.check(_lib.load().dt_patch_tile(C.byref(th), C.byref(tw)), "dt_patch_tile")

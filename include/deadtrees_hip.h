@@ -502,6 +502,22 @@ int dt_raster_cut_u8(const uint8_t* rgbn_chw, const uint8_t* mask, const uint8_t
                      const int32_t* slot, int64_t pool_rows, uint8_t* images, uint8_t* masks, uint8_t* lu_out,
                      uint64_t* sums, int64_t* census, void* stream);
 
+/* Masks and zones from polygons (data/polygons.py states the contract): exact all-touched rasterisation of polygons on a
+ * fixed-point pixel grid of 1/256 pixel into out uint8 [h][w], every byte written; h, w in 1..16384; `out` may have any
+ * byte alignment (a view into a larger buffer).  Pixel (i, j) is the square (256 j, 256 j + 256) x (256 i, 256 i + 256).
+ * edges int32 [n_edges][4] = (ax, ay, bx, by), |coordinate| <= 2^23: every ring closed, every edge taken upwards (ay < by,
+ *   or ay == by and ax < bx), zero-length segments left out; n_edges <= 0x7fff0000.
+ * polys int32 [n_polys][8] = (minx, miny, maxx, maxy, e0, e1, value, 0): the bounding box of the polygon's vertices, its
+ *   edges e0 .. e1 (all its rings: even-odd parity) and its value in 1..255.  Both tables 16-byte aligned.
+ * A polygon burns a pixel iff the pixel's centre is inside it (crossing number of the ray to +x, half-open rule ay <= cy <
+ * by, side from the sign of the exact cross product) or, with all_touched != 0, one of its edges meets the pixel's open
+ * square (bounding boxes strictly overlap in x and y, and the four corners' cross products against the edge have min < 0 <
+ * max).  A pixel gets the minimum value among the polygons that burn it, 0 if none does.
+ * One launch, integers only, no atomics, no scratch memory, no capacity limit (polygons per tile and edges per polygon
+ * stream through LDS in chunks), no synchronisation: the map is a pure function of the tables. */
+int dt_rasterize_polygons_u8(const int32_t* edges, int64_t n_edges, const int32_t* polys, int n_polys, int h, int w,
+                             int all_touched, uint8_t* out, void* stream);
+
 /* Signed Euclidean distance maps of the boundary loss, computed on the device in place of the
  * loader's scipy pass: data/deadtreedata.py:182-185 -> loss/losses.py:159-178 one_hot2dist(resolution=[1,1]).
  * labels int64 [B,H,W] -> dist fp32 [B,K,H,W]; per class: floor(edt to the class) outside it, 1 - floor(edt to the
