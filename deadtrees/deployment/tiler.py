@@ -3,3 +3,5 @@ from deadtrees_amd.deployment.tiler import TileInfo, Tiler, divisible_without_re
 from deadtrees_amd.deployment.tiler import blend_ramp, window_grid  # noqa: F401  (overlap-stitch geometry)
 from deadtrees_amd.deployment.tiler import tta_views  # noqa: F401  (test-time augmentation views)
 from deadtrees_amd.deployment.tiler import PatchConfig, PatchTable  # noqa: F401  (dead-tree patches of a map)
+from deadtrees_amd.deployment.tiler import (outlines_geojson, polygonize, polygonize_host,  # noqa: F401  (their outlines)
+                                            write_outlines_geojson)

@@ -169,6 +169,13 @@ SIGNATURES = {
     "dt_patch_areas": (C.c_int, [c_f, C.c_int, C.c_int, c_f, c_f]),
     "dt_sieve_patches_u8": (C.c_int, [c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, c_f]),
     "dt_patch_measure": (C.c_int, [c_f, c_f, C.c_int, C.c_int, c_f, C.c_int, c_f, c_f, c_f, c_f, c_f]),
+    "dt_outline_chunk": (C.c_int, [C.POINTER(C.c_int)]),
+    "dt_outline_count": (C.c_int, [c_f, C.c_int, C.c_int, c_f, c_f]),
+    "dt_outline_edges": (C.c_int, [c_f, C.c_int, C.c_int, C.c_int, c_f, C.c_int, c_f, c_f, c_f, c_f]),
+    "dt_outline_rounds": (C.c_int, [C.c_int]),
+    "dt_outline_jump": (C.c_int, [c_f, c_f, C.c_int, c_f, c_f]),
+    "dt_outline_rings": (C.c_int, [c_f, C.c_int, C.c_int, C.c_int, c_f, c_f, c_f, C.c_int, c_f, C.c_int, c_f, c_f, c_f]),
+    "dt_outline_scatter": (C.c_int, [c_f, c_f, C.c_int, C.c_int, c_f, c_f, C.c_int, I64, c_f, c_f]),
     "dt_signed_distmap_workspace": (I64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "dt_signed_distmap": (C.c_int, [c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, c_f]),
     "dt_conv2d_bf16_stat_rows": (C.c_int, [_P]),

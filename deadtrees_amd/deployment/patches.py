@@ -245,11 +245,18 @@ def sieve_host(classes_u8, labels, min_pixels: int):
     return c, lab
 
 
-def patches_host(classes_u8, K: int, config: PatchConfig):
-    """label -> sieve -> measure on the host: (classes', PatchTable) — what the host paths of ``infer_tile`` and
-    ``Tiler.stats`` run; ``classes'`` is ``classes_u8`` itself when the configuration does not sieve"""
+def labelled_patches_host(classes_u8, K: int, config: PatchConfig):
+    """label -> sieve -> measure on the host: (classes', labels', PatchTable); ``classes'`` is ``classes_u8`` itself when
+    the configuration does not sieve, ``labels'`` the label plane of ``classes'``"""
     c = np.ascontiguousarray(classes_u8)
     labels = label_patches_host(c, K, config.connectivity)
     if config.sieves:
         c, labels = sieve_host(c, labels, config.min_pixels)
-    return c, measure_patches_host(labels, c)
+    return c, labels, measure_patches_host(labels, c)
+
+
+def patches_host(classes_u8, K: int, config: PatchConfig):
+    """``labelled_patches_host`` without the label plane: (classes', PatchTable) — what the host paths of ``infer_tile``
+    and ``Tiler.stats`` run"""
+    c, _, table = labelled_patches_host(classes_u8, K, config)
+    return c, table

@@ -64,9 +64,11 @@ class RasterStats:
     """the counts table of one raster (or of a sum of rasters) and the reference's figures read off it.  ``counts`` int64
     [Z, K]: rows zones, columns classes; class 0 is background, classes >= 1 are dead trees.  ``patches``: the raster's
     ``PatchTable`` (``deployment/patches.py``) when one was asked for, else None; a sum of rasters has none, because the
-    tables of different rasters do not share a grid"""
+    tables of different rasters do not share a grid.  ``outlines``: the patches' outlines (``deployment/outlines.py``: a
+    ``PolygonSet`` on the raster's grid, polygon ``k`` is row ``k`` of ``patches``) when they were asked for, else None;
+    a sum of rasters has none either"""
 
-    def __init__(self, counts, pixel_area_m2: float = PIXEL_AREA_M2, patches=None):
+    def __init__(self, counts, pixel_area_m2: float = PIXEL_AREA_M2, patches=None, outlines=None):
         counts = np.array(counts, dtype=np.int64)
         if counts.ndim != 2 or counts.shape[0] < 1 or counts.shape[1] < 2:
             raise ValueError(f"RasterStats: counts must be [Z >= 1, K >= 2], got shape {counts.shape}")
@@ -80,10 +82,21 @@ class RasterStats:
             if not isinstance(patches, PatchTable):
                 raise ValueError(f"RasterStats: patches must be a PatchTable or None, got {type(patches).__name__}")
         self._patches = patches
+        if outlines is not None:
+            from ..data.polygons import PolygonSet
+            if not isinstance(outlines, PolygonSet):
+                raise ValueError(f"RasterStats: outlines must be a PolygonSet or None, got {type(outlines).__name__}")
+            if patches is None or len(outlines) != patches.n:
+                raise ValueError("RasterStats: outlines need the PatchTable they belong to (one polygon per row)")
+        self._outlines = outlines
 
     @property
     def patches(self):
         return self._patches
+
+    @property
+    def outlines(self):
+        return self._outlines
 
     @property
     def counts(self) -> np.ndarray:
@@ -128,16 +141,21 @@ class RasterStats:
     def __eq__(self, other) -> bool:
         if not isinstance(other, RasterStats):
             return NotImplemented
-        if (self._patches is None) != (other._patches is None):
+        if (self._patches is None) != (other._patches is None) or (self._outlines is None) != (other._outlines is None):
             return False
         return (self._counts.shape == other._counts.shape and bool((self._counts == other._counts).all())
                 and self.pixel_area_m2 == other.pixel_area_m2
-                and (self._patches is None or self._patches == other._patches))
+                and (self._patches is None or self._patches == other._patches)
+                and (self._outlines is None or all(
+                    np.array_equal(getattr(self._outlines, a), getattr(other._outlines, a))
+                    for a in ("xy", "ring_offsets", "ring_polygon", "values"))))
 
     __hash__ = None
 
     def __repr__(self) -> str:
         tail = "" if self._patches is None else f", patches={self._patches!r}"
+        if self._outlines is not None:
+            tail += f", outlines={self._outlines!r}"
         return f"RasterStats(counts={self._counts.tolist()}, pixel_area_m2={self.pixel_area_m2!r}{tail})"
 
 

@@ -26,7 +26,19 @@ from typing import List, Optional, Tuple, Union
 import numpy as np
 import torch
 
+from .outlines import outlines_geojson, polygonize, polygonize_host, write_outlines_geojson  # noqa: F401
 from .patches import PatchConfig, PatchTable, check_patches  # noqa: F401  (the ``patches`` argument of infer_tile)
+
+
+def check_outlines(outlines, config, who: str) -> bool:
+    """the ``outlines`` argument of ``infer_tile`` / ``Tiler.stats`` -> bool; outlines without patches are a ``ValueError``"""
+    if outlines is None:
+        return False
+    if not isinstance(outlines, bool):
+        raise ValueError(f"{who}: outlines must be True, False or None, got {outlines!r}")
+    if outlines and config is None:
+        raise ValueError(f"{who}: outlines need patches (the outlines are those of the PatchTable's patches)")
+    return outlines
 
 
 def divisible_without_remainder(a, b):
@@ -237,30 +249,37 @@ class Tiler:
         """the merged class map cropped to the raster size (what ``write_file`` stores)"""
         return self._outdata[0:self._tile_info.size[0], 0:self._tile_info.size[1]]
 
-    def stats(self, zones=None, classes: int = 3, n_zones: Optional[int] = None, patches=None):
+    def stats(self, zones=None, classes: int = 3, n_zones: Optional[int] = None, patches=None, outlines=None):
         """``RasterStats`` of ``result`` (``stats.zonal_counts_host``): what ``infer_tile(..., stats=True)`` returns, for a
         caller of the reference's own ``get_batches`` / ``put_batches`` loop.  ``zones``: uint8 [h, w] on the raster's grid
         (``n_zones`` defaults to ``zones.max() + 1``) or a ``PolygonSet`` in its pixel coordinates (burnt by
         ``rasterize_host``; ``n_zones`` defaults to the largest value + 1); ``classes``: the model's class count.  ``patches`` (True or a
         ``PatchConfig``): the statistics carry the ``PatchTable`` of the map (``patches.patches_host``); a configuration
-        that sieves changes ``result`` itself, and the counts are those of the sieved map"""
+        that sieves changes ``result`` itself, and the counts are those of the sieved map.  ``outlines=True`` (needs
+        ``patches``): the statistics also carry the patches' outlines (``outlines.polygonize_host`` on the final label
+        plane), polygon ``k`` for row ``k`` of the table"""
         from ..data.polygons import PolygonSet, rasterize_host
-        from .patches import patches_host
+        from .outlines import outlines_from_labels
+        from .patches import labelled_patches_host
         from .stats import RasterStats, check_zones, zonal_counts_host
         if self._outdata is None:
             raise RuntimeError("Tiler: load_file / load_array first")
         config = check_patches(patches)
+        outlines = check_outlines(outlines, config, "Tiler.stats")
         result = self.result
         zones, Z = check_zones(zones, result.shape, n_zones)
         if isinstance(zones, PolygonSet):
             zones = rasterize_host(zones, result.shape[0], result.shape[1])
-        table = None
+        table = rings = None
         if config is not None:
-            sieved, table = patches_host(result, classes, config)
+            sieved, labels, table = labelled_patches_host(result, classes, config)
+            if outlines:
+                rings = outlines_from_labels(labels, sieved, config.connectivity)
             if config.sieves:
                 self._outdata[0:result.shape[0], 0:result.shape[1]] = sieved
                 result = self.result
-        return RasterStats(zonal_counts_host(np.ascontiguousarray(result), zones, classes, Z), patches=table)
+        return RasterStats(zonal_counts_host(np.ascontiguousarray(result), zones, classes, Z), patches=table,
+                           outlines=rings)
 
     def write_file(self, outfile: Union[str, Path]) -> None:
         """reference tiler.py:136-142 (LZW-compressed tiled GeoTIFF through rioxarray)"""
@@ -274,13 +293,13 @@ class Tiler:
 def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, rank: int = 0, world: int = 1,
                   device: str = "cuda", tile_shape: Optional[Tuple[int, int]] = None, skip_blank: bool = True,
                   overlap: int = 0, blend: str = "crop", return_probs: bool = False, tta=None, stats: bool = False,
-                  zones=None, n_zones: Optional[int] = None, patches=None):
+                  zones=None, n_zones: Optional[int] = None, patches=None, outlines=None):
     """the directory loop of scripts/inference.py:71-115 over in-memory rasters (GeoTIFF I/O needs rioxarray, absent
     here): ``rasters`` yields ``array`` or ``(key, array)``; rank r of ``world`` takes rasters r, r + world, ... (tiles are
     independent: no collective).  Yields ``(key, class_map)`` in input order of the rank's share; rasters whose band 1
     holds only 0 / 255 (``is_valid_tile``, :60-62) are skipped like the reference does — ``(key, None)`` — without a
     forward pass (device reduction over the uploaded raster, ``ops.band_has_data``).  ``overlap`` / ``blend`` /
-    ``return_probs`` / ``tta`` / ``stats`` / ``n_zones`` / ``patches``: as in ``infer_tile`` (every raster stays on its rank, so overlap
+    ``return_probs`` / ``tta`` / ``stats`` / ``n_zones`` / ``patches`` / ``outlines``: as in ``infer_tile`` (every raster stays on its rank, so overlap
     needs no exchange); ``zones``: a callable ``key -> uint8 [h, w] array, PolygonSet or None``, or a mapping (a missing
     key is None).
     The second item of every pair is whatever ``infer_tile`` returned: with ``stats=True`` ``(map, RasterStats)`` — the
@@ -289,6 +308,7 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
         raise ValueError("infer_rasters: zones need stats=True")
     if check_patches(patches) is not None and not stats:
         raise ValueError("infer_rasters: patches need stats=True")
+    check_outlines(outlines, check_patches(patches), "infer_rasters")
     for i, item in enumerate(rasters):
         if i % world != rank:
             continue
@@ -296,14 +316,14 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
         z = None if zones is None else zones(key) if callable(zones) else zones.get(key)
         yield key, infer_tile(inference, arr, subtile=subtile, batch_size=batch_size, device=device, tile_shape=tile_shape,
                               skip_blank=skip_blank, overlap=overlap, blend=blend, return_probs=return_probs, tta=tta,
-                              stats=stats, zones=z, n_zones=n_zones, patches=patches)
+                              stats=stats, zones=z, n_zones=n_zones, patches=patches, outlines=outlines)
 
 
 def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size: int = 64, rank: int = 0,
                world: int = 1, device: str = "cuda", group=None, tile_shape: Optional[Tuple[int, int]] = None,
                on_device: Optional[bool] = None, skip_blank: bool = False, overlap: int = 0, blend: str = "crop",
                return_probs: bool = False, tta=None, stats: bool = False, zones=None, n_zones: Optional[int] = None,
-               patches=None):
+               patches=None, outlines=None):
     """whole-tile inference of scripts/inference.py:80-115 on the MI355X path: split -> (uint8 H2D, normalise on the
     device) -> forward + fused argmax -> uint8 D2H -> merge.  With world > 1 the sub-tile batches j = rank (mod world)
     are processed locally and the uint8 class maps are all-gathered (no other collective: tiles are independent).
@@ -339,11 +359,19 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     download (``ops.label_patches`` / ``patch_areas`` / ``sieve_patches`` / ``patch_table``); the host path runs the same
     contract in numpy / scipy.  With a sieve the returned map is the sieved one and ``counts`` are the counts of the
     RETURNED map; the probabilities of ``return_probs`` are not touched by the sieve.  With ``min_pixels <= 1`` the map is
-    bit-identical to the call without ``patches``."""
+    bit-identical to the call without ``patches``.
+
+    ``outlines=True`` (needs ``patches``): the ``RasterStats`` also carries ``.outlines``, a ``PolygonSet`` on the raster's
+    grid with one polygon per patch — polygon ``k`` is row ``k`` of ``.patches`` (``deployment/outlines.py``: exact ring
+    tracing along the pixel edges; ``outlines_geojson`` writes them out).  On every device path they are traced from the
+    final label plane, after the sieve, in HBM before the map leaves the device (``ops.patch_outlines``: only the four
+    ``PolygonSet`` arrays are downloaded); the host path runs ``polygonize_host``.  The map, the counts and the table are
+    those of the call without ``outlines``."""
     if blend not in ("crop", "average"):
         raise ValueError(f"blend {blend!r}: use 'crop' or 'average'")
     want_stats = None
     config = check_patches(patches)
+    outlines = check_outlines(outlines, config, "infer_tile")
     if not stats:
         if zones is not None or n_zones is not None:
             raise ValueError("infer_tile: zones / n_zones need stats=True")
@@ -355,7 +383,7 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
         K = getattr(inference, "classes", None)
         if K is None:
             raise ValueError("infer_tile: stats=True needs an inference object with a `classes` count")
-        want_stats = (zones, int(K), Z, config)
+        want_stats = (zones, int(K), Z, config, outlines)
     members = getattr(inference, "members", None)
     if overlap or tta is not None or members is not None:
         views = None if tta is None else tta_views(tta)
@@ -443,18 +471,19 @@ def _upload(inference, arr_chw_u8: np.ndarray, device: str, skip_blank: bool, wa
 
 def _download(out: torch.Tensor, probs: Optional[torch.Tensor], want_stats, zones_dev):
     """the end of every device path: the D2H copy of the final map ``out`` (uint8 [h, w], contiguous) and of the
-    probabilities when there are any.  With ``want_stats`` = (zones, K, Z, patch config) one ``ops.zonal_counts`` is enqueued
+    probabilities when there are any.  With ``want_stats`` = (zones, K, Z, patch config, outlines) one ``ops.zonal_counts`` is enqueued
     on ``out`` BEFORE the download (no synchronisation of its own); the counts and the flag are read after the map has
     arrived.  With a patch configuration ``out`` is labelled, its patch areas are taken and — if the configuration sieves —
     it is sieved IN PLACE, all before the counts; the roots are compacted and measured behind the download (the compaction
     reads the row count back).  Labels, the area plane (reused as the root -> row plane) and the compaction's flags are
-    the workspace: about 12 bytes per pixel next to the map"""
+    the workspace: about 12 bytes per pixel next to the map.  With ``outlines`` the final label plane is traced behind the
+    table (``ops.patch_outlines``: two more scalar read-backs, 4 bytes per pixel and 40 per boundary edge of workspace)"""
     if want_stats is None:
         return out.cpu().numpy() if probs is None else (out.cpu().numpy(), probs.cpu().numpy())
     from .. import ops
     from .stats import RasterStats
-    _, K, Z, config = want_stats
-    labels = area = table = None
+    _, K, Z, config, outlines = want_stats
+    labels = area = table = rings = None
     err = torch.zeros(1, dtype=torch.int32, device=out.device)
     if config is not None:
         labels, _ = ops.label_patches(out, K, config.connectivity, err=err)
@@ -466,6 +495,8 @@ def _download(out: torch.Tensor, probs: Optional[torch.Tensor], want_stats, zone
     if host is not None:
         host.copy_(out, non_blocking=True)                      # enqueued; the table's read-back waits for it
         table = ops.patch_table(labels, out, area, reuse_area_plane=True)
+        if outlines:
+            rings = ops.patch_outlines(labels, out, config.connectivity)
         torch.cuda.current_stream(out.device).synchronize()
         result = (host.numpy(),)
     else:
@@ -476,7 +507,7 @@ def _download(out: torch.Tensor, probs: Optional[torch.Tensor], want_stats, zone
     if flag:          # cannot happen with checked zones: the map is an argmax over K classes
         raise RuntimeError(f"infer_tile: raster statistics met a value out of range (flag {flag}: 1 class >= {K}, "
                            f"2 zone >= {Z})")
-    return result + (RasterStats(counts.cpu().numpy(), patches=table),)
+    return result + (RasterStats(counts.cpu().numpy(), patches=table, outlines=rings),)
 
 
 def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch_size: int, device: str,

@@ -1201,11 +1201,21 @@ def _patch_tile():
     return th.value, tw.value
 
 
+def _outline_chunk():
+    chunk = C.c_int(0)
+    _lib.check(_lib.load().dt_outline_chunk(C.byref(chunk)), "dt_outline_chunk")
+    return chunk.value
+
+
 def __getattr__(name):
     # PATCH_TILE = (th, tw): the tile of dt_label_patches_u8's local launch, asked of the library on first use
     if name == "PATCH_TILE":
         globals()["PATCH_TILE"] = _patch_tile()
         return globals()["PATCH_TILE"]
+    # OUTLINE_CHUNK: the consecutive pixels one workgroup of dt_outline_count takes
+    if name == "OUTLINE_CHUNK":
+        globals()["OUTLINE_CHUNK"] = _outline_chunk()
+        return globals()["OUTLINE_CHUNK"]
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -1294,6 +1304,65 @@ def patch_table(labels: torch.Tensor, classes_u8: torch.Tensor, area_plane: torc
         _lib.check(_lib.load().dt_patch_measure(_p(labels.contiguous()), _p(classes_u8.contiguous()), h, w, _p(dense), n,
                                                 _p(cls), _p(bbox), _p(sum_y), _p(sum_x), _st()), "dt_patch_measure")
     return PatchTable(*(t.cpu().numpy() for t in (root, cls, area, bbox, sum_y, sum_x)), shape=(h, w))
+
+
+def patch_outlines(labels: torch.Tensor, classes_u8: torch.Tensor, connectivity: int = 8):
+    """the outlines of the patches of a label plane int32 [h, w] (``label_patches``, sieved or not) and its class map, as a
+    ``PolygonSet`` of host arrays (csrc/outlines.hip; the contract is ``deployment.outlines.polygonize_host``): one
+    polygon per patch in ascending root — polygon ``k`` is row ``k`` of ``patch_table`` —, the exterior ring first, one
+    vertex per corner, ``xy`` in 1/256 pixel.  ``connectivity`` must be the labelling's.  Neither tensor is written; a
+    non-contiguous view is made contiguous.  Sides <= 16384.
+
+    All per-edge work runs in the ``dt_outline_*`` kernels: count -> (scan; E and V are read back: the first of two
+    read-backs) -> edges -> ceil(log2 E) pointer-jumping rounds -> (the ring heads are compacted: R is read back) ->
+    rings -> (a stable sort by label and a scan over the R rings) -> scatter.  Only the four ``PolygonSet`` arrays are
+    downloaded.  Workspace: 4 bytes per pixel and about 40 bytes per boundary edge (two 16-byte states, the edge word,
+    head flag and ring row), next to the label plane."""
+    from .data.polygons import PolygonSet
+    from .deployment.outlines import empty_outlines
+    h, w = _patch_planes("patch_outlines", classes_u8, labels=labels)
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise RuntimeError(f"patch_outlines: connectivity must be 4 or 8, got {connectivity!r}")
+    lib, dev = _lib.load(), labels.device
+    labels, classes_u8 = labels.contiguous(), classes_u8.contiguous()
+    i32 = dict(dtype=torch.int32, device=dev)
+    counts = torch.empty((-(-h * w // _outline_chunk()), 2), **i32)
+    _lib.check(lib.dt_outline_count(_p(labels), h, w, _p(counts), _st()), "dt_outline_count")
+    scan = torch.cumsum(counts, 0, dtype=torch.int32)
+    E, V = (int(v) for v in scan[-1].tolist())                 # read-back 1: edges and vertices
+    if E == 0:
+        return empty_outlines()
+    chunk_first = (scan[:, 0] - counts[:, 0]).contiguous()
+    first = torch.empty(h * w, **i32)
+    edges = torch.empty(E, **i32)
+    state = torch.empty((2, E, 4), **i32)
+    head = torch.empty(E, dtype=torch.uint8, device=dev)
+    _lib.check(lib.dt_outline_edges(_p(labels), h, w, int(connectivity), _p(chunk_first), E, _p(first), _p(edges),
+                                    _p(state[0]), _st()), "dt_outline_edges")
+    _lib.check(lib.dt_outline_jump(_p(state[0]), _p(state[1]), E, _p(head), _st()), "dt_outline_jump")
+    final = state[lib.dt_outline_rounds(E) & 1]
+    heads = torch.nonzero(head).view(-1)                       # int64, ascending ring id; read-back 2: the ring count
+    R = int(heads.numel())
+    corners = torch.empty(R, **i32)
+    ring_label = torch.empty(R, **i32)
+    _lib.check(lib.dt_outline_rings(_p(labels), h, w, int(connectivity), _p(first), _p(edges), _p(final), E, _p(heads), R,
+                                    _p(corners), _p(ring_label), _st()), "dt_outline_rings")
+    # (label, ring id): ids ascend already, so a stable sort by label; the exterior 4 * root + 0 is a patch's smallest key
+    ring_label, order = torch.sort(ring_label, stable=True)
+    ring_offsets = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+    ring_offsets[1:] = torch.cumsum(corners[order], 0, dtype=torch.int64)
+    row_of = torch.empty(E, **i32)
+    row_of[heads[order]] = torch.arange(R, **i32)
+    new_polygon = torch.ones(R, dtype=torch.bool, device=dev)
+    new_polygon[1:] = ring_label[1:] != ring_label[:-1]
+    ring_polygon = torch.cumsum(new_polygon, 0, dtype=torch.int32) - 1
+    values = torch.zeros(R, dtype=torch.uint8, device=dev)      # one per polygon, P <= R of them: cut on the host
+    values[ring_polygon.long()] = classes_u8.view(-1)[(ring_label.long() - 1).clamp_(0, h * w - 1)]
+    xy = torch.zeros((V, 2), **i32)
+    _lib.check(lib.dt_outline_scatter(_p(edges), _p(final), E, w, _p(row_of), _p(ring_offsets), R, V, _p(xy), _st()),
+               "dt_outline_scatter")
+    xy, ring_offsets, ring_polygon, values = (t.cpu().numpy() for t in (xy, ring_offsets, ring_polygon, values))
+    return PolygonSet(xy, ring_offsets, ring_polygon, values[:int(ring_polygon[-1]) + 1])
 
 
 def signed_distmap(labels: torch.Tensor, K: int):

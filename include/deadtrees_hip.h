@@ -474,6 +474,43 @@ int dt_sieve_patches_u8(uint8_t* classes, int32_t* labels, int32_t* area_plane, 
 int dt_patch_measure(const int32_t* labels, const uint8_t* classes, int h, int w, const int32_t* dense_plane, int n,
                      uint8_t* cls, int32_t* bbox, int64_t* sum_y, int64_t* sum_x, void* stream);
 
+/* Dead-tree patch outlines (deployment/outlines.py states the contract): the boundaries of the patches of a label plane
+ * int32 [h][w] in device memory (dt_label_patches_u8, sieved or not; a value <= 0 is background), traced into rings along
+ * the pixel edges; h, w in 1..16384.  A labelled pixel p = y * w + x owns side s (0 top, 1 right, 2 bottom, 3 left) iff the
+ * neighbour across it carries another label; edges are compacted in ascending key 4 p + s (E of them), the successor of
+ * an edge is the next edge of its ring (connectivity 4 or 8 decides at saddle vertices), a ring's id is its smallest
+ * edge and its vertices are the end points of the edges behind which the ring turns (the corners), V in all.  Integers
+ * only, no atomics, no entry point synchronises; the caller reads E and V back after dt_outline_count and the ring
+ * count R after dt_outline_jump (ops.patch_outlines is the driver).  Workspace: 4 bytes per pixel (first), 36 per edge
+ * (edges + two states) and 1 per edge for the head flags.
+ *
+ * dt_outline_chunk: the pixels one workgroup of dt_outline_count takes.
+ * dt_outline_count: chunk_counts int32 [ceil(h w / chunk)][2] (overwritten): owned sides and corners per chunk of
+ *   consecutive row-major pixels.  The caller scans them: E and V are the totals.
+ * dt_outline_edges: chunk_first int32 [chunks] = the exclusive scan of the edge counts.  Overwrites first int32 [h w] (the
+ *   compact index of a pixel's first edge), edges uint32 [E] (4 p + s, bit 31: the end point is a corner) and state
+ *   int32 [E][4] = (e, 0, corner, successor's compact index), 16-byte aligned.
+ * dt_outline_rounds: ceil(log2(E)), the rounds dt_outline_jump runs.
+ * dt_outline_jump: pointer jumping, one launch per round, ping-pong between state and scratch (same size, 16-byte
+ *   aligned): the result lies in state when the round count is even, else in scratch.  Row e becomes (ring id, corners from e
+ *   forward to the ring's id edge without that edge's own, -, -).  head uint8 [E] (overwritten): 1 where e is a ring id.
+ * dt_outline_rings: heads int64 [R] = the ring ids ascending; overwrites ring_corners int32 [R] (the ring's vertex count)
+ *   and ring_label int32 [R] (the label of its patch).  state: the result of dt_outline_jump.
+ * dt_outline_scatter: row_of int32 [E] holds at every ring id the row of that ring in the caller's order (other entries are
+ *   not read), ring_offsets int64 [R + 1] the scan of the rings' vertex counts in that order.  Writes xy int32 [V][2]: the
+ *   vertices (x, y) in 1/256 pixel, a ring's in cycle order from its id edge on. */
+int dt_outline_chunk(int* chunk);
+int dt_outline_count(const int32_t* labels, int h, int w, int32_t* chunk_counts, void* stream);
+int dt_outline_edges(const int32_t* labels, int h, int w, int connectivity, const int32_t* chunk_first, int n_edges,
+                     int32_t* first, uint32_t* edges, int32_t* state, void* stream);
+int dt_outline_rounds(int n_edges);
+int dt_outline_jump(int32_t* state, int32_t* scratch, int n_edges, uint8_t* head, void* stream);
+int dt_outline_rings(const int32_t* labels, int h, int w, int connectivity, const int32_t* first, const uint32_t* edges,
+                     const int32_t* state, int n_edges, const int64_t* heads, int n_rings, int32_t* ring_corners,
+                     int32_t* ring_label, void* stream);
+int dt_outline_scatter(const uint32_t* edges, const int32_t* state, int n_edges, int w, const int32_t* row_of,
+                       const int64_t* ring_offsets, int n_rings, int64_t n_vertices, int32_t* xy, void* stream);
+
 /* Training samples from an ortho raster (the array arithmetic of scripts/createdataset.py:53-194 and
  * scripts/computestats.py:111-161; deadtrees_amd/data/rasters.py states the contract in numpy).  rgbn_chw uint8 [4][h][w]
  * with 1 <= h, w <= S is the top-left corner of a zero [4][S][S] array; mask / lu uint8 [h][w] are padded the same way.
