@@ -5,3 +5,5 @@ from deadtrees_amd.deployment.tiler import tta_views  # noqa: F401  (test-time a
 from deadtrees_amd.deployment.tiler import PatchConfig, PatchTable  # noqa: F401  (dead-tree patches of a map)
 from deadtrees_amd.deployment.tiler import (outlines_geojson, polygonize, polygonize_host,  # noqa: F401  (their outlines)
                                             write_outlines_geojson)
+from deadtrees_amd.deployment.tiler import (PatchMatch, PatchOverlaps, PatchTracks, overlap_pairs_host,  # noqa: F401
+                                            patch_overlaps)  # (overlaps of two maps' patches)

@@ -182,13 +182,15 @@ def polygonize(classes, K: int, connectivity: int = 8, device=None) -> PolygonSe
 
 # ---------------------------------------------------------------------------------------------- GeoJSON
 def outlines_geojson(polys: PolygonSet, transform=None, value_property: str = "type",
-                     table: Optional[PatchTable] = None, rfc7946_winding: bool = False) -> dict:
+                     table: Optional[PatchTable] = None, rfc7946_winding: bool = False, properties=None) -> dict:
     """a GeoJSON ``FeatureCollection`` with one ``Polygon`` feature per polygon: the exterior ring, then the holes, every
     ring closed by repeating its first vertex.  Coordinates are ``x0 + x * dx, y0 + y * dy`` for the north-up GDAL
     geotransform ``(x0, dx, rx, y0, ry, dy)`` (rotation terms other than zero raise ``ValueError``, as in
     ``PolygonSet.to_pixels``); None gives pixel coordinates.  ``properties`` holds the class under ``value_property``, so
     that ``PolygonSet.from_geojson(..., keep_values=None)`` reads it back, and with the ``PatchTable`` of the same label
-    plane also ``root``, ``area`` and ``area_m2``.
+    plane also ``root``, ``area`` and ``area_m2``.  ``properties``: a mapping from name to a sequence with one entry per
+    polygon (a wrong length is a ``ValueError``); every entry goes into its feature's ``properties`` as a Python scalar —
+    ``properties={"state": tracks.b_state, "matched": match.b_to_a >= 0}`` colours a change map.
 
     Vertex order: by default every ring keeps the order of the canonical form, so that ``from_geojson(...).to_pixels(
     transform)`` gives the input arrays back exactly.  The canonical exterior has POSITIVE shoelace area in pixel
@@ -214,6 +216,13 @@ def outlines_geojson(polys: PolygonSet, transform=None, value_property: str = "t
         if not isinstance(table, PatchTable) or table.n != len(polys):
             raise ValueError("outlines_geojson: table must be the PatchTable of the outlines' label plane (one row per polygon)")
         area_m2 = table.area_m2()
+    extra = {}
+    for name, column in (properties or {}).items():
+        column = column.tolist() if isinstance(column, np.ndarray) else [v.item() if isinstance(v, np.generic) else v
+                                                                         for v in column]
+        if len(column) != len(polys):
+            raise ValueError(f"outlines_geojson: property {name!r} has {len(column)} entries for {len(polys)} polygons")
+        extra[str(name)] = column
     world = np.empty((len(polys.xy), 2), np.float64)
     world[:, 0] = x0 + (polys.xy[:, 0] / SUBPIXEL) * dx
     world[:, 1] = y0 + (polys.xy[:, 1] / SUBPIXEL) * dy
@@ -233,13 +242,15 @@ def outlines_geojson(polys: PolygonSet, transform=None, value_property: str = "t
         props = {value_property: int(polys.values[k])}
         if table is not None:
             props.update(root=int(table.root[k]), area=int(table.area[k]), area_m2=float(area_m2[k]))
+        for name, column in extra.items():
+            props[name] = column[k]
         features.append({"type": "Feature", "properties": props, "geometry": {"type": "Polygon", "coordinates": rings}})
     return {"type": "FeatureCollection", "features": features}
 
 
 def write_outlines_geojson(path, polys: PolygonSet, transform=None, value_property: str = "type",
-                           table: Optional[PatchTable] = None, rfc7946_winding: bool = False) -> None:
+                           table: Optional[PatchTable] = None, rfc7946_winding: bool = False, properties=None) -> None:
     """``outlines_geojson`` written to ``path`` as JSON"""
-    obj = outlines_geojson(polys, transform, value_property, table, rfc7946_winding)
+    obj = outlines_geojson(polys, transform, value_property, table, rfc7946_winding, properties=properties)
     with open(os.fspath(path), "w") as f:
         json.dump(obj, f)

@@ -66,9 +66,11 @@ class RasterStats:
     ``PatchTable`` (``deployment/patches.py``) when one was asked for, else None; a sum of rasters has none, because the
     tables of different rasters do not share a grid.  ``outlines``: the patches' outlines (``deployment/outlines.py``: a
     ``PolygonSet`` on the raster's grid, polygon ``k`` is row ``k`` of ``patches``) when they were asked for, else None;
-    a sum of rasters has none either"""
+    a sum of rasters has none either.  ``overlaps``: the ``PatchOverlaps`` (``deployment/overlaps.py``) of the map asked
+    for with ``against`` (its ``table_a``) and this raster's patches (its ``table_b`` is ``patches``), else None; a sum of
+    rasters has none"""
 
-    def __init__(self, counts, pixel_area_m2: float = PIXEL_AREA_M2, patches=None, outlines=None):
+    def __init__(self, counts, pixel_area_m2: float = PIXEL_AREA_M2, patches=None, outlines=None, overlaps=None):
         counts = np.array(counts, dtype=np.int64)
         if counts.ndim != 2 or counts.shape[0] < 1 or counts.shape[1] < 2:
             raise ValueError(f"RasterStats: counts must be [Z >= 1, K >= 2], got shape {counts.shape}")
@@ -89,6 +91,13 @@ class RasterStats:
             if patches is None or len(outlines) != patches.n:
                 raise ValueError("RasterStats: outlines need the PatchTable they belong to (one polygon per row)")
         self._outlines = outlines
+        if overlaps is not None:
+            from .overlaps import PatchOverlaps
+            if not isinstance(overlaps, PatchOverlaps):
+                raise ValueError(f"RasterStats: overlaps must be a PatchOverlaps or None, got {type(overlaps).__name__}")
+            if patches is None or overlaps.table_b != patches:
+                raise ValueError("RasterStats: overlaps need the PatchTable they belong to (their table_b)")
+        self._overlaps = overlaps
 
     @property
     def patches(self):
@@ -97,6 +106,10 @@ class RasterStats:
     @property
     def outlines(self):
         return self._outlines
+
+    @property
+    def overlaps(self):
+        return self._overlaps
 
     @property
     def counts(self) -> np.ndarray:
@@ -143,12 +156,15 @@ class RasterStats:
             return NotImplemented
         if (self._patches is None) != (other._patches is None) or (self._outlines is None) != (other._outlines is None):
             return False
+        if (self._overlaps is None) != (other._overlaps is None):
+            return False
         return (self._counts.shape == other._counts.shape and bool((self._counts == other._counts).all())
                 and self.pixel_area_m2 == other.pixel_area_m2
                 and (self._patches is None or self._patches == other._patches)
                 and (self._outlines is None or all(
                     np.array_equal(getattr(self._outlines, a), getattr(other._outlines, a))
-                    for a in ("xy", "ring_offsets", "ring_polygon", "values"))))
+                    for a in ("xy", "ring_offsets", "ring_polygon", "values")))
+                and (self._overlaps is None or self._overlaps == other._overlaps))
 
     __hash__ = None
 
@@ -156,6 +172,8 @@ class RasterStats:
         tail = "" if self._patches is None else f", patches={self._patches!r}"
         if self._outlines is not None:
             tail += f", outlines={self._outlines!r}"
+        if self._overlaps is not None:
+            tail += f", overlaps={self._overlaps!r}"
         return f"RasterStats(counts={self._counts.tolist()}, pixel_area_m2={self.pixel_area_m2!r}{tail})"
 
 

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from .outlines import outlines_geojson, polygonize, polygonize_host, write_outlines_geojson  # noqa: F401
+from .overlaps import (PatchMatch, PatchOverlaps, PatchTracks, overlap_pairs_host, patch_overlaps)  # noqa: F401
 from .patches import PatchConfig, PatchTable, check_patches  # noqa: F401  (the ``patches`` argument of infer_tile)
 
 
@@ -39,6 +40,24 @@ def check_outlines(outlines, config, who: str) -> bool:
     if outlines and config is None:
         raise ValueError(f"{who}: outlines need patches (the outlines are those of the PatchTable's patches)")
     return outlines
+
+
+def check_against(against, against_patches, config, shape, K, who: str):
+    """the ``against`` / ``against_patches`` arguments of ``infer_tile`` / ``Tiler.stats`` -> ``(map, PatchConfig)``, or
+    ``(None, None)`` when no map was given.  ``against`` without patches, on another grid, of another dtype or with a value
+    >= K is a ``ValueError``; ``against_patches`` defaults to the connectivity of ``patches`` without a sieve"""
+    from .overlaps import check_against_map
+    if against is None:
+        if against_patches is not None:
+            raise ValueError(f"{who}: against_patches needs against")
+        return None, None
+    if config is None:
+        raise ValueError(f"{who}: against needs patches (the overlaps are those of the PatchTable's patches)")
+    if against_patches is None:
+        against_patches = PatchConfig(config.connectivity)
+    elif not isinstance(against_patches, PatchConfig):
+        raise ValueError(f"{who}: against_patches must be a PatchConfig or None, got {against_patches!r}")
+    return check_against_map(against, shape, int(K), who), against_patches
 
 
 def divisible_without_remainder(a, b):
@@ -249,7 +268,8 @@ class Tiler:
         """the merged class map cropped to the raster size (what ``write_file`` stores)"""
         return self._outdata[0:self._tile_info.size[0], 0:self._tile_info.size[1]]
 
-    def stats(self, zones=None, classes: int = 3, n_zones: Optional[int] = None, patches=None, outlines=None):
+    def stats(self, zones=None, classes: int = 3, n_zones: Optional[int] = None, patches=None, outlines=None,
+              against=None, against_patches=None):
         """``RasterStats`` of ``result`` (``stats.zonal_counts_host``): what ``infer_tile(..., stats=True)`` returns, for a
         caller of the reference's own ``get_batches`` / ``put_batches`` loop.  ``zones``: uint8 [h, w] on the raster's grid
         (``n_zones`` defaults to ``zones.max() + 1``) or a ``PolygonSet`` in its pixel coordinates (burnt by
@@ -257,9 +277,13 @@ class Tiler:
         ``PatchConfig``): the statistics carry the ``PatchTable`` of the map (``patches.patches_host``); a configuration
         that sieves changes ``result`` itself, and the counts are those of the sieved map.  ``outlines=True`` (needs
         ``patches``): the statistics also carry the patches' outlines (``outlines.polygonize_host`` on the final label
-        plane), polygon ``k`` for row ``k`` of the table"""
+        plane), polygon ``k`` for row ``k`` of the table.  ``against`` (needs ``patches``): a uint8 class map on the raster's
+        grid or a ``PolygonSet`` in its pixel coordinates (burnt with ``all_touched=True``), with ``against_patches`` its
+        ``PatchConfig`` (default: the connectivity of ``patches``, no sieve): the statistics carry ``.overlaps``, the
+        ``PatchOverlaps`` of that map (A) and the final map (B) (``deployment/overlaps.py``)"""
         from ..data.polygons import PolygonSet, rasterize_host
         from .outlines import outlines_from_labels
+        from .overlaps import PatchOverlaps, overlap_pairs_host
         from .patches import labelled_patches_host
         from .stats import RasterStats, check_zones, zonal_counts_host
         if self._outdata is None:
@@ -267,19 +291,25 @@ class Tiler:
         config = check_patches(patches)
         outlines = check_outlines(outlines, config, "Tiler.stats")
         result = self.result
+        against, against_config = check_against(against, against_patches, config, result.shape, classes, "Tiler.stats")
         zones, Z = check_zones(zones, result.shape, n_zones)
         if isinstance(zones, PolygonSet):
             zones = rasterize_host(zones, result.shape[0], result.shape[1])
-        table = rings = None
+        table = rings = pairs = None
         if config is not None:
             sieved, labels, table = labelled_patches_host(result, classes, config)
+            if against is not None:
+                if isinstance(against, PolygonSet):
+                    against = rasterize_host(against, result.shape[0], result.shape[1], all_touched=True)
+                _, labels_a, table_a = labelled_patches_host(against, classes, against_config)
+                pairs = PatchOverlaps(table_a, table, *overlap_pairs_host(labels_a, labels))
             if outlines:
                 rings = outlines_from_labels(labels, sieved, config.connectivity)
             if config.sieves:
                 self._outdata[0:result.shape[0], 0:result.shape[1]] = sieved
                 result = self.result
         return RasterStats(zonal_counts_host(np.ascontiguousarray(result), zones, classes, Z), patches=table,
-                           outlines=rings)
+                           outlines=rings, overlaps=pairs)
 
     def write_file(self, outfile: Union[str, Path]) -> None:
         """reference tiler.py:136-142 (LZW-compressed tiled GeoTIFF through rioxarray)"""
@@ -293,7 +323,8 @@ class Tiler:
 def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, rank: int = 0, world: int = 1,
                   device: str = "cuda", tile_shape: Optional[Tuple[int, int]] = None, skip_blank: bool = True,
                   overlap: int = 0, blend: str = "crop", return_probs: bool = False, tta=None, stats: bool = False,
-                  zones=None, n_zones: Optional[int] = None, patches=None, outlines=None):
+                  zones=None, n_zones: Optional[int] = None, patches=None, outlines=None, against=None,
+                  against_patches=None):
     """the directory loop of scripts/inference.py:71-115 over in-memory rasters (GeoTIFF I/O needs rioxarray, absent
     here): ``rasters`` yields ``array`` or ``(key, array)``; rank r of ``world`` takes rasters r, r + world, ... (tiles are
     independent: no collective).  Yields ``(key, class_map)`` in input order of the rank's share; rasters whose band 1
@@ -301,7 +332,8 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
     forward pass (device reduction over the uploaded raster, ``ops.band_has_data``).  ``overlap`` / ``blend`` /
     ``return_probs`` / ``tta`` / ``stats`` / ``n_zones`` / ``patches`` / ``outlines``: as in ``infer_tile`` (every raster stays on its rank, so overlap
     needs no exchange); ``zones``: a callable ``key -> uint8 [h, w] array, PolygonSet or None``, or a mapping (a missing
-    key is None).
+    key is None); ``against``: the same for the map every raster is compared with (a uint8 array, a ``PolygonSet`` or
+    None: that raster's statistics carry no overlaps), ``against_patches`` as in ``infer_tile``.
     The second item of every pair is whatever ``infer_tile`` returned: with ``stats=True`` ``(map, RasterStats)`` — the
     ``RasterStats`` of a rank's share add up (``+``) to that rank's part of the regional totals."""
     if zones is not None and not stats:
@@ -309,21 +341,27 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
     if check_patches(patches) is not None and not stats:
         raise ValueError("infer_rasters: patches need stats=True")
     check_outlines(outlines, check_patches(patches), "infer_rasters")
+    if against is not None and (not stats or check_patches(patches) is None):
+        raise ValueError("infer_rasters: against needs stats=True and patches")
+    if against is None and against_patches is not None:
+        raise ValueError("infer_rasters: against_patches needs against")
     for i, item in enumerate(rasters):
         if i % world != rank:
             continue
         key, arr = item if isinstance(item, tuple) else (i, item)
         z = None if zones is None else zones(key) if callable(zones) else zones.get(key)
+        other = None if against is None else against(key) if callable(against) else against.get(key)
         yield key, infer_tile(inference, arr, subtile=subtile, batch_size=batch_size, device=device, tile_shape=tile_shape,
                               skip_blank=skip_blank, overlap=overlap, blend=blend, return_probs=return_probs, tta=tta,
-                              stats=stats, zones=z, n_zones=n_zones, patches=patches, outlines=outlines)
+                              stats=stats, zones=z, n_zones=n_zones, patches=patches, outlines=outlines, against=other,
+                              against_patches=None if other is None else against_patches)
 
 
 def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size: int = 64, rank: int = 0,
                world: int = 1, device: str = "cuda", group=None, tile_shape: Optional[Tuple[int, int]] = None,
                on_device: Optional[bool] = None, skip_blank: bool = False, overlap: int = 0, blend: str = "crop",
                return_probs: bool = False, tta=None, stats: bool = False, zones=None, n_zones: Optional[int] = None,
-               patches=None, outlines=None):
+               patches=None, outlines=None, against=None, against_patches=None):
     """whole-tile inference of scripts/inference.py:80-115 on the MI355X path: split -> (uint8 H2D, normalise on the
     device) -> forward + fused argmax -> uint8 D2H -> merge.  With world > 1 the sub-tile batches j = rank (mod world)
     are processed locally and the uint8 class maps are all-gathered (no other collective: tiles are independent).
@@ -366,7 +404,18 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     tracing along the pixel edges; ``outlines_geojson`` writes them out).  On every device path they are traced from the
     final label plane, after the sieve, in HBM before the map leaves the device (``ops.patch_outlines``: only the four
     ``PolygonSet`` arrays are downloaded); the host path runs ``polygonize_host``.  The map, the counts and the table are
-    those of the call without ``outlines``."""
+    those of the call without ``outlines``.
+
+    ``against`` (needs ``stats=True`` and ``patches``): a map to compare the result with patch by patch — a uint8 [h, w]
+    class map on the raster's grid with values < K (last year's map, a burnt annotation) or a ``PolygonSet`` in its pixel
+    coordinates (the annotators' polygons; burnt with ``all_touched=True``, the rule of the training masks).  The
+    ``RasterStats`` carries ``.overlaps``, a ``PatchOverlaps`` (``deployment/overlaps.py``): ``table_a`` the patches of
+    ``against`` under ``against_patches`` (a ``PatchConfig``; default: the connectivity of ``patches``, no sieve),
+    ``table_b`` the ``.patches`` of the final map, and one row per pair of patches that share a pixel — ``match()`` gives
+    the crown-level accuracy, ``track()`` the year-to-year fate of every patch.  On every device path ``against`` is
+    uploaded next to the raster (a ``PolygonSet`` is burnt in HBM instead), labelled, sieved if asked and tabled there, and
+    ``ops.patch_overlaps`` runs on the two label planes before the map is downloaded; the host path runs
+    ``overlap_pairs_host``.  The map, the counts, the table and the outlines are those of the call without ``against``."""
     if blend not in ("crop", "average"):
         raise ValueError(f"blend {blend!r}: use 'crop' or 'average'")
     want_stats = None
@@ -377,13 +426,17 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
             raise ValueError("infer_tile: zones / n_zones need stats=True")
         if config is not None:
             raise ValueError("infer_tile: patches need stats=True")
+        if against is not None or against_patches is not None:
+            raise ValueError("infer_tile: against / against_patches need stats=True")
     else:
         from .stats import check_zones
         zones, Z = check_zones(zones, np.shape(arr_chw_u8)[1:], n_zones)
         K = getattr(inference, "classes", None)
         if K is None:
             raise ValueError("infer_tile: stats=True needs an inference object with a `classes` count")
-        want_stats = (zones, int(K), Z, config, outlines)
+        against, against_patches = check_against(against, against_patches, config, np.shape(arr_chw_u8)[1:], K,
+                                                 "infer_tile")
+        want_stats = (zones, int(K), Z, config, outlines, against, against_patches)
     members = getattr(inference, "members", None)
     if overlap or tta is not None or members is not None:
         views = None if tta is None else tta_views(tta)
@@ -448,42 +501,54 @@ def _upload(inference, arr_chw_u8: np.ndarray, device: str, skip_blank: bool, wa
     """the start of every device path: ONE uint8 H2D copy of the band planes the network reads (the N of an RGBN raster
     under an RGB model stays on the host), the zones map of a ``stats=True`` call uploaded next to it (None without one;
     a ``PolygonSet`` is rasterised on the device instead),
-    and ``skip_blank``'s ``is_valid_tile`` on the uploaded raster.  Returns ``(raster, zones)`` on the device, or None for
-    a raster with nothing but 0 / 255 in band 1"""
+    the ``against`` map alike (a ``PolygonSet`` is burnt with ``all_touched=True``),
+    and ``skip_blank``'s ``is_valid_tile`` on the uploaded raster.  Returns ``(raster, (zones, against))`` on the device, or
+    None for a raster with nothing but 0 / 255 in band 1"""
     C = arr_chw_u8.shape[0]
     nch = int(getattr(inference, "in_channels", C) or C)
     if 0 < nch < C:
         arr_chw_u8 = arr_chw_u8[:nch]
     x = torch.from_numpy(np.ascontiguousarray(arr_chw_u8)).to(device, non_blocking=True)
-    zones_dev = None
+    zones_dev = against_dev = None
     if want_stats is not None and want_stats[0] is not None:
         from ..data.polygons import PolygonSet, rasterize
         if isinstance(want_stats[0], PolygonSet):          # burnt where it is read: the tables travel, not the plane
             zones_dev = rasterize(want_stats[0], arr_chw_u8.shape[1:], device=x.device)
         else:
             zones_dev = torch.from_numpy(np.ascontiguousarray(want_stats[0])).to(device, non_blocking=True)
+    if want_stats is not None and want_stats[5] is not None:
+        from ..data.polygons import PolygonSet, rasterize
+        if isinstance(want_stats[5], PolygonSet):
+            against_dev = rasterize(want_stats[5], arr_chw_u8.shape[1:], device=x.device, all_touched=True)
+        else:                                              # (a copy: torch wraps writable memory only)
+            against_dev = torch.from_numpy(np.array(want_stats[5], order="C")).to(device, non_blocking=True)
     if skip_blank:
         from .. import ops
         if int(ops.band_has_data(x[0])) == 0:
             return None
-    return x, zones_dev
+    return x, (zones_dev, against_dev)
 
 
-def _download(out: torch.Tensor, probs: Optional[torch.Tensor], want_stats, zones_dev):
+def _download(out: torch.Tensor, probs: Optional[torch.Tensor], want_stats, planes):
     """the end of every device path: the D2H copy of the final map ``out`` (uint8 [h, w], contiguous) and of the
-    probabilities when there are any.  With ``want_stats`` = (zones, K, Z, patch config, outlines) one ``ops.zonal_counts`` is enqueued
+    probabilities when there are any.  ``planes``: ``_upload``'s (zones, against) on the device.  With ``want_stats`` =
+    (zones, K, Z, patch config, outlines, against, its patch config) one ``ops.zonal_counts`` is enqueued
     on ``out`` BEFORE the download (no synchronisation of its own); the counts and the flag are read after the map has
     arrived.  With a patch configuration ``out`` is labelled, its patch areas are taken and — if the configuration sieves —
     it is sieved IN PLACE, all before the counts; the roots are compacted and measured behind the download (the compaction
     reads the row count back).  Labels, the area plane (reused as the root -> row plane) and the compaction's flags are
     the workspace: about 12 bytes per pixel next to the map.  With ``outlines`` the final label plane is traced behind the
-    table (``ops.patch_outlines``: two more scalar read-backs, 4 bytes per pixel and 40 per boundary edge of workspace)"""
+    table (``ops.patch_outlines``: two more scalar read-backs, 4 bytes per pixel and 40 per boundary edge of workspace).
+    With ``against`` that map is labelled, sieved if asked and tabled like ``out`` (its own label and area planes), and
+    ``ops.patch_overlaps`` reads the two final label planes behind the tables: three more scalar read-backs, 8 bytes per
+    1024 pixels and 12 per run of workspace"""
     if want_stats is None:
         return out.cpu().numpy() if probs is None else (out.cpu().numpy(), probs.cpu().numpy())
     from .. import ops
     from .stats import RasterStats
-    _, K, Z, config, outlines = want_stats
-    labels = area = table = rings = None
+    _, K, Z, config, outlines, against, against_config = want_stats
+    zones_dev, against_dev = planes
+    labels = area = table = rings = pairs = None
     err = torch.zeros(1, dtype=torch.int32, device=out.device)
     if config is not None:
         labels, _ = ops.label_patches(out, K, config.connectivity, err=err)
@@ -497,6 +562,10 @@ def _download(out: torch.Tensor, probs: Optional[torch.Tensor], want_stats, zone
         table = ops.patch_table(labels, out, area, reuse_area_plane=True)
         if outlines:
             rings = ops.patch_outlines(labels, out, config.connectivity)
+        if against is not None:
+            from .overlaps import PatchOverlaps, _device_patches
+            labels_a, table_a = _device_patches(against_dev, K, against_config, err)
+            pairs = PatchOverlaps(table_a, table, *ops.patch_overlaps(labels_a, labels))
         torch.cuda.current_stream(out.device).synchronize()
         result = (host.numpy(),)
     else:
@@ -507,7 +576,7 @@ def _download(out: torch.Tensor, probs: Optional[torch.Tensor], want_stats, zone
     if flag:          # cannot happen with checked zones: the map is an argmax over K classes
         raise RuntimeError(f"infer_tile: raster statistics met a value out of range (flag {flag}: 1 class >= {K}, "
                            f"2 zone >= {Z})")
-    return result + (RasterStats(counts.cpu().numpy(), patches=table, outlines=rings),)
+    return result + (RasterStats(counts.cpu().numpy(), patches=table, outlines=rings, overlaps=pairs),)
 
 
 def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch_size: int, device: str,
@@ -526,7 +595,7 @@ def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch
     up = _upload(inference, arr_chw_u8, device, skip_blank, want_stats)
     if up is None:
         return None
-    x, zones_dev = up
+    x, planes = up
     C = x.shape[0]
     if hasattr(inference, "run_blocks"):
         # round 3: split + zero padding + Normalize + NHWC in one gather per batch (dt_split_normalize_u8), no ATen passes
@@ -540,7 +609,7 @@ def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch
         outs = [inference.run_u8(blocks[j:j + batch_size], device=device) for j in range(0, nby * nbx, batch_size)]
     maps = (outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)).to(torch.uint8)
     merged = maps.view(nby, nbx, d, d).permute(0, 2, 1, 3).reshape(nby * d, nbx * d)
-    return _download(merged[:h, :w].contiguous(), None, want_stats, zones_dev)
+    return _download(merged[:h, :w].contiguous(), None, want_stats, planes)
 
 
 def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.ndarray, d: int, overlap: int, blend: str,
@@ -563,7 +632,7 @@ def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.
     up = _upload(inference, arr_chw_u8, device, skip_blank, want_stats)
     if up is None:
         return None
-    x, zones_dev = up
+    x, planes = up
     kw = {} if views is None else {"views": views}   # a duck-typed run_windows without TTA need not take the keyword
     per = batch_size if views is None else max(1, batch_size // len(views))     # batch_size counts forward tiles
     weight = "ramp" if blend == "average" else "keep"
@@ -588,11 +657,11 @@ def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.
         maps = [class_map(m) for m in models]
         if len(maps) > 1:
             maps = [ops.ensemble_vote(torch.stack(maps, dim=0), int(inference.classes), dtype="uint8")[0]]
-        return _download(maps[0], None, want_stats, zones_dev)
+        return _download(maps[0], None, want_stats, planes)
     acc = None
     for m in models:
         acc = accumulate(m, acc)
     if return_probs:
         classes, probs = ops.stitch_finalize(acc, want_probs=True)
-        return _download(classes, probs, want_stats, zones_dev)
-    return _download(ops.stitch_finalize(acc), None, want_stats, zones_dev)
+        return _download(classes, probs, want_stats, planes)
+    return _download(ops.stitch_finalize(acc), None, want_stats, planes)

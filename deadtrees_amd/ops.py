@@ -1207,6 +1207,12 @@ def _outline_chunk():
     return chunk.value
 
 
+def _overlap_chunk():
+    chunk = C.c_int(0)
+    _lib.check(_lib.load().dt_overlap_chunk(C.byref(chunk)), "dt_overlap_chunk")
+    return chunk.value
+
+
 def __getattr__(name):
     # PATCH_TILE = (th, tw): the tile of dt_label_patches_u8's local launch, asked of the library on first use
     if name == "PATCH_TILE":
@@ -1216,6 +1222,10 @@ def __getattr__(name):
     if name == "OUTLINE_CHUNK":
         globals()["OUTLINE_CHUNK"] = _outline_chunk()
         return globals()["OUTLINE_CHUNK"]
+    # OVERLAP_CHUNK: the consecutive pixels one workgroup of dt_overlap_count takes
+    if name == "OVERLAP_CHUNK":
+        globals()["OVERLAP_CHUNK"] = _overlap_chunk()
+        return globals()["OVERLAP_CHUNK"]
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -1363,6 +1373,69 @@ def patch_outlines(labels: torch.Tensor, classes_u8: torch.Tensor, connectivity:
                "dt_outline_scatter")
     xy, ring_offsets, ring_polygon, values = (t.cpu().numpy() for t in (xy, ring_offsets, ring_polygon, values))
     return PolygonSet(xy, ring_offsets, ring_polygon, values[:int(ring_polygon[-1]) + 1])
+
+
+def _overlap_planes(labels_a: torch.Tensor, labels_b: torch.Tensor):
+    """the argument checks of ``patch_overlaps``: (h, w, a, b) with both planes contiguous and 16-byte aligned"""
+    h, w = _patch_planes("patch_overlaps", labels_a=labels_a, labels_b=labels_b)
+    if h * w > 2 ** 31 - 2:
+        raise RuntimeError(f"patch_overlaps: {h * w} pixels do not fit int32 labels (h * w <= {2 ** 31 - 2})")
+    planes = []
+    for t in (labels_a, labels_b):
+        t = t.contiguous()
+        planes.append(t if t.data_ptr() % 16 == 0 else t.clone())       # a view at an odd storage offset: 16-byte loads
+    return h, w, planes[0], planes[1]
+
+
+def _overlap_count(lib, a, b, h, w):
+    counts = torch.empty((-(-h * w // _overlap_chunk()), 2), dtype=torch.int32, device=a.device)
+    _lib.check(lib.dt_overlap_count(_p(a), _p(b), h, w, _p(counts), _st()), "dt_overlap_count")
+    return counts
+
+
+def _overlap_runs(lib, a, b, h, w, counts, scan, R):
+    chunk_first = (scan[:, 0] - counts[:, 0]).contiguous()
+    key = torch.empty(R, dtype=torch.int64, device=a.device)
+    start = torch.empty(R, dtype=torch.int32, device=a.device)
+    _lib.check(lib.dt_overlap_runs(_p(a), _p(b), h, w, _p(chunk_first), R, _p(key), _p(start), _st()), "dt_overlap_runs")
+    return key, start
+
+
+def patch_overlaps(labels_a: torch.Tensor, labels_b: torch.Tensor):
+    """the overlap table of two label planes int32 [h, w] on one HIP device (``label_patches``, sieved or not; contract in
+    ``deployment/overlaps.py``, csrc/overlaps.hip): host int64 arrays ``(a, b, n)``, one row per pair of patches that
+    share a pixel — ``a`` / ``b`` the roots (label - 1) in the two planes, ``n`` the shared pixels — ascending in
+    ``(a, b)``.  Neither plane is written; a non-contiguous view is made contiguous.  ``h * w <= 2**31 - 2``.
+
+    All per-pixel work runs in two kernels over the runs of equal pair keys in flat row-major order: ``dt_overlap_count``
+    -> (a scan over the chunks; the run count R and the runs with a key are read back: read-back 1) ->
+    ``dt_overlap_runs`` (key and start of every run) -> on the R runs only: lengths by difference, ``torch.sort`` by key,
+    segment ids where the sorted key changes (the pair count P is read back: read-back 2), a segmented int64 sum of the
+    lengths, the key-0 segment dropped.  Only the three result arrays are downloaded; without any overlap nothing is
+    launched after the count.  Workspace: 8 bytes per chunk of ``OVERLAP_CHUNK`` = 1024 pixels (the second count is what
+    lets a pair of maps without overlap stop after one launch) and 12 bytes per run, plus the sort's own."""
+    h, w, a, b = _overlap_planes(labels_a, labels_b)
+    lib, dev = _lib.load(), a.device
+    empty = tuple(torch.zeros(0, dtype=torch.int64).numpy() for _ in range(3))
+    counts = _overlap_count(lib, a, b, h, w)
+    scan = torch.cumsum(counts, 0, dtype=torch.int32)
+    R, live = (int(v) for v in scan[-1].tolist())              # read-back 1: runs, and runs whose key is not 0
+    if live == 0:
+        return empty
+    key, start = _overlap_runs(lib, a, b, h, w, counts, scan, R)
+    length = torch.empty(R, dtype=torch.int64, device=dev)
+    length[:-1] = start[1:] - start[:-1]
+    length[-1] = h * w - start[-1]
+    key, order = torch.sort(key)
+    segment = torch.zeros(R, dtype=torch.int64, device=dev)
+    segment[1:] = torch.cumsum(key[1:] != key[:-1], 0)
+    S = int(segment[-1]) + 1                                   # read-back 2: the segments; P = S - (one of key 0, if any)
+    n = torch.zeros(S, dtype=torch.int64, device=dev).index_add_(0, segment, length[order])
+    pair = torch.empty(S, dtype=torch.int64, device=dev)
+    pair[segment] = key                                        # every run of a segment writes the same value
+    first = 1 if live < R else 0                               # keys are >= 0 and sorted: the key-0 segment comes first
+    pair, n = pair[first:], n[first:]
+    return tuple(t.cpu().numpy() for t in ((pair >> 32) - 1, (pair & 0xffffffff) - 1, n))
 
 
 def signed_distmap(labels: torch.Tensor, K: int):

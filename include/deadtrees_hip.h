@@ -511,6 +511,24 @@ int dt_outline_rings(const int32_t* labels, int h, int w, int connectivity, cons
 int dt_outline_scatter(const uint32_t* edges, const int32_t* state, int n_edges, int w, const int32_t* row_of,
                        const int64_t* ring_offsets, int n_rings, int64_t n_vertices, int32_t* xy, void* stream);
 
+/* Patch overlaps (deployment/overlaps.py states the contract): the runs of equal pair keys of two label planes int32
+ * [h][w] in device memory (dt_label_patches_u8, sieved or not; a value <= 0 is background), 16-byte aligned, h * w <=
+ * 2^31 - 2.  key(p) = ((int64)labels_a[p] << 32) | (uint32)labels_b[p] where both labels are > 0, else 0; a run is a maximal
+ * stretch of consecutive pixels p = y * w + x with one key (rows are not told apart).  Integers only, no atomics, no entry
+ * point synchronises, neither plane is written; the caller reads the run count R back after dt_overlap_count, sorts the
+ * runs by key and sums the lengths of equal keys (ops.patch_overlaps is the driver).  Workspace: 8 bytes per chunk and 12
+ * per run.
+ *
+ * dt_overlap_chunk: the pixels one workgroup takes.
+ * dt_overlap_count: chunk_counts int32 [ceil(h w / chunk)][2] (overwritten): the run heads per chunk of consecutive
+ *   row-major pixels, and those among them whose key is not 0.  The caller scans the first column: R is its total.
+ * dt_overlap_runs: chunk_first int32 [chunks] = the exclusive scan of the head counts.  Overwrites run_key int64 [R] and
+ *   run_start int32 [R] (the run's first pixel), runs in ascending start. */
+int dt_overlap_chunk(int* chunk);
+int dt_overlap_count(const int32_t* labels_a, const int32_t* labels_b, int h, int w, int32_t* chunk_counts, void* stream);
+int dt_overlap_runs(const int32_t* labels_a, const int32_t* labels_b, int h, int w, const int32_t* chunk_first, int n_runs,
+                    int64_t* run_key, int32_t* run_start, void* stream);
+
 /* Training samples from an ortho raster (the array arithmetic of scripts/createdataset.py:53-194 and
  * scripts/computestats.py:111-161; deadtrees_amd/data/rasters.py states the contract in numpy).  rgbn_chw uint8 [4][h][w]
  * with 1 <= h, w <= S is the top-left corner of a zero [4][S][S] array; mask / lu uint8 [h][w] are padded the same way.
