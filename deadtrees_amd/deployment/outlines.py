@@ -37,7 +37,7 @@ from typing import Optional
 import numpy as np
 
 from ..data.polygons import MAX_SIDE, SUBPIXEL, PolygonSet
-from .patches import PatchTable, _check_labels, _check_map, label_patches_host
+from .patches import PatchConfig, PatchTable, _check_labels, _check_map, label_patches_host
 from .stats import MAX_CLASSES
 
 # pixel offsets (di, dj): the neighbour across side s, the pixel B ahead of side s, and A = B's neighbour across side s
@@ -169,10 +169,10 @@ def polygonize(classes, K: int, connectivity: int = 8, device=None) -> PolygonSe
     dev = classes.device if isinstance(classes, torch.Tensor) else (None if device is None else torch.device(device))
     if dev is not None and dev.type == "cuda":
         from .. import ops
-        if not isinstance(classes, torch.Tensor):                # (a copy: torch wraps writable memory only)
-            classes = torch.from_numpy(np.array(_check_map(classes, "polygonize"), order="C"))
-        c = classes.to(dev)
-        labels, err = ops.label_patches(c, K, connectivity)
+        from .analysis import device_labels, map_plane
+        is_tensor = isinstance(classes, torch.Tensor)
+        c = classes.to(dev) if is_tensor else map_plane(_check_map(classes, "polygonize"), None, False, dev)
+        c, labels, _, err = device_labels(c, K, PatchConfig(connectivity), areas=False)
         polys = ops.patch_outlines(labels, c, connectivity)
         if int(err):
             raise ValueError(f"polygonize: class value out of range (K={K})")

@@ -289,39 +289,6 @@ class PatchTracks:
 
 
 # ---------------------------------------------------------------------------------------------- maps in, table out
-def check_against_map(against, shape, K: int, who: str):
-    """a map to compare with: a uint8 [h, w] class map on the grid ``shape`` with values < K, or a ``PolygonSet`` in pixel
-    coordinates with values < K (returned as it is, for the caller to burn where its map lives).  ``ValueError``
-    otherwise"""
-    from ..data.polygons import PolygonSet
-    if isinstance(against, PolygonSet):
-        against.tables()                            # raises for polygons that are still in world coordinates
-        if len(against) and int(against.values.max()) >= K:
-            raise ValueError(f"{who}: polygon value {int(against.values.max())} out of range (K={K})")
-        return against
-    m = np.asarray(against)
-    if m.dtype != np.uint8:
-        raise ValueError(f"{who}: the map must be uint8, got {m.dtype}")
-    if m.ndim != 2 or m.size == 0 or (shape is not None and tuple(m.shape) != tuple(shape)):
-        raise ValueError(f"{who}: the map {tuple(m.shape)} must lie on the raster's grid"
-                         + ("" if shape is None else f" {tuple(shape)}"))
-    if int(m.max()) >= K:
-        raise ValueError(f"{who}: class value {int(m.max())} out of range (K={K})")
-    return m
-
-
-def _device_patches(classes, K: int, config: PatchConfig, err):
-    """label -> areas -> (sieve) -> table of a uint8 device map: (labels, PatchTable); a sieve works on a copy"""
-    from .. import ops
-    if config.sieves:
-        classes = classes.clone()
-    labels, _ = ops.label_patches(classes, K, config.connectivity, err=err)
-    area = ops.patch_areas(labels)
-    if config.sieves:
-        ops.sieve_patches(classes, labels, area, config.min_pixels)
-    return labels, ops.patch_table(labels, classes, area, reuse_area_plane=True)
-
-
 def patch_overlaps(map_a, map_b, K: int, config_a: Optional[PatchConfig] = None, config_b: Optional[PatchConfig] = None,
                    device=None, shape=None) -> PatchOverlaps:
     """the ``PatchOverlaps`` of two maps on one grid: uint8 class maps (arrays or tensors), or ``PolygonSet``s in pixel
@@ -333,7 +300,8 @@ def patch_overlaps(map_a, map_b, K: int, config_a: Optional[PatchConfig] = None,
     ``ops.label_patches`` -> ``ops.patch_areas`` -> (``ops.sieve_patches``) -> ``ops.patch_table`` on both maps, then
     ``ops.patch_overlaps``: only the tables are downloaded.  Neither input is written"""
     import torch
-    from ..data.polygons import PolygonSet, rasterize
+    from ..data.polygons import PolygonSet
+    from .analysis import check_against_map, device_patches, map_plane
     K = int(K)
     if not 2 <= K <= MAX_CLASSES:
         raise ValueError(f"patch_overlaps: K must be in 2..{MAX_CLASSES}, got {K}")
@@ -362,19 +330,13 @@ def patch_overlaps(map_a, map_b, K: int, config_a: Optional[PatchConfig] = None,
                                  f"{tuple(m.shape)}")
             maps[k] = m.to(dev) if on_device else check_against_map(m.cpu().numpy(), shape, K, "patch_overlaps")
             continue
-        m = check_against_map(m, shape, K, "patch_overlaps")
-        if isinstance(m, PolygonSet):
-            maps[k] = rasterize(m, shape, device=dev if on_device else None, all_touched=True)
-        elif on_device:
-            maps[k] = torch.from_numpy(np.array(m, order="C")).to(dev)      # (a copy: torch wraps writable memory only)
-        else:
-            maps[k] = m
+        maps[k] = map_plane(check_against_map(m, shape, K, "patch_overlaps"), shape, True, dev if on_device else None)
     if not on_device:
         planes = [labelled_patches_host(m, K, c) for m, c in zip(maps, configs)]
         return PatchOverlaps(planes[0][2], planes[1][2], *overlap_pairs_host(planes[0][1], planes[1][1]))
     from .. import ops
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    (labels_a, table_a), (labels_b, table_b) = (_device_patches(m, K, c, err) for m, c in zip(maps, configs))
+    (labels_a, table_a), (labels_b, table_b) = (device_patches(m, K, c, err) for m, c in zip(maps, configs))
     rows = ops.patch_overlaps(labels_a, labels_b)
     if int(err.cpu()):
         raise ValueError(f"patch_overlaps: class value out of range (K={K})")

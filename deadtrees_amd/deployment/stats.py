@@ -177,36 +177,6 @@ class RasterStats:
         return f"RasterStats(counts={self._counts.tolist()}, pixel_area_m2={self.pixel_area_m2!r}{tail})"
 
 
-def check_zones(zones, shape, n_zones: Optional[int] = None):
-    """the ``zones`` / ``n_zones`` arguments of ``infer_tile`` -> (uint8 [h, w] array, Z); ``ValueError`` for a wrong
-    shape or dtype, ``n_zones`` outside 1..8 or smaller than ``zones.max() + 1``.  ``zones`` None -> (None, 1).  A
-    ``PolygonSet`` in the raster's pixel coordinates (``data/polygons.py``: zone ids as polygon values, 0 outside every
-    polygon) is returned as it is, for the caller to burn where its map lives; its largest value stands for
-    ``zones.max()``"""
-    from ..data.polygons import PolygonSet
-    if zones is None:
-        if n_zones not in (None, 1):
-            raise ValueError(f"n_zones={n_zones} needs a zones map (without one every pixel is zone 0)")
-        return None, 1
-    if isinstance(zones, PolygonSet):
-        zones.tables()                              # raises for polygons that are still in world coordinates
-        z = zones
-        need = int(zones.values.max()) + 1 if len(zones) else 1
-    else:
-        z = np.asarray(zones)
-        if z.dtype != np.uint8:
-            raise ValueError(f"zones must be uint8, got {z.dtype}")
-        if tuple(z.shape) != tuple(shape):
-            raise ValueError(f"zones {tuple(z.shape)} must lie on the raster's grid {tuple(shape)}")
-        need = int(z.max()) + 1
-    Z = need if n_zones is None else int(n_zones)
-    if not 1 <= Z <= MAX_ZONES:
-        raise ValueError(f"n_zones must be in 1..{MAX_ZONES}, got {Z}")
-    if Z < need:
-        raise ValueError(f"n_zones={Z} is smaller than zones.max() + 1 = {need}")
-    return z, Z
-
-
 # ---------------------------------------------------------------------- computestats_inference.py
 REFERENCE_CLASSES = (0, 1, 2)       # computestats_inference.py:12
 

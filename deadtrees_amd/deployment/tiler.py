@@ -26,38 +26,10 @@ from typing import List, Optional, Tuple, Union
 import numpy as np
 import torch
 
+from .analysis import MapAnalysis, run_device, run_host
 from .outlines import outlines_geojson, polygonize, polygonize_host, write_outlines_geojson  # noqa: F401
 from .overlaps import (PatchMatch, PatchOverlaps, PatchTracks, overlap_pairs_host, patch_overlaps)  # noqa: F401
-from .patches import PatchConfig, PatchTable, check_patches  # noqa: F401  (the ``patches`` argument of infer_tile)
-
-
-def check_outlines(outlines, config, who: str) -> bool:
-    """the ``outlines`` argument of ``infer_tile`` / ``Tiler.stats`` -> bool; outlines without patches are a ``ValueError``"""
-    if outlines is None:
-        return False
-    if not isinstance(outlines, bool):
-        raise ValueError(f"{who}: outlines must be True, False or None, got {outlines!r}")
-    if outlines and config is None:
-        raise ValueError(f"{who}: outlines need patches (the outlines are those of the PatchTable's patches)")
-    return outlines
-
-
-def check_against(against, against_patches, config, shape, K, who: str):
-    """the ``against`` / ``against_patches`` arguments of ``infer_tile`` / ``Tiler.stats`` -> ``(map, PatchConfig)``, or
-    ``(None, None)`` when no map was given.  ``against`` without patches, on another grid, of another dtype or with a value
-    >= K is a ``ValueError``; ``against_patches`` defaults to the connectivity of ``patches`` without a sieve"""
-    from .overlaps import check_against_map
-    if against is None:
-        if against_patches is not None:
-            raise ValueError(f"{who}: against_patches needs against")
-        return None, None
-    if config is None:
-        raise ValueError(f"{who}: against needs patches (the overlaps are those of the PatchTable's patches)")
-    if against_patches is None:
-        against_patches = PatchConfig(config.connectivity)
-    elif not isinstance(against_patches, PatchConfig):
-        raise ValueError(f"{who}: against_patches must be a PatchConfig or None, got {against_patches!r}")
-    return check_against_map(against, shape, int(K), who), against_patches
+from .patches import PatchConfig, PatchTable  # noqa: F401  (the ``patches`` argument of infer_tile)
 
 
 def divisible_without_remainder(a, b):
@@ -270,46 +242,22 @@ class Tiler:
 
     def stats(self, zones=None, classes: int = 3, n_zones: Optional[int] = None, patches=None, outlines=None,
               against=None, against_patches=None):
-        """``RasterStats`` of ``result`` (``stats.zonal_counts_host``): what ``infer_tile(..., stats=True)`` returns, for a
-        caller of the reference's own ``get_batches`` / ``put_batches`` loop.  ``zones``: uint8 [h, w] on the raster's grid
-        (``n_zones`` defaults to ``zones.max() + 1``) or a ``PolygonSet`` in its pixel coordinates (burnt by
-        ``rasterize_host``; ``n_zones`` defaults to the largest value + 1); ``classes``: the model's class count.  ``patches`` (True or a
-        ``PatchConfig``): the statistics carry the ``PatchTable`` of the map (``patches.patches_host``); a configuration
-        that sieves changes ``result`` itself, and the counts are those of the sieved map.  ``outlines=True`` (needs
-        ``patches``): the statistics also carry the patches' outlines (``outlines.polygonize_host`` on the final label
-        plane), polygon ``k`` for row ``k`` of the table.  ``against`` (needs ``patches``): a uint8 class map on the raster's
-        grid or a ``PolygonSet`` in its pixel coordinates (burnt with ``all_touched=True``), with ``against_patches`` its
-        ``PatchConfig`` (default: the connectivity of ``patches``, no sieve): the statistics carry ``.overlaps``, the
-        ``PatchOverlaps`` of that map (A) and the final map (B) (``deployment/overlaps.py``)"""
-        from ..data.polygons import PolygonSet, rasterize_host
-        from .outlines import outlines_from_labels
-        from .overlaps import PatchOverlaps, overlap_pairs_host
-        from .patches import labelled_patches_host
-        from .stats import RasterStats, check_zones, zonal_counts_host
+        """``RasterStats`` of ``result``: what ``infer_tile(..., stats=True)`` returns, for a caller of the reference's own
+        ``get_batches`` / ``put_batches`` loop, computed on the host (``analysis.run_host``).  ``classes``: the model's class
+        count; ``zones`` / ``n_zones`` / ``patches`` / ``outlines`` / ``against`` / ``against_patches``: as in ``infer_tile``,
+        with the same rules (``MapAnalysis``).  Polygons are burnt by ``rasterize_host``; a ``patches`` configuration that
+        sieves changes ``result`` itself, and the counts are those of the sieved map"""
         if self._outdata is None:
             raise RuntimeError("Tiler: load_file / load_array first")
-        config = check_patches(patches)
-        outlines = check_outlines(outlines, config, "Tiler.stats")
-        result = self.result
-        against, against_config = check_against(against, against_patches, config, result.shape, classes, "Tiler.stats")
-        zones, Z = check_zones(zones, result.shape, n_zones)
-        if isinstance(zones, PolygonSet):
-            zones = rasterize_host(zones, result.shape[0], result.shape[1])
-        table = rings = pairs = None
-        if config is not None:
-            sieved, labels, table = labelled_patches_host(result, classes, config)
-            if against is not None:
-                if isinstance(against, PolygonSet):
-                    against = rasterize_host(against, result.shape[0], result.shape[1], all_touched=True)
-                _, labels_a, table_a = labelled_patches_host(against, classes, against_config)
-                pairs = PatchOverlaps(table_a, table, *overlap_pairs_host(labels_a, labels))
-            if outlines:
-                rings = outlines_from_labels(labels, sieved, config.connectivity)
-            if config.sieves:
-                self._outdata[0:result.shape[0], 0:result.shape[1]] = sieved
-                result = self.result
-        return RasterStats(zonal_counts_host(np.ascontiguousarray(result), zones, classes, Z), patches=table,
-                           outlines=rings, overlaps=pairs)
+        return self._analyse(MapAnalysis.of("Tiler.stats", self.result.shape, classes, zones, against, n_zones=n_zones,
+                                            patches=patches, outlines=outlines, against_patches=against_patches))
+
+    def _analyse(self, request: MapAnalysis):
+        """the ``RasterStats`` of ``result`` under a checked request (``analysis.run_host``); a sieved map replaces ``result``"""
+        sieved, stats = run_host(request, self.result)
+        if request.patches is not None and request.patches.sieves:
+            self.result[...] = sieved                            # a view into ``_outdata``
+        return stats
 
     def write_file(self, outfile: Union[str, Path]) -> None:
         """reference tiler.py:136-142 (LZW-compressed tiled GeoTIFF through rioxarray)"""
@@ -330,31 +278,24 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
     independent: no collective).  Yields ``(key, class_map)`` in input order of the rank's share; rasters whose band 1
     holds only 0 / 255 (``is_valid_tile``, :60-62) are skipped like the reference does — ``(key, None)`` — without a
     forward pass (device reduction over the uploaded raster, ``ops.band_has_data``).  ``overlap`` / ``blend`` /
-    ``return_probs`` / ``tta`` / ``stats`` / ``n_zones`` / ``patches`` / ``outlines``: as in ``infer_tile`` (every raster stays on its rank, so overlap
-    needs no exchange); ``zones``: a callable ``key -> uint8 [h, w] array, PolygonSet or None``, or a mapping (a missing
-    key is None); ``against``: the same for the map every raster is compared with (a uint8 array, a ``PolygonSet`` or
-    None: that raster's statistics carry no overlaps), ``against_patches`` as in ``infer_tile``.
+    ``return_probs`` / ``tta`` / ``stats`` / ``n_zones`` / ``patches`` / ``outlines`` / ``against_patches``: as in
+    ``infer_tile``, with the same rules, checked before the first raster is read (every raster stays on its rank, so
+    overlap needs no exchange); ``zones``: a callable ``key -> uint8 [h, w] array, PolygonSet or None``, or a mapping (a
+    missing key is None); ``against``: the same for the map every raster is compared with (a uint8 array, a ``PolygonSet``
+    or None: that raster's statistics carry no overlaps).
     The second item of every pair is whatever ``infer_tile`` returned: with ``stats=True`` ``(map, RasterStats)`` — the
     ``RasterStats`` of a rank's share add up (``+``) to that rank's part of the regional totals."""
-    if zones is not None and not stats:
-        raise ValueError("infer_rasters: zones need stats=True")
-    if check_patches(patches) is not None and not stats:
-        raise ValueError("infer_rasters: patches need stats=True")
-    check_outlines(outlines, check_patches(patches), "infer_rasters")
-    if against is not None and (not stats or check_patches(patches) is None):
-        raise ValueError("infer_rasters: against needs stats=True and patches")
-    if against is None and against_patches is not None:
-        raise ValueError("infer_rasters: against_patches needs against")
+    rules = MapAnalysis.rules("infer_rasters", getattr(inference, "classes", None) if stats else None, stats, zones, n_zones,
+                              patches, outlines, against, against_patches)
     for i, item in enumerate(rasters):
         if i % world != rank:
             continue
         key, arr = item if isinstance(item, tuple) else (i, item)
         z = None if zones is None else zones(key) if callable(zones) else zones.get(key)
         other = None if against is None else against(key) if callable(against) else against.get(key)
-        yield key, infer_tile(inference, arr, subtile=subtile, batch_size=batch_size, device=device, tile_shape=tile_shape,
-                              skip_blank=skip_blank, overlap=overlap, blend=blend, return_probs=return_probs, tta=tta,
-                              stats=stats, zones=z, n_zones=n_zones, patches=patches, outlines=outlines, against=other,
-                              against_patches=None if other is None else against_patches)
+        request = None if rules is None else rules.bind("infer_tile", np.shape(arr)[1:], z, other)
+        yield key, _infer_tile(inference, arr, request, subtile, batch_size, 0, 1, device, None, tile_shape, None, skip_blank,
+                               overlap, blend, return_probs, tta)
 
 
 def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size: int = 64, rank: int = 0,
@@ -380,63 +321,50 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     stitched device path, ``overlap=0`` included (``_infer_tile_stitched``); ``batch_size`` counts forward tiles.
 
     ``stats=True`` returns ``(map, RasterStats)`` (``(map, probs, RasterStats)`` with ``return_probs``; a blank raster under
-    ``skip_blank`` is still None): the class counts of the map (``deployment/stats.py``), K = ``inference.classes``.
-    ``zones``: a uint8 [h, w] array on the raster's grid (forest mask, land use, a previous year's map — the counts are then
-    the year-to-year transition matrix) splits the counts by zone, ``n_zones`` (<= 8) defaults to ``zones.max() + 1``.  On
-    every device path the zones are uploaded next to the raster and ONE ``ops.zonal_counts`` runs on the final device map
-    before its download; the host path (``on_device=False``, ``world > 1``, CPU) counts the merged map with
-    ``zonal_counts_host``.  The map is the one the call without ``stats`` returns.  ``zones`` may also be a ``PolygonSet``
-    in the raster's pixel coordinates (``data/polygons.py``: forest masks and stand boundaries arrive as polygons; zone ids
-    as values, 0 outside every polygon, ``n_zones`` defaults to the largest value + 1): on the device paths the plane is
-    burnt on the device (``ops.rasterize_polygons``) in place of its upload, on the host path by ``rasterize_host``; maps
-    and counts are those of the call with the burnt array.
+    ``skip_blank`` is still None): the class counts of the map (``deployment/stats.py``), K = ``inference.classes``.  The
+    options below need it; their rules are checked by ``MapAnalysis`` (``deployment/analysis.py``) before anything runs.  On
+    every device path the maps they name are uploaded next to the raster — a ``PolygonSet`` in the raster's pixel
+    coordinates is burnt in HBM instead (``ops.rasterize_polygons``) — and everything is computed from the final map in
+    HBM before its download, in the fixed order of ``analysis.run_device``; the host path (``on_device=False``,
+    ``world > 1``, CPU) runs the same contracts in numpy / scipy on the merged map (``analysis.run_host``).
 
-    ``patches=True`` or a ``PatchConfig(connectivity=8, min_pixels=0)`` (needs ``stats=True``): the ``RasterStats`` carries
-    the map's ``PatchTable`` as ``.patches`` (``deployment/patches.py``: one row per connected dead-tree patch).  On every
-    device path the final map is labelled, measured and — with ``min_pixels > 1`` — sieved in HBM before the counts and the
-    download (``ops.label_patches`` / ``patch_areas`` / ``sieve_patches`` / ``patch_table``); the host path runs the same
-    contract in numpy / scipy.  With a sieve the returned map is the sieved one and ``counts`` are the counts of the
-    RETURNED map; the probabilities of ``return_probs`` are not touched by the sieve.  With ``min_pixels <= 1`` the map is
-    bit-identical to the call without ``patches``.
+    ``zones``: a uint8 [h, w] array on the raster's grid (forest mask, land use, a previous year's map — the counts are then
+    the year-to-year transition matrix) splits the counts by zone (ONE ``ops.zonal_counts``), ``n_zones`` (<= 8) defaults
+    to ``zones.max() + 1``.  The map is the one the call without ``stats`` returns.  As a ``PolygonSet`` (``data/polygons.py``:
+    forest masks and stand boundaries arrive as polygons; zone ids as values, 0 outside every polygon, ``n_zones`` defaults
+    to the largest value + 1) maps and counts are those of the call with the burnt array.
+
+    ``patches=True`` or a ``PatchConfig(connectivity=8, min_pixels=0)``: the ``RasterStats`` carries the map's ``PatchTable``
+    as ``.patches`` (``deployment/patches.py``: one row per connected dead-tree patch).  With ``min_pixels > 1`` the map is
+    sieved before the counts: the returned map is the sieved one and ``counts`` are the counts of the RETURNED map; the
+    probabilities of ``return_probs`` are not touched by the sieve.  With ``min_pixels <= 1`` the map is bit-identical to the
+    call without ``patches``.
 
     ``outlines=True`` (needs ``patches``): the ``RasterStats`` also carries ``.outlines``, a ``PolygonSet`` on the raster's
     grid with one polygon per patch — polygon ``k`` is row ``k`` of ``.patches`` (``deployment/outlines.py``: exact ring
-    tracing along the pixel edges; ``outlines_geojson`` writes them out).  On every device path they are traced from the
-    final label plane, after the sieve, in HBM before the map leaves the device (``ops.patch_outlines``: only the four
-    ``PolygonSet`` arrays are downloaded); the host path runs ``polygonize_host``.  The map, the counts and the table are
-    those of the call without ``outlines``.
+    tracing along the pixel edges of the final label plane, after the sieve; ``outlines_geojson`` writes them out).  The
+    map, the counts and the table are those of the call without ``outlines``.
 
-    ``against`` (needs ``stats=True`` and ``patches``): a map to compare the result with patch by patch — a uint8 [h, w]
-    class map on the raster's grid with values < K (last year's map, a burnt annotation) or a ``PolygonSet`` in its pixel
-    coordinates (the annotators' polygons; burnt with ``all_touched=True``, the rule of the training masks).  The
-    ``RasterStats`` carries ``.overlaps``, a ``PatchOverlaps`` (``deployment/overlaps.py``): ``table_a`` the patches of
-    ``against`` under ``against_patches`` (a ``PatchConfig``; default: the connectivity of ``patches``, no sieve),
-    ``table_b`` the ``.patches`` of the final map, and one row per pair of patches that share a pixel — ``match()`` gives
-    the crown-level accuracy, ``track()`` the year-to-year fate of every patch.  On every device path ``against`` is
-    uploaded next to the raster (a ``PolygonSet`` is burnt in HBM instead), labelled, sieved if asked and tabled there, and
-    ``ops.patch_overlaps`` runs on the two label planes before the map is downloaded; the host path runs
-    ``overlap_pairs_host``.  The map, the counts, the table and the outlines are those of the call without ``against``."""
+    ``against`` (needs ``patches``): a map to compare the result with patch by patch — a uint8 [h, w] class map on the
+    raster's grid with values < K (last year's map, a burnt annotation) or a ``PolygonSet`` in its pixel coordinates (the
+    annotators' polygons; burnt with ``all_touched=True``, the rule of the training masks).  The ``RasterStats`` carries
+    ``.overlaps``, a ``PatchOverlaps`` (``deployment/overlaps.py``): ``table_a`` the patches of ``against`` under
+    ``against_patches`` (a ``PatchConfig``; default: the connectivity of ``patches``, no sieve), ``table_b`` the
+    ``.patches`` of the final map, and one row per pair of patches that share a pixel — ``match()`` gives the crown-level
+    accuracy, ``track()`` the year-to-year fate of every patch.  The map, the counts, the table and the outlines are those
+    of the call without ``against``."""
+    request = MapAnalysis.of("infer_tile", np.shape(arr_chw_u8)[1:], getattr(inference, "classes", None) if stats else None,
+                             zones, against, stats=stats, n_zones=n_zones, patches=patches, outlines=outlines,
+                             against_patches=against_patches)
+    return _infer_tile(inference, arr_chw_u8, request, subtile, batch_size, rank, world, device, group, tile_shape, on_device,
+                       skip_blank, overlap, blend, return_probs, tta)
+
+
+def _infer_tile(inference, arr_chw_u8, request: Optional[MapAnalysis], subtile, batch_size, rank, world, device, group,
+                tile_shape, on_device, skip_blank, overlap, blend, return_probs, tta):
+    """``infer_tile`` behind the check of its statistics options: ``request`` is their ``MapAnalysis``, None without ``stats``"""
     if blend not in ("crop", "average"):
         raise ValueError(f"blend {blend!r}: use 'crop' or 'average'")
-    want_stats = None
-    config = check_patches(patches)
-    outlines = check_outlines(outlines, config, "infer_tile")
-    if not stats:
-        if zones is not None or n_zones is not None:
-            raise ValueError("infer_tile: zones / n_zones need stats=True")
-        if config is not None:
-            raise ValueError("infer_tile: patches need stats=True")
-        if against is not None or against_patches is not None:
-            raise ValueError("infer_tile: against / against_patches need stats=True")
-    else:
-        from .stats import check_zones
-        zones, Z = check_zones(zones, np.shape(arr_chw_u8)[1:], n_zones)
-        K = getattr(inference, "classes", None)
-        if K is None:
-            raise ValueError("infer_tile: stats=True needs an inference object with a `classes` count")
-        against, against_patches = check_against(against, against_patches, config, np.shape(arr_chw_u8)[1:], K,
-                                                 "infer_tile")
-        want_stats = (zones, int(K), Z, config, outlines, against, against_patches)
     members = getattr(inference, "members", None)
     if overlap or tta is not None or members is not None:
         views = None if tta is None else tta_views(tta)
@@ -454,7 +382,7 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
         if arr_chw_u8.dtype != np.uint8:
             raise ValueError(f"infer_tile: the stitched device path reads a uint8 raster, got {arr_chw_u8.dtype}")
         return _infer_tile_stitched(inference, models, vote, arr_chw_u8, subtile, overlap, blend, batch_size, device,
-                                    skip_blank, return_probs, views, want_stats)
+                                    skip_blank, return_probs, views, request)
     if return_probs:
         raise ValueError("infer_tile: return_probs needs overlap > 0 and blend='average'")
     if tile_shape is None:
@@ -470,7 +398,7 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
         if world != 1:
             raise ValueError("infer_tile: the on-device split / merge is the single-rank form")
         return _infer_tile_on_device(inference, arr_chw_u8, subtile, batch_size, device, tile_shape, skip_blank,
-                                     want_stats)
+                                     request)
     if skip_blank and bool(np.isin(arr_chw_u8[0], [0, 255]).all()):    # scripts/inference.py:60-62 is_valid_tile
         return None
     t = Tiler(tile_shape=tile_shape, subtile_shape=(subtile, subtile))
@@ -491,96 +419,31 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
             for j, o in lst:
                 outs[j] = o
     t.put_batches(np.concatenate(outs, axis=0))
-    if want_stats is not None:
-        st = t.stats(*want_stats)           # before the map is read: a sieve changes it
+    if request is not None:
+        st = t._analyse(request)            # before the map is read: a sieve changes it
         return t.result, st
     return t.result
 
 
-def _upload(inference, arr_chw_u8: np.ndarray, device: str, skip_blank: bool, want_stats):
+def _upload(inference, arr_chw_u8: np.ndarray, device: str, skip_blank: bool, request: Optional[MapAnalysis]):
     """the start of every device path: ONE uint8 H2D copy of the band planes the network reads (the N of an RGBN raster
-    under an RGB model stays on the host), the zones map of a ``stats=True`` call uploaded next to it (None without one;
-    a ``PolygonSet`` is rasterised on the device instead),
-    the ``against`` map alike (a ``PolygonSet`` is burnt with ``all_touched=True``),
-    and ``skip_blank``'s ``is_valid_tile`` on the uploaded raster.  Returns ``(raster, (zones, against))`` on the device, or
-    None for a raster with nothing but 0 / 255 in band 1"""
+    under an RGB model stays on the host), the request's maps next to it (``MapAnalysis.device_planes``) and ``skip_blank``'s
+    ``is_valid_tile`` on the device: ``(raster, (zones, against))``, or None for a raster with only 0 / 255 in band 1"""
     C = arr_chw_u8.shape[0]
     nch = int(getattr(inference, "in_channels", C) or C)
     if 0 < nch < C:
         arr_chw_u8 = arr_chw_u8[:nch]
     x = torch.from_numpy(np.ascontiguousarray(arr_chw_u8)).to(device, non_blocking=True)
-    zones_dev = against_dev = None
-    if want_stats is not None and want_stats[0] is not None:
-        from ..data.polygons import PolygonSet, rasterize
-        if isinstance(want_stats[0], PolygonSet):          # burnt where it is read: the tables travel, not the plane
-            zones_dev = rasterize(want_stats[0], arr_chw_u8.shape[1:], device=x.device)
-        else:
-            zones_dev = torch.from_numpy(np.ascontiguousarray(want_stats[0])).to(device, non_blocking=True)
-    if want_stats is not None and want_stats[5] is not None:
-        from ..data.polygons import PolygonSet, rasterize
-        if isinstance(want_stats[5], PolygonSet):
-            against_dev = rasterize(want_stats[5], arr_chw_u8.shape[1:], device=x.device, all_touched=True)
-        else:                                              # (a copy: torch wraps writable memory only)
-            against_dev = torch.from_numpy(np.array(want_stats[5], order="C")).to(device, non_blocking=True)
+    planes = (None, None) if request is None else request.device_planes(arr_chw_u8.shape[1:], x.device)
     if skip_blank:
         from .. import ops
         if int(ops.band_has_data(x[0])) == 0:
             return None
-    return x, (zones_dev, against_dev)
-
-
-def _download(out: torch.Tensor, probs: Optional[torch.Tensor], want_stats, planes):
-    """the end of every device path: the D2H copy of the final map ``out`` (uint8 [h, w], contiguous) and of the
-    probabilities when there are any.  ``planes``: ``_upload``'s (zones, against) on the device.  With ``want_stats`` =
-    (zones, K, Z, patch config, outlines, against, its patch config) one ``ops.zonal_counts`` is enqueued
-    on ``out`` BEFORE the download (no synchronisation of its own); the counts and the flag are read after the map has
-    arrived.  With a patch configuration ``out`` is labelled, its patch areas are taken and — if the configuration sieves —
-    it is sieved IN PLACE, all before the counts; the roots are compacted and measured behind the download (the compaction
-    reads the row count back).  Labels, the area plane (reused as the root -> row plane) and the compaction's flags are
-    the workspace: about 12 bytes per pixel next to the map.  With ``outlines`` the final label plane is traced behind the
-    table (``ops.patch_outlines``: two more scalar read-backs, 4 bytes per pixel and 40 per boundary edge of workspace).
-    With ``against`` that map is labelled, sieved if asked and tabled like ``out`` (its own label and area planes), and
-    ``ops.patch_overlaps`` reads the two final label planes behind the tables: three more scalar read-backs, 8 bytes per
-    1024 pixels and 12 per run of workspace"""
-    if want_stats is None:
-        return out.cpu().numpy() if probs is None else (out.cpu().numpy(), probs.cpu().numpy())
-    from .. import ops
-    from .stats import RasterStats
-    _, K, Z, config, outlines, against, against_config = want_stats
-    zones_dev, against_dev = planes
-    labels = area = table = rings = pairs = None
-    err = torch.zeros(1, dtype=torch.int32, device=out.device)
-    if config is not None:
-        labels, _ = ops.label_patches(out, K, config.connectivity, err=err)
-        area = ops.patch_areas(labels)
-        if config.sieves:
-            ops.sieve_patches(out, labels, area, config.min_pixels)
-    counts, _ = ops.zonal_counts(out, zones_dev, K, Z, err=err)
-    host = torch.empty(out.shape, dtype=out.dtype, pin_memory=True) if config is not None else None
-    if host is not None:
-        host.copy_(out, non_blocking=True)                      # enqueued; the table's read-back waits for it
-        table = ops.patch_table(labels, out, area, reuse_area_plane=True)
-        if outlines:
-            rings = ops.patch_outlines(labels, out, config.connectivity)
-        if against is not None:
-            from .overlaps import PatchOverlaps, _device_patches
-            labels_a, table_a = _device_patches(against_dev, K, against_config, err)
-            pairs = PatchOverlaps(table_a, table, *ops.patch_overlaps(labels_a, labels))
-        torch.cuda.current_stream(out.device).synchronize()
-        result = (host.numpy(),)
-    else:
-        result = (out.cpu().numpy(),)
-    if probs is not None:
-        result += (probs.cpu().numpy(),)
-    flag = int(err.cpu())
-    if flag:          # cannot happen with checked zones: the map is an argmax over K classes
-        raise RuntimeError(f"infer_tile: raster statistics met a value out of range (flag {flag}: 1 class >= {K}, "
-                           f"2 zone >= {Z})")
-    return result + (RasterStats(counts.cpu().numpy(), patches=table, outlines=rings, overlaps=pairs),)
+    return x, planes
 
 
 def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch_size: int, device: str,
-                          tile_shape: Tuple[int, int], skip_blank: bool = False, want_stats=None):
+                          tile_shape: Tuple[int, int], skip_blank: bool = False, request=None):
     """single-rank form of ``infer_tile`` with the block split / merge on the device: ONE uint8 H2D copy of the raster, the
     sub-tiles of ``Tiler.get_batches`` (same ones, same row-major order: the [0:ceil(h/d), 0:ceil(w/d)] blocks of the
     zero-padded tile, reference tiler.py:121-134 + utils/data_handling.py:9-20) as a strided view -> NHWC uint8 batches
@@ -592,7 +455,7 @@ def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch
     if tile_shape[0] % d or tile_shape[1] % d:
         raise ValueError(f"Shapes unaligned: {tuple(tile_shape)} / {d}")
     nby, nbx = -(-h // d), -(-w // d)
-    up = _upload(inference, arr_chw_u8, device, skip_blank, want_stats)
+    up = _upload(inference, arr_chw_u8, device, skip_blank, request)
     if up is None:
         return None
     x, planes = up
@@ -609,11 +472,11 @@ def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch
         outs = [inference.run_u8(blocks[j:j + batch_size], device=device) for j in range(0, nby * nbx, batch_size)]
     maps = (outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)).to(torch.uint8)
     merged = maps.view(nby, nbx, d, d).permute(0, 2, 1, 3).reshape(nby * d, nbx * d)
-    return _download(merged[:h, :w].contiguous(), None, want_stats, planes)
+    return run_device(request, merged[:h, :w].contiguous(), None, planes)
 
 
 def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.ndarray, d: int, overlap: int, blend: str,
-                         batch_size: int, device: str, skip_blank: bool, return_probs: bool, views, want_stats=None):
+                         batch_size: int, device: str, skip_blank: bool, return_probs: bool, views, request=None):
     """``infer_tile`` on the window grid: overlapping windows, test-time augmentation (``views``: canonical pairs, or None
     for the plain window), an ensemble (``models``; ``vote`` None for a single model) and their combinations.  ONE uint8 H2D
     copy of the raster; per model and batch of windows one gather (``dt_window_normalize_u8``) + forward + one stitch kernel
@@ -629,7 +492,7 @@ def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.
     _, h, w = arr_chw_u8.shape
     ny, nx, _ = window_grid(h, w, d, overlap)
     n = ny * nx
-    up = _upload(inference, arr_chw_u8, device, skip_blank, want_stats)
+    up = _upload(inference, arr_chw_u8, device, skip_blank, request)
     if up is None:
         return None
     x, planes = up
@@ -657,11 +520,11 @@ def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.
         maps = [class_map(m) for m in models]
         if len(maps) > 1:
             maps = [ops.ensemble_vote(torch.stack(maps, dim=0), int(inference.classes), dtype="uint8")[0]]
-        return _download(maps[0], None, want_stats, planes)
+        return run_device(request, maps[0], None, planes)
     acc = None
     for m in models:
         acc = accumulate(m, acc)
     if return_probs:
         classes, probs = ops.stitch_finalize(acc, want_probs=True)
-        return _download(classes, probs, want_stats, planes)
-    return _download(ops.stitch_finalize(acc), None, want_stats, planes)
+        return run_device(request, classes, probs, planes)
+    return run_device(request, ops.stitch_finalize(acc), None, planes)

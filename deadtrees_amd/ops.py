@@ -345,10 +345,7 @@ def head_eval(x, w_ohwi, bias, labels, lu=None, dist=None, gamma: float = 2.0, c
         counts = torch.zeros((2, K, K), dtype=torch.int64, device=dev)
     elif counts.dtype != torch.int64 or tuple(counts.shape) != (2, K, K) or counts.device != dev or not counts.is_contiguous():
         raise RuntimeError(f"head_eval: counts must be a contiguous int64 [2,{K},{K}] on {dev}")
-    if err is None:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-    elif err.dtype != torch.int32 or err.numel() < 1 or err.device != dev:
-        raise RuntimeError(f"head_eval: err must be int32[1] on {dev}")
+    err = _err_flag("head_eval", err, dev)
     n = lib.dt_head_eval_acc_doubles(B, K, H, W)
     if n <= 0:
         raise RuntimeError(f"head_eval: bad sizes B={B} K={K} H={H} W={W}")
@@ -1104,10 +1101,7 @@ def zonal_counts(classes_u8: torch.Tensor, zones_u8: torch.Tensor = None, K: int
         counts = torch.zeros((max(Z, 0), max(K, 0)), dtype=torch.int64, device=dev)
     elif counts.dtype != torch.int64 or tuple(counts.shape) != (Z, K) or counts.device != dev or not counts.is_contiguous():
         raise RuntimeError(f"zonal_counts: counts must be contiguous int64 [{Z},{K}] on {dev}")
-    if err is None:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-    elif err.dtype != torch.int32 or tuple(err.shape) != (1,) or err.device != dev:
-        raise RuntimeError(f"zonal_counts: err must be int32 [1] on {dev}")
+    err = _err_flag("zonal_counts", err, dev)
     classes_u8 = classes_u8.contiguous()
     zones_u8 = None if zones_u8 is None else zones_u8.contiguous()
     _lib.check(_lib.load().dt_zonal_counts_u8(_p(classes_u8), _p(zones_u8), classes_u8.numel(), K, Z, _p(counts), _p(err),
@@ -1195,38 +1189,42 @@ def rasterize_polygons(edges: torch.Tensor, polys: torch.Tensor, shape, all_touc
     return out
 
 
-def _patch_tile():
-    th, tw = C.c_int(0), C.c_int(0)
-    _lib.check(_lib.load().dt_patch_tile(C.byref(th), C.byref(tw)), "dt_patch_tile")
-    return th.value, tw.value
+# constants asked of the library on first use -> (getter, count).  PATCH_TILE = (th, tw): the tile of dt_label_patches_u8's
+# local launch; OUTLINE_CHUNK / OVERLAP_CHUNK: the consecutive pixels one workgroup of dt_outline_count / dt_overlap_count takes
+_LIB_CONSTANTS = {"PATCH_TILE": ("dt_patch_tile", 2), "OUTLINE_CHUNK": ("dt_outline_chunk", 1),
+                  "OVERLAP_CHUNK": ("dt_overlap_chunk", 1)}
 
 
-def _outline_chunk():
-    chunk = C.c_int(0)
-    _lib.check(_lib.load().dt_outline_chunk(C.byref(chunk)), "dt_outline_chunk")
-    return chunk.value
-
-
-def _overlap_chunk():
-    chunk = C.c_int(0)
-    _lib.check(_lib.load().dt_overlap_chunk(C.byref(chunk)), "dt_overlap_chunk")
-    return chunk.value
+def _constant(name: str):
+    if name not in globals():
+        entry, n = _LIB_CONSTANTS[name]
+        vals = [C.c_int(0) for _ in range(n)]
+        _lib.check(getattr(_lib.load(), entry)(*map(C.byref, vals)), entry)
+        globals()[name] = vals[0].value if n == 1 else tuple(v.value for v in vals)
+    return globals()[name]
 
 
 def __getattr__(name):
-    # PATCH_TILE = (th, tw): the tile of dt_label_patches_u8's local launch, asked of the library on first use
-    if name == "PATCH_TILE":
-        globals()["PATCH_TILE"] = _patch_tile()
-        return globals()["PATCH_TILE"]
-    # OUTLINE_CHUNK: the consecutive pixels one workgroup of dt_outline_count takes
-    if name == "OUTLINE_CHUNK":
-        globals()["OUTLINE_CHUNK"] = _outline_chunk()
-        return globals()["OUTLINE_CHUNK"]
-    # OVERLAP_CHUNK: the consecutive pixels one workgroup of dt_overlap_count takes
-    if name == "OVERLAP_CHUNK":
-        globals()["OVERLAP_CHUNK"] = _overlap_chunk()
-        return globals()["OVERLAP_CHUNK"]
+    if name in _LIB_CONSTANTS:
+        return _constant(name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def _err_flag(what: str, err, device):
+    """the ``err`` argument of a wrapper: int32 [1] on ``device``, allocated zeroed when not given"""
+    if err is None:
+        return torch.zeros(1, dtype=torch.int32, device=device)
+    if err.dtype != torch.int32 or tuple(err.shape) != (1,) or err.device != device:
+        raise RuntimeError(f"{what}: err must be int32 [1] on {device}")
+    return err
+
+
+def _chunk_scan(counts):
+    """int32 [chunks, 2] counts per chunk, scanned: (the two totals as Python ints — ONE read-back —, int32 [chunks]: the
+    exclusive scan of column 0, the first slot of every chunk)"""
+    scan = torch.cumsum(counts, 0, dtype=torch.int32)
+    first, second = (int(v) for v in scan[-1].tolist())
+    return first, second, (scan[:, 0] - counts[:, 0]).contiguous()
 
 
 def _patch_planes(what, classes_u8=None, **planes):
@@ -1252,10 +1250,7 @@ def label_patches(classes_u8: torch.Tensor, K: int, connectivity: int = 8, err=N
     given) and is background.  Returns (labels, err)."""
     h, w = _patch_planes("label_patches", classes_u8)
     dev = classes_u8.device
-    if err is None:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-    elif err.dtype != torch.int32 or tuple(err.shape) != (1,) or err.device != dev:
-        raise RuntimeError(f"label_patches: err must be int32 [1] on {dev}")
+    err = _err_flag("label_patches", err, dev)
     labels = torch.empty((h, w), dtype=torch.int32, device=dev)
     _lib.check(_lib.load().dt_label_patches_u8(_p(classes_u8.contiguous()), h, w, int(K), int(connectivity), _p(labels),
                                                _p(err), _st()), "dt_label_patches_u8")
@@ -1336,13 +1331,11 @@ def patch_outlines(labels: torch.Tensor, classes_u8: torch.Tensor, connectivity:
     lib, dev = _lib.load(), labels.device
     labels, classes_u8 = labels.contiguous(), classes_u8.contiguous()
     i32 = dict(dtype=torch.int32, device=dev)
-    counts = torch.empty((-(-h * w // _outline_chunk()), 2), **i32)
+    counts = torch.empty((-(-h * w // _constant("OUTLINE_CHUNK")), 2), **i32)
     _lib.check(lib.dt_outline_count(_p(labels), h, w, _p(counts), _st()), "dt_outline_count")
-    scan = torch.cumsum(counts, 0, dtype=torch.int32)
-    E, V = (int(v) for v in scan[-1].tolist())                 # read-back 1: edges and vertices
+    E, V, chunk_first = _chunk_scan(counts)                    # read-back 1: edges and vertices
     if E == 0:
         return empty_outlines()
-    chunk_first = (scan[:, 0] - counts[:, 0]).contiguous()
     first = torch.empty(h * w, **i32)
     edges = torch.empty(E, **i32)
     state = torch.empty((2, E, 4), **i32)
@@ -1387,20 +1380,6 @@ def _overlap_planes(labels_a: torch.Tensor, labels_b: torch.Tensor):
     return h, w, planes[0], planes[1]
 
 
-def _overlap_count(lib, a, b, h, w):
-    counts = torch.empty((-(-h * w // _overlap_chunk()), 2), dtype=torch.int32, device=a.device)
-    _lib.check(lib.dt_overlap_count(_p(a), _p(b), h, w, _p(counts), _st()), "dt_overlap_count")
-    return counts
-
-
-def _overlap_runs(lib, a, b, h, w, counts, scan, R):
-    chunk_first = (scan[:, 0] - counts[:, 0]).contiguous()
-    key = torch.empty(R, dtype=torch.int64, device=a.device)
-    start = torch.empty(R, dtype=torch.int32, device=a.device)
-    _lib.check(lib.dt_overlap_runs(_p(a), _p(b), h, w, _p(chunk_first), R, _p(key), _p(start), _st()), "dt_overlap_runs")
-    return key, start
-
-
 def patch_overlaps(labels_a: torch.Tensor, labels_b: torch.Tensor):
     """the overlap table of two label planes int32 [h, w] on one HIP device (``label_patches``, sieved or not; contract in
     ``deployment/overlaps.py``, csrc/overlaps.hip): host int64 arrays ``(a, b, n)``, one row per pair of patches that
@@ -1411,18 +1390,20 @@ def patch_overlaps(labels_a: torch.Tensor, labels_b: torch.Tensor):
     -> (a scan over the chunks; the run count R and the runs with a key are read back: read-back 1) ->
     ``dt_overlap_runs`` (key and start of every run) -> on the R runs only: lengths by difference, ``torch.sort`` by key,
     segment ids where the sorted key changes (the pair count P is read back: read-back 2), a segmented int64 sum of the
-    lengths, the key-0 segment dropped.  Only the three result arrays are downloaded; without any overlap nothing is
-    launched after the count.  Workspace: 8 bytes per chunk of ``OVERLAP_CHUNK`` = 1024 pixels (the second count is what
-    lets a pair of maps without overlap stop after one launch) and 12 bytes per run, plus the sort's own."""
+    lengths, the key-0 segment dropped.  Only the three result arrays are downloaded; without any overlap neither
+    ``dt_overlap_runs`` nor the sort is launched.  Workspace: 8 bytes per chunk of ``OVERLAP_CHUNK`` = 1024 pixels (the second
+    count is what lets a pair of maps without overlap stop after the scan) and 12 bytes per run, plus the sort's own."""
     h, w, a, b = _overlap_planes(labels_a, labels_b)
     lib, dev = _lib.load(), a.device
     empty = tuple(torch.zeros(0, dtype=torch.int64).numpy() for _ in range(3))
-    counts = _overlap_count(lib, a, b, h, w)
-    scan = torch.cumsum(counts, 0, dtype=torch.int32)
-    R, live = (int(v) for v in scan[-1].tolist())              # read-back 1: runs, and runs whose key is not 0
+    counts = torch.empty((-(-h * w // _constant("OVERLAP_CHUNK")), 2), dtype=torch.int32, device=dev)
+    _lib.check(lib.dt_overlap_count(_p(a), _p(b), h, w, _p(counts), _st()), "dt_overlap_count")
+    R, live, chunk_first = _chunk_scan(counts)                 # read-back 1: runs, and runs whose key is not 0
     if live == 0:
         return empty
-    key, start = _overlap_runs(lib, a, b, h, w, counts, scan, R)
+    key = torch.empty(R, dtype=torch.int64, device=dev)
+    start = torch.empty(R, dtype=torch.int32, device=dev)
+    _lib.check(lib.dt_overlap_runs(_p(a), _p(b), h, w, _p(chunk_first), R, _p(key), _p(start), _st()), "dt_overlap_runs")
     length = torch.empty(R, dtype=torch.int64, device=dev)
     length[:-1] = start[1:] - start[:-1]
     length[-1] = h * w - start[-1]
