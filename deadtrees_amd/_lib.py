@@ -257,6 +257,20 @@ def stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+# the two values of dt_conv2d_bf16_config's row_tiles (mt) that name a kernel family instead of a tile multiplier: the
+# LDS-DMA staged kernel (conv_bf16_dma.hip, reads the chunked weight images) and the lean narrow-layer kernel
+# (conv_bf16_narrow.hip)
+BF16_MT_DMA, BF16_MT_NARROW = 8, 16
+
+
+def bf16_config(desc):
+    """(tw, tn, ck, mt) of the kernel dt_conv2d_bf16 picks for `desc`, or None where its validator refuses the descriptor"""
+    o = [C.c_int(-1) for _ in range(4)]
+    if load().dt_conv2d_bf16_config(C.byref(desc), *[C.byref(x) for x in o]) != 0:
+        return None
+    return tuple(x.value for x in o)
+
+
 def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = load().dt_last_error()

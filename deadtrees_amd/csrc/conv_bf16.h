@@ -14,7 +14,10 @@ struct ConvBfArgs {
   // fused BatchNorm-backward reduction (dt_conv2d_bf16_bn_bwd): bnb.y (bf16, shape of `out`) set -> `stats` receives
   // sum g, sum g*xhat of the layer this data gradient belongs to instead of sum v, sum v^2
   dt_bn_bwd_fuse bnb;
-  int B, Hin, Win, C0, C1, mode0, Ho, Wo, Cout, pad, tiles_x, tiles_y, n_tiles, P, cout_split, accumulate;
+  int B, Hin, Win, C0, C1, mode0, Ho, Wo, Cout, pad;
+  // tile geometry: written by the family that launches (n_tiles: the tiled and LDS-DMA kernels only)
+  int tiles_x = 0, tiles_y = 0, n_tiles = 0, P = 0;
+  int cout_split, accumulate;
   int pstats = 0;   // conv_bf16_dma.hip: BatchNorm partial sums accumulated over a workgroup's tiles, one row per workgroup
 };
 

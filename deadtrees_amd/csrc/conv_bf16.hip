@@ -433,19 +433,27 @@ static int bf_dispatch(const ConvBfArgs& a, int tw, int tn, int ck, int mt, hipS
   return bf_launch<KS, STRIDE, 8, 32, 32, 2>(a, st);
 }
 
-static void bf_cfg(const dt_conv_desc* d, int* tw_, int* tn_, int* ck_, int* mt_) {
-  if (d->ksize == 4) {   // space-to-depth stem: one variant
-    *tw_ = 32; *tn_ = 64; *ck_ = 16; *mt_ = 2;
-    return;
-  }
-  if (dt_conv_bf16_narrow_supported(d)) {   // conv_bf16_narrow.hip: Cin, Cout in {16, 32} at full resolution (mt = 16)
-    *tw_ = 32; *tn_ = 16; *ck_ = 16; *mt_ = 16;
-    return;
-  }
-  if (dt_conv_bf16_dma_supported(d)) {   // conv_bf16_dma.hip: 512-pixel x 64-channel tiles, 8 waves (reported as mt = 8)
-    *tw_ = 32; *tn_ = 64; *ck_ = 32; *mt_ = 8;
-    return;
-  }
+// The one place that decides which kernel family runs a descriptor.  tw / tn / ck / mt are what dt_conv2d_bf16_config
+// reports: for BF_NARROW and BF_DMA mt is no tile multiplier but the ABI's name of the family (BF_MT_*).
+enum BfFamily { BF_STEM, BF_NARROW, BF_DMA, BF_TILED };
+enum { BF_MT_DMA = 8, BF_MT_NARROW = 16 };
+struct BfPlan {
+  BfFamily family;
+  int tw, tn, ck, mt;
+  int rows;   // of the statistics buffer
+};
+
+// register-staged tiles (and the stem on them): 128 * mt pixels, tw wide, one statistics row per spatial tile
+static BfPlan bf_tiled_plan(BfFamily family, const dt_conv_desc* d, int tw, int tn, int ck, int mt) {
+  return {family, tw, tn, ck, mt, d->B * dt_cdiv(d->Ho, 128 * mt / tw) * dt_cdiv(d->Wo, tw)};
+}
+
+static BfPlan bf_plan(const dt_conv_desc* d) {
+  if (d->ksize == 4) return bf_tiled_plan(BF_STEM, d, 32, 64, 16, 2);   // space-to-depth stem: one variant
+  // conv_bf16_narrow.hip: Cin, Cout in {16, 32} at full resolution
+  if (dt_conv_bf16_narrow_supported(d)) return {BF_NARROW, 32, 16, 16, BF_MT_NARROW, dt_conv_bf16_narrow_rows(d)};
+  // conv_bf16_dma.hip: 512-pixel x 64-channel tiles, 8 waves
+  if (dt_conv_bf16_dma_supported(d)) return {BF_DMA, 32, 64, 32, BF_MT_DMA, dt_conv_bf16_dma_stat_rows(d)};
   const int tw = d->Wo > 16 ? 32 : (d->Wo > 8 ? 16 : 8);
   int tn = d->Cout >= 64 ? 64 : 32;
   if (d->cout_split > 0 && (d->cout_split % 64) != 0) tn = 32;
@@ -453,35 +461,41 @@ static void bf_cfg(const dt_conv_desc* d, int* tw_, int* tn_, int* ck_, int* mt_
     const long wgs = (long)d->B * dt_cdiv(d->Ho, 256 / tw) * dt_cdiv(d->Wo, tw) * dt_cdiv(d->Cout, 64);
     if (wgs < 512) tn = 32;
   }
-  *tw_ = tw;
-  *tn_ = tn;
-  *ck_ = (tn == 32 && d->ksize == 3 && d->stride == 1 && d->C1 == 0 && d->C0 <= BF_NARROW_CIN) ? 16 : 32;
-  *mt_ = 2;
   if (tn == 64 && tw == 32 && d->ksize == 3 && d->stride == 1 && (d->C0 % 16) == 0 && (d->C1 % 16) == 0 && d->Ho >= 16 &&
       d->Cout >= 128) {
     // 512-pixel tiles when they still fill the chip twice over.  Measured per layer (scripts/bench_conv.py, B=64):
     // +8 % on 128->128 @64x64, +5 % on 384->128 @64x64, nothing on 64-channel outputs (one n-tile) -> Cout >= 128 only
     const long wgs = (long)d->B * dt_cdiv(d->Ho, 16) * dt_cdiv(d->Wo, 32) * dt_cdiv(d->Cout, 64);
-    if (wgs >= 1024) {
-      *mt_ = 4;
-      *ck_ = 16;
-    }
+    if (wgs >= 1024) return bf_tiled_plan(BF_TILED, d, tw, tn, 16, 4);
   }
+  const int ck = (tn == 32 && d->ksize == 3 && d->stride == 1 && d->C1 == 0 && d->C0 <= BF_NARROW_CIN) ? 16 : 32;
+  return bf_tiled_plan(BF_TILED, d, tw, tn, ck, 2);
 }
 
 extern "C" int dt_conv2d_bf16_config(const dt_conv_desc* d, int* tw, int* tn, int* ck, int* mt) {
   if (bf_validate(d) != DT_OK) return DT_EINVAL;
-  bf_cfg(d, tw, tn, ck, mt);
+  const BfPlan p = bf_plan(d);
+  *tw = p.tw; *tn = p.tn; *ck = p.ck; *mt = p.mt;
   return DT_OK;
 }
 
 extern "C" int dt_conv2d_bf16_stat_rows(const dt_conv_desc* d) {
   if (bf_validate(d) != DT_OK) return DT_EINVAL;
-  int tw, tn, ck, mt;
-  bf_cfg(d, &tw, &tn, &ck, &mt);
-  if (mt == 8) return dt_conv_bf16_dma_stat_rows(d);
-  if (mt == 16) return dt_conv_bf16_narrow_rows(d);
-  return d->B * dt_cdiv(d->Ho, 128 * mt / tw) * dt_cdiv(d->Wo, tw);
+  return bf_plan(d).rows;
+}
+
+// everything of the argument block but the tile geometry (tiles_x, tiles_y, n_tiles, P, pstats), which the family that
+// launches writes
+static ConvBfArgs bf_args(const dt_conv_desc* d, const void* src0, const void* src1, const void* w_bf16, void* out, void* out1,
+                          float* stats, const float* in_scale, const float* in_shift, const dt_bn_bwd_fuse* fuse) {
+  ConvBfArgs a;
+  a.bnb = fuse ? *fuse : dt_bn_bwd_fuse{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  a.out1 = (__bf16*)out1; a.stats = stats; a.cout_split = d->cout_split; a.accumulate = d->accumulate;
+  a.src0 = (const __bf16*)src0; a.src1 = (const __bf16*)src1; a.w = (const __bf16*)w_bf16;
+  a.in_scale = in_scale; a.in_shift = in_shift; a.out = (__bf16*)out;
+  a.B = d->B; a.Hin = d->Hin; a.Win = d->Win; a.C0 = d->C0; a.C1 = d->C1; a.mode0 = d->mode0;
+  a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.pad = d->pad;
+  return a;
 }
 
 static int conv2d_bf16_impl(const dt_conv_desc* d, const void* src0, const void* src1, const void* w_bf16, void* out,
@@ -493,28 +507,21 @@ static int conv2d_bf16_impl(const dt_conv_desc* d, const void* src0, const void*
   DT_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "conv_bf16: in_scale/in_shift must come together");
   DT_REQUIRE(in_scale == nullptr || d->C0 <= BF_TF_MAXC, "conv_bf16: input transform needs C0 <= %d", BF_TF_MAXC);
   DT_REQUIRE(d->cout_split == 0 || out1, "conv_bf16: out1 missing");
-  int tw, tn, ck, mt;
-  bf_cfg(d, &tw, &tn, &ck, &mt);
-  ConvBfArgs a;
-  a.bnb = fuse ? *fuse : dt_bn_bwd_fuse{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  a.out1 = (__bf16*)out1; a.stats = stats; a.cout_split = d->cout_split; a.accumulate = d->accumulate;
-  a.src0 = (const __bf16*)src0; a.src1 = (const __bf16*)src1; a.w = (const __bf16*)w_bf16;
-  a.in_scale = in_scale; a.in_shift = in_shift; a.out = (__bf16*)out;
-  a.B = d->B; a.Hin = d->Hin; a.Win = d->Win; a.C0 = d->C0; a.C1 = d->C1; a.mode0 = d->mode0;
-  a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.pad = d->pad;
-  a.tiles_x = dt_cdiv(d->Wo, tw); a.tiles_y = dt_cdiv(d->Ho, 128 * mt / tw); a.n_tiles = dt_cdiv(d->Cout, tn);
-  a.P = d->B * a.tiles_x * a.tiles_y;
+  const BfPlan p = bf_plan(d);
+  ConvBfArgs a = bf_args(d, src0, src1, w_bf16, out, out1, stats, in_scale, in_shift, fuse);
   hipStream_t st = (hipStream_t)stream;
-  if (mt == 8) return dt_conv_bf16_dma_launch(a, st);
-  if (mt == 16) return dt_conv_bf16_narrow_launch(d, a, st);   // (accumulate == 0 there: no stored-activation joins)
-  if (d->ksize == 4) {
+  if (p.family == BF_DMA) return dt_conv_bf16_dma_launch(a, st);
+  if (p.family == BF_NARROW) return dt_conv_bf16_narrow_launch(d, a, st);   // (accumulate == 0 there: no stored-activation joins)
+  a.tiles_x = dt_cdiv(d->Wo, p.tw); a.tiles_y = dt_cdiv(d->Ho, 128 * p.mt / p.tw); a.n_tiles = dt_cdiv(d->Cout, p.tn);
+  a.P = p.rows;
+  if (p.family == BF_STEM) {
     DT_REQUIRE(in_scale == nullptr && fuse == nullptr, "conv_bf16: the stem takes no input transform / fused reduction");
     return bf_launch<4, 1, 32, 64, 16, 2>(a, st);
   }
-  if (d->ksize == 3 && d->stride == 1) return bf_dispatch<3, 1>(a, tw, tn, ck, mt, st);
-  if (d->ksize == 3 && d->stride == 2) return bf_dispatch<3, 2>(a, tw, tn, ck, mt, st);
-  if (d->ksize == 1 && d->stride == 1) return bf_dispatch<1, 1>(a, tw, tn, ck, mt, st);
-  return bf_dispatch<1, 2>(a, tw, tn, ck, mt, st);
+  if (d->ksize == 3 && d->stride == 1) return bf_dispatch<3, 1>(a, p.tw, p.tn, p.ck, p.mt, st);
+  if (d->ksize == 3 && d->stride == 2) return bf_dispatch<3, 2>(a, p.tw, p.tn, p.ck, p.mt, st);
+  if (d->ksize == 1 && d->stride == 1) return bf_dispatch<1, 1>(a, p.tw, p.tn, p.ck, p.mt, st);
+  return bf_dispatch<1, 2>(a, p.tw, p.tn, p.ck, p.mt, st);
 }
 
 extern "C" int dt_conv2d_bf16(const dt_conv_desc* d, const void* src0, const void* src1, const void* w_bf16,
@@ -550,14 +557,8 @@ extern "C" int dt_conv2d_bf16_upsampled_dgrad(const dt_conv_desc* d, const void*
   DT_REQUIRE(d && dy && w_bf16 && gx && red && fuse && fuse->y && fuse->mean && fuse->invstd && fuse->act_scale &&
                  fuse->act_shift && fuse->act == nullptr, "conv_bf16_upsampled_dgrad: null pointer / stored activation");
   DT_REQUIRE(dt_conv2d_bf16_upsampled_dgrad_supported(d), "conv_bf16_upsampled_dgrad: layer shape not supported");
-  ConvBfArgs a;
-  a.bnb = *fuse;
-  a.out1 = nullptr; a.stats = red; a.cout_split = 0; a.accumulate = 0;
-  a.src0 = (const __bf16*)dy; a.src1 = nullptr; a.w = (const __bf16*)w_bf16;
-  a.in_scale = nullptr; a.in_shift = nullptr; a.out = (__bf16*)gx;
-  a.B = d->B; a.Hin = d->Hin; a.Win = d->Win; a.C0 = d->C0; a.C1 = 0; a.mode0 = 0;
-  a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.pad = d->pad;
-  a.n_tiles = 1;
+  // (a supported descriptor has C1 == 0, mode0 == 0, no split and no join)
+  const ConvBfArgs a = bf_args(d, dy, nullptr, w_bf16, gx, nullptr, red, nullptr, nullptr, fuse);
   return dt_conv_bf16_narrow_launch(d, a, (hipStream_t)stream, true);
 }
 
@@ -1170,25 +1171,6 @@ __global__ __launch_bounds__(256, (KS == 3 && STRIDE == 2) ? 1 : 2) void conv_wg
   }
 }
 
-static int wb_cfg(const dt_conv_desc* d, int* tw, int* ksplit, int* T, int* cib, int* cob) {
-  const int Cin = d->C0 + d->C1;
-  *tw = d->Wo > 16 ? 32 : 16;
-  const bool stem = d->ksize == 4;
-  const int blk = ((Cin <= 32 && d->Cout <= 32 && d->ksize == 3 && d->stride == 1) || stem) ? 32 : 64;
-  *cib = dt_cdiv(Cin, blk);
-  *cob = dt_cdiv(d->Cout, blk);
-  const int th = 128 / *tw;
-  *T = d->B * dt_cdiv(d->Ho, th) * dt_cdiv(d->Wo, *tw);
-  int ks = 512 / (*cib * *cob * (stem ? 2 : 1));
-  if (ks < 1) ks = 1;
-  if (ks > *T) ks = *T;
-  *ksplit = ks;
-  return DT_OK;
-}
-
-// DT_BF16_WGRAD_DMA=0 keeps every layer on the register-staged kernel below (A/B switch; read once)
-static bool wb_use_dma() { return dt_env_on("DT_BF16_WGRAD_DMA"); }
-
 static int wb_validate(const dt_conv_desc* d) {
   DT_TRY(dt_conv_validate_null(d, "wgrad_bf16"));
   if (d->ksize == 4) {   // the space-to-depth stem (see dt_stem_s2d_bf16)
@@ -1204,21 +1186,57 @@ static int wb_validate(const dt_conv_desc* d) {
   return dt_conv_validate_out(d, "wgrad_bf16");
 }
 
+// The one place that decides which kernel family computes a weight gradient.  tw .. co_blocks describe the register-staged
+// launch (the other two families keep their geometry in their own files); bytes = the split-K slabs the family writes.
+enum WbFamily { WB_NARROW, WB_DMA, WB_TILED };
+struct WbPlan {
+  WbFamily family;
+  int tw, ksplit, T, ci_blocks, co_blocks;
+  size_t bytes;
+};
+
+// elements of the weight tensor: a multiple of 4 for every descriptor wb_validate lets through (Cin * Cout % 64 == 0;
+// stem: 16 * 16 * Cout), which the float4 quads of wgrad_bf16_final_kernel rely on
+static int64_t wb_elems(const dt_conv_desc* d) { return (int64_t)d->ksize * d->ksize * (d->C0 + d->C1) * d->Cout; }
+
+static WbPlan wb_tiled_plan(const dt_conv_desc* d) {
+  WbPlan p;
+  p.family = WB_TILED;
+  const int Cin = d->C0 + d->C1;
+  p.tw = d->Wo > 16 ? 32 : 16;
+  const bool stem = d->ksize == 4;
+  const int blk = ((Cin <= 32 && d->Cout <= 32 && d->ksize == 3 && d->stride == 1) || stem) ? 32 : 64;
+  p.ci_blocks = dt_cdiv(Cin, blk);
+  p.co_blocks = dt_cdiv(d->Cout, blk);
+  p.T = d->B * dt_cdiv(d->Ho, 128 / p.tw) * dt_cdiv(d->Wo, p.tw);
+  p.ksplit = 512 / (p.ci_blocks * p.co_blocks * (stem ? 2 : 1));
+  if (p.ksplit < 1) p.ksplit = 1;
+  if (p.ksplit > p.T) p.ksplit = p.T;
+  p.bytes = (size_t)p.ksplit * wb_elems(d) * sizeof(float);
+  return p;
+}
+
+// The rule: the lean persistent kernel where its shape conditions hold (conv_bf16_narrow.hip), then the LDS-DMA kernel
+// (conv_bf16_wgrad_dma.hip) — a DMA cannot transform, so only for a stored input, and only with DT_BF16_WGRAD_DMA on (A/B
+// switch; read once) —, else the register-staged tiles
+static WbPlan wb_plan(const dt_conv_desc* d, bool has_input_transform) {
+  WbPlan p = wb_tiled_plan(d);
+  if (dt_wgrad_bf16_narrow_supported(d)) {
+    p.family = WB_NARROW;
+    p.bytes = dt_wgrad_bf16_narrow_workspace(d);
+  } else if (!has_input_transform && dt_env_on("DT_BF16_WGRAD_DMA") && dt_wgrad_bf16_dma_supported(d)) {
+    p.family = WB_DMA;
+    p.bytes = dt_wgrad_bf16_dma_workspace(d);
+  }
+  return p;
+}
+
 extern "C" size_t dt_conv2d_wgrad_bf16_workspace(const dt_conv_desc* d) {
   if (wb_validate(d) != DT_OK) return 0;
-  int tw, ks, T, cib, cob;
-  wb_cfg(d, &tw, &ks, &T, &cib, &cob);
-  const size_t E = (size_t)d->ksize * d->ksize * (d->C0 + d->C1) * d->Cout;
-  size_t need = (size_t)ks * E * sizeof(float);
-  if (dt_wgrad_bf16_narrow_supported(d)) {
-    const size_t n3 = dt_wgrad_bf16_narrow_workspace(d);
-    if (n3 > need) need = n3;
-  }
-  if (wb_use_dma() && dt_wgrad_bf16_dma_supported(d)) {   // the larger of the two: in_scale decides the kernel at launch
-    const size_t n2 = dt_wgrad_bf16_dma_workspace(d);
-    if (n2 > need) need = n2;
-  }
-  return need;
+  // in_scale is not known here and decides between LDS-DMA and tiled at launch: the larger of the two.  The tiled need
+  // also stays in the maximum for a narrow layer, which never runs tiled: the sizes callers have recorded include it.
+  const size_t tiled = wb_tiled_plan(d).bytes, planned = wb_plan(d, false).bytes;
+  return tiled > planned ? tiled : planned;
 }
 
 // dw[e] = sum_p ws[p][e] in ONE launch whatever the number of split-K slabs: a workgroup owns 64 consecutive elements
@@ -1274,57 +1292,51 @@ static int wb_launch(const WgradBfArgs& a, int grid, hipStream_t st) {
   return DT_OK;
 }
 
+// the register-staged tiles -> number of split-K slabs written to `ws`, or a negative code
+static int wb_tiled_launch(const dt_conv_desc* d, const WbPlan& p, const void* src0, const void* src1, const void* dy,
+                           float* ws, const float* in_scale, const float* in_shift, hipStream_t st) {
+  WgradBfArgs a;
+  a.ksplit = p.ksplit; a.T = p.T; a.ci_blocks = p.ci_blocks; a.co_blocks = p.co_blocks;
+  a.src0 = (const __bf16*)src0; a.src1 = (const __bf16*)src1; a.dy = (const __bf16*)dy; a.ws = ws;
+  a.in_scale = in_scale; a.in_shift = in_shift;
+  a.B = d->B; a.Hin = d->Hin; a.Win = d->Win; a.C0 = d->C0; a.C1 = d->C1; a.mode0 = d->mode0;
+  a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.pad = d->pad;
+  a.tiles_x = dt_cdiv(d->Wo, p.tw); a.tiles_y = dt_cdiv(d->Ho, 128 / p.tw);
+  const int grid = a.ci_blocks * a.co_blocks * a.ksplit * (d->ksize == 4 ? 2 : 1);
+  const bool w32 = p.tw == 32;
+  int rc = DT_OK;
+  if (d->ksize == 4) {
+    DT_REQUIRE(in_scale == nullptr, "wgrad_bf16: the stem takes no input transform");
+    hipLaunchKernelGGL((conv_wgrad_bf16_kernel<4, 1, 32, false, 32>), dim3(grid), dim3(256), 0, st, a);
+    DT_LAUNCH_CHECK();
+  } else if (d->ksize == 3 && d->stride == 1) rc = w32 ? wb_launch<3, 1, 32>(a, grid, st) : wb_launch<3, 1, 16>(a, grid, st);
+  else if (d->ksize == 3) rc = w32 ? wb_launch<3, 2, 32>(a, grid, st) : wb_launch<3, 2, 16>(a, grid, st);
+  else if (d->stride == 2) rc = w32 ? wb_launch<1, 2, 32>(a, grid, st) : wb_launch<1, 2, 16>(a, grid, st);
+  else rc = w32 ? wb_launch<1, 1, 32>(a, grid, st) : wb_launch<1, 1, 16>(a, grid, st);   // ResUnet identity_conv
+  if (rc != DT_OK) return rc;
+  return p.ksplit;
+}
+
+static int wb_finalize(const float* ws, float* dw, int parts, int64_t E, hipStream_t st) {
+  hipLaunchKernelGGL(wgrad_bf16_final_kernel, dim3((unsigned)((E / 4 + 15) / 16)), dim3(256), 0, st, ws, dw, parts, E);
+  DT_LAUNCH_CHECK();
+  return DT_OK;
+}
+
 extern "C" int dt_conv2d_wgrad_bf16(const dt_conv_desc* d, const void* src0, const void* src1, const void* dy,
                                     float* dw_hwio, float* workspace, size_t workspace_bytes, const float* in_scale,
                                     const float* in_shift, void* stream) {
-  int rc = wb_validate(d);
-  if (rc != DT_OK) return rc;
+  DT_TRY(wb_validate(d));
   DT_REQUIRE(src0 && dy && dw_hwio && workspace, "wgrad_bf16: null pointer");
   DT_REQUIRE(d->C1 == 0 || src1, "wgrad_bf16: src1 missing");
   DT_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "wgrad_bf16: in_scale/in_shift must come together");
   DT_REQUIRE(workspace_bytes >= dt_conv2d_wgrad_bf16_workspace(d), "wgrad_bf16: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  const int64_t E = (int64_t)d->ksize * d->ksize * (d->C0 + d->C1) * d->Cout;
-  if (dt_wgrad_bf16_narrow_supported(d)) {
-    // Cin, Cout in {16, 32} at full resolution: the lean persistent kernel (conv_bf16_narrow.hip), one slab per workgroup
-    const int parts = dt_wgrad_bf16_narrow_launch(d, src0, dy, workspace, in_scale, in_shift, st);
-    if (parts < 0) return parts;
-    hipLaunchKernelGGL(wgrad_bf16_final_kernel, dim3((unsigned)((E / 4 + 15) / 16)), dim3(256), 0, st, workspace, dw_hwio,
-                       parts, E);
-    DT_LAUNCH_CHECK();
-    return DT_OK;
-  }
-  if (in_scale == nullptr && wb_use_dma() && dt_wgrad_bf16_dma_supported(d)) {
-    // 3x3 stride-1 layers with 64-channel blocks and a stored (untransformed) input: the LDS-DMA persistent kernel
-    const int parts = dt_wgrad_bf16_dma_launch(d, src0, src1, dy, workspace, st);
-    if (parts < 0) return parts;
-    hipLaunchKernelGGL(wgrad_bf16_final_kernel, dim3((unsigned)((E / 4 + 15) / 16)), dim3(256), 0, st, workspace, dw_hwio,
-                       parts, E);
-    DT_LAUNCH_CHECK();
-    return DT_OK;
-  }
-  WgradBfArgs a;
-  int tw;
-  wb_cfg(d, &tw, &a.ksplit, &a.T, &a.ci_blocks, &a.co_blocks);
-  a.src0 = (const __bf16*)src0; a.src1 = (const __bf16*)src1; a.dy = (const __bf16*)dy; a.ws = workspace;
-  a.in_scale = in_scale; a.in_shift = in_shift;
-  a.B = d->B; a.Hin = d->Hin; a.Win = d->Win; a.C0 = d->C0; a.C1 = d->C1; a.mode0 = d->mode0;
-  a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.pad = d->pad;
-  a.tiles_x = dt_cdiv(d->Wo, tw); a.tiles_y = dt_cdiv(d->Ho, 128 / tw);
-  const int grid = a.ci_blocks * a.co_blocks * a.ksplit * (d->ksize == 4 ? 2 : 1);
-  if (d->ksize == 4) {
-    DT_REQUIRE(in_scale == nullptr, "wgrad_bf16: the stem takes no input transform");
-    hipLaunchKernelGGL((conv_wgrad_bf16_kernel<4, 1, 32, false, 32>), dim3(grid), dim3(256), 0, st, a);
-    DT_LAUNCH_CHECK();
-    rc = DT_OK;
-  } else if (d->ksize == 3 && d->stride == 1) rc = tw == 32 ? wb_launch<3, 1, 32>(a, grid, st) : wb_launch<3, 1, 16>(a, grid, st);
-  else if (d->ksize == 3) rc = tw == 32 ? wb_launch<3, 2, 32>(a, grid, st) : wb_launch<3, 2, 16>(a, grid, st);
-  else if (d->stride == 2) rc = tw == 32 ? wb_launch<1, 2, 32>(a, grid, st) : wb_launch<1, 2, 16>(a, grid, st);
-  else rc = tw == 32 ? wb_launch<1, 1, 32>(a, grid, st) : wb_launch<1, 1, 16>(a, grid, st);   // ResUnet identity_conv
-  if (rc != DT_OK) return rc;
-  DT_REQUIRE((E & 3) == 0, "wgrad_bf16: weight tensor size must be a multiple of 4");
-  const int64_t g = (E / 4 + 15) / 16;
-  hipLaunchKernelGGL(wgrad_bf16_final_kernel, dim3((unsigned)g), dim3(256), 0, st, workspace, dw_hwio, a.ksplit, E);
-  DT_LAUNCH_CHECK();
-  return DT_OK;
+  const WbPlan p = wb_plan(d, in_scale != nullptr);
+  int parts;   // split-K slabs in the workspace, or a negative code
+  if (p.family == WB_NARROW) parts = dt_wgrad_bf16_narrow_launch(d, src0, dy, workspace, in_scale, in_shift, st);
+  else if (p.family == WB_DMA) parts = dt_wgrad_bf16_dma_launch(d, src0, src1, dy, workspace, st);
+  else parts = wb_tiled_launch(d, p, src0, src1, dy, workspace, in_scale, in_shift, st);
+  if (parts < 0) return parts;
+  return wb_finalize(workspace, dw_hwio, parts, wb_elems(d), st);
 }

@@ -326,14 +326,17 @@ __global__ __launch_bounds__(256, (CB == 2 && NB == 2) ? 2 : (CB == 1 && NB == 1
 // ---------------------------------------------------------------- host side
 static bool nr_enabled() { return dt_env_on("DT_BF16_NARROW"); }
 
-int dt_conv_bf16_narrow_supported(const dt_conv_desc* d) {
-  if (!nr_enabled() || d == nullptr) return 0;
-  if (d->ksize != 3 || d->stride != 1 || d->pad != 1 || d->C1 != 0 || d->cout_split != 0 || d->accumulate != 0) return 0;
-  if ((d->C0 != 16 && d->C0 != 32) || (d->Cout != 16 && d->Cout != 32)) return 0;
-  if (d->mode0 != 0 && d->mode0 != 1) return 0;
-  if (d->Ho != d->Hin || d->Wo != d->Win || d->Wo < 32 || d->Ho < 8) return 0;
-  return 1;
+// the layer shapes both narrow kernels (forward and weight gradient) take: 3x3 / stride 1 / pad 1, Cin, Cout in {16, 32},
+// one plain or up-sampled source, a same-size map of at least one 8 x 32 tile
+static bool nr_shape(const dt_conv_desc* d) {
+  if (!nr_enabled() || d == nullptr) return false;
+  if (d->ksize != 3 || d->stride != 1 || d->pad != 1 || d->C1 != 0) return false;
+  if ((d->C0 != 16 && d->C0 != 32) || (d->Cout != 16 && d->Cout != 32)) return false;
+  if (d->mode0 != 0 && d->mode0 != 1) return false;
+  return d->Ho == d->Hin && d->Wo == d->Win && d->Wo >= 32 && d->Ho >= 8;
 }
+
+int dt_conv_bf16_narrow_supported(const dt_conv_desc* d) { return nr_shape(d) && d->cout_split == 0 && d->accumulate == 0; }
 
 static int nr_tiles(const dt_conv_desc* d) { return d->B * dt_cdiv(d->Ho, NR_TH) * dt_cdiv(d->Wo, NR_TW); }
 
@@ -578,14 +581,7 @@ __global__ __launch_bounds__(256, (CB == 2 && NB == 2) ? 2 : 3) void conv3x3_wgr
   }
 }
 
-int dt_wgrad_bf16_narrow_supported(const dt_conv_desc* d) {
-  if (!nr_enabled() || d == nullptr) return 0;
-  if (d->ksize != 3 || d->stride != 1 || d->pad != 1 || d->C1 != 0) return 0;
-  if ((d->C0 != 16 && d->C0 != 32) || (d->Cout != 16 && d->Cout != 32)) return 0;
-  if (d->mode0 != 0 && d->mode0 != 1) return 0;
-  if (d->Ho != d->Hin || d->Wo != d->Win || d->Wo < 32 || d->Ho < 8) return 0;
-  return 1;
-}
+int dt_wgrad_bf16_narrow_supported(const dt_conv_desc* d) { return nr_shape(d); }
 
 size_t dt_wgrad_bf16_narrow_workspace(const dt_conv_desc* d) {
   return (size_t)dt_persist_rows(nr_tiles(d)) * 9 * d->C0 * d->Cout * sizeof(float);

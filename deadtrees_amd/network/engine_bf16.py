@@ -10,6 +10,7 @@ from typing import Optional
 
 import torch
 
+from .. import _lib
 from .bnview import BnView
 from .engine_core import _Saved, _pair
 from .spec import ConvSpec
@@ -17,37 +18,30 @@ from .spec import ConvSpec
 _BF = torch.bfloat16
 
 
+def _conv_kernel_name(desc, cfg, tf=False, bnb=False) -> str:
+    """the kernel dt_conv2d_bf16 / dt_conv2d_bf16_bn_bwd launches for `desc`, as the profile names it; cfg = its
+    _lib.bf16_config, tf: with an input transform, bnb: with the fused BatchNorm-backward sums"""
+    tw, tn, ck, mt = cfg
+    t = {False: "false", True: "true"}
+    if mt == _lib.BF16_MT_DMA:      # conv_bf16_dma.hip; epilogue: 1 = fused sums, 2 = gradient join, 3 = both
+        return f"conv3x3_bf16_dma_kernel<{t[tf]}, {int(bnb) + (2 if desc.accumulate else 0)}>"
+    if mt == _lib.BF16_MT_NARROW:   # conv_bf16_narrow.hip
+        return f"conv3x3_bf16_narrow_kernel<{desc.C0 // 16}, {desc.Cout // 16}, {t[tf]}, {t[bnb]}>"
+    if bnb:
+        return "conv_fwd_bf16_kernel (data gradient + BatchNorm-backward sums)"
+    return f"conv_fwd_bf16_kernel<{desc.ksize}, {desc.stride}, {tw}, {tn}, {ck}, {mt}, {t[tf]}>"
+
+
 class Bf16Schedule:
     # ------------------------------------------------------------------ convolution launches
-    def _bf16_mt(self, desc) -> int:
-        """kernel family dt_conv2d_bf16 picks for `desc`: 8 = LDS-DMA staged (conv_bf16_dma.hip), 16 = lean narrow-layer
-        kernel (conv_bf16_narrow.hip), else the register-staged kernels' tile multiplier"""
-        tw, tn, ck, mt = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-        if self.lib.dt_conv2d_bf16_config(C.byref(desc), C.byref(tw), C.byref(tn), C.byref(ck), C.byref(mt)) != 0:
-            return -1
-        return mt.value
-
-    def _uses_dma_kernel(self, desc) -> bool:
-        """the LDS-DMA staged kernels (reported as mt == 8) read the CHUNKED weight images"""
-        return self._bf16_mt(desc) == 8
-
     def _conv_bf16(self, desc, src0, src1, w, out0, out1, stats, in_ss, w_chunked=None):
-        if w_chunked is not None and self._uses_dma_kernel(desc):
+        cfg = _lib.bf16_config(desc) if w_chunked is not None else None
+        if cfg is not None and cfg[3] == _lib.BF16_MT_DMA:      # the LDS-DMA staged kernels read the CHUNKED weight images
             w = w_chunked
         e0 = self._pb()
         self._call("dt_conv2d_bf16", desc, src0, src1, w, out0, out1, stats, *_pair(in_ss))
         if e0 is not None:
-            tw, tn, ck, mt = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-            self.lib.dt_conv2d_bf16_config(C.byref(desc), C.byref(tw), C.byref(tn), C.byref(ck), C.byref(mt))
-            if mt.value == 8:     # the LDS-DMA staged 512-pixel kernel (conv_bf16_dma.hip)
-                name = f"conv3x3_bf16_dma_kernel<{'true' if in_ss else 'false'}, {2 if desc.accumulate else 0}>"
-            elif mt.value == 16:  # the lean narrow-layer kernel (conv_bf16_narrow.hip)
-                name = (f"conv3x3_bf16_narrow_kernel<{desc.C0 // 16}, {desc.Cout // 16}, "
-                        f"{'true' if in_ss else 'false'}, false>")
-            else:
-                name = (f"conv_fwd_bf16_kernel<{desc.ksize}, {desc.stride}, {tw.value}, {tn.value}, {ck.value}, "
-                        f"{mt.value}, {'true' if in_ss else 'false'}>")
-            self._pe(e0, name, *self._conv_work(desc, 2))
+            self._pe(e0, _conv_kernel_name(desc, cfg or _lib.bf16_config(desc), tf=bool(in_ss)), *self._conv_work(desc, 2))
 
     def _stem_bf16(self, x, params, y, stats, B, H, W, Cin):
         """7x7/2 stem of the bf16 path into `y` (bf16) with optional BatchNorm partial statistics -> (stat rows P, the
@@ -231,15 +225,12 @@ class Bf16Schedule:
         P = self.lib.dt_conv2d_bf16_stat_rows(C.byref(desc))
         red = self._buf("bn_red_fused", self.lib.dt_bn_stats_floats(P, Cq), device=dy.device)
         fuse = bn.fuse(bn_conv, y, act)
-        dma = self._uses_dma_kernel(desc)
+        cfg = _lib.bf16_config(desc)
+        dma = cfg is not None and cfg[3] == _lib.BF16_MT_DMA
         e0 = self._pb()
         self._call("dt_conv2d_bf16_bn_bwd", desc, dy, c.w(self._wbd[1] if dma else self._wbd[0]), out0, red, fuse)
         if e0 is not None:
-            narrow = self._bf16_mt(desc) == 16
-            self._pe(e0, f"conv3x3_bf16_dma_kernel<false, {1 if act is None else 3}>" if dma else
-                     (f"conv3x3_bf16_narrow_kernel<{desc.C0 // 16}, {desc.Cout // 16}, false, true>" if narrow else
-                      "conv_fwd_bf16_kernel (data gradient + BatchNorm-backward sums)"),
-                     *self._conv_work(desc, 2, 2.0 * out0.numel()))
+            self._pe(e0, _conv_kernel_name(desc, cfg, bnb=True), *self._conv_work(desc, 2, 2.0 * out0.numel()))
         return red, P
 
     def _dgrad_bf16(self, c: ConvSpec, dy, B, Hin, Win, out0, out1=None, split=0, acc=False):

@@ -27,35 +27,70 @@ def conv_desc(B, Hin, Win, C0, C1, mode0, Cout, k, stride, pad, split=0, acc=0):
     return _lib.ConvDesc(B, Hin, Win, C0, C1, mode0, Ho, Wo, Cout, k, stride, pad, split, acc)
 
 
+# ---- what the convolution wrappers of the three families (fp32 direct, Winograd, bf16) share
+def _src_desc(src0, src1, mode0, Cout, k, stride, pad, split=0, accumulate=False):
+    """descriptor of a convolution over the virtual input (src0 up-sampled x2 / zero-inserted for mode0 1 / 2) | src1"""
+    B, H, W, C0 = src0.shape
+    if mode0 != 0:
+        H, W = 2 * H, 2 * W
+    C1 = 0 if src1 is None else src1.shape[-1]
+    return conv_desc(B, H, W, C0, C1, mode0, Cout, k, stride, pad, split, 1 if accumulate else 0)
+
+
+def _split_outputs(d, split, out0, out1, dtype, device):
+    """the outputs the caller did not bring: out0 (the first `split` channels, or all), out1 (the rest of a split)"""
+    if out0 is None:
+        out0 = torch.empty((d.B, d.Ho, d.Wo, split if split else d.Cout), dtype=dtype, device=device)
+    if split and out1 is None:
+        out1 = torch.empty((d.B, d.Ho, d.Wo, d.Cout - split), dtype=dtype, device=device)
+    return out0, out1
+
+
+def _rows_buffer(P, Cc, device):
+    """BatchNorm partial-sum buffer (statistics or `red`) for the answer P of a rows query -> (the buffer the ABI takes,
+    its [2, P, Cc] view); a refused query (P <= 0) raises the library's message"""
+    lib = _lib.load()
+    if P <= 0:
+        raise RuntimeError(lib.dt_last_error().decode())
+    buf = torch.empty(lib.dt_bn_stats_floats(P, Cc), dtype=torch.float32, device=device)
+    return buf, buf[:2 * P * Cc].view(2, P, Cc)
+
+
+def _wgrad(entry, d, src0, src1, dy, dw, in_scale=None, in_shift=None, what=None):
+    """weight gradient `entry` (the entry points share one signature) into dw, on a workspace of `<entry>_workspace`
+    bytes; a refused workspace query (0) raises the library's message"""
+    lib = _lib.load()
+    nbytes = getattr(lib, entry + "_workspace")(C.byref(d))
+    if nbytes <= 0:
+        raise RuntimeError(lib.dt_last_error().decode())
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dy.device)
+    _lib.check(getattr(lib, entry)(C.byref(d), _p(src0), _p(src1), _p(dy.contiguous()), _p(dw), _p(ws), nbytes,
+                                   _p(in_scale), _p(in_shift), _st()), what or entry)
+    return dw
+
+
+def _bn_bwd_setup(rows_query, src0, Cout, dtype, y, mean, invstd, act_scale, act_shift, act, join_into):
+    """what the *_bn_bwd wrappers prepare: descriptor of the plain 3x3 data gradient (a join when join_into is given),
+    output, `red` buffer and its view, fuse block"""
+    B, H, W, C0 = src0.shape
+    d = conv_desc(B, H, W, C0, 0, 0, Cout, 3, 1, 1, 0, 1 if join_into is not None else 0)
+    red, red_view = _rows_buffer(rows_query(C.byref(d)), Cout, src0.device)
+    out = join_into if join_into is not None else torch.empty((B, H, W, Cout), dtype=dtype, device=src0.device)
+    fuse = _lib.BnBwdFuse(_p(y.contiguous()), _p(mean), _p(invstd), _p(act_scale), _p(act_shift), _p(act))
+    return d, out, red, red_view, fuse
+
+
 def conv2d(src0, w_hwio, k, stride, pad, src1=None, mode0=0, split=0, out0=None, out1=None, accumulate=False,
            want_stats=False, in_scale=None, in_shift=None):
     """NHWC conv through dt_conv2d.  Returns (out0, out1, stats[2,P,Cout] or None)."""
     _gpu(src0, src1, w_hwio)
     lib = _lib.load()
-    B = src0.shape[0]
-    C0 = src0.shape[-1]
-    C1 = 0 if src1 is None else src1.shape[-1]
-    if mode0 == 0:
-        Hin, Win = src0.shape[1], src0.shape[2]
-    else:
-        Hin, Win = 2 * src0.shape[1], 2 * src0.shape[2]
     Cout = w_hwio.shape[-1]
-    d = conv_desc(B, Hin, Win, C0, C1, mode0, Cout, k, stride, pad, split, 1 if accumulate else 0)
-    dev = src0.device
-    if out0 is None:
-        out0 = torch.empty((B, d.Ho, d.Wo, split if split else Cout), dtype=torch.float32, device=dev)
-    if split and out1 is None:
-        out1 = torch.empty((B, d.Ho, d.Wo, Cout - split), dtype=torch.float32, device=dev)
-    stats = None
-    if want_stats:
-        P = lib.dt_conv2d_stat_rows(C.byref(d))
-        if P <= 0:
-            raise RuntimeError(lib.dt_last_error().decode())
-        stats = torch.empty(lib.dt_bn_stats_floats(P, Cout), dtype=torch.float32, device=dev)
-    _lib.check(lib.dt_conv2d(C.byref(d), _p(src0), _p(src1), _p(w_hwio.contiguous()), _p(out0), _p(out1), _p(stats),
+    d = _src_desc(src0, src1, mode0, Cout, k, stride, pad, split, accumulate)
+    out0, out1 = _split_outputs(d, split, out0, out1, torch.float32, src0.device)
+    buf, stats = _rows_buffer(lib.dt_conv2d_stat_rows(C.byref(d)), Cout, src0.device) if want_stats else (None, None)
+    _lib.check(lib.dt_conv2d(C.byref(d), _p(src0), _p(src1), _p(w_hwio.contiguous()), _p(out0), _p(out1), _p(buf),
                              _p(in_scale), _p(in_shift), _st()), "dt_conv2d")
-    if stats is not None:
-        stats = stats[:2 * P * Cout].view(2, P, Cout)
     return out0, out1, stats
 
 
@@ -63,12 +98,8 @@ def conv2d_affine(src0, w_hwio, k, stride, pad, scale, shift, relu=True, src1=No
     """inference form through dt_conv2d_affine: [relu](conv(x) * scale + shift) in one launch (eval-mode BatchNorm folded
     into per-channel scale / shift) -> NHWC activation"""
     _gpu(src0, src1, w_hwio, scale, shift)
-    B, C0 = src0.shape[0], src0.shape[-1]
-    C1 = 0 if src1 is None else src1.shape[-1]
-    Hin, Win = (src0.shape[1], src0.shape[2]) if mode0 == 0 else (2 * src0.shape[1], 2 * src0.shape[2])
-    Cout = w_hwio.shape[-1]
-    d = conv_desc(B, Hin, Win, C0, C1, mode0, Cout, k, stride, pad)
-    out = torch.empty((B, d.Ho, d.Wo, Cout), dtype=torch.float32, device=src0.device)
+    d = _src_desc(src0, src1, mode0, w_hwio.shape[-1], k, stride, pad)
+    out = torch.empty((d.B, d.Ho, d.Wo, d.Cout), dtype=torch.float32, device=src0.device)
     _lib.check(_lib.load().dt_conv2d_affine(C.byref(d), _p(src0), _p(src1), _p(w_hwio.contiguous()), _p(out), _p(scale),
                                             _p(shift), 1 if relu else 0, _st()), "dt_conv2d_affine")
     return out
@@ -77,20 +108,11 @@ def conv2d_affine(src0, w_hwio, k, stride, pad, scale, shift, relu=True, src1=No
 def conv2d_wgrad_winograd(src0, dy, src1=None, mode0=0, in_scale=None, in_shift=None):
     """3x3 stride-1 pad-1 weight gradient through dt_conv2d_wgrad_winograd -> dw HWIO"""
     _gpu(src0, src1, dy)
-    lib = _lib.load()
-    B, C0 = src0.shape[0], src0.shape[-1]
-    C1 = 0 if src1 is None else src1.shape[-1]
-    Hin, Win = (src0.shape[1], src0.shape[2]) if mode0 == 0 else (2 * src0.shape[1], 2 * src0.shape[2])
-    Cout = dy.shape[-1]
-    d = conv_desc(B, Hin, Win, C0, C1, mode0, Cout, 3, 1, 1)
-    if not lib.dt_conv2d_wgrad_winograd_supported(C.byref(d)):
+    d = _src_desc(src0, src1, mode0, dy.shape[-1], 3, 1, 1)
+    if not _lib.load().dt_conv2d_wgrad_winograd_supported(C.byref(d)):
         raise ValueError("layer shape not supported by the Winograd weight-gradient kernel")
-    nbytes = lib.dt_conv2d_wgrad_winograd_workspace(C.byref(d))
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dy.device)
-    dw = torch.empty((3, 3, C0 + C1, Cout), dtype=torch.float32, device=dy.device)
-    _lib.check(lib.dt_conv2d_wgrad_winograd(C.byref(d), _p(src0), _p(src1), _p(dy.contiguous()), _p(dw), _p(ws), nbytes,
-                                            _p(in_scale), _p(in_shift), _st()), "dt_conv2d_wgrad_winograd")
-    return dw
+    dw = torch.empty((3, 3, d.C0 + d.C1, d.Cout), dtype=torch.float32, device=dy.device)
+    return _wgrad("dt_conv2d_wgrad_winograd", d, src0, src1, dy, dw, in_scale, in_shift)
 
 
 def winograd_weights(w_hwio):
@@ -108,26 +130,14 @@ def conv2d_winograd(src0, u, src1=None, mode0=0, split=0, out0=None, out1=None, 
     """3x3 stride-1 pad-1 NHWC conv through dt_conv2d_winograd.  Returns (out0, out1, stats[2,P,Cout] or None)."""
     _gpu(src0, src1, u)
     lib = _lib.load()
-    B, C0 = src0.shape[0], src0.shape[-1]
-    C1 = 0 if src1 is None else src1.shape[-1]
-    Hin, Win = (src0.shape[1], src0.shape[2]) if mode0 == 0 else (2 * src0.shape[1], 2 * src0.shape[2])
     Cout = u.shape[3]
-    d = conv_desc(B, Hin, Win, C0, C1, mode0, Cout, 3, 1, 1, split, 1 if accumulate else 0)
+    d = _src_desc(src0, src1, mode0, Cout, 3, 1, 1, split, accumulate)
     if not lib.dt_conv2d_winograd_supported(C.byref(d)):
         raise ValueError("layer shape not supported by the Winograd kernel")
-    dev = src0.device
-    if out0 is None:
-        out0 = torch.empty((B, d.Ho, d.Wo, split if split else Cout), dtype=torch.float32, device=dev)
-    if split and out1 is None:
-        out1 = torch.empty((B, d.Ho, d.Wo, Cout - split), dtype=torch.float32, device=dev)
-    stats = None
-    if want_stats:
-        P = lib.dt_conv2d_winograd_stat_rows(C.byref(d))
-        stats = torch.empty(lib.dt_bn_stats_floats(P, Cout), dtype=torch.float32, device=dev)
-    _lib.check(lib.dt_conv2d_winograd(C.byref(d), _p(src0), _p(src1), _p(u), _p(out0), _p(out1), _p(stats),
+    out0, out1 = _split_outputs(d, split, out0, out1, torch.float32, src0.device)
+    buf, stats = _rows_buffer(lib.dt_conv2d_winograd_stat_rows(C.byref(d)), Cout, src0.device) if want_stats else (None, None)
+    _lib.check(lib.dt_conv2d_winograd(C.byref(d), _p(src0), _p(src1), _p(u), _p(out0), _p(out1), _p(buf),
                                       _p(in_scale), _p(in_shift), _st()), "dt_conv2d_winograd")
-    if stats is not None:
-        stats = stats[:2 * P * Cout].view(2, P, Cout)
     return out0, out1, stats
 
 
@@ -142,22 +152,10 @@ def weight_flip_transpose(w_hwio):
 
 def conv2d_wgrad(src0, dy, k, stride, pad, src1=None, mode0=0, in_scale=None, in_shift=None):
     _gpu(src0, src1, dy)
-    lib = _lib.load()
-    B = src0.shape[0]
-    C0 = src0.shape[-1]
-    C1 = 0 if src1 is None else src1.shape[-1]
-    Hin, Win = (src0.shape[1], src0.shape[2]) if mode0 == 0 else (2 * src0.shape[1], 2 * src0.shape[2])
-    Cout = dy.shape[-1]
-    d = conv_desc(B, Hin, Win, C0, C1, mode0, Cout, k, stride, pad)
+    d = _src_desc(src0, src1, mode0, dy.shape[-1], k, stride, pad)
     assert (d.Ho, d.Wo) == (dy.shape[1], dy.shape[2]), ((d.Ho, d.Wo), dy.shape)
-    nbytes = lib.dt_conv2d_wgrad_workspace(C.byref(d))
-    if nbytes == 0:
-        raise RuntimeError(lib.dt_last_error().decode())
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dy.device)
-    dw = torch.empty((k, k, C0 + C1, Cout), dtype=torch.float32, device=dy.device)
-    _lib.check(lib.dt_conv2d_wgrad(C.byref(d), _p(src0), _p(src1), _p(dy.contiguous()), _p(dw), _p(ws), nbytes,
-                                   _p(in_scale), _p(in_shift), _st()), "dt_conv2d_wgrad")
-    return dw
+    dw = torch.empty((k, k, d.C0 + d.C1, d.Cout), dtype=torch.float32, device=dy.device)
+    return _wgrad("dt_conv2d_wgrad", d, src0, src1, dy, dw, in_scale, in_shift)
 
 
 def bn_finalize(stats, count, gamma, beta, running_mean=None, running_var=None, eps=1e-5, momentum=0.1):
@@ -499,36 +497,22 @@ def conv2d_bf16(src0, w_packed, k, stride, pad, cout, src1=None, mode0=0, split=
     """bf16 NHWC conv (fp32 accumulate) through dt_conv2d_bf16; w_packed = [k*k, cout, cin] bf16."""
     _gpu(src0, src1, w_packed)
     lib = _lib.load()
-    B, C0 = src0.shape[0], src0.shape[-1]
-    C1 = 0 if src1 is None else src1.shape[-1]
-    Hin, Win = (src0.shape[1], src0.shape[2]) if mode0 == 0 else (2 * src0.shape[1], 2 * src0.shape[2])
-    d = conv_desc(B, Hin, Win, C0, C1, mode0, cout, k, stride, pad, split, 1 if accumulate else 0)
-    dev, bf = src0.device, torch.bfloat16
-    if out0 is None:
-        out0 = torch.empty((B, d.Ho, d.Wo, split if split else cout), dtype=bf, device=dev)
-    if split and out1 is None:
-        out1 = torch.empty((B, d.Ho, d.Wo, cout - split), dtype=bf, device=dev)
-    stats = None
-    if want_stats:
-        P = lib.dt_conv2d_bf16_stat_rows(C.byref(d))
-        if P <= 0:
-            raise RuntimeError(lib.dt_last_error().decode())
-        stats = torch.empty(lib.dt_bn_stats_floats(P, cout), dtype=torch.float32, device=dev)
-    w_packed = _dma_image(d, w_packed, k, C0 + C1, cout)
-    _lib.check(lib.dt_conv2d_bf16(C.byref(d), _p(src0), _p(src1), _p(w_packed), _p(out0), _p(out1), _p(stats),
+    d = _src_desc(src0, src1, mode0, cout, k, stride, pad, split, accumulate)
+    out0, out1 = _split_outputs(d, split, out0, out1, torch.bfloat16, src0.device)
+    buf, stats = _rows_buffer(lib.dt_conv2d_bf16_stat_rows(C.byref(d)), cout, src0.device) if want_stats else (None, None)
+    w_packed = _dma_image(d, w_packed)
+    _lib.check(lib.dt_conv2d_bf16(C.byref(d), _p(src0), _p(src1), _p(w_packed), _p(out0), _p(out1), _p(buf),
                                   _p(in_scale), _p(in_shift), _st()), "dt_conv2d_bf16")
-    if stats is not None:
-        stats = stats[:2 * P * cout].view(2, P, cout)
     return out0, out1, stats
 
 
-def _dma_image(d, w_packed, k, cin, cout):
-    """the LDS-DMA staged kernels (dt_conv2d_bf16_config reports mt == 8) read the weights in the chunked layout
-    [tap][Cin/32][Cout][32] (dt_weight_images modes 3 / 4); this test-level wrapper re-arranges a [tap][Cout][Cin] image"""
-    tw, tn, ck, mt = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    if _lib.load().dt_conv2d_bf16_config(C.byref(d), C.byref(tw), C.byref(tn), C.byref(ck), C.byref(mt)) != 0 or mt.value != 8:
+def _dma_image(d, w_packed):
+    """the LDS-DMA staged kernels (_lib.BF16_MT_DMA) read the weights in the chunked layout [tap][Cin/32][Cout][32]
+    (dt_weight_images modes 3 / 4); this test-level wrapper re-arranges a [tap][Cout][Cin] image"""
+    cfg = _lib.bf16_config(d)
+    if cfg is None or cfg[3] != _lib.BF16_MT_DMA:
         return w_packed
-    return w_packed.view(k * k, cout, cin // 32, 32).permute(0, 2, 1, 3).contiguous()
+    return w_packed.view(d.ksize * d.ksize, d.Cout, (d.C0 + d.C1) // 32, 32).permute(0, 2, 1, 3).contiguous()
 
 
 def pack_weights_bf16(w_hwio, dgrad=False):
@@ -549,21 +533,10 @@ def pack_weights_bf16(w_hwio, dgrad=False):
 
 def conv2d_wgrad_bf16(src0, dy, k, stride, pad, src1=None, mode0=0, in_scale=None, in_shift=None):
     _gpu(src0, src1, dy)
-    lib = _lib.load()
-    B, C0 = src0.shape[0], src0.shape[-1]
-    C1 = 0 if src1 is None else src1.shape[-1]
-    Hin, Win = (src0.shape[1], src0.shape[2]) if mode0 == 0 else (2 * src0.shape[1], 2 * src0.shape[2])
-    Cout = dy.shape[-1]
-    d = conv_desc(B, Hin, Win, C0, C1, mode0, Cout, k, stride, pad)
+    d = _src_desc(src0, src1, mode0, dy.shape[-1], k, stride, pad)
     assert (d.Ho, d.Wo) == (dy.shape[1], dy.shape[2])
-    nbytes = lib.dt_conv2d_wgrad_bf16_workspace(C.byref(d))
-    if nbytes == 0:
-        raise RuntimeError(lib.dt_last_error().decode())
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dy.device)
-    dw = torch.empty((k, k, C0 + C1, Cout), dtype=torch.float32, device=dy.device)
-    _lib.check(lib.dt_conv2d_wgrad_bf16(C.byref(d), _p(src0), _p(src1), _p(dy.contiguous()), _p(dw), _p(ws), nbytes,
-                                        _p(in_scale), _p(in_shift), _st()), "dt_conv2d_wgrad_bf16")
-    return dw
+    dw = torch.empty((k, k, d.C0 + d.C1, d.Cout), dtype=torch.float32, device=dy.device)
+    return _wgrad("dt_conv2d_wgrad_bf16", d, src0, src1, dy, dw, in_scale, in_shift)
 
 
 def confusion_matrix(pred, target, lu=None, K=2, counts=None):
@@ -600,32 +573,22 @@ def conv2d_bn_bwd(src0, w_hwio, y, mean, invstd, act_scale=None, act_shift=None,
     -> (out [B,H,W,Cout], red [2,P,Cout])"""
     _gpu(src0, w_hwio, y, mean, invstd, act_scale, act_shift, act, join_into)
     lib = _lib.load()
-    B, H, W, C0 = src0.shape
-    Cout = w_hwio.shape[-1]
-    d = conv_desc(B, H, W, C0, 0, 0, Cout, 3, 1, 1, 0, 1 if join_into is not None else 0)
-    P = lib.dt_conv2d_stat_rows(C.byref(d))
-    red = torch.empty(lib.dt_bn_stats_floats(P, Cout), dtype=torch.float32, device=src0.device)
-    out = join_into if join_into is not None else torch.empty((B, H, W, Cout), dtype=torch.float32, device=src0.device)
-    fuse = _lib.BnBwdFuse(_p(y.contiguous()), _p(mean), _p(invstd), _p(act_scale), _p(act_shift), _p(act))
+    d, out, red, red_view, fuse = _bn_bwd_setup(lib.dt_conv2d_stat_rows, src0, w_hwio.shape[-1], torch.float32, y, mean,
+                                                invstd, act_scale, act_shift, act, join_into)
     _lib.check(lib.dt_conv2d_bn_bwd(C.byref(d), _p(src0), _p(w_hwio.contiguous()), _p(out), _p(red), C.byref(fuse),
                                     _st()), "dt_conv2d_bn_bwd")
-    return out, red[:2 * P * Cout].view(2, P, Cout)
+    return out, red_view
 
 
 def conv2d_winograd_bn_bwd(src0, u, y, mean, invstd, act_scale=None, act_shift=None, act=None, join_into=None):
     """Winograd form of conv2d_bn_bwd (u = winograd_weights of the data-gradient HWIO image) -> (out, red [2,P,Cout])"""
     _gpu(src0, u, y, mean, invstd, act_scale, act_shift, act, join_into)
     lib = _lib.load()
-    B, H, W, C0 = src0.shape
-    Cout = u.shape[3]
-    d = conv_desc(B, H, W, C0, 0, 0, Cout, 3, 1, 1, 0, 1 if join_into is not None else 0)
-    P = lib.dt_conv2d_winograd_stat_rows(C.byref(d))
-    red = torch.empty(lib.dt_bn_stats_floats(P, Cout), dtype=torch.float32, device=src0.device)
-    out = join_into if join_into is not None else torch.empty((B, H, W, Cout), dtype=torch.float32, device=src0.device)
-    fuse = _lib.BnBwdFuse(_p(y.contiguous()), _p(mean), _p(invstd), _p(act_scale), _p(act_shift), _p(act))
+    d, out, red, red_view, fuse = _bn_bwd_setup(lib.dt_conv2d_winograd_stat_rows, src0, u.shape[3], torch.float32, y, mean,
+                                                invstd, act_scale, act_shift, act, join_into)
     _lib.check(lib.dt_conv2d_winograd_bn_bwd(C.byref(d), _p(src0), _p(u), _p(out), _p(red), C.byref(fuse), _st()),
                "dt_conv2d_winograd_bn_bwd")
-    return out, red[:2 * P * Cout].view(2, P, Cout)
+    return out, red_view
 
 
 def conv2d_bf16_bn_bwd(src0, w_packed, cout, y, mean, invstd, act_scale=None, act_shift=None, act=None,
@@ -634,17 +597,11 @@ def conv2d_bf16_bn_bwd(src0, w_packed, cout, y, mean, invstd, act_scale=None, ac
     -> (out bf16, red [2,P,Cout])"""
     _gpu(src0, w_packed, y, mean, invstd, act_scale, act_shift, act, join_into)
     lib = _lib.load()
-    B, H, W, C0 = src0.shape
-    d = conv_desc(B, H, W, C0, 0, 0, cout, 3, 1, 1, 0, 1 if join_into is not None else 0)
-    P = lib.dt_conv2d_bf16_stat_rows(C.byref(d))
-    red = torch.empty(lib.dt_bn_stats_floats(P, cout), dtype=torch.float32, device=src0.device)
-    out = join_into if join_into is not None else torch.empty((B, H, W, cout), dtype=torch.bfloat16,
-                                                              device=src0.device)
-    fuse = _lib.BnBwdFuse(_p(y.contiguous()), _p(mean), _p(invstd), _p(act_scale), _p(act_shift), _p(act))
-    w_packed = _dma_image(d, w_packed, 3, C0, cout)
-    _lib.check(lib.dt_conv2d_bf16_bn_bwd(C.byref(d), _p(src0), _p(w_packed), _p(out), _p(red), C.byref(fuse), _st()),
-               "dt_conv2d_bf16_bn_bwd")
-    return out, red[:2 * P * cout].view(2, P, cout)
+    d, out, red, red_view, fuse = _bn_bwd_setup(lib.dt_conv2d_bf16_stat_rows, src0, cout, torch.bfloat16, y, mean, invstd,
+                                                act_scale, act_shift, act, join_into)
+    _lib.check(lib.dt_conv2d_bf16_bn_bwd(C.byref(d), _p(src0), _p(_dma_image(d, w_packed)), _p(out), _p(red), C.byref(fuse),
+                                         _st()), "dt_conv2d_bf16_bn_bwd")
+    return out, red_view
 
 
 def conv2d_bf16_upsampled_dgrad(dy, w_packed_dgrad, cin, y, mean, invstd, act_scale, act_shift):
@@ -657,13 +614,12 @@ def conv2d_bf16_upsampled_dgrad(dy, w_packed_dgrad, cin, y, mean, invstd, act_sc
     d = conv_desc(B, H, W, cout, 0, 0, cin, 3, 1, 1)
     if not lib.dt_conv2d_bf16_upsampled_dgrad_supported(C.byref(d)):
         raise ValueError("conv2d_bf16_upsampled_dgrad: layer shape not covered by the narrow kernel")
-    P = lib.dt_conv2d_bf16_stat_rows(C.byref(d))
-    red = torch.empty(lib.dt_bn_stats_floats(P, cin), dtype=torch.float32, device=dy.device)
+    red, red_view = _rows_buffer(lib.dt_conv2d_bf16_stat_rows(C.byref(d)), cin, dy.device)
     gx = torch.empty((B, H // 2, W // 2, cin), dtype=torch.bfloat16, device=dy.device)
     fuse = _lib.BnBwdFuse(_p(y.contiguous()), _p(mean), _p(invstd), _p(act_scale), _p(act_shift))
     _lib.check(lib.dt_conv2d_bf16_upsampled_dgrad(C.byref(d), _p(dy.contiguous()), _p(w_packed_dgrad), _p(gx), _p(red),
                                                   C.byref(fuse), _st()), "dt_conv2d_bf16_upsampled_dgrad")
-    return gx, red[:2 * P * cin].view(2, P, cin)
+    return gx, red_view
 
 
 def upsample2x_bwd_bn(dup, y, mean, invstd, act_scale, act_shift):
@@ -694,15 +650,14 @@ def conv2d_upsampled_dgrad(dy, w_hwio, cin, y=None, mean=None, invstd=None, act_
     if not lib.dt_conv2d_upsampled_dgrad_supported(C.byref(d)):
         raise ValueError("conv2d_upsampled_dgrad: layer shape not covered by the sub-pixel kernel")
     gx = torch.empty((B, H // 2, W // 2, cin), dtype=torch.float32, device=dy.device)
-    red, fuse, P = None, None, 0
+    red, red_view, fuse = None, None, None
     if y is not None:
         _gpu(y, mean, invstd, act_scale, act_shift)
-        P = lib.dt_conv2d_upsampled_dgrad_rows(C.byref(d))
-        red = torch.empty(lib.dt_bn_stats_floats(P, cin), dtype=torch.float32, device=dy.device)
+        red, red_view = _rows_buffer(lib.dt_conv2d_upsampled_dgrad_rows(C.byref(d)), cin, dy.device)
         fuse = _lib.BnBwdFuse(_p(y.contiguous()), _p(mean), _p(invstd), _p(act_scale), _p(act_shift))
     _lib.check(lib.dt_conv2d_upsampled_dgrad(C.byref(d), _p(dy.contiguous()), _p(w_hwio.contiguous()), _p(gx), _p(red),
                                              C.byref(fuse) if fuse is not None else None, _st()), "dt_conv2d_upsampled_dgrad")
-    return gx, (red[:2 * P * cin].view(2, P, cin) if red is not None else None)
+    return gx, red_view
 
 
 def stem_conv_bf16(x_nhwc_f32, w_hwio_7x7, want_stats=False):
@@ -720,16 +675,9 @@ def stem_conv_bf16(x_nhwc_f32, w_hwio_7x7, want_stats=False):
                "dt_stem_pack_weights_bf16")
     d = _lib.ConvDesc(B, H // 2, W // 2, 16, 0, 0, H // 2, W // 2, Cout, 4, 1, 2, 0, 0)
     out = torch.empty((B, H // 2, W // 2, Cout), dtype=torch.bfloat16, device=x_nhwc_f32.device)
-    stats = None
-    if want_stats:
-        P = lib.dt_conv2d_bf16_stat_rows(C.byref(d))
-        if P <= 0:
-            raise RuntimeError(lib.dt_last_error().decode())
-        stats = torch.empty(lib.dt_bn_stats_floats(P, Cout), dtype=torch.float32, device=out.device)
-    _lib.check(lib.dt_conv2d_bf16(C.byref(d), _p(s2d), None, _p(wp), _p(out), None, _p(stats), None, None, st),
+    buf, stats = _rows_buffer(lib.dt_conv2d_bf16_stat_rows(C.byref(d)), Cout, out.device) if want_stats else (None, None)
+    _lib.check(lib.dt_conv2d_bf16(C.byref(d), _p(s2d), None, _p(wp), _p(out), None, _p(buf), None, None, st),
                "dt_conv2d_bf16(stem)")
-    if stats is not None:
-        stats = stats[:2 * P * Cout].view(2, P, Cout)
     return out, stats
 
 
@@ -744,13 +692,8 @@ def stem_wgrad_bf16(x_nhwc_f32, dy_bf16):
     s2d = torch.empty((B, H // 2, W // 2, 16), dtype=torch.bfloat16, device=x_nhwc_f32.device)
     _lib.check(lib.dt_stem_s2d_bf16(_p(x_nhwc_f32.contiguous()), _p(s2d), B, H, W, Cin, st), "dt_stem_s2d_bf16")
     d = _lib.ConvDesc(B, H // 2, W // 2, 16, 0, 0, H // 2, W // 2, Cout, 4, 1, 2, 0, 0)
-    nbytes = lib.dt_conv2d_wgrad_bf16_workspace(C.byref(d))
-    if nbytes == 0:
-        raise RuntimeError(lib.dt_last_error().decode())
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=s2d.device)
     dw4 = torch.empty(16 * 16 * Cout, dtype=torch.float32, device=s2d.device)
-    _lib.check(lib.dt_conv2d_wgrad_bf16(C.byref(d), _p(s2d), None, _p(dy_bf16.contiguous()), _p(dw4), _p(ws), nbytes,
-                                        None, None, st), "dt_conv2d_wgrad_bf16(stem)")
+    _wgrad("dt_conv2d_wgrad_bf16", d, s2d, None, dy_bf16, dw4, what="dt_conv2d_wgrad_bf16(stem)")
     dw7 = torch.empty((7, 7, Cin, Cout), dtype=torch.float32, device=s2d.device)
     _lib.check(lib.dt_stem_unpack_wgrad(_p(dw4), _p(dw7), Cin, Cout, st), "dt_stem_unpack_wgrad")
     return dw7

@@ -589,6 +589,12 @@ int dt_signed_distmap(const int64_t* labels, float* dist, void* workspace, int32
  * dt_conv2d (mode0 0/1/2, concat, split outputs, accumulate, BatchNorm partial statistics from the fp32
  * accumulators, fused input BatchNorm-apply + ReLU). */
 int dt_conv2d_bf16_stat_rows(const dt_conv_desc* d);
+/* The kernel dt_conv2d_bf16 runs for `d`.  row_tiles names the family:
+ *    2  register-staged tiles of 256 pixels x tile_n channels, tile_w wide, chunk_k channels per chunk (and the stem);
+ *    4  register-staged tiles of 512 pixels (tile_w 32, tile_n 64, chunk_k 16);
+ *    8  the LDS-DMA staged kernel (512 pixels x 64 channels): reads the CHUNKED weight images, see dt_weight_images;
+ *   16  the lean persistent kernel of the narrow full-resolution layers (Cin, Cout in {16, 32}).
+ * For 8 and 16 the other three values describe that kernel's fixed tile and select nothing. */
 int dt_conv2d_bf16_config(const dt_conv_desc* d, int* tile_w, int* tile_n, int* chunk_k, int* row_tiles);  /* conv_fwd_bf16_kernel<k,s,tw,tn,tf> */
 int dt_conv2d_bf16(const dt_conv_desc* d, const void* src0, const void* src1, const void* w_bf16, void* out,
                    void* out1, float* stats, const float* in_scale, const float* in_shift, void* stream);
@@ -647,8 +653,8 @@ int dt_channel_slice_bf16(const void* src, void* dst, int64_t n_pix, int C_narro
  * taps*ceil(Cin/32)*ceil(Cout/32); total_tiles = that sum over all layers.  The image of layer l lands at out + w_off
  * (in elements of the output type).  mode 0 = dt_weight_flip_transpose (fp32), 1 = dt_pack_weights_bf16,
  * 2 = dt_pack_dgrad_weights_bf16; 3 / 4 = the forward / data-gradient bf16 images in the chunked layout
- * [tap][K/32][N][32] that the LDS-DMA staged kernels read (dt_conv2d_bf16 reports them with mt == 8 in
- * dt_conv2d_bf16_config: pass THAT image to such a launch); layers with K or N not a multiple of 32 are skipped. */
+ * [tap][K/32][N][32] that the LDS-DMA staged kernels read (dt_conv2d_bf16_config reports them with
+ * row_tiles 8: pass THAT image to such a launch); layers with K or N not a multiple of 32 are skipped. */
 int dt_weight_images(const float* params, void* out, const int32_t* table, int n_layers, int total_tiles, int mode,
                      void* stream);
 /* modes 1 - 4 (the four bf16 images of a bf16 training step: forward / data-gradient, plain / chunked for the LDS-DMA

@@ -229,7 +229,8 @@ def _family(answers):
             fams.append("tiled")
     brc, _, _, _, mt = q["dt_conv2d_bf16_config"]
     if brc == 0:
-        fams.append({8: "bf16 lds-dma", 16: "bf16 narrow", 4: "bf16 512-pixel"}.get(mt, "bf16 tiled"))
+        from deadtrees_amd._lib import BF16_MT_DMA, BF16_MT_NARROW
+        fams.append({BF16_MT_DMA: "bf16 lds-dma", BF16_MT_NARROW: "bf16 narrow", 4: "bf16 512-pixel"}.get(mt, "bf16 tiled"))
     if q["dt_conv2d_wgrad_winograd_supported"]:
         fams.append("winograd wgrad")
     return fams

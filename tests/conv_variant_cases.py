@@ -66,11 +66,7 @@ def fp32_config(t):
 
 def bf16_config(t):
     """(tw, tn, ck, mt) or None when the bf16 validator refuses the descriptor"""
-    lib, d = _lib().load(), descriptor(t)
-    o = [C.c_int(-1) for _ in range(4)]
-    if lib.dt_conv2d_bf16_config(C.byref(d), *[C.byref(x) for x in o]) != 0:
-        return None
-    return tuple(x.value for x in o)
+    return _lib().bf16_config(descriptor(t))
 
 
 def dma_default():
@@ -185,7 +181,7 @@ def cases():
                 key = kf(t)
                 if key is None or key in seen[prec]:
                     continue
-                if prec == "bf16" and key[6] == 8 and bf16_config_without_dma(t)[1] != 64:
+                if prec == "bf16" and key[6] == _lib().BF16_MT_DMA and bf16_config_without_dma(t)[1] != 64:
                     continue      # an LDS-DMA case also serves, with that kernel off, the register-staged 64-wide tiles
                 seen[prec].add(key)
                 rank = (pen, macs(t), t)

@@ -554,19 +554,14 @@ def test_conv_bf16_dma_kernel_is_bit_identical_to_the_register_staged_kernel(B, 
     a, bq = res[0], res[2]
     # the register-staged variants with 16-channel chunks (narrow layers, 512-pixel tiles) accumulate the same products
     # in another order: equal up to fp32 summation order there, bit-identical against the 32-channel-chunk variants
-    import ctypes as C
     from deadtrees_amd import _lib
     d = ops.conv_desc(B, Hin, Win, C0, C1, mode0, Cout, 3, 1, 1, split, 1 if split else 0)
-    tw, tn, ck, mt = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    _set_dma(0)
-    _lib.load().dt_conv2d_bf16_config(C.byref(d), C.byref(tw), C.byref(tn), C.byref(ck), C.byref(mt))
     _set_dma(2)
-    _lib.load().dt_conv2d_bf16_config(C.byref(d), C.byref(tw), C.byref(tn), C.byref(ck), C.byref(mt))
-    assert mt.value == 8                                    # the DMA kernel really ran in mode 2
+    assert _lib.bf16_config(d)[3] == _lib.BF16_MT_DMA       # the DMA kernel really ran in mode 2
     _set_dma(0)
-    _lib.load().dt_conv2d_bf16_config(C.byref(d), C.byref(tw), C.byref(tn), C.byref(ck), C.byref(mt))
+    ck = _lib.bf16_config(d)[2]
     _set_dma(1)
-    same_order = ck.value == 32
+    same_order = ck == 32
 
     def check(x, y):
         if same_order:

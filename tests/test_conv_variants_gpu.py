@@ -273,7 +273,7 @@ def _bf16_case(key, t):
     if key[0] == 4:
         return _bf16_stem(key, t)
     _, inp, want, mag, wdev = _run_case("bf16", key, t)
-    if key[6] == 8:
+    if key[6] == cvc._lib().BF16_MT_DMA:
         # the LDS-DMA kernel ran above; with it switched off the same batch takes the register-staged 64-wide tiles
         # (256-pixel ones, mt = 2, at these batches: the 512-pixel form has its own case off the table)
         try:
