@@ -7,3 +7,5 @@ from deadtrees_amd.deployment.tiler import (outlines_geojson, polygonize, polygo
                                             write_outlines_geojson)
 from deadtrees_amd.deployment.tiler import (PatchMatch, PatchOverlaps, PatchTracks, overlap_pairs_host,  # noqa: F401
                                             patch_overlaps)  # (overlaps of two maps' patches)
+from deadtrees_amd.deployment.tiler import (PatchDistances, PatchGaps, ProximityConfig, patch_distances,  # noqa: F401
+                                            patch_gaps, patch_proximity_host)  # (nearest-patch distances)

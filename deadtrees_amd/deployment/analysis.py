@@ -1,6 +1,7 @@
 """What ``infer_tile`` / ``infer_rasters`` / ``Tiler.stats`` compute from a final class map — counts per zone, patch table,
-outlines, overlaps with another map — as ONE request (``MapAnalysis``, the only place that checks the options' rules), one
-host runner and one device runner.  The results' contracts are those of ``stats`` / ``patches`` / ``outlines`` / ``overlaps``."""
+outlines, overlaps with another map, nearest-patch distances — as ONE request (``MapAnalysis``, the only place that checks the
+options' rules), one host runner and one device runner.  The results' contracts are those of ``stats`` / ``patches`` /
+``outlines`` / ``overlaps`` / ``proximity``."""
 from __future__ import annotations
 
 from dataclasses import dataclass, replace
@@ -10,6 +11,7 @@ import numpy as np
 
 from ..data.polygons import PolygonSet, rasterize
 from .patches import PatchConfig, check_patches, labelled_patches_host
+from .proximity import ProximityConfig, check_proximity, distances_of, gaps_of
 from .stats import MAX_ZONES, RasterStats, zonal_counts_host
 
 
@@ -76,7 +78,9 @@ class MapAnalysis:
     """what a caller asked to be computed from a final class map.  ``K``: the model's class count; ``zones`` (uint8 [h, w]
     array, ``PolygonSet`` or None) and ``Z``: the counts are split by zone; ``patches``: the ``PatchConfig`` of the
     ``PatchTable``, or None; ``outlines``: the patches' outlines as well; ``against`` (array, ``PolygonSet`` or None) and
-    ``against_patches``: the map the result is compared with, and its ``PatchConfig``; ``n_zones``: the caller's figure.
+    ``against_patches``: the map the result is compared with, and its ``PatchConfig``; ``n_zones``: the caller's figure;
+    ``distances`` / ``gaps``: the ``ProximityConfig`` of the distances to the patches of ``against`` / to the map's own other
+    patches, or None.
     ``rules`` checks what depends on no raster, ``bind`` the maps of one raster, ``of`` both; ``stats=False`` gives None"""
     K: Optional[int]
     zones: object = None
@@ -86,14 +90,21 @@ class MapAnalysis:
     against: object = None
     against_patches: Optional[PatchConfig] = None
     n_zones: Optional[int] = None
+    distances: Optional[ProximityConfig] = None
+    gaps: Optional[ProximityConfig] = None
 
     @classmethod
     def rules(cls, who: str, K, stats: bool = True, zones=None, n_zones=None, patches=None, outlines=None, against=None,
-              against_patches=None) -> Optional["MapAnalysis"]:
+              against_patches=None, distances=None, gaps=None) -> Optional["MapAnalysis"]:
         """the options as ``infer_tile`` receives them -> a request without maps yet, or None without ``stats``; ``zones`` and
         ``against`` only say whether there are any (``infer_rasters`` passes its mappings).  ``ValueError``: an option without
-        ``stats``, outlines or ``against`` without patches, ``against_patches`` without ``against``, a value of a wrong type"""
+        ``stats``, outlines, ``against`` or ``gaps`` without patches, ``against_patches`` or ``distances`` without ``against``, a
+        value of a wrong type"""
         config = check_patches(patches)
+        try:
+            distances, gaps = check_proximity(distances, "distances"), check_proximity(gaps, "gaps")
+        except ValueError as e:
+            raise ValueError(f"{who}: {e}") from None
         if outlines is not None and not isinstance(outlines, bool):
             raise ValueError(f"{who}: outlines must be True, False or None, got {outlines!r}")
         if outlines and config is None:
@@ -105,7 +116,13 @@ class MapAnalysis:
                 raise ValueError(f"{who}: patches need stats=True")
             if against is not None or against_patches is not None:
                 raise ValueError(f"{who}: against / against_patches need stats=True")
+            if distances is not None or gaps is not None:
+                raise ValueError(f"{who}: distances / gaps need stats=True")
             return None
+        if gaps is not None and config is None:
+            raise ValueError(f"{who}: gaps need patches (the gaps are those of the PatchTable's patches)")
+        if distances is not None and against is None:
+            raise ValueError(f"{who}: distances need against (they are measured to the patches of that map)")
         if against is None:
             if against_patches is not None:
                 raise ValueError(f"{who}: against_patches needs against")
@@ -115,7 +132,8 @@ class MapAnalysis:
             against_patches = PatchConfig(config.connectivity)
         elif not isinstance(against_patches, PatchConfig):
             raise ValueError(f"{who}: against_patches must be a PatchConfig or None, got {against_patches!r}")
-        return cls(K=K, patches=config, outlines=bool(outlines), against_patches=against_patches, n_zones=n_zones)
+        return cls(K=K, patches=config, outlines=bool(outlines), against_patches=against_patches, n_zones=n_zones,
+                   distances=distances, gaps=gaps)
 
     def bind(self, who: str, shape, zones=None, against=None) -> "MapAnalysis":
         """the request of one raster of ``shape`` (h, w) and its maps, of the kinds ``rules`` was told of.  ``ValueError``: a map
@@ -125,7 +143,8 @@ class MapAnalysis:
             raise ValueError(f"{who}: stats=True needs an inference object with a `classes` count")
         against = None if against is None else check_against_map(against, shape, int(self.K), who)
         return replace(self, K=int(self.K), zones=zones, Z=Z, against=against,
-                       against_patches=None if against is None else self.against_patches)
+                       against_patches=None if against is None else self.against_patches,
+                       distances=None if against is None else self.distances)
 
     @classmethod
     def of(cls, who: str, shape, K, zones=None, against=None, **options) -> Optional["MapAnalysis"]:
@@ -145,17 +164,21 @@ def run_host(request: MapAnalysis, result: np.ndarray):
     from .overlaps import PatchOverlaps, overlap_pairs_host
     K, config = request.K, request.patches
     zones = map_plane(request.zones, result.shape, True)
-    table = rings = pairs = None
+    table = rings = pairs = gaps = None
     if config is not None:
         result, labels, table = labelled_patches_host(result, K, config)
+        if request.gaps is not None:
+            gaps = gaps_of(labels, table, request.gaps.limit2)
         if request.against is not None:
             _, labels_a, table_a = labelled_patches_host(map_plane(request.against, result.shape, True), K,
                                                          request.against_patches)
-            pairs = PatchOverlaps(table_a, table, *overlap_pairs_host(labels_a, labels))
+            apart = (None if request.distances is None
+                     else distances_of(labels_a, table_a, labels, table, request.distances.limit2))
+            pairs = PatchOverlaps(table_a, table, *overlap_pairs_host(labels_a, labels), distances=apart)
         if request.outlines:
             rings = outlines_from_labels(labels, result, config.connectivity)
     counts = zonal_counts_host(np.ascontiguousarray(result), zones, K, request.Z)
-    return result, RasterStats(counts, patches=table, outlines=rings, overlaps=pairs)
+    return result, RasterStats(counts, patches=table, outlines=rings, overlaps=pairs, gaps=gaps)
 
 
 def device_labels(classes, K: int, config: PatchConfig, err=None, in_place: bool = False, areas: bool = True):
@@ -184,18 +207,22 @@ def run_device(request: Optional[MapAnalysis], out, probs=None, planes=(None, No
     arrays.  ``planes``: the request's ``device_planes``.  The order of the enqueued work is fixed: (1) with patches ``out``
     is labelled, measured and — if asked — sieved IN PLACE; (2) ONE ``ops.zonal_counts`` on ``out``, no synchronisation of
     its own; (3) with patches the map leaves by a pinned, non-blocking copy (without them by ``out.cpu()``); (4) the roots
-    are compacted and measured behind it (``ops.patch_table`` reads the row count back); (5) ``outlines`` traces the final
-    label plane (two more scalar read-backs); (6) ``against`` is labelled, sieved on a clone if asked and tabled like
-    ``out``, and ``ops.patch_overlaps`` reads the two label planes (three more read-backs); (7) one stream synchronise, then
-    the counts and the ``err`` flag are read.  Workspace next to the map: about 12 bytes per pixel for the patches (labels,
-    the area plane reused as the root -> row plane, the compaction's flags), as much again for ``against``"""
+    are compacted and measured behind it (``ops.patch_table`` reads the row count back), and with ``gaps`` one
+    ``ops.patch_proximity`` of the label plane against itself follows (no scalar read-back, its result is downloaded); (5)
+    ``outlines`` traces the final label plane (two more scalar read-backs); (6) ``against`` is labelled, sieved on a clone if
+    asked and tabled like ``out``, ``ops.patch_overlaps`` reads the two label planes (three more read-backs), and with
+    ``distances`` two ``ops.patch_proximity`` calls, one per direction, read them again; (7) one stream synchronise, then
+    the counts and the ``err`` flag are read.  Without ``gaps`` / ``distances`` nothing of theirs is enqueued.  Workspace next
+    to the map: about 12 bytes per pixel for the patches (labels, the area plane reused as the root -> row plane, the
+    compaction's flags), as much again for ``against``; a proximity call holds 16 bytes per pixel while it runs (column
+    tables and the root -> row plane), 28 for ``gaps``"""
     if request is None:
         return out.cpu().numpy() if probs is None else (out.cpu().numpy(), probs.cpu().numpy())
     import torch
     from .. import ops
     from .overlaps import PatchOverlaps
     K, config = request.K, request.patches
-    table = rings = pairs = None
+    table = rings = pairs = gaps = None
     err = torch.zeros(1, dtype=torch.int32, device=out.device)
     if config is not None:
         _, labels, area, _ = device_labels(out, K, config, err, in_place=True)
@@ -204,11 +231,16 @@ def run_device(request: Optional[MapAnalysis], out, probs=None, planes=(None, No
         host = torch.empty(out.shape, dtype=out.dtype, pin_memory=True)
         host.copy_(out, non_blocking=True)                      # enqueued; the table's read-back waits for it
         table = ops.patch_table(labels, out, area, reuse_area_plane=True)
+        if request.gaps is not None:
+            gaps = gaps_of(labels, table, request.gaps.limit2, device=True)
         if request.outlines:
             rings = ops.patch_outlines(labels, out, config.connectivity)
         if request.against is not None:
             labels_a, table_a = device_patches(planes[1], K, request.against_patches, err)
-            pairs = PatchOverlaps(table_a, table, *ops.patch_overlaps(labels_a, labels))
+            rows = ops.patch_overlaps(labels_a, labels)
+            apart = (None if request.distances is None
+                     else distances_of(labels_a, table_a, labels, table, request.distances.limit2, device=True))
+            pairs = PatchOverlaps(table_a, table, *rows, distances=apart)
         torch.cuda.current_stream(out.device).synchronize()
         result = (host.numpy(),)
     else:
@@ -219,4 +251,4 @@ def run_device(request: Optional[MapAnalysis], out, probs=None, planes=(None, No
     if flag:          # cannot happen with checked zones: the map is an argmax over K classes
         raise RuntimeError(f"infer_tile: raster statistics met a value out of range (flag {flag}: 1 class >= {K}, "
                            f"2 zone >= {request.Z})")
-    return result + (RasterStats(counts.cpu().numpy(), patches=table, outlines=rings, overlaps=pairs),)
+    return result + (RasterStats(counts.cpu().numpy(), patches=table, outlines=rings, overlaps=pairs, gaps=gaps),)

@@ -67,9 +67,10 @@ class PatchOverlaps:
     ``PatchTable``.  ``table_a`` / ``table_b`` (same ``shape``); ``a`` / ``b`` / ``n``: the rows of the module's contract;
     ``ia`` / ``ib`` int64: the row of each pair's patch in the two tables; ``inter`` is ``n``.  ``ValueError`` when a root
     is missing from its table, the rows are not strictly ascending in ``(a, b)``, or some ``n`` is below 1 or above
-    ``min(area_a, area_b)``"""
+    ``min(area_a, area_b)``.  ``distances``: the ``PatchDistances`` (``deployment/proximity.py``) of the same two tables when
+    they were asked for, else None — then ``repr`` and ``==`` do not mention them"""
 
-    def __init__(self, table_a: PatchTable, table_b: PatchTable, a, b, n):
+    def __init__(self, table_a: PatchTable, table_b: PatchTable, a, b, n, distances=None):
         if not isinstance(table_a, PatchTable) or not isinstance(table_b, PatchTable):
             raise ValueError("PatchOverlaps: table_a and table_b must be PatchTables")
         if table_a.shape != table_b.shape:
@@ -95,6 +96,13 @@ class PatchOverlaps:
         self._ib.setflags(write=False)
         if ((self._n < 1) | (self._n > np.minimum(table_a.area[self._ia], table_b.area[self._ib]))).any():
             raise ValueError("PatchOverlaps: n must be in 1..min(area_a, area_b)")
+        if distances is not None:
+            from .proximity import PatchDistances
+            if not isinstance(distances, PatchDistances):
+                raise ValueError(f"PatchOverlaps: distances must be a PatchDistances or None, got {type(distances).__name__}")
+            if distances.table_a != table_a or distances.table_b != table_b:
+                raise ValueError("PatchOverlaps: distances need the two PatchTables they belong to")
+        self._distances = distances
 
     a = property(lambda self: self._a)
     b = property(lambda self: self._b)
@@ -102,6 +110,7 @@ class PatchOverlaps:
     inter = property(lambda self: self._n)
     ia = property(lambda self: self._ia)
     ib = property(lambda self: self._ib)
+    distances = property(lambda self: self._distances)
 
     def __len__(self) -> int:
         return len(self._a)
@@ -142,14 +151,18 @@ class PatchOverlaps:
     def __eq__(self, other) -> bool:
         if not isinstance(other, PatchOverlaps):
             return NotImplemented
+        if (self._distances is None) != (other._distances is None):
+            return False
         return (self.table_a == other.table_a and self.table_b == other.table_b
-                and all(np.array_equal(getattr(self, c), getattr(other, c)) for c in ("_a", "_b", "_n")))
+                and all(np.array_equal(getattr(self, c), getattr(other, c)) for c in ("_a", "_b", "_n"))
+                and (self._distances is None or self._distances == other._distances))
 
     __hash__ = None
 
     def __repr__(self) -> str:
+        tail = "" if self._distances is None else f", distances={self._distances!r}"
         return (f"PatchOverlaps(pairs={len(self)}, n_a={self.table_a.n}, n_b={self.table_b.n}, "
-                f"shared pixels={int(self._n.sum())})")
+                f"shared pixels={int(self._n.sum())}{tail})")
 
     # ------------------------------------------------------------------ crown-level accuracy
     def match(self, min_iou: float = 0.5, same_class: bool = True) -> "PatchMatch":
@@ -289,28 +302,23 @@ class PatchTracks:
 
 
 # ---------------------------------------------------------------------------------------------- maps in, table out
-def patch_overlaps(map_a, map_b, K: int, config_a: Optional[PatchConfig] = None, config_b: Optional[PatchConfig] = None,
-                   device=None, shape=None) -> PatchOverlaps:
-    """the ``PatchOverlaps`` of two maps on one grid: uint8 class maps (arrays or tensors), or ``PolygonSet``s in pixel
-    coordinates, burnt with ``rasterize(..., all_touched=True)`` — the rule the training masks are made with; a polygon
-    value >= K is a ``ValueError``.  Label -> (sieve) -> table on both maps (``config_a`` / ``config_b``, default
-    ``PatchConfig()``), then the overlap table.  ``shape``: the grid, needed only when both maps are polygons.
-
-    On the host ``labelled_patches_host`` + ``overlap_pairs_host``.  With device tensors, or ``device`` a ``cuda`` device,
-    ``ops.label_patches`` -> ``ops.patch_areas`` -> (``ops.sieve_patches``) -> ``ops.patch_table`` on both maps, then
-    ``ops.patch_overlaps``: only the tables are downloaded.  Neither input is written"""
+def checked_maps(who: str, maps, K: int, configs_in, device=None, shape=None):
+    """the maps of ``patch_overlaps`` and its kin where they are read: ``(planes, configs, device)`` — uint8 planes on
+    the ``cuda`` device when there is one (device tensors, or ``device`` names one), else host arrays and None; a
+    ``PolygonSet`` is burnt with ``all_touched=True``; a configuration None is ``PatchConfig()``.  ``ValueError``: K outside
+    2..8, a configuration of a wrong type, a map off the grid, not uint8 or with a value >= K, no grid at all"""
     import torch
     from ..data.polygons import PolygonSet
-    from .analysis import check_against_map, device_patches, map_plane
+    from .analysis import check_against_map, map_plane
     K = int(K)
     if not 2 <= K <= MAX_CLASSES:
-        raise ValueError(f"patch_overlaps: K must be in 2..{MAX_CLASSES}, got {K}")
+        raise ValueError(f"{who}: K must be in 2..{MAX_CLASSES}, got {K}")
     configs = []
-    for c in (config_a, config_b):
+    for c in configs_in:
         if c is not None and not isinstance(c, PatchConfig):
-            raise ValueError(f"patch_overlaps: a configuration must be a PatchConfig or None, got {c!r}")
+            raise ValueError(f"{who}: a configuration must be a PatchConfig or None, got {c!r}")
         configs.append(PatchConfig() if c is None else c)
-    maps = [map_a, map_b]
+    maps = list(maps)
     dev = None if device is None else torch.device(device)
     for m in maps:
         if isinstance(m, torch.Tensor):
@@ -321,23 +329,50 @@ def patch_overlaps(map_a, map_b, K: int, config_a: Optional[PatchConfig] = None,
         elif not isinstance(m, PolygonSet) and shape is None:
             shape = tuple(np.shape(m))
     if shape is None:
-        raise ValueError("patch_overlaps: two PolygonSets need the grid's shape")
+        raise ValueError(f"{who}: PolygonSets alone need the grid's shape")
     on_device = dev is not None and dev.type == "cuda"
     for k, m in enumerate(maps):
         if isinstance(m, torch.Tensor):
             if m.dtype != torch.uint8 or tuple(m.shape) != tuple(shape) or m.dim() != 2 or m.numel() == 0:
-                raise ValueError(f"patch_overlaps: a map must be uint8 on the grid {tuple(shape)}, got {m.dtype} "
+                raise ValueError(f"{who}: a map must be uint8 on the grid {tuple(shape)}, got {m.dtype} "
                                  f"{tuple(m.shape)}")
-            maps[k] = m.to(dev) if on_device else check_against_map(m.cpu().numpy(), shape, K, "patch_overlaps")
+            maps[k] = m.to(dev) if on_device else check_against_map(m.cpu().numpy(), shape, K, who)
             continue
-        maps[k] = map_plane(check_against_map(m, shape, K, "patch_overlaps"), shape, True, dev if on_device else None)
-    if not on_device:
+        maps[k] = map_plane(check_against_map(m, shape, K, who), shape, True, dev if on_device else None)
+    return maps, configs, dev if on_device else None
+
+
+def labelled_maps(who: str, maps, K: int, configs, device=None, shape=None):
+    """label -> (sieve) -> table of every map of ``checked_maps``: ``(label planes, PatchTables, device)`` — on the host
+    (``device`` None) ``labelled_patches_host``, on a ``cuda`` device ``analysis.device_patches``: the label planes stay
+    there and only the tables are downloaded.  No input is written"""
+    maps, configs, dev = checked_maps(who, maps, K, configs, device, shape)
+    K = int(K)
+    if dev is None:
         planes = [labelled_patches_host(m, K, c) for m, c in zip(maps, configs)]
-        return PatchOverlaps(planes[0][2], planes[1][2], *overlap_pairs_host(planes[0][1], planes[1][1]))
-    from .. import ops
+        return [p[1] for p in planes], [p[2] for p in planes], None
+    import torch
+    from .analysis import device_patches
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    (labels_a, table_a), (labels_b, table_b) = (device_patches(m, K, c, err) for m, c in zip(maps, configs))
-    rows = ops.patch_overlaps(labels_a, labels_b)
+    planes = [device_patches(m, K, c, err) for m, c in zip(maps, configs)]
     if int(err.cpu()):
-        raise ValueError(f"patch_overlaps: class value out of range (K={K})")
-    return PatchOverlaps(table_a, table_b, *rows)
+        raise ValueError(f"{who}: class value out of range (K={K})")
+    return [p[0] for p in planes], [p[1] for p in planes], dev
+
+
+def patch_overlaps(map_a, map_b, K: int, config_a: Optional[PatchConfig] = None, config_b: Optional[PatchConfig] = None,
+                   device=None, shape=None) -> PatchOverlaps:
+    """the ``PatchOverlaps`` of two maps on one grid: uint8 class maps (arrays or tensors), or ``PolygonSet``s in pixel
+    coordinates, burnt with ``rasterize(..., all_touched=True)`` — the rule the training masks are made with; a polygon
+    value >= K is a ``ValueError``.  Label -> (sieve) -> table on both maps (``config_a`` / ``config_b``, default
+    ``PatchConfig()``), then the overlap table.  ``shape``: the grid, needed only when both maps are polygons.
+
+    On the host ``labelled_patches_host`` + ``overlap_pairs_host``.  With device tensors, or ``device`` a ``cuda`` device,
+    ``ops.label_patches`` -> ``ops.patch_areas`` -> (``ops.sieve_patches``) -> ``ops.patch_table`` on both maps, then
+    ``ops.patch_overlaps``: only the tables are downloaded.  Neither input is written"""
+    (labels_a, labels_b), (table_a, table_b), dev = labelled_maps("patch_overlaps", (map_a, map_b), K, (config_a, config_b),
+                                                                  device, shape)
+    if dev is None:
+        return PatchOverlaps(table_a, table_b, *overlap_pairs_host(labels_a, labels_b))
+    from .. import ops
+    return PatchOverlaps(table_a, table_b, *ops.patch_overlaps(labels_a, labels_b))

@@ -68,9 +68,11 @@ class RasterStats:
     ``PolygonSet`` on the raster's grid, polygon ``k`` is row ``k`` of ``patches``) when they were asked for, else None;
     a sum of rasters has none either.  ``overlaps``: the ``PatchOverlaps`` (``deployment/overlaps.py``) of the map asked
     for with ``against`` (its ``table_a``) and this raster's patches (its ``table_b`` is ``patches``), else None; a sum of
-    rasters has none"""
+    rasters has none.  ``gaps``: the ``PatchGaps`` (``deployment/proximity.py``: every patch's distance to the nearest other
+    patch, aligned with ``patches``) when they were asked for, else None — then ``repr`` and ``==`` do not mention them; a sum
+    of rasters has none"""
 
-    def __init__(self, counts, pixel_area_m2: float = PIXEL_AREA_M2, patches=None, outlines=None, overlaps=None):
+    def __init__(self, counts, pixel_area_m2: float = PIXEL_AREA_M2, patches=None, outlines=None, overlaps=None, gaps=None):
         counts = np.array(counts, dtype=np.int64)
         if counts.ndim != 2 or counts.shape[0] < 1 or counts.shape[1] < 2:
             raise ValueError(f"RasterStats: counts must be [Z >= 1, K >= 2], got shape {counts.shape}")
@@ -98,6 +100,13 @@ class RasterStats:
             if patches is None or overlaps.table_b != patches:
                 raise ValueError("RasterStats: overlaps need the PatchTable they belong to (their table_b)")
         self._overlaps = overlaps
+        if gaps is not None:
+            from .proximity import PatchGaps
+            if not isinstance(gaps, PatchGaps):
+                raise ValueError(f"RasterStats: gaps must be a PatchGaps or None, got {type(gaps).__name__}")
+            if patches is None or gaps.table != patches:
+                raise ValueError("RasterStats: gaps need the PatchTable they belong to")
+        self._gaps = gaps
 
     @property
     def patches(self):
@@ -110,6 +119,10 @@ class RasterStats:
     @property
     def overlaps(self):
         return self._overlaps
+
+    @property
+    def gaps(self):
+        return self._gaps
 
     @property
     def counts(self) -> np.ndarray:
@@ -156,7 +169,7 @@ class RasterStats:
             return NotImplemented
         if (self._patches is None) != (other._patches is None) or (self._outlines is None) != (other._outlines is None):
             return False
-        if (self._overlaps is None) != (other._overlaps is None):
+        if (self._overlaps is None) != (other._overlaps is None) or (self._gaps is None) != (other._gaps is None):
             return False
         return (self._counts.shape == other._counts.shape and bool((self._counts == other._counts).all())
                 and self.pixel_area_m2 == other.pixel_area_m2
@@ -164,7 +177,8 @@ class RasterStats:
                 and (self._outlines is None or all(
                     np.array_equal(getattr(self._outlines, a), getattr(other._outlines, a))
                     for a in ("xy", "ring_offsets", "ring_polygon", "values")))
-                and (self._overlaps is None or self._overlaps == other._overlaps))
+                and (self._overlaps is None or self._overlaps == other._overlaps)
+                and (self._gaps is None or self._gaps == other._gaps))
 
     __hash__ = None
 
@@ -174,6 +188,8 @@ class RasterStats:
             tail += f", outlines={self._outlines!r}"
         if self._overlaps is not None:
             tail += f", overlaps={self._overlaps!r}"
+        if self._gaps is not None:
+            tail += f", gaps={self._gaps!r}"
         return f"RasterStats(counts={self._counts.tolist()}, pixel_area_m2={self.pixel_area_m2!r}{tail})"
 
 

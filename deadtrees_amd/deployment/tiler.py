@@ -29,6 +29,8 @@ import torch
 from .analysis import MapAnalysis, run_device, run_host
 from .outlines import outlines_geojson, polygonize, polygonize_host, write_outlines_geojson  # noqa: F401
 from .overlaps import (PatchMatch, PatchOverlaps, PatchTracks, overlap_pairs_host, patch_overlaps)  # noqa: F401
+from .proximity import (PatchDistances, PatchGaps, ProximityConfig, patch_distances, patch_gaps,  # noqa: F401
+                        patch_proximity_host)
 from .patches import PatchConfig, PatchTable  # noqa: F401  (the ``patches`` argument of infer_tile)
 
 
@@ -241,16 +243,17 @@ class Tiler:
         return self._outdata[0:self._tile_info.size[0], 0:self._tile_info.size[1]]
 
     def stats(self, zones=None, classes: int = 3, n_zones: Optional[int] = None, patches=None, outlines=None,
-              against=None, against_patches=None):
+              against=None, against_patches=None, distances=None, gaps=None):
         """``RasterStats`` of ``result``: what ``infer_tile(..., stats=True)`` returns, for a caller of the reference's own
         ``get_batches`` / ``put_batches`` loop, computed on the host (``analysis.run_host``).  ``classes``: the model's class
-        count; ``zones`` / ``n_zones`` / ``patches`` / ``outlines`` / ``against`` / ``against_patches``: as in ``infer_tile``,
-        with the same rules (``MapAnalysis``).  Polygons are burnt by ``rasterize_host``; a ``patches`` configuration that
+        count; ``zones`` / ``n_zones`` / ``patches`` / ``outlines`` / ``against`` / ``against_patches`` / ``distances`` /
+        ``gaps``: as in ``infer_tile``, with the same rules (``MapAnalysis``).  Polygons are burnt by ``rasterize_host``; a ``patches`` configuration that
         sieves changes ``result`` itself, and the counts are those of the sieved map"""
         if self._outdata is None:
             raise RuntimeError("Tiler: load_file / load_array first")
         return self._analyse(MapAnalysis.of("Tiler.stats", self.result.shape, classes, zones, against, n_zones=n_zones,
-                                            patches=patches, outlines=outlines, against_patches=against_patches))
+                                            patches=patches, outlines=outlines, against_patches=against_patches,
+                                            distances=distances, gaps=gaps))
 
     def _analyse(self, request: MapAnalysis):
         """the ``RasterStats`` of ``result`` under a checked request (``analysis.run_host``); a sieved map replaces ``result``"""
@@ -272,21 +275,21 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
                   device: str = "cuda", tile_shape: Optional[Tuple[int, int]] = None, skip_blank: bool = True,
                   overlap: int = 0, blend: str = "crop", return_probs: bool = False, tta=None, stats: bool = False,
                   zones=None, n_zones: Optional[int] = None, patches=None, outlines=None, against=None,
-                  against_patches=None):
+                  against_patches=None, distances=None, gaps=None):
     """the directory loop of scripts/inference.py:71-115 over in-memory rasters (GeoTIFF I/O needs rioxarray, absent
     here): ``rasters`` yields ``array`` or ``(key, array)``; rank r of ``world`` takes rasters r, r + world, ... (tiles are
     independent: no collective).  Yields ``(key, class_map)`` in input order of the rank's share; rasters whose band 1
     holds only 0 / 255 (``is_valid_tile``, :60-62) are skipped like the reference does — ``(key, None)`` — without a
     forward pass (device reduction over the uploaded raster, ``ops.band_has_data``).  ``overlap`` / ``blend`` /
-    ``return_probs`` / ``tta`` / ``stats`` / ``n_zones`` / ``patches`` / ``outlines`` / ``against_patches``: as in
-    ``infer_tile``, with the same rules, checked before the first raster is read (every raster stays on its rank, so
+    ``return_probs`` / ``tta`` / ``stats`` / ``n_zones`` / ``patches`` / ``outlines`` / ``against_patches`` / ``distances`` /
+    ``gaps``: as in ``infer_tile``, with the same rules, checked before the first raster is read (every raster stays on its rank, so
     overlap needs no exchange); ``zones``: a callable ``key -> uint8 [h, w] array, PolygonSet or None``, or a mapping (a
     missing key is None); ``against``: the same for the map every raster is compared with (a uint8 array, a ``PolygonSet``
     or None: that raster's statistics carry no overlaps).
     The second item of every pair is whatever ``infer_tile`` returned: with ``stats=True`` ``(map, RasterStats)`` — the
     ``RasterStats`` of a rank's share add up (``+``) to that rank's part of the regional totals."""
     rules = MapAnalysis.rules("infer_rasters", getattr(inference, "classes", None) if stats else None, stats, zones, n_zones,
-                              patches, outlines, against, against_patches)
+                              patches, outlines, against, against_patches, distances, gaps)
     for i, item in enumerate(rasters):
         if i % world != rank:
             continue
@@ -302,7 +305,7 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
                world: int = 1, device: str = "cuda", group=None, tile_shape: Optional[Tuple[int, int]] = None,
                on_device: Optional[bool] = None, skip_blank: bool = False, overlap: int = 0, blend: str = "crop",
                return_probs: bool = False, tta=None, stats: bool = False, zones=None, n_zones: Optional[int] = None,
-               patches=None, outlines=None, against=None, against_patches=None):
+               patches=None, outlines=None, against=None, against_patches=None, distances=None, gaps=None):
     """whole-tile inference of scripts/inference.py:80-115 on the MI355X path: split -> (uint8 H2D, normalise on the
     device) -> forward + fused argmax -> uint8 D2H -> merge.  With world > 1 the sub-tile batches j = rank (mod world)
     are processed locally and the uint8 class maps are all-gathered (no other collective: tiles are independent).
@@ -352,10 +355,18 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     ``against_patches`` (a ``PatchConfig``; default: the connectivity of ``patches``, no sieve), ``table_b`` the
     ``.patches`` of the final map, and one row per pair of patches that share a pixel — ``match()`` gives the crown-level
     accuracy, ``track()`` the year-to-year fate of every patch.  The map, the counts, the table and the outlines are those
-    of the call without ``against``."""
+    of the call without ``against``.
+
+    ``distances=True`` or a ``ProximityConfig(max_distance=None)`` (needs ``against``): ``.overlaps.distances`` is a
+    ``PatchDistances`` (``deployment/proximity.py``) — for every patch of either map the squared distance, pixel centre to
+    pixel centre, to the nearest dead pixel of the other map and the table row of the patch that pixel belongs to: the
+    spread distance of a ``NEW`` patch from last year's dead trees.  ``gaps=True`` or a ``ProximityConfig`` (needs
+    ``patches``): ``.gaps`` is a ``PatchGaps`` aligned with ``.patches`` — every patch's distance to the nearest OTHER patch
+    of the map.  ``max_distance`` (pixels) bounds the search: a patch farther than that from everything has no neighbour.
+    Everything else is that of the call without the two options."""
     request = MapAnalysis.of("infer_tile", np.shape(arr_chw_u8)[1:], getattr(inference, "classes", None) if stats else None,
                              zones, against, stats=stats, n_zones=n_zones, patches=patches, outlines=outlines,
-                             against_patches=against_patches)
+                             against_patches=against_patches, distances=distances, gaps=gaps)
     return _infer_tile(inference, arr_chw_u8, request, subtile, batch_size, rank, world, device, group, tile_shape, on_device,
                        skip_blank, overlap, blend, return_probs, tta)
 

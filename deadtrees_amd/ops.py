@@ -1133,9 +1133,12 @@ def rasterize_polygons(edges: torch.Tensor, polys: torch.Tensor, shape, all_touc
 
 
 # constants asked of the library on first use -> (getter, count).  PATCH_TILE = (th, tw): the tile of dt_label_patches_u8's
-# local launch; OUTLINE_CHUNK / OVERLAP_CHUNK: the consecutive pixels one workgroup of dt_outline_count / dt_overlap_count takes
+# local launch; OUTLINE_CHUNK / OVERLAP_CHUNK: the consecutive pixels one workgroup of dt_outline_count / dt_overlap_count takes;
+# PROXIMITY_SEGMENT: the rows of one column segment of dt_proximity_columns; PROXIMITY_WINDOW: the pixels of one row that a
+# workgroup of dt_proximity_query takes
 _LIB_CONSTANTS = {"PATCH_TILE": ("dt_patch_tile", 2), "OUTLINE_CHUNK": ("dt_outline_chunk", 1),
-                  "OVERLAP_CHUNK": ("dt_overlap_chunk", 1)}
+                  "OVERLAP_CHUNK": ("dt_overlap_chunk", 1), "PROXIMITY_SEGMENT": ("dt_proximity_segment", 1),
+                  "PROXIMITY_WINDOW": ("dt_proximity_window", 1)}
 
 
 def _constant(name: str):
@@ -1311,11 +1314,11 @@ def patch_outlines(labels: torch.Tensor, classes_u8: torch.Tensor, connectivity:
     return PolygonSet(xy, ring_offsets, ring_polygon, values[:int(ring_polygon[-1]) + 1])
 
 
-def _overlap_planes(labels_a: torch.Tensor, labels_b: torch.Tensor):
+def _overlap_planes(labels_a: torch.Tensor, labels_b: torch.Tensor, what: str = "patch_overlaps"):
     """the argument checks of ``patch_overlaps``: (h, w, a, b) with both planes contiguous and 16-byte aligned"""
-    h, w = _patch_planes("patch_overlaps", labels_a=labels_a, labels_b=labels_b)
+    h, w = _patch_planes(what, labels_a=labels_a, labels_b=labels_b)
     if h * w > 2 ** 31 - 2:
-        raise RuntimeError(f"patch_overlaps: {h * w} pixels do not fit int32 labels (h * w <= {2 ** 31 - 2})")
+        raise RuntimeError(f"{what}: {h * w} pixels do not fit int32 labels (h * w <= {2 ** 31 - 2})")
     planes = []
     for t in (labels_a, labels_b):
         t = t.contiguous()
@@ -1360,6 +1363,76 @@ def patch_overlaps(labels_a: torch.Tensor, labels_b: torch.Tensor):
     first = 1 if live < R else 0                               # keys are >= 0 and sorted: the key-0 segment comes first
     pair, n = pair[first:], n[first:]
     return tuple(t.cpu().numpy() for t in ((pair >> 32) - 1, (pair & 0xffffffff) - 1, n))
+
+
+def proximity_tables(labels_src: torch.Tensor, second: bool = False):
+    """the column tables of a source label plane int32 [h, w] (``dt_proximity_columns``; contiguous and 16-byte aligned, as
+    ``_overlap_planes`` returns it): ``(dist uint16 [P, h, w], nearest int32 [P, h, w], flag int32 [1])``, P = 2, or 4 with
+    ``second`` (what ``exclude_own`` needs).  12 bytes per pixel, 24 with ``second``, and 32 bytes per column and segment of
+    ``PROXIMITY_SEGMENT`` rows for the carried states.  No synchronisation"""
+    h, w = labels_src.shape
+    if max(h, w) > 16384:
+        raise RuntimeError(f"patch_proximity: raster {h}x{w}: sides must be <= 16384 (column distances are uint16)")
+    dev, P = labels_src.device, 4 if second else 2
+    dist = torch.empty((P, h, w), dtype=torch.int16, device=dev)                   # read as uint16 by the kernels
+    nearest = torch.empty((P, h, w), dtype=torch.int32, device=dev)
+    carry = torch.empty((2, -(-h // _constant("PROXIMITY_SEGMENT")), w, 4), dtype=torch.int32, device=dev)
+    flag = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().dt_proximity_columns(_p(labels_src), h, w, 1 if second else 0, _p(dist), _p(nearest), _p(carry),
+                                                _p(flag), _st()), "dt_proximity_columns")
+    return dist, nearest, flag
+
+
+def proximity_query(tables, labels_qry: torch.Tensor, roots_qry: torch.Tensor, exclude_own: bool = False, limit2: int = -1):
+    """``dt_proximity_query`` over the tables of ``proximity_tables``: int64 [n] on the device, ``d2 << 32 | root`` per query
+    root (``roots_qry`` int64 [n] on the device, n >= 1), -1 (all ones) for none.  No synchronisation"""
+    dist, nearest, flag = tables
+    h, w = labels_qry.shape
+    dev, n = labels_qry.device, int(roots_qry.numel())
+    dense = torch.full((h * w + 1,), -1, dtype=torch.int32, device=dev)      # the last entry takes the roots off the raster
+    on_grid = (roots_qry >= 0) & (roots_qry < h * w)
+    dense[torch.where(on_grid, roots_qry, h * w)] = torch.arange(n, dtype=torch.int32, device=dev)
+    best = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().dt_proximity_query(_p(dist), _p(nearest), _p(flag), _p(labels_qry), h, w, _p(dense), n,
+                                              1 if exclude_own else 0, 1 if dist.shape[0] == 4 else 0, int(limit2), _p(best),
+                                              _st()), "dt_proximity_query")
+    return best
+
+
+def patch_proximity(labels_src: torch.Tensor, labels_qry: torch.Tensor, roots_qry, exclude_own: bool = False, limit2=None):
+    """nearest-patch distances between two label planes int32 [h, w] on one HIP device (``label_patches``, sieved or not;
+    contract in ``deployment/proximity.py``, csrc/proximity.hip): host int64 arrays ``(d2, nearest_root)`` with one entry per
+    element of ``roots_qry`` (the ascending roots of the query plane's table, a host array or a device tensor) — the smallest
+    squared distance between a pixel of the query patch and a labelled pixel of ``labels_src``, and the smallest root among
+    the source patches that reach it; ``-1, -1`` when there is none.  ``exclude_own``: source pixels that carry the query
+    pixel's own label do not count (``labels_src`` is ``labels_qry``: the gap to the nearest OTHER patch).  ``limit2`` (an
+    int >= 0, None: no limit): pairs with ``d2 > limit2`` do not count.  Neither plane is written; a non-contiguous view is
+    made contiguous.  Sides <= 16384, ``h * w <= 2**31 - 2``.
+
+    ``dt_proximity_columns`` (three launches: the column tables of ``labels_src``) -> ``dt_proximity_query`` (one launch:
+    outward search along the rows, 64-bit ``atomicMin`` per patch).  No scalar is read back — n is the length of
+    ``roots_qry`` — and the only download is the result; with n == 0 nothing is launched.  Workspace: the tables of
+    ``proximity_tables`` and 4 bytes per pixel for the root -> row plane"""
+    h, w, src, qry = _overlap_planes(labels_src, labels_qry, "patch_proximity")
+    if limit2 is not None and (isinstance(limit2, bool) or int(limit2) != limit2 or limit2 < 0):
+        raise RuntimeError(f"patch_proximity: limit2 must be an int >= 0 or None, got {limit2!r}")
+    if max(h, w) > 16384:
+        raise RuntimeError(f"patch_proximity: raster {h}x{w}: sides must be <= 16384 (column distances are uint16)")
+    roots = roots_qry if isinstance(roots_qry, torch.Tensor) else torch.tensor(roots_qry)     # a copy: the table's is read-only
+    if roots.dim() != 1 or roots.dtype not in (torch.int64, torch.int32):
+        raise RuntimeError(f"patch_proximity: roots_qry must be a one-dimensional integer array, got {roots.dtype} "
+                           f"{tuple(roots.shape)}")
+    n = int(roots.numel())
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int64).numpy(), torch.zeros(0, dtype=torch.int64).numpy()
+    if n > h * w:
+        raise RuntimeError(f"patch_proximity: {n} roots for {h * w} pixels")
+    roots = roots.to(src.device, torch.int64, non_blocking=True)
+    tables = proximity_tables(src, second=bool(exclude_own))
+    best = proximity_query(tables, qry, roots, bool(exclude_own), -1 if limit2 is None else int(limit2))
+    none = best < 0
+    out = torch.stack((torch.where(none, best, best >> 32), torch.where(none, best, best & 0xffffffff))).cpu().numpy()
+    return out[0], out[1]
 
 
 def signed_distmap(labels: torch.Tensor, K: int):
