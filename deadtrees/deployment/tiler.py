@@ -9,3 +9,5 @@ from deadtrees_amd.deployment.tiler import (PatchMatch, PatchOverlaps, PatchTrac
                                             patch_overlaps)  # (overlaps of two maps' patches)
 from deadtrees_amd.deployment.tiler import (PatchDistances, PatchGaps, ProximityConfig, patch_distances,  # noqa: F401
                                             patch_gaps, patch_proximity_host)  # (nearest-patch distances)
+from deadtrees_amd.deployment.tiler import (AttributeConfig, PatchAttributes, patch_attributes,  # noqa: F401
+                                            patch_attributes_host)  # (band statistics, indices and confidence per patch)

@@ -28,6 +28,7 @@
 #include <limits.h>
 
 #include "conv_host.h"
+#include "patch_runs.h"
 
 #define PT_TH 32                         // tile rows
 #define PT_TW 64                         // tile columns: one wave per tile row, 64 consecutive class bytes per load
@@ -168,25 +169,6 @@ __global__ __launch_bounds__(256) void patch_flatten_kernel(int32_t* lab, int64_
   if (i >= n || PT_LOAD(&lab[i]) == 0) return;
   const int root = pt_find(lab, (int)i);
   __hip_atomic_store(&lab[i], root + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// a label plane handed in by a caller: whatever is no label of an n-pixel plane counts as background, so that no index
-// derived from it leaves the planes
-__device__ __forceinline__ int pt_label_at(const int32_t* __restrict__ labels, int64_t i, int64_t n) {
-  if (i >= n) return 0;
-  const int label = labels[i];
-  return label > 0 && label <= n ? label : 0;
-}
-
-// ---------------------------------------------------------------- runs of equal labels in a wave
-// head: this lane starts a run (lane 0, another label than the lane before, or `brk`); len: the run's length, valid in
-// head lanes; heads: the ballot of head
-__device__ __forceinline__ void pt_runs(int label, bool brk, int lane, bool& head, int& len, uint64_t& heads) {
-  const int prev = __shfl_up(label, 1, 64);
-  head = lane == 0 || prev != label || brk;
-  heads = __ballot(head);
-  const uint64_t above = lane == 63 ? 0ull : heads >> (lane + 1);
-  len = above ? __ffsll((long long)above) : 64 - lane;
 }
 
 // area_plane[root] += pixels of that root.  A wave owns PT_SPAN * 64 consecutive pixels

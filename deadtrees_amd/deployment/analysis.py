@@ -1,7 +1,7 @@
 """What ``infer_tile`` / ``infer_rasters`` / ``Tiler.stats`` compute from a final class map — counts per zone, patch table,
-outlines, overlaps with another map, nearest-patch distances — as ONE request (``MapAnalysis``, the only place that checks the
-options' rules), one host runner and one device runner.  The results' contracts are those of ``stats`` / ``patches`` /
-``outlines`` / ``overlaps`` / ``proximity``."""
+outlines, overlaps with another map, nearest-patch distances, patch attributes — as ONE request (``MapAnalysis``, the only
+place that checks the options' rules), one host runner and one device runner.  The results' contracts are those of
+``stats`` / ``patches`` / ``outlines`` / ``overlaps`` / ``proximity`` / ``attributes``."""
 from __future__ import annotations
 
 from dataclasses import dataclass, replace
@@ -10,6 +10,7 @@ from typing import Optional
 import numpy as np
 
 from ..data.polygons import PolygonSet, rasterize
+from .attributes import AttributeConfig, attributes_of, check_attributes, check_raster
 from .patches import PatchConfig, check_patches, labelled_patches_host
 from .proximity import ProximityConfig, check_proximity, distances_of, gaps_of
 from .stats import MAX_ZONES, RasterStats, zonal_counts_host
@@ -80,7 +81,8 @@ class MapAnalysis:
     ``PatchTable``, or None; ``outlines``: the patches' outlines as well; ``against`` (array, ``PolygonSet`` or None) and
     ``against_patches``: the map the result is compared with, and its ``PatchConfig``; ``n_zones``: the caller's figure;
     ``distances`` / ``gaps``: the ``ProximityConfig`` of the distances to the patches of ``against`` / to the map's own other
-    patches, or None.
+    patches, or None; ``attributes``: the ``AttributeConfig`` of the patches' band statistics and confidence, or None — after
+    ``bind`` with the index pairs of that raster written out.
     ``rules`` checks what depends on no raster, ``bind`` the maps of one raster, ``of`` both; ``stats=False`` gives None"""
     K: Optional[int]
     zones: object = None
@@ -92,17 +94,21 @@ class MapAnalysis:
     n_zones: Optional[int] = None
     distances: Optional[ProximityConfig] = None
     gaps: Optional[ProximityConfig] = None
+    attributes: Optional[AttributeConfig] = None
 
     @classmethod
     def rules(cls, who: str, K, stats: bool = True, zones=None, n_zones=None, patches=None, outlines=None, against=None,
-              against_patches=None, distances=None, gaps=None) -> Optional["MapAnalysis"]:
+              against_patches=None, distances=None, gaps=None, attributes=None, no_probs: Optional[str] = None
+              ) -> Optional["MapAnalysis"]:
         """the options as ``infer_tile`` receives them -> a request without maps yet, or None without ``stats``; ``zones`` and
         ``against`` only say whether there are any (``infer_rasters`` passes its mappings).  ``ValueError``: an option without
-        ``stats``, outlines, ``against`` or ``gaps`` without patches, ``against_patches`` or ``distances`` without ``against``, a
-        value of a wrong type"""
+        ``stats``, outlines, ``against``, ``gaps`` or ``attributes`` without patches, ``against_patches`` or ``distances`` without
+        ``against``, a value of a wrong type, ``attributes`` with confidence in a call without probabilities (``no_probs``: what
+        the caller's path would need to have some; None: it has)"""
         config = check_patches(patches)
         try:
             distances, gaps = check_proximity(distances, "distances"), check_proximity(gaps, "gaps")
+            attributes = check_attributes(attributes)
         except ValueError as e:
             raise ValueError(f"{who}: {e}") from None
         if outlines is not None and not isinstance(outlines, bool):
@@ -118,9 +124,15 @@ class MapAnalysis:
                 raise ValueError(f"{who}: against / against_patches need stats=True")
             if distances is not None or gaps is not None:
                 raise ValueError(f"{who}: distances / gaps need stats=True")
+            if attributes is not None:
+                raise ValueError(f"{who}: attributes need stats=True")
             return None
         if gaps is not None and config is None:
             raise ValueError(f"{who}: gaps need patches (the gaps are those of the PatchTable's patches)")
+        if attributes is not None and config is None:
+            raise ValueError(f"{who}: attributes need patches (the attributes are those of the PatchTable's patches)")
+        if attributes is not None and attributes.confidence and no_probs is not None:
+            raise ValueError(f"{who}: attributes with confidence=True need probabilities ({no_probs})")
         if distances is not None and against is None:
             raise ValueError(f"{who}: distances need against (they are measured to the patches of that map)")
         if against is None:
@@ -133,42 +145,55 @@ class MapAnalysis:
         elif not isinstance(against_patches, PatchConfig):
             raise ValueError(f"{who}: against_patches must be a PatchConfig or None, got {against_patches!r}")
         return cls(K=K, patches=config, outlines=bool(outlines), against_patches=against_patches, n_zones=n_zones,
-                   distances=distances, gaps=gaps)
+                   distances=distances, gaps=gaps, attributes=attributes)
 
-    def bind(self, who: str, shape, zones=None, against=None) -> "MapAnalysis":
+    def bind(self, who: str, shape, zones=None, against=None, raster=None) -> "MapAnalysis":
         """the request of one raster of ``shape`` (h, w) and its maps, of the kinds ``rules`` was told of.  ``ValueError``: a map
-        off the grid, not uint8 or with a value out of range; ``n_zones`` that does not fit the zones; no class count"""
+        off the grid, not uint8 or with a value out of range; ``n_zones`` that does not fit the zones; no class count; with
+        ``attributes`` a ``raster`` ([C, h, w]: only its dtype and shape are read) that is missing, not uint8, off the grid, of
+        more than 8 bands, or without a band an index names"""
         zones, Z = check_zones(zones, shape, self.n_zones)
         if self.K is None:
             raise ValueError(f"{who}: stats=True needs an inference object with a `classes` count")
         against = None if against is None else check_against_map(against, shape, int(self.K), who)
-        return replace(self, K=int(self.K), zones=zones, Z=Z, against=against,
+        attributes = self.attributes
+        if attributes is not None:
+            if raster is None:
+                raise ValueError(f"{who}: attributes need the raster the map was made from")
+            try:
+                attributes = AttributeConfig(attributes.pairs(check_raster(raster, shape, "attributes")), attributes.confidence)
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from None
+        return replace(self, K=int(self.K), zones=zones, Z=Z, against=against, attributes=attributes,
                        against_patches=None if against is None else self.against_patches,
                        distances=None if against is None else self.distances)
 
     @classmethod
-    def of(cls, who: str, shape, K, zones=None, against=None, **options) -> Optional["MapAnalysis"]:
+    def of(cls, who: str, shape, K, zones=None, against=None, raster=None, **options) -> Optional["MapAnalysis"]:
         """``rules`` + ``bind``: the checked request of one raster, or None without ``stats``"""
         request = cls.rules(who, K, zones=zones, against=against, **options)
-        return None if request is None else request.bind(who, shape, zones, against)
+        return None if request is None else request.bind(who, shape, zones, against, raster)
 
     def device_planes(self, shape, device):
         """``(zones, against)`` as uint8 planes on ``device`` (None without one); polygons are burnt with ``all_touched=True``"""
         return map_plane(self.zones, shape, True, device), map_plane(self.against, shape, True, device)
 
 
-def run_host(request: MapAnalysis, result: np.ndarray):
+def run_host(request: MapAnalysis, result: np.ndarray, raster=None, probs=None):
     """``(map, RasterStats)`` of a uint8 [h, w] host map in numpy / scipy: ``map`` is ``result``, or its sieved copy when the
-    request sieves, and the counts are those of ``map``"""
+    request sieves, and the counts are those of ``map``.  ``raster`` (uint8 [C, h, w]) and ``probs`` (fp32 [K, h, w]): what the
+    request's ``attributes`` are read from, on the final label plane"""
     from .outlines import outlines_from_labels
     from .overlaps import PatchOverlaps, overlap_pairs_host
     K, config = request.K, request.patches
     zones = map_plane(request.zones, result.shape, True)
-    table = rings = pairs = gaps = None
+    table = rings = pairs = gaps = attributes = None
     if config is not None:
         result, labels, table = labelled_patches_host(result, K, config)
         if request.gaps is not None:
             gaps = gaps_of(labels, table, request.gaps.limit2)
+        if request.attributes is not None:
+            attributes = attributes_of(labels, table, raster, result, probs, request.attributes)
         if request.against is not None:
             _, labels_a, table_a = labelled_patches_host(map_plane(request.against, result.shape, True), K,
                                                          request.against_patches)
@@ -178,7 +203,7 @@ def run_host(request: MapAnalysis, result: np.ndarray):
         if request.outlines:
             rings = outlines_from_labels(labels, result, config.connectivity)
     counts = zonal_counts_host(np.ascontiguousarray(result), zones, K, request.Z)
-    return result, RasterStats(counts, patches=table, outlines=rings, overlaps=pairs, gaps=gaps)
+    return result, RasterStats(counts, patches=table, outlines=rings, overlaps=pairs, gaps=gaps, attributes=attributes)
 
 
 def device_labels(classes, K: int, config: PatchConfig, err=None, in_place: bool = False, areas: bool = True):
@@ -201,28 +226,31 @@ def device_patches(classes, K: int, config: PatchConfig, err):
     return labels, ops.patch_table(labels, classes, area, reuse_area_plane=True)
 
 
-def run_device(request: Optional[MapAnalysis], out, probs=None, planes=(None, None)):
+def run_device(request: Optional[MapAnalysis], out, probs=None, planes=(None, None), raster=None, return_probs: bool = True):
     """the end of every device path: the D2H copy of the final map ``out`` (uint8 [h, w], contiguous) and of the
     probabilities when there are any, with a request its ``RasterStats`` behind them: ``(map[, probs][, stats])`` as host
     arrays.  ``planes``: the request's ``device_planes``.  The order of the enqueued work is fixed: (1) with patches ``out``
     is labelled, measured and — if asked — sieved IN PLACE; (2) ONE ``ops.zonal_counts`` on ``out``, no synchronisation of
     its own; (3) with patches the map leaves by a pinned, non-blocking copy (without them by ``out.cpu()``); (4) the roots
     are compacted and measured behind it (``ops.patch_table`` reads the row count back), and with ``gaps`` one
-    ``ops.patch_proximity`` of the label plane against itself follows (no scalar read-back, its result is downloaded); (5)
+    ``ops.patch_proximity`` of the label plane against itself follows (no scalar read-back, its result is downloaded), and
+    with ``attributes`` one ``ops.patch_attributes`` of the final label plane over ``raster`` (the uploaded uint8 [C, h, w]
+    planes) and, with confidence, ``out`` and ``probs`` (no scalar read-back, its two tables are downloaded); (5)
     ``outlines`` traces the final label plane (two more scalar read-backs); (6) ``against`` is labelled, sieved on a clone if
     asked and tabled like ``out``, ``ops.patch_overlaps`` reads the two label planes (three more read-backs), and with
     ``distances`` two ``ops.patch_proximity`` calls, one per direction, read them again; (7) one stream synchronise, then
-    the counts and the ``err`` flag are read.  Without ``gaps`` / ``distances`` nothing of theirs is enqueued.  Workspace next
+    the counts and the ``err`` flag are read.  Without ``gaps`` / ``distances`` / ``attributes`` nothing of theirs is enqueued.
+    ``return_probs=False``: ``probs`` are there for the attributes only and stay on the device.  Workspace next
     to the map: about 12 bytes per pixel for the patches (labels, the area plane reused as the root -> row plane, the
     compaction's flags), as much again for ``against``; a proximity call holds 16 bytes per pixel while it runs (column
-    tables and the root -> row plane), 28 for ``gaps``"""
+    tables and the root -> row plane), 28 for ``gaps``; the attributes hold 4 (their root -> row plane)"""
     if request is None:
         return out.cpu().numpy() if probs is None else (out.cpu().numpy(), probs.cpu().numpy())
     import torch
     from .. import ops
     from .overlaps import PatchOverlaps
     K, config = request.K, request.patches
-    table = rings = pairs = gaps = None
+    table = rings = pairs = gaps = attributes = None
     err = torch.zeros(1, dtype=torch.int32, device=out.device)
     if config is not None:
         _, labels, area, _ = device_labels(out, K, config, err, in_place=True)
@@ -233,6 +261,8 @@ def run_device(request: Optional[MapAnalysis], out, probs=None, planes=(None, No
         table = ops.patch_table(labels, out, area, reuse_area_plane=True)
         if request.gaps is not None:
             gaps = gaps_of(labels, table, request.gaps.limit2, device=True)
+        if request.attributes is not None:
+            attributes = attributes_of(labels, table, raster, out, probs, request.attributes, device=True)
         if request.outlines:
             rings = ops.patch_outlines(labels, out, config.connectivity)
         if request.against is not None:
@@ -245,10 +275,11 @@ def run_device(request: Optional[MapAnalysis], out, probs=None, planes=(None, No
         result = (host.numpy(),)
     else:
         result = (out.cpu().numpy(),)
-    if probs is not None:
+    if probs is not None and return_probs:
         result += (probs.cpu().numpy(),)
     flag = int(err.cpu())
     if flag:          # cannot happen with checked zones: the map is an argmax over K classes
         raise RuntimeError(f"infer_tile: raster statistics met a value out of range (flag {flag}: 1 class >= {K}, "
                            f"2 zone >= {request.Z})")
-    return result + (RasterStats(counts.cpu().numpy(), patches=table, outlines=rings, overlaps=pairs, gaps=gaps),)
+    return result + (RasterStats(counts.cpu().numpy(), patches=table, outlines=rings, overlaps=pairs, gaps=gaps,
+                                 attributes=attributes),)

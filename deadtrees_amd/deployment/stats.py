@@ -70,9 +70,11 @@ class RasterStats:
     for with ``against`` (its ``table_a``) and this raster's patches (its ``table_b`` is ``patches``), else None; a sum of
     rasters has none.  ``gaps``: the ``PatchGaps`` (``deployment/proximity.py``: every patch's distance to the nearest other
     patch, aligned with ``patches``) when they were asked for, else None — then ``repr`` and ``==`` do not mention them; a sum
-    of rasters has none"""
+    of rasters has none.  ``attributes``: the ``PatchAttributes`` (``deployment/attributes.py``: band statistics, indices and
+    confidence per patch, aligned with ``patches``), handled like ``gaps``"""
 
-    def __init__(self, counts, pixel_area_m2: float = PIXEL_AREA_M2, patches=None, outlines=None, overlaps=None, gaps=None):
+    def __init__(self, counts, pixel_area_m2: float = PIXEL_AREA_M2, patches=None, outlines=None, overlaps=None, gaps=None,
+                 attributes=None):
         counts = np.array(counts, dtype=np.int64)
         if counts.ndim != 2 or counts.shape[0] < 1 or counts.shape[1] < 2:
             raise ValueError(f"RasterStats: counts must be [Z >= 1, K >= 2], got shape {counts.shape}")
@@ -107,6 +109,13 @@ class RasterStats:
             if patches is None or gaps.table != patches:
                 raise ValueError("RasterStats: gaps need the PatchTable they belong to")
         self._gaps = gaps
+        if attributes is not None:
+            from .attributes import PatchAttributes
+            if not isinstance(attributes, PatchAttributes):
+                raise ValueError(f"RasterStats: attributes must be a PatchAttributes or None, got {type(attributes).__name__}")
+            if patches is None or attributes.table != patches:
+                raise ValueError("RasterStats: attributes need the PatchTable they belong to")
+        self._attributes = attributes
 
     @property
     def patches(self):
@@ -123,6 +132,10 @@ class RasterStats:
     @property
     def gaps(self):
         return self._gaps
+
+    @property
+    def attributes(self):
+        return self._attributes
 
     @property
     def counts(self) -> np.ndarray:
@@ -171,6 +184,8 @@ class RasterStats:
             return False
         if (self._overlaps is None) != (other._overlaps is None) or (self._gaps is None) != (other._gaps is None):
             return False
+        if (self._attributes is None) != (other._attributes is None):
+            return False
         return (self._counts.shape == other._counts.shape and bool((self._counts == other._counts).all())
                 and self.pixel_area_m2 == other.pixel_area_m2
                 and (self._patches is None or self._patches == other._patches)
@@ -178,7 +193,8 @@ class RasterStats:
                     np.array_equal(getattr(self._outlines, a), getattr(other._outlines, a))
                     for a in ("xy", "ring_offsets", "ring_polygon", "values")))
                 and (self._overlaps is None or self._overlaps == other._overlaps)
-                and (self._gaps is None or self._gaps == other._gaps))
+                and (self._gaps is None or self._gaps == other._gaps)
+                and (self._attributes is None or self._attributes == other._attributes))
 
     __hash__ = None
 
@@ -190,6 +206,8 @@ class RasterStats:
             tail += f", overlaps={self._overlaps!r}"
         if self._gaps is not None:
             tail += f", gaps={self._gaps!r}"
+        if self._attributes is not None:
+            tail += f", attributes={self._attributes!r}"
         return f"RasterStats(counts={self._counts.tolist()}, pixel_area_m2={self.pixel_area_m2!r}{tail})"
 
 

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from .analysis import MapAnalysis, run_device, run_host
+from .attributes import AttributeConfig, PatchAttributes, patch_attributes, patch_attributes_host  # noqa: F401
 from .outlines import outlines_geojson, polygonize, polygonize_host, write_outlines_geojson  # noqa: F401
 from .overlaps import (PatchMatch, PatchOverlaps, PatchTracks, overlap_pairs_host, patch_overlaps)  # noqa: F401
 from .proximity import (PatchDistances, PatchGaps, ProximityConfig, patch_distances, patch_gaps,  # noqa: F401
@@ -243,21 +244,28 @@ class Tiler:
         return self._outdata[0:self._tile_info.size[0], 0:self._tile_info.size[1]]
 
     def stats(self, zones=None, classes: int = 3, n_zones: Optional[int] = None, patches=None, outlines=None,
-              against=None, against_patches=None, distances=None, gaps=None):
+              against=None, against_patches=None, distances=None, gaps=None, attributes=None):
         """``RasterStats`` of ``result``: what ``infer_tile(..., stats=True)`` returns, for a caller of the reference's own
         ``get_batches`` / ``put_batches`` loop, computed on the host (``analysis.run_host``).  ``classes``: the model's class
         count; ``zones`` / ``n_zones`` / ``patches`` / ``outlines`` / ``against`` / ``against_patches`` / ``distances`` /
-        ``gaps``: as in ``infer_tile``, with the same rules (``MapAnalysis``).  Polygons are burnt by ``rasterize_host``; a ``patches`` configuration that
-        sieves changes ``result`` itself, and the counts are those of the sieved map"""
+        ``gaps`` / ``attributes``: as in ``infer_tile``, with the same rules (``MapAnalysis``); the attributes are read from the
+        loaded raster, and the host path has no probabilities, so ``confidence=True`` is refused.  Polygons are burnt by
+        ``rasterize_host``; a ``patches`` configuration that sieves changes ``result`` itself, and the counts are those of the
+        sieved map"""
         if self._outdata is None:
             raise RuntimeError("Tiler: load_file / load_array first")
-        return self._analyse(MapAnalysis.of("Tiler.stats", self.result.shape, classes, zones, against, n_zones=n_zones,
-                                            patches=patches, outlines=outlines, against_patches=against_patches,
-                                            distances=distances, gaps=gaps))
+        return self._analyse(MapAnalysis.of("Tiler.stats", self.result.shape, classes, zones, against, self._raster(),
+                                            n_zones=n_zones, patches=patches, outlines=outlines,
+                                            against_patches=against_patches, distances=distances, gaps=gaps,
+                                            attributes=attributes, no_probs="Tiler.stats runs on the host, which has none"))
+
+    def _raster(self) -> np.ndarray:
+        """the loaded raster cropped to its own size: a view of the padded input"""
+        return self._indata[:, 0:self._tile_info.size[0], 0:self._tile_info.size[1]]
 
     def _analyse(self, request: MapAnalysis):
         """the ``RasterStats`` of ``result`` under a checked request (``analysis.run_host``); a sieved map replaces ``result``"""
-        sieved, stats = run_host(request, self.result)
+        sieved, stats = run_host(request, self.result, raster=self._raster())
         if request.patches is not None and request.patches.sieves:
             self.result[...] = sieved                            # a view into ``_outdata``
         return stats
@@ -275,28 +283,29 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
                   device: str = "cuda", tile_shape: Optional[Tuple[int, int]] = None, skip_blank: bool = True,
                   overlap: int = 0, blend: str = "crop", return_probs: bool = False, tta=None, stats: bool = False,
                   zones=None, n_zones: Optional[int] = None, patches=None, outlines=None, against=None,
-                  against_patches=None, distances=None, gaps=None):
+                  against_patches=None, distances=None, gaps=None, attributes=None):
     """the directory loop of scripts/inference.py:71-115 over in-memory rasters (GeoTIFF I/O needs rioxarray, absent
     here): ``rasters`` yields ``array`` or ``(key, array)``; rank r of ``world`` takes rasters r, r + world, ... (tiles are
     independent: no collective).  Yields ``(key, class_map)`` in input order of the rank's share; rasters whose band 1
     holds only 0 / 255 (``is_valid_tile``, :60-62) are skipped like the reference does — ``(key, None)`` — without a
     forward pass (device reduction over the uploaded raster, ``ops.band_has_data``).  ``overlap`` / ``blend`` /
     ``return_probs`` / ``tta`` / ``stats`` / ``n_zones`` / ``patches`` / ``outlines`` / ``against_patches`` / ``distances`` /
-    ``gaps``: as in ``infer_tile``, with the same rules, checked before the first raster is read (every raster stays on its rank, so
-    overlap needs no exchange); ``zones``: a callable ``key -> uint8 [h, w] array, PolygonSet or None``, or a mapping (a
-    missing key is None); ``against``: the same for the map every raster is compared with (a uint8 array, a ``PolygonSet``
+    ``gaps`` / ``attributes``: as in ``infer_tile``, with the same rules, checked before the first raster is read (every raster
+    stays on its rank, so overlap needs no exchange); ``zones``: a callable ``key -> uint8 [h, w] array, PolygonSet or None``,
+    or a mapping (a missing key is None); ``against``: the same for the map every raster is compared with (a uint8 array, a ``PolygonSet``
     or None: that raster's statistics carry no overlaps).
     The second item of every pair is whatever ``infer_tile`` returned: with ``stats=True`` ``(map, RasterStats)`` — the
     ``RasterStats`` of a rank's share add up (``+``) to that rank's part of the regional totals."""
     rules = MapAnalysis.rules("infer_rasters", getattr(inference, "classes", None) if stats else None, stats, zones, n_zones,
-                              patches, outlines, against, against_patches, distances, gaps)
+                              patches, outlines, against, against_patches, distances, gaps, attributes,
+                              _no_probs(inference, overlap, blend, tta))
     for i, item in enumerate(rasters):
         if i % world != rank:
             continue
         key, arr = item if isinstance(item, tuple) else (i, item)
         z = None if zones is None else zones(key) if callable(zones) else zones.get(key)
         other = None if against is None else against(key) if callable(against) else against.get(key)
-        request = None if rules is None else rules.bind("infer_tile", np.shape(arr)[1:], z, other)
+        request = None if rules is None else rules.bind("infer_tile", np.shape(arr)[1:], z, other, arr)
         yield key, _infer_tile(inference, arr, request, subtile, batch_size, 0, 1, device, None, tile_shape, None, skip_blank,
                                overlap, blend, return_probs, tta)
 
@@ -305,7 +314,8 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
                world: int = 1, device: str = "cuda", group=None, tile_shape: Optional[Tuple[int, int]] = None,
                on_device: Optional[bool] = None, skip_blank: bool = False, overlap: int = 0, blend: str = "crop",
                return_probs: bool = False, tta=None, stats: bool = False, zones=None, n_zones: Optional[int] = None,
-               patches=None, outlines=None, against=None, against_patches=None, distances=None, gaps=None):
+               patches=None, outlines=None, against=None, against_patches=None, distances=None, gaps=None,
+               attributes=None):
     """whole-tile inference of scripts/inference.py:80-115 on the MI355X path: split -> (uint8 H2D, normalise on the
     device) -> forward + fused argmax -> uint8 D2H -> merge.  With world > 1 the sub-tile batches j = rank (mod world)
     are processed locally and the uint8 class maps are all-gathered (no other collective: tiles are independent).
@@ -363,12 +373,33 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     spread distance of a ``NEW`` patch from last year's dead trees.  ``gaps=True`` or a ``ProximityConfig`` (needs
     ``patches``): ``.gaps`` is a ``PatchGaps`` aligned with ``.patches`` — every patch's distance to the nearest OTHER patch
     of the map.  ``max_distance`` (pixels) bounds the search: a patch farther than that from everything has no neighbour.
-    Everything else is that of the call without the two options."""
+    Everything else is that of the call without the two options.
+
+    ``attributes=True`` or an ``AttributeConfig(indices=None, confidence=False)`` (needs ``patches``; a uint8 raster of at most
+    8 bands): ``.attributes`` is a ``PatchAttributes`` (``deployment/attributes.py``) aligned with ``.patches`` — per patch and
+    band the sum, sum of squares, minimum and maximum of the raster's pixels (``mean()``, ``std()``), per index pair the mean
+    normalised difference (``index(k)``; default NDVI = bands (3, 0) of an RGBN raster), all from the final, sieved label
+    plane.  On the device paths ALL bands of the raster are uploaded, still in one copy, and the network reads its leading
+    ``in_channels`` planes: an RGB model over an RGBN raster still yields NDVI.  ``confidence=True`` adds the mean and the
+    minimum probability of the patch's class (``confidence()``, ``min_confidence()``); it is accepted exactly where
+    ``return_probs=True`` is, and without ``return_probs`` the probabilities stay on the device.  Everything else is that of
+    the call without the option."""
     request = MapAnalysis.of("infer_tile", np.shape(arr_chw_u8)[1:], getattr(inference, "classes", None) if stats else None,
-                             zones, against, stats=stats, n_zones=n_zones, patches=patches, outlines=outlines,
-                             against_patches=against_patches, distances=distances, gaps=gaps)
+                             zones, against, arr_chw_u8, stats=stats, n_zones=n_zones, patches=patches, outlines=outlines,
+                             against_patches=against_patches, distances=distances, gaps=gaps, attributes=attributes,
+                             no_probs=_no_probs(inference, overlap, blend, tta))
     return _infer_tile(inference, arr_chw_u8, request, subtile, batch_size, rank, world, device, group, tile_shape, on_device,
                        skip_blank, overlap, blend, return_probs, tta)
+
+
+def _no_probs(inference, overlap, blend, tta) -> Optional[str]:
+    """what a call lacks to have raster probabilities — the rule of ``return_probs`` — or None when it has them"""
+    members = getattr(inference, "members", None)
+    if not (overlap or tta is not None or members is not None):
+        return "return_probs needs overlap > 0 and blend='average'"
+    if blend != "average" or (members is not None and getattr(inference, "vote", "hard") == "hard"):
+        return "return_probs needs blend='average' and, for an ensemble, vote='soft'"
+    return None
 
 
 def _infer_tile(inference, arr_chw_u8, request: Optional[MapAnalysis], subtile, batch_size, rank, world, device, group,
@@ -384,8 +415,8 @@ def _infer_tile(inference, arr_chw_u8, request: Optional[MapAnalysis], subtile, 
             raise ValueError("infer_tile: overlap stitching, test-time augmentation and ensembles are the single-rank form "
                              "(shard by raster: infer_rasters)")
         vote = getattr(inference, "vote", "hard") if members is not None else None
-        if return_probs and (blend != "average" or vote == "hard"):
-            raise ValueError("infer_tile: return_probs needs blend='average' and, for an ensemble, vote='soft'")
+        if return_probs and _no_probs(inference, overlap, blend, tta):
+            raise ValueError("infer_tile: " + _no_probs(inference, overlap, blend, tta))
         models = list(members) if members is not None else [inference]
         if on_device is False or not all(hasattr(m, "run_windows") for m in models):
             raise ValueError("infer_tile: overlap stitching, test-time augmentation and ensembles run on the device and need "
@@ -395,7 +426,7 @@ def _infer_tile(inference, arr_chw_u8, request: Optional[MapAnalysis], subtile, 
         return _infer_tile_stitched(inference, models, vote, arr_chw_u8, subtile, overlap, blend, batch_size, device,
                                     skip_blank, return_probs, views, request)
     if return_probs:
-        raise ValueError("infer_tile: return_probs needs overlap > 0 and blend='average'")
+        raise ValueError("infer_tile: " + _no_probs(inference, overlap, blend, tta))
     if tile_shape is None:
         h, w = arr_chw_u8.shape[1], arr_chw_u8.shape[2]
         if h <= 2048 and w <= 2048 and 2048 % subtile == 0:
@@ -431,7 +462,7 @@ def _infer_tile(inference, arr_chw_u8, request: Optional[MapAnalysis], subtile, 
                 outs[j] = o
     t.put_batches(np.concatenate(outs, axis=0))
     if request is not None:
-        st = t._analyse(request)            # before the map is read: a sieve changes it
+        st = t._analyse(request)            # before the map is read: a sieve changes it; attributes read t's raster
         return t.result, st
     return t.result
 
@@ -439,18 +470,24 @@ def _infer_tile(inference, arr_chw_u8, request: Optional[MapAnalysis], subtile, 
 def _upload(inference, arr_chw_u8: np.ndarray, device: str, skip_blank: bool, request: Optional[MapAnalysis]):
     """the start of every device path: ONE uint8 H2D copy of the band planes the network reads (the N of an RGBN raster
     under an RGB model stays on the host), the request's maps next to it (``MapAnalysis.device_planes``) and ``skip_blank``'s
-    ``is_valid_tile`` on the device: ``(raster, (zones, against))``, or None for a raster with only 0 / 255 in band 1"""
+    ``is_valid_tile`` on the device: ``(x, (zones, against), raster)``, or None for a raster with only 0 / 255 in band 1.  With
+    ``attributes`` the one copy carries ALL bands: ``raster`` is that tensor and ``x`` the view of its leading planes the network
+    reads; without them ``raster`` is None"""
     C = arr_chw_u8.shape[0]
     nch = int(getattr(inference, "in_channels", C) or C)
-    if 0 < nch < C:
+    everything = request is not None and request.attributes is not None
+    if 0 < nch < C and not everything:
         arr_chw_u8 = arr_chw_u8[:nch]
     x = torch.from_numpy(np.ascontiguousarray(arr_chw_u8)).to(device, non_blocking=True)
+    raster = x if everything else None
+    if everything and 0 < nch < C:
+        x = x[:nch]
     planes = (None, None) if request is None else request.device_planes(arr_chw_u8.shape[1:], x.device)
     if skip_blank:
         from .. import ops
         if int(ops.band_has_data(x[0])) == 0:
             return None
-    return x, planes
+    return x, planes, raster
 
 
 def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch_size: int, device: str,
@@ -469,7 +506,7 @@ def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch
     up = _upload(inference, arr_chw_u8, device, skip_blank, request)
     if up is None:
         return None
-    x, planes = up
+    x, planes, raster = up
     C = x.shape[0]
     if hasattr(inference, "run_blocks"):
         # round 3: split + zero padding + Normalize + NHWC in one gather per batch (dt_split_normalize_u8), no ATen passes
@@ -483,7 +520,7 @@ def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch
         outs = [inference.run_u8(blocks[j:j + batch_size], device=device) for j in range(0, nby * nbx, batch_size)]
     maps = (outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)).to(torch.uint8)
     merged = maps.view(nby, nbx, d, d).permute(0, 2, 1, 3).reshape(nby * d, nbx * d)
-    return run_device(request, merged[:h, :w].contiguous(), None, planes)
+    return run_device(request, merged[:h, :w].contiguous(), None, planes, raster)
 
 
 def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.ndarray, d: int, overlap: int, blend: str,
@@ -506,7 +543,8 @@ def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.
     up = _upload(inference, arr_chw_u8, device, skip_blank, request)
     if up is None:
         return None
-    x, planes = up
+    x, planes, raster = up
+    want_probs = return_probs or (request is not None and request.attributes is not None and request.attributes.confidence)
     kw = {} if views is None else {"views": views}   # a duck-typed run_windows without TTA need not take the keyword
     per = batch_size if views is None else max(1, batch_size // len(views))     # batch_size counts forward tiles
     weight = "ramp" if blend == "average" else "keep"
@@ -527,15 +565,15 @@ def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.
             return out
         return ops.stitch_finalize(accumulate(model, None))
 
-    if vote != "soft" and not return_probs:          # one map per model (return_probs under a hard vote was refused)
+    if vote != "soft" and not want_probs:            # one map per model (probabilities under a hard vote were refused)
         maps = [class_map(m) for m in models]
         if len(maps) > 1:
             maps = [ops.ensemble_vote(torch.stack(maps, dim=0), int(inference.classes), dtype="uint8")[0]]
-        return run_device(request, maps[0], None, planes)
+        return run_device(request, maps[0], None, planes, raster)
     acc = None
     for m in models:
         acc = accumulate(m, acc)
-    if return_probs:
+    if want_probs:
         classes, probs = ops.stitch_finalize(acc, want_probs=True)
-        return run_device(request, classes, probs, planes)
-    return run_device(request, ops.stitch_finalize(acc), None, planes)
+        return run_device(request, classes, probs, planes, raster, return_probs)
+    return run_device(request, ops.stitch_finalize(acc), None, planes, raster)

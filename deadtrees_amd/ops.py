@@ -1135,10 +1135,10 @@ def rasterize_polygons(edges: torch.Tensor, polys: torch.Tensor, shape, all_touc
 # constants asked of the library on first use -> (getter, count).  PATCH_TILE = (th, tw): the tile of dt_label_patches_u8's
 # local launch; OUTLINE_CHUNK / OVERLAP_CHUNK: the consecutive pixels one workgroup of dt_outline_count / dt_overlap_count takes;
 # PROXIMITY_SEGMENT: the rows of one column segment of dt_proximity_columns; PROXIMITY_WINDOW: the pixels of one row that a
-# workgroup of dt_proximity_query takes
+# workgroup of dt_proximity_query takes; ATTRIBUTE_SPAN: the consecutive 64-pixel chunks a wave of dt_patch_attributes_u8 takes
 _LIB_CONSTANTS = {"PATCH_TILE": ("dt_patch_tile", 2), "OUTLINE_CHUNK": ("dt_outline_chunk", 1),
                   "OVERLAP_CHUNK": ("dt_overlap_chunk", 1), "PROXIMITY_SEGMENT": ("dt_proximity_segment", 1),
-                  "PROXIMITY_WINDOW": ("dt_proximity_window", 1)}
+                  "PROXIMITY_WINDOW": ("dt_proximity_window", 1), "ATTRIBUTE_SPAN": ("dt_attribute_span", 1)}
 
 
 def _constant(name: str):
@@ -1433,6 +1433,69 @@ def patch_proximity(labels_src: torch.Tensor, labels_qry: torch.Tensor, roots_qr
     none = best < 0
     out = torch.stack((torch.where(none, best, best >> 32), torch.where(none, best, best & 0xffffffff))).cpu().numpy()
     return out[0], out[1]
+
+
+def patch_attributes(labels: torch.Tensor, roots, raster_u8: torch.Tensor, classes_u8: torch.Tensor = None,
+                     probs: torch.Tensor = None, indices=()):
+    """the attribute tables of the patches of a label plane int32 [h, w] on a HIP device (``label_patches``, sieved or not)
+    over a planar raster uint8 [C, h, w] on its grid, 1 <= C <= 8 (contract in ``deployment/attributes.py``,
+    csrc/attributes.hip): host arrays ``(sums int64 [n, Q], extremes int32 [n, M])`` in the layout of
+    ``attributes.table_columns``, one row per element of ``roots`` (the ascending roots of the plane's table, a host array or a
+    device tensor).  ``indices``: up to 4 band pairs ``(a, b)``, bands < C.  ``classes_u8`` uint8 [h, w] and ``probs`` fp32
+    [K, h, w]: both or neither; with them the sum and the minimum of the quantised probability of every pixel's own class.
+    No input is written; a non-contiguous view is made contiguous, a contiguous one is read where it lies.  Sides <= 16384,
+    ``h * w <= 2**31 - 2``.
+
+    ``dt_patch_attributes_u8``: one init launch, one pass over the pixels with one integer atomic per quantity and run of
+    equal labels.  No scalar is read back — n is the length of ``roots`` — and the two tables are the only downloads; with
+    n == 0 nothing is launched.  Workspace: 4 bytes per pixel for the root -> row plane"""
+    h, w = _patch_planes("patch_attributes", labels=labels)
+    dev = labels.device
+    if max(h, w) > 16384 or h * w > 2 ** 31 - 2:
+        raise RuntimeError(f"patch_attributes: raster {h}x{w}: sides must be <= 16384 and h * w <= {2 ** 31 - 2}")
+    _gpu(raster_u8)
+    if (raster_u8.dtype != torch.uint8 or raster_u8.dim() != 3 or tuple(raster_u8.shape[1:]) != (h, w)
+            or not 1 <= raster_u8.shape[0] <= 8 or raster_u8.device != dev):
+        raise RuntimeError(f"patch_attributes: raster must be uint8 [C, {h}, {w}] with 1 <= C <= 8 on {dev}, got "
+                           f"{raster_u8.dtype} {tuple(raster_u8.shape)}")
+    C_ = int(raster_u8.shape[0])
+    pairs = [(int(a), int(b)) for a, b in indices]
+    if len(pairs) > 4 or any(not (0 <= a < C_ and 0 <= b < C_) for a, b in pairs):
+        raise RuntimeError(f"patch_attributes: indices must be at most 4 pairs of bands below {C_}, got {pairs}")
+    if (classes_u8 is None) != (probs is None):
+        raise RuntimeError("patch_attributes: probabilities come with their class map (classes_u8 and probs: both or neither)")
+    K = 0
+    if probs is not None:
+        _patch_planes("patch_attributes", classes_u8, labels=labels)
+        _gpu(probs)
+        if (probs.dtype != torch.float32 or probs.dim() != 3 or tuple(probs.shape[1:]) != (h, w)
+                or not 2 <= probs.shape[0] <= 8 or probs.device != dev):
+            raise RuntimeError(f"patch_attributes: probs must be float32 [K, {h}, {w}] with 2 <= K <= 8 on {dev}, got "
+                               f"{probs.dtype} {tuple(probs.shape)}")
+        K = int(probs.shape[0])
+        classes_u8, probs = classes_u8.contiguous(), probs.contiguous()
+    roots = roots if isinstance(roots, torch.Tensor) else torch.tensor(roots)          # a copy: the table's is read-only
+    if roots.dim() != 1 or roots.dtype not in (torch.int64, torch.int32):
+        raise RuntimeError(f"patch_attributes: roots must be a one-dimensional integer array, got {roots.dtype} "
+                           f"{tuple(roots.shape)}")
+    n = int(roots.numel())
+    if n > h * w:
+        raise RuntimeError(f"patch_attributes: {n} roots for {h * w} pixels")
+    conf = probs is not None
+    Q, M = 2 * C_ + len(pairs) + conf, 2 * C_ + conf
+    if n == 0:
+        return torch.zeros((0, Q), dtype=torch.int64).numpy(), torch.zeros((0, M), dtype=torch.int32).numpy()
+    roots = roots.to(dev, torch.int64, non_blocking=True)
+    dense = torch.full((h * w + 1,), -1, dtype=torch.int32, device=dev)      # the last entry takes the roots off the raster
+    on_grid = (roots >= 0) & (roots < h * w)
+    dense[torch.where(on_grid, roots, h * w)] = torch.arange(n, dtype=torch.int32, device=dev)
+    sums = torch.empty((n, Q), dtype=torch.int64, device=dev)
+    extremes = torch.empty((n, M), dtype=torch.int32, device=dev)
+    flat = (C.c_int * max(1, 2 * len(pairs)))(*[v for pair in pairs for v in pair])
+    _lib.check(_lib.load().dt_patch_attributes_u8(_p(labels.contiguous()), _p(raster_u8.contiguous()), C_, h, w, _p(dense), n,
+                                                  _p(classes_u8), _p(probs), K, flat, len(pairs), _p(sums), _p(extremes),
+                                                  _st()), "dt_patch_attributes_u8")
+    return sums.cpu().numpy(), extremes.cpu().numpy()
 
 
 def signed_distmap(labels: torch.Tensor, K: int):

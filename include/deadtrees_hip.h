@@ -557,6 +557,25 @@ int dt_proximity_query(const uint16_t* dist, const int32_t* nearest, const int32
                        int w, const int32_t* dense_plane, int n, int exclude_own, int second, int64_t limit2, uint64_t* best,
                        void* stream);
 
+/* Patch attributes (deployment/attributes.py states the contract): what the patches of a label plane look like in a raster
+ * on the same grid and how sure the model was.  labels int32 [h][w] (dt_label_patches_u8, sieved or not; a value outside
+ * 1 .. h * w is background), raster uint8 [C][h][w] planar, 1 <= C <= 8, dense_plane int32 [h * w]: root -> table row as
+ * dt_patch_measure takes it (a row outside 0 .. n - 1: no row), all in device memory; sides <= 16384, h * w <= 2^31 - 2.
+ * pairs: HOST array of n_pairs <= 4 band pairs (a, b), bands < C.  classes uint8 [h][w] and probs fp32 [K][h][w], 2 <= K <= 8:
+ * both or neither (NULL); a class >= K counts as probability 0.
+ * Per table row, over the pixels that carry its label (integers only, so the tables are a pure function of the inputs):
+ *   sums int64 [n][Q], Q = 2 C + n_pairs + (probs ? 1 : 0): the C band sums, the C sums of squares, per pair the sum of
+ *     t = (v_a * 65534 + (s >> 1)) / s with s = v_a + v_b (unsigned; 32767 for s == 0), then the sum of
+ *     q = floor(min(max(p, 0), 1) * 65535 + 0.5) over p = probs[classes[i]][i], product and sum each rounded to fp32, NaN -> 0;
+ *   extremes int32 [n][M], M = 2 C + (probs ? 1 : 0): the C band minima, the C band maxima, then the minimum of q.
+ * Two launches: one presets the rows (sums 0, minima 255 / 65535, maxima 0), one walks the pixels: a wave takes
+ * dt_attribute_span consecutive 64-pixel chunks, reduces every quantity per run of equal labels and issues one integer atomic
+ * per quantity and finished run.  n == 0 launches nothing.  No synchronisation, no input is written. */
+int dt_attribute_span(int* chunks);
+int dt_patch_attributes_u8(const int32_t* labels, const uint8_t* raster, int C, int h, int w, const int32_t* dense_plane,
+                           int n, const uint8_t* classes, const float* probs, int K, const int* pairs, int n_pairs,
+                           int64_t* sums, int32_t* extremes, void* stream);
+
 /* Training samples from an ortho raster (the array arithmetic of scripts/createdataset.py:53-194 and
  * scripts/computestats.py:111-161; deadtrees_amd/data/rasters.py states the contract in numpy).  rgbn_chw uint8 [4][h][w]
  * with 1 <= h, w <= S is the top-left corner of a zero [4][S][S] array; mask / lu uint8 [h][w] are padded the same way.
