@@ -14,6 +14,7 @@ import torch
 
 from ..data.synthetic import MEAN, STD
 from ..network.segmodel import SemSegment
+from ..utils.graph_replay import GraphReplay, ReplayCache
 from .. import ops
 
 
@@ -173,7 +174,7 @@ class PyTorchEnsembleInference:
 
 class GraphedTilePredictor:
     """uint8 NHWC tiles -> uint8 class maps with the whole chain (normalise, U-Net forward, argmax) replayed as ONE
-    HIP graph per batch shape: ~120 Python launches per batch become one, which keeps the tile queue of
+    HIP graph per batch shape (``utils.graph_replay``): ~120 Python launches per batch become one, which keeps the tile queue of
     scripts/inference.py:80-115 independent of host jitter (eight ranks sharing a node).  On an idle host the eager
     chain is already GPU-bound (bench.py --mode infer: same rate with and without the graph).  The returned tensor is the graph's static output: consume or copy it before the next
     call.  Weights are read from the engine's cached images, so a model whose parameters change must run one eager
@@ -182,27 +183,16 @@ class GraphedTilePredictor:
     def __init__(self, model, in_channels: int = 3, precision: str = "fp32"):
         self.model, self.c, self.precision = model, in_channels, precision
         self.in_channels = in_channels
-        self._graphs = {}
+        self._replays = ReplayCache(keep_all=True)
 
     def _eager(self, tiles_u8):
         x = ops.normalize_u8(tiles_u8, MEAN, STD, self.c)
         return self.model.predict_classes(x, dtype="uint8", precision=self.precision, nhwc=True)
 
     def __call__(self, tiles_u8: torch.Tensor) -> torch.Tensor:
-        key = (tuple(tiles_u8.shape), tiles_u8.device)
-        g = self._graphs.get(key)
-        if g is None:
-            eng = self.model.engine
-            self._eager(tiles_u8)                      # warm-up: lazy initialisation + weight images packed eagerly
-            g = {"inp": tiles_u8.clone()}
-            graph = torch.cuda.CUDAGraph()
-            # activations / scratch of the capture live in the graph's pool; the bf16 weight images packed eagerly stay
-            with eng.capture_workspaces(keep=("bf16_w",)) as g["ws"]:
-                torch.cuda.synchronize()
-                with torch.cuda.graph(graph):
-                    g["out"] = self._eager(g["inp"])
-            g["graph"] = graph
-            self._graphs[key] = g
-        g["inp"].copy_(tiles_u8)
-        g["graph"].replay()
-        return g["out"]
+        # activations / scratch of the capture live in the graph's pool; the bf16 weight images packed eagerly stay
+        r = self._replays.get((tuple(tiles_u8.shape), tiles_u8.device),
+                              lambda: GraphReplay(self.model.engine, self._eager, warmup=1, keep=("bf16_w",)))
+        if not r.captured:
+            r(tiles_u8)                                # warm-up: lazy initialisation + weight images packed eagerly
+        return r(tiles_u8)                             # (first call of a key: capture;) copy in, replay

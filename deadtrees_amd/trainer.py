@@ -14,7 +14,8 @@ import json
 import math
 import os
 from dataclasses import dataclass
-from typing import Callable, Dict, List, Optional, Sequence
+from functools import partial
+from typing import Callable, List, Optional, Sequence
 
 import torch
 
@@ -22,6 +23,7 @@ from .data.distmap import distmaps_on_device
 from .loss.seg_loss import PART_KEYS, loss_algebra, loss_backward, loss_forward
 from .network.unet import UNetHIP
 from .ops import FlatAdam, WeightAverager, confusion_matrix, eval_accumulate
+from .utils.graph_replay import GraphReplay, ReplayCache
 
 
 class GradReducer:
@@ -61,7 +63,7 @@ class HipTrainer:
         average is local to each rank: ranks hold equal parameters, hence equal averages, and no collective runs.
         graph=True: after two eager steps the whole step (forward, loss, backward, clip, Adam) is captured into a
         HIP graph and replayed — ~750 kernel launches become one, which matters once the bf16 step is shorter than
-        the Python launch path."""
+        the Python launch path.  Warm-up, capture and replay are ``utils.graph_replay``'s."""
         if getattr(model, "inference_only", False):
             model._require_trainable("HipTrainer (missing backward path)")
         if not model.flat_params.is_cuda:
@@ -82,10 +84,10 @@ class HipTrainer:
         # with distributed=True the bucketed RCCL all-reduces are captured too (rehearsed at world size 1 on RCCL 2.26;
         # bench.py keeps multi-GPU runs eager until that has run on a real 8-GPU node)
         self.use_graph = bool(graph)
-        self._graph = None
+        self._step_replays = ReplayCache(keep_all=False)    # new shapes / loss blend: drop the old graph, warm up again
         self.averager = None if average is None else WeightAverager(model.flat_params.data, average)
-        self._recal_graph = None
-        self._val_graphs: Dict = {}      # validation batches: one captured graph per key (shapes, precision, loss set)
+        self._recal_replays = ReplayCache(keep_all=False)
+        self._val_replays = ReplayCache(keep_all=True)      # one captured graph per key (shapes, precision, loss set)
         self._val_state = None           # device accumulators of a validation epoch (the captured graphs write them)
 
     @torch.no_grad()
@@ -127,25 +129,10 @@ class HipTrainer:
         return k
 
     def _recal_graph_batch(self, x: torch.Tensor, precision: str):
-        m, eng = self.model, self.model.engine
-        key = (tuple(x.shape), precision)
-        g = self._recal_graph
-        if g is None or g["key"] != key:
-            self._recal_graph = g = {"key": key, "warm": 0}
-        if "graph" not in g:
-            if g["warm"] < 2:    # eager warm-up: lazy initialisation (workspaces) must not be captured
-                g["warm"] += 1
-                return m.recalibrate_batch(x, precision)
-            g["x"] = x.clone()
-            graph = torch.cuda.CUDAGraph()
-            with eng.capture_workspaces() as g["ws"]:   # workspaces of the captured pass live (and stay) in the graph's pool
-                torch.cuda.synchronize()
-                with torch.cuda.graph(graph):
-                    m.recalibrate_batch(g["x"], precision)
-            g["graph"] = graph
-        if x is not g["x"]:
-            g["x"].copy_(x)
-        g["graph"].replay()
+        """``recalibrate_batch`` through ``GraphReplay``: two eager batches, then one graph per (shape, precision)"""
+        m = self.model
+        self._recal_replays.get((tuple(x.shape), precision), lambda: GraphReplay(
+            m.engine, lambda x: m.recalibrate_batch(x, precision), warmup=2))(x)
 
     # ------------------------------------------------------------------ validation epoch
     def _val_buffers(self):
@@ -157,7 +144,7 @@ class HipTrainer:
             st = self._val_state = {"epoch": torch.zeros(9, dtype=torch.float64, device=dev),
                                     "counts": torch.zeros((2, K, K), dtype=torch.int64, device=dev),
                                     "err": torch.zeros(1, dtype=torch.int32, device=dev)}
-            self._val_graphs = {}
+            self._val_replays.clear()
         return st
 
     def _val_batch(self, img, mask, lu, distmap, alpha):
@@ -188,31 +175,16 @@ class HipTrainer:
         eval_accumulate(parts, float(B), st["epoch"])
 
     def _val_graph_batch(self, img, mask, lu, distmap, alpha):
-        """``_val_batch`` through a captured graph per key, after two eager batches of that key (written the way
-        ``_recal_graph_batch`` is; a validation set whose last batch is smaller keeps one graph per batch size)"""
+        """``_val_batch`` through ``GraphReplay``: a captured graph per key, after two eager batches of that key (a
+        validation set whose last batch is smaller keeps one graph per batch size).  alpha is baked into the captured
+        blend: it belongs to the key where it is read (BOUNDARY-RAMPED)"""
         key = (tuple(img.shape), img.dtype, tuple(mask.shape), mask.dtype,
                None if lu is None else (tuple(lu.shape), lu.dtype),
                None if distmap is None else (tuple(distmap.shape), distmap.dtype),
                self.model.precision, self.losses, float(alpha) if "BOUNDARY-RAMPED" in self.losses else None)
         self._val_buffers()              # (a moved model drops the graphs)
-        g = self._val_graphs.setdefault(key, {"warm": 0})
-        if "graph" not in g:
-            if g["warm"] < 2:    # eager warm-up: lazy initialisation (workspaces, device tables) must not be captured
-                g["warm"] += 1
-                return self._val_batch(img, mask, lu, distmap, alpha)
-            g["img"], g["mask"] = img.clone(), mask.clone()
-            g["lu"] = None if lu is None else lu.clone()
-            g["distmap"] = None if distmap is None else distmap.clone()
-            graph = torch.cuda.CUDAGraph()
-            with self.model.engine.capture_workspaces() as g["ws"]:
-                torch.cuda.synchronize()
-                with torch.cuda.graph(graph):
-                    self._val_batch(g["img"], g["mask"], g["lu"], g["distmap"], alpha)
-            g["graph"] = graph
-        for name, t in (("img", img), ("mask", mask), ("lu", lu), ("distmap", distmap)):
-            if t is not None and t is not g[name]:
-                g[name].copy_(t)
-        g["graph"].replay()
+        self._val_replays.get(key, lambda: GraphReplay(
+            self.model.engine, lambda *batch: self._val_batch(*batch, alpha), warmup=2))(img, mask, lu, distmap)
 
     @torch.no_grad()
     def validate(self, loader, to_device=None, stage: str = "val", alpha: float = 1.0) -> dict:
@@ -288,52 +260,33 @@ class HipTrainer:
                None if distmap is None else tuple(distmap.shape),
                float(alpha) if "BOUNDARY-RAMPED" in self.losses else None,
                self.model.encoder_frozen, self.model.encoder.training or not self.model.training)
-        g = self._graph
-        if g is None or g["key"] != key:
-            self._graph = g = {"key": key, "warm": 0}     # new shapes / loss blend: drop the old graph, warm up again
-        if "graph" not in g:
-            if g["warm"] < 2:    # eager warm-up: lazy initialisation (workspaces, autograd) must not be captured
-                g["warm"] += 1
-                return self._eager_step(img, mask, distmap, alpha)
-            self._capture(g, img, mask, distmap, alpha)
-        # a loader that writes its batches straight into the graph's static buffers (`static_batch()`) hands them back
-        # here: nothing to copy (at B = 64 the image copy alone is 201 MB = 0.2 ms of a 25 ms step)
-        if img is not g["img"]:
-            g["img"].copy_(img)
-        if mask is not g["mask"]:
-            g["mask"].copy_(mask)
-        if distmap is not None and distmap is not g["distmap"]:
-            g["distmap"].copy_(distmap)
-        self.opt.sync_lr()                   # a changed learning rate reaches the replay through lr_dev
-        self.opt.t += 1                      # host mirror; the authoritative count is the device's t_dev
-        g["graph"].replay()
-        self.model.engine.mark_weights_changed()
-        self.model._bn_tracked_inc()         # module bookkeeping outside the graph (smp state_dict key)
-        self.last = g["last"]
-        return g["last"]["loss"]
+
+        def step_last(img, mask, distmap, capturing=False):      # -> ``self.last`` of that step: what a replay hands back
+            self._eager_step(img, mask, distmap, alpha, capturing=capturing)
+            return self.last
+        r = self._step_replays.get(key, lambda: GraphReplay(self.model.engine, step_last, warmup=2,
+                                                            capture_fn=partial(step_last, capturing=True)))
+        # two eager warm-up steps (real steps, with their own bookkeeping), then GraphReplay captures on its static
+        # buffers.  A loader that writes its batches straight into them (`static_batch()`) hands them back here: nothing
+        # to copy (at B = 64 the image copy alone is 201 MB = 0.2 ms of a 25 ms step)
+        self.opt.sync_lr()                   # never inside a capture: a changed learning rate reaches the replay via lr_dev
+        t_host = self.opt.t
+        last = r(img, mask, distmap)
+        if r.captured:
+            self.opt.t = t_host + 1          # host mirror (a capture launches nothing); the device's t_dev is authoritative
+            self.model.engine.mark_weights_changed()
+            self.model._bn_tracked_inc()     # module bookkeeping outside the graph (smp state_dict key)
+            self.last = last
+        return last["loss"]
 
     def static_batch(self):
         """(img, mask, distmap) buffers the captured step reads — available once the graph exists (after the eager
         warm-up steps); a data pipeline that fills THESE tensors (H2D copies, device-side augmentation) and passes them
         to ``step`` saves the per-step staging copy.  None before capture or without graph replay."""
-        g = self._graph
-        if not self.use_graph or g is None or "graph" not in g:
+        r = next(iter(self._step_replays.values()), None)
+        if not self.use_graph or r is None or not r.captured:
             return None
-        return g["img"], g["mask"], g["distmap"]
-
-    def _capture(self, g, img, mask, distmap, alpha):
-        eng = self.model.engine
-        g["img"], g["mask"] = img.clone(), mask.clone()
-        g["distmap"] = None if distmap is None else distmap.clone()
-        self.opt.sync_lr()
-        t_host = self.opt.t
-        graph = torch.cuda.CUDAGraph()
-        with eng.capture_workspaces() as g["ws"]:   # workspaces of the captured step live (and stay) in the graph's pool
-            torch.cuda.synchronize()
-            with torch.cuda.graph(graph):
-                self._eager_step(g["img"], g["mask"], g["distmap"], alpha, capturing=True)
-        self.opt.t = t_host                   # capture launched nothing: the step count has not moved
-        g["graph"], g["last"] = graph, self.last
+        return r.inputs
 
     def _eager_step(self, img, mask, distmap, alpha, capturing: bool = False):
         """forward -> fused loss -> hand-scheduled backward -> (all-reduce) -> clip + Adam, straight on the C ABI:

@@ -207,7 +207,8 @@ def test_frozen_graph_equals_eager_with_toggle(precision):
             m.encoder.requires_grad_(step >= 4)      # frozen for 4 steps, then trainable: a re-capture
             losses.append(float(tr.step(img, mask)))
         if mode == "graph":
-            assert "graph" in tr._graph and tr._graph["key"][-2] is False
+            (key,), (r,) = tr._step_replays.keys(), tr._step_replays.values()
+            assert r.captured and key[-2] is False
         out[mode] = (losses, m.flat_params.detach().clone(), tr.opt.m.clone(), m.bn_state.clone())
     le, pe, me, be = out["eager"]
     lg, pg, mg, bg = out["graph"]

@@ -297,7 +297,7 @@ def test_update_bn_graph_replay_equals_eager(precision):
     want = m.bn_state.clone()
     tr = HipTrainer(m, precision=precision, graph=True)
     assert tr.update_bn(imgs) == 4
-    assert tr._recal_graph is not None and "graph" in tr._recal_graph
+    assert len(tr._recal_replays) == 1 and tr._recal_replays.values()[0].captured
     assert torch.equal(m.bn_state, want)
     assert tr.update_bn(imgs + imgs[:1]) == 5          # a second pass replays the same graph from batch one
     got5 = m.bn_state.clone()
@@ -351,7 +351,7 @@ def test_ema_inside_the_step(precision):
                      None if tr.averager is None else tr.averager.avg.clone(),
                      None if tr.averager is None else tr.averager.n_averaged, snaps)
         if mode == "graph":
-            assert "graph" in tr._graph
+            assert tr._step_replays.values()[0].captured
         if mode == "eager":     # a non-finite loss: the step is skipped, avg and its count stay
             bad = batches[0][0].clone()
             bad[0, 0, 0, 0] = float("nan")

@@ -141,14 +141,14 @@ def test_validate_does_not_disturb_the_captured_training_graph():
         tr = _trainer(graph=True, warm=0, seed=3)
         for img, mask, _, _ in train[:3]:
             tr.step(img, mask)
-        assert "graph" in tr._graph
-        graph = tr._graph["graph"]
+        assert tr._step_replays.values()[0].captured
+        graph = tr._step_replays.values()[0].graph
         if with_val:
             for _ in range(3):                        # eager warm-up, capture and replay of the validation batches
                 tr.validate(_batches())
-            assert any("graph" in g for g in tr._val_graphs.values())
+            assert any(r.captured for r in tr._val_replays.values())
         loss = float(tr.step(train[3][0], train[3][1]))
-        assert tr._graph["graph"] is graph
+        assert tr._step_replays.values()[0].graph is graph
         out.append((loss, tr.model.flat_params.detach().clone(), tr.model.bn_state.clone(), tr.opt.m.clone()))
     assert out[0][0] == out[1][0]
     for a, b in zip(out[0][1:], out[1][1:]):
@@ -167,10 +167,10 @@ def test_graph_replayed_validation_equals_eager(precision, losses):
                {k: v for k, v in eager.items() if k.startswith("val/")}, i
         assert torch.equal(val["cm_px"], eager["cm_px"]) and torch.equal(val["cm_px_masked"], eager["cm_px_masked"])
     # batch sizes 2 and 1: two keys; the size-2 graph exists after its two eager batches, the size-1 one after two epochs
-    assert len(tr._val_graphs) == 2 and all("graph" in g for g in tr._val_graphs.values())
+    assert len(tr._val_replays) == 2 and all(r.captured for r in tr._val_replays.values())
     if "BOUNDARY-RAMPED" in losses:                   # alpha is read by the captured blend: it belongs to the key
         other = tr.validate(batches, alpha=0.9)
-        assert len(tr._val_graphs) == 4 and other["val/total_loss"] != val["val/total_loss"]
+        assert len(tr._val_replays) == 4 and other["val/total_loss"] != val["val/total_loss"]
         assert other["val/dice"] == val["val/dice"]
 
 
