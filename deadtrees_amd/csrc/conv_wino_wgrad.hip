@@ -15,6 +15,10 @@
 //     memory (32 lanes x 8 B = one 256-B row per pixel), transforms both in registers and writes the 16 positions to
 //     LDS `[pos][k-half][k-step][64 channels]` with conflict-free ds_write_b64; fragments are conflict-free ds_read_b32;
 //   * LDS images double-buffered, one barrier per chunk; loads run two chunks ahead (two register sets);
+//   * one wave per SIMD hides almost none of its own vector instructions behind its MFMAs (measured: DESIGN.md section 38),
+//     so the staging stream is kept short: PK issues every two-channel add / subtract of the transforms as ONE
+//     v_pk_add_f32 (hipcc splits a <2 x float> subtraction into two scalar adds) and reads the fragments of two k-steps
+//     with one ds_read2st64_b32.  Same IEEE operations on the same values: bit-identical to the scalar form;
 //   * partial dU blocks go to a workspace; a fixed-order two-stage reduction sums the splits and applies G^T . G
 //     (deterministic: no float atomics).
 #include "conv_host.h"
@@ -38,11 +42,22 @@ struct WinoWgArgs {
   unsigned bytes0, bytes1, dybytes, wsbytes;
 };
 
+// (NA ? -a : a) + (NB ? -b : b) on both channels in one instruction (the negations are source modifiers)
+template <bool NA, bool NB>
+__device__ __forceinline__ f32x2 ww_pk_add(f32x2 a, f32x2 b) {
+  f32x2 d;
+  if constexpr (NA && NB) asm("v_pk_add_f32 %0, %1, %2 neg_lo:[1,1] neg_hi:[1,1]" : "=v"(d) : "v"(a), "v"(b));
+  else if constexpr (NB) asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
+  else if constexpr (NA) asm("v_pk_add_f32 %0, %1, %2 neg_lo:[1,0] neg_hi:[1,0]" : "=v"(d) : "v"(a), "v"(b));
+  else asm("v_pk_add_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+  return d;
+}
+
 // CO32: a layer with 32 output channels (dec3.conv1: 128 -> 32): one 32-channel co block.  The two waves of a ci half
 // (wn = 0, 1) would multiply the same 32 x 32 block twice, so they split the chunk's K instead — wave wn takes k-steps
 // 2 wn, 2 wn + 1 of every position (32 MFMAs per chunk, the staging work of two of the 64-slot schedule's slots behind each)
 // — and write their accumulators as two partial slabs (part 2 split + wn) for the existing fixed-order reduction.
-template <bool TF, bool CO32 = false>
+template <bool TF, bool CO32 = false, bool PK = true>
 __global__ __launch_bounds__(256, 1) void conv3x3_wino_wgrad_kernel(const WinoWgArgs a) {
   __shared__ __attribute__((aligned(1024))) float lds[4 * WW_BUF + (TF ? 2 * WW_TF_MAXC : 4)];
   float* Vb = lds;                 // [2][WW_BUF] transformed input patches
@@ -200,19 +215,21 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_wgrad_kernel(const WinoWg
   };
   // LDS image: [pos][k-half][k-step][64 channels]; tile tau is k-half tau >> 2, k-step tau & 3
   const int woff = ((tau >> 2) * 4 + (tau & 3)) * 64 + 2 * c2;
+  auto add2 = [](f32x2 u, f32x2 v) { if constexpr (PK) return ww_pk_add<false, false>(u, v); else return u + v; };
+  auto sub2 = [](f32x2 u, f32x2 v) { if constexpr (PK) return ww_pk_add<false, true>(u, v); else return u - v; };
   auto x_col = [&](auto set_tag, int j) {   // column j of B^T d
     constexpr int SET = decltype(set_tag)::value;
-    t[0 + j] = dx[SET][0 + j] - dx[SET][8 + j];
-    t[4 + j] = dx[SET][4 + j] + dx[SET][8 + j];
-    t[8 + j] = dx[SET][8 + j] - dx[SET][4 + j];
-    t[12 + j] = dx[SET][4 + j] - dx[SET][12 + j];
+    t[0 + j] = sub2(dx[SET][0 + j], dx[SET][8 + j]);
+    t[4 + j] = add2(dx[SET][4 + j], dx[SET][8 + j]);
+    t[8 + j] = sub2(dx[SET][8 + j], dx[SET][4 + j]);
+    t[12 + j] = sub2(dx[SET][4 + j], dx[SET][12 + j]);
   };
   auto x_row_write = [&](float* Vd, int i) {   // row i of (B^T d) B -> 4 positions
     float* dst = Vd + woff;
-    const f32x2 v0 = t[4 * i + 0] - t[4 * i + 2];
-    const f32x2 v1 = t[4 * i + 1] + t[4 * i + 2];
-    const f32x2 v2 = t[4 * i + 2] - t[4 * i + 1];
-    const f32x2 v3 = t[4 * i + 1] - t[4 * i + 3];
+    const f32x2 v0 = sub2(t[4 * i + 0], t[4 * i + 2]);
+    const f32x2 v1 = add2(t[4 * i + 1], t[4 * i + 2]);
+    const f32x2 v2 = sub2(t[4 * i + 2], t[4 * i + 1]);
+    const f32x2 v3 = sub2(t[4 * i + 1], t[4 * i + 3]);
     *reinterpret_cast<f32x2*>(dst + (4 * i + 0) * 512) = v0;
     *reinterpret_cast<f32x2*>(dst + (4 * i + 1) * 512) = v1;
     *reinterpret_cast<f32x2*>(dst + (4 * i + 2) * 512) = v2;
@@ -223,14 +240,21 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_wgrad_kernel(const WinoWg
     constexpr int SET = decltype(set_tag)::value;
     const f32x2 g00 = dg[SET][0], g01 = dg[SET][1], g10 = dg[SET][2], g11 = dg[SET][3];
     f32x2 r0, r1;   // row i of A dY: (col 0, col 1)
-    if (i == 0) { r0 = g00; r1 = g01; }
-    else if (i == 1) { r0 = g00 + g10; r1 = g01 + g11; }
-    else if (i == 2) { r0 = g00 - g10; r1 = g01 - g11; }
-    else { r0 = -g10; r1 = -g11; }
     float* dst = Wd + woff;
+    if (PK && i == 3) {   // r0 = -g10, r1 = -g11 stay source modifiers: (-g10) + (-g11), (-g10) - (-g11), -(-g11)
+      *reinterpret_cast<f32x2*>(dst + 12 * 512) = -g10;
+      *reinterpret_cast<f32x2*>(dst + 13 * 512) = ww_pk_add<true, true>(g10, g11);
+      *reinterpret_cast<f32x2*>(dst + 14 * 512) = ww_pk_add<true, false>(g10, g11);
+      *reinterpret_cast<f32x2*>(dst + 15 * 512) = g11;
+      return;
+    }
+    if (i == 0) { r0 = g00; r1 = g01; }
+    else if (i == 1) { r0 = add2(g00, g10); r1 = add2(g01, g11); }
+    else if (i == 2) { r0 = sub2(g00, g10); r1 = sub2(g01, g11); }
+    else { r0 = -g10; r1 = -g11; }
     *reinterpret_cast<f32x2*>(dst + (4 * i + 0) * 512) = r0;
-    *reinterpret_cast<f32x2*>(dst + (4 * i + 1) * 512) = r0 + r1;
-    *reinterpret_cast<f32x2*>(dst + (4 * i + 2) * 512) = r0 - r1;
+    *reinterpret_cast<f32x2*>(dst + (4 * i + 1) * 512) = add2(r0, r1);
+    *reinterpret_cast<f32x2*>(dst + (4 * i + 2) * 512) = sub2(r0, r1);
     *reinterpret_cast<f32x2*>(dst + (4 * i + 3) * 512) = -r1;
   };
 
@@ -299,9 +323,15 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_wgrad_kernel(const WinoWg
       constexpr int mslot = decltype(mc)::value;
       constexpr int p = mslot / NJ, j = mslot % NJ, cur = p & 1;
       acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][j], fb[cur][j], acc[p], 0, 0, 0);
-      if (p + 1 < 16) {   // the next position's k-step j
-        fa[cur ^ 1][j] = Vc[(p + 1) * 512 + j * 64];
-        fb[cur ^ 1][j] = Wc[(p + 1) * 512 + j * 64];
+      if (p + 1 < 16) {   // the next position's k-step j; PK: k-steps j, j + 1 in the even slot (64 floats apart: one read2st64)
+        if constexpr (!PK || (j & 1) == 0) {
+          fa[cur ^ 1][j] = Vc[(p + 1) * 512 + j * 64];
+          fb[cur ^ 1][j] = Wc[(p + 1) * 512 + j * 64];
+        }
+        if constexpr (PK && (j & 1) == 0) {
+          fa[cur ^ 1][j + 1] = Vc[(p + 1) * 512 + (j + 1) * 64];
+          fb[cur ^ 1][j + 1] = Wc[(p + 1) * 512 + (j + 1) * 64];
+        }
       }
       if constexpr (CO32) {
         slot_work(std::integral_constant<int, 2 * mslot>{});
@@ -416,6 +446,13 @@ static bool ww_co32(const dt_conv_desc* d) {   // 32 output channels: the K-spli
   return dt_env_on("DT_FP32_WINO_WGRAD_CO32") && d->Cout == 32;
 }
 
+// packed transforms + paired fragment reads (DT_FP32_WINO_WGRAD_PACKED=0: the scalar form, for the A/B and the bit-equality test)
+template <bool TF, bool CO32>
+static void ww_launch(dim3 g, hipStream_t st, const WinoWgArgs& a) {
+  if (dt_env_on("DT_FP32_WINO_WGRAD_PACKED")) hipLaunchKernelGGL((conv3x3_wino_wgrad_kernel<TF, CO32, true>), g, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((conv3x3_wino_wgrad_kernel<TF, CO32, false>), g, dim3(256), 0, st, a);
+}
+
 extern "C" int dt_conv2d_wgrad_winograd_supported(const dt_conv_desc* d) {
   if (d == nullptr) return 0;
   if (d->ksize != 3 || d->stride != 1 || d->pad != 1 || d->mode0 == 2) return 0;
@@ -456,12 +493,12 @@ extern "C" int dt_conv2d_wgrad_winograd(const dt_conv_desc* d, const float* src0
   a.dybytes = (unsigned)((size_t)d->B * d->Ho * d->Wo * d->Cout * 4);
   a.wsbytes = (unsigned)(slab * c.parts);
   hipStream_t st = (hipStream_t)stream;
-  dim3 g((unsigned)(c.ci_blocks * c.co_blocks * c.ksplit)), blk(256);
+  dim3 g((unsigned)(c.ci_blocks * c.co_blocks * c.ksplit));
   if (d->Cout == 32) {
-    if (in_scale != nullptr) hipLaunchKernelGGL((conv3x3_wino_wgrad_kernel<true, true>), g, blk, 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_wino_wgrad_kernel<false, true>), g, blk, 0, st, a);
-  } else if (in_scale != nullptr) hipLaunchKernelGGL((conv3x3_wino_wgrad_kernel<true>), g, blk, 0, st, a);
-  else hipLaunchKernelGGL((conv3x3_wino_wgrad_kernel<false>), g, blk, 0, st, a);
+    if (in_scale != nullptr) ww_launch<true, true>(g, st, a);
+    else ww_launch<false, true>(g, st, a);
+  } else if (in_scale != nullptr) ww_launch<true, false>(g, st, a);
+  else ww_launch<false, false>(g, st, a);
   DT_LAUNCH_CHECK();
   const float* parts_src = workspace;
   int parts = c.parts;
