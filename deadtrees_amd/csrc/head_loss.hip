@@ -12,6 +12,7 @@
 // All HBM-bound: one read of the 16-channel decoder output / of the logits, wave64 shuffle
 // reductions -> LDS -> one fp64 row per workgroup (fixed-order finalize, no float atomics).
 #include "conv_host.h"
+#include "loss_softmax.h"
 
 #include <math.h>
 
@@ -96,22 +97,7 @@ __device__ __forceinline__ int head_argmax(const float (&z)[K]) {
 }
 
 // ---- downstream of the logits: ONE definition of every step the loss kernels and head_eval_kernel share
-// Channel softmax: max, expf(z - max), sum in class order, times 1 / sum.  `p` may be `z` itself.
-template <int K>
-__device__ __forceinline__ void loss_softmax(const float (&z)[K], float (&p)[K]) {
-  float m = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < K; ++k) m = fmaxf(m, z[k]);
-  float sum = 0.f;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    p[k] = expf(z[k] - m);
-    sum += p[k];
-  }
-  const float inv = 1.f / sum;
-#pragma unroll
-  for (int k = 0; k < K; ++k) p[k] = p[k] * inv;
-}
+// (loss_softmax, the channel softmax, lives in loss_softmax.h: curves.hip bins the same probabilities)
 
 // GWDICE applies softmax to the PROBABILITIES once more (gwdl.py:104 on segmodel.py:176's y_hat): q[k] = expf(p[k])
 // UN-normalised and the return value 1 / sum.  Where the caller multiplies that in is part of its rounding — the three

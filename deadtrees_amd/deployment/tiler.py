@@ -33,6 +33,7 @@ from .overlaps import (PatchMatch, PatchOverlaps, PatchTracks, overlap_pairs_hos
 from .proximity import (PatchDistances, PatchGaps, ProximityConfig, patch_distances, patch_gaps,  # noqa: F401
                         patch_proximity_host)
 from .patches import PatchConfig, PatchTable  # noqa: F401  (the ``patches`` argument of infer_tile)
+from ..loss.curves import Decision, check_decision  # noqa: F401  (the ``decision`` argument of infer_tile)
 
 
 def divisible_without_remainder(a, b):
@@ -283,14 +284,14 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
                   device: str = "cuda", tile_shape: Optional[Tuple[int, int]] = None, skip_blank: bool = True,
                   overlap: int = 0, blend: str = "crop", return_probs: bool = False, tta=None, stats: bool = False,
                   zones=None, n_zones: Optional[int] = None, patches=None, outlines=None, against=None,
-                  against_patches=None, distances=None, gaps=None, attributes=None):
+                  against_patches=None, distances=None, gaps=None, attributes=None, decision=None):
     """the directory loop of scripts/inference.py:71-115 over in-memory rasters (GeoTIFF I/O needs rioxarray, absent
     here): ``rasters`` yields ``array`` or ``(key, array)``; rank r of ``world`` takes rasters r, r + world, ... (tiles are
     independent: no collective).  Yields ``(key, class_map)`` in input order of the rank's share; rasters whose band 1
     holds only 0 / 255 (``is_valid_tile``, :60-62) are skipped like the reference does — ``(key, None)`` — without a
     forward pass (device reduction over the uploaded raster, ``ops.band_has_data``).  ``overlap`` / ``blend`` /
     ``return_probs`` / ``tta`` / ``stats`` / ``n_zones`` / ``patches`` / ``outlines`` / ``against_patches`` / ``distances`` /
-    ``gaps`` / ``attributes``: as in ``infer_tile``, with the same rules, checked before the first raster is read (every raster
+    ``gaps`` / ``attributes`` / ``decision``: as in ``infer_tile``, with the same rules, checked before the first raster is read (every raster
     stays on its rank, so overlap needs no exchange); ``zones``: a callable ``key -> uint8 [h, w] array, PolygonSet or None``,
     or a mapping (a missing key is None); ``against``: the same for the map every raster is compared with (a uint8 array, a ``PolygonSet``
     or None: that raster's statistics carry no overlaps).
@@ -299,6 +300,7 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
     rules = MapAnalysis.rules("infer_rasters", getattr(inference, "classes", None) if stats else None, stats, zones, n_zones,
                               patches, outlines, against, against_patches, distances, gaps, attributes,
                               _no_probs(inference, overlap, blend, tta))
+    decision = _check_decision("infer_rasters", inference, decision, overlap, blend, tta)
     for i, item in enumerate(rasters):
         if i % world != rank:
             continue
@@ -307,7 +309,7 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
         other = None if against is None else against(key) if callable(against) else against.get(key)
         request = None if rules is None else rules.bind("infer_tile", np.shape(arr)[1:], z, other, arr)
         yield key, _infer_tile(inference, arr, request, subtile, batch_size, 0, 1, device, None, tile_shape, None, skip_blank,
-                               overlap, blend, return_probs, tta)
+                               overlap, blend, return_probs, tta, decision)
 
 
 def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size: int = 64, rank: int = 0,
@@ -315,7 +317,7 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
                on_device: Optional[bool] = None, skip_blank: bool = False, overlap: int = 0, blend: str = "crop",
                return_probs: bool = False, tta=None, stats: bool = False, zones=None, n_zones: Optional[int] = None,
                patches=None, outlines=None, against=None, against_patches=None, distances=None, gaps=None,
-               attributes=None):
+               attributes=None, decision=None):
     """whole-tile inference of scripts/inference.py:80-115 on the MI355X path: split -> (uint8 H2D, normalise on the
     device) -> forward + fused argmax -> uint8 D2H -> merge.  With world > 1 the sub-tile batches j = rank (mod world)
     are processed locally and the uint8 class maps are all-gathered (no other collective: tiles are independent).
@@ -383,13 +385,35 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     ``in_channels`` planes: an RGB model over an RGBN raster still yields NDVI.  ``confidence=True`` adds the mean and the
     minimum probability of the patch's class (``confidence()``, ``min_confidence()``); it is accepted exactly where
     ``return_probs=True`` is, and without ``return_probs`` the probabilities stay on the device.  Everything else is that of
-    the call without the option."""
+    the call without the option.
+
+    ``decision``: a ``Decision`` (``loss/curves.py``: a threshold per class ``1..K-1``, as ``validate(curves=True)`` finds them)
+    replaces the arg-max as the rule that turns the blended probabilities into the map: a pixel takes the class c >= 1
+    with the largest quantised probability among those that reach their threshold, class 0 without one
+    (``ops.decide_classes`` on the probabilities of ``stitch_finalize``).  It is accepted exactly where ``return_probs=True``
+    is, and everything downstream — counts, sieve, patch table, outlines, overlaps, gaps, attributes — sees the decided map;
+    ``confidence`` is the probability of the decided class.  The probabilities are returned only when ``return_probs`` asks.
+    Validation probabilities are single-tile softmaxes, these are blended ones: the threshold transfers, the bit-for-bit
+    closure of the curves holds for identical inputs.  None: nothing changes."""
+    decision = _check_decision("infer_tile", inference, decision, overlap, blend, tta)
     request = MapAnalysis.of("infer_tile", np.shape(arr_chw_u8)[1:], getattr(inference, "classes", None) if stats else None,
                              zones, against, arr_chw_u8, stats=stats, n_zones=n_zones, patches=patches, outlines=outlines,
                              against_patches=against_patches, distances=distances, gaps=gaps, attributes=attributes,
                              no_probs=_no_probs(inference, overlap, blend, tta))
     return _infer_tile(inference, arr_chw_u8, request, subtile, batch_size, rank, world, device, group, tile_shape, on_device,
-                       skip_blank, overlap, blend, return_probs, tta)
+                       skip_blank, overlap, blend, return_probs, tta, decision)
+
+
+def _check_decision(caller: str, inference, decision, overlap, blend, tta):
+    """the ``decision`` argument, checked before anything runs: a ``Decision`` for the model's classes, and only where the
+    call has raster probabilities (the rule of ``return_probs``); None stays None"""
+    if decision is None:
+        return None
+    decision = check_decision(decision, getattr(inference, "classes", None), caller)
+    lacking = _no_probs(inference, overlap, blend, tta)
+    if lacking:
+        raise ValueError(f"{caller}: decision thresholds the blended probabilities: " + lacking.replace("return_probs", "it"))
+    return decision
 
 
 def _no_probs(inference, overlap, blend, tta) -> Optional[str]:
@@ -403,7 +427,7 @@ def _no_probs(inference, overlap, blend, tta) -> Optional[str]:
 
 
 def _infer_tile(inference, arr_chw_u8, request: Optional[MapAnalysis], subtile, batch_size, rank, world, device, group,
-                tile_shape, on_device, skip_blank, overlap, blend, return_probs, tta):
+                tile_shape, on_device, skip_blank, overlap, blend, return_probs, tta, decision=None):
     """``infer_tile`` behind the check of its statistics options: ``request`` is their ``MapAnalysis``, None without ``stats``"""
     if blend not in ("crop", "average"):
         raise ValueError(f"blend {blend!r}: use 'crop' or 'average'")
@@ -424,7 +448,7 @@ def _infer_tile(inference, arr_chw_u8, request: Optional[MapAnalysis], subtile, 
         if arr_chw_u8.dtype != np.uint8:
             raise ValueError(f"infer_tile: the stitched device path reads a uint8 raster, got {arr_chw_u8.dtype}")
         return _infer_tile_stitched(inference, models, vote, arr_chw_u8, subtile, overlap, blend, batch_size, device,
-                                    skip_blank, return_probs, views, request)
+                                    skip_blank, return_probs, views, request, decision)
     if return_probs:
         raise ValueError("infer_tile: " + _no_probs(inference, overlap, blend, tta))
     if tile_shape is None:
@@ -524,7 +548,8 @@ def _infer_tile_on_device(inference, arr_chw_u8: np.ndarray, subtile: int, batch
 
 
 def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.ndarray, d: int, overlap: int, blend: str,
-                         batch_size: int, device: str, skip_blank: bool, return_probs: bool, views, request=None):
+                         batch_size: int, device: str, skip_blank: bool, return_probs: bool, views, request=None,
+                         decision=None):
     """``infer_tile`` on the window grid: overlapping windows, test-time augmentation (``views``: canonical pairs, or None
     for the plain window), an ensemble (``models``; ``vote`` None for a single model) and their combinations.  ONE uint8 H2D
     copy of the raster; per model and batch of windows one gather (``dt_window_normalize_u8``) + forward + one stitch kernel
@@ -535,7 +560,10 @@ def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.
     accumulates probabilities (``weight="ramp"`` for ``blend="average"``, ``weight="keep"`` for crop with views) and
     finalizes.  Hard vote: one ``ops.ensemble_vote`` over the members' raster maps.  Soft vote: ONE accumulator, members
     outer / window batches inner, no 1/M (finalize normalises) — each pixel's terms arrive model-major, windows ascending,
-    views ascending, for every batch size."""
+    views ascending, for every batch size.
+
+    ``decision``: the probabilities are finalized as for ``return_probs`` and ``ops.decide_classes`` overwrites the arg-max
+    plane before ``run_device``; they leave the device only when ``return_probs`` asks."""
     from .. import ops
     _, h, w = arr_chw_u8.shape
     ny, nx, _ = window_grid(h, w, d, overlap)
@@ -544,7 +572,8 @@ def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.
     if up is None:
         return None
     x, planes, raster = up
-    want_probs = return_probs or (request is not None and request.attributes is not None and request.attributes.confidence)
+    keep_probs = return_probs or (request is not None and request.attributes is not None and request.attributes.confidence)
+    want_probs = keep_probs or decision is not None
     kw = {} if views is None else {"views": views}   # a duck-typed run_windows without TTA need not take the keyword
     per = batch_size if views is None else max(1, batch_size // len(views))     # batch_size counts forward tiles
     weight = "ramp" if blend == "average" else "keep"
@@ -575,5 +604,7 @@ def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.
         acc = accumulate(m, acc)
     if want_probs:
         classes, probs = ops.stitch_finalize(acc, want_probs=True)
-        return run_device(request, classes, probs, planes, raster, return_probs)
+        if decision is not None:
+            ops.decide_classes(probs, decision, out=classes)
+        return run_device(request, classes, probs if keep_probs else None, planes, raster, return_probs)
     return run_device(request, ops.stitch_finalize(acc), None, planes, raster)

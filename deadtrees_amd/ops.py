@@ -566,6 +566,62 @@ def confusion_matrix(pred, target, lu=None, K=2, counts=None):
     return counts, err
 
 
+def prob_histogram(src, labels, lu=None, hist=None, err=None, logits: bool = False, want_q: bool = False):
+    """probability histogram of ``loss/curves.py`` through dt_prob_histogram: ``src`` fp32 [B,K,H,W] probabilities (``logits``:
+    logits, through the loss kernels' softmax), ``labels`` / ``lu`` [B,H,W].  ``hist`` int64 [2,K,2,256] is added to (+=;
+    allocated zeroed when None), ``err`` int32 [1] likewise.  -> ``(hist, err)``, with ``want_q`` ``(hist, err, q)``: the
+    quantised probabilities uint16 [B,K,H,W]."""
+    _gpu(src, labels, lu, hist, err)
+    if src.dtype != torch.float32 or src.dim() != 4:
+        raise RuntimeError(f"prob_histogram: src must be float32 [B,K,H,W], got {src.dtype} {tuple(src.shape)}")
+    B, K, H, W = src.shape
+    n = B * H * W
+    # the kernel reads labels / lu as int64 for B * H * W elements: anything else would run past the allocation
+    if n == 0 or labels.numel() != n or (lu is not None and lu.numel() != n):
+        raise RuntimeError(f"prob_histogram: src {tuple(src.shape)}, labels {tuple(labels.shape)}" +
+                           (f", lu {tuple(lu.shape)}" if lu is not None else "") + " must have the same number of pixels (> 0)")
+    if labels.dtype != torch.int64:
+        labels = labels.long()
+    if lu is not None and lu.dtype != torch.int64:
+        lu = lu.long()
+    if hist is None:
+        hist = torch.zeros((2, K, 2, 256), dtype=torch.int64, device=src.device)
+    elif hist.dtype != torch.int64 or tuple(hist.shape) != (2, K, 2, 256) or hist.device != src.device \
+            or not hist.is_contiguous():
+        raise RuntimeError(f"prob_histogram: hist must be contiguous int64 [2,{K},2,256] on {src.device}")
+    err = _err_flag("prob_histogram", err, src.device)
+    q = torch.empty((B, K, H, W), dtype=torch.uint16, device=src.device) if want_q else None
+    _lib.check(_lib.load().dt_prob_histogram(_p(src.contiguous()), _p(labels.contiguous()),
+                                             _p(lu.contiguous()) if lu is not None else None, _p(hist), _p(err), _p(q),
+                                             B, K, H, W, 1 if logits else 0, _st()), "dt_prob_histogram")
+    return (hist, err, q) if want_q else (hist, err)
+
+
+def decide_classes(probs, decision_or_thresholds, out=None):
+    """the decision of ``loss/curves.py`` through dt_decide_classes_u8: ``probs`` fp32 [K, ...] -> uint8 class map [...]
+    (``out``: written in place).  ``decision_or_thresholds``: a ``Decision`` for K classes, or its K integer thresholds on
+    the q axis (entry 0 is not read)."""
+    from .loss.curves import Decision
+    _gpu(probs, out)
+    if probs.dtype != torch.float32 or probs.dim() < 2 or not probs.is_contiguous() or probs.numel() == 0:
+        raise RuntimeError("decide_classes: probs must be non-empty contiguous float32 [K, ...]")
+    K = probs.shape[0]
+    if isinstance(decision_or_thresholds, Decision):
+        thr = [int(v) for v in decision_or_thresholds.thresholds_u16(K)]
+    else:
+        thr = [int(v) for v in decision_or_thresholds]
+        if len(thr) != K or any(not 1 <= v <= 65535 for v in thr[1:]):
+            raise ValueError(f"decide_classes: {K} thresholds, those of the classes 1..{K - 1} in 1..65535; got {thr}")
+        thr[0] = 0
+    if out is None:
+        out = torch.empty(tuple(probs.shape[1:]), dtype=torch.uint8, device=probs.device)
+    elif out.dtype != torch.uint8 or out.numel() * K != probs.numel() or out.device != probs.device or not out.is_contiguous():
+        raise RuntimeError(f"decide_classes: out must be contiguous uint8 {tuple(probs.shape[1:])} on {probs.device}")
+    _lib.check(_lib.load().dt_decide_classes_u8(_p(probs), (C.c_uint16 * K)(*thr), _p(out), K, out.numel(), _st()),
+               "dt_decide_classes_u8")
+    return out
+
+
 def conv2d_bn_bwd(src0, w_hwio, y, mean, invstd, act_scale=None, act_shift=None, act=None, join_into=None):
     """3x3 stride-1 conv (a data gradient) whose epilogue also produces the BatchNorm-backward partial sums of the
     layer with raw output `y` (same shape as the result).  Virtual activation: give act_scale/act_shift; block
@@ -1135,8 +1191,10 @@ def rasterize_polygons(edges: torch.Tensor, polys: torch.Tensor, shape, all_touc
 # constants asked of the library on first use -> (getter, count).  PATCH_TILE = (th, tw): the tile of dt_label_patches_u8's
 # local launch; OUTLINE_CHUNK / OVERLAP_CHUNK: the consecutive pixels one workgroup of dt_outline_count / dt_overlap_count takes;
 # PROXIMITY_SEGMENT: the rows of one column segment of dt_proximity_columns; PROXIMITY_WINDOW: the pixels of one row that a
-# workgroup of dt_proximity_query takes; ATTRIBUTE_SPAN: the consecutive 64-pixel chunks a wave of dt_patch_attributes_u8 takes
+# workgroup of dt_proximity_query takes; ATTRIBUTE_SPAN: the consecutive 64-pixel chunks a wave of dt_patch_attributes_u8 takes;
+# CURVE_CHUNK: the consecutive pixels of the B * H * W axis one workgroup of dt_prob_histogram takes
 _LIB_CONSTANTS = {"PATCH_TILE": ("dt_patch_tile", 2), "OUTLINE_CHUNK": ("dt_outline_chunk", 1),
+                  "CURVE_CHUNK": ("dt_curve_chunk", 1),
                   "OVERLAP_CHUNK": ("dt_overlap_chunk", 1), "PROXIMITY_SEGMENT": ("dt_proximity_segment", 1),
                   "PROXIMITY_WINDOW": ("dt_proximity_window", 1), "ATTRIBUTE_SPAN": ("dt_attribute_span", 1)}
 

@@ -22,7 +22,7 @@ import torch
 from .data.distmap import distmaps_on_device
 from .loss.seg_loss import PART_KEYS, loss_algebra, loss_backward, loss_forward
 from .network.unet import UNetHIP
-from .ops import FlatAdam, WeightAverager, confusion_matrix, eval_accumulate
+from .ops import FlatAdam, WeightAverager, confusion_matrix, eval_accumulate, prob_histogram
 from .utils.graph_replay import GraphReplay, ReplayCache
 
 
@@ -137,20 +137,24 @@ class HipTrainer:
     # ------------------------------------------------------------------ validation epoch
     def _val_buffers(self):
         """the device accumulators of a validation epoch: epoch f64[9] (weighted sums of the eight ``parts`` + the sum of
-        weights), confusion counts int64 [2,K,K], label flag int32[1].  Allocated once: captured graphs write them."""
+        weights), confusion counts int64 [2,K,K], label flag int32[1], and "hist", the probability histogram int64
+        [2,K,2,256] of ``validate(curves=True)`` (``loss/curves.py``).  Allocated once: captured graphs write them."""
         dev, K = self.model.flat_params.device, self.model.spec.classes
         st = self._val_state
         if st is None or st["epoch"].device != dev:
             st = self._val_state = {"epoch": torch.zeros(9, dtype=torch.float64, device=dev),
                                     "counts": torch.zeros((2, K, K), dtype=torch.int64, device=dev),
-                                    "err": torch.zeros(1, dtype=torch.int32, device=dev)}
+                                    "err": torch.zeros(1, dtype=torch.int32, device=dev),
+                                    "hist": torch.zeros((2, K, 2, 256), dtype=torch.int64, device=dev)}
             self._val_replays.clear()
         return st
 
-    def _val_batch(self, img, mask, lu, distmap, alpha):
+    def _val_batch(self, img, mask, lu, distmap, alpha, curves=False):
         """one validation batch, launches only: eval-mode forward up to the decoder output, the fused evaluation head
         (losses with GWDICE: logits, ``loss_forward`` and ``confusion_matrix``, the unfused chain), the scalar algebra
-        and the weighted accumulation into the epoch buffers.  Reads no module mode and writes no model state."""
+        and the weighted accumulation into the epoch buffers.  Reads no module mode and writes no model state.
+        ``curves``: the unfused chain as well, plus ONE ``prob_histogram`` of the logits into the epoch's histogram — the
+        fused ``dt_head_eval`` never materialises the logits, so it has nothing a histogram could read."""
         m, eng, st = self.model, self.model.engine, self._val_buffers()
         params = m.flat_params.detach()
         B, K = img.shape[0], m.spec.classes
@@ -160,7 +164,7 @@ class HipTrainer:
         if boundary and distmap is None:
             distmap = distmaps_on_device(mask, K)
         dist = distmap if boundary else None
-        if "GWDICE" in self.losses:
+        if "GWDICE" in self.losses or curves:
             if m.precision == "bf16":
                 logits, am = eng.forward_bf16_eval(x, params, m.bn_state, want_argmax="uint8")
             else:
@@ -168,26 +172,29 @@ class HipTrainer:
             parts, err, _ = loss_forward(logits, mask, dist, {"losses": self.losses, "alpha": alpha})
             _, err_cm = confusion_matrix(am, mask, lu, K=K, counts=st["counts"])
             torch.maximum(st["err"], torch.maximum(err, err_cm), out=st["err"])
+            if curves:
+                prob_histogram(logits, mask, lu, hist=st["hist"], err=st["err"], logits=True)
         else:
             head = eng.forward_bf16_eval_head if m.precision == "bf16" else eng.forward_eval_head
             acc, _, _, _ = head(x, params, m.bn_state, mask, lu, dist, 2.0, st["counts"], st["err"])
             parts = loss_algebra(acc, self.losses, B, K, H, W, dist is not None, alpha)[0]
         eval_accumulate(parts, float(B), st["epoch"])
 
-    def _val_graph_batch(self, img, mask, lu, distmap, alpha):
+    def _val_graph_batch(self, img, mask, lu, distmap, alpha, curves=False):
         """``_val_batch`` through ``GraphReplay``: a captured graph per key, after two eager batches of that key (a
         validation set whose last batch is smaller keeps one graph per batch size).  alpha is baked into the captured
         blend: it belongs to the key where it is read (BOUNDARY-RAMPED)"""
         key = (tuple(img.shape), img.dtype, tuple(mask.shape), mask.dtype,
                None if lu is None else (tuple(lu.shape), lu.dtype),
                None if distmap is None else (tuple(distmap.shape), distmap.dtype),
-               self.model.precision, self.losses, float(alpha) if "BOUNDARY-RAMPED" in self.losses else None)
+               self.model.precision, self.losses, float(alpha) if "BOUNDARY-RAMPED" in self.losses else None) + \
+            ((True,) if curves else ())
         self._val_buffers()              # (a moved model drops the graphs)
         self._val_replays.get(key, lambda: GraphReplay(
-            self.model.engine, lambda *batch: self._val_batch(*batch, alpha), warmup=2))(img, mask, lu, distmap)
+            self.model.engine, lambda *batch: self._val_batch(*batch, alpha, curves), warmup=2))(img, mask, lu, distmap)
 
     @torch.no_grad()
-    def validate(self, loader, to_device=None, stage: str = "val", alpha: float = 1.0) -> dict:
+    def validate(self, loader, to_device=None, stage: str = "val", alpha: float = 1.0, curves: bool = False) -> dict:
         """One validation epoch: eval-mode BatchNorm in this trainer's precision; per batch the loss terms of
         ``self.losses`` and both F-scores as ``SemSegment.validation_step`` logs them, the confusion counts over all pixels
         and over ``lu == 1``.  Batches are ``(img, mask[, distmap[, lu[, stats]]])`` tuples or the datamodule's dicts;
@@ -203,8 +210,19 @@ class HipTrainer:
         all-reduce, so every rank sees the same numbers).  graph=True replays a captured batch (one host synchronisation
         per new key, when it is captured).  A label outside [0, K) raises the AssertionError of ``_check_labels``.
         Left as found: the train / eval flags of the model and of ``model.encoder``, the freeze, ``bn_state``,
-        ``num_batches_tracked``, the parameters and the captured training graph."""
+        ``num_batches_tracked``, the parameters and the captured training graph.
+
+        ``curves=True`` also collects, per class, the histogram of the predicted probability split by ground truth (over
+        all pixels and over ``lu == 1``) and returns it under "curves" as a ``ProbabilityCurves`` (``loss/curves.py``:
+        precision / recall, ROC, F1 and the best threshold of every operating point, not the arg-max alone), with the
+        model's class names when it has them.  Every batch then takes the unfused chain (logits -> ``loss_forward`` ->
+        ``confusion_matrix`` -> one ``prob_histogram`` of the logits): the fused ``dt_head_eval`` path is not used with
+        curves because it never materialises the logits.  The counts are exact; the real-valued metrics are those of
+        ``curves=False`` to fp32 summation order.  The histogram travels in the epoch's one transfer (and all-reduce) as
+        fp64, exact below 2^53 like the confusion counts.  With ``curves=False`` not one launch differs from before."""
         from .network.segmodel import create_combined_batch
+        if not isinstance(curves, (bool,)):
+            raise ValueError(f"validate: curves must be True or False, got {curves!r}")
         m = self.model
         K = m.spec.classes
         st = self._val_buffers()
@@ -228,18 +246,28 @@ class HipTrainer:
                 mask = mask.long()
             if lu is not None and lu.dtype != torch.int64:
                 lu = lu.long()
-            run(img, mask, lu, distmap, alpha)
+            run(img, mask, lu, distmap, alpha, curves) if curves else run(img, mask, lu, distmap, alpha)
             batches += 1
         if batches == 0:
             raise ValueError("validate: no batches")
         # the one transfer of the epoch: nine doubles, the counts (exact in fp64 below 2^53) and the label flag
-        buf = torch.cat([st["epoch"], st["counts"].reshape(-1).double(), st["err"].double()])
+        parts = [st["epoch"], st["counts"].reshape(-1).double()]
+        if curves:
+            parts.append(st["hist"].reshape(-1).double())
+        buf = torch.cat(parts + [st["err"].double()])
         if self.reducer and self.world > 1:
             self.reducer.dist.all_reduce(buf, op=self.reducer.dist.ReduceOp.SUM, group=self.reducer.group)
         host = buf.cpu()
         if float(host[-1]) != 0.0:
             raise AssertionError(f"labels outside [0, {K}) were seen this epoch (class2one_hot)")
-        return epoch_metrics(host[:9], host[9:9 + 2 * K * K].reshape(2, K, K), self.losses, stage, batches)
+        out = epoch_metrics(host[:9], host[9:9 + 2 * K * K].reshape(2, K, K), self.losses, stage, batches)
+        if curves:
+            from .loss.curves import ProbabilityCurves
+            names = getattr(m, "classes", None)
+            names = list(names) if isinstance(names, (list, tuple)) and len(names) == K else None
+            hist = host[9 + 2 * K * K:-1].reshape(2, K, 2, 256).to(torch.int64).numpy()
+            out["curves"] = ProbabilityCurves(hist, names)
+        return out
 
     def step(self, img: torch.Tensor, mask: torch.Tensor, distmap: Optional[torch.Tensor] = None,
              alpha: float = 1.0):
@@ -631,7 +659,7 @@ def checkpoint_writer(trainer: "HipTrainer", pl_module=None, training_conf: Opti
 
 def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: int = 10, to_device=None,
         on_epoch_end=None, callbacks=None, pl_module=None, swa=None, val_loader=None, check_val_every_n_epoch: int = 1,
-        checkpoint=None, early_stopping=None):
+        checkpoint=None, early_stopping=None, curves: bool = False):
     """Minimal stand-in for ``Trainer.fit`` on the hot path (reference deadtrees/train.py:113): per-batch
     ``HipTrainer.step`` and the per-epoch ``CosineAnnealingLR(T_max)`` of segmodel.py:426-428.
 
@@ -648,6 +676,9 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
     early_stopping: an ``EarlyStoppingConfig`` — the loop ends after the epoch in which patience runs out (or the
     monitored value is not finite).  The rules are those of ``ModelSelection``.  Validation sees the current weights,
     not the SWA average (as under Lightning's SWA callback); the SWA swap and recalibration run after the loop.
+    curves=True: ``validate(..., curves=True)``; the ``ProbabilityCurves`` object stays out of the history (as the ``cm_*``
+    matrices do) and its scalars go in, for every class c >= 1: "val/ap_<c>", "val/roc_auc_<c>", "val/best_f1_<c>" and
+    "val/best_threshold_<c>" (the float T / 65535).  Monitors stay restricted to ``validation_keys``.
 
     swa: None | True | SWAConfig — the loop of torch's SWA documentation on a ``HipTrainer(average="swa")``: epochs before
     ``swa_start`` keep the cosine schedule (or whatever a callback put in its place); from ``swa_start`` the rate follows
@@ -662,6 +693,10 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
     if checkpoint is not None or early_stopping is not None:      # (a plain loop asks nothing new of `trainer`)
         checkpoint = resolve_checkpoint(checkpoint, trainer.losses)
         early_stopping = resolve_early_stopping(early_stopping, trainer.losses)
+    if not isinstance(curves, bool):
+        raise ValueError(f"fit(curves=...): True or False, not {curves!r}")
+    if curves and val_loader is None:
+        raise ValueError("fit(curves=True) collects its histograms during validation: give val_loader")
     if int(check_val_every_n_epoch) != check_val_every_n_epoch or check_val_every_n_epoch < 1:
         raise ValueError(f"check_val_every_n_epoch {check_val_every_n_epoch!r}: an integer >= 1")
     if val_loader is None and (checkpoint is not None or early_stopping is not None):
@@ -707,8 +742,11 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
             history[-1]["swa/n_averaged"] = trainer.averager.n_averaged
         stop = False
         if val_loader is not None and (epoch + 1) % check_val_every_n_epoch == 0:
-            val = trainer.validate(val_loader, to_device=to_device, alpha=alpha)
-            history[-1].update({k: v for k, v in val.items() if not k.startswith("cm_")})
+            val = (trainer.validate(val_loader, to_device=to_device, alpha=alpha, curves=True) if curves
+                   else trainer.validate(val_loader, to_device=to_device, alpha=alpha))
+            history[-1].update({k: v for k, v in val.items() if not k.startswith("cm_") and k != "curves"})
+            if curves:
+                history[-1].update(val["curves"].summary("val"))
             if select is not None:
                 stop = select.update(epoch, val)
         if on_epoch_end:

@@ -576,6 +576,26 @@ int dt_patch_attributes_u8(const int32_t* labels, const uint8_t* raster, int C, 
                            int n, const uint8_t* classes, const float* probs, int K, const int* pairs, int n_pairs,
                            int64_t* sums, int32_t* extremes, void* stream);
 
+/* Operating points (deadtrees_amd/loss/curves.py states the contract): probability histograms of a validation epoch and the
+ * decision that applies a threshold per class.  Both quantise a probability p the same way:
+ * q = floor(min(max(p, 0), 1) * 65535 + 0.5), product and sum each rounded to fp32, NaN -> 0; bin = q >> 8.
+ *
+ * dt_curve_chunk: the consecutive pixels of the B * H * W axis one workgroup of dt_prob_histogram takes.
+ * dt_prob_histogram: src fp32 [B][K][H][W], probabilities or, with is_logits != 0, logits (they pass through the channel
+ *   softmax of dt_seg_loss_fwd first), labels int64 [B][H][W], lu int64 [B][H][W] or NULL, 2 <= K <= 8, any alignment.
+ *   hist int64 [2][K][2][256] (+=, as dt_confusion_matrix: one buffer collects an epoch): hist[plane][c][t][bin] counts the
+ *   pixels whose q of class c falls into bin, t = 1 iff label == c; plane 0 every pixel, plane 1 those with lu == 1 (lu
+ *   NULL: plane 1 is not touched).  A label outside [0, K) sets err_flag[0] = 1 and the pixel enters no count.  q_out
+ *   uint16 [B][K][H][W] or NULL: every q, out-of-range pixels included.  One launch, integer atomics only: exact and
+ *   independent of the order; no synchronisation.
+ * dt_decide_classes_u8: probs fp32 [K][n] in device memory, thresholds a HOST array uint16 [K] (entry 0 is not read, the
+ *   others in 1..65535).  out_u8[i] = the class c >= 1 with the largest q_c(i) among those with q_c(i) >= thresholds[c],
+ *   ties -> the smallest c; 0 without one.  Every byte of out_u8 [n] is written; plane 0 of probs is not read. */
+int dt_curve_chunk(int* chunk);
+int dt_prob_histogram(const float* src, const int64_t* labels, const int64_t* lu, int64_t* hist, int32_t* err_flag,
+                      uint16_t* q_out, int B, int K, int H, int W, int is_logits, void* stream);
+int dt_decide_classes_u8(const float* probs, const uint16_t* thresholds, uint8_t* out_u8, int K, int64_t n, void* stream);
+
 /* Training samples from an ortho raster (the array arithmetic of scripts/createdataset.py:53-194 and
  * scripts/computestats.py:111-161; deadtrees_amd/data/rasters.py states the contract in numpy).  rgbn_chw uint8 [4][h][w]
  * with 1 <= h, w <= S is the top-left corner of a zero [4][S][S] array; mask / lu uint8 [h][w] are padded the same way.
