@@ -189,7 +189,12 @@ SIGNATURES = {
     "dt_curve_chunk": (C.c_int, [C.POINTER(C.c_int)]),
     "dt_prob_histogram": (C.c_int, [c_f, c_f, c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f]),
     "dt_decide_classes_u8": (C.c_int, [c_f, C.POINTER(C.c_uint16), c_f, C.c_int, I64, c_f]),
-    "dt_signed_distmap_workspace": (I64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dt_support_span": (C.c_int, [C.POINTER(C.c_int)]),
+    "dt_decide_candidates_u8": (C.c_int, [c_f, C.POINTER(C.c_uint16), c_f, c_f, C.c_int, I64, c_f]),
+    "dt_patch_support": (C.c_int, [c_f, c_f, C.c_int, C.c_int, c_f, c_f, c_f, c_f]),
+    "dt_reject_patches_u8": (C.c_int, [c_f, c_f, c_f, c_f, c_f, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.c_int,
+                                       C.c_int, C.c_int, c_f]),
+    "dt_signed_distmap_workspace":(I64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "dt_signed_distmap": (C.c_int, [c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, c_f]),
     "dt_conv2d_bf16_stat_rows": (C.c_int, [_P]),
     "dt_conv2d_bf16_config": (C.c_int, [_P] + [C.POINTER(C.c_int)] * 4),

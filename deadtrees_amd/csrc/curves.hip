@@ -1,6 +1,7 @@
 // Operating points (deadtrees_amd/loss/curves.py holds the contract): the per-class histogram of the predicted
 // probability split by ground truth, accumulated on the device during validation, and the decision kernel that applies a
-// threshold per class to stitched probabilities.  Both ends quantise a probability to the same 16-bit integer q (the rule
+// threshold per class to stitched probabilities, pixel by pixel or patch by patch (hysteresis and a confidence filter: the
+// last part of this file).  All of them quantise a probability to the same 16-bit integer q (the rule
 // of attributes.hip's confidence: clip to [0, 1], NaN -> 0, floor(p * 65535 + 0.5) in two fp32 roundings), so a curve
 // read at a threshold describes the maps decided at that threshold exactly.  Counts are integers: the histogram does not
 // depend on the order in which pixels, workgroups, batches or ranks arrive.
@@ -19,6 +20,7 @@
 
 #include "conv_host.h"
 #include "loss_softmax.h"
+#include "patch_runs.h"
 
 #define CURVE_CHUNK 16384                // pixels per workgroup: 512 workgroups at B = 32, 512 x 512
 #define CURVE_MAXK 8                     // classes
@@ -206,13 +208,17 @@ extern "C" int dt_prob_histogram(const float* src, const int64_t* labels, const 
 
 // ---------------------------------------------------------------- decision
 // Pixel i takes the class c >= 1 with the largest q_c(i) among those with q_c(i) >= T_c (ties -> the smallest c), class 0
-// without one.  4 pixels per lane, one 16-byte load per class plane where it lines up; plane 0 is never read.
+// without one.  4 pixels per lane, one 16-byte load per class plane where it lines up; plane 0 is never read.  QOWN (the
+// candidates of a patch-wise decision): the winner's q goes into a uint16 plane as well, 0 on class 0.
 struct curve_thresholds {
   unsigned t[CURVE_MAXK];
 };
 
+// align: bit 0 probs 16-byte, bit 1 out 4-byte, bit 2 q_own 8-byte aligned
+template <bool QOWN>
 __global__ __launch_bounds__(256) void decide_classes_kernel(const float* __restrict__ probs, curve_thresholds thr,
-                                                             uint8_t* __restrict__ out, int K, int64_t n, int align) {
+                                                             uint8_t* __restrict__ out, uint16_t* __restrict__ q_own, int K,
+                                                             int64_t n, int align) {
   const int64_t g = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   if (g >= n) return;
   const bool whole = g + 3 < n;
@@ -244,6 +250,26 @@ __global__ __launch_bounds__(256) void decide_classes_kernel(const float* __rest
     for (int j = 0; j < 4; ++j)
       if (g + j < n) out[g + j] = (uint8_t)best[j];
   }
+  if constexpr (QOWN) {
+    if (whole && (align & 4)) {
+      *reinterpret_cast<u16x4*>(q_own + g) =
+          u16x4{(unsigned short)bq[0], (unsigned short)bq[1], (unsigned short)bq[2], (unsigned short)bq[3]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (g + j < n) q_own[g + j] = (uint16_t)bq[j];
+    }
+  }
+}
+
+// thresholds[1 .. K - 1] -> thr, each in 1..65535
+static int curve_read_thresholds(const char* tag, const uint16_t* thresholds, int K, curve_thresholds& thr) {
+  for (int c = 0; c < CURVE_MAXK; ++c) thr.t[c] = 0u;
+  for (int c = 1; c < K; ++c) {
+    DT_REQUIRE(thresholds[c] >= 1, "%s: the threshold of class %d must be in 1..65535", tag, c);
+    thr.t[c] = thresholds[c];
+  }
+  return DT_OK;
 }
 
 extern "C" int dt_decide_classes_u8(const float* probs, const uint16_t* thresholds, uint8_t* out_u8, int K, int64_t n,
@@ -252,16 +278,249 @@ extern "C" int dt_decide_classes_u8(const float* probs, const uint16_t* threshol
   DT_REQUIRE(K >= 2 && K <= CURVE_MAXK, "decide_classes_u8: K=%d unsupported (2..%d)", K, CURVE_MAXK);
   DT_REQUIRE(n >= 1, "decide_classes_u8: n=%lld pixels", (long long)n);
   curve_thresholds thr;
-  for (int c = 0; c < CURVE_MAXK; ++c) thr.t[c] = 0u;
-  for (int c = 1; c < K; ++c) {
-    DT_REQUIRE(thresholds[c] >= 1, "decide_classes_u8: the threshold of class %d must be in 1..65535", c);
-    thr.t[c] = thresholds[c];
-  }
+  DT_TRY(curve_read_thresholds("decide_classes_u8", thresholds, K, thr));
   const int64_t groups = (n + CURVE_STEP - 1) / CURVE_STEP;
   DT_REQUIRE(groups <= INT_MAX, "decide_classes_u8: %lld pixels are more than one launch takes", (long long)n);
   const int align = (curve_aligned(probs, 16) ? 1 : 0) | (curve_aligned(out_u8, 4) ? 2 : 0);
-  hipLaunchKernelGGL(decide_classes_kernel, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, probs, thr, out_u8, K, n,
-                     align);
+  hipLaunchKernelGGL(decide_classes_kernel<false>, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, probs, thr,
+                     out_u8, (uint16_t*)nullptr, K, n, align);
+  DT_LAUNCH_CHECK();
+  return DT_OK;
+}
+
+// ---------------------------------------------------------------- patch-wise decision (hysteresis, confidence filter)
+// Candidates at the low thresholds (decide_classes_kernel<true>), their label plane (patches.hip), then two launches here:
+// the support of every patch — the maximum, the sum and the count of its pixels' own q, in planes indexed by the root
+// (label - 1) — and the rejection of the patches that lack a pixel at T_c or a mean of M_c.  Integers only: the planes do
+// not depend on the order in which runs arrive.
+//
+// patch_support_kernel walks the pixels as patch_attributes_kernel does: a wave owns HY_SPAN consecutive 64-pixel chunks,
+// pt_runs finds the runs of equal label (a run may wrap a row end: nothing here is geometry), a segmented scan gives every
+// run its maximum and its 32-bit partial sum (64 terms of at most 65535), the run still open at the end of a chunk is
+// carried in 64 bits, and a finished run writes once per quantity.  Two things keep one raster-sized patch from queueing
+// every wave on one address: the atomic max is skipped when a relaxed load already shows a value that is large enough (a
+// hint: a stale value only costs the atomic), and the runs the four waves of a workgroup END with go through LDS, where
+// equal labels are combined before one lane writes them — a workgroup inside one patch issues one write per quantity.
+#define HY_SPAN 16                       // 64-pixel chunks per wave
+#define HY_MAX_SIDE 16384
+#define HY_MAX_PIXELS 2147483646ll       // labels are int32 and 1-based
+#define HY_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+struct hy_run {
+  int label, qmax, count;
+  unsigned long long sum;
+};
+
+template <bool SUMS>
+__device__ __forceinline__ void hy_emit(const hy_run& r, int32_t* __restrict__ qmax, unsigned long long* __restrict__ qsum,
+                                        int32_t* __restrict__ area) {
+  const int root = r.label - 1;
+  if (HY_LOAD(&qmax[root]) < r.qmax) atomicMax(&qmax[root], r.qmax);
+  if constexpr (SUMS) {
+    atomicAdd(&qsum[root], r.sum);
+    atomicAdd(&area[root], r.count);
+  }
+}
+
+__device__ __forceinline__ void hy_merge(hy_run& into, const hy_run& other) {
+  into.qmax = max(into.qmax, other.qmax);
+  into.sum += other.sum;
+  into.count += other.count;
+}
+
+template <bool SUMS>
+__global__ __launch_bounds__(256) void patch_support_kernel(const int32_t* __restrict__ labels,
+                                                            const uint16_t* __restrict__ q_own, int64_t n,
+                                                            int32_t* __restrict__ qmax, unsigned long long* __restrict__ qsum,
+                                                            int32_t* __restrict__ area) {
+  __shared__ hy_run tail[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t base = ((int64_t)blockIdx.x * 4 + wave) * (HY_SPAN * 64);
+  hy_run carry = {0, 0, 0, 0ull};                          // wave-uniform: the run left open by the previous chunk
+  for (int j = 0; j < HY_SPAN; ++j) {
+    const int64_t i = base + j * 64 + lane;
+    if (i - lane >= n) break;
+    const int label = pt_label_at(labels, i, n);
+    if (__ballot(label != 0) == 0) {                      // background only, most chunks of a real map: q_own is not read
+      if (lane == 0 && carry.label) hy_emit<SUMS>(carry, qmax, qsum, area);
+      carry.label = 0;
+      continue;
+    }
+    const unsigned q = label ? q_own[i] : 0u;             // a label implies i < n
+    bool head;
+    int len;
+    uint64_t heads;
+    pt_runs(label, false, lane, head, len, heads);        // len: the distance to the next head, in every lane
+    // maximum and sum over the lanes lane .. lane + len - 1; background is never written out, so its lanes take no partner
+    const int reach = label ? len : 1;
+    unsigned hi = q, sum = q;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const bool take = d < reach;
+      if (__ballot(take) == 0) break;
+      const unsigned other_hi = __shfl_down(hi, d, 64);
+      if (take) hi = max(hi, other_hi);
+      if constexpr (SUMS) {
+        const unsigned other_sum = __shfl_down(sum, d, 64);
+        if (take) sum += other_sum;
+      }
+    }
+    hy_run run = {label, (int)hi, len, (unsigned long long)sum};
+    const int first = __shfl(label, 0, 64), last_head = 63 - __clzll((long long)heads);
+    if (lane == 0 && carry.label) {
+      if (carry.label == first) hy_merge(run, carry);
+      else hy_emit<SUMS>(carry, qmax, qsum, area);
+    }
+    if (head && lane != last_head && label) hy_emit<SUMS>(run, qmax, qsum, area);
+    carry.label = __shfl(run.label, last_head, 64);
+    carry.qmax = __shfl(run.qmax, last_head, 64);
+    carry.count = __shfl(run.count, last_head, 64);
+    carry.sum = __shfl(run.sum, last_head, 64);
+  }
+  // the runs the four waves end with (label 0: none; a wave past the plane has none): equal neighbours become one write
+  if (lane == 0) tail[wave] = carry;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  hy_run open = {0, 0, 0, 0ull};
+  for (int k = 0; k < 4; ++k) {
+    const hy_run t = tail[k];
+    if (t.label == 0) continue;
+    if (t.label == open.label) {
+      hy_merge(open, t);
+    } else {
+      if (open.label) hy_emit<SUMS>(open, qmax, qsum, area);
+      open = t;
+    }
+  }
+  if (open.label) hy_emit<SUMS>(open, qmax, qsum, area);
+}
+
+// In place: a labelled pixel whose patch fails the core test or the confidence filter becomes class 0.  4 pixels per lane,
+// one 16-byte load of the labels and one packed 4-byte load and store of the classes where they line up.
+// align: bit 0 labels 16-byte, bit 1 classes 4-byte aligned
+template <bool SUMS>
+__global__ __launch_bounds__(256) void reject_patches_kernel(uint8_t* __restrict__ classes, const int32_t* __restrict__ labels,
+                                                             const int32_t* __restrict__ qmax,
+                                                             const long long* __restrict__ qsum,
+                                                             const int32_t* __restrict__ area, curve_thresholds thr,
+                                                             curve_thresholds conf, int K, int64_t n, int align) {
+  const int64_t g = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (g >= n) return;
+  const bool whole = g + 3 < n;
+  int label[4];
+  if (whole && (align & 1)) {
+    const i32x4 l4 = *reinterpret_cast<const i32x4*>(labels + g);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) label[j] = l4[j] > 0 && l4[j] <= n ? l4[j] : 0;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) label[j] = pt_label_at(labels, g + j, n);
+  }
+  if ((label[0] | label[1] | label[2] | label[3]) == 0) return;      // (labels are >= 0 here) background: nothing to write
+  const bool packed = whole && (align & 2);
+  unsigned cls[4];
+  if (packed) {
+    const unsigned c4 = *reinterpret_cast<const unsigned*>(classes + g);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cls[j] = (c4 >> (8 * j)) & 255u;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cls[j] = label[j] ? classes[g + j] : 0u;
+  }
+  // the class a pixel keeps: its own on background and in a kept patch, 0 in a rejected one
+  unsigned kept[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const unsigned c = cls[j];
+    const int root = label[j] ? label[j] - 1 : 0;         // (entry 0 is read for nothing on background)
+    bool keep = c >= 1u && c < (unsigned)K && (unsigned)qmax[root] >= thr.t[c & (CURVE_MAXK - 1)];
+    if constexpr (SUMS) {
+      const unsigned m = conf.t[c & (CURVE_MAXK - 1)];
+      if (keep && m) keep = qsum[root] >= (long long)m * area[root];
+    }
+    kept[j] = keep || label[j] == 0 ? c : 0u;
+  }
+  if (kept[0] == cls[0] && kept[1] == cls[1] && kept[2] == cls[2] && kept[3] == cls[3]) return;
+  if (packed) {
+    *reinterpret_cast<unsigned*>(classes + g) = kept[0] | (kept[1] << 8) | (kept[2] << 16) | (kept[3] << 24);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (label[j]) classes[g + j] = (uint8_t)kept[j];
+  }
+}
+
+static int hy_check_size(const char* tag, int h, int w) {
+  DT_REQUIRE(h >= 1 && w >= 1 && h <= HY_MAX_SIDE && w <= HY_MAX_SIDE && (int64_t)h * w <= HY_MAX_PIXELS,
+             "%s: raster %dx%d: sides must be in 1..%d and h * w <= 2^31 - 2", tag, h, w, HY_MAX_SIDE);
+  return DT_OK;
+}
+
+extern "C" int dt_support_span(int* chunks) {
+  DT_REQUIRE(chunks, "support_span: null pointer");
+  *chunks = HY_SPAN;
+  return DT_OK;
+}
+
+extern "C" int dt_decide_candidates_u8(const float* probs, const uint16_t* low, uint8_t* out_u8, uint16_t* q_own, int K,
+                                       int64_t n, void* stream) {
+  DT_REQUIRE(probs && low && out_u8 && q_own, "decide_candidates_u8: null pointer");
+  DT_REQUIRE(K >= 2 && K <= CURVE_MAXK, "decide_candidates_u8: K=%d unsupported (2..%d)", K, CURVE_MAXK);
+  DT_REQUIRE(n >= 1 && n <= HY_MAX_PIXELS, "decide_candidates_u8: n=%lld pixels (1 .. 2^31 - 2)", (long long)n);
+  curve_thresholds thr;
+  DT_TRY(curve_read_thresholds("decide_candidates_u8", low, K, thr));
+  const int64_t groups = (n + CURVE_STEP - 1) / CURVE_STEP;
+  const int align = (curve_aligned(probs, 16) ? 1 : 0) | (curve_aligned(out_u8, 4) ? 2 : 0) | (curve_aligned(q_own, 8) ? 4 : 0);
+  hipLaunchKernelGGL(decide_classes_kernel<true>, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, probs, thr,
+                     out_u8, q_own, K, n, align);
+  DT_LAUNCH_CHECK();
+  return DT_OK;
+}
+
+extern "C" int dt_patch_support(const int32_t* labels, const uint16_t* q_own, int h, int w, int32_t* qmax, int64_t* qsum,
+                                int32_t* area, void* stream) {
+  DT_REQUIRE(labels && q_own && qmax, "patch_support: null pointer");
+  DT_REQUIRE((qsum == nullptr) == (area == nullptr), "patch_support: the sum plane comes with the area plane");
+  DT_TRY(hy_check_size("patch_support", h, w));
+  const int64_t n = (int64_t)h * w;
+  const dim3 grid((unsigned)((n + 4 * HY_SPAN * 64 - 1) / (4 * HY_SPAN * 64)));
+  if (qsum)
+    hipLaunchKernelGGL(patch_support_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, labels, q_own, n, qmax,
+                       (unsigned long long*)qsum, area);
+  else
+    hipLaunchKernelGGL(patch_support_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, labels, q_own, n, qmax,
+                       (unsigned long long*)nullptr, (int32_t*)nullptr);
+  DT_LAUNCH_CHECK();
+  return DT_OK;
+}
+
+extern "C" int dt_reject_patches_u8(uint8_t* classes, const int32_t* labels, const int32_t* qmax, const int64_t* qsum,
+                                    const int32_t* area, const uint16_t* thresholds, const uint16_t* min_confidence, int K,
+                                    int h, int w, void* stream) {
+  DT_REQUIRE(classes && labels && qmax && thresholds, "reject_patches_u8: null pointer");
+  DT_REQUIRE((qsum == nullptr) == (area == nullptr), "reject_patches_u8: the sum plane comes with the area plane");
+  DT_REQUIRE(K >= 2 && K <= CURVE_MAXK, "reject_patches_u8: K=%d unsupported (2..%d)", K, CURVE_MAXK);
+  DT_TRY(hy_check_size("reject_patches_u8", h, w));
+  curve_thresholds thr, conf;
+  DT_TRY(curve_read_thresholds("reject_patches_u8", thresholds, K, thr));
+  bool filter = false;
+  for (int c = 0; c < CURVE_MAXK; ++c) conf.t[c] = 0u;
+  for (int c = 1; c < K && min_confidence; ++c) {
+    conf.t[c] = min_confidence[c];
+    filter = filter || conf.t[c] != 0u;
+  }
+  DT_REQUIRE(!filter || qsum, "reject_patches_u8: a confidence filter needs the sum and area planes");
+  const int64_t n = (int64_t)h * w;
+  const dim3 grid((unsigned)((n + CURVE_STEP - 1) / CURVE_STEP));
+  const int align = (curve_aligned(labels, 16) ? 1 : 0) | (curve_aligned(classes, 4) ? 2 : 0);
+  if (filter)
+    hipLaunchKernelGGL(reject_patches_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, classes, labels, qmax,
+                       (const long long*)qsum, area, thr, conf, K, n, align);
+  else
+    hipLaunchKernelGGL(reject_patches_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, classes, labels, qmax,
+                       (const long long*)nullptr, (const int32_t*)nullptr, thr, conf, K, n, align);
   DT_LAUNCH_CHECK();
   return DT_OK;
 }

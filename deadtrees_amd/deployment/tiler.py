@@ -394,7 +394,9 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     is, and everything downstream — counts, sieve, patch table, outlines, overlaps, gaps, attributes — sees the decided map;
     ``confidence`` is the probability of the decided class.  The probabilities are returned only when ``return_probs`` asks.
     Validation probabilities are single-tile softmaxes, these are blended ones: the threshold transfers, the bit-for-bit
-    closure of the curves holds for identical inputs.  None: nothing changes."""
+    closure of the curves holds for identical inputs.  A patch-wise decision (``Decision(T, low=..., min_confidence=...,
+    connectivity=...)``: grow patches at the low thresholds, keep those with a pixel at ``T`` and a mean of ``M``) runs
+    through ``ops.decide_patchwise`` in the same place.  None: nothing changes."""
     decision = _check_decision("infer_tile", inference, decision, overlap, blend, tta)
     request = MapAnalysis.of("infer_tile", np.shape(arr_chw_u8)[1:], getattr(inference, "classes", None) if stats else None,
                              zones, against, arr_chw_u8, stats=stats, n_zones=n_zones, patches=patches, outlines=outlines,
@@ -562,8 +564,9 @@ def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.
     outer / window batches inner, no 1/M (finalize normalises) — each pixel's terms arrive model-major, windows ascending,
     views ascending, for every batch size.
 
-    ``decision``: the probabilities are finalized as for ``return_probs`` and ``ops.decide_classes`` overwrites the arg-max
-    plane before ``run_device``; they leave the device only when ``return_probs`` asks."""
+    ``decision``: the probabilities are finalized as for ``return_probs`` and ``ops.decide_classes`` (a patch-wise decision:
+    ``ops.decide_patchwise``) overwrites the arg-max plane before ``run_device``, which relabels the decided map itself;
+    they leave the device only when ``return_probs`` asks."""
     from .. import ops
     _, h, w = arr_chw_u8.shape
     ny, nx, _ = window_grid(h, w, d, overlap)
@@ -604,7 +607,9 @@ def _infer_tile_stitched(inference, models, vote: Optional[str], arr_chw_u8: np.
         acc = accumulate(m, acc)
     if want_probs:
         classes, probs = ops.stitch_finalize(acc, want_probs=True)
-        if decision is not None:
+        if decision is not None and decision.patchwise:
+            ops.decide_patchwise(probs, decision, out=classes)
+        elif decision is not None:
             ops.decide_classes(probs, decision, out=classes)
         return run_device(request, classes, probs if keep_probs else None, planes, raster, return_probs)
     return run_device(request, ops.stitch_finalize(acc), None, planes, raster)

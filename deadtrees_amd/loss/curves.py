@@ -23,12 +23,29 @@ an integer, so device and host compare with ``array_equal``:
   ``c >= 1`` with ``q_c >= T_c``; without a candidate the pixel is class 0, otherwise it takes the candidate with the largest
   ``q_c``, ties to the smallest ``c``.  For K = 2 this is "class 1 iff ``q_1 >= T_1``": whenever ``T_1`` is a multiple of 256,
   the confusion counts of the decided maps ARE ``counts(1)`` at ``j = T_1 / 256``, bit for bit.  For K > 2 the curves are
-  one-vs-rest and the decision is the rule above: the closure is exact for K = 2 only.
+  one-vs-rest and the decision is the rule above: the closure is exact for K = 2 only;
+* patch-wise decision (``ops.decide_patchwise`` on the device, ``decide_patchwise_host`` here): a hysteresis
+  with low thresholds ``1 <= L_c <= T_c`` and a confidence filter ``M_c`` in ``0..65535`` (0: none), for ``probs`` fp32
+  ``[K, h, w]``, sides ``<= 16384``, ``h * w <= 2**31 - 2``, ``2 <= K <= 8``:
+
+  1. ``cand = decide_host(probs, Decision.from_q(L))`` — the pixel rule above at the low thresholds;
+  2. ``labels = label_patches_host(cand, K, connectivity)`` — the label plane of ``deployment/patches.py``;
+  3. per patch ``P`` of class ``c``, with ``q(p) = quantise(probs[c, p])``: ``qmax = max q``, ``S = sum q`` (int64),
+     ``A = |P|``; ``P`` is kept iff ``qmax >= T_c`` and ``S >= M_c * A``, a 64-bit integer compare;
+  4. the result is ``cand`` on kept patches and 0 elsewhere.
+
+  With ``L = T`` and no ``M`` this is ``decide_host(probs, Decision(T))`` (every candidate is its own proof).  For K = 2
+  and no ``M``, pixel by pixel: decided at ``T`` ⊆ result ⊆ decided at ``L``.  For K > 2 only the rule itself holds — a pixel
+  that is class 1 at ``T`` can be a class-2 candidate at ``L`` (``q_2 >= L_2`` and ``q_2 > q_1``), as the curves above are
+  one-vs-rest.  Relabelling the result with the same connectivity gives exactly the kept patches of ``cand``, with their
+  roots: a patch goes or stays whole, and two kept patches of one class never touch.  Out of scope: validation-side
+  curves over ``(L, T)`` pairs, object-level precision / recall sweeps, the ``against`` map, decisions stored in
+  checkpoints, temperature scaling.
 
 Validation probabilities are single-tile softmaxes and raster probabilities are blended ones (``infer_tile`` with
 ``blend="average"``): a threshold transfers, but the exact closure is a statement about identical inputs.
 
-numpy and the standard library only.
+numpy and the standard library only (the patch-wise host rule labels with ``label_patches_host``, which imports scipy lazily).
 """
 from __future__ import annotations
 
@@ -250,54 +267,115 @@ def _threshold(c, t) -> int:
     raise ValueError(f"Decision: threshold {t!r} of class {c}: a float in (0, 1] or an int in 1..{Q_SCALE}")
 
 
+def _class_thresholds(thresholds, what: str) -> dict:
+    """a mapping class -> threshold, parsed by ``_threshold``: ``{c: q}`` in ascending ``c``"""
+    if not isinstance(thresholds, Mapping):
+        raise ValueError(f"Decision: {what} must be a mapping class -> threshold, got {thresholds!r}")
+    q = {}
+    for c, t in thresholds.items():
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 1 <= c < MAX_CLASSES:
+            raise ValueError(f"Decision: class {c!r} is not in 1..{MAX_CLASSES - 1}")
+        q[int(c)] = _threshold(c, t)
+    return {c: q[c] for c in sorted(q)}
+
+
 class Decision:
     """a threshold per class ``1..K-1``: ``Decision({1: 0.3})`` for K = 2, ``Decision({1: 0.3, 2: 0.5})`` for K = 3.  A float in
     ``(0, 1]`` becomes ``T = floor(t * 65535 + 0.5)`` (float64, clipped to ``[1, 65535]``), an int is taken as ``T``
     (``Decision.from_q`` takes integers only).  Every class from 1 to the largest one named must be there; ``K`` is that
-    largest class + 1 and must be the model's.  The rule is the module's contract."""
+    largest class + 1 and must be the model's.  The rule is the module's contract.
 
-    def __init__(self, thresholds: Mapping[int, float]):
+    Patch-wise (``decide_patchwise_host`` states the rule): ``low`` names a low threshold ``L_c <= T_c`` for exactly the
+    classes of ``thresholds`` (None: ``L = T``), ``min_confidence`` a minimum mean ``M_c`` of a patch's quantised probability
+    for any of them (absent: 0, no filter), both parsed like ``thresholds``; ``connectivity`` (4 or 8) is that of the
+    candidates' patches.  ``patchwise`` tells whether any of this changes a map: a decision with ``L = T`` and no ``M`` IS
+    the plain decision — it compares equal to it, prints like it and takes its code path."""
+
+    def __init__(self, thresholds: Mapping[int, float], low: Optional[Mapping[int, float]] = None,
+                 min_confidence: Optional[Mapping[int, float]] = None, connectivity: int = 8):
         if not isinstance(thresholds, Mapping) or not thresholds:
             raise ValueError(f"Decision: a non-empty mapping class -> threshold, got {thresholds!r}")
-        q = {}
-        for c, t in thresholds.items():
-            if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 1 <= c < MAX_CLASSES:
-                raise ValueError(f"Decision: class {c!r} is not in 1..{MAX_CLASSES - 1}")
-            q[int(c)] = _threshold(c, t)
+        q = _class_thresholds(thresholds, "thresholds")
         missing = sorted(set(range(1, max(q) + 1)) - set(q))
         if missing:
             raise ValueError(f"Decision: no threshold for class(es) {missing}: every class 1..K-1 must be named")
-        self.q = {c: q[c] for c in sorted(q)}
+        self.q = q
+        if isinstance(connectivity, (bool, np.bool_)) or connectivity not in (4, 8):
+            raise ValueError(f"Decision: connectivity must be 4 or 8, got {connectivity!r}")
+        self.connectivity = int(connectivity)
+        self.low = dict(q)
+        if low is not None:
+            self.low = _class_thresholds(low, "low")
+            if set(self.low) != set(q):
+                raise ValueError(f"Decision: low names the classes {sorted(self.low)}, thresholds the classes {sorted(q)}: "
+                                 "they must be the same")
+            above = [c for c in q if self.low[c] > q[c]]
+            if above:
+                raise ValueError(f"Decision: low threshold above the high one for class(es) {above}: "
+                                 f"low {self.low}, thresholds {q} (on the q axis)")
+        self.min_confidence = {}
+        if min_confidence is not None:
+            self.min_confidence = _class_thresholds(min_confidence, "min_confidence")
+            unknown = sorted(set(self.min_confidence) - set(q))
+            if unknown:
+                raise ValueError(f"Decision: min_confidence names class(es) {unknown} that thresholds does not")
 
     @classmethod
-    def from_q(cls, thresholds: Mapping[int, int]) -> "Decision":
-        """thresholds given as integers ``T`` on the ``q`` axis, taken as they are"""
-        if isinstance(thresholds, Mapping):
-            for c, t in thresholds.items():
-                if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)):
-                    raise ValueError(f"Decision.from_q: threshold {t!r} of class {c!r} is not an integer")
-        return cls(thresholds)
+    def from_q(cls, thresholds: Mapping[int, int], low: Optional[Mapping[int, int]] = None,
+               min_confidence: Optional[Mapping[int, int]] = None, connectivity: int = 8) -> "Decision":
+        """thresholds given as integers ``T`` (``L``, ``M``) on the ``q`` axis, taken as they are"""
+        for given in (thresholds, low, min_confidence):
+            if isinstance(given, Mapping):
+                for c, t in given.items():
+                    if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)):
+                        raise ValueError(f"Decision.from_q: threshold {t!r} of class {c!r} is not an integer")
+        return cls(thresholds, low=low, min_confidence=min_confidence, connectivity=connectivity)
 
     @property
     def K(self) -> int:
         return len(self.q) + 1
 
-    def thresholds_u16(self, K: Optional[int] = None) -> np.ndarray:
-        """uint16 [K]: ``T_c`` at index ``c``, 0 (not read) at index 0; a ``K`` other than this decision's is a ``ValueError``"""
+    @property
+    def patchwise(self) -> bool:
+        """True iff some ``L_c < T_c`` or some ``M_c > 0``: the decision looks at patches, not at pixels alone"""
+        return self.low != self.q or bool(self.min_confidence)
+
+    def _u16(self, values: Mapping[int, int], K: Optional[int]) -> np.ndarray:
         if K is not None and int(K) != self.K:
             raise ValueError(f"Decision: thresholds for the classes 1..{self.K - 1}, but K={K}: every class 1..K-1 must be "
                              "named, and no other")
-        return np.array([0] + [self.q[c] for c in range(1, self.K)], dtype=np.uint16)
+        return np.array([0] + [values.get(c, 0) for c in range(1, self.K)], dtype=np.uint16)
+
+    def thresholds_u16(self, K: Optional[int] = None) -> np.ndarray:
+        """uint16 [K]: ``T_c`` at index ``c``, 0 (not read) at index 0; a ``K`` other than this decision's is a ``ValueError``"""
+        return self._u16(self.q, K)
+
+    def low_u16(self, K: Optional[int] = None) -> np.ndarray:
+        """uint16 [K]: ``L_c`` at index ``c`` (``T_c`` without ``low``), 0 at index 0"""
+        return self._u16(self.low, K)
+
+    def min_confidence_u16(self, K: Optional[int] = None) -> np.ndarray:
+        """uint16 [K]: ``M_c`` at index ``c``, 0 for a class without a filter and at index 0"""
+        return self._u16(self.min_confidence, K)
+
+    def _key(self):
+        if not self.patchwise:                                     # the connectivity of a pixel rule changes no map
+            return (self.q,)
+        return self.q, self.low, self.min_confidence, self.connectivity
 
     def __eq__(self, other) -> bool:
         if not isinstance(other, Decision):
             return NotImplemented
-        return self.q == other.q
+        return self._key() == other._key()
 
     __hash__ = None
 
     def __repr__(self) -> str:
-        return f"Decision.from_q({self.q!r})"
+        if not self.patchwise:
+            return f"Decision.from_q({self.q!r})"
+        low = f", low={self.low!r}" if self.low != self.q else ""
+        conf = f", min_confidence={self.min_confidence!r}" if self.min_confidence else ""
+        return f"Decision.from_q({self.q!r}{low}{conf}, connectivity={self.connectivity})"
 
 
 def check_decision(option, K: Optional[int], caller: str) -> Optional[Decision]:
@@ -322,3 +400,65 @@ def decide_host(probs, decision: Decision) -> np.ndarray:
     q = np.where(q >= T[1:].reshape((-1,) + (1,) * (probs.ndim - 1)), q, -1)
     best = np.argmax(q, axis=0)                                   # the first of equal maxima: the smallest class
     return np.where(np.take_along_axis(q, best[None], 0)[0] >= 0, best + 1, 0).astype(np.uint8)
+
+
+# ---------------------------------------------------------------------- patch-wise decisions
+MAX_SIDE = 16384
+MAX_PIXELS = 2 ** 31 - 2      # labels are int32 and 1-based (``deployment/patches.py``)
+
+
+def _check_plane_shape(shape, what: str) -> None:
+    if len(shape) != 2 or min(shape) < 1 or max(shape) > MAX_SIDE or shape[0] * shape[1] > MAX_PIXELS:
+        raise ValueError(f"{what}: a plane of shape {tuple(shape)}: sides in 1..{MAX_SIDE} and h * w <= {MAX_PIXELS}")
+
+
+def patch_support_host(probs, cand, labels):
+    """the numpy form of the support pass (``dt_patch_support``): fp32 ``[K, h, w]`` probabilities, the candidates' uint8 class
+    map and its int32 label plane -> ``(roots, cls, qmax, qsum, area)``, one entry per patch in ascending root: ``roots``
+    int64 (label - 1), ``cls`` uint8, and over the patch's pixels the maximum (int64), the sum (int64) and the count (int64)
+    of ``q`` of the pixel's own class.  Integer arithmetic throughout"""
+    probs = np.asarray(probs, dtype=np.float32)
+    cand, labels = np.asarray(cand), np.asarray(labels)
+    if probs.ndim != 3 or not 2 <= probs.shape[0] <= MAX_CLASSES:
+        raise ValueError(f"patch_support_host: probs must be [K, h, w] with K in 2..{MAX_CLASSES}, got shape {probs.shape}")
+    _check_plane_shape(probs.shape[1:], "patch_support_host")
+    if cand.dtype != np.uint8 or labels.dtype != np.int32 or cand.shape != probs.shape[1:] or labels.shape != cand.shape:
+        raise ValueError(f"patch_support_host: a uint8 class map and an int32 label plane of shape {probs.shape[1:]}, got "
+                         f"{cand.dtype} {cand.shape} and {labels.dtype} {labels.shape}")
+    if cand.size and int(cand.max()) >= probs.shape[0]:
+        raise ValueError(f"patch_support_host: class value {int(cand.max())} out of range (K={probs.shape[0]})")
+    flat = labels.ravel()
+    at = np.flatnonzero(flat)
+    if at.size == 0:
+        empty = np.zeros(0, np.int64)
+        return empty, np.zeros(0, np.uint8), empty.copy(), empty.copy(), empty.copy()
+    q = quantise(np.take_along_axis(probs.reshape(probs.shape[0], -1), cand.reshape(1, -1).astype(np.int64), 0)[0][at])
+    order = np.argsort(flat[at], kind="stable")
+    sorted_labels = flat[at][order]
+    starts = np.flatnonzero(np.concatenate([[True], sorted_labels[1:] != sorted_labels[:-1]]))
+    roots = sorted_labels[starts].astype(np.int64) - 1
+    q = q[order].astype(np.int64)
+    area = np.diff(np.concatenate([starts, [sorted_labels.size]])).astype(np.int64)
+    return roots, cand.ravel()[roots], np.maximum.reduceat(q, starts), np.add.reduceat(q, starts), area
+
+
+def decide_patchwise_host(probs, decision: Decision) -> np.ndarray:
+    """the numpy form of ``ops.decide_patchwise``, the patch-wise rule of the contract: fp32 ``[K, h, w]`` probabilities ->
+    uint8 ``[h, w]``.  Candidates at the low thresholds, their patches (``label_patches_host`` with the decision's
+    connectivity), and a patch of class ``c`` is kept iff ``max q >= T_c`` and ``sum q >= M_c * area`` (64-bit integers);
+    the pixels of every other patch become class 0"""
+    from ..deployment.patches import label_patches_host
+    probs = np.asarray(probs, dtype=np.float32)
+    if probs.ndim != 3:
+        raise ValueError(f"decide_patchwise_host: probs must be [K, h, w], got shape {probs.shape}")
+    K = probs.shape[0]
+    _check_plane_shape(probs.shape[1:], "decide_patchwise_host")
+    T = decision.thresholds_u16(K).astype(np.int64)
+    L, M = decision.low_u16(K), decision.min_confidence_u16(K).astype(np.int64)
+    cand = decide_host(probs, Decision.from_q({c: int(L[c]) for c in range(1, K)}))
+    labels = label_patches_host(cand, K, decision.connectivity)
+    roots, cls, qmax, qsum, area = patch_support_host(probs, cand, labels)
+    keep = (qmax >= T[cls]) & (qsum >= M[cls] * area)
+    kept = np.zeros(labels.size + 1, bool)                      # by label; label 0 is background
+    kept[roots[keep] + 1] = True
+    return np.where(kept[labels], cand, 0).astype(np.uint8)

@@ -622,6 +622,49 @@ def decide_classes(probs, decision_or_thresholds, out=None):
     return out
 
 
+def decide_patchwise(probs, decision, out=None, return_support: bool = False):
+    """the patch-wise decision of ``loss/curves.py`` (hysteresis and confidence filter): ``probs`` contiguous fp32 [K, h, w]
+    -> uint8 class map [h, w] (``out``: written in place).  Four steps on the stream, no host synchronisation and no scalar
+    read back: candidates at the low thresholds with their own q (``dt_decide_candidates_u8``), their label plane
+    (``label_patches`` with the decision's connectivity), the per-root maximum / sum / count of q (``dt_patch_support``;
+    sum and count only with a confidence filter) and the rejection in place (``dt_reject_patches_u8``).  Workspace next to
+    the map: 2 + 4 + 4 bytes per pixel, 12 more with a confidence filter.  A decision that is not ``patchwise`` goes
+    through ``decide_classes``.  ``return_support=True`` -> ``(classes, labels, qmax, qsum | None, area | None)``: the label
+    plane int32 [h, w] of the CANDIDATES and the planes int32 / int64 / int32 [h * w], indexed by root, as the support pass
+    left them."""
+    from .loss.curves import Decision
+    _gpu(probs, out)
+    if probs.dtype != torch.float32 or probs.dim() != 3 or not probs.is_contiguous() or probs.numel() == 0:
+        raise RuntimeError("decide_patchwise: probs must be non-empty contiguous float32 [K, h, w]")
+    if not isinstance(decision, Decision):
+        raise ValueError(f"decide_patchwise: decision must be a Decision, got {decision!r}")
+    K, h, w = probs.shape
+    high, low, conf = (a(K) for a in (decision.thresholds_u16, decision.low_u16, decision.min_confidence_u16))
+    if max(h, w) > 16384 or h * w > 2 ** 31 - 2:
+        raise RuntimeError(f"decide_patchwise: raster {h}x{w}: sides must be <= 16384 and h * w <= 2^31 - 2")
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (h, w) or out.device != probs.device
+                            or not out.is_contiguous()):
+        raise RuntimeError(f"decide_patchwise: out must be contiguous uint8 {(h, w)} on {probs.device}")
+    if not decision.patchwise and not return_support:
+        return decide_classes(probs, decision, out=out)
+    dev, lib = probs.device, _lib.load()
+    if out is None:
+        out = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    u16 = C.c_uint16 * K
+    q_own = torch.empty((h, w), dtype=torch.uint16, device=dev)
+    _lib.check(lib.dt_decide_candidates_u8(_p(probs), u16(*low.tolist()), _p(out), _p(q_own), K, h * w, _st()),
+               "dt_decide_candidates_u8")
+    labels, _ = label_patches(out, K, decision.connectivity)
+    filtered = bool(conf.any())
+    qmax = torch.zeros(h * w, dtype=torch.int32, device=dev)
+    qsum = torch.zeros(h * w, dtype=torch.int64, device=dev) if filtered else None
+    area = torch.zeros(h * w, dtype=torch.int32, device=dev) if filtered else None
+    _lib.check(lib.dt_patch_support(_p(labels), _p(q_own), h, w, _p(qmax), _p(qsum), _p(area), _st()), "dt_patch_support")
+    _lib.check(lib.dt_reject_patches_u8(_p(out), _p(labels), _p(qmax), _p(qsum), _p(area), u16(*high.tolist()),
+                                        u16(*conf.tolist()), K, h, w, _st()), "dt_reject_patches_u8")
+    return (out, labels, qmax, qsum, area) if return_support else out
+
+
 def conv2d_bn_bwd(src0, w_hwio, y, mean, invstd, act_scale=None, act_shift=None, act=None, join_into=None):
     """3x3 stride-1 conv (a data gradient) whose epilogue also produces the BatchNorm-backward partial sums of the
     layer with raw output `y` (same shape as the result).  Virtual activation: give act_scale/act_shift; block
@@ -1196,7 +1239,8 @@ def rasterize_polygons(edges: torch.Tensor, polys: torch.Tensor, shape, all_touc
 _LIB_CONSTANTS = {"PATCH_TILE": ("dt_patch_tile", 2), "OUTLINE_CHUNK": ("dt_outline_chunk", 1),
                   "CURVE_CHUNK": ("dt_curve_chunk", 1),
                   "OVERLAP_CHUNK": ("dt_overlap_chunk", 1), "PROXIMITY_SEGMENT": ("dt_proximity_segment", 1),
-                  "PROXIMITY_WINDOW": ("dt_proximity_window", 1), "ATTRIBUTE_SPAN": ("dt_attribute_span", 1)}
+                  "PROXIMITY_WINDOW": ("dt_proximity_window", 1), "ATTRIBUTE_SPAN": ("dt_attribute_span", 1),
+                  "SUPPORT_SPAN": ("dt_support_span", 1)}
 
 
 def _constant(name: str):

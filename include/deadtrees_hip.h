@@ -596,6 +596,31 @@ int dt_prob_histogram(const float* src, const int64_t* labels, const int64_t* lu
                       uint16_t* q_out, int B, int K, int H, int W, int is_logits, void* stream);
 int dt_decide_classes_u8(const float* probs, const uint16_t* thresholds, uint8_t* out_u8, int K, int64_t n, void* stream);
 
+/* Patch-wise decisions (hysteresis and a confidence filter; deadtrees_amd/loss/curves.py states the contract): candidates at
+ * the low thresholds L_c, their patches (dt_label_patches_u8), per patch the maximum, the sum and the count of the
+ * candidates' own q, and the rejection of every patch without a pixel at T_c or with sum < M_c * count.  Integers only.
+ * Sides <= 16384, h * w <= 2^31 - 2, 2 <= K <= 8; low / thresholds / min_confidence are HOST arrays uint16 [K] (entry 0 is not
+ * read; low and thresholds in 1..65535, min_confidence 0 for "no filter").  Grids follow the pixel count, uncapped.
+ *
+ * dt_decide_candidates_u8: dt_decide_classes_u8 at `low`, which also writes q_own uint16 [n]: the q of the class the pixel
+ *   took, 0 on class 0.  Every element of out_u8 and q_own is written.
+ * dt_patch_support: labels int32 [h][w] (a value outside 1 .. h * w is background) and q_own -> planes indexed by root
+ *   (label - 1), which the CALLER has zeroed: qmax int32 [h * w] (atomic max), qsum int64 [h * w] and area int32 [h * w]
+ *   (atomic adds).  qsum and area: both or neither (NULL: never touched).  A wave takes dt_support_span consecutive 64-pixel
+ *   chunks, reduces per run of equal labels, carries the open run in 64 bits, and a workgroup combines the runs its four
+ *   waves end with before it writes them.  The planes do not depend on the order of arrival.
+ * dt_reject_patches_u8: IN PLACE on classes uint8 [h][w]: a labelled pixel of class c becomes 0 unless
+ *   qmax[label - 1] >= thresholds[c] and, where min_confidence[c] > 0, qsum[label - 1] >= (int64) min_confidence[c] *
+ *   area[label - 1].  qsum / area NULL: min_confidence must be NULL or all zero.  Unlabelled pixels are not written. */
+int dt_support_span(int* chunks);
+int dt_decide_candidates_u8(const float* probs, const uint16_t* low, uint8_t* out_u8, uint16_t* q_own, int K, int64_t n,
+                            void* stream);
+int dt_patch_support(const int32_t* labels, const uint16_t* q_own, int h, int w, int32_t* qmax, int64_t* qsum, int32_t* area,
+                     void* stream);
+int dt_reject_patches_u8(uint8_t* classes, const int32_t* labels, const int32_t* qmax, const int64_t* qsum,
+                         const int32_t* area, const uint16_t* thresholds, const uint16_t* min_confidence, int K, int h, int w,
+                         void* stream);
+
 /* Training samples from an ortho raster (the array arithmetic of scripts/createdataset.py:53-194 and
  * scripts/computestats.py:111-161; deadtrees_amd/data/rasters.py states the contract in numpy).  rgbn_chw uint8 [4][h][w]
  * with 1 <= h, w <= S is the top-left corner of a zero [4][S][S] array; mask / lu uint8 [h][w] are padded the same way.
