@@ -194,6 +194,11 @@ SIGNATURES = {
     "dt_patch_support": (C.c_int, [c_f, c_f, C.c_int, C.c_int, c_f, c_f, c_f, c_f]),
     "dt_reject_patches_u8": (C.c_int, [c_f, c_f, c_f, c_f, c_f, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.c_int,
                                        C.c_int, C.c_int, c_f]),
+    "dt_object_planes": (C.c_int, [c_f, c_f, C.POINTER(C.c_uint16)] + [C.c_int] * 7 + [c_f] * 5),
+    "dt_object_vote": (C.c_int, [c_f, c_f, C.c_int, C.c_int, c_f, c_f]),
+    "dt_object_inter": (C.c_int, [c_f, c_f, c_f, C.c_int, C.c_int, c_f, c_f]),
+    "dt_object_targets": (C.c_int, [c_f] * 7 + [C.c_int] * 3 + [I64] * 3 + [c_f] * 3),
+    "dt_object_histogram": (C.c_int, [c_f] * 6 + [C.c_int] * 3 + [I64, c_f, c_f]),
     "dt_signed_distmap_workspace":(I64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "dt_signed_distmap": (C.c_int, [c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, c_f]),
     "dt_conv2d_bf16_stat_rows": (C.c_int, [_P]),

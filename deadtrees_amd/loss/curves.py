@@ -38,9 +38,9 @@ an integer, so device and host compare with ``array_equal``:
   and no ``M``, pixel by pixel: decided at ``T`` ⊆ result ⊆ decided at ``L``.  For K > 2 only the rule itself holds — a pixel
   that is class 1 at ``T`` can be a class-2 candidate at ``L`` (``q_2 >= L_2`` and ``q_2 > q_1``), as the curves above are
   one-vs-rest.  Relabelling the result with the same connectivity gives exactly the kept patches of ``cand``, with their
-  roots: a patch goes or stays whole, and two kept patches of one class never touch.  Out of scope: validation-side
-  curves over ``(L, T)`` pairs, object-level precision / recall sweeps, the ``against`` map, decisions stored in
-  checkpoints, temperature scaling.
+  roots: a patch goes or stays whole, and two kept patches of one class never touch.  Object-level precision / recall
+  sweeps over ``(T, M)`` at one ``L`` are ``loss/objects.py``.  Out of scope: sweeps over ``L`` inside one
+  pass, the ``against`` map, decisions stored in checkpoints, temperature scaling.
 
 Validation probabilities are single-tile softmaxes and raster probabilities are blended ones (``infer_tile`` with
 ``blend="average"``): a threshold transfers, but the exact closure is a statement about identical inputs.
@@ -427,12 +427,21 @@ def patch_support_host(probs, cand, labels):
                          f"{cand.dtype} {cand.shape} and {labels.dtype} {labels.shape}")
     if cand.size and int(cand.max()) >= probs.shape[0]:
         raise ValueError(f"patch_support_host: class value {int(cand.max())} out of range (K={probs.shape[0]})")
+    own = np.take_along_axis(probs.reshape(probs.shape[0], -1), cand.reshape(1, -1).astype(np.int64), 0)[0]
+    return patch_support_q_host(quantise(own), cand, labels)
+
+
+def patch_support_q_host(q_own, cand, labels):
+    """the integer core of ``patch_support_host``: ``q_own`` holds, per pixel, the ``q`` of the pixel's own class (any shape
+    with ``labels.size`` elements; read on labelled pixels only) -> ``(roots, cls, qmax, qsum, area)``"""
+    cand, labels = np.asarray(cand), np.asarray(labels)
+    q_own = np.asarray(q_own).reshape(-1)
     flat = labels.ravel()
     at = np.flatnonzero(flat)
     if at.size == 0:
         empty = np.zeros(0, np.int64)
         return empty, np.zeros(0, np.uint8), empty.copy(), empty.copy(), empty.copy()
-    q = quantise(np.take_along_axis(probs.reshape(probs.shape[0], -1), cand.reshape(1, -1).astype(np.int64), 0)[0][at])
+    q = q_own[at]
     order = np.argsort(flat[at], kind="stable")
     sorted_labels = flat[at][order]
     starts = np.flatnonzero(np.concatenate([[True], sorted_labels[1:] != sorted_labels[:-1]]))

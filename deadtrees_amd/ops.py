@@ -7,6 +7,7 @@ and raises RuntimeError when the library reports an error.  Used by the engine-i
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -663,6 +664,82 @@ def decide_patchwise(probs, decision, out=None, return_support: bool = False):
     _lib.check(lib.dt_reject_patches_u8(_p(out), _p(labels), _p(qmax), _p(qsum), _p(area), u16(*high.tolist()),
                                         u16(*conf.tolist()), K, h, w, _st()), "dt_reject_patches_u8")
     return (out, labels, qmax, qsum, area) if return_support else out
+
+
+def object_plane_shape(B: int, H: int, W: int):
+    """``(cols, ph, pw)``: the batch plane of ``object_histogram`` — ``ceil(sqrt(B))`` cells of ``(H + 1) x (W + 1)`` per row,
+    the width rounded up to 4 pixels where that still fits a side of 16384 (packed stores).  Not part of the contract"""
+    cols = math.isqrt(B - 1) + 1 if B > 1 else 1
+    ph, pw = -(-B // cols) * (H + 1), cols * (W + 1)
+    return cols, ph, (pw + 3) // 4 * 4 if (pw + 3) // 4 * 4 <= 16384 else pw
+
+
+def object_histogram(q, target, sweep, hist=None, targets=None, err=None, _timed=None):
+    """the crown-level histogram of ``loss/objects.py`` on the device: ``q`` contiguous uint16 [B,K,H,W] (what
+    ``prob_histogram(..., want_q=True)`` returns), ``target`` int64 [B,H,W], ``sweep`` an ``ObjectSweep`` for K classes.
+    ``hist`` int64 [K,2,256,256] and ``targets`` int64 [K] are added to (+=; allocated zeroed when None), ``err`` int32 [1]
+    likewise (a target label outside [0, K)).  -> ``(hist, targets, err)``.  Launches only — no host synchronisation, no
+    scalar read back, no sort: the images are laid out in one plane with background gutters (``dt_object_planes``),
+    ``label_patches`` twice, ``patch_areas`` on the target, ``dt_patch_support`` on the candidates, then ``dt_object_vote``,
+    ``dt_object_inter``, ``dt_object_targets`` and ``dt_object_histogram``.  Workspace: 45 bytes per plane pixel.  A plane
+    beyond the labeller's limits (sides <= 16384, at most 2^31 - 2 pixels) is a ``RuntimeError`` before any launch.
+    ``_timed(name, fn)``, for ``scripts/bench_objects.py`` alone, is called in place of every step and must return ``fn()``."""
+    from .loss.objects import ObjectSweep
+    _gpu(q, target, hist, targets, err)
+    if not isinstance(sweep, ObjectSweep):
+        raise ValueError(f"object_histogram: sweep must be an ObjectSweep, got {sweep!r}")
+    if q.dtype != torch.uint16 or q.dim() != 4 or q.numel() == 0 or not q.is_contiguous():
+        raise RuntimeError(f"object_histogram: q must be non-empty contiguous uint16 [B,K,H,W], got {q.dtype} {tuple(q.shape)}")
+    B, K, H, W = q.shape
+    dev = q.device
+    if target.dtype != torch.int64 or tuple(target.shape) != (B, H, W) or target.device != dev or not target.is_contiguous():
+        raise RuntimeError(f"object_histogram: target must be contiguous int64 {(B, H, W)} on {dev}, got {target.dtype} "
+                           f"{tuple(target.shape)}")
+    if not 2 <= K <= 8:
+        raise RuntimeError(f"object_histogram: K={K} unsupported (2..8)")
+    low = sweep.low_u16(K)
+    cols, ph, pw = object_plane_shape(B, H, W)
+    if max(ph, pw) > 16384 or ph * pw > 2 ** 31 - 2:
+        raise RuntimeError(f"object_histogram: {B} images of {H}x{W} need a plane of {ph}x{pw}: sides must be <= 16384 and "
+                           "h * w <= 2^31 - 2")
+    if hist is None:
+        hist = torch.zeros((K, 2, 256, 256), dtype=torch.int64, device=dev)
+    elif hist.dtype != torch.int64 or tuple(hist.shape) != (K, 2, 256, 256) or hist.device != dev or not hist.is_contiguous():
+        raise RuntimeError(f"object_histogram: hist must be contiguous int64 [{K},2,256,256] on {dev}")
+    if targets is None:
+        targets = torch.zeros(K, dtype=torch.int64, device=dev)
+    elif targets.dtype != torch.int64 or tuple(targets.shape) != (K,) or targets.device != dev or not targets.is_contiguous():
+        raise RuntimeError(f"object_histogram: targets must be contiguous int64 [{K}] on {dev}")
+    err = _err_flag("object_histogram", err, dev)
+    lib, n = _lib.load(), ph * pw
+    step = _timed if _timed is not None else (lambda name, fn: fn())
+    cand = torch.empty((ph, pw), dtype=torch.uint8, device=dev)
+    tcls = torch.empty((ph, pw), dtype=torch.uint8, device=dev)
+    q_own = torch.empty((ph, pw), dtype=torch.uint16, device=dev)
+    step("planes", lambda: _lib.check(lib.dt_object_planes(_p(q), _p(target), (C.c_uint16 * K)(*low.tolist()), B, K, H, W, cols,
+                                                            ph, pw, _p(cand), _p(q_own), _p(tcls), _p(err), _st()),
+                                      "dt_object_planes"))
+    labels_p = step("label_pred", lambda: label_patches(cand, K, sweep.connectivity, err=err)[0])
+    labels_t = step("label_target", lambda: label_patches(tcls, K, sweep.connectivity, err=err)[0])
+    area_t = step("areas_target", lambda: patch_areas(labels_t))
+    # one zeroed workspace, carved by element size: vote and qsum int64, inter, qmax and area int32, matched uint8
+    ws = step("zero", lambda: torch.zeros(29 * n + 8, dtype=torch.uint8, device=dev))
+    wide, mid = ws[:16 * n].view(torch.int64), ws[16 * n:28 * n].view(torch.int32)
+    vote, qsum = wide[:n], wide[n:]
+    inter, qmax, area = mid[:n], mid[n:2 * n], mid[2 * n:]
+    matched = ws[28 * n:29 * n]
+    step("support", lambda: _lib.check(lib.dt_patch_support(_p(labels_p), _p(q_own), ph, pw, _p(qmax), _p(qsum), _p(area), _st()),
+                                       "dt_patch_support"))
+    step("vote", lambda: _lib.check(lib.dt_object_vote(_p(labels_t), _p(labels_p), ph, pw, _p(vote), _st()), "dt_object_vote"))
+    step("inter", lambda: _lib.check(lib.dt_object_inter(_p(labels_t), _p(labels_p), _p(vote), ph, pw, _p(inter), _st()),
+                                     "dt_object_inter"))
+    step("targets", lambda: _lib.check(lib.dt_object_targets(_p(labels_t), _p(tcls), _p(cand), _p(vote), _p(inter), _p(area_t),
+                                                             _p(area), K, ph, pw, sweep.min_pixels, sweep.iou_p, sweep.iou_q,
+                                                             _p(targets), _p(matched), _st()), "dt_object_targets"))
+    step("histogram", lambda: _lib.check(lib.dt_object_histogram(_p(labels_p), _p(cand), _p(qmax), _p(qsum), _p(area),
+                                                                 _p(matched), K, ph, pw, sweep.min_pixels, _p(hist), _st()),
+                                         "dt_object_histogram"))
+    return hist, targets, err
 
 
 def conv2d_bn_bwd(src0, w_hwio, y, mean, invstd, act_scale=None, act_shift=None, act=None, join_into=None):

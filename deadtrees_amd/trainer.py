@@ -22,7 +22,7 @@ import torch
 from .data.distmap import distmaps_on_device
 from .loss.seg_loss import PART_KEYS, loss_algebra, loss_backward, loss_forward
 from .network.unet import UNetHIP
-from .ops import FlatAdam, WeightAverager, confusion_matrix, eval_accumulate, prob_histogram
+from .ops import FlatAdam, WeightAverager, confusion_matrix, eval_accumulate, object_histogram, prob_histogram
 from .utils.graph_replay import GraphReplay, ReplayCache
 
 
@@ -89,6 +89,7 @@ class HipTrainer:
         self._recal_replays = ReplayCache(keep_all=False)
         self._val_replays = ReplayCache(keep_all=True)      # one captured graph per key (shapes, precision, loss set)
         self._val_state = None           # device accumulators of a validation epoch (the captured graphs write them)
+        self._obj_state = None           # those of validate(objects=...): allocated on first use, untouched without it
 
     @torch.no_grad()
     def broadcast_parameters(self, src: int = 0):
@@ -149,12 +150,24 @@ class HipTrainer:
             self._val_replays.clear()
         return st
 
-    def _val_batch(self, img, mask, lu, distmap, alpha, curves=False):
+    def _obj_buffers(self):
+        """the accumulators of ``validate(objects=...)`` (``loss/objects.py``): "hist" int64 [K,2,256,256] and "targets"
+        int64 [K].  Kept apart from ``_val_buffers``: an epoch without ``objects`` neither allocates nor zeroes them."""
+        dev, K = self.model.flat_params.device, self.model.spec.classes
+        st = self._obj_state
+        if st is None or st["hist"].device != dev:
+            st = self._obj_state = {"hist": torch.zeros((K, 2, 256, 256), dtype=torch.int64, device=dev),
+                                    "targets": torch.zeros(K, dtype=torch.int64, device=dev)}
+        return st
+
+    def _val_batch(self, img, mask, lu, distmap, alpha, curves=False, objects=None):
         """one validation batch, launches only: eval-mode forward up to the decoder output, the fused evaluation head
         (losses with GWDICE: logits, ``loss_forward`` and ``confusion_matrix``, the unfused chain), the scalar algebra
         and the weighted accumulation into the epoch buffers.  Reads no module mode and writes no model state.
         ``curves``: the unfused chain as well, plus ONE ``prob_histogram`` of the logits into the epoch's histogram — the
-        fused ``dt_head_eval`` never materialises the logits, so it has nothing a histogram could read."""
+        fused ``dt_head_eval`` never materialises the logits, so it has nothing a histogram could read.  ``objects`` (an
+        ``ObjectSweep``): the unfused chain too; ``q`` is ``prob_histogram``'s own (into the epoch's histogram with ``curves``,
+        into a throw-away one without), and ``object_histogram`` adds the batch's crowns to the object buffers."""
         m, eng, st = self.model, self.model.engine, self._val_buffers()
         params = m.flat_params.detach()
         B, K = img.shape[0], m.spec.classes
@@ -164,7 +177,7 @@ class HipTrainer:
         if boundary and distmap is None:
             distmap = distmaps_on_device(mask, K)
         dist = distmap if boundary else None
-        if "GWDICE" in self.losses or curves:
+        if "GWDICE" in self.losses or curves or objects is not None:
             if m.precision == "bf16":
                 logits, am = eng.forward_bf16_eval(x, params, m.bn_state, want_argmax="uint8")
             else:
@@ -172,7 +185,14 @@ class HipTrainer:
             parts, err, _ = loss_forward(logits, mask, dist, {"losses": self.losses, "alpha": alpha})
             _, err_cm = confusion_matrix(am, mask, lu, K=K, counts=st["counts"])
             torch.maximum(st["err"], torch.maximum(err, err_cm), out=st["err"])
-            if curves:
+            if objects is not None:
+                ost = self._obj_buffers()
+                if curves:
+                    _, _, q = prob_histogram(logits, mask, lu, hist=st["hist"], err=st["err"], logits=True, want_q=True)
+                else:
+                    _, _, q = prob_histogram(logits, mask, None, err=st["err"], logits=True, want_q=True)
+                object_histogram(q, mask.contiguous(), objects, hist=ost["hist"], targets=ost["targets"], err=st["err"])
+            elif curves:
                 prob_histogram(logits, mask, lu, hist=st["hist"], err=st["err"], logits=True)
         else:
             head = eng.forward_bf16_eval_head if m.precision == "bf16" else eng.forward_eval_head
@@ -180,7 +200,7 @@ class HipTrainer:
             parts = loss_algebra(acc, self.losses, B, K, H, W, dist is not None, alpha)[0]
         eval_accumulate(parts, float(B), st["epoch"])
 
-    def _val_graph_batch(self, img, mask, lu, distmap, alpha, curves=False):
+    def _val_graph_batch(self, img, mask, lu, distmap, alpha, curves=False, objects=None):
         """``_val_batch`` through ``GraphReplay``: a captured graph per key, after two eager batches of that key (a
         validation set whose last batch is smaller keeps one graph per batch size).  alpha is baked into the captured
         blend: it belongs to the key where it is read (BOUNDARY-RAMPED)"""
@@ -190,11 +210,15 @@ class HipTrainer:
                self.model.precision, self.losses, float(alpha) if "BOUNDARY-RAMPED" in self.losses else None) + \
             ((True,) if curves else ())
         self._val_buffers()              # (a moved model drops the graphs)
+        if objects is not None:          # the sweep is baked into the captured launches: it belongs to the key
+            key += (("objects",) + objects._key(),)
+            self._obj_buffers()
         self._val_replays.get(key, lambda: GraphReplay(
-            self.model.engine, lambda *batch: self._val_batch(*batch, alpha, curves), warmup=2))(img, mask, lu, distmap)
+            self.model.engine, lambda *batch: self._val_batch(*batch, alpha, curves, objects), warmup=2))(img, mask, lu, distmap)
 
     @torch.no_grad()
-    def validate(self, loader, to_device=None, stage: str = "val", alpha: float = 1.0, curves: bool = False) -> dict:
+    def validate(self, loader, to_device=None, stage: str = "val", alpha: float = 1.0, curves: bool = False,
+                 objects=None) -> dict:
         """One validation epoch: eval-mode BatchNorm in this trainer's precision; per batch the loss terms of
         ``self.losses`` and both F-scores as ``SemSegment.validation_step`` logs them, the confusion counts over all pixels
         and over ``lu == 1``.  Batches are ``(img, mask[, distmap[, lu[, stats]]])`` tuples or the datamodule's dicts;
@@ -219,15 +243,29 @@ class HipTrainer:
         ``confusion_matrix`` -> one ``prob_histogram`` of the logits): the fused ``dt_head_eval`` path is not used with
         curves because it never materialises the logits.  The counts are exact; the real-valued metrics are those of
         ``curves=False`` to fp32 summation order.  The histogram travels in the epoch's one transfer (and all-reduce) as
-        fp64, exact below 2^53 like the confusion counts.  With ``curves=False`` not one launch differs from before."""
+        fp64, exact below 2^53 like the confusion counts.  With ``curves=False`` not one launch differs from before.
+
+        ``objects`` (an ``ObjectSweep``, ``loss/objects.py``) also collects the crown-level histogram of the hysteresis
+        patches at the sweep's low thresholds against the target's crowns and returns it under "objects" as an
+        ``ObjectCurves``: crown-level precision / recall / F1 for every ``(T, M)`` of a ``Decision`` at once, and
+        ``best_decision()``.  Every batch takes the unfused chain as with ``curves``, then ``ops.object_histogram`` on
+        ``prob_histogram``'s ``q``; with graph=True the batch is captured like every other one (the sweep is part of the
+        key).  The counts travel in the same transfer and all-reduce.  Without ``objects`` not one launch, key or returned
+        entry differs."""
         from .network.segmodel import create_combined_batch
         if not isinstance(curves, (bool,)):
             raise ValueError(f"validate: curves must be True or False, got {curves!r}")
         m = self.model
         K = m.spec.classes
+        if objects is not None:
+            from .loss.objects import check_sweep
+            objects = check_sweep(objects, K, "validate")
         st = self._val_buffers()
         for t in st.values():
             t.zero_()
+        if objects is not None:
+            for t in self._obj_buffers().values():
+                t.zero_()
         run = self._val_graph_batch if self.use_graph else self._val_batch
         batches = 0
         for batch in loader:
@@ -246,7 +284,10 @@ class HipTrainer:
                 mask = mask.long()
             if lu is not None and lu.dtype != torch.int64:
                 lu = lu.long()
-            run(img, mask, lu, distmap, alpha, curves) if curves else run(img, mask, lu, distmap, alpha)
+            if objects is not None:
+                run(img, mask, lu, distmap, alpha, curves, objects)
+            else:
+                run(img, mask, lu, distmap, alpha, curves) if curves else run(img, mask, lu, distmap, alpha)
             batches += 1
         if batches == 0:
             raise ValueError("validate: no batches")
@@ -254,6 +295,8 @@ class HipTrainer:
         parts = [st["epoch"], st["counts"].reshape(-1).double()]
         if curves:
             parts.append(st["hist"].reshape(-1).double())
+        if objects is not None:
+            parts += [self._obj_state["hist"].reshape(-1).double(), self._obj_state["targets"].double()]
         buf = torch.cat(parts + [st["err"].double()])
         if self.reducer and self.world > 1:
             self.reducer.dist.all_reduce(buf, op=self.reducer.dist.ReduceOp.SUM, group=self.reducer.group)
@@ -265,8 +308,14 @@ class HipTrainer:
             from .loss.curves import ProbabilityCurves
             names = getattr(m, "classes", None)
             names = list(names) if isinstance(names, (list, tuple)) and len(names) == K else None
-            hist = host[9 + 2 * K * K:-1].reshape(2, K, 2, 256).to(torch.int64).numpy()
+            hist = host[9 + 2 * K * K:9 + 2 * K * K + 2 * K * 2 * 256].reshape(2, K, 2, 256).to(torch.int64).numpy()
             out["curves"] = ProbabilityCurves(hist, names)
+        if objects is not None:
+            from .loss.objects import ObjectCurves
+            names = getattr(m, "classes", None)
+            names = list(names) if isinstance(names, (list, tuple)) and len(names) == K else None
+            tail = host[-1 - K - K * 2 * 256 * 256:-1].to(torch.int64).numpy()
+            out["objects"] = ObjectCurves(tail[:-K].reshape(K, 2, 256, 256), tail[-K:], objects, names)
         return out
 
     def step(self, img: torch.Tensor, mask: torch.Tensor, distmap: Optional[torch.Tensor] = None,
@@ -511,21 +560,22 @@ class EarlyStoppingConfig:
     min_delta: float = 0.0
 
 
-def _check_monitor(what: str, monitor, mode, losses, stage: str = "val"):
+def _check_monitor(what: str, monitor, mode, losses, stage: str = "val", extra: Sequence[str] = ()):
     if mode not in ("min", "max"):
         raise ValueError(f"{what}: mode {mode!r}: use 'min' or 'max'")
-    keys = [k for k in validation_keys(losses, stage) if not k.endswith(("/batches", "/samples"))]
+    keys = [k for k in validation_keys(losses, stage) if not k.endswith(("/batches", "/samples"))] + list(extra)
     if monitor not in keys:
         raise ValueError(f"{what}: monitor {monitor!r} is not a validation metric of losses {tuple(losses)}: {keys}")
 
 
-def resolve_checkpoint(cfg, losses: Sequence[str]) -> Optional[CheckpointConfig]:
-    """``fit``'s checkpoint argument -> a checked CheckpointConfig (None stays None)"""
+def resolve_checkpoint(cfg, losses: Sequence[str], extra: Sequence[str] = ()) -> Optional[CheckpointConfig]:
+    """``fit``'s checkpoint argument -> a checked CheckpointConfig (None stays None); ``extra``: further scalars the monitor may
+    name (the crown-level ones of ``fit(objects=...)``)"""
     if cfg is None:
         return None
     if not isinstance(cfg, CheckpointConfig):
         raise ValueError(f"fit(checkpoint=...): None or a CheckpointConfig, not {type(cfg).__name__}")
-    _check_monitor("checkpoint", cfg.monitor, cfg.mode, losses)
+    _check_monitor("checkpoint", cfg.monitor, cfg.mode, losses, extra=extra)
     if isinstance(cfg.save_top_k, bool) or int(cfg.save_top_k) != cfg.save_top_k or cfg.save_top_k < 0:
         raise ValueError(f"save_top_k {cfg.save_top_k!r}: an integer >= 0")
     if not cfg.dirpath:
@@ -539,13 +589,14 @@ def resolve_checkpoint(cfg, losses: Sequence[str]) -> Optional[CheckpointConfig]
     return CheckpointConfig(str(cfg.dirpath), cfg.monitor, cfg.mode, int(cfg.save_top_k), bool(cfg.save_last), cfg.filename)
 
 
-def resolve_early_stopping(cfg, losses: Sequence[str]) -> Optional[EarlyStoppingConfig]:
-    """``fit``'s early_stopping argument -> a checked EarlyStoppingConfig (None stays None)"""
+def resolve_early_stopping(cfg, losses: Sequence[str], extra: Sequence[str] = ()) -> Optional[EarlyStoppingConfig]:
+    """``fit``'s early_stopping argument -> a checked EarlyStoppingConfig (None stays None); ``extra`` as in
+    ``resolve_checkpoint``"""
     if cfg is None:
         return None
     if not isinstance(cfg, EarlyStoppingConfig):
         raise ValueError(f"fit(early_stopping=...): None or an EarlyStoppingConfig, not {type(cfg).__name__}")
-    _check_monitor("early_stopping", cfg.monitor, cfg.mode, losses)
+    _check_monitor("early_stopping", cfg.monitor, cfg.mode, losses, extra=extra)
     if isinstance(cfg.patience, bool) or int(cfg.patience) != cfg.patience or cfg.patience < 0:
         raise ValueError(f"patience {cfg.patience!r}: an integer >= 0")
     if not float(cfg.min_delta) >= 0.0:
@@ -659,7 +710,7 @@ def checkpoint_writer(trainer: "HipTrainer", pl_module=None, training_conf: Opti
 
 def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: int = 10, to_device=None,
         on_epoch_end=None, callbacks=None, pl_module=None, swa=None, val_loader=None, check_val_every_n_epoch: int = 1,
-        checkpoint=None, early_stopping=None, curves: bool = False):
+        checkpoint=None, early_stopping=None, curves: bool = False, objects=None):
     """Minimal stand-in for ``Trainer.fit`` on the hot path (reference deadtrees/train.py:113): per-batch
     ``HipTrainer.step`` and the per-epoch ``CosineAnnealingLR(T_max)`` of segmodel.py:426-428.
 
@@ -679,6 +730,11 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
     curves=True: ``validate(..., curves=True)``; the ``ProbabilityCurves`` object stays out of the history (as the ``cm_*``
     matrices do) and its scalars go in, for every class c >= 1: "val/ap_<c>", "val/roc_auc_<c>", "val/best_f1_<c>" and
     "val/best_threshold_<c>" (the float T / 65535).  Monitors stay restricted to ``validation_keys``.
+    objects: an ``ObjectSweep`` (``loss/objects.py``) — ``validate(..., objects=...)``; the ``ObjectCurves`` object stays out of
+    the history and its ``summary("val")`` scalars go in ("val/crown_ap_<c>", "val/crown_best_f1_<c>",
+    "val/crown_best_threshold_<c>", "val/crown_best_min_confidence_<c>", "val/crown_targets_<c>").  With ``objects``, and
+    only then, a monitor may also name "val/crown_best_f1_<c>" or "val/crown_ap_<c>": the best checkpoint by crown score
+    (``nan``, a class without target crowns, is "not finite": ``ModelSelection``'s rule).
 
     swa: None | True | SWAConfig — the loop of torch's SWA documentation on a ``HipTrainer(average="swa")``: epochs before
     ``swa_start`` keep the cosine schedule (or whatever a callback put in its place); from ``swa_start`` the rate follows
@@ -690,9 +746,15 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
     swa = resolve_swa(swa, epochs, base_lr)
     if swa is not None and (getattr(trainer, "averager", None) is None or trainer.averager.mode != "swa"):
         raise ValueError("fit(swa=...) needs HipTrainer(average='swa')")
+    if objects is not None:
+        from .loss.objects import check_sweep, crown_monitors
+        objects = check_sweep(objects, trainer.model.spec.classes, "fit(objects=...)")
+        if val_loader is None:
+            raise ValueError("fit(objects=...) collects its histogram during validation: give val_loader")
     if checkpoint is not None or early_stopping is not None:      # (a plain loop asks nothing new of `trainer`)
-        checkpoint = resolve_checkpoint(checkpoint, trainer.losses)
-        early_stopping = resolve_early_stopping(early_stopping, trainer.losses)
+        crown = {} if objects is None else {"extra": crown_monitors(trainer.model.spec.classes)}
+        checkpoint = resolve_checkpoint(checkpoint, trainer.losses, **crown)
+        early_stopping = resolve_early_stopping(early_stopping, trainer.losses, **crown)
     if not isinstance(curves, bool):
         raise ValueError(f"fit(curves=...): True or False, not {curves!r}")
     if curves and val_loader is None:
@@ -742,11 +804,17 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
             history[-1]["swa/n_averaged"] = trainer.averager.n_averaged
         stop = False
         if val_loader is not None and (epoch + 1) % check_val_every_n_epoch == 0:
-            val = (trainer.validate(val_loader, to_device=to_device, alpha=alpha, curves=True) if curves
-                   else trainer.validate(val_loader, to_device=to_device, alpha=alpha))
-            history[-1].update({k: v for k, v in val.items() if not k.startswith("cm_") and k != "curves"})
+            asked = dict(curves=True) if curves else {}
+            if objects is not None:
+                asked["objects"] = objects
+            val = trainer.validate(val_loader, to_device=to_device, alpha=alpha, **asked)
+            history[-1].update({k: v for k, v in val.items() if not k.startswith("cm_") and k not in ("curves", "objects")})
             if curves:
                 history[-1].update(val["curves"].summary("val"))
+            if objects is not None:
+                crowns = val["objects"].summary("val")
+                history[-1].update(crowns)
+                val = {**val, **crowns}                          # what a crown-level monitor reads
             if select is not None:
                 stop = select.update(epoch, val)
         if on_epoch_end:

@@ -621,6 +621,39 @@ int dt_reject_patches_u8(uint8_t* classes, const int32_t* labels, const int32_t*
                          const int32_t* area, const uint16_t* thresholds, const uint16_t* min_confidence, int K, int h, int w,
                          void* stream);
 
+/* Crown-level validation curves (deadtrees_amd/loss/objects.py states the contract): the candidates of a batch at the low
+ * thresholds matched, patch by patch, to the target's crowns above an IoU of iou_p / iou_q >= 1/2, and one histogram entry per
+ * predicted patch.  Integers only, no synchronisation, no sort; every grid follows the pixel count, uncapped.  The B images
+ * lie in ONE plane uint8 / uint16 / int32 [ph][pw] of (H + 1) x (W + 1) cells, `cols` per row, image b in cell (b / cols,
+ * b % cols): ph = ceil(B / cols) * (H + 1), pw >= cols * (W + 1), sides <= 16384, ph * pw <= 2^31 - 2.  Everything outside the
+ * images is class 0, so dt_label_patches_u8, dt_patch_areas and dt_patch_support run on the plane as on one raster.
+ *
+ * dt_object_planes: q uint16 [B][K][H][W] (dt_prob_histogram's q_out), target int64 [B][H][W], low a HOST array uint16 [K]
+ *   (entry 0 is not read, the others in 1..65535), any alignment.  Every element of cand, q_own and tcls is written: cand the
+ *   class c >= 1 with the largest q_c among those with q_c >= low[c] (ties -> the smallest c; 0 without one), q_own that q
+ *   (0 on class 0), tcls the target's class.  A label outside [0, K) sets err_flag[0] = 1 and is class 0.
+ * dt_object_vote: labels_t / labels_p int32 [h][w] (a value outside 1 .. h * w is background), vote int64 [h * w] ZEROED BY
+ *   THE CALLER: at a target root, (candidate << 32) | count of a majority summary of labels_p (0 included) over the target
+ *   patch's pixels.  The candidate is the strict majority where there is one, whatever the order of arrival.
+ * dt_object_inter: inter int32 [h * w], zeroed by the caller: at a target root += the pixels of the patch whose labels_p
+ *   value is the candidate of vote.
+ * dt_object_targets: targets int64 [K] += the target patches per class; matched uint8 [h * w], zeroed by the caller:
+ *   matched[b] = 1 where the candidate b of a target patch a has a's class, area_p[b] >= min_pixels and
+ *   inter * iou_q > iou_p * (area_t[a] + area_p[b] - inter) (64-bit).  1 <= iou_q <= 10^6, iou_q <= 2 iou_p < 2 iou_q.
+ * dt_object_histogram: hist int64 [K][2][256][256] += 1 at [cand][matched][qmax >> 8][(qsum / area) >> 8] for every root of
+ *   labels_p with area >= min_pixels (qmax, qsum, area: the planes of dt_patch_support). */
+int dt_object_planes(const uint16_t* q, const int64_t* target, const uint16_t* low, int B, int K, int H, int W, int cols,
+                     int ph, int pw, uint8_t* cand, uint16_t* q_own, uint8_t* tcls, int32_t* err_flag, void* stream);
+int dt_object_vote(const int32_t* labels_t, const int32_t* labels_p, int h, int w, int64_t* vote, void* stream);
+int dt_object_inter(const int32_t* labels_t, const int32_t* labels_p, const int64_t* vote, int h, int w, int32_t* inter,
+                    void* stream);
+int dt_object_targets(const int32_t* labels_t, const uint8_t* tcls, const uint8_t* cand, const int64_t* vote,
+                      const int32_t* inter, const int32_t* area_t, const int32_t* area_p, int K, int h, int w,
+                      int64_t min_pixels, int64_t iou_p, int64_t iou_q, int64_t* targets, uint8_t* matched, void* stream);
+int dt_object_histogram(const int32_t* labels_p, const uint8_t* cand, const int32_t* qmax, const int64_t* qsum,
+                        const int32_t* area, const uint8_t* matched, int K, int h, int w, int64_t min_pixels, int64_t* hist,
+                        void* stream);
+
 /* Training samples from an ortho raster (the array arithmetic of scripts/createdataset.py:53-194 and
  * scripts/computestats.py:111-161; deadtrees_amd/data/rasters.py states the contract in numpy).  rgbn_chw uint8 [4][h][w]
  * with 1 <= h, w <= S is the top-left corner of a zero [4][S][S] array; mask / lu uint8 [h][w] are padded the same way.
