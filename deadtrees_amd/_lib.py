@@ -186,6 +186,12 @@ SIGNATURES = {
     "dt_attribute_span": (C.c_int, [C.POINTER(C.c_int)]),
     "dt_patch_attributes_u8": (C.c_int, [c_f, c_f, C.c_int, C.c_int, C.c_int, c_f, C.c_int, c_f, c_f, C.c_int,
                                          C.POINTER(C.c_int), C.c_int, c_f, c_f, c_f]),
+    "dt_crown_segment": (C.c_int, [C.POINTER(C.c_int)]),
+    "dt_patch_depth2_u8": (C.c_int, [c_f] + [C.c_int] * 5 + [c_f] * 6),
+    "dt_crown_grow": (C.c_int, [c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, c_f, c_f]),
+    "dt_crown_remainder": (C.c_int, [c_f, c_f, C.c_int, C.c_int, C.c_int, c_f, c_f, c_f]),
+    "dt_crown_merge": (C.c_int, [c_f, c_f, c_f, C.c_int, C.c_int, c_f, c_f, c_f]),
+    "dt_crown_relabel": (C.c_int, [c_f, c_f, c_f, C.c_int, C.c_int, c_f, c_f, c_f]),
     "dt_curve_chunk": (C.c_int, [C.POINTER(C.c_int)]),
     "dt_prob_histogram": (C.c_int, [c_f, c_f, c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f]),
     "dt_decide_classes_u8": (C.c_int, [c_f, C.POINTER(C.c_uint16), c_f, C.c_int, I64, c_f]),

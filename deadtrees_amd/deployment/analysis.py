@@ -11,6 +11,7 @@ import numpy as np
 
 from ..data.polygons import PolygonSet, rasterize
 from .attributes import AttributeConfig, attributes_of, check_attributes, check_raster
+from .crowns import CrownConfig, CrownSplit, check_crowns
 from .patches import PatchConfig, check_patches, labelled_patches_host
 from .proximity import ProximityConfig, check_proximity, distances_of, gaps_of
 from .stats import MAX_ZONES, RasterStats, zonal_counts_host
@@ -82,7 +83,9 @@ class MapAnalysis:
     ``against_patches``: the map the result is compared with, and its ``PatchConfig``; ``n_zones``: the caller's figure;
     ``distances`` / ``gaps``: the ``ProximityConfig`` of the distances to the patches of ``against`` / to the map's own other
     patches, or None; ``attributes``: the ``AttributeConfig`` of the patches' band statistics and confidence, or None — after
-    ``bind`` with the index pairs of that raster written out.
+    ``bind`` with the index pairs of that raster written out; ``crowns`` / ``against_crowns``: the ``CrownConfig`` under which
+    the patches of the map / of ``against`` are split into crowns behind the sieve (``deployment/crowns.py``), or None — with
+    one, everything that follows the label plane is crown-level.
     ``rules`` checks what depends on no raster, ``bind`` the maps of one raster, ``of`` both; ``stats=False`` gives None"""
     K: Optional[int]
     zones: object = None
@@ -95,20 +98,24 @@ class MapAnalysis:
     distances: Optional[ProximityConfig] = None
     gaps: Optional[ProximityConfig] = None
     attributes: Optional[AttributeConfig] = None
+    crowns: Optional[CrownConfig] = None
+    against_crowns: Optional[CrownConfig] = None
 
     @classmethod
     def rules(cls, who: str, K, stats: bool = True, zones=None, n_zones=None, patches=None, outlines=None, against=None,
-              against_patches=None, distances=None, gaps=None, attributes=None, no_probs: Optional[str] = None
-              ) -> Optional["MapAnalysis"]:
+              against_patches=None, distances=None, gaps=None, attributes=None, no_probs: Optional[str] = None,
+              crowns=None, against_crowns=None) -> Optional["MapAnalysis"]:
         """the options as ``infer_tile`` receives them -> a request without maps yet, or None without ``stats``; ``zones`` and
         ``against`` only say whether there are any (``infer_rasters`` passes its mappings).  ``ValueError``: an option without
         ``stats``, outlines, ``against``, ``gaps`` or ``attributes`` without patches, ``against_patches`` or ``distances`` without
         ``against``, a value of a wrong type, ``attributes`` with confidence in a call without probabilities (``no_probs``: what
-        the caller's path would need to have some; None: it has)"""
+        the caller's path would need to have some; None: it has), ``crowns`` without patches, ``against_crowns`` without
+        ``against``"""
         config = check_patches(patches)
         try:
             distances, gaps = check_proximity(distances, "distances"), check_proximity(gaps, "gaps")
             attributes = check_attributes(attributes)
+            crowns, against_crowns = check_crowns(crowns), check_crowns(against_crowns, "against_crowns")
         except ValueError as e:
             raise ValueError(f"{who}: {e}") from None
         if outlines is not None and not isinstance(outlines, bool):
@@ -126,7 +133,13 @@ class MapAnalysis:
                 raise ValueError(f"{who}: distances / gaps need stats=True")
             if attributes is not None:
                 raise ValueError(f"{who}: attributes need stats=True")
+            if crowns is not None or against_crowns is not None:
+                raise ValueError(f"{who}: crowns / against_crowns need stats=True")
             return None
+        if crowns is not None and config is None:
+            raise ValueError(f"{who}: crowns need patches (the crowns are cut from the PatchTable's patches)")
+        if against_crowns is not None and (config is None or against is None):
+            raise ValueError(f"{who}: against_crowns needs patches and against (the crowns are cut from that map's patches)")
         if gaps is not None and config is None:
             raise ValueError(f"{who}: gaps need patches (the gaps are those of the PatchTable's patches)")
         if attributes is not None and config is None:
@@ -145,7 +158,7 @@ class MapAnalysis:
         elif not isinstance(against_patches, PatchConfig):
             raise ValueError(f"{who}: against_patches must be a PatchConfig or None, got {against_patches!r}")
         return cls(K=K, patches=config, outlines=bool(outlines), against_patches=against_patches, n_zones=n_zones,
-                   distances=distances, gaps=gaps, attributes=attributes)
+                   distances=distances, gaps=gaps, attributes=attributes, crowns=crowns, against_crowns=against_crowns)
 
     def bind(self, who: str, shape, zones=None, against=None, raster=None) -> "MapAnalysis":
         """the request of one raster of ``shape`` (h, w) and its maps, of the kinds ``rules`` was told of.  ``ValueError``: a map
@@ -166,6 +179,7 @@ class MapAnalysis:
                 raise ValueError(f"{who}: {e}") from None
         return replace(self, K=int(self.K), zones=zones, Z=Z, against=against, attributes=attributes,
                        against_patches=None if against is None else self.against_patches,
+                       against_crowns=None if against is None else self.against_crowns,
                        distances=None if against is None else self.distances)
 
     @classmethod
@@ -187,28 +201,49 @@ def run_host(request: MapAnalysis, result: np.ndarray, raster=None, probs=None):
     from .overlaps import PatchOverlaps, overlap_pairs_host
     K, config = request.K, request.patches
     zones = map_plane(request.zones, result.shape, True)
-    table = rings = pairs = gaps = attributes = None
+    table = rings = pairs = gaps = attributes = split = None
     if config is not None:
-        result, labels, table = labelled_patches_host(result, K, config)
+        if request.crowns is None:
+            result, labels, table = labelled_patches_host(result, K, config)
+        else:
+            result, labels, table, split = labelled_patches_host(result, K, config, crowns=request.crowns)
         if request.gaps is not None:
             gaps = gaps_of(labels, table, request.gaps.limit2)
         if request.attributes is not None:
             attributes = attributes_of(labels, table, raster, result, probs, request.attributes)
         if request.against is not None:
             _, labels_a, table_a = labelled_patches_host(map_plane(request.against, result.shape, True), K,
-                                                         request.against_patches)
+                                                         request.against_patches, crowns=request.against_crowns)[:3]
             apart = (None if request.distances is None
                      else distances_of(labels_a, table_a, labels, table, request.distances.limit2))
             pairs = PatchOverlaps(table_a, table, *overlap_pairs_host(labels_a, labels), distances=apart)
         if request.outlines:
             rings = outlines_from_labels(labels, result, config.connectivity)
     counts = zonal_counts_host(np.ascontiguousarray(result), zones, K, request.Z)
-    return result, RasterStats(counts, patches=table, outlines=rings, overlaps=pairs, gaps=gaps, attributes=attributes)
+    return result, RasterStats(counts, patches=table, outlines=rings, overlaps=pairs, gaps=gaps, attributes=attributes,
+                               crowns=split)
 
 
-def device_labels(classes, K: int, config: PatchConfig, err=None, in_place: bool = False, areas: bool = True):
+class DeviceSplit:
+    """what ``device_labels`` keeps of a split until the crown table is there: the label plane before the split, the
+    per-crown depths and the flags of ``ops.split_patches``, all on the device; ``finish`` gathers them at the table's roots"""
+
+    def __init__(self, labels_before, crown_depth, flags, config: CrownConfig):
+        self.labels_before, self.crown_depth, self.flags, self.config = labels_before, crown_depth, flags, config
+
+    def finish(self, table) -> CrownSplit:
+        import torch
+        root = torch.from_numpy(np.array(table.root)).to(self.crown_depth.device)
+        parent = self.labels_before.view(-1)[root].to(torch.int64) - 1
+        depth, flags = self.crown_depth[root].cpu().numpy(), self.flags.cpu().numpy()
+        return CrownSplit(table, parent.cpu().numpy(), depth, not flags[1], self.config)
+
+
+def device_labels(classes, K: int, config: PatchConfig, err=None, in_place: bool = False, areas: bool = True, crowns=None):
     """label -> areas -> (sieve) of a uint8 device map, no host synchronisation: ``(classes', labels, area plane, err)``.  A
-    sieve writes ``classes`` itself with ``in_place``, else a clone; ``areas=False`` skips the plane when nothing sieves"""
+    sieve writes ``classes`` itself with ``in_place``, else a clone; ``areas=False`` skips the plane when nothing sieves.
+    With ``crowns`` (a ``CrownConfig``) ``ops.split_patches`` follows the sieve — it reads a few flags back per group of growth
+    rounds —, ``labels`` is the crown plane, the area plane is recomputed on it, and a fifth item is the ``DeviceSplit``"""
     from .. import ops
     if config.sieves and not in_place:
         classes = classes.clone()
@@ -216,22 +251,33 @@ def device_labels(classes, K: int, config: PatchConfig, err=None, in_place: bool
     area = ops.patch_areas(labels) if areas or config.sieves else None
     if config.sieves:
         ops.sieve_patches(classes, labels, area, config.min_pixels)
-    return classes, labels, area, err
+    if crowns is None:
+        return classes, labels, area, err
+    before = labels
+    labels, _, crown_depth, flags = ops.split_patches(classes, before, K, config.connectivity, crowns, err=err)
+    return classes, labels, ops.patch_areas(labels), err, DeviceSplit(before, crown_depth, flags, crowns)
 
 
-def device_patches(classes, K: int, config: PatchConfig, err):
-    """``device_labels`` -> table of a uint8 device map the caller keeps: ``(labels, PatchTable)``"""
+def device_patches(classes, K: int, config: PatchConfig, err, crowns=None):
+    """``device_labels`` -> table of a uint8 device map the caller keeps: ``(labels, PatchTable)``; with ``crowns`` the crown
+    plane, the crown table and, third, the ``CrownSplit``"""
     from .. import ops
-    classes, labels, area, _ = device_labels(classes, K, config, err)
-    return labels, ops.patch_table(labels, classes, area, reuse_area_plane=True)
+    if crowns is None:
+        classes, labels, area, _ = device_labels(classes, K, config, err)
+        return labels, ops.patch_table(labels, classes, area, reuse_area_plane=True)
+    classes, labels, area, _, split = device_labels(classes, K, config, err, crowns=crowns)
+    table = ops.patch_table(labels, classes, area, reuse_area_plane=True)
+    return labels, table, split.finish(table)
 
 
 def run_device(request: Optional[MapAnalysis], out, probs=None, planes=(None, None), raster=None, return_probs: bool = True):
     """the end of every device path: the D2H copy of the final map ``out`` (uint8 [h, w], contiguous) and of the
     probabilities when there are any, with a request its ``RasterStats`` behind them: ``(map[, probs][, stats])`` as host
     arrays.  ``planes``: the request's ``device_planes``.  The order of the enqueued work is fixed: (1) with patches ``out``
-    is labelled, measured and — if asked — sieved IN PLACE; (2) ONE ``ops.zonal_counts`` on ``out``, no synchronisation of
-    its own; (3) with patches the map leaves by a pinned, non-blocking copy (without them by ``out.cpu()``); (4) the roots
+    is labelled, measured and — if asked — sieved IN PLACE, and with ``crowns`` split behind the sieve (``ops.split_patches``
+    reads its growth flags back once per group of rounds; the label plane is the crown plane from here on); (2) ONE
+    ``ops.zonal_counts`` on ``out``, no synchronisation of its own; (3) with patches the map leaves by a pinned,
+    non-blocking copy (without them by ``out.cpu()``); (4) the roots
     are compacted and measured behind it (``ops.patch_table`` reads the row count back), and with ``gaps`` one
     ``ops.patch_proximity`` of the label plane against itself follows (no scalar read-back, its result is downloaded), and
     with ``attributes`` one ``ops.patch_attributes`` of the final label plane over ``raster`` (the uploaded uint8 [C, h, w]
@@ -250,15 +296,19 @@ def run_device(request: Optional[MapAnalysis], out, probs=None, planes=(None, No
     from .. import ops
     from .overlaps import PatchOverlaps
     K, config = request.K, request.patches
-    table = rings = pairs = gaps = attributes = None
+    table = rings = pairs = gaps = attributes = split = None
     err = torch.zeros(1, dtype=torch.int32, device=out.device)
-    if config is not None:
+    if config is not None and request.crowns is None:
         _, labels, area, _ = device_labels(out, K, config, err, in_place=True)
+    elif config is not None:
+        _, labels, area, _, split = device_labels(out, K, config, err, in_place=True, crowns=request.crowns)
     counts, _ = ops.zonal_counts(out, planes[0], K, request.Z, err=err)
     if config is not None:
         host = torch.empty(out.shape, dtype=out.dtype, pin_memory=True)
         host.copy_(out, non_blocking=True)                      # enqueued; the table's read-back waits for it
         table = ops.patch_table(labels, out, area, reuse_area_plane=True)
+        if split is not None:
+            split = split.finish(table)
         if request.gaps is not None:
             gaps = gaps_of(labels, table, request.gaps.limit2, device=True)
         if request.attributes is not None:
@@ -266,7 +316,7 @@ def run_device(request: Optional[MapAnalysis], out, probs=None, planes=(None, No
         if request.outlines:
             rings = ops.patch_outlines(labels, out, config.connectivity)
         if request.against is not None:
-            labels_a, table_a = device_patches(planes[1], K, request.against_patches, err)
+            labels_a, table_a = device_patches(planes[1], K, request.against_patches, err, request.against_crowns)[:2]
             rows = ops.patch_overlaps(labels_a, labels)
             apart = (None if request.distances is None
                      else distances_of(labels_a, table_a, labels, table, request.distances.limit2, device=True))
@@ -282,4 +332,4 @@ def run_device(request: Optional[MapAnalysis], out, probs=None, planes=(None, No
         raise RuntimeError(f"infer_tile: raster statistics met a value out of range (flag {flag}: 1 class >= {K}, "
                            f"2 zone >= {request.Z})")
     return result + (RasterStats(counts.cpu().numpy(), patches=table, outlines=rings, overlaps=pairs, gaps=gaps,
-                                 attributes=attributes),)
+                                 attributes=attributes, crowns=split),)

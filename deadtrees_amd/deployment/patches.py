@@ -245,13 +245,18 @@ def sieve_host(classes_u8, labels, min_pixels: int):
     return c, lab
 
 
-def labelled_patches_host(classes_u8, K: int, config: PatchConfig):
+def labelled_patches_host(classes_u8, K: int, config: PatchConfig, crowns=None):
     """label -> sieve -> measure on the host: (classes', labels', PatchTable); ``classes'`` is ``classes_u8`` itself when
-    the configuration does not sieve, ``labels'`` the label plane of ``classes'``"""
+    the configuration does not sieve, ``labels'`` the label plane of ``classes'``.  With ``crowns`` (a ``CrownConfig``,
+    ``deployment/crowns.py``) the patches are split behind the sieve: ``labels'`` is the crown plane, the table has one row per
+    crown, and a fourth item is the ``CrownSplit``"""
     c = np.ascontiguousarray(classes_u8)
     labels = label_patches_host(c, K, config.connectivity)
     if config.sieves:
         c, labels = sieve_host(c, labels, config.min_pixels)
+    if crowns is not None:
+        from .crowns import crowned_patches_host
+        return (c,) + crowned_patches_host(c, labels, K, config.connectivity, crowns)
     return c, labels, measure_patches_host(labels, c)
 
 

@@ -71,10 +71,12 @@ class RasterStats:
     rasters has none.  ``gaps``: the ``PatchGaps`` (``deployment/proximity.py``: every patch's distance to the nearest other
     patch, aligned with ``patches``) when they were asked for, else None — then ``repr`` and ``==`` do not mention them; a sum
     of rasters has none.  ``attributes``: the ``PatchAttributes`` (``deployment/attributes.py``: band statistics, indices and
-    confidence per patch, aligned with ``patches``), handled like ``gaps``"""
+    confidence per patch, aligned with ``patches``), handled like ``gaps``.  ``crowns``: the ``CrownSplit``
+    (``deployment/crowns.py``) when the patches were split into crowns — ``patches`` then has one row per crown, and everything
+    aligned with it is crown-level —, handled like ``gaps``"""
 
     def __init__(self, counts, pixel_area_m2: float = PIXEL_AREA_M2, patches=None, outlines=None, overlaps=None, gaps=None,
-                 attributes=None):
+                 attributes=None, crowns=None):
         counts = np.array(counts, dtype=np.int64)
         if counts.ndim != 2 or counts.shape[0] < 1 or counts.shape[1] < 2:
             raise ValueError(f"RasterStats: counts must be [Z >= 1, K >= 2], got shape {counts.shape}")
@@ -116,6 +118,17 @@ class RasterStats:
             if patches is None or attributes.table != patches:
                 raise ValueError("RasterStats: attributes need the PatchTable they belong to")
         self._attributes = attributes
+        if crowns is not None:
+            from .crowns import CrownSplit
+            if not isinstance(crowns, CrownSplit):
+                raise ValueError(f"RasterStats: crowns must be a CrownSplit or None, got {type(crowns).__name__}")
+            if patches is None or crowns.table != patches:
+                raise ValueError("RasterStats: crowns need the PatchTable they belong to")
+        self._crowns = crowns
+
+    @property
+    def crowns(self):
+        return self._crowns
 
     @property
     def patches(self):
@@ -184,7 +197,7 @@ class RasterStats:
             return False
         if (self._overlaps is None) != (other._overlaps is None) or (self._gaps is None) != (other._gaps is None):
             return False
-        if (self._attributes is None) != (other._attributes is None):
+        if (self._attributes is None) != (other._attributes is None) or (self._crowns is None) != (other._crowns is None):
             return False
         return (self._counts.shape == other._counts.shape and bool((self._counts == other._counts).all())
                 and self.pixel_area_m2 == other.pixel_area_m2
@@ -194,7 +207,8 @@ class RasterStats:
                     for a in ("xy", "ring_offsets", "ring_polygon", "values")))
                 and (self._overlaps is None or self._overlaps == other._overlaps)
                 and (self._gaps is None or self._gaps == other._gaps)
-                and (self._attributes is None or self._attributes == other._attributes))
+                and (self._attributes is None or self._attributes == other._attributes)
+                and (self._crowns is None or self._crowns == other._crowns))
 
     __hash__ = None
 
@@ -208,6 +222,8 @@ class RasterStats:
             tail += f", gaps={self._gaps!r}"
         if self._attributes is not None:
             tail += f", attributes={self._attributes!r}"
+        if self._crowns is not None:
+            tail += f", crowns={self._crowns!r}"
         return f"RasterStats(counts={self._counts.tolist()}, pixel_area_m2={self.pixel_area_m2!r}{tail})"
 
 

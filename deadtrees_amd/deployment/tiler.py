@@ -28,6 +28,7 @@ import torch
 
 from .analysis import MapAnalysis, run_device, run_host
 from .attributes import AttributeConfig, PatchAttributes, patch_attributes, patch_attributes_host  # noqa: F401
+from .crowns import CrownConfig, CrownSplit, split_patches, split_patches_host  # noqa: F401
 from .outlines import outlines_geojson, polygonize, polygonize_host, write_outlines_geojson  # noqa: F401
 from .overlaps import (PatchMatch, PatchOverlaps, PatchTracks, overlap_pairs_host, patch_overlaps)  # noqa: F401
 from .proximity import (PatchDistances, PatchGaps, ProximityConfig, patch_distances, patch_gaps,  # noqa: F401
@@ -245,11 +246,13 @@ class Tiler:
         return self._outdata[0:self._tile_info.size[0], 0:self._tile_info.size[1]]
 
     def stats(self, zones=None, classes: int = 3, n_zones: Optional[int] = None, patches=None, outlines=None,
-              against=None, against_patches=None, distances=None, gaps=None, attributes=None):
+              against=None, against_patches=None, distances=None, gaps=None, attributes=None, crowns=None,
+              against_crowns=None):
         """``RasterStats`` of ``result``: what ``infer_tile(..., stats=True)`` returns, for a caller of the reference's own
         ``get_batches`` / ``put_batches`` loop, computed on the host (``analysis.run_host``).  ``classes``: the model's class
         count; ``zones`` / ``n_zones`` / ``patches`` / ``outlines`` / ``against`` / ``against_patches`` / ``distances`` /
-        ``gaps`` / ``attributes``: as in ``infer_tile``, with the same rules (``MapAnalysis``); the attributes are read from the
+        ``gaps`` / ``attributes`` / ``crowns`` / ``against_crowns``: as in ``infer_tile``, with the same rules
+        (``MapAnalysis``); the attributes are read from the
         loaded raster, and the host path has no probabilities, so ``confidence=True`` is refused.  Polygons are burnt by
         ``rasterize_host``; a ``patches`` configuration that sieves changes ``result`` itself, and the counts are those of the
         sieved map"""
@@ -258,7 +261,8 @@ class Tiler:
         return self._analyse(MapAnalysis.of("Tiler.stats", self.result.shape, classes, zones, against, self._raster(),
                                             n_zones=n_zones, patches=patches, outlines=outlines,
                                             against_patches=against_patches, distances=distances, gaps=gaps,
-                                            attributes=attributes, no_probs="Tiler.stats runs on the host, which has none"))
+                                            attributes=attributes, no_probs="Tiler.stats runs on the host, which has none",
+                                            crowns=crowns, against_crowns=against_crowns))
 
     def _raster(self) -> np.ndarray:
         """the loaded raster cropped to its own size: a view of the padded input"""
@@ -284,14 +288,16 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
                   device: str = "cuda", tile_shape: Optional[Tuple[int, int]] = None, skip_blank: bool = True,
                   overlap: int = 0, blend: str = "crop", return_probs: bool = False, tta=None, stats: bool = False,
                   zones=None, n_zones: Optional[int] = None, patches=None, outlines=None, against=None,
-                  against_patches=None, distances=None, gaps=None, attributes=None, decision=None):
+                  against_patches=None, distances=None, gaps=None, attributes=None, decision=None, crowns=None,
+                  against_crowns=None):
     """the directory loop of scripts/inference.py:71-115 over in-memory rasters (GeoTIFF I/O needs rioxarray, absent
     here): ``rasters`` yields ``array`` or ``(key, array)``; rank r of ``world`` takes rasters r, r + world, ... (tiles are
     independent: no collective).  Yields ``(key, class_map)`` in input order of the rank's share; rasters whose band 1
     holds only 0 / 255 (``is_valid_tile``, :60-62) are skipped like the reference does — ``(key, None)`` — without a
     forward pass (device reduction over the uploaded raster, ``ops.band_has_data``).  ``overlap`` / ``blend`` /
     ``return_probs`` / ``tta`` / ``stats`` / ``n_zones`` / ``patches`` / ``outlines`` / ``against_patches`` / ``distances`` /
-    ``gaps`` / ``attributes`` / ``decision``: as in ``infer_tile``, with the same rules, checked before the first raster is read (every raster
+    ``gaps`` / ``attributes`` / ``decision`` / ``crowns`` / ``against_crowns``: as in ``infer_tile``, with the same rules,
+    checked before the first raster is read (every raster
     stays on its rank, so overlap needs no exchange); ``zones``: a callable ``key -> uint8 [h, w] array, PolygonSet or None``,
     or a mapping (a missing key is None); ``against``: the same for the map every raster is compared with (a uint8 array, a ``PolygonSet``
     or None: that raster's statistics carry no overlaps).
@@ -299,7 +305,7 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
     ``RasterStats`` of a rank's share add up (``+``) to that rank's part of the regional totals."""
     rules = MapAnalysis.rules("infer_rasters", getattr(inference, "classes", None) if stats else None, stats, zones, n_zones,
                               patches, outlines, against, against_patches, distances, gaps, attributes,
-                              _no_probs(inference, overlap, blend, tta))
+                              _no_probs(inference, overlap, blend, tta), crowns=crowns, against_crowns=against_crowns)
     decision = _check_decision("infer_rasters", inference, decision, overlap, blend, tta)
     for i, item in enumerate(rasters):
         if i % world != rank:
@@ -317,7 +323,7 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
                on_device: Optional[bool] = None, skip_blank: bool = False, overlap: int = 0, blend: str = "crop",
                return_probs: bool = False, tta=None, stats: bool = False, zones=None, n_zones: Optional[int] = None,
                patches=None, outlines=None, against=None, against_patches=None, distances=None, gaps=None,
-               attributes=None, decision=None):
+               attributes=None, decision=None, crowns=None, against_crowns=None):
     """whole-tile inference of scripts/inference.py:80-115 on the MI355X path: split -> (uint8 H2D, normalise on the
     device) -> forward + fused argmax -> uint8 D2H -> merge.  With world > 1 the sub-tile batches j = rank (mod world)
     are processed locally and the uint8 class maps are all-gathered (no other collective: tiles are independent).
@@ -396,12 +402,20 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     Validation probabilities are single-tile softmaxes, these are blended ones: the threshold transfers, the bit-for-bit
     closure of the curves holds for identical inputs.  A patch-wise decision (``Decision(T, low=..., min_confidence=...,
     connectivity=...)``: grow patches at the low thresholds, keep those with a pixel at ``T`` and a mean of ``M``) runs
-    through ``ops.decide_patchwise`` in the same place.  None: nothing changes."""
+    through ``ops.decide_patchwise`` in the same place.  None: nothing changes.
+
+    ``crowns=True`` or a ``CrownConfig(min_core2, max_rounds=256, depth_cap2=65535)`` (needs ``patches``; ``True``:
+    ``CrownConfig.from_radius(2)``): touching crowns are split by their inscribed depth behind the sieve
+    (``deployment/crowns.py``: cores where the squared distance to another class reaches ``min_core2``, grown back over their
+    patch).  The label plane IS the crown plane from there on: ``.patches`` has one row per crown, and outlines, overlaps,
+    distances, gaps and attributes align with it as they do with patches; ``.crowns`` is the ``CrownSplit`` (per crown the
+    patch it was cut from and its inscribed depth; ``converged``).  ``against_crowns`` (needs ``against``) splits the patches of
+    ``against`` the same way.  The returned map and the counts do not change: splitting moves no pixel between classes."""
     decision = _check_decision("infer_tile", inference, decision, overlap, blend, tta)
     request = MapAnalysis.of("infer_tile", np.shape(arr_chw_u8)[1:], getattr(inference, "classes", None) if stats else None,
                              zones, against, arr_chw_u8, stats=stats, n_zones=n_zones, patches=patches, outlines=outlines,
                              against_patches=against_patches, distances=distances, gaps=gaps, attributes=attributes,
-                             no_probs=_no_probs(inference, overlap, blend, tta))
+                             no_probs=_no_probs(inference, overlap, blend, tta), crowns=crowns, against_crowns=against_crowns)
     return _infer_tile(inference, arr_chw_u8, request, subtile, batch_size, rank, world, device, group, tile_shape, on_device,
                        skip_blank, overlap, blend, return_probs, tta, decision)
 

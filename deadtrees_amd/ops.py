@@ -1317,7 +1317,9 @@ _LIB_CONSTANTS = {"PATCH_TILE": ("dt_patch_tile", 2), "OUTLINE_CHUNK": ("dt_outl
                   "CURVE_CHUNK": ("dt_curve_chunk", 1),
                   "OVERLAP_CHUNK": ("dt_overlap_chunk", 1), "PROXIMITY_SEGMENT": ("dt_proximity_segment", 1),
                   "PROXIMITY_WINDOW": ("dt_proximity_window", 1), "ATTRIBUTE_SPAN": ("dt_attribute_span", 1),
-                  "SUPPORT_SPAN": ("dt_support_span", 1)}
+                  "SUPPORT_SPAN": ("dt_support_span", 1), "CROWN_SEGMENT": ("dt_crown_segment", 1)}
+# growth rounds of ``split_patches`` enqueued back to back before the host reads their flags
+CROWN_ROUND_GROUP = 8
 
 
 def _constant(name: str):
@@ -1675,6 +1677,102 @@ def patch_attributes(labels: torch.Tensor, roots, raster_u8: torch.Tensor, class
                                                   _p(classes_u8), _p(probs), K, flat, len(pairs), _p(sums), _p(extremes),
                                                   _st()), "dt_patch_attributes_u8")
     return sums.cpu().numpy(), extremes.cpu().numpy()
+
+
+def _aligned(t: torch.Tensor, to: int = 16) -> torch.Tensor:
+    """``t`` contiguous at an address that is a multiple of ``to`` (a view at an odd storage offset is copied)"""
+    t = t.contiguous()
+    return t if t.data_ptr() % to == 0 else t.clone()
+
+
+def _crown_limits(what: str, h: int, w: int):
+    if max(h, w) > 16384 or h * w > 2 ** 31 - 2:
+        raise RuntimeError(f"{what}: raster {h}x{w}: sides must be <= 16384 and h * w <= {2 ** 31 - 2}")
+
+
+def patch_depth2(classes_u8: torch.Tensor, K: int, cap2: int = 65535, err=None, core2=None):
+    """the depth plane of a uint8 class map [h, w] on the device (``dt_patch_depth2_u8``; step 1 of the contract in
+    ``deployment/crowns.py``): int32 [h, w], 0 on class 0, elsewhere ``min(cap2, squared distance to the nearest pixel inside
+    the raster of another class)``.  Returns ``(depth2, err)``; with ``core2`` (E) ``(depth2, core, err)``, ``core`` uint8
+    [h, w] the class where ``depth2 >= core2``, written in the same pass.  No host synchronisation: a class >= K ORs 1 into
+    ``err`` and has depth 0.  The map is not written.  Four launches; workspace 2 bytes per pixel (the column distances) and
+    16 bytes per column and segment of ``CROWN_SEGMENT`` rows"""
+    h, w = _patch_planes("patch_depth2", classes_u8)
+    _crown_limits("patch_depth2", h, w)
+    for name, v in (("cap2", cap2),) + ((("core2", core2),) if core2 is not None else ()):
+        if isinstance(v, bool) or int(v) != v or not 1 <= v <= 2 ** 30:
+            raise RuntimeError(f"patch_depth2: {name} must be an integer in 1..2**30, got {v!r}")
+    if core2 is not None and core2 > cap2:
+        raise RuntimeError(f"patch_depth2: core2={core2} above cap2={cap2}")
+    dev = classes_u8.device
+    err = _err_flag("patch_depth2", err, dev)
+    column = torch.empty((h, w), dtype=torch.int16, device=dev)                     # read as uint16 by the kernels
+    carry = torch.empty((-(-h // _constant("CROWN_SEGMENT")), w, 4), dtype=torch.int32, device=dev)
+    depth2 = torch.empty((h, w), dtype=torch.int32, device=dev)
+    core = None if core2 is None else torch.empty((h, w), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().dt_patch_depth2_u8(_p(classes_u8.contiguous()), h, w, int(K), int(cap2),
+                                              int(core2 if core2 is not None else 1), _p(column), _p(carry), _p(depth2),
+                                              _p(core), _p(err), _st()), "dt_patch_depth2_u8")
+    return (depth2, err) if core2 is None else (depth2, core, err)
+
+
+def split_patches(classes_u8: torch.Tensor, labels: torch.Tensor, K: int, connectivity: int, config, err=None):
+    """the crown plane of a uint8 class map [h, w] and its label plane on the device (csrc/crowns.hip; contract in
+    ``deployment/crowns.py``): ``(crowns int32 [h, w], depth2 int32 [h, w], crown_depth int32 [h * w], flags int32 [3])`` —
+    ``crowns`` keeps the label contract (a crown's label names its first pixel), ``crown_depth`` holds at every crown's root
+    the largest ``depth2`` of its pixels (``crowns.crown_depths_host``), ``flags`` = (1 if a class >= K was met, 1 if the
+    growth has NOT converged, the growth rounds that labelled a pixel).  ``labels`` is the plane ``label_patches`` gave for
+    ``classes_u8`` (after the sieve); neither input is written.
+
+    ``patch_depth2`` (depth and cores in one pass) -> ``label_patches`` on the cores -> ``dt_crown_grow`` once per round, in
+    groups of ``CROWN_ROUND_GROUP`` with no synchronisation inside a group; after a group the host reads the group's flag
+    slots (ONE small read-back per group) and stops when the last round of the group labelled nothing: later rounds would be
+    no-ops -> ``dt_crown_remainder`` -> ``label_patches`` on the remainder -> ``dt_crown_merge`` -> ``dt_crown_relabel``.
+    Workspace per pixel while it runs: 24 bytes of int32 planes (depth2, the two growth planes — one ends as ``crowns``,
+    the other as the merge's first-pixel plane —, the remainder's labels, the per-seg depth and ``crown_depth``) and 4 bytes
+    of narrow ones (column distances, cores, remainder); 12 bytes per pixel are returned"""
+    from .deployment.crowns import CrownConfig
+    h, w = _patch_planes("split_patches", classes_u8, labels=labels)
+    _crown_limits("split_patches", h, w)
+    if not isinstance(config, CrownConfig):
+        raise RuntimeError(f"split_patches: config must be a CrownConfig, got {config!r}")
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise RuntimeError(f"split_patches: connectivity must be 4 or 8, got {connectivity!r}")
+    lib, dev = _lib.load(), classes_u8.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    classes_u8 = _aligned(classes_u8, 4)
+    flags = torch.zeros(3, **i32)
+    depth2, core, _ = patch_depth2(classes_u8, K, config.depth_cap2, err=flags[0:1], core2=config.min_core2)
+    src, _ = label_patches(core, K, connectivity, err=flags[0:1])
+    src = _aligned(src)
+    dst = torch.empty((h, w), **i32)
+    rounds = done = 0
+    stream = _st()
+    while done < config.max_rounds:
+        group = min(CROWN_ROUND_GROUP, config.max_rounds - done)
+        slots = torch.zeros(group, **i32)
+        for k in range(group):                                 # slot k of the group: 4 bytes each
+            _lib.check(lib.dt_crown_grow(_p(classes_u8), _p(src), _p(dst), h, w, int(connectivity), _p(slots) + 4 * k, stream),
+                       "dt_crown_grow")
+            src, dst = dst, src
+        done += group
+        took = slots.tolist()                                  # the group's one read-back
+        rounds += sum(1 for v in took if v)
+        if took[-1] == 0:
+            break
+    flags[2] = rounds
+    remainder = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    _lib.check(lib.dt_crown_remainder(_p(classes_u8), _p(src), h, w, int(connectivity), _p(remainder), _p(flags[1:2]), _st()),
+               "dt_crown_remainder")
+    seg, _ = label_patches(remainder, K, connectivity, err=flags[0:1])
+    first = dst.view(-1).fill_(2 ** 31 - 1)
+    depth = torch.zeros(h * w, **i32)
+    crown_depth = torch.zeros(h * w, **i32)
+    _lib.check(lib.dt_crown_merge(_p(src), _p(seg), _p(depth2), h, w, _p(first), _p(depth), _st()), "dt_crown_merge")
+    _lib.check(lib.dt_crown_relabel(_p(seg), _p(first), _p(depth), h, w, _p(src), _p(crown_depth), _st()), "dt_crown_relabel")
+    if err is not None:
+        _err_flag("split_patches", err, dev).bitwise_or_(flags[0:1])
+    return src, depth2, crown_depth, flags
 
 
 def signed_distmap(labels: torch.Tensor, K: int):

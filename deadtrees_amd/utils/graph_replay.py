@@ -7,6 +7,7 @@ workspaces redirected into the graph's pool, then for every later call copy the 
 """
 from __future__ import annotations
 
+import gc
 from typing import Callable, Optional, Sequence
 
 import torch
@@ -38,8 +39,19 @@ class GraphReplay:
         # workspaces of the captured pass live (and stay) in the graph's pool
         with self._engine.capture_workspaces(self._keep) as self._ws:
             torch.cuda.synchronize()
-            with torch.cuda.graph(graph):
-                self._result = self._capture_fn(*self._inputs)
+            # a cyclic collection that starts inside the capture tears down whatever garbage it finds — an earlier
+            # trainer's graph and its pool, tensors with recorded streams — with calls a capturing stream does not allow,
+            # and the process aborts.  torch.cuda.graph no longer collects on entry: collect here, and keep the collector
+            # off until the capture has ended
+            gc.collect()
+            collecting = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(graph):
+                    self._result = self._capture_fn(*self._inputs)
+            finally:
+                if collecting:
+                    gc.enable()
         self._graph = graph
 
     def __call__(self, *inputs):

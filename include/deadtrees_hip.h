@@ -576,6 +576,39 @@ int dt_patch_attributes_u8(const int32_t* labels, const uint8_t* raster, int C, 
                            int n, const uint8_t* classes, const float* probs, int K, const int* pairs, int n_pairs,
                            int64_t* sums, int32_t* extremes, void* stream);
 
+/* Crowns (deployment/crowns.py states the contract): touching crowns split by their inscribed depth.  classes uint8 [h][w]
+ * and int32 planes [h][w] in device memory, sides <= 16384, h * w <= 2^31 - 2, connectivity 4 or 8.  Integers only, no entry
+ * point synchronises, no workgroup waits for another, every grid follows the pixel count; the results are pure functions of
+ * the inputs (minima and maxima do not depend on the order of the atomics).
+ *
+ * dt_crown_segment: the rows of one column segment of dt_patch_depth2_u8.
+ * dt_patch_depth2_u8: depth2 int32 [h][w] (overwritten): 0 on class 0 and on a class >= K (which ORs 1 into err_flag[0]),
+ *   elsewhere min(cap2, the squared distance to the nearest pixel inside the raster of another class), 1 <= cap2 <= 2^30.
+ *   core uint8 [h][w] or NULL: the class where depth2 >= core2 (1 <= core2 <= cap2), else 0.  Workspace: column uint16 [h][w]
+ *   and carry int32 [ceil(h / segment)][w][4], 16-byte aligned.  Four launches: three for the columns (segment states, one
+ *   lane per column chains them, the distances), one for the rows (outward search in LDS, at most 2 sqrt(cap2) entries).
+ * dt_crown_grow: ONE growth round: dst = src, except that a pixel with a class and src == 0 takes the minimum of src over its
+ *   neighbours of the same class with src != 0.  src and dst are different planes, 16-byte aligned, classes 4-byte aligned.
+ *   slot int32 [1]: |= 1 when the round labelled a pixel.
+ * dt_crown_remainder: remainder uint8 [h][w] = the class where grown == 0, else 0; flag int32 [1] |= 1 when a pixel with a
+ *   class and grown == 0 has a neighbour of its class with grown != 0 (the growth has not converged).
+ * dt_crown_merge: seg (the label plane of the remainder) becomes grown where that is not 0 — a value outside 1 .. h * w is 0
+ *   —, IN PLACE; first int32 [h * w] PRESET TO INT32_MAX and depth int32 [h * w] ZEROED by the caller: first[seg - 1] = the
+ *   smallest pixel index of the seg, depth[seg - 1] = its largest depth2.
+ * dt_crown_relabel: crowns int32 [h][w] (overwritten, a plane of its own) = 1 + first[seg - 1], 0 where seg is 0;
+ *   crown_depth int32 [h * w], ZEROED by the caller: at a crown's root (label - 1) the largest depth2 of its pixels. */
+int dt_crown_segment(int* rows);
+int dt_patch_depth2_u8(const uint8_t* classes, int h, int w, int K, int cap2, int core2, uint16_t* column, int32_t* carry,
+                       int32_t* depth2, uint8_t* core, int32_t* err_flag, void* stream);
+int dt_crown_grow(const uint8_t* classes, const int32_t* src, int32_t* dst, int h, int w, int connectivity, int32_t* slot,
+                  void* stream);
+int dt_crown_remainder(const uint8_t* classes, const int32_t* grown, int h, int w, int connectivity, uint8_t* remainder,
+                       int32_t* flag, void* stream);
+int dt_crown_merge(const int32_t* grown, int32_t* seg, const int32_t* depth2, int h, int w, int32_t* first, int32_t* depth,
+                   void* stream);
+int dt_crown_relabel(const int32_t* seg, const int32_t* first, const int32_t* depth, int h, int w, int32_t* crowns,
+                     int32_t* crown_depth, void* stream);
+
 /* Operating points (deadtrees_amd/loss/curves.py states the contract): probability histograms of a validation epoch and the
  * decision that applies a threshold per class.  Both quantise a probability p the same way:
  * q = floor(min(max(p, 0), 1) * 65535 + 0.5), product and sum each rounded to fp32, NaN -> 0; bin = q >> 8.
