@@ -1864,6 +1864,12 @@ class FlatAdam:
             idx = torch.tensor(src, dtype=torch.int64, device=dev)
             self.t_seg = self.t_seg.index_select(0, idx)
             self.hyper_seg = self.hyper_seg.view(-1, 3).index_select(0, idx).reshape(-1).contiguous()
+        self._set_partition(segs, trainable)
+
+    def _set_partition(self, segs, trainable):
+        """the range table of a partition: what the ranged kernels read (``table``, its rows, the longest range, the
+        partial-sum buffer) is derived here from ``segs`` / ``trainable`` and from nothing else"""
+        dev = self.p.device
         self._segments, self._trainable = segs, trainable
         table, row = [], 0
         lib = _lib.load()
@@ -1889,6 +1895,72 @@ class FlatAdam:
         self.t = 0
         if lr is not None:
             self.lr = float(lr)
+
+    def state_dict(self) -> dict:
+        """everything a continued run needs, on the host: the moments, the device step counts and bias corrections (per
+        range too once ranges exist), the device learning rate, and the host fields.  The range table, its rows and the
+        partial-sum buffer are not stored: ``load_state_dict`` derives them from the partition (host sync)."""
+        sd = {name: getattr(self, name).detach().cpu() for name in ("m", "v", "t_dev", "hyper", "lr_dev")}
+        if self._segments is not None:
+            sd["t_seg"], sd["hyper_seg"] = self.t_seg.detach().cpu(), self.hyper_seg.detach().cpu()
+        sd.update(t=int(self.t), lr=float(self.lr), betas=[float(b) for b in self.betas], eps=float(self.eps),
+                  max_norm=None if self.max_norm is None else float(self.max_norm),
+                  _segments=None if self._segments is None else [[int(a), int(b)] for a, b in self._segments],
+                  _trainable=None if self._trainable is None else [bool(t) for t in self._trainable])
+        return sd
+
+    def check_state_dict(self, sd):
+        """RuntimeError unless ``sd`` fits this buffer; reads only"""
+        n = self.p.numel()
+        want = {"m": n, "v": n, "t_dev": 1, "hyper": 3, "lr_dev": 1}
+        segs = sd.get("_segments")
+        if segs is not None:
+            want.update(t_seg=len(segs), hyper_seg=3 * len(segs))
+        for name, numel in want.items():
+            if name not in sd:
+                raise RuntimeError(f"FlatAdam: the state has no {name!r}")
+            if sd[name].numel() != numel:
+                raise RuntimeError(f"FlatAdam: state {name!r} of {sd[name].numel()} elements, this optimiser's has {numel}")
+        if segs is not None:
+            flags = sd.get("_trainable")
+            cuts = [int(a) for a, _ in segs] + [int(segs[-1][1])] if segs else []
+            if (not segs or cuts[0] != 0 or cuts[-1] != n or any(int(b) != c for (_, b), c in zip(segs, cuts[1:]))
+                    or any(a >= b for a, b in zip(cuts[:-1], cuts[1:])) or flags is None or len(flags) != len(segs)
+                    or not any(flags)):
+                raise RuntimeError(f"FlatAdam: the saved ranges {segs} / {flags} do not partition a {n}-float buffer")
+            if sum(bool(f) for f in flags) > MAX_TRAINABLE_SEGMENTS:
+                raise RuntimeError(f"FlatAdam: {sum(bool(f) for f in flags)} trainable ranges, at most {MAX_TRAINABLE_SEGMENTS}")
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        """continue where ``state_dict()`` was taken.  Every length is checked first (RuntimeError, nothing written).  The
+        saved partition goes through ``set_trainable``'s table builder; then the values are copied INTO the existing device
+        tensors — ``m``, ``v``, ``t_dev``, ``hyper`` and ``lr_dev`` are never rebound, so whoever holds them (a captured
+        graph, a view) keeps seeing the optimiser's state.  The per-range tensors are rebound where their length changes,
+        as ``set_trainable`` does: call outside graph capture and drop graphs captured on another partition."""
+        self.check_state_dict(sd)
+        dev = self.p.device
+        segs = sd.get("_segments")
+        if segs is None:
+            self._segments = self._trainable = None
+            self.t_seg = self.hyper_seg = self.table = None
+            self._table_rows = self._table_n = self._max_len = 0
+        else:
+            segs = [(int(a), int(b)) for a, b in segs]
+            for name, numel, like in (("t_seg", len(segs), self.t_dev), ("hyper_seg", 3 * len(segs), self.hyper)):
+                if getattr(self, name) is None or getattr(self, name).numel() != numel:
+                    setattr(self, name, torch.zeros(numel, dtype=like.dtype, device=dev))
+            self._set_partition(segs, [bool(t) for t in sd["_trainable"]])
+            self.t_seg.copy_(sd["t_seg"].to(dev, self.t_seg.dtype).view(-1))
+            self.hyper_seg.copy_(sd["hyper_seg"].to(dev, self.hyper_seg.dtype).view(-1))
+        for name in ("m", "v", "t_dev", "hyper", "lr_dev"):
+            t = getattr(self, name)
+            t.copy_(sd[name].to(dev, t.dtype).view(-1))
+        self.t, self.lr = int(sd["t"]), float(sd["lr"])
+        self.betas, self.eps = tuple(float(b) for b in sd["betas"]), float(sd["eps"])
+        self.max_norm = None if sd["max_norm"] is None else float(sd["max_norm"])
+        # what the device holds is the saved run's: sync_lr fills again exactly when that run's next step would have
+        self._lr_on_dev = float(sd["lr_dev"].double().view(-1)[0])
 
     def sync_lr(self):
         """push a changed learning rate to the device (stream-ordered fill: the value travels as a kernel argument).

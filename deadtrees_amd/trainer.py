@@ -10,6 +10,7 @@ statistics, mean-reduced gradients — SURVEY §8e).
 """
 from __future__ import annotations
 
+import hashlib
 import json
 import math
 import os
@@ -317,6 +318,80 @@ class HipTrainer:
             tail = host[-1 - K - K * 2 * 256 * 256:-1].to(torch.int64).numpy()
             out["objects"] = ObjectCurves(tail[:-K].reshape(K, 2, 256, 256), tail[-K:], objects, names)
         return out
+
+    # ------------------------------------------------------------------ full state: what an exact continuation needs
+    _DESCRIPTION = ("decoder", "in_channels", "classes", "n_params", "layout", "precision", "losses", "average",
+                    "average_decay", "world")
+
+    def describe(self) -> dict:
+        """what must agree between the trainer that saved a state and the one that loads it (JSON-serialisable);
+        "layout" is a fingerprint of the spec's (key, offset, length) list.  ``graph`` is not part of it."""
+        spec, avg = self.model.spec, self.averager
+        layout = hashlib.sha256(repr([(c.key, int(c.w_off), int(c.w_size)) for c in spec.convs]).encode()).hexdigest()
+        return {"decoder": spec.decoder_kind, "in_channels": int(spec.in_channels), "classes": int(spec.classes),
+                "n_params": int(spec.n_params), "layout": layout, "precision": self.model.precision,
+                "losses": list(self.losses), "average": None if avg is None else avg.mode,
+                "average_decay": None if avg is None else float(avg.decay), "world": int(self.world)}
+
+    @torch.no_grad()
+    def state_dict(self) -> dict:
+        """Everything the next ``step`` depends on, downloaded: the RAW flat buffers (``flat_params`` with its alignment
+        padding and the outer taps of a 1x1 head held as a 3x3 kernel, which no smp key names; ``bn_state``;
+        ``num_batches_tracked``), the optimiser's and the averager's state, the module flags and ``describe()``."""
+        m = self.model
+        return {"description": self.describe(),
+                "flat_params": m.flat_params.detach().cpu(), "bn_state": m.bn_state.detach().cpu(),
+                "num_batches_tracked": m.num_batches_tracked.detach().cpu(),
+                "opt": self.opt.state_dict(),
+                "averager": None if self.averager is None else self._need_averager("state_dict").state_dict(),
+                "flags": {"encoder_frozen": bool(m.encoder_frozen), "encoder_training": bool(m.encoder.training),
+                          "training": bool(m.training)}}
+
+    def check_state_dict(self, sd: dict):
+        """ValueError naming the first field of the description that differs (RuntimeError for a tensor of another
+        length); reads only"""
+        mine, theirs = self.describe(), sd.get("description")
+        if not isinstance(theirs, dict):
+            raise ValueError("load_state_dict: not a HipTrainer state (no description)")
+        for field in self._DESCRIPTION:
+            if theirs.get(field) != mine[field]:
+                raise ValueError(f"load_state_dict: {field} differs: the state was saved with {theirs.get(field)!r}, this "
+                                 f"trainer has {mine[field]!r}")
+        m = self.model
+        for name, t in (("flat_params", m.flat_params), ("bn_state", m.bn_state),
+                        ("num_batches_tracked", m.num_batches_tracked)):
+            if sd[name].numel() != t.numel():
+                raise RuntimeError(f"load_state_dict: {name} of {sd[name].numel()} elements, the model's has {t.numel()}")
+        self.opt.check_state_dict(sd["opt"])
+        if self.averager is not None and sd["averager"]["avg"].numel() != self.averager.avg.numel():
+            raise RuntimeError(f"load_state_dict: average of {sd['averager']['avg'].numel()} floats, "
+                               f"this trainer's has {self.averager.avg.numel()}")
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict):
+        """Continue where ``state_dict()`` was taken, on this trainer's own tensors.  The description is checked first
+        (ValueError, nothing modified).  Every tensor is then written IN PLACE — the optimiser, the averager and the
+        engine hold views of these buffers — the engine's weight images are marked stale, and the step, recalibration and
+        validation replay caches are dropped: their graphs were captured on another trajectory's partition and flags, so
+        the next ``step`` warms up and captures again on the restored state (``static_batch()`` is None until then)."""
+        self.check_state_dict(sd)
+        m = self.model
+        dev = m.flat_params.device
+        m.flat_params.data.copy_(sd["flat_params"].to(dev, torch.float32).view(-1))
+        m.bn_state.copy_(sd["bn_state"].to(dev, torch.float32).view(-1))
+        m.num_batches_tracked.copy_(sd["num_batches_tracked"].to(dev, torch.int64).view(-1))
+        self.opt.load_state_dict(sd["opt"])
+        if self.averager is not None:
+            self._need_averager("load_state_dict").load_state_dict(sd["averager"])
+        flags = sd["flags"]
+        m.train(bool(flags["training"]))                     # (recurses into the encoder view: its own flag comes after)
+        m.encoder.train(bool(flags["encoder_training"]))
+        m.encoder_frozen = bool(flags["encoder_frozen"])
+        m.engine.mark_weights_changed()
+        self._step_replays.clear()
+        self._recal_replays.clear()
+        self._val_replays.clear()
+        self.last = {}
 
     def step(self, img: torch.Tensor, mask: torch.Tensor, distmap: Optional[torch.Tensor] = None,
              alpha: float = 1.0):
@@ -682,6 +757,48 @@ class ModelSelection:
                 return True
         return False
 
+    def state_dict(self) -> dict:
+        """the decisions so far, JSON-serialisable (``es_best`` starts at +-inf: Python's ``json`` round-trips ``Infinity``
+        and ``NaN``).  The configuration is not part of it: a resumed run brings its own."""
+        return {"kept": [[float(s), str(p)] for s, p in self.kept],
+                "best_model_path": self.best_model_path, "best_model_score": self.best_model_score,
+                "last_model_path": self.last_model_path, "es_best": self.es_best, "wait": int(self.wait),
+                "stopped_epoch": self.stopped_epoch}
+
+    def load_state_dict(self, sd: dict):
+        self.kept = [(float(s), str(p)) for s, p in sd["kept"]]
+        self.best_model_path, self.last_model_path = sd["best_model_path"], sd["last_model_path"]
+        self.best_model_score = None if sd["best_model_score"] is None else float(sd["best_model_score"])
+        self.es_best = None if sd["es_best"] is None else float(sd["es_best"])
+        self.wait = int(sd["wait"])
+        self.stopped_epoch = None if sd["stopped_epoch"] is None else int(sd["stopped_epoch"])
+
+
+def _generic_hparams(trainer, training_conf: Optional[dict] = None) -> dict:
+    """hyper-parameters of a checkpoint from the model's own configuration (``checkpoint_writer`` without a module)"""
+    from .utils.config import default_network, default_training
+    model = trainer if isinstance(trainer, UNetHIP) else trainer.model
+    K = model.spec.classes
+    classes = ["background", "deadtree"] if K == 2 else ["background"] + [f"class{i}" for i in range(1, K)]
+    net = dict(default_network(architecture=model.spec.decoder_kind, in_channels=model.spec.in_channels, classes=classes,
+                               losses=list(getattr(trainer, "losses", ("GDICE", "FOCAL")))))
+    if model.spec.decoder_kind == "efficientunetplusplus":
+        net.update(squeeze_ratio=model.spec.squeeze_ratio, expansion_ratio=model.spec.expansion_ratio)
+    return {"network": net, "training": dict(default_training(**(training_conf or {})))}
+
+
+def checkpoint_payload(trainer: "HipTrainer", pl_module=None, training_conf: Optional[dict] = None) -> dict:
+    """what ``checkpoint_writer``'s file holds, as a dict: ``state_dict`` (smp names, ``model.`` prefix) and
+    ``hyper_parameters_json`` — the module's own when ``pl_module`` has ``save_checkpoint`` and ``hparams``"""
+    if pl_module is not None and hasattr(pl_module, "save_checkpoint") and hasattr(pl_module, "hparams"):
+        model = pl_module.model
+        hp = {"network": dict(pl_module.hparams["network"]), "training": dict(pl_module.hparams["training"])}
+    else:
+        model = trainer if isinstance(trainer, UNetHIP) else trainer.model
+        hp = _generic_hparams(trainer, training_conf)
+    sd = {f"model.{k}": v for k, v in model.smp_state_dict().items()}
+    return {"state_dict": sd, "hyper_parameters_json": json.dumps(hp)}
+
 
 def checkpoint_writer(trainer: "HipTrainer", pl_module=None, training_conf: Optional[dict] = None) -> Callable[[str], None]:
     """path -> one ``.ckpt`` in ``SemSegment.save_checkpoint``'s payload (``SemSegment.load_from_checkpoint`` and
@@ -692,15 +809,8 @@ def checkpoint_writer(trainer: "HipTrainer", pl_module=None, training_conf: Opti
     reference checkpoint) has no trainer; its file records the default loss list and the decoder's two ratios."""
     if pl_module is not None and hasattr(pl_module, "save_checkpoint"):
         return pl_module.save_checkpoint
-    from .utils.config import default_network, default_training
     model = trainer if isinstance(trainer, UNetHIP) else trainer.model
-    K = model.spec.classes
-    classes = ["background", "deadtree"] if K == 2 else ["background"] + [f"class{i}" for i in range(1, K)]
-    net = dict(default_network(architecture=model.spec.decoder_kind, in_channels=model.spec.in_channels, classes=classes,
-                               losses=list(getattr(trainer, "losses", ("GDICE", "FOCAL")))))
-    if model.spec.decoder_kind == "efficientunetplusplus":
-        net.update(squeeze_ratio=model.spec.squeeze_ratio, expansion_ratio=model.spec.expansion_ratio)
-    hp = {"network": net, "training": dict(default_training(**(training_conf or {})))}
+    hp = _generic_hparams(trainer, training_conf)
 
     def save(path):
         sd = {f"model.{k}": v for k, v in model.smp_state_dict().items()}
@@ -708,9 +818,60 @@ def checkpoint_writer(trainer: "HipTrainer", pl_module=None, training_conf: Opti
     return save
 
 
+@dataclass
+class StateConfig:
+    """``fit(state=...)``: the full training state goes to ``path`` after every ``every_n_epochs``-th epoch"""
+    path: str
+    every_n_epochs: int = 1
+
+
+def resolve_state(cfg) -> Optional[StateConfig]:
+    """``fit``'s state argument (None, a path or a StateConfig) -> a checked StateConfig (None stays None)"""
+    if cfg is None:
+        return None
+    if isinstance(cfg, (str, os.PathLike)):
+        cfg = StateConfig(os.fspath(cfg))
+    if not isinstance(cfg, StateConfig):
+        raise ValueError(f"fit(state=...): None, a path or a StateConfig, not {type(cfg).__name__}")
+    if not isinstance(cfg.path, (str, os.PathLike)) or not os.fspath(cfg.path):
+        raise ValueError(f"state: path {cfg.path!r}: a file path")
+    n = cfg.every_n_epochs
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"state: every_n_epochs {n!r}: an integer >= 1")
+    return StateConfig(os.fspath(cfg.path), n)
+
+
+def _swa_record(swa: Optional[SWAConfig]):
+    return None if swa is None else {"swa_start": swa.swa_start, "swa_lr": swa.swa_lr, "anneal_epochs": swa.anneal_epochs,
+                                     "anneal_strategy": swa.anneal_strategy}
+
+
+def _check_resume(file: dict, path, trainer, epochs: int, base_lr: float, t_max: int, swa, overrides: bool) -> dict:
+    """everything ``fit(resume=...)`` refuses, checked on the loaded file before anything is modified -> the fit state"""
+    fs = file["fit"]
+    saved = int(fs["epoch"])
+    if fs["stopped"]:
+        raise ValueError(f"resume {path}: that run had stopped after epoch {saved} (early stopping): nothing is left to "
+                         "continue")
+    if saved + 1 >= epochs:
+        raise ValueError(f"resume {path}: epoch {saved} of that run is complete and epochs is {epochs}: nothing is left "
+                         "to run; pass a larger epochs")
+    if _swa_record(swa) != fs["swa"]:
+        raise ValueError(f"resume {path}: swa differs: the state was saved under {fs['swa']!r}, this call resolves to "
+                         f"{_swa_record(swa)!r}")
+    if not overrides:
+        for name, mine in (("base_lr", float(base_lr)), ("t_max", int(t_max))):
+            if fs[name] != mine:
+                raise ValueError(f"resume {path}: {name} differs: saved {fs[name]!r}, this call {mine!r} "
+                                 "(resume_overrides=True takes this call's)")
+    trainer.check_state_dict(file["trainer"])
+    return fs
+
+
 def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: int = 10, to_device=None,
         on_epoch_end=None, callbacks=None, pl_module=None, swa=None, val_loader=None, check_val_every_n_epoch: int = 1,
-        checkpoint=None, early_stopping=None, curves: bool = False, objects=None):
+        checkpoint=None, early_stopping=None, curves: bool = False, objects=None, state=None, resume=None,
+        resume_overrides: bool = False):
     """Minimal stand-in for ``Trainer.fit`` on the hot path (reference deadtrees/train.py:113): per-batch
     ``HipTrainer.step`` and the per-epoch ``CosineAnnealingLR(T_max)`` of segmodel.py:426-428.
 
@@ -740,9 +901,29 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
     ``swa_start`` keep the cosine schedule (or whatever a callback put in its place); from ``swa_start`` the rate follows
     ``swa_lr`` (SWALR, annealing from the rate the schedule had reached) and the average is updated at the end of every
     epoch; after the last epoch the average is swapped in and the BatchNorm statistics are recomputed over ``loader``.
-    The history then carries "swa/n_averaged" per epoch and a final {"swa/bn_batches": k} record."""
+    The history then carries "swa/n_averaged" per epoch and a final {"swa/bn_batches": k} record.
+
+    state: a path or a ``StateConfig`` — after every ``every_n_epochs``-th epoch the full training state
+    (``utils.train_state.save_training_state``: the trainer's ``state_dict()``, the schedule, the SWA hand-over rate, the
+    selection state, the history, and the weights as any checkpoint holds them) replaces the file at that path, after
+    the epoch's validation and model selection and before ``on_epoch_end``; rank 0 writes.
+    resume: such a file.  ``epochs`` stays the total: the trainer is restored, the schedule, history and selection state
+    are taken from the file, ``loader.set_epoch`` is called where the loader has it, and the loop starts at the saved
+    epoch + 1.  Callbacks see ``current_epoch`` continue; stages that have passed are not run again, their effects are in
+    the restored state.  Because the training step is run-to-run bit-identical, the resumed run's parameters, optimiser
+    state and history equal the uninterrupted run's.  Refused with ValueError before anything is modified: a run that
+    had stopped, ``saved + 1 >= epochs``, another resolved ``swa``, another ``base_lr`` / ``t_max`` (unless
+    ``resume_overrides=True``: this call's values then replace the schedule's) and a trainer of another description
+    (``HipTrainer.describe``).  Without ``state`` and ``resume`` nothing differs."""
     from .network.segmodel import cosine_lr, create_combined_batch
     from .utils.config import to_attrdict
+    state = resolve_state(state)
+    if resume is not None and (not isinstance(resume, (str, os.PathLike)) or not os.fspath(resume)):
+        raise ValueError(f"fit(resume=...): None or the path of a training state file, not {resume!r}")
+    if not isinstance(resume_overrides, bool):
+        raise ValueError(f"fit(resume_overrides=...): True or False, not {resume_overrides!r}")
+    if resume_overrides and resume is None:
+        raise ValueError("fit(resume_overrides=True) without resume")
     swa = resolve_swa(swa, epochs, base_lr)
     if swa is not None and (getattr(trainer, "averager", None) is None or trainer.averager.mode != "swa"):
         raise ValueError("fit(swa=...) needs HipTrainer(average='swa')")
@@ -763,6 +944,11 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
         raise ValueError(f"check_val_every_n_epoch {check_val_every_n_epoch!r}: an integer >= 1")
     if val_loader is None and (checkpoint is not None or early_stopping is not None):
         raise ValueError("fit(checkpoint=... / early_stopping=...) monitor a validation metric: give val_loader")
+    resumed = None
+    if resume is not None:
+        from .utils.train_state import load_training_state
+        file = load_training_state(resume)
+        resumed = _check_resume(file, resume, trainer, epochs, base_lr, t_max, swa, resume_overrides)
     select = None
     if checkpoint is not None or early_stopping is not None:
         rank0 = trainer.world == 1 or trainer.reducer.dist.get_rank(trainer.reducer.group) == 0
@@ -778,7 +964,25 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
         pl_module = _ModuleView(trainer.model, getattr(trainer.model, "encoder_weights", None), hp)
     elif callbacks and not hasattr(pl_module, "model"):
         raise ValueError("fit(callbacks=...): pl_module must have .model")
-    for epoch in range(epochs):
+    first = 0
+    if resumed is not None:
+        trainer.load_state_dict(file["trainer"])
+        del file
+        first = int(resumed["epoch"]) + 1
+        history = [dict(rec) for rec in resumed["history"]]
+        swa_from = resumed["swa_from"]
+        sched.update(base_lr=float(resumed["sched"]["base_lr"]), t_max=int(resumed["sched"]["t_max"]),
+                     start=int(resumed["sched"]["start"]))
+        if resume_overrides:              # this call's values replace the schedule's where they differ from the saved call's
+            if float(base_lr) != resumed["base_lr"]:
+                sched["base_lr"] = float(base_lr)
+            if int(t_max) != resumed["t_max"]:
+                sched["t_max"] = int(t_max)
+        if select is not None and resumed["selection"] is not None:
+            select.load_state_dict(resumed["selection"])
+        if hasattr(loader, "set_epoch"):
+            loader.set_epoch(int(resumed["loader_next_epoch"]))
+    for epoch in range(first, epochs):
         tview.current_epoch = epoch
         for cb in callbacks or ():
             if hasattr(cb, "on_train_epoch_start"):
@@ -795,7 +999,10 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
             if to_device:
                 img, mask = img.to(to_device), mask.to(to_device)
                 distmap = distmap.to(to_device) if distmap is not None else None
-            losses.append(trainer.step(img, mask, distmap, alpha=alpha))
+            loss = trainer.step(img, mask, distmap, alpha=alpha)
+            # a replayed step hands back the graph's static output, the same tensor every time: the epoch mean needs a
+            # copy of each value (without it the mean of replayed steps was the last step's loss)
+            losses.append(loss.clone() if getattr(trainer, "use_graph", False) else loss)
         mean = float(torch.stack(losses).mean()) if losses else float("nan")
         history.append({"epoch": epoch, "lr": trainer.opt.lr, "train/total_loss": mean})
         if swa is not None:
@@ -817,6 +1024,14 @@ def fit(trainer: HipTrainer, loader, epochs: int, base_lr: float = 3e-4, t_max: 
                 val = {**val, **crowns}                          # what a crown-level monitor reads
             if select is not None:
                 stop = select.update(epoch, val)
+        if state is not None and (epoch + 1) % state.every_n_epochs == 0:
+            from .utils.train_state import save_training_state
+            save_training_state(state.path, trainer, {
+                "epoch": epoch, "history": history, "sched": dict(sched), "swa_from": swa_from, "swa": _swa_record(swa),
+                "base_lr": float(base_lr), "t_max": int(t_max), "stopped": bool(stop),
+                "selection": None if select is None else select.state_dict(),
+                "loader_next_epoch": int(getattr(loader, "_next_epoch", epoch + 1))},
+                pl_module=pl_module, training_conf={"learning_rate": base_lr, "cosineannealing_tmax": t_max})
         if on_epoch_end:
             on_epoch_end(history[-1])
         if stop:
