@@ -11,3 +11,5 @@ from deadtrees_amd.deployment.tiler import (PatchDistances, PatchGaps, Proximity
                                             patch_gaps, patch_proximity_host)  # (nearest-patch distances)
 from deadtrees_amd.deployment.tiler import (AttributeConfig, PatchAttributes, patch_attributes,  # noqa: F401
                                             patch_attributes_host)  # (band statistics, indices and confidence per patch)
+from deadtrees_amd.deployment.tiler import (CoverGrid, GridConfig, cover_grid, cover_grid_host,  # noqa: F401
+                                            write_cover_csv)  # (area-weighted class and zone counts per grid cell)

@@ -162,6 +162,7 @@ SIGNATURES = {
     "dt_weight_images_bf16_all": (C.c_int, [c_f, c_f, c_f, c_f, c_f, c_f, C.c_int, C.c_int, c_f]),
     "dt_ensemble_vote": (C.c_int, [c_f, C.c_int, I64, C.c_int, c_f, c_f, c_f, c_f]),
     "dt_zonal_counts_u8": (C.c_int, [c_f, c_f, I64, C.c_int, C.c_int, c_f, c_f, c_f]),
+    "dt_cover_grid_u8": (C.c_int, [c_f, c_f] + [C.c_int] * 4 + [c_f, C.c_int, c_f, C.c_int, c_f, c_f, c_f]),
     "dt_raster_cut_u8": (C.c_int, [c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, c_f, I64, c_f, c_f, c_f, c_f, c_f, c_f]),
     "dt_rasterize_polygons_u8": (C.c_int, [c_f, I64, c_f, C.c_int, C.c_int, C.c_int, C.c_int, c_f, c_f]),
     "dt_patch_tile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),

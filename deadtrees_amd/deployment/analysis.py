@@ -11,6 +11,7 @@ import numpy as np
 
 from ..data.polygons import PolygonSet, rasterize
 from .attributes import AttributeConfig, attributes_of, check_attributes, check_raster
+from .cover import MAX_SUMS, CoverGrid, GridConfig, check_grid, cover_grid_host
 from .crowns import CrownConfig, CrownSplit, check_crowns
 from .patches import PatchConfig, check_patches, labelled_patches_host
 from .proximity import ProximityConfig, check_proximity, distances_of, gaps_of
@@ -85,7 +86,8 @@ class MapAnalysis:
     patches, or None; ``attributes``: the ``AttributeConfig`` of the patches' band statistics and confidence, or None — after
     ``bind`` with the index pairs of that raster written out; ``crowns`` / ``against_crowns``: the ``CrownConfig`` under which
     the patches of the map / of ``against`` are split into crowns behind the sieve (``deployment/crowns.py``), or None — with
-    one, everything that follows the label plane is crown-level.
+    one, everything that follows the label plane is crown-level; ``grid``: the ``GridConfig`` of the map's ``CoverGrid``
+    (``deployment/cover.py``), or None — after ``bind`` ``grid_edges`` holds its edge tables for that raster's shape.
     ``rules`` checks what depends on no raster, ``bind`` the maps of one raster, ``of`` both; ``stats=False`` gives None"""
     K: Optional[int]
     zones: object = None
@@ -100,22 +102,25 @@ class MapAnalysis:
     attributes: Optional[AttributeConfig] = None
     crowns: Optional[CrownConfig] = None
     against_crowns: Optional[CrownConfig] = None
+    grid: Optional[GridConfig] = None
+    grid_edges: Optional[tuple] = None
 
     @classmethod
     def rules(cls, who: str, K, stats: bool = True, zones=None, n_zones=None, patches=None, outlines=None, against=None,
               against_patches=None, distances=None, gaps=None, attributes=None, no_probs: Optional[str] = None,
-              crowns=None, against_crowns=None) -> Optional["MapAnalysis"]:
+              crowns=None, against_crowns=None, grid=None) -> Optional["MapAnalysis"]:
         """the options as ``infer_tile`` receives them -> a request without maps yet, or None without ``stats``; ``zones`` and
         ``against`` only say whether there are any (``infer_rasters`` passes its mappings).  ``ValueError``: an option without
         ``stats``, outlines, ``against``, ``gaps`` or ``attributes`` without patches, ``against_patches`` or ``distances`` without
         ``against``, a value of a wrong type, ``attributes`` with confidence in a call without probabilities (``no_probs``: what
         the caller's path would need to have some; None: it has), ``crowns`` without patches, ``against_crowns`` without
-        ``against``"""
+        ``against``, ``grid`` without ``stats``"""
         config = check_patches(patches)
         try:
             distances, gaps = check_proximity(distances, "distances"), check_proximity(gaps, "gaps")
             attributes = check_attributes(attributes)
             crowns, against_crowns = check_crowns(crowns), check_crowns(against_crowns, "against_crowns")
+            grid = check_grid(grid)
         except ValueError as e:
             raise ValueError(f"{who}: {e}") from None
         if outlines is not None and not isinstance(outlines, bool):
@@ -135,6 +140,8 @@ class MapAnalysis:
                 raise ValueError(f"{who}: attributes need stats=True")
             if crowns is not None or against_crowns is not None:
                 raise ValueError(f"{who}: crowns / against_crowns need stats=True")
+            if grid is not None:
+                raise ValueError(f"{who}: grid needs stats=True")
             return None
         if crowns is not None and config is None:
             raise ValueError(f"{who}: crowns need patches (the crowns are cut from the PatchTable's patches)")
@@ -158,13 +165,15 @@ class MapAnalysis:
         elif not isinstance(against_patches, PatchConfig):
             raise ValueError(f"{who}: against_patches must be a PatchConfig or None, got {against_patches!r}")
         return cls(K=K, patches=config, outlines=bool(outlines), against_patches=against_patches, n_zones=n_zones,
-                   distances=distances, gaps=gaps, attributes=attributes, crowns=crowns, against_crowns=against_crowns)
+                   distances=distances, gaps=gaps, attributes=attributes, crowns=crowns, against_crowns=against_crowns,
+                   grid=grid)
 
     def bind(self, who: str, shape, zones=None, against=None, raster=None) -> "MapAnalysis":
         """the request of one raster of ``shape`` (h, w) and its maps, of the kinds ``rules`` was told of.  ``ValueError``: a map
         off the grid, not uint8 or with a value out of range; ``n_zones`` that does not fit the zones; no class count; with
         ``attributes`` a ``raster`` ([C, h, w]: only its dtype and shape are read) that is missing, not uint8, off the grid, of
-        more than 8 bands, or without a band an index names"""
+        more than 8 bands, or without a band an index names; with ``grid`` a lattice whose tables for ``shape`` the contract
+        refuses"""
         zones, Z = check_zones(zones, shape, self.n_zones)
         if self.K is None:
             raise ValueError(f"{who}: stats=True needs an inference object with a `classes` count")
@@ -177,7 +186,16 @@ class MapAnalysis:
                 attributes = AttributeConfig(attributes.pairs(check_raster(raster, shape, "attributes")), attributes.confidence)
             except ValueError as e:
                 raise ValueError(f"{who}: {e}") from None
-        return replace(self, K=int(self.K), zones=zones, Z=Z, against=against, attributes=attributes,
+        grid_edges = None
+        if self.grid is not None:
+            try:
+                grid_edges = self.grid.edges(shape)
+                if (len(grid_edges[1]) - 1) * (len(grid_edges[3]) - 1) * Z * int(self.K) > MAX_SUMS:
+                    raise ValueError(f"grid: {len(grid_edges[1]) - 1} x {len(grid_edges[3]) - 1} cells of {Z} x {int(self.K)} "
+                                     f"bins are more than {MAX_SUMS} sums")
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from None
+        return replace(self, K=int(self.K), zones=zones, Z=Z, against=against, attributes=attributes, grid_edges=grid_edges,
                        against_patches=None if against is None else self.against_patches,
                        against_crowns=None if against is None else self.against_crowns,
                        distances=None if against is None else self.distances)
@@ -220,8 +238,12 @@ def run_host(request: MapAnalysis, result: np.ndarray, raster=None, probs=None):
         if request.outlines:
             rings = outlines_from_labels(labels, result, config.connectivity)
     counts = zonal_counts_host(np.ascontiguousarray(result), zones, K, request.Z)
+    cover = None
+    if request.grid_edges is not None:
+        sums, _ = cover_grid_host(result, zones, K, request.Z, request.grid_edges[1], request.grid_edges[3])
+        cover = CoverGrid.of(sums, request.grid_edges, result.shape, table)
     return result, RasterStats(counts, patches=table, outlines=rings, overlaps=pairs, gaps=gaps, attributes=attributes,
-                               crowns=split)
+                               crowns=split, grid=cover)
 
 
 class DeviceSplit:
@@ -276,7 +298,8 @@ def run_device(request: Optional[MapAnalysis], out, probs=None, planes=(None, No
     arrays.  ``planes``: the request's ``device_planes``.  The order of the enqueued work is fixed: (1) with patches ``out``
     is labelled, measured and — if asked — sieved IN PLACE, and with ``crowns`` split behind the sieve (``ops.split_patches``
     reads its growth flags back once per group of rounds; the label plane is the crown plane from here on); (2) ONE
-    ``ops.zonal_counts`` on ``out``, no synchronisation of its own; (3) with patches the map leaves by a pinned,
+    ``ops.zonal_counts`` on ``out``, no synchronisation of its own, and with ``grid`` ONE ``ops.cover_grid`` on ``out`` and the
+    same zones plane behind it (its two edge tables are uploaded, nothing is read back); (3) with patches the map leaves by a pinned,
     non-blocking copy (without them by ``out.cpu()``); (4) the roots
     are compacted and measured behind it (``ops.patch_table`` reads the row count back), and with ``gaps`` one
     ``ops.patch_proximity`` of the label plane against itself follows (no scalar read-back, its result is downloaded), and
@@ -303,6 +326,9 @@ def run_device(request: Optional[MapAnalysis], out, probs=None, planes=(None, No
     elif config is not None:
         _, labels, area, _, split = device_labels(out, K, config, err, in_place=True, crowns=request.crowns)
     counts, _ = ops.zonal_counts(out, planes[0], K, request.Z, err=err)
+    cover = None
+    if request.grid_edges is not None:
+        cover, _ = ops.cover_grid(out, planes[0], K, request.Z, request.grid_edges[1], request.grid_edges[3], err=err)
     if config is not None:
         host = torch.empty(out.shape, dtype=out.dtype, pin_memory=True)
         host.copy_(out, non_blocking=True)                      # enqueued; the table's read-back waits for it
@@ -331,5 +357,7 @@ def run_device(request: Optional[MapAnalysis], out, probs=None, planes=(None, No
     if flag:          # cannot happen with checked zones: the map is an argmax over K classes
         raise RuntimeError(f"infer_tile: raster statistics met a value out of range (flag {flag}: 1 class >= {K}, "
                            f"2 zone >= {request.Z})")
+    if cover is not None:
+        cover = CoverGrid.of(cover.cpu().numpy(), request.grid_edges, tuple(out.shape), table)
     return result + (RasterStats(counts.cpu().numpy(), patches=table, outlines=rings, overlaps=pairs, gaps=gaps,
-                                 attributes=attributes, crowns=split),)
+                                 attributes=attributes, crowns=split, grid=cover),)

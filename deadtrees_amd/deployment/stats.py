@@ -73,10 +73,12 @@ class RasterStats:
     of rasters has none.  ``attributes``: the ``PatchAttributes`` (``deployment/attributes.py``: band statistics, indices and
     confidence per patch, aligned with ``patches``), handled like ``gaps``.  ``crowns``: the ``CrownSplit``
     (``deployment/crowns.py``) when the patches were split into crowns — ``patches`` then has one row per crown, and everything
-    aligned with it is crown-level —, handled like ``gaps``"""
+    aligned with it is crown-level —, handled like ``gaps``.  ``grid``: the ``CoverGrid`` (``deployment/cover.py``: area-weighted counts per cell of a coarser grid, with the
+    patches binned by centroid when there are any) when one was asked for, else None — then ``repr`` and ``==`` do not mention
+    it; a sum of rasters has none: ``CoverGrid.merge`` is the explicit route"""
 
     def __init__(self, counts, pixel_area_m2: float = PIXEL_AREA_M2, patches=None, outlines=None, overlaps=None, gaps=None,
-                 attributes=None, crowns=None):
+                 attributes=None, crowns=None, grid=None):
         counts = np.array(counts, dtype=np.int64)
         if counts.ndim != 2 or counts.shape[0] < 1 or counts.shape[1] < 2:
             raise ValueError(f"RasterStats: counts must be [Z >= 1, K >= 2], got shape {counts.shape}")
@@ -125,6 +127,17 @@ class RasterStats:
             if patches is None or crowns.table != patches:
                 raise ValueError("RasterStats: crowns need the PatchTable they belong to")
         self._crowns = crowns
+        if grid is not None:
+            from .cover import CoverGrid
+            if not isinstance(grid, CoverGrid):
+                raise ValueError(f"RasterStats: grid must be a CoverGrid or None, got {type(grid).__name__}")
+            if (grid.Z, grid.K) != counts.shape:
+                raise ValueError(f"RasterStats: the grid's [Z, K] = {(grid.Z, grid.K)} must be that of the counts {counts.shape}")
+        self._grid = grid
+
+    @property
+    def grid(self):
+        return self._grid
 
     @property
     def crowns(self):
@@ -199,6 +212,8 @@ class RasterStats:
             return False
         if (self._attributes is None) != (other._attributes is None) or (self._crowns is None) != (other._crowns is None):
             return False
+        if (self._grid is None) != (other._grid is None):
+            return False
         return (self._counts.shape == other._counts.shape and bool((self._counts == other._counts).all())
                 and self.pixel_area_m2 == other.pixel_area_m2
                 and (self._patches is None or self._patches == other._patches)
@@ -208,7 +223,8 @@ class RasterStats:
                 and (self._overlaps is None or self._overlaps == other._overlaps)
                 and (self._gaps is None or self._gaps == other._gaps)
                 and (self._attributes is None or self._attributes == other._attributes)
-                and (self._crowns is None or self._crowns == other._crowns))
+                and (self._crowns is None or self._crowns == other._crowns)
+                and (self._grid is None or self._grid == other._grid))
 
     __hash__ = None
 
@@ -224,6 +240,8 @@ class RasterStats:
             tail += f", attributes={self._attributes!r}"
         if self._crowns is not None:
             tail += f", crowns={self._crowns!r}"
+        if self._grid is not None:
+            tail += f", grid={self._grid!r}"
         return f"RasterStats(counts={self._counts.tolist()}, pixel_area_m2={self.pixel_area_m2!r}{tail})"
 
 

@@ -19,15 +19,17 @@ this image, so ``load_file`` / ``write_file`` raise an ``ImportError`` that says
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from pathlib import Path
-from typing import List, Optional, Tuple, Union
+from typing import List, Mapping, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
 from .analysis import MapAnalysis, run_device, run_host
 from .attributes import AttributeConfig, PatchAttributes, patch_attributes, patch_attributes_host  # noqa: F401
+from .cover import (CoverGrid, GridConfig, check_grid, cover_grid, cover_grid_host,  # noqa: F401
+                    write_cover_csv)  # (the ``grid`` argument of infer_tile)
 from .crowns import CrownConfig, CrownSplit, split_patches, split_patches_host  # noqa: F401
 from .outlines import outlines_geojson, polygonize, polygonize_host, write_outlines_geojson  # noqa: F401
 from .overlaps import (PatchMatch, PatchOverlaps, PatchTracks, overlap_pairs_host, patch_overlaps)  # noqa: F401
@@ -247,11 +249,11 @@ class Tiler:
 
     def stats(self, zones=None, classes: int = 3, n_zones: Optional[int] = None, patches=None, outlines=None,
               against=None, against_patches=None, distances=None, gaps=None, attributes=None, crowns=None,
-              against_crowns=None):
+              against_crowns=None, grid=None):
         """``RasterStats`` of ``result``: what ``infer_tile(..., stats=True)`` returns, for a caller of the reference's own
         ``get_batches`` / ``put_batches`` loop, computed on the host (``analysis.run_host``).  ``classes``: the model's class
         count; ``zones`` / ``n_zones`` / ``patches`` / ``outlines`` / ``against`` / ``against_patches`` / ``distances`` /
-        ``gaps`` / ``attributes`` / ``crowns`` / ``against_crowns``: as in ``infer_tile``, with the same rules
+        ``gaps`` / ``attributes`` / ``crowns`` / ``against_crowns`` / ``grid``: as in ``infer_tile``, with the same rules
         (``MapAnalysis``); the attributes are read from the
         loaded raster, and the host path has no probabilities, so ``confidence=True`` is refused.  Polygons are burnt by
         ``rasterize_host``; a ``patches`` configuration that sieves changes ``result`` itself, and the counts are those of the
@@ -262,7 +264,7 @@ class Tiler:
                                             n_zones=n_zones, patches=patches, outlines=outlines,
                                             against_patches=against_patches, distances=distances, gaps=gaps,
                                             attributes=attributes, no_probs="Tiler.stats runs on the host, which has none",
-                                            crowns=crowns, against_crowns=against_crowns))
+                                            crowns=crowns, against_crowns=against_crowns, grid=grid))
 
     def _raster(self) -> np.ndarray:
         """the loaded raster cropped to its own size: a view of the padded input"""
@@ -289,7 +291,7 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
                   overlap: int = 0, blend: str = "crop", return_probs: bool = False, tta=None, stats: bool = False,
                   zones=None, n_zones: Optional[int] = None, patches=None, outlines=None, against=None,
                   against_patches=None, distances=None, gaps=None, attributes=None, decision=None, crowns=None,
-                  against_crowns=None):
+                  against_crowns=None, grid=None):
     """the directory loop of scripts/inference.py:71-115 over in-memory rasters (GeoTIFF I/O needs rioxarray, absent
     here): ``rasters`` yields ``array`` or ``(key, array)``; rank r of ``world`` takes rasters r, r + world, ... (tiles are
     independent: no collective).  Yields ``(key, class_map)`` in input order of the rank's share; rasters whose band 1
@@ -300,12 +302,18 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
     checked before the first raster is read (every raster
     stays on its rank, so overlap needs no exchange); ``zones``: a callable ``key -> uint8 [h, w] array, PolygonSet or None``,
     or a mapping (a missing key is None); ``against``: the same for the map every raster is compared with (a uint8 array, a ``PolygonSet``
-    or None: that raster's statistics carry no overlaps).
+    or None: that raster's statistics carry no overlaps); ``grid``: one ``GridConfig`` for every raster, or a callable ``key ->
+    GridConfig or None`` or a mapping (a missing key is None) — every raster has its own pixel frame, so a regional lattice is
+    one ``GridConfig.from_world`` per geotransform, and ``CoverGrid.merge`` of the rasters' ``.grid`` is the regional grid.
     The second item of every pair is whatever ``infer_tile`` returned: with ``stats=True`` ``(map, RasterStats)`` — the
     ``RasterStats`` of a rank's share add up (``+``) to that rank's part of the regional totals."""
+    per_raster = grid is not None and not isinstance(grid, GridConfig) and (callable(grid) or isinstance(grid, Mapping))
+    if per_raster and not stats:
+        raise ValueError("infer_rasters: grid needs stats=True")
     rules = MapAnalysis.rules("infer_rasters", getattr(inference, "classes", None) if stats else None, stats, zones, n_zones,
                               patches, outlines, against, against_patches, distances, gaps, attributes,
-                              _no_probs(inference, overlap, blend, tta), crowns=crowns, against_crowns=against_crowns)
+                              _no_probs(inference, overlap, blend, tta), crowns=crowns, against_crowns=against_crowns,
+                              grid=None if per_raster else grid)
     decision = _check_decision("infer_rasters", inference, decision, overlap, blend, tta)
     for i, item in enumerate(rasters):
         if i % world != rank:
@@ -313,6 +321,11 @@ def infer_rasters(inference, rasters, subtile: int = 256, batch_size: int = 64, 
         key, arr = item if isinstance(item, tuple) else (i, item)
         z = None if zones is None else zones(key) if callable(zones) else zones.get(key)
         other = None if against is None else against(key) if callable(against) else against.get(key)
+        if per_raster:
+            try:
+                rules = replace(rules, grid=check_grid(grid(key) if callable(grid) else grid.get(key)))
+            except ValueError as e:
+                raise ValueError(f"infer_rasters: {e}") from None
         request = None if rules is None else rules.bind("infer_tile", np.shape(arr)[1:], z, other, arr)
         yield key, _infer_tile(inference, arr, request, subtile, batch_size, 0, 1, device, None, tile_shape, None, skip_blank,
                                overlap, blend, return_probs, tta, decision)
@@ -323,7 +336,7 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
                on_device: Optional[bool] = None, skip_blank: bool = False, overlap: int = 0, blend: str = "crop",
                return_probs: bool = False, tta=None, stats: bool = False, zones=None, n_zones: Optional[int] = None,
                patches=None, outlines=None, against=None, against_patches=None, distances=None, gaps=None,
-               attributes=None, decision=None, crowns=None, against_crowns=None):
+               attributes=None, decision=None, crowns=None, against_crowns=None, grid=None):
     """whole-tile inference of scripts/inference.py:80-115 on the MI355X path: split -> (uint8 H2D, normalise on the
     device) -> forward + fused argmax -> uint8 D2H -> merge.  With world > 1 the sub-tile batches j = rank (mod world)
     are processed locally and the uint8 class maps are all-gathered (no other collective: tiles are independent).
@@ -410,12 +423,21 @@ def infer_tile(inference, arr_chw_u8: np.ndarray, subtile: int = 256, batch_size
     patch).  The label plane IS the crown plane from there on: ``.patches`` has one row per crown, and outlines, overlaps,
     distances, gaps and attributes align with it as they do with patches; ``.crowns`` is the ``CrownSplit`` (per crown the
     patch it was cut from and its inscribed depth; ``converged``).  ``against_crowns`` (needs ``against``) splits the patches of
-    ``against`` the same way.  The returned map and the counts do not change: splitting moves no pixel between classes."""
+    ``against`` the same way.  The returned map and the counts do not change: splitting moves no pixel between classes.
+
+    ``grid``: a ``GridConfig`` (``deployment/cover.py``: cell size and origin in this raster's pixels, or
+    ``GridConfig.from_world`` of its geotransform): ``.grid`` is the ``CoverGrid`` of the final map — the map the counts are
+    taken from, after sieve, decision and crowns —, area-weighted sums per cell, zone and class in exact integers (ONE
+    ``ops.cover_grid`` behind the counts on the device paths, ``cover_grid_host`` on the host path: identical), with
+    ``zones`` — array or ``PolygonSet`` — splitting them as it splits the counts (a previous year's map gives per-cell
+    transition matrices), and with ``patches`` the patch (or crown) count and area per cell and class, binned by centroid.
+    Everything else is that of the call without the option."""
     decision = _check_decision("infer_tile", inference, decision, overlap, blend, tta)
     request = MapAnalysis.of("infer_tile", np.shape(arr_chw_u8)[1:], getattr(inference, "classes", None) if stats else None,
                              zones, against, arr_chw_u8, stats=stats, n_zones=n_zones, patches=patches, outlines=outlines,
                              against_patches=against_patches, distances=distances, gaps=gaps, attributes=attributes,
-                             no_probs=_no_probs(inference, overlap, blend, tta), crowns=crowns, against_crowns=against_crowns)
+                             no_probs=_no_probs(inference, overlap, blend, tta), crowns=crowns, against_crowns=against_crowns,
+                             grid=grid)
     return _infer_tile(inference, arr_chw_u8, request, subtile, batch_size, rank, world, device, group, tile_shape, on_device,
                        skip_blank, overlap, blend, return_probs, tta, decision)
 

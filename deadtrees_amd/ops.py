@@ -1228,6 +1228,39 @@ def zonal_counts(classes_u8: torch.Tensor, zones_u8: torch.Tensor = None, K: int
     return counts, err
 
 
+def cover_grid(classes_u8: torch.Tensor, zones_u8: torch.Tensor = None, K: int = 3, Z: int = 1, yq=None, xq=None, sums=None,
+               err=None):
+    """area-weighted class counts per zone and per cell of a coarser grid, of a uint8 [h, w] class map on the device
+    (``dt_cover_grid_u8``; the contract is ``deployment/cover.py``): sums int64 [gy, gx, Z, K] (+=) in 1/65536 pixel.  ``yq`` /
+    ``xq``: the edge tables in 1/256 pixel as HOST integer arrays (checked here — ``ValueError`` before any launch — and
+    uploaded as int32).  ``zones_u8`` None: every pixel is zone 0 and Z must be 1.  A non-contiguous view is made
+    contiguous, a contiguous one (a crop of full rows, a member of a stacked tensor) is read where it lies.  ``sums`` /
+    ``err`` (int32 [1]) are allocated zeroed when not given and accumulated into otherwise.  No host synchronisation: a
+    class >= K ORs 1 into ``err``, a zone >= Z ORs 2, and such a pixel enters no sum.  Returns (sums, err)."""
+    from .deployment.cover import check_cover
+    _gpu(classes_u8, zones_u8, sums, err)
+    yq, xq = (q.numpy() if isinstance(q, torch.Tensor) and not q.is_cuda else q for q in (yq, xq))
+    if isinstance(yq, torch.Tensor) or isinstance(xq, torch.Tensor):
+        raise ValueError("cover_grid: the edge tables are host arrays (they are checked before the launch)")
+    K, Z, yq, xq = check_cover(classes_u8, zones_u8, K, Z, yq, xq)
+    dev = classes_u8.device
+    if zones_u8 is not None and zones_u8.device != dev:
+        raise ValueError("cover_grid: the map and zones must be on the same device")
+    gy, gx = len(yq) - 1, len(xq) - 1
+    if sums is None:
+        sums = torch.zeros((gy, gx, Z, K), dtype=torch.int64, device=dev)
+    elif sums.dtype != torch.int64 or tuple(sums.shape) != (gy, gx, Z, K) or sums.device != dev or not sums.is_contiguous():
+        raise ValueError(f"cover_grid: sums must be contiguous int64 [{gy},{gx},{Z},{K}] on {dev}")
+    err = _err_flag("cover_grid", err, dev)
+    tables = torch.cat([torch.from_numpy(yq), torch.from_numpy(xq)]).to(torch.int32).to(dev, non_blocking=True)
+    classes_u8 = classes_u8.contiguous()
+    zones_u8 = None if zones_u8 is None else zones_u8.contiguous()
+    h, w = classes_u8.shape
+    _lib.check(_lib.load().dt_cover_grid_u8(_p(classes_u8), _p(zones_u8), h, w, K, Z, _p(tables), gy, _p(tables[gy + 1:]), gx,
+                                            _p(sums), _p(err), _st()), "dt_cover_grid_u8")
+    return sums, err
+
+
 def raster_cut(rgbn: torch.Tensor, mask: Optional[torch.Tensor] = None, lu: Optional[torch.Tensor] = None,
                source_dim: int = 2048, tile_size: int = 256, slot: Optional[torch.Tensor] = None, out=None, census=True):
     """Sub-tile cut and census of one raster on the device (``dt_raster_cut_u8``, csrc/raster_cut.hip; the contract is

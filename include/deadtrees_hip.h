@@ -452,6 +452,18 @@ int dt_ensemble_vote(const uint8_t* maps, int M, int64_t n, int K, uint8_t* out_
 int dt_zonal_counts_u8(const uint8_t* classes, const uint8_t* zones, int64_t n, int K, int Z, int64_t* counts,
                        int32_t* err_flag, void* stream);
 
+/* Cover grids (deployment/cover.py states the contract): area-weighted class counts per zone and per cell of a coarser
+ * grid, from a uint8 class map [h][w] in device memory, 1 <= h, w <= 16384.  The grid is two edge tables in device memory,
+ * int32 in units of 1/256 pixel: yq[gy + 1] and xq[gx + 1], strictly increasing, every cell at least 256 wide, |q| <= 2^23
+ * (the CALLER checks the tables; whatever they hold, nothing outside `sums` is written).  Pixel (i, j) is the square
+ * (j, j + 1) x (i, i + 1); wy(g, i) = max(0, min(yq[g + 1], 256 (i + 1)) - max(yq[g], 256 i)), wx likewise.  sums int64
+ * [gy][gx][Z][K] (+=): sums[g][x][z][c] += the sum of wy(g, i) * wx(x, j) over the pixels with zones == z and classes == c,
+ * in units of 1/65536 pixel.  zones may be NULL: Z must then be 1.  2 <= K <= 8, 1 <= Z <= 8, gy * gx * Z * K <= 2^26; any
+ * byte alignment of either map.  A class >= K ORs 1 into err_flag[0], a zone >= Z ORs 2; such a pixel enters no sum.
+ * One launch over the dt_patch_tile tiles of the map, no synchronisation.  Integers only: exact, order independent. */
+int dt_cover_grid_u8(const uint8_t* classes, const uint8_t* zones, int h, int w, int K, int Z, const int32_t* yq, int gy,
+                     const int32_t* xq, int gx, int64_t* sums, int32_t* err_flag, void* stream);
+
 /* Dead-tree patches (deployment/patches.py states the contract): connected components of a uint8 class map [h][w] in
  * device memory, h * w <= 2^31 - 2.  A patch is a maximal set of pixels of one class c, 1 <= c < K, connected through
  * 4- or 8-neighbourhoods; class 0 is background.  No entry point synchronises; all integers: exact, order independent.
